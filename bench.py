@@ -426,6 +426,41 @@ def csrc_fingerprint():
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES = 60_000_000       # (under 64 MB, npy headers included)
+
+
+def dump_outputs(d, outputs, seed):
+    """--dump-outputs: per distinct read set i of the last timed step, what its last sample returned — set{i}_contain_count,
+    set{i}_cov_off and set{i}_covs (the sorted coverage values of every genome, concatenated) — and table_stats (per set: read set index,
+    sample table entries, duplicates removed).  Counts below 2^24 go out as float32, larger ones as float64.  Beyond DUMP_BYTES in all,
+    each set keeps a sample of its coverage values at positions drawn from a generator seeded with --seed (the same for the same lengths)."""
+    os.makedirs(d, exist_ok=True)
+
+    def flt(a):
+        a = np.asarray(a)
+        return a.astype(np.float32 if (a.size == 0 or int(a.max()) < (1 << 24)) else np.float64)
+    arrays = {}
+    for i in sorted(outputs):
+        o = outputs[i]
+        arrays[f"set{i}_contain_count"] = flt(o["contain_count"])
+        arrays[f"set{i}_cov_off"] = flt(o["cov_off"])
+        arrays[f"set{i}_covs"] = flt(o["covs"])
+    fixed = sum(a.nbytes for n, a in arrays.items() if not n.endswith("_covs"))
+    covs = sum(a.nbytes for n, a in arrays.items() if n.endswith("_covs"))
+    if fixed + covs > DUMP_BYTES:
+        keep_frac = max(0.0, (DUMP_BYTES - fixed - 4096) / covs)
+        rng = np.random.default_rng(seed)
+        for n in sorted(arrays):
+            if n.endswith("_covs"):
+                a = arrays[n]
+                pick = np.sort(rng.choice(a.size, size=int(a.size * keep_frac), replace=False))
+                arrays[n] = a[pick]
+    arrays["table_stats"] = np.array([[i, *outputs[i]["table"]] for i in sorted(outputs)], dtype=np.float64).reshape(-1, 3)
+    for n, a in arrays.items():
+        np.save(os.path.join(d, n + ".npy"), a)
+    log(f"[bench] outputs of the last step ({len(outputs)} read set(s), {sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) -> {d}")
+
+
 def pct(xs, q):
     xs = sorted(xs)
     return xs[min(len(xs) - 1, int(q * len(xs)))] if xs else None
@@ -466,7 +501,18 @@ def main():
     ap.add_argument("--sweep", default="", help="tuning runs only: JSON list of pipeline configurations ({name, workers, depth, max_batch, options{}, "
                                                 "pipe_options{}}) measured one after the other on the workload of this run, after the timed region; "
                                                 "results go into the line's `sweep` object (never into `value`)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure too: the other mode's leg, the kernel timers and roofline objects, the packed-input and "
+                         "default-dedup legs, verify against the oracle, the host-fed leg, the CPU baseline and the files leg.  Without it a run sets up, "
+                         "calibrates, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step returned for each distinct read set it ran (rank 0) as DIR/<name>.npy: "
+                         "contain_count, cov_off (relative to the sample's first value) and covs per genome, float32 where exact, else float64; "
+                         "at most 64 MB in all (a fixed, seeded sample of the coverage values beyond that)")
     args = ap.parse_args()
+    if not args.full:         # a plain run: only what `value` and `ms_per_step` need
+        args.no_kernel_timers = args.no_second_leg = args.no_packed_leg = args.no_filter_leg = True
+        args.no_verify = args.no_h2d = args.no_cpu_baseline = args.no_files_leg = True
     if args.main_dedup_fpr:
         args.no_verify = args.no_filter_leg = True
 
@@ -610,20 +656,31 @@ def main():
 
     pipe_box = [None]
 
-    def run_pipelined(n, stamps=None, rows=None):
-        """n samples through sylph_pipeline_*; stamps: completion time of every sample (perf_counter)"""
+    def sample_outputs(cc, off, covs, n_table, dup):
+        """a copy of what the caller of the timed path receives for one sample: its rows of a probe batch's results"""
+        off = np.asarray(off, dtype=np.int64)
+        return {"contain_count": np.array(cc), "cov_off": off - off[0], "covs": np.array(covs[off[0]:off[-1]]), "table": (n_table, dup)}
+
+    def run_pipelined(n, stamps=None, rows=None, keep=None):
+        """n samples through sylph_pipeline_*; stamps: completion time of every sample (perf_counter); keep: read set -> its last outputs"""
         p = pipe_box[0]
         sub = done = 0
+        set_of = {}
         while done < n:
             while sub < n and p.outstanding < depth:
+                if keep is not None:
+                    set_of[sub] = sample_no[0] % n_sets
                 rs = next_read_set()
                 if not p.submit_device(rs["batches"], tag=sub, enc=rs.get("enc", _ENC_ASCII)):
                     raise RuntimeError("pipeline refused a sample below its depth")
                 sub += 1
                 if sub == n and comm is not None:
                     p.flush()                # the last probe batch of this call may be a partial one (the same on every rank)
-            r = p.next(views=False)
+            last_of_set = keep is not None and done >= n - n_sets      # (results come back in submission order)
+            r = p.next(views=last_of_set)
             done += 1
+            if last_of_set:
+                keep[set_of[r["tag"]]] = sample_outputs(r["contain_count"], r["cov_off"], r["covs"], r["n_table"], r["dup_removed"])
             if stamps is not None:
                 stamps.append(time.perf_counter())
             if rows is not None:
@@ -643,11 +700,12 @@ def main():
                 sk.push_enc(bptr, optr, nb, _MEM_DEVICE, rs["enc"], n_records=nrec)
         return sk, sk.finish_device()
 
-    def run_sequential(n, stamps=None, rows=None, keep_last=None):
+    def run_sequential(n, stamps=None, rows=None, keep_last=None, keep=None):
         """n samples one at a time on the main context (probe batches of spb: their sketches run one after the other first)"""
         done = 0
         while done < n:
             m = min(spb, n - done)
+            sets = [(sample_no[0] + j) % n_sets for j in range(m)]
             t_a = time.perf_counter()
             sess = [sketch_inline(next_read_set()) for _ in range(m)]
             t_b = time.perf_counter()
@@ -659,6 +717,11 @@ def main():
             else:
                 res = db.contain_batch(refs, device_ptrs=True)      # borrowed pinned views
             t_c = time.perf_counter()
+            if keep is not None:
+                G_ = len(res[0]) // m
+                for j, (_, (dk, dc, nt, dup)) in enumerate(sess):
+                    if done + j >= n - n_sets:
+                        keep[sets[j]] = sample_outputs(res[0][j * G_:(j + 1) * G_], res[1][j * G_:(j + 1) * G_ + 1], res[2], nt, dup)
             if keep_last is not None:
                 keep_last["res"] = tuple(np.array(x) for x in res)
                 keep_last["table"] = sess[0][1][:3]
@@ -737,8 +800,9 @@ def main():
         sps = int(agree(max(1, int(np.ceil(args.min_seconds * 1.1 / max(1, args.steps) / est / spb))) * spb))
     log(f"[bench] calibration {cal}: value from the {mode} mode, {sps} sample(s) per step")
 
-    def timed(mode, n_steps, per_step, only=None):
+    def timed(mode, n_steps, per_step, only=None, keep=None):
         """-> elapsed seconds (max over ranks), per-step seconds, per-sample completion stamps, rows, kernel families.
+        `keep`: filled with the outputs of the last step (read set -> what its last sample returned).
         `only`: the kernel families the library times with HIP events in this region (None: all of them).  Every timed family costs two
         event records per launch group on its stream — all of them together 1 % of a pipelined sample and 4 % of a sample run alone
         (profiles/r05_ab_timers.txt) — so the regions a rate is quoted on time the dominant kernel only; the other families' durations come
@@ -754,10 +818,10 @@ def main():
         torch.cuda.synchronize()
         t_start = time.perf_counter()
         stamps, rows, bounds = [], [], [t_start]
-        for _ in range(n_steps):
+        for i in range(n_steps):
             # (pipelined: the pipeline drains at the end of every step — its last samples have nothing to overlap with; with
             #  hundreds of samples per step that tail is below one per cent, and a step stays a closed unit of work)
-            runners[mode](per_step, stamps, rows)
+            runners[mode](per_step, stamps, rows, keep=keep if i == n_steps - 1 else None)
             bounds.append(time.perf_counter())
         if dist is not None:
             dist.barrier()
@@ -775,7 +839,10 @@ def main():
 
     for _ in range(args.warmup):
         runners[mode](sps)
-    elapsed, step_s, gaps, rows, fam = timed(mode, args.steps, sps, only="seeds,exchange" if comm is not None else "seeds")
+    outputs = {} if args.dump_outputs else None
+    elapsed, step_s, gaps, rows, fam = timed(mode, args.steps, sps, only="seeds,exchange" if comm is not None else "seeds", keep=outputs)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, args.seed)
     # the other kernel families in the same mix: a shorter pass of the same mode with every family timed (never the quoted rate)
     fam_pass = None
     if not args.no_kernel_timers and not args.all_kernel_timers and not args.no_second_leg:
@@ -791,7 +858,8 @@ def main():
         second = (other, per2) + timed(other, steps2, per2, only="seeds,probe")
 
     last = {}
-    run_sequential(spb, keep_last=last)      # untimed: seed occurrences for the roofline's algorithmic bytes, results for --verify
+    if args.full:
+        run_sequential(spb, keep_last=last)  # untimed: seed occurrences for the roofline's algorithmic bytes, results for --verify
 
     def leg_summary(mode_name, per_step, n_steps, elapsed_s, step_list, gap_list, rws, fm):
         n_samples = per_step * n_steps
@@ -1230,7 +1298,7 @@ def main():
             out["end_to_end_from_files"] = end_to_end_from_files(read_sets[0]["bases"], n_pairs, read_len, args.files_leg_pairs)
         except Exception as e:
             out["end_to_end_from_files"] = {"error": str(e)[:400]}
-    if rank == 0:
+    if rank == 0 and args.full:
         # every rate a reader needs to compare, side by side at the top level: GPU with the inputs resident (= `value`, and
         # with the reference's default flags), fed over PCIe, from files through the product's own command; the CPU path on the same inputs
         e2e = out.get("end_to_end_from_files", {}) if isinstance(out.get("end_to_end_from_files"), dict) else {}

@@ -1,4 +1,24 @@
+import os
+
 import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def golden_bytes(rel):
+    """The bytes of the fixture tests/golden/<rel>.  A fixture above the repository's 1 MiB limit per committed file is kept as
+    <rel>.part0, <rel>.part1, ... (pieces of at most 1,000 KiB, in order) and joined here."""
+    path = os.path.join(GOLDEN, rel)
+    if os.path.exists(path):
+        with open(path, "rb") as f:
+            return f.read()
+    parts = []
+    while os.path.exists(f"{path}.part{len(parts)}"):
+        with open(f"{path}.part{len(parts)}", "rb") as f:
+            parts.append(f.read())
+    if not parts:
+        raise FileNotFoundError(path)
+    return b"".join(parts)
 
 
 def xor_sum(a):

@@ -6,6 +6,7 @@ the GPU with the oracle twice.  The derived floats (naive ANI, lambda, adjusted 
 statistics (libsylph_host.so) on the GPU's integers and are held to the north_star's 1e-6."""
 import ctypes as C
 import hashlib
+import io
 import json
 import os
 
@@ -14,7 +15,7 @@ import pytest
 
 import sylph_amd as S
 
-from .helpers import concat, hist, xor_sum
+from .helpers import concat, golden_bytes, hist, xor_sum
 from .test_host import HostStats
 
 pytestmark = pytest.mark.gpu
@@ -29,8 +30,8 @@ def kat(golden_dir):
 
 
 @pytest.fixture(scope="module")
-def genomes(golden_dir):
-    z = np.load(os.path.join(golden_dir, "ecoli_full_bases.npz"))
+def genomes():
+    z = np.load(io.BytesIO(golden_bytes("ecoli_full_bases.npz")))
     out = []
     for g in range(3):
         n = int(z[f"g{g}_n"][0])

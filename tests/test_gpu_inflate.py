@@ -15,11 +15,9 @@ import pytest
 import sylph_amd as S
 from sylph_amd.binding import ERR_FORMAT, MEM_DEVICE, SylphHipError
 
-from .helpers import bgzf_compress
+from .helpers import bgzf_compress, golden_bytes
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-REF_FILES = os.path.join(HERE, "golden", "ref_test_files")
 
 
 def fastq_text(rng, n_records, read_len=150, quals="binned"):
@@ -57,7 +55,7 @@ def check(ctx, gz, expect):
 
 @pytest.mark.parametrize("name", ["e.coli-EC590.fasta.gz", "e.coli-K12.fasta.gz", "e.coli-o157.fasta.gz"])
 def test_reference_fasta_gz(ctx, name):
-    gz = open(os.path.join(REF_FILES, name), "rb").read()
+    gz = golden_bytes(os.path.join("ref_test_files", name))
     info = check(ctx, gz, gzip.decompress(gz))
     assert info["members"] == 1 and info["blocks"] >= 10 and info["host_members"] == 0
     assert info["candidates"] <= info["blocks"] + 2          # a false block start is a rare thing (one in ~4,000 blocks of a FASTQ file)

@@ -244,7 +244,7 @@ def test_bench_two_ranks_on_one_gpu_small_workload(db_mode):
     env = dict(os.environ, MASTER_PORT={"default": "29577", "shard": "29578", "genome": "29579"}[db_mode])
     extra = [] if db_mode == "default" else ["--db-mode", db_mode]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "small", "--steps", "3", "--warmup", "1",
-                        "--min-seconds", "0.3", "--no-cpu-baseline", "--no-h2d"] + extra, capture_output=True, text=True, timeout=900, env=env)
+                        "--min-seconds", "0.3", "--full", "--no-cpu-baseline", "--no-h2d"] + extra, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -271,7 +271,7 @@ def test_bench_line_contract_one_gpu_small_workload():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "small", "--steps", "3", "--warmup", "1", "--min-seconds", "0.3",
-                        "--cpu-baseline-bounded", "--no-files-leg", "--no-packed-leg"], capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-baseline-bounded", "--no-files-leg", "--no-packed-leg"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -294,6 +294,44 @@ def test_bench_line_contract_one_gpu_small_workload():
         assert d["value_default_flags"] > 0 and d["default_pair_dedup"]["verify"]["table_equal"] is True
 
 
+def test_bench_plain_line_and_dumped_outputs_one_gpu_small_workload(tmp_path):
+    """A plain `python bench.py` (no --full) times the steps and prints the headline line without the legs behind --full; with
+    --dump-outputs it writes what the last timed step returned per read set as float .npy files, the same from run to run, and every
+    sample's containment counts agree with its coverage offsets."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "small", "--steps", "3", "--warmup", "1", "--min-seconds", "0.3",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["ms_per_step"] * 3 - d["timed_region_s"] * 1e3) < 0.01 * d["timed_region_s"] * 1e3 + 0.01
+        for key in ("roofline", "cpu_baseline", "verify", "rates_gbp_per_s", "value_h2d_inclusive", "end_to_end_from_files", "default_pair_dedup", "resident_2bit"):
+            assert key not in d, key
+        files = sorted(os.listdir(out))
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(f.endswith(".npy") for f in files) and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+        stats = arrays["table_stats"]
+        assert len(stats) >= 1 and (stats[:, 1] > 0).all()
+        for i_set in stats[:, 0].astype(int):
+            cc, off, covs = (arrays[f"set{i_set}_{n}"] for n in ("contain_count", "cov_off", "covs"))
+            assert len(off) == len(cc) + 1 and off[0] == 0 and off[-1] == len(covs) > 0
+            assert np.array_equal(np.diff(off.astype(np.int64)), cc.astype(np.int64))
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][n], runs[1][n]) for n in runs[0])
+
+
 def test_bench_two_ranks_genome_sharded_arm_composed_outside_the_library():
     """`bench.py --gpus 2 --db-mode genome-py`: round 4's composition of the cut by genome (sylph_amd/shard.py: unsharded index per rank,
     torch.distributed all-gathers of tables, counts and coverage values) — kept beside the library mode for the A/B."""
@@ -304,7 +342,7 @@ def test_bench_two_ranks_genome_sharded_arm_composed_outside_the_library():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT="29580")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "small", "--db-mode", "genome-py", "--steps", "2",
-                        "--warmup", "1", "--min-seconds", "0.2", "--no-cpu-baseline", "--no-h2d"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--min-seconds", "0.2", "--full", "--no-cpu-baseline", "--no-h2d"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -12,7 +12,7 @@ import zlib
 import numpy as np
 import pytest
 
-from .helpers import bgzf_compress
+from .helpers import bgzf_compress, golden_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -151,8 +151,8 @@ def test_model_road_declines_damage(L):
     assert got == text and info["redone"] == 0
 
 
-def test_reference_fasta_gz_through_the_model(L, golden_dir):
-    gz = open(os.path.join(golden_dir, "ref_test_files", "e.coli-K12.fasta.gz"), "rb").read()
+def test_reference_fasta_gz_through_the_model(L):
+    gz = golden_bytes(os.path.join("ref_test_files", "e.coli-K12.fasta.gz"))
     want = gzip.decompress(gz)
     # the model tests every bit position one bit at a time: cut the file's text to 600 kB and re-deflate it the way the file was (zlib level 6)
     cut = want[:600000]

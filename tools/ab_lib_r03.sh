@@ -5,7 +5,7 @@ out=gpurun_out/ab; mkdir -p $out
 for i in $(seq ${AB_ROUNDS:-3}); do
   for v in base new; do
     cp sylph_amd/libsylph_hip.so.$v sylph_amd/libsylph_hip.so
-    python bench.py --steps 6 --warmup 2 --min-seconds ${AB_SECONDS:-1.0} --no-cpu-baseline --no-h2d --no-verify ${AB_FLAGS} 2>/dev/null | python -c "
+    python bench.py --full --steps 6 --warmup 2 --min-seconds ${AB_SECONDS:-1.0} --no-cpu-baseline --no-h2d --no-verify ${AB_FLAGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=d.get('pipelined',{}); s=d.get('one_step_at_a_time',{})

@@ -6,7 +6,7 @@
 #   inflate                    tests/test_gpu_inflate.py with both LDS ring sizes + tools/inflate_bench.py on bench.py's file shape and an
 #                              Illumina-like one (gzip -1 / -6, BGZF), per-wave statistics on
 #   gz-trace [Gbp]             tools/gz_e2e_trace.py: `sylph-hip sketch` on a plain / gzip pair with the feed's and the library's phase traces
-#   bench [bench.py args]      the default bench line -> gpurun_out/bench/bench.json (+ the rates summary on stdout)
+#   bench [bench.py args]      the bench line with every leg (bench.py --full) into bench/bench.json under the output folder (+ the rates summary on stdout)
 #   a10                        filter-dedup tests + the default-flag bench leg with one and with two partition levels
 #   a10-profile [--no-pmc]     rocprofv3 kernel trace (+ FETCH_SIZE / WRITE_SIZE) of the filter pass's kernels, one sample at a time
 #   ab-env cfg...              alternate environment configurations on the pipelined default-flag rate (AB_ROUNDS, AB_SECONDS, AB_FPR)
@@ -30,7 +30,7 @@ case "$what" in
   gz-trace)
     SYLPH_HIP_INFLATE_STATS=1 timeout 900 python tools/gz_e2e_trace.py "$@" 2>&1 | grep -v 'pool miss' | tee "$out/gz_trace.txt" | grep -v 'engine:' | cut -c1-200 ;;
   bench)
-    timeout 1500 python bench.py "$@" > "$out/bench.json" 2> "$out/bench.err"; tail -c 400 "$out/bench.err"
+    timeout 1500 python bench.py --full "$@" > "$out/bench.json" 2> "$out/bench.err"; tail -c 400 "$out/bench.err"
     python -c "import json; o = json.load(open('$out/bench.json')); print(json.dumps({k: o.get(k) for k in ('value', 'value_default_flags', 'ms_per_step', 'rates_gbp_per_s')}, indent=1))" ;;
   a10)
     # the filter dedup's pass with one partition level (default) and with round 5's two (SYLPH_HIP_A10_LEVELS=2): tests, then the default-flag leg
@@ -40,7 +40,7 @@ case "$what" in
     # configurations levels:split:pad — partition levels (1 | 2), workgroups per range of the one-level pass, extra LDS bytes per workgroup (footprint A/B)
     for cfg in ${A10_CONFIGS:-1:2:0 2:2:0 1:1:0 1:4:0 1:2:24576 1:2:0 2:2:0}; do
       lv=${cfg%%:*}; rest=${cfg#*:}; split=${rest%%:*}; pad=${rest##*:}; tpb=${split}_$pad
-      SYLPH_HIP_A10_LEVELS=$lv SYLPH_HIP_A10_RANGE_SPLIT=$split SYLPH_HIP_A10_RANGE_LDS_PAD=$pad timeout 600 python bench.py --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --all-kernel-timers "$@" > "$out/bench_levels${lv}_$tpb.json" 2> "$out/bench_levels${lv}_$tpb.err"
+      SYLPH_HIP_A10_LEVELS=$lv SYLPH_HIP_A10_RANGE_SPLIT=$split SYLPH_HIP_A10_RANGE_LDS_PAD=$pad timeout 600 python bench.py --full --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --all-kernel-timers "$@" > "$out/bench_levels${lv}_$tpb.json" 2> "$out/bench_levels${lv}_$tpb.err"
       python - "$out/bench_levels${lv}_$tpb.json" $cfg <<'PY'
 import json, sys
 o = json.load(open(sys.argv[1])); f = o.get("default_pair_dedup", {})
@@ -50,7 +50,7 @@ PY
     done ;;
   a10-profile)
     # per-kernel durations (rocprofv3 kernel trace) and HBM counters of the filter pass: every sample behind sylph's default filter, one at a time
-    BF="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --no-verify --main-dedup-fpr 1e-4 --no-kernel-timers"
+    BF="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --no-verify --main-dedup-fpr 1e-4 --no-kernel-timers"
     rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o s -- $BF > /dev/null 2> "$out/trace.err"
     python - $out <<'PY'
 import csv, glob, sys
@@ -71,7 +71,7 @@ PY
   ab-env)
     # A/B of environment knobs on the pipelined default-flag rate (every session behind sylph's default filter): AB_ROUNDS rounds over the
     # configurations given as arguments ("-" = no variable; "A=1,B=2" = two), alternating, one short bench process each
-    BF="python bench.py --main-dedup-fpr ${AB_FPR:-1e-4} --no-filter-leg --no-second-leg --no-verify --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --min-seconds ${AB_SECONDS:-3} ${AB_EXTRA:-}"
+    BF="python bench.py --full --main-dedup-fpr ${AB_FPR:-1e-4} --no-filter-leg --no-second-leg --no-verify --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --min-seconds ${AB_SECONDS:-3} ${AB_EXTRA:-}"
     : > "$out/ab.txt"
     for r in $(seq 1 ${AB_ROUNDS:-4}); do
       for cfg in "$@"; do

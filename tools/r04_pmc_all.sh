@@ -1,7 +1,7 @@
 # VALU / SALU / LDS instruction counts of EVERY kernel of one sample (sequential mode), one counter group per run
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 out=gpurun_out/r04h; mkdir -p $out
-B="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg"
+B="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --kernel-include-regex 'sylph::' --output-format csv -d $out/pmc_all -o s -- $B > /dev/null 2> $out/pmc.err
 python - <<'PY'
 import csv, glob, collections

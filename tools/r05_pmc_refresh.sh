@@ -3,7 +3,7 @@
 # choice — needs this again), then the default bench line once more on it and a 30-second run of the sample loop.
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 out=gpurun_out/r05_final; mkdir -p $out
-B="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg --no-filter-leg --no-files-leg"
+B="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg --no-filter-leg --no-files-leg"
 K='reads_kernel|probe_kernel|bucket_replay_kernel|hits_scatter_kernel|rows_sort_kernel|hits_count_kernel'
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-include-regex "$K" --output-format csv -d $out/pmc_$c -o s -- $B > /dev/null 2>&1
@@ -35,7 +35,7 @@ print({k: len(v) for k, v in res.items()})
 PY
 rm -rf $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE $out/pmc_SQ $out/pmc_SQ2 $out/pmc_SQ_c3r $out/pmc_c5_FETCH_SIZE $out/pmc_c5_WRITE_SIZE $out/pmc_c5_SQ
 # the filter dedup's partitioned pass: every sample behind sylph's default filter (--main-dedup-fpr), counters per (kernel, grid)
-BF="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --main-dedup-fpr 1e-4"
+BF="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --main-dedup-fpr 1e-4"
 KA='a10_|part_'
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-include-regex "$KA" --output-format csv -d $out/pmca_$c -o s -- $BF --no-kernel-timers > /dev/null 2>&1
@@ -44,11 +44,11 @@ rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST
 python tools/pmc_by_kernel.py $out/pmca_FETCH_SIZE $out/pmca_WRITE_SIZE $out/pmca_SQ > $out/pmc_a10.json
 rm -rf $out/pmca_FETCH_SIZE $out/pmca_WRITE_SIZE $out/pmca_SQ
 # a first bench line (probes per launch, hashed k-mers) -> profiles/seeds_traffic.json for THIS tree, on the box
-python bench.py --steps 4 --warmup 1 --min-seconds 0.5 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_c3_pre.json 2> $out/bench_c3_pre.err
+python bench.py --full --steps 4 --warmup 1 --min-seconds 0.5 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_c3_pre.json 2> $out/bench_c3_pre.err
 python tools/make_r05_profile_md.py --traffic-only > $out/traffic_only.txt 2>&1; tail -2 $out/traffic_only.txt
-python bench.py --steps 20 --warmup 5 > $out/bench_c3_final.json 2> $out/bench_c3_final.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_c3_final.json 2> $out/bench_c3_final.err
 tail -c 300 $out/bench_c3_final.json; echo
-python bench.py --steps 40 --warmup 5 --min-seconds 30 --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg --no-second-leg > $out/bench_long_run.json 2> $out/bench_long_run.err
+python bench.py --full --steps 40 --warmup 5 --min-seconds 30 --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg --no-second-leg > $out/bench_long_run.json 2> $out/bench_long_run.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r05_final/bench_long_run.json").read().strip().splitlines()[-1])

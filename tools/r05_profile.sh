@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 out=gpurun_out/r05_final; mkdir -p $out
 timeout 900 python -m pytest tests -m gpu -x -q > $out/pytest_gpu.txt 2>&1; tail -2 $out/pytest_gpu.txt
-B="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg --no-filter-leg --no-files-leg"
+B="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-kernel-timers --no-packed-leg --no-filter-leg --no-files-leg"
 K='reads_kernel|probe_kernel|bucket_replay_kernel|hits_scatter_kernel|rows_sort_kernel|hits_count_kernel'
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-include-regex "$K" --output-format csv -d $out/pmc_$c -o s -- $B > /dev/null 2>&1
@@ -36,7 +36,7 @@ print({k: len(v) for k, v in res.items()})
 PY
 rm -rf $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE $out/pmc_SQ $out/pmc_SQ2 $out/pmc_SQ_c3r $out/pmc_c5_FETCH_SIZE $out/pmc_c5_WRITE_SIZE $out/pmc_c5_SQ
 # the filter dedup's partitioned pass: every sample behind sylph's default filter (--main-dedup-fpr), counters per (kernel, grid)
-BF="python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --main-dedup-fpr 1e-4"
+BF="python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-packed-leg --no-files-leg --main-dedup-fpr 1e-4"
 KA='a10_|part_'
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-include-regex "$KA" --output-format csv -d $out/pmca_$c -o s -- $BF --no-kernel-timers > /dev/null 2>&1
@@ -45,29 +45,29 @@ rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST
 python tools/pmc_by_kernel.py $out/pmca_FETCH_SIZE $out/pmca_WRITE_SIZE $out/pmca_SQ > $out/pmc_a10.json
 rm -rf $out/pmca_FETCH_SIZE $out/pmca_WRITE_SIZE $out/pmca_SQ
 # a first bench line (probes per launch, hashed k-mers) -> profiles/seeds_traffic.json for THIS tree, on the box
-python bench.py --steps 4 --warmup 1 --min-seconds 0.5 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_c3_pre.json 2> $out/bench_c3_pre.err
+python bench.py --full --steps 4 --warmup 1 --min-seconds 0.5 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_c3_pre.json 2> $out/bench_c3_pre.err
 python tools/make_r05_profile_md.py --traffic-only > $out/traffic_only.txt 2>&1; tail -2 $out/traffic_only.txt
 # ---- the bench lines (they read the traffic figures written just now)
-python bench.py --steps 20 --warmup 5 > $out/bench_c3.json 2> $out/bench_c3.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_c3.json 2> $out/bench_c3.err
 tail -c 300 $out/bench_c3.json
 for wl in c3r c2; do
-  python bench.py --workload $wl --steps 6 --warmup 2 --min-seconds 1.0 --no-cpu-baseline --no-h2d > $out/bench_$wl.json 2> $out/bench_$wl.err
+  python bench.py --full --workload $wl --steps 6 --warmup 2 --min-seconds 1.0 --no-cpu-baseline --no-h2d > $out/bench_$wl.json 2> $out/bench_$wl.err
 done
 for wl in c4 c5; do      # with the CPU leg: the WHOLE sample verified (table + every genome), as c3 has it
-  python bench.py --workload $wl --steps 6 --warmup 2 --min-seconds 1.0 --no-h2d --no-files-leg > $out/bench_$wl.json 2> $out/bench_$wl.err
+  python bench.py --full --workload $wl --steps 6 --warmup 2 --min-seconds 1.0 --no-h2d --no-files-leg > $out/bench_$wl.json 2> $out/bench_$wl.err
 done
-python bench.py --gpus 2 --workload small --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks.json 2> $out/bench_small_2ranks.err
-MASTER_PORT=29581 python bench.py --gpus 2 --workload small --db-mode genome --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks_genome.json 2> $out/bench_small_2ranks_genome.err
-MASTER_PORT=29583 python bench.py --gpus 2 --workload small --db-mode shard --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks_shard.json 2> $out/bench_small_2ranks_shard.err
+python bench.py --full --gpus 2 --workload small --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks.json 2> $out/bench_small_2ranks.err
+MASTER_PORT=29581 python bench.py --full --gpus 2 --workload small --db-mode genome --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks_genome.json 2> $out/bench_small_2ranks_genome.err
+MASTER_PORT=29583 python bench.py --full --gpus 2 --workload small --db-mode shard --steps 3 --warmup 1 --min-seconds 0.3 --no-cpu-baseline --no-h2d > $out/bench_small_2ranks_shard.json 2> $out/bench_small_2ranks_shard.err
 python tools/multi_gpu_pipeline_bench.py --gpus 2 --share > $out/multi_pipeline_2replicas_one_gpu.json 2> $out/multi.err
 # (a) the default (pipelined) command under the tracer: per-kernel durations as the bench line's HIP events see them
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_p -o c3 -- python bench.py --steps 4 --warmup 1 --min-seconds 0.3 --mode pipelined --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_prof.json 2> $out/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_p -o c3 -- python bench.py --full --steps 4 --warmup 1 --min-seconds 0.3 --mode pipelined --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_prof.json 2> $out/prof.err
 f=$(find $out/stats_p -name '*kernel_trace.csv' | head -1)
 python tools/step_timeline.py $f --steps 60 --anchor reads_kernel --summary-only > $out/kernels_pipelined.md
 { echo; echo "## how the seeding kernels of consecutive samples follow each other (tools/seeding_gaps.py over the same trace)"; echo; python tools/seeding_gaps.py $f --last 200 | sed 's/^/    /'; } >> $out/kernels_pipelined.md
 rm -rf $out/stats_p
 # (b) one sample at a time: the dispatch sequence of a sample with its gaps, every kernel alone on the GPU
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o c3 -- python bench.py --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_prof_seq.json 2>> $out/prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o c3 -- python bench.py --full --steps 3 --warmup 1 --min-seconds 0.02 --mode sequential --no-second-leg --no-cpu-baseline --no-h2d --no-verify --no-packed-leg --no-filter-leg --no-files-leg > $out/bench_prof_seq.json 2>> $out/prof.err
 f=$(find $out/stats -name '*kernel_trace.csv' | head -1)
 python tools/step_timeline.py $f --steps 5 --anchor reads_kernel > $out/step_timeline.md
 find $out/stats -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats.csv \;
@@ -79,7 +79,7 @@ python tools/step_timeline.py $f --steps 5 --anchor reads_kernel > $out/step_tim
 find $out/stats_f -name '*kernel_stats.csv' -exec cp {} $out/kernel_stats_filter.csv \;
 rm -rf $out/stats_f
 # a 30-second run of the sample loop (35,000 samples): no drift, no growth
-python bench.py --steps 40 --warmup 2 --min-seconds 30 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg --no-second-leg --no-verify > $out/bench_long_run.json 2> $out/bench_long_run.err
+python bench.py --full --steps 40 --warmup 2 --min-seconds 30 --no-cpu-baseline --no-h2d --no-packed-leg --no-filter-leg --no-files-leg --no-second-leg --no-verify > $out/bench_long_run.json 2> $out/bench_long_run.err
 # R05_SKIP_HOST=1 (the refresh at the round's last kernel sources): the host-side legs below did not change, their outputs stay
 [ -n "$R05_SKIP_HOST" ] && exit 0
 python tools/feed_bench.py 3333334 > $out/feed.txt 2> $out/feed.err
