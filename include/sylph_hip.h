@@ -257,6 +257,20 @@ int sylph_inflated_info(const sylph_inflated *t, uint64_t *n_members, uint64_t *
 int sylph_inflated_read(sylph_inflated *t, uint64_t first, uint64_t n, void *host_out);
 void sylph_inflated_destroy(sylph_inflated *t);
 
+/* ---- bzip2 decoded on the device (csrc/bunzip2.hip) ------------------------------------------------------------------------------
+ * The reference reads a .bz2 file through needletail -> libbz2 on the thread that sketches it.  sylph_bunzip2 takes the COMPRESSED
+ * bytes of one file (host memory), finds every block magic, decodes all blocks side by side and checks every block CRC and every
+ * stream's combined CRC; several streams in one file (what pbzip2 writes) are one text.  The result is the same handle as
+ * sylph_inflate's: sylph_inflated_file / _text / _read / _destroy work unchanged, and the text is readable 256 bytes either side.
+ * sylph_inflated_info of such a handle: members = bzip2 streams, blocks = bzip2 blocks, candidates = block magics decoded, host
+ * members = 0, decoded again = 0.  Returns SYLPH_ERR_FORMAT, having done nothing else, when the bytes are not BZh1-9 streams back to
+ * back, a block is randomised, a CRC or any structure check fails: the caller then decodes with libbz2.  SYLPH_ERR_NOMEM when the
+ * text does not fit.  sylph_bunzip2_files: several files (the two mates of a pair) in one call and one decode launch; file i's text
+ * is sylph_inflated_file(t, i, ...).  All files or none. */
+int sylph_bunzip2(sylph_ctx *ctx, const void *bz, uint64_t n_bytes, int mem, sylph_inflated **out);
+int sylph_bunzip2_files(sylph_ctx *ctx, const void *const *bz, const uint64_t *n_bytes, uint32_t n_files, int mem,
+                        sylph_inflated **out);
+
 /* Finish the sample: (k-mer, count) table in ascending k-mer order == SequencesSketch.kmer_counts
  * (types.rs:145-155) as a keyed multiset, and the number of occurrences removed as duplicates
  * (sketch.rs:886-892).  The *_device variant leaves the table in HBM (owned by the session, valid until

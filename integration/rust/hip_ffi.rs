@@ -135,6 +135,11 @@ extern "C" {
                                n_host_members: *mut u64, n_decoded_again: *mut u64) -> c_int;
     pub fn sylph_inflated_read(t: *mut SylphInflated, first: u64, n: u64, host_out: *mut c_void) -> c_int;
     pub fn sylph_inflated_destroy(t: *mut SylphInflated);
+    // bzip2 decoded on the device (what needletail's BzDecoder does inside parse_fastx_file): the same handle as sylph_inflate's;
+    // ERR_FORMAT = -5: keep the libbz2 reader for this file
+    pub fn sylph_bunzip2(ctx: *mut SylphCtx, bz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;
+    pub fn sylph_bunzip2_files(ctx: *mut SylphCtx, bz: *const *const c_void, n_bytes: *const u64, n_files: u32, mem: c_int,
+                               out: *mut *mut SylphInflated) -> c_int;   // the two mates of a pair in one pass
     // k-mer-range shards: bounds for `world` GPUs, upload of this rank's range, communicator, the collective batch call
     pub fn sylph_shard_bounds(max_kmer: u64, world: u32, bounds: *mut u64) -> c_int;
     pub fn sylph_db_upload_shard(ctx: *mut SylphCtx, kmers: *const u64, genome_off: *const u64, n_genomes: u64, mem: c_int,

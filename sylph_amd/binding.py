@@ -39,7 +39,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_db_replicate", "sylph_pipeline_create_multi", "sylph_pipeline_replica_of_last", "sylph_device_count",
            "sylph_genome_shard_bounds", "sylph_db_upload_genome_shard",
            "sylph_fastq_index", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
-           "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy"]
+           "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
+           "sylph_bunzip2", "sylph_bunzip2_files"]
 
 
 def load():
@@ -89,6 +90,8 @@ def load():
     L.sylph_inflated_read.argtypes = [vp, u64, u64, vp]
     L.sylph_inflated_destroy.argtypes = [vp]
     L.sylph_inflated_destroy.restype = None
+    L.sylph_bunzip2.argtypes = [vp, vp, u64, i32, P(vp)]
+    L.sylph_bunzip2_files.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, P(vp)]
     L.sylph_pack_2bit.argtypes = [vp, u64, vp]
     L.sylph_sketch_finish.argtypes = [vp, P(vp), P(vp), P(u64), P(u64)]
     L.sylph_sketch_finish_device.argtypes = [vp, P(vp), P(vp), P(u64), P(u64)]
@@ -282,6 +285,8 @@ class Inflated:
     stays in HBM: .dev_ptr / .n_bytes go to FastqText(ctx, ptr, MEM_DEVICE, n_bytes); read() copies a range back.  Raises SylphHipError
     with code ERR_FORMAT when the library declines the stream (not gzip, damaged, ...): inflate on the host then."""
 
+    _one, _many = "sylph_inflate", "sylph_inflate_files"
+
     def __init__(self, ctx, gz):
         """gz: the bytes of one file, or a list of them (sylph_inflate_files: one pass over all; .files[i] = (dev_ptr, n_bytes))"""
         self._h = None
@@ -291,9 +296,9 @@ class Inflated:
         if many:
             ptrs = (C.c_void_p * len(keeps))(*[k.ctypes.data for k in keeps])
             lens = (C.c_uint64 * len(keeps))(*[len(k) for k in keeps])
-            _check(load().sylph_inflate_files(ctx._h, ptrs, lens, len(keeps), MEM_HOST, C.byref(h)))
+            _check(getattr(load(), self._many)(ctx._h, ptrs, lens, len(keeps), MEM_HOST, C.byref(h)))
         else:
-            _check(load().sylph_inflate(ctx._h, _ptr(keeps[0]) if len(keeps[0]) else None, len(keeps[0]), MEM_HOST, C.byref(h)))
+            _check(getattr(load(), self._one)(ctx._h, _ptr(keeps[0]) if len(keeps[0]) else None, len(keeps[0]), MEM_HOST, C.byref(h)))
         self._h = h
         self.files = []
         for i in range(len(keeps)):
@@ -324,6 +329,13 @@ class Inflated:
         except Exception:
             pass
 
+
+
+class Bunzipped(Inflated):
+    """sylph_bunzip2: the bytes of one bzip2 file (or a list of them: sylph_bunzip2_files) decoded on the device (csrc/bunzip2.hip),
+    the same handle as Inflated's.  n_members = streams, n_blocks = bzip2 blocks, n_candidates = block magics decoded.  Raises
+    SylphHipError with code ERR_FORMAT when the library declines the bytes (not bzip2, damaged, randomised, ...): decode on the host then."""
+    _one, _many = "sylph_bunzip2", "sylph_bunzip2_files"
 
 class FastqText:
     """sylph_fastq_*: plain four-line FASTQ text whose records the DEVICE finds (csrc/fastq.hip).  `text`: bytes / a uint8 array

@@ -1,0 +1,252 @@
+// bunzip2_plan.h — the bookkeeping of the device-side bzip2 decoder (csrc/bunzip2.hip), host-compilable: nothing here touches HIP,
+// so tests/bunzip2_plan_capi.cpp builds it with g++ and the CPU suite checks it against Python's bz2 (tests/test_bunzip2_host.py).
+//
+// A bzip2 stream is "BZh" + a level '1'-'9', then bit-aligned blocks, each behind the 48-bit magic 0x314159265359 and holding at most
+// level x 100 000 bytes of BWT column, then the end-of-stream magic 0x177245385090, the stream's combined CRC and padding to a byte.
+// Blocks carry no length, so where one ENDS is known only once it has been decoded.  csrc/bunzip2.hip makes that table work:
+//   * every bit position of the file is tested for the block magic — the CANDIDATES, a superset of the true block starts (a false
+//     one turns up with odds 2^-48 per bit position);
+//   * one wavefront decodes each candidate and reports where its end-of-block symbol ended (BlockReport);
+//   * this file walks the chain over those reports (ChainWalk): the stream header -> the candidate at bit 32 -> the one where that
+//     block ended -> ... -> the end-of-stream magic -> the combined CRC -> the next stream's header -> ...; a candidate that is not
+//     on the chain was never a block start;
+//   * the block CRCs (CRC-32 with polynomial 0x04C11DB7, MSB first: the non-reflected form, unlike gzip's) are put together from
+//     the CRCs of pieces computed anywhere on the device (crc_shift below: the CRC is linear over GF(2)), and the run-length
+//     decode of a block is a scan of small state-transfer functions (RleFn).
+// Anything that does not add up makes the whole call decline (SYLPH_ERR_FORMAT): the caller decodes the file with libbz2 as before.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define SYLPH_HD __host__ __device__
+#else
+#define SYLPH_HD
+#endif
+
+namespace sylph {
+namespace bunzip2_plan {
+
+constexpr uint64_t BLOCK_MAGIC = 0x314159265359ull;
+constexpr uint64_t EOS_MAGIC = 0x177245385090ull;
+constexpr uint32_t MAX_BLOCK = 900000;        // bytes of BWT column in a block at level 9
+constexpr uint32_t MAX_SELECTORS = 18002;     // what libbz2 1.0.8 keeps (2 + 900 000 / 50); a block that sends more is declined
+
+// ---- CRC-32/BZIP2 as polynomial arithmetic over GF(2) ------------------------------------------------------------------------
+// Bit 31 of a word is the coefficient of x^31, bit 0 that of x^0; the implicit x^32 of the polynomial is left out.
+constexpr uint32_t CRC_POLY = 0x04C11DB7u;
+
+// a * b mod P
+SYLPH_HD inline uint32_t crc_multmodp(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 31; i >= 0; i--) {
+        p = (p & 0x80000000u) ? (p << 1) ^ CRC_POLY : p << 1;
+        if ((a >> i) & 1) p ^= b;
+    }
+    return p;
+}
+// x2n[k] = x^(2^k) mod P, k = 0 .. 63
+inline void crc_x2n_table(uint32_t t[64]) {
+    uint32_t p = 2u;                              // x^1
+    t[0] = p;
+    for (int k = 1; k < 64; k++) t[k] = p = crc_multmodp(p, p);
+}
+// x^(8 n) mod P
+SYLPH_HD inline uint32_t crc_x8n(const uint32_t* x2n, unsigned long long n_bytes) {
+    uint32_t p = 1u;                              // x^0
+    unsigned k = 3;
+    while (n_bytes) {
+        if (n_bytes & 1) p = crc_multmodp(x2n[k & 63], p);
+        n_bytes >>= 1;
+        k++;
+    }
+    return p;
+}
+// the register of the CRC loop (no initial or final inversion) after n more zero bytes
+SYLPH_HD inline uint32_t crc_shift(const uint32_t* x2n, uint32_t reg, unsigned long long n_bytes) {
+    return n_bytes ? crc_multmodp(crc_x8n(x2n, n_bytes), reg) : reg;
+}
+// a block's CRC from `raw` = XOR over its pieces of crc_shift(register of the piece started at 0, bytes behind the piece in the
+// block): the initial 0xFFFFFFFF travels through all n bytes, the final inversion is on top
+inline uint32_t crc_finish(const uint32_t* x2n, uint32_t raw, unsigned long long n_bytes) {
+    return ~(raw ^ crc_shift(x2n, 0xFFFFFFFFu, n_bytes));
+}
+inline void crc_byte_table(uint32_t t[256]) {
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t c = i << 24;
+        for (int k = 0; k < 8; k++) c = (c & 0x80000000u) ? (c << 1) ^ CRC_POLY : c << 1;
+        t[i] = c;
+    }
+}
+SYLPH_HD inline uint32_t crc_raw(const uint32_t* t, uint32_t reg, const uint8_t* p, size_t n) {
+    for (size_t i = 0; i < n; i++) reg = (reg << 8) ^ t[(reg >> 24) ^ p[i]];
+    return reg;
+}
+// a stream's combined CRC, block after block
+inline uint32_t combine_stream(uint32_t c, uint32_t block_crc) { return ((c << 1) | (c >> 31)) ^ block_crc; }
+
+// ---- the run-length decode as a scan -------------------------------------------------------------------------------------------
+// The inverse BWT gives the "RLE1" text: after 4 equal bytes the next byte is a repeat count (0-255) of the fourth.  The state in
+// front of a byte is k = the length of the current run of equal non-count bytes (4: the byte is a count).  Seen from a chunk that
+// begins with byte b, what came before matters only through eff_k: 4 when a count is due, k in 1..3 when the run's byte is b,
+// 0 otherwise.  RleFn is the chunk's map eff_k -> (k behind its last byte, bytes it writes); behind a chunk with k_out >= 1 the
+// run's byte is the chunk's last byte.
+struct RleFn {
+    uint32_t len[5];
+    uint32_t k_out;        // 3 bits per eff_k
+    SYLPH_HD uint32_t kout(uint32_t k) const { return (k_out >> (3 * k)) & 7; }
+};
+SYLPH_HD inline RleFn rle_fn(const uint8_t* p, uint32_t n) {
+    RleFn f;
+    f.k_out = 0;
+    for (uint32_t k0 = 0; k0 < 5; k0++) {
+        uint32_t k = k0, len = 0;
+        uint8_t c = p[0];                          // (eff_k 1..3: the run's byte is the first byte)
+        for (uint32_t i = 0; i < n; i++) {
+            const uint8_t x = p[i];
+            if (k == 4) { len += x; k = 0; }
+            else if (k > 0 && x == c) { k++; len++; }
+            else { c = x; k = 1; len++; }
+        }
+        f.len[k0] = len;
+        f.k_out |= k << (3 * k0);
+    }
+    return f;
+}
+// eff_k in front of a chunk that begins with `first`, behind a chunk that ended in state k_out with last byte `last`
+SYLPH_HD inline uint32_t rle_eff(uint32_t k_out, uint8_t last, uint8_t first) {
+    return k_out == 4 ? 4u : (k_out >= 1 && last == first ? k_out : 0u);
+}
+// expands p[0..n) from eff_k into out (run byte in front: `prev`, used when eff_k = 4); returns the bytes written
+SYLPH_HD inline uint32_t rle_expand(const uint8_t* p, uint32_t n, uint32_t k, uint8_t prev, uint8_t* out) {
+    uint8_t c = k == 4 ? prev : p[0];
+    uint32_t o = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t x = p[i];
+        if (k == 4) { for (uint32_t r = 0; r < x; r++) out[o++] = c; k = 0; }
+        else if (k > 0 && x == c) { k++; out[o++] = x; }
+        else { c = x; k = 1; out[o++] = x; }
+    }
+    return o;
+}
+
+// ---- what a decoding wavefront reports per candidate -------------------------------------------------------------------------
+enum : uint32_t {
+    ST_OK = 0,
+    ST_ERR_MAGIC = 16,      // no block magic at the candidate (cannot happen: the scan found one)
+    ST_ERR_HEADER = 17,     // symbol map / groups / selectors / code lengths out of range
+    ST_ERR_CODE = 18,       // a Huffman code longer than 20 bits or outside the table, a selector past the last
+    ST_ERR_SIZE = 19,       // more than MAX_BLOCK bytes, or a run too long
+    ST_ERR_ORIG = 20,       // origPtr outside the block
+    ST_ERR_OVERRUN = 21,    // ran out of input
+    ST_ERR_SELECTORS = 22,  // more selectors than libbz2 keeps
+};
+struct BlockReport {
+    unsigned long long end_bit;   // first bit behind the end-of-block symbol
+    uint32_t status;
+    uint32_t n;                   // bytes of BWT column
+    uint32_t orig_ptr;
+    uint32_t crc;                 // the block CRC the stream stores
+    uint32_t randomised;
+    uint32_t symbols;             // (diagnostics) symbols decoded
+};
+
+// ---- the chain ------------------------------------------------------------------------------------------------------------------
+struct Segments {                 // the files of one call: each its own bytes; in the device's buffer they lie back to back
+    std::vector<const uint8_t*> ptr;
+    std::vector<uint64_t> base;   // base[i] = byte offset of file i; base.back() = the total
+};
+// the k <= 48 bits at `bit` (MSB-first) of d[0, n), zero beyond n bytes
+inline uint64_t bits_at(const uint8_t* d, uint64_t n, uint64_t bit, unsigned k) {
+    uint64_t v = 0;
+    for (unsigned i = 0; i < k; i++) {
+        const uint64_t b = bit + i;
+        v = (v << 1) | (b / 8 < n ? (d[b / 8] >> (7 - b % 8)) & 1u : 0u);
+    }
+    return v;
+}
+inline int stream_level(const uint8_t* d, uint64_t n, uint64_t p) {
+    return p + 4 <= n && d[p] == 'B' && d[p + 1] == 'Z' && d[p + 2] == 'h' && d[p + 3] >= '1' && d[p + 3] <= '9' ? d[p + 3] - '0' : 0;
+}
+
+struct ChainBlock { uint32_t cand, file, stream; uint32_t n; };
+// Walks the chain one step at a time as candidates' reports come in (the device decodes them in batches, in bit order):
+// step() follows the chain while the report it needs is there; it stops in front of a candidate index >= `have` (wants()).
+struct ChainWalk {
+    const Segments* S = nullptr;
+    const std::vector<uint64_t>* cand = nullptr;   // sorted candidate bits
+    std::vector<ChainBlock> blocks;
+    uint32_t n_streams = 0;
+    std::string why;                               // non-empty: declined, and why
+    bool done = false;
+    // position
+    uint32_t file = 0;
+    uint64_t bit = 0;                              // where the next block / end-of-stream magic starts (in_stream) or the next header byte * 8
+    bool in_stream = false;
+    int level = 0;
+    uint32_t combined = 0;
+    size_t next_cand = 0;                          // candidates before it lie behind the chain
+
+    void start(const Segments* s, const std::vector<uint64_t>* c) {
+        S = s; cand = c;
+        file = 0; bit = S->base[0] * 8; in_stream = false; done = false;
+        skip_empty_files();
+    }
+    void skip_empty_files() {        // (a file without a byte is no bzip2 file)
+        if (file + 1 < S->base.size() && S->base[file + 1] == S->base[file]) why = "file " + std::to_string(file) + " is empty";
+    }
+    // -> index of the candidate at `b`, or SIZE_MAX
+    size_t find(uint64_t b) {
+        while (next_cand < cand->size() && (*cand)[next_cand] < b) next_cand++;
+        return next_cand < cand->size() && (*cand)[next_cand] == b ? next_cand : SIZE_MAX;
+    }
+    // follow the chain; reports of candidates [0, have) are known.  Returns false when it stopped for a report it has not got.
+    bool step(const BlockReport* rep, size_t have) {
+        while (!done && why.empty()) {
+            const uint8_t* d = S->ptr[file];
+            const uint64_t fb = S->base[file], fn = S->base[file + 1] - fb;   // the file's bytes; `bit` counts in the whole buffer
+            const uint64_t lb = bit - fb * 8;
+            if (!in_stream) {
+                level = stream_level(d, fn, lb / 8);
+                if (!level) { why = "no bzip2 stream header at byte " + std::to_string(lb / 8) + " of file " + std::to_string(file); return true; }
+                in_stream = true;
+                combined = 0;
+                bit += 32;
+                n_streams++;
+                continue;
+            }
+            const uint64_t m = bits_at(d, fn, lb, 48);
+            if (m == EOS_MAGIC) {
+                if (lb + 80 > fn * 8) { why = "end-of-stream trailer beyond the end of the file"; return true; }
+                const uint32_t stored = (uint32_t)bits_at(d, fn, lb + 48, 32);
+                if (stored != combined) { why = "stream " + std::to_string(n_streams - 1) + ": combined CRC differs"; return true; }
+                in_stream = false;
+                bit = fb * 8 + (lb + 80 + 7) / 8 * 8;
+                if (bit == (fb + fn) * 8) {
+                    file++;
+                    if (file + 1 == S->base.size()) { done = true; return true; }
+                    skip_empty_files();
+                }
+                continue;
+            }
+            if (m != BLOCK_MAGIC) { why = "chain breaks at bit " + std::to_string(lb) + " of file " + std::to_string(file) + " (neither a block nor the end of the stream)"; return true; }
+            const size_t i = find(bit);
+            if (i == SIZE_MAX) { why = "block magic at bit " + std::to_string(lb) + " is no candidate"; return true; }
+            if (i >= have) return false;
+            const BlockReport& r = rep[i];
+            if (r.status != ST_OK) { why = "block at bit " + std::to_string(lb) + ": decoder status " + std::to_string(r.status); return true; }
+            if (r.randomised) { why = "block at bit " + std::to_string(lb) + " is randomised"; return true; }
+            if (r.n > (uint32_t)level * 100000u) { why = "block at bit " + std::to_string(lb) + " is larger than the stream's level allows"; return true; }
+            if (r.end_bit + 48 > (fb + fn) * 8) { why = "block at bit " + std::to_string(lb) + " runs past the end of its file"; return true; }
+            blocks.push_back(ChainBlock{(uint32_t)i, file, n_streams - 1, r.n});
+            combined = combine_stream(combined, r.crc);
+            bit = r.end_bit;
+        }
+        return true;
+    }
+};
+
+}  // namespace bunzip2_plan
+}  // namespace sylph

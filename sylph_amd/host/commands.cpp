@@ -306,6 +306,17 @@ bool is_gzip_file(const std::string& f) {
     fclose(fp);
     return n == 2 && h[0] == 0x1f && h[1] == 0x8b;
 }
+// needletail's test for bzip2: the first two bytes are "BZ" (a regular file only, like is_gzip_file)
+bool is_bzip2_file(const std::string& f) {
+    struct stat st;
+    if (stat(f.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return false;
+    FILE* fp = fopen(f.c_str(), "rb");
+    if (!fp) return false;
+    unsigned char h[2] = {0, 0};
+    const size_t n = fread(h, 1, 2, fp);
+    fclose(fp);
+    return n == 2 && h[0] == 'B' && h[1] == 'Z';
+}
 // Batches of whole records (pairs) of at most BATCH_BASES bases / BATCH_RECS records
 std::vector<std::pair<size_t, size_t>> cut_batches(size_t n, bool paired, const std::vector<uint64_t>& ca, const std::vector<uint64_t>& cb) {
     std::vector<std::pair<size_t, size_t>> out;
@@ -417,6 +428,16 @@ bool device_inflate_enabled() {
     }();
     return on;
 }
+// bzip2 on the device (csrc/bunzip2.hip), the same way: the compressed bytes travel, sylph_bunzip2_files decodes them there;
+// SYLPH_HIP_BUNZIP2_DEVICE=0 keeps the host's reader (libbz2 in FastxReader).  What the library declines goes the host way.
+bool device_bunzip2_enabled() {
+    static const bool on = [] {
+        if (!device_feed_enabled()) return false;
+        if (const char* e = getenv("SYLPH_HIP_BUNZIP2_DEVICE")) return atoi(e) != 0;
+        return true;
+    }();
+    return on;
+}
 namespace {
 struct MappedFile {                       // the compressed bytes of one file (read-only mapping of the page cache)
     const uint8_t* data = nullptr;
@@ -442,7 +463,8 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
                             double& mean_read_length, const IndexedInput* text = nullptr) {
     if (!device_feed_enabled()) return false;
     const bool gz = !text && device_inflate_enabled() && is_gzip_file(f1) && (!f2 || is_gzip_file(*f2));
-    if (!gz && !e.ready()) return false;             // (a gzip sample waits for the engine: nothing on the host side is faster than that)
+    const bool bz = !text && !gz && device_bunzip2_enabled() && is_bzip2_file(f1) && (!f2 || is_bzip2_file(*f2));
+    if (!gz && !bz && !e.ready()) return false;      // (a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that)
     static const bool trace = getenv("SYLPH_HIP_FEED_TRACE") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_prev = now();
@@ -457,8 +479,8 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     if (f2) files.push_back(*f2);
     std::vector<TextUploader::Text> texts;
     InflatedText inflated;                           // (destroyed behind the indexes that borrow its text: declared before them)
-    if (gz) {
-        // both mates in ONE call (sylph_inflate_files): one scan, one decode launch, one chain — the mates share a block's latency
+    if (gz || bz) {
+        // both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files): one scan, one decode launch, one chain — the mates share a block's latency
         std::vector<std::unique_ptr<MappedFile>> maps;
         std::vector<const void*> ptrs;
         std::vector<uint64_t> lens;
@@ -468,12 +490,13 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             ptrs.push_back(maps.back()->data);
             lens.push_back(maps.back()->size);
         }
-        const int rc = sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
+        const int rc = gz ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h)
+                          : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
         if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device inflate declined %s: %s\n", files[0].c_str(), sylph_last_error());
+            if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", files[0].c_str(), sylph_last_error());
             return false;
         }
-        hip_check(rc, "sylph_inflate_files");
+        hip_check(rc, gz ? "sylph_inflate_files" : "sylph_bunzip2_files");
         for (uint32_t i = 0; i < ptrs.size(); i++) {
             const void* dev = nullptr;
             uint64_t bytes = 0;
@@ -481,7 +504,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             if (!bytes) return false;
             texts.push_back(TextUploader::Text{(const uint8_t*)dev, bytes});
         }
-        lap("device route: gzip inflated on the device");
+        lap(gz ? "device route: gzip inflated on the device" : "device route: bzip2 decoded on the device");
     } else if (text) {
         // The first text an engine sends pays for the route's device buffers (~40-90 ms of allocations, once); skipping the host's index
         // and gather of an inflated copy buys that back only for a sample of some size: 0.45 against 0.53 s for a 1 Gbp gzip pair, 0.34
@@ -492,7 +515,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
         if (f2) mem.push_back({text->b->data, text->b->size});
         if (!e.text.send(ctx, mem, parse_threads(), texts)) return false;
     } else if (!e.text.send(ctx, files, parse_threads(), texts)) return false;
-    if (!gz) lap("device route: text uploaded");
+    if (!gz && !bz) lap("device route: text uploaded");
     struct Fq { sylph_fastq* f = nullptr; ~Fq() { sylph_fastq_destroy(f); } } fa, fb;
     auto index = [&](const TextUploader::Text& t, Fq& out) {
         const int rc = sylph_fastq_index(ctx, t.dev, t.bytes, SYLPH_MEM_DEVICE, &out.f);
@@ -983,13 +1006,15 @@ int sketch(Engine& e, const SketchArgs& args) {
         const auto& jf = job_files[j];
         const bool gz = device_feed_enabled() && is_gzip_file(jf.first);
         const bool gz_dev = gz && device_inflate_enabled();                      // round 6: the compressed bytes travel, the device inflates
-        const bool dev = device_feed_enabled() && (gz_dev || (eng.ready() && !gz));
+        const bool bz = device_feed_enabled() && !gz && is_bzip2_file(jf.first);
+        const bool bz_dev = bz && device_bunzip2_enabled();                      // bzip2 the same way (SYLPH_HIP_BUNZIP2_DEVICE=0: libbz2 on the host)
+        const bool dev = device_feed_enabled() && (gz_dev || bz_dev || (eng.ready() && !gz && !bz));
         std::optional<IndexedInput> pre;
         if (gz && !gz_dev) pre = index_inputs(jf.first, jf.second ? &*jf.second : nullptr, false);   // inflated on the host, its text then sent as it is
         else if (!dev) pre = ahead.get(j);
         // (a gzip sample on the device route needs none of the page-locked feed buffers: an engine still in its bring-up leaves them to
         //  whoever wants them first — ~80 ms of hipHostMalloc that would run beside the sample's own allocations and copies)
-        if (gz_dev && !eng.ready()) { eng.defer_pinned.store(true); eng.warm_text_route.store(true); }
+        if ((gz_dev || bz_dev) && !eng.ready()) { eng.defer_pinned.store(true); eng.warm_text_route.store(true); }
         trace_mark(dev ? "sketch: the sample goes the device route" : "sketch: the sample's files are indexed (or not indexable)");
         if (++indexes_obtained == n_jobs) set_no_more_inflates(true);   // nobody will want a recycled inflate buffer any more
         // the index goes (2 x 1 GB of mappings to unmap / inflated copies to hand back: 30-60 ms per sample) on a thread of its own, behind the sample
@@ -1497,7 +1522,9 @@ int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
                 } else {
                     const bool gz = device_feed_enabled() && is_gzip_file(files[0]);   // (see sketch(): the device route)
                     const bool gz_dev = gz && device_inflate_enabled();
-                    const bool dev = device_feed_enabled() && (gz_dev || (eng.ready() && !gz));
+                    const bool bz = device_feed_enabled() && !gz && is_bzip2_file(files[0]);
+                    const bool bz_dev = bz && device_bunzip2_enabled();
+                    const bool dev = device_feed_enabled() && (gz_dev || bz_dev || (eng.ready() && !gz && !bz));
                     std::optional<IndexedInput> pre;
                     if (gz && !gz_dev) pre = index_inputs(files[0], files.size() > 1 ? &files[1] : nullptr, false);
                     else if (!dev) pre = ahead.get(j);

@@ -1,4 +1,5 @@
-// formats.cpp — .sylsp / .syldb (bincode 1.3.3 default layout) and FASTA/FASTQ(+gzip) records.
+// formats.cpp — .sylsp / .syldb (bincode 1.3.3 default layout) and FASTA/FASTQ(+gzip, +bzip2) records.
+#include <dlfcn.h>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -237,6 +238,92 @@ bool is_fasta(const std::string& f) {
 }
 
 // ---- FASTX ---------------------------------------------------------------------------------------------------------
+namespace {
+// libbz2 (what needletail 0.5.1 decodes a "BZ" file with: bzip2-rs over the C library) bound with dlopen — there is no header to
+// build against, so bz_stream is declared here with the layout of bzlib.h 1.0.x
+struct BzStream {
+    char* next_in;
+    unsigned int avail_in, total_in_lo32, total_in_hi32;
+    char* next_out;
+    unsigned int avail_out, total_out_lo32, total_out_hi32;
+    void* state;
+    void* (*bzalloc)(void*, int, int);
+    void (*bzfree)(void*, void*);
+    void* opaque;
+};
+constexpr int BZ_OK = 0, BZ_STREAM_END = 4;
+struct Bz2Lib {
+    void* lib = nullptr;
+    int (*init)(BzStream*, int, int) = nullptr;
+    int (*run)(BzStream*) = nullptr;
+    int (*end)(BzStream*) = nullptr;
+    Bz2Lib() {
+        for (const char* name : {"libbz2.so.1.0", "libbz2.so.1"})
+            if ((lib = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
+        if (!lib) return;
+        init = (decltype(init))dlsym(lib, "BZ2_bzDecompressInit");
+        run = (decltype(run))dlsym(lib, "BZ2_bzDecompress");
+        end = (decltype(end))dlsym(lib, "BZ2_bzDecompressEnd");
+        if (!init || !run || !end) lib = nullptr;
+    }
+};
+const Bz2Lib& bz2_lib() { static const Bz2Lib b; return b; }
+bool bz2_stream_head(const char* p, size_t n) { return n >= 4 && p[0] == 'B' && p[1] == 'Z' && p[2] == 'h' && p[3] >= '1' && p[3] <= '9'; }
+}  // namespace
+
+// Every stream of the file is decoded (a file that pbzip2 wrote is many), as `bzip2 -d` and Python's bz2 do; bytes behind the last
+// stream that do not begin another one are ignored.  A damaged or truncated stream is an error from then on.
+struct FastxReader::Bz2 {
+    gzFile raw;                    // the file's bytes as they are (gzopen in transparent mode: a file or a named pipe)
+    BzStream zs;
+    bool open = false, raw_eof = false, failed = false, done = false;
+    std::string in;
+    size_t in_pos = 0;
+    Bz2(gzFile g, std::string head) : raw(g), in(std::move(head)) { memset(&zs, 0, sizeof(zs)); }
+    ~Bz2() { if (open) bz2_lib().end(&zs); }
+    bool more_raw() {              // false at the end of the file
+        if (raw_eof) return false;
+        if (in_pos == in.size()) { in.clear(); in_pos = 0; }
+        const size_t have = in.size();
+        in.resize(have + (1 << 20));
+        const int n = gzread(raw, &in[have], 1 << 20);
+        in.resize(have + (size_t)std::max(n, 0));
+        if (n <= 0) raw_eof = true;
+        if (n < 0) failed = true;
+        return n > 0;
+    }
+    int read(char* dst, int cap) {
+        if (failed) return -1;
+        int got = 0;
+        while (got < cap && !done) {
+            if (!open) {
+                while (in.size() - in_pos < 4 && more_raw()) {}
+                if (failed) return -1;
+                if (!bz2_stream_head(in.data() + in_pos, in.size() - in_pos)) { done = true; break; }   // the end, or trailing bytes
+                if (bz2_lib().init(&zs, 0, 0) != BZ_OK) { failed = true; return -1; }
+                open = true;
+            }
+            if (in_pos == in.size()) more_raw();
+            if (failed) return -1;
+            zs.next_in = &in[0] + in_pos;
+            zs.avail_in = (unsigned)(in.size() - in_pos);
+            zs.next_out = dst + got;
+            zs.avail_out = (unsigned)(cap - got);
+            const int rc = bz2_lib().run(&zs);
+            const size_t in_was = in_pos;
+            const int got_was = got;
+            in_pos = in.size() - zs.avail_in;
+            got = cap - (int)zs.avail_out;
+            if (rc == BZ_STREAM_END) { bz2_lib().end(&zs); memset(&zs, 0, sizeof(zs)); open = false; }
+            else if (rc != BZ_OK) { failed = true; return -1; }
+            else if (in_pos == in_was && got == got_was && raw_eof) { failed = true; return -1; }   // a stream without its end: truncated
+        }
+        return got;
+    }
+};
+
+int FastxReader::fill(char* dst, int cap) { return bz_ ? bz_->read(dst, cap) : gzread((gzFile)gz_, dst, cap); }
+
 FastxReader::FastxReader(const std::string& path) {
     gz_ = gzopen(path.c_str(), "rb");   // transparently reads plain files too
     if (!gz_) throw Error{1, path + " is not a valid fasta/fastq file; skipping."};
@@ -247,18 +334,30 @@ FastxReader::FastxReader(const std::string& path) {
     // first byte that is neither '>' nor '@': peek, so that callers take their "not a valid fasta/fastq file; skipping" branch
     // instead of writing an empty sketch
     buf_.resize(1 << 20);
-    const int n = gzread((gzFile)gz_, &buf_[0], 1 << 20);
-    if (n < 0) { gzclose((gzFile)gz_); gz_ = nullptr; throw Error{1, path + " is not a valid fasta/fastq file; skipping."}; }
+    int n = gzread((gzFile)gz_, &buf_[0], 1 << 20);
+    // needletail's first two bytes "BZ" (the file's own, not a gzip member's text): bzip2
+    if (n >= 2 && gzdirect((gzFile)gz_) && buf_[0] == 'B' && buf_[1] == 'Z') {
+        if (!bz2_lib().lib) {
+            gzclose((gzFile)gz_);
+            gz_ = nullptr;
+            throw Error{1, path + " is bzip2-compressed and libbz2 (libbz2.so.1.0 / libbz2.so.1) could not be loaded; skipping."};
+        }
+        bz_.reset(new Bz2((gzFile)gz_, buf_.substr(0, (size_t)n)));
+        buf_.resize(1 << 20);
+        n = bz_->read(&buf_[0], 1 << 20);
+    }
+    if (n < 0) { bz_.reset(); gzclose((gzFile)gz_); gz_ = nullptr; throw Error{1, path + " is not a valid fasta/fastq file; skipping."}; }
     buf_.resize((size_t)n);
     if (n == 0) eof_ = true;
     // (the very first byte decides, as in needletail's parse_fastx_reader: a file that begins with a blank line is rejected too)
     if (buf_.empty() || (buf_[0] != '>' && buf_[0] != '@')) {
+        bz_.reset();
         gzclose((gzFile)gz_);
         gz_ = nullptr;
         throw Error{1, path + " is not a valid fasta/fastq file; skipping."};
     }
 }
-FastxReader::~FastxReader() { if (gz_) gzclose((gzFile)gz_); }
+FastxReader::~FastxReader() { bz_.reset(); if (gz_) gzclose((gzFile)gz_); }
 
 bool FastxReader::getline(std::string& line) {
     line.clear();
@@ -281,8 +380,13 @@ bool FastxReader::getline(std::string& line) {
             return !line.empty();
         }
         buf_.resize(1 << 20);
-        const int n = gzread((gzFile)gz_, &buf_[0], 1 << 20);
-        if (n < 0) throw Error{1, "read error"};
+        const int n = fill(&buf_[0], 1 << 20);
+        if (n < 0) {
+            buf_.clear();
+            pos_ = 0;
+            if (bz_) { eof_ = true; throw Error{1, "bzip2 stream damaged or truncated"}; }   // (reported once; the records end there)
+            throw Error{1, "read error"};
+        }
         buf_.resize((size_t)n);
         pos_ = 0;
         if (n == 0) eof_ = true;

@@ -76,7 +76,8 @@ std::vector<GenomeSketch> read_syldb(const std::string& path);                //
 // single-threaded 13 GB bincode read, the dominant cost of a one-sample profile at GTDB scale)
 std::vector<GenomeSketch> read_syldb_views(const std::string& path);
 
-// ---- FASTA/FASTQ (+gzip) records with needletail 0.5.1 semantics: seq() without newlines, id() = whole header ----
+// ---- FASTA/FASTQ (+gzip, +bzip2) records with needletail 0.5.1 semantics: seq() without newlines, id() = whole header ----
+// A file whose first two bytes are "BZ" (needletail's test) is decoded through libbz2, bound with dlopen (formats.cpp Bz2Lib).
 struct FastxRecord { std::string id; std::string seq; };
 class FastxReader {
    public:
@@ -85,6 +86,9 @@ class FastxReader {
     bool next(FastxRecord& rec);                      // false at EOF; throws Error on a malformed record
    private:
     void* gz_ = nullptr;
+    struct Bz2;                                       // the bzip2 decoder over the file's raw bytes (formats.cpp)
+    std::unique_ptr<Bz2> bz_;
+    int fill(char* dst, int cap);                     // the file's text: gzread, or the bzip2 decoder; < 0 on an error
     std::string buf_;
     size_t pos_ = 0;
     bool eof_ = false, fastq_ = false, started_ = false;
