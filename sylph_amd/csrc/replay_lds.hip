@@ -61,7 +61,7 @@ __device__ __forceinline__ uint32_t marker_tag(uint64_t m) { return (uint32_t)((
 // arrival number whenever that difference fits in 54 bits (bm.composite, decided by the host; else — tiny samples — the
 // two-part comparison is spelled out).  Records are then written straight to their sorted slots.
 // Handles buckets with min_n < n <= CAP; larger ones bump `overflow` (when count_overflow) and are left to the caller.
-template <int CAP, int RTPB>
+template <int CAP, int RTPB, bool LEAN>
 __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
                                                              const uint32_t* __restrict__ boff,
                                                              const uint32_t* __restrict__ p_nv, int paired, int no_dedup,
@@ -105,16 +105,36 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     const uint64_t lo_hash = composite ? (((((uint64_t)b << 32) + bm.mult - 1u) / bm.mult) << bm.sh) : 0ull;
     OccRec r[ITEMS];
     uint32_t pidx[ITEMS], rank[ITEMS];
+    // LEAN, 256 slots: the rank loops below also count the members with a smaller HASH — the sorted position of the k-mer's first
+    // occurrence, i.e. its segment head (equal hashes share a sub-range) — so that no scan has to find the heads afterwards
+    constexpr bool SEG_DIRECT = LEAN && CAP == CAP_SMALL;
+    uint32_t seg0[ITEMS];
+#pragma unroll
+    for (int q = 0; q < ITEMS; q++) seg0[q] = 0;
     uint32_t* const s_pidx = reinterpret_cast<uint32_t*>(s_rid);   // (s_rid is free until the sorted records are written)
     const int levels = (int)((n + RTPB - 1) / RTPB);   // lanes of level q hold a record iff q < levels (wave-uniform)
+    if constexpr (LEAN) {
+        // every load of the bucket before the first wait: a lane past the end loads the bucket's last entry again (one line for the
+        // whole wavefront), so there is no branch around the loads and the gather is two load latencies, not one per record
 #pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const uint32_t i = tid + q * RTPB;
-        pidx[q] = 0xFFFFFFFFu;
-        rank[q] = 0;
-        if (i < n) {
-            pidx[q] = perm[first + i];
-            r[q] = recs[pidx[q]];
+        for (int q = 0; q < ITEMS; q++) pidx[q] = perm[first + min(tid + q * RTPB, n - 1u)];
+#pragma unroll
+        for (int q = 0; q < ITEMS; q++) r[q] = recs[pidx[q]];
+#pragma unroll
+        for (int q = 0; q < ITEMS; q++) {
+            rank[q] = 0;
+            if (tid + q * RTPB >= n) pidx[q] = 0xFFFFFFFFu;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < ITEMS; q++) {
+            const uint32_t i = tid + q * RTPB;
+            pidx[q] = 0xFFFFFFFFu;
+            rank[q] = 0;
+            if (i < n) {
+                pidx[q] = perm[first + i];
+                r[q] = recs[pidx[q]];
+            }
         }
     }
     if (composite) {
@@ -136,6 +156,8 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         unsigned long long* const s_min = reinterpret_cast<unsigned long long*>(s_hash);
         unsigned long long* const s_max = reinterpret_cast<unsigned long long*>(s_rid);
         for (uint32_t t = tid; t <= (uint32_t)CAP; t += RTPB) s_cnt[t] = 0;
+        if constexpr (LEAN)      // (the placement's counters too: s_seg is not written before the segments)
+            for (uint32_t t = tid; t < (uint32_t)CAP / 2; t += RTPB) reinterpret_cast<uint32_t*>(s_seg)[t] = 0;
         if constexpr (TWO_LEVEL)
             for (uint32_t t = tid; t < (uint32_t)CAP; t += RTPB) { s_min[t] = ~0ull; s_max[t] = 0ull; }
         __syncthreads();
@@ -221,8 +243,10 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         // place (cursor = a second counter array would cost LDS: take places from the END of each sub-range instead, counting the
         // start words' neighbours down is not possible either — so the places come from s_seg, which is free until the segments)
         uint16_t* const s_fill = s_seg;                               // members placed so far per sub-range (<= CAP: 16 bits do)
-        for (uint32_t t = tid; t < (uint32_t)CAP; t += RTPB) s_fill[t] = 0;
-        __syncthreads();
+        if constexpr (!LEAN) {
+            for (uint32_t t = tid; t < (uint32_t)CAP; t += RTPB) s_fill[t] = 0;
+            __syncthreads();
+        }
         // ranking key of an occurrence inside its sub-range: (hash - a lower bound of the sub-range's hashes, index) in one word
         // when the host found room for both (rank_bits > 0), else the hash with the indices in a second array
         uint64_t rkey[ITEMS];
@@ -254,7 +278,19 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
                 if (i < n) {
                     const uint32_t lo = starts[bin[q]], hi = starts[bin[q] + 1];
                     uint32_t smaller = 0;
-                    for (uint32_t p = lo; p < hi; p++) smaller += s_key[p] < rkey[q] ? 1u : 0u;
+                    if constexpr (SEG_DIRECT) {
+                        // (key < hkey <=> smaller hash: the index sits below rank_bits)
+                        const uint64_t hkey = rkey[q] & ~((1ull << rank_bits) - 1ull);
+                        uint32_t below = 0;
+                        for (uint32_t p = lo; p < hi; p++) {
+                            const uint64_t kp = s_key[p];
+                            smaller += kp < rkey[q] ? 1u : 0u;
+                            below += kp < hkey ? 1u : 0u;
+                        }
+                        seg0[q] = lo + below;
+                    } else {
+                        for (uint32_t p = lo; p < hi; p++) smaller += s_key[p] < rkey[q] ? 1u : 0u;
+                    }
                     rank[q] = lo + smaller;
                 }
             }
@@ -264,12 +300,14 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
                 const uint32_t i = tid + q * RTPB;
                 if (i < n) {
                     const uint32_t lo = starts[bin[q]], hi = starts[bin[q] + 1];
-                    uint32_t smaller = 0;
+                    uint32_t smaller = 0, below = 0;
                     for (uint32_t p = lo; p < hi; p++) {
                         const uint64_t kp = s_key[p];
                         smaller += (kp < r[q].hash || (kp == r[q].hash && s_pidx[p] < pidx[q])) ? 1u : 0u;
+                        if constexpr (SEG_DIRECT) below += kp < r[q].hash ? 1u : 0u;
                     }
                     rank[q] = lo + smaller;
+                    seg0[q] = lo + below;
                 }
             }
         }
@@ -302,8 +340,10 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             const uint64_t kj = s_key[j];
 #pragma unroll
             for (int q = 0; q < ITEMS; q++)
-                if (q < levels && tid + q * RTPB < n)
+                if (q < levels && tid + q * RTPB < n) {
                     rank[q] += ((kj < r[q].hash) || (kj == r[q].hash && (uint32_t)s_arr[j] < arrival[q])) ? 1u : 0u;
+                    if constexpr (SEG_DIRECT) seg0[q] += kj < r[q].hash ? 1u : 0u;
+                }
         }
     }
     __syncthreads();                      // every lane is done with s_key (= s_m0), s_pidx (= s_rid), the counters (= s_m1, s_seg, s_a)
@@ -313,6 +353,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         if (i < n) {
             const uint32_t d = rank[q];
             s_hash[d] = r[q].hash; s_rid[d] = r[q].rid; s_m0[d] = r[q].m0; s_m1[d] = r[q].m1;
+            if constexpr (SEG_DIRECT) s_seg[d] = (uint16_t)seg0[q];
         }
     }
     __syncthreads();
@@ -324,6 +365,14 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     uint32_t heads = 0, last_head = 0;
     bool has_head = false;
     uint8_t headbits = 0;
+    if constexpr (SEG_DIRECT) {
+        // s_seg came with the sorted records: a head is a position that is its own segment's start
+        for (uint32_t t = 0; t < items; t++) {
+            const uint32_t j = j0 + t;
+            if (j >= n) break;
+            if ((uint32_t)s_seg[j] == j) { heads++; headbits |= (uint8_t)(1u << t); }
+        }
+    } else {
     for (uint32_t t = 0; t < items; t++) {
         const uint32_t j = j0 + t;
         if (j >= n) break;
@@ -358,12 +407,14 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         }
     }
     __syncthreads();
+    }
     constexpr bool HASHED = CAP != CAP_SMALL;
     constexpr uint32_t MARKER_TAB = 4 * CAP;    // slots of the marker table: 2 x (2 entries per occurrence)
     if constexpr (!HASHED) {
         // a long k-mer segment of occurrences that carry markers: not for the quadratic marker test below (reads above 400 bases
         // carry none — the test does not run for them, however deep the k-mer)
-        if (!no_dedup) {
+        // (LEAN: a composite bucket got here only if no sub-range held SEG_LIMIT occurrences — every k-mer is shallower)
+        if (!no_dedup && !(LEAN && composite)) {
             __shared__ uint32_t s_longest;
             if (tid == 0) s_longest = 0;
             __syncthreads();
@@ -524,9 +575,36 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     if (dbg_stage == 3) { if (tid == 0) n_distinct[b] = 0; return; }
     // ---- P_i = would-be-counted occurrences before i in its k-mer; counted_i (cut-off rule, sketch.rs:706) ------
     // two block scans in total: (would-count, heads) packed 16+16 bits here, (counted, removed) below; sums <= CAP
+    uint32_t base_h = 0, total_heads = 0, total_removed = 0;
+    if (LEAN && CAP <= 512 && cutoff == 0) {
+        // pairs (no cut-off): counted = would-count, so ONE block scan of (would-count, heads, removed) packed 10+10+10 bits (sums <= CAP
+        // <= 512) gives both the distinct indices and Ec; the per-k-mer prefix P is not needed
+        uint32_t my_removed = 0;
+        for (uint32_t t = 0; t < items; t++) {
+            const uint32_t j = j0 + t;
+            if (j >= n) break;
+            if (!(s_fl[j] & 1) && !((ubits >> t) & 1)) my_removed++;
+        }
+        uint32_t tot = 0;
+        const uint32_t base = block_excl_sum<RTPB>(my_u | (heads << 10) | (my_removed << 20), s_wave, &tot);
+        base_h = (base >> 10) & 0x3FFu;
+        total_heads = (tot >> 10) & 0x3FFu;
+        total_removed = tot >> 20;
+        uint32_t run = base & 0x3FFu;
+        for (uint32_t t = 0; t < items; t++) {
+            const uint32_t j = j0 + t;
+            if (j >= n) break;
+            s_b[j] = (uint16_t)run;             // Ec[j] = Eu[j]
+            if (ubits & (1u << t)) run++;
+        }
+        if (j0 < n && j0 + items >= n) s_b[n] = (uint16_t)run;
+        __syncthreads();
+    } else {
     uint32_t tot_uh = 0;
     const uint32_t base_uh = block_excl_sum<RTPB>(my_u | (heads << 16), s_wave, &tot_uh);
-    const uint32_t base_u = base_uh & 0xFFFFu, base_h = base_uh >> 16, total_heads = tot_uh >> 16;
+    const uint32_t base_u = base_uh & 0xFFFFu;
+    base_h = base_uh >> 16;
+    total_heads = tot_uh >> 16;
     {
         uint32_t run = base_u;
         for (uint32_t t = 0; t < items; t++) {
@@ -551,7 +629,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     }
     uint32_t tot_cr = 0;
     const uint32_t base_c = block_excl_sum<RTPB>(my_c | (my_removed << 16), s_wave, &tot_cr) & 0xFFFFu;
-    const uint32_t total_removed = tot_cr >> 16;
+    total_removed = tot_cr >> 16;
     {
         uint32_t rc = base_c;
         for (uint32_t t = 0; t < items; t++) {
@@ -563,6 +641,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         if (j0 < n && j0 + items >= n) s_b[n] = (uint16_t)rc;   // Ec[n], written by the lane that owns the last position
     }
     __syncthreads();
+    }
     // heads emit (k-mer, count); the distinct index of a head = number of heads before it
     if constexpr (HASHED) {
         // segment end = position of the next head: the heads publish their positions by distinct index (s_a is free by now)
@@ -609,7 +688,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     if (tid == 0) { n_distinct[b] = total_heads; removed_b[b] = total_removed; }
 }
 
-template <int CAP, int RTPB>
+template <int CAP, int RTPB, bool LEAN>
 __global__ __launch_bounds__(RTPB) void bucket_replay_kernel(const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
                                                              const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv,
                                                              int paired, int no_dedup, uint32_t cutoff, BucketMap bm,
@@ -618,7 +697,7 @@ __global__ __launch_bounds__(RTPB) void bucket_replay_kernel(const OccRec* __res
                                                              uint32_t* __restrict__ overflow, uint32_t* __restrict__ mid_list,
                                                              uint32_t* __restrict__ large_list, uint32_t* __restrict__ ovf_list,
                                                              int dbg_stage) {
-    replay_bucket<CAP, RTPB>(blockIdx.x, recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct, removed_b,
+    replay_bucket<CAP, RTPB, LEAN>(blockIdx.x, recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct, removed_b,
                              overflow, mid_list, large_list, ovf_list, dbg_stage);
 }
 
@@ -758,7 +837,7 @@ __global__ __launch_bounds__(RTPB) void bucket_count_list_kernel(const uint64_t*
 }
 
 // second configuration: a fixed, small grid walks the (usually empty) list of buckets the first one queued
-template <int CAP, int RTPB>
+template <int CAP, int RTPB, bool LEAN>
 __global__ __launch_bounds__(RTPB) void bucket_replay_list_kernel(const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
                                                                   const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv,
                                                                   int paired, int no_dedup, uint32_t cutoff, BucketMap bm,
@@ -769,7 +848,7 @@ __global__ __launch_bounds__(RTPB) void bucket_replay_list_kernel(const OccRec* 
                                                                   int dbg_stage) {
     const uint32_t n_listed = my_list[0];
     for (uint32_t i = blockIdx.x; i < n_listed; i += gridDim.x) {
-        replay_bucket<CAP, RTPB>(my_list[1 + i], recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct,
+        replay_bucket<CAP, RTPB, LEAN>(my_list[1 + i], recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct,
                                  removed_b, overflow, nullptr, large_list, ovf_list, dbg_stage);
         __syncthreads();   // the LDS arrays are reused by the next bucket
     }
@@ -984,6 +1063,15 @@ bool finish_bucketed(sylph_sketch* sk) {
     // not fit the sub-range arithmetic get their records written and take the usual kernels
     if (!slotted && sk->n_plain && !(sk->n_plain == sk->n_occ && bm.composite)) materialise_plain_records(sk);
     bool plain = !slotted && sk->n_plain != 0;
+    // Run-time shape switches (A/B of one build, profiles/r07_ab_tail.txt).  SYLPH_HIP_REPLAY_LEAN=0: round 6's replay (one load round trip
+    // per record of the gather, a max-scan for the segment heads, two block scans for pairs, the long-segment recheck).
+    // SYLPH_HIP_PART_TILE_BLOCKS / SYLPH_HIP_PART_STAGE_PAIRS: seeding blocks per partition tile and pairs the scatter stages in LDS for the
+    // slotted sample — round 6 had 16 / 4096 (36.7 KiB of LDS per scatter workgroup, which waits for room beside the seeding kernel).
+    static const bool lean = [] { const char* e = getenv("SYLPH_HIP_REPLAY_LEAN"); return e ? atoi(e) != 0 : true; }();
+    static const uint32_t tile_blocks = [] { const char* e = getenv("SYLPH_HIP_PART_TILE_BLOCKS"); return e ? (uint32_t)std::max(1, std::min(32, atoi(e))) : BLK_PER_TILE; }();
+    // (2048 pairs: 16 KiB + the range counters, 20 KiB per workgroup; a tile holds ~3,000 occurrences, the rest goes out directly —
+    //  pipelined exact set +0.4..0.9 % over 4096 on top of the lean replay, 1536 and 1024 within noise of it: profiles/r07_ab_tail.txt)
+    static const uint32_t stage_pairs = [] { const char* e = getenv("SYLPH_HIP_PART_STAGE_PAIRS"); return e ? (uint32_t)std::max(256, std::min(8192, atoi(e))) : 2048u; }();
     PartIn in{};
     in.slotted = slotted ? 1 : 0;
     in.key_sh = bm.sh;
@@ -994,8 +1082,9 @@ bool finish_bucketed(sylph_sketch* sk) {
         in.n_blk = sk->pend.n_blk;
         in.slot_cap = sk->pend.slot_cap;
         in.blk_count = sk->slot_meta.as<uint32_t>() + (sk->pend.n_blk + 1);   // (layout: reads.hip SlotMeta)
-        in.blk_per_tile = BLK_PER_TILE;
-        n_tiles = (in.n_blk + BLK_PER_TILE - 1) / BLK_PER_TILE;
+        in.blk_per_tile = tile_blocks;
+        in.stage_pairs = stage_pairs;
+        n_tiles = (in.n_blk + tile_blocks - 1) / tile_blocks;
         recs = sk->slot_rec.as<OccRec>();
     } else {
         in.hash = sk->hash.as<uint64_t>();
@@ -1053,7 +1142,8 @@ bool finish_bucketed(sylph_sketch* sk) {
                                    sorted_hash, (const uint32_t*)nullptr, boff, d_nv, bm, b_tmpk.as<uint64_t>(),
                                    b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, large_list, ovf_list);
             else
-                hipLaunchKernelGGL((bucket_replay_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream,
+                hipLaunchKernelGGL((lean ? bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, true> : bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, false>),
+                                   dim3(B), dim3(RTPB_SMALL), 0, ctx->stream,
                                    recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired, sk->dedup_mode(), cutoff, bm,
                                    b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, mid_list, large_list,
                                    ovf_list, dbg);
@@ -1122,12 +1212,14 @@ bool finish_bucketed(sylph_sketch* sk) {
                                        b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, large_list, ovf_list);
             } else {
             if (host.n_mid)
-                hipLaunchKernelGGL((bucket_replay_list_kernel<CAP_MID, RTPB_MID>), dim3(std::min<uint32_t>(host.n_mid, 1280u)),
+                hipLaunchKernelGGL((lean ? bucket_replay_list_kernel<CAP_MID, RTPB_MID, true> : bucket_replay_list_kernel<CAP_MID, RTPB_MID, false>),
+                                   dim3(std::min<uint32_t>(host.n_mid, 1280u)),
                                    dim3(RTPB_MID), 0, ctx->stream, recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired,
                                    sk->dedup_mode(), cutoff, bm, b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b,
                                    d_overflow, mid_list, large_list, ovf_list, dbg);
             if (host.n_large)
-                hipLaunchKernelGGL((bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE>), dim3(std::min<uint32_t>(host.n_large, 512u)),
+                hipLaunchKernelGGL((lean ? bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE, true> : bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE, false>),
+                                   dim3(std::min<uint32_t>(host.n_large, 512u)),
                                    dim3(RTPB_LARGE), 0, ctx->stream, recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired,
                                    sk->dedup_mode(), cutoff, bm, b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b,
                                    d_overflow, large_list, large_list, ovf_list, dbg);
