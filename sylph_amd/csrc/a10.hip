@@ -302,19 +302,18 @@ __global__ __launch_bounds__(A10_TPB) void a10_debug_kernel(Occs o, Filters F, u
 
 // ---- the partitioned pass (round 5): one filter, no device-wide atomics -------------------------------------------------------
 // While the sample stays inside filter 0 (at most `capacity` operations: 1 Gbp of pairs has 8 M against the reference's 10^7),
-// "first operation of its class" needs no table at all: the operations are SORTED by class — the two-level partition that groups the
-// occurrences by k-mer hash for the replay (partition.h) moves one 8-byte word per operation, {upper 32 bits of the mixed class key |
-// operation id = 2 x slot + marker}, into ~128-operation buckets of equal class-hash ranges — and one workgroup per bucket finds the
-// words that share their upper half with another word (exact duplicates: 2-4 % of a sample; chance: 2^-16 per pair of a bucket).
+// "first operation of its class" needs no table at all: the operations are GROUPED by class — the coarse level of the partition that
+// groups the occurrences by k-mer hash for the replay (partition.h) moves one 8-byte word per operation, {upper 32 bits of the mixed
+// class key | operation id = 2 x slot + marker}, into ~8,000-operation ranges of equal class-hash width — and the workgroups of a range
+// find the words that share their upper half with another word (exact duplicates: 2-4 % of a sample; chance: 2^-16 per pair of words).
 // Only those fetch their occurrence record, compute the exact class key and their place in the walk (op_key), and the ones that are
 // not the earliest of their class set RID_A10_BIT — an atomic OR on ~3 % of the records instead of two atomics and a load per
 // operation on a 256 MB table.  Skipped mate-2 occurrences (sketch.rs:852) take part here although the walk never sees them: their
 // items are those of the mate-1 occurrence of the same k-mer in the same pair, which precedes them — they are never the first of a
 // class, change no other operation's answer, and the replay drops them before it looks at the mark.
-// What the pass cannot do is tell by itself that one filter was enough: it leaves {buckets too full for the workgroup, operations
+// What the pass cannot do is tell by itself that one filter was enough: it leaves {ranges too full for the workgroup, operations
 // found} in two device words, the caller reads them with whatever it reads anyway (finish_bucketed's tail block), and a sample with
-// more operations than the capacity — or thousands of copies of one item in one bucket — is marked again by the phase walk above.
-constexpr int RES_CAP = 256, RES_TPB = 128;
+// more operations than the capacity — or thousands of copies of one item — is marked again by the phase walk above.
 constexpr uint32_t OPS_BLK_PER_TILE = 8;           // two words per slot: half the blocks per partition tile
 
 struct OpsIn { const uint64_t* hash; const OccRec* recs; const uint32_t* blk_count; uint32_t n_dense, n_blk, slot_cap; int slotted; };
@@ -334,7 +333,7 @@ __global__ __launch_bounds__(64) void a10_ops_slots_kernel(OpsIn in, Filter d, u
 }
 // The same for a whole partition TILE of the slots (in.blk_per_tile blocks of the seeding kernel) per workgroup, counting the words per
 // class range on the way: hist[c * n_tiles + t] is what part_hist_kernel would find in a pass of its own over the 64 MB of words
-// (round 6, one-level pass only; eight groups of 32 lanes walk eight blocks at a time, as partition.h's for_tile_entries does)
+// (round 6; eight groups of 32 lanes walk eight blocks at a time, as partition.h's for_tile_entries does)
 __global__ __launch_bounds__(PART_TPB) void a10_ops_tile_kernel(OpsIn in, Filter d, uint32_t blk_per_tile, BucketMap bm, uint32_t n_tiles, ulonglong2* __restrict__ ops,
                                                                 uint32_t* __restrict__ hist, uint32_t* __restrict__ tail) {
     __shared__ uint32_t s_h[MAX_COARSE];
@@ -367,105 +366,11 @@ __global__ __launch_bounds__(256) void a10_ops_dense_kernel(OpsIn in, Filter d, 
     ops[i] = op_words(d, in.recs[i], in.hash[i] != INVALID_HASH, i);
 }
 
-// One workgroup = one bucket of class hashes.  Sub-range counting sort as in the replay (the words are uniform over the bucket's
-// range: RES_CAP sub-ranges hold half a word each, equal upper halves share one); candidates = words with an equal upper half in
-// their sub-range; those resolve through their records.
-__global__ __launch_bounds__(RES_TPB) void a10_resolve_kernel(const uint64_t* __restrict__ sorted, const uint32_t* __restrict__ boff, BucketMap bm,
-                                                              Filter d, OccRec* __restrict__ recs, uint32_t* __restrict__ tail) {
-    constexpr int ITEMS = RES_CAP / RES_TPB;
-    __shared__ uint64_t s_w[RES_CAP], s_g[RES_CAP], s_k[RES_CAP];
-    __shared__ uint32_t s_cnt[RES_CAP + 1];
-    __shared__ __attribute__((aligned(8))) uint16_t s_fill[RES_CAP];
-    __shared__ uint32_t s_wave[RES_TPB / 64];
-    const uint32_t tid = threadIdx.x, b = blockIdx.x;
-    const uint32_t first = boff[b], n = boff[b + 1] - first;
-    if (b == 0 && tid == 0) tail[1] = boff[bm.B];             // operations found (every valid word of the layout)
-    if (n == 0) return;
-    if (n > (uint32_t)RES_CAP) { if (tid == 0) atomicAdd(&tail[0], 1u); return; }
-    const uint32_t lo_key = (uint32_t)((((uint64_t)b << 32) + bm.mult - 1u) / bm.mult);      // smallest 32-bit key of the bucket
-    const uint32_t sub_mult = bm.sub_mult[0];
-    uint64_t h[ITEMS];
-    uint32_t sub[ITEMS], place[ITEMS];
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const uint32_t i = tid + q * RES_TPB;
-        h[q] = i < n ? sorted[first + i] : 0ull;
-    }
-    for (uint32_t t = tid; t <= (uint32_t)RES_CAP; t += RES_TPB) s_cnt[t] = 0;
-    for (uint32_t t = tid; t < (uint32_t)RES_CAP; t += RES_TPB) s_fill[t] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const uint32_t i = tid + q * RES_TPB;
-        sub[q] = 0;
-        if (i < n) {
-            const uint32_t res = (uint32_t)(h[q] >> 32) - lo_key;
-            sub[q] = sub_mult ? min(__umulhi(res, sub_mult), (uint32_t)RES_CAP - 1u) : min(res, (uint32_t)RES_CAP - 1u);
-            atomicAdd(&s_cnt[sub[q]], 1u);
-        }
-    }
-    __syncthreads();
-    {
-        uint32_t v[ITEMS], sum = 0;
-#pragma unroll
-        for (int e = 0; e < ITEMS; e++) { v[e] = s_cnt[tid * ITEMS + e]; sum += v[e]; }
-        uint32_t run = block_excl_sum<RES_TPB>(sum, s_wave, nullptr);
-#pragma unroll
-        for (int e = 0; e < ITEMS; e++) { s_cnt[tid * ITEMS + e] = run; run += v[e]; }
-        if (tid == RES_TPB - 1) s_cnt[RES_CAP] = run;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const uint32_t i = tid + q * RES_TPB;
-        place[q] = 0;
-        if (i < n) {
-            uint32_t* const w = reinterpret_cast<uint32_t*>(s_fill) + (sub[q] >> 1);
-            const uint32_t old = atomicAdd(w, (sub[q] & 1u) ? 65536u : 1u);
-            place[q] = s_cnt[sub[q]] + ((sub[q] & 1u) ? (old >> 16) : (old & 0xFFFFu));
-            s_w[place[q]] = h[q];
-        }
-    }
-    __syncthreads();
-    bool cand[ITEMS];
-    uint64_t g[ITEMS], key[ITEMS];
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        const uint32_t i = tid + q * RES_TPB;
-        cand[q] = false;
-        g[q] = ~0ull;
-        key[q] = 0;
-        if (i < n) {
-            const uint32_t lo = s_cnt[sub[q]], hi = s_cnt[sub[q] + 1], up = (uint32_t)(h[q] >> 32);
-            for (uint32_t p = lo; p < hi; p++) cand[q] |= p != place[q] && (uint32_t)(s_w[p] >> 32) == up;
-            if (cand[q]) {
-                const uint32_t opid = (uint32_t)h[q];
-                const OccRec r = recs[opid >> 1];
-                g[q] = reduced_key(d, item_hash(r.hash, (opid & 1u) ? r.m1 : r.m0));      // < 2^63: never the ~0 of a word that is no candidate
-                key[q] = op_key(r.rid, opid & 1u);
-            }
-            s_g[place[q]] = g[q];
-            s_k[place[q]] = key[q];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < ITEMS; q++) {
-        if (!cand[q]) continue;
-        const uint32_t lo = s_cnt[sub[q]], hi = s_cnt[sub[q] + 1];
-        bool contained = false;
-        for (uint32_t p = lo; p < hi; p++) contained |= s_g[p] == g[q] && s_k[p] < key[q];
-        // (the two operations of an occurrence may both be contained, from two workgroups: the OR commutes; readers of the rid in
-        //  this kernel look at its record and rank bits only)
-        if (contained) atomicOr(reinterpret_cast<uint32_t*>(&recs[(uint32_t)h[q] >> 1].rid) + 1, (uint32_t)(RID_A10_BIT >> 32));
-    }
-}
-
 // ---- one partition level (round 6) ------------------------------------------------------------------------------------------
-// The fine level above costs a read and a write of every word (part_fine) before the resolve kernel reads them a third time.
-// Here the words stay where part_scatter left them, grouped by coarse range (~8,000 words), and the words that share their upper half
-// with another one are found WITHOUT sorting them.  The upper halves are uniform over the range, so `(upper half - lowest of the
-// range) x slots / width` is a direct-mapped slot of a bit table in LDS:
+// (Round 5 went on to a fine partition level and one workgroup per ~128-word bucket: a read and a write of every word more.  Measured,
+// removed: profiles/r06_ab_a10.txt.)  The words stay where part_scatter left them, grouped by coarse range (~8,000 words), and the
+// words that share their upper half with another one are found WITHOUT sorting them.  The upper halves are uniform over the range,
+// so `(upper half - lowest of the range) x slots / width` is a direct-mapped slot of a bit table in LDS:
 //   pass 1  every word sets its slot's bit; a word that finds it set is a SECOND ARRIVAL (every duplicate but one of each group, and by
 //           chance words / 2 slots = 1.5 % of the rest): its upper half goes into a small open-addressing set;
 //   pass 2  every word asks the set for its upper half: the ones found are the candidates (all words with an equal upper half — true
@@ -481,7 +386,7 @@ __global__ __launch_bounds__(RES_TPB) void a10_resolve_kernel(const uint64_t* __
 // the passes (112 VGPRs) slower again.
 // A workgroup with more second arrivals or candidates than its lists take (heavily duplicated samples) cuts its part into P slices,
 // resolved one after the other (equal classes share a slot); a slice that is still too full — ~a thousand copies of one item —
-// bumps the verdict word as the two-level pass does.
+// bumps the verdict word.
 constexpr uint32_t RNG_SLOT_BITS = 17, RNG_SLOTS = 1u << RNG_SLOT_BITS;     // per workgroup, one bit each: 16 KB
 constexpr uint32_t RNG_CAND = 512, RNG_TAB = 1024, RNG_TAB_BITS = 10;       // candidates per slice, table entries (both tables)
 constexpr uint32_t RNG_WORDS = 8192;                                       // words per range aimed for
@@ -502,7 +407,7 @@ __global__ __launch_bounds__(TPB) void a10_range_kernel(const uint64_t* __restri
     if (c >= C) return;                                       // (padding of the grid to whole groups of 8 ranges)
     const uint32_t lo = cbase[c], hi = cbase[c + 1];
     if (hi == lo) return;
-    const uint32_t lo_key = (uint32_t)((((uint64_t)c << 32) + mult - 1u) / mult);      // smallest upper half of the range
+    const uint32_t lo_key = (uint32_t)bucket_lo_hash(c, mult, 0);      // smallest upper half of the range
     const uint32_t all_slots = split << RNG_SLOT_BITS;
     unsigned long long* const t_key = reinterpret_cast<unsigned long long*>(s_bits);              // [RNG_TAB] class keys (~0: free)
     unsigned long long* const t_min = reinterpret_cast<unsigned long long*>(s_bits) + RNG_TAB;    // [RNG_TAB] earliest place of the class
@@ -658,16 +563,13 @@ static void a10_mark_partitioned(sylph_sketch* sk) {
     HostPhase ph(ctx, "finish: a10 filter marks (partitioned)");
     sk->a10_tail.reserve(16);
     uint32_t* tail = sk->a10_tail.as<uint32_t>();
-    DevBuf b_ops(ctx), b_pairs(ctx), b_sorted(ctx), b_hist(ctx), b_boff(ctx);
+    DevBuf b_ops(ctx), b_pairs(ctx), b_hist(ctx);
     b_ops.reserve(n_slots * 16);
     b_pairs.reserve(n_slots * 16);
     const Filter f0 = filter_geometry(sk, 0);
-    // buckets: equal ranges of the words' upper 32 bits, ~bucket_target operations each
-    static const int env_levels = [] { const char* e = getenv("SYLPH_HIP_A10_LEVELS"); return e ? atoi(e) : 1; }();
-    const bool one_level = env_levels != 2;
+    // ranges: equal ranges of the words' upper 32 bits, ~RNG_WORDS operations each
     static const uint32_t env_words = [] { const char* e = getenv("SYLPH_HIP_A10_RANGE_WORDS"); return e ? (uint32_t)std::max(512, std::min(1 << 20, atoi(e))) : RNG_WORDS; }();
-    const uint32_t B = one_level ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, 2 * n_expect / env_words), MAX_COARSE)
-                                 : (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, 2 * n_expect / ctx->bucket_target), 1u << 24);
+    const uint32_t B = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(1, 2 * n_expect / env_words), MAX_COARSE);
     BucketMap bm{};
     bm.sh = 32;
     bm.mult = B;                                                   // (B << 32) / 2^32
@@ -675,9 +577,7 @@ static void a10_mark_partitioned(sylph_sketch* sk) {
     bm.composite = 1;
     const uint64_t range = (0x100000000ull + B - 1) / B + 1;       // widest bucket in key units
     bm.range_hs = (uint32_t)std::min<uint64_t>(range, 0xFFFFFFFFull);
-    bm.sub_mult[0] = range > (uint64_t)RES_CAP ? (uint32_t)(((uint64_t)RES_CAP << 32) / range) : 0u;
-    if (!one_level) b_sorted.reserve(n_slots * 16);
-    const PartGeom geom = one_level ? PartGeom{0, B} : part_geometry(B);
+    const PartGeom geom{0, B};
     OpsIn oin{};
     PartIn in{};
     in.key_sh = 32;
@@ -696,34 +596,26 @@ static void a10_mark_partitioned(sylph_sketch* sk) {
         n_tiles = (uint32_t)((2 * sk->n_occ + in.tile_entries - 1) / in.tile_entries);
     }
     static const uint32_t env_stage = [] { const char* e = getenv("SYLPH_HIP_A10_STAGE_PAIRS"); return e ? (uint32_t)std::max(256, std::min(8192, atoi(e))) : 0u; }();
-    if (one_level) in.stage_pairs = env_stage;
+    in.stage_pairs = env_stage;
     in.hash = b_ops.as<uint64_t>();
     b_hist.reserve(part_hist_words(geom, n_tiles) * 4);
-    b_boff.reserve(((size_t)B + 2) * 4);
     ScopedKernelTimer t(ctx, "a10");
     static const bool env_fused_hist = [] { const char* e = getenv("SYLPH_HIP_A10_FUSED_HIST"); return !e || atoi(e) != 0; }();
-    const bool fused_hist = slotted && one_level && env_fused_hist;         // the operation words' kernel also counts them per (range, tile)
+    const bool fused_hist = slotted && env_fused_hist;         // the operation words' kernel also counts them per (range, tile)
     if (fused_hist)
         hipLaunchKernelGGL(a10_ops_tile_kernel, dim3(((n_tiles + 7) / 8) * 8), dim3(PART_TPB), 0, ctx->stream, oin, f0, in.blk_per_tile, bm, n_tiles, b_ops.as<ulonglong2>(),
                            b_hist.as<uint32_t>(), tail);
     else if (slotted) hipLaunchKernelGGL(a10_ops_slots_kernel, dim3(oin.n_blk), dim3(64), 0, ctx->stream, oin, f0, b_ops.as<ulonglong2>(), tail);
     else hipLaunchKernelGGL(a10_ops_dense_kernel, dim3((uint32_t)((sk->n_occ + 255) / 256)), dim3(256), 0, ctx->stream, oin, f0, b_ops.as<ulonglong2>(), tail);
-    if (one_level) {
-        // words grouped by range where the scatter left them; slot of a word inside its range = (upper half - lowest of the range) x slots / width
-        launch_partition_coarse(ctx, in, bm, n_tiles, b_hist.as<uint32_t>(), b_pairs.as<uint2>(), fused_hist);
-        static const int env_split = [] { const char* e = getenv("SYLPH_HIP_A10_RANGE_SPLIT"); return e ? std::max(1, std::min(8, atoi(e))) : 2; }();
-        static const int env_pad = [] { const char* e = getenv("SYLPH_HIP_A10_RANGE_LDS_PAD"); return e ? atoi(e) : 0; }();     // (A/B: LDS footprint)
-        const uint32_t split = (uint32_t)env_split;
-        const uint64_t all_slots = (uint64_t)split << RNG_SLOT_BITS;
-        const uint32_t slot_mult = range > all_slots ? (uint32_t)((all_slots << 32) / range) : 0u;
-        hipLaunchKernelGGL(a10_range_kernel<256>, dim3(((B + 7) / 8) * 8 * split), dim3(256), (size_t)env_pad, ctx->stream, b_pairs.as<uint64_t>(),
-                           part_cbase(b_hist.as<uint32_t>(), B, n_tiles), B, bm.mult, slot_mult, split, f0, const_cast<OccRec*>(oin.recs), tail);
-    } else {
-        launch_partition(ctx, in, bm, geom, n_tiles, 2 * n_expect, b_hist.as<uint32_t>(), b_pairs.as<uint2>(), b_boff.as<uint32_t>(), nullptr,
-                         b_sorted.as<uint64_t>(), nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-        hipLaunchKernelGGL(a10_resolve_kernel, dim3(B), dim3(RES_TPB), 0, ctx->stream, b_sorted.as<uint64_t>(), b_boff.as<uint32_t>(), bm, f0,
-                           const_cast<OccRec*>(oin.recs), tail);
-    }
+    // words grouped by range where the scatter left them; slot of a word inside its range = (upper half - lowest of the range) x slots / width
+    launch_partition_coarse(ctx, in, bm, n_tiles, b_hist.as<uint32_t>(), b_pairs.as<uint2>(), fused_hist);
+    static const int env_split = [] { const char* e = getenv("SYLPH_HIP_A10_RANGE_SPLIT"); return e ? std::max(1, std::min(8, atoi(e))) : 2; }();
+    static const int env_pad = [] { const char* e = getenv("SYLPH_HIP_A10_RANGE_LDS_PAD"); return e ? atoi(e) : 0; }();     // (A/B: LDS footprint)
+    const uint32_t split = (uint32_t)env_split;
+    const uint64_t all_slots = (uint64_t)split << RNG_SLOT_BITS;
+    const uint32_t slot_mult = range > all_slots ? (uint32_t)((all_slots << 32) / range) : 0u;
+    hipLaunchKernelGGL(a10_range_kernel<256>, dim3(((B + 7) / 8) * 8 * split), dim3(256), (size_t)env_pad, ctx->stream, b_pairs.as<uint64_t>(),
+                       part_cbase(b_hist.as<uint32_t>(), B, n_tiles), B, bm.mult, slot_mult, split, f0, const_cast<OccRec*>(oin.recs), tail);
     SY_HIP(hipGetLastError());
     sk->a10_state = 1;
     if (ctx->profile) ctx->stats["a10_part"].launches++;              // (tests ask sylph_ctx_kernel_stats which pass ran)

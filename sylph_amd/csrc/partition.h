@@ -19,6 +19,18 @@ namespace {
 struct BucketMap { int sh; uint32_t mult; uint32_t B; int composite; uint32_t range_hs; uint32_t sub_mult[3]; uint32_t sub_width[3]; int rank_bits[3]; };
 
 __device__ __forceinline__ uint32_t bucket_of_key(uint32_t key, const BucketMap m) { return min(__umulhi(key, m.mult), m.B - 1u); }
+// lowest hash that maps to bucket b: key >= ceil(b * 2^32 / mult), the exact inverse of bucket_of_key
+__device__ __forceinline__ uint64_t bucket_lo_hash(uint32_t b, uint32_t mult, int sh) { return ((((uint64_t)b << 32) + mult - 1u) / mult) << sh; }
+// sub-range (of `cap`) of a key's distance `res` to its bucket's lowest key; sub_mult = BucketMap::sub_mult of the configuration
+__device__ __forceinline__ uint32_t sub_range_of(uint32_t res, uint32_t sub_mult, uint32_t cap) {
+    return sub_mult ? min(__umulhi(res, sub_mult), cap - 1u) : min(res, cap - 1u);
+}
+// The place an entry takes inside its bin: how many took one there before it.  `fill` holds one 16-bit counter per bin, zeroed by the
+// caller (16-bit LDS atomics do not exist: the counter pairs share a word; add 1 or 65536 to the word and take the half).
+__device__ __forceinline__ uint32_t take_place(uint16_t* fill, uint32_t bin) {
+    const uint32_t old = atomicAdd(reinterpret_cast<uint32_t*>(fill) + (bin >> 1), (bin & 1u) ? 65536u : 1u);
+    return (bin & 1u) ? (old >> 16) : (old & 0xFFFFu);
+}
 
 // ---- partition ------------------------------------------------------------------------------------------------------------
 // Where finish() reads the occurrences from: the dense arrays (hash[i], i < n_dense; INVALID_HASH entries are skipped) or the
@@ -276,6 +288,22 @@ __device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_wave,
     }
     if (total) *total = tot;
     return base + x - v;
+}
+
+// Exclusive scan of CAP counters in LDS, CAP / TPB consecutive ones per lane: start[t] = sum of cnt[0 .. t), start[CAP] = their total
+// (start may be cnt).  Returns the largest of the lane's own counters.  The caller's next barrier publishes `start`.
+template <int CAP, int TPB>
+__device__ __forceinline__ uint32_t scan_counters(const uint32_t* cnt, uint32_t* start, uint32_t* s_wave) {
+    constexpr int PER = CAP / TPB;
+    const uint32_t tid = threadIdx.x;
+    uint32_t v[PER], sum = 0, most = 0;
+#pragma unroll
+    for (int e = 0; e < PER; e++) { v[e] = cnt[tid * PER + e]; sum += v[e]; }
+    uint32_t run = block_excl_sum<TPB>(sum, s_wave, nullptr);
+#pragma unroll
+    for (int e = 0; e < PER; e++) { start[tid * PER + e] = run; run += v[e]; most = max(most, v[e]); }
+    if (tid == TPB - 1) start[CAP] = run;
+    return most;
 }
 
 // F = 2^fine_bits buckets per coarse range (about 512 ranges)

@@ -33,9 +33,6 @@ namespace {
 #ifndef SYLPH_REPLAY_TPB
 #define SYLPH_REPLAY_TPB 128
 #endif
-#ifndef SYLPH_REPLAY_TAGS
-#define SYLPH_REPLAY_TAGS 1
-#endif
 constexpr int CAP_SMALL = 256, RTPB_SMALL = SYLPH_REPLAY_TPB;
 constexpr int CAP_MID = 512, RTPB_MID = 256;       // hashed marker test, ~31 KiB of LDS: 5 workgroups per CU
 constexpr int CAP_LARGE = 1024, RTPB_LARGE = 256;   // hashed marker test, ~59 KiB of LDS: 2 workgroups per CU
@@ -45,6 +42,39 @@ constexpr int IDX_BITS = 10;         // arrival index inside a bucket (< CAP_LAR
 // configuration, whose marker test is a hash table in LDS: linear in the bucket size.
 constexpr uint32_t SEG_LIMIT = 96;
 
+
+// What a replay / count workgroup needs besides its bucket: filled once by finish_bucketed and passed to the kernels by value.
+struct ReplayArgs {
+    const OccRec* recs;          // replay: the occurrence records, gathered through perm
+    const uint64_t* hash;        // count (marker-less samples): the hashes — sorted by bucket already when perm is null
+    const uint32_t* perm;        // occurrence indices grouped by bucket
+    const uint32_t* boff;        // boff[b] = first position of bucket b
+    const uint32_t* p_nv;        // number of valid occurrences (= boff[B])
+    int paired, dedup;           // dedup: a DEDUP_* mode
+    uint32_t cutoff;             // 4 for single-end (sketch.rs:937), 0 for pairs
+    BucketMap bm;
+    uint64_t* tmp_k;             // rows of bucket b go to tmp_k / tmp_c [boff[b] ..), n_distinct[b] of them
+    uint32_t* tmp_c;
+    uint32_t* n_distinct;
+    uint32_t* removed_b;
+    uint32_t* overflow;          // FinishTail::overflow
+    uint32_t* mid_list;          // [0] = buckets queued for the CAP_MID configuration, [1..] = their ids; the same for CAP_LARGE ...
+    uint32_t* large_list;
+    uint32_t* ovf_list;          // ... and for the host, which sends those buckets' occurrences through the device-wide path
+    int dbg_stage;
+};
+
+// What the host reads back at the end of a pass: written by table_compact_kernel (`overflow`: by the replay), copied in one piece.
+struct FinishTail {
+    unsigned long long removed;  // duplicates dropped
+    uint32_t overflow;           // buckets with inconsistent bounds (defensive)
+    uint32_t n_seg;              // rows of the table
+    uint32_t n_ovf, n_mid, n_large;   // heads of the three lists
+    uint32_t verdict[2];         // deferred seeding verdict (reads.hip ReadsState: long_record, overflowing blocks)
+    uint32_t a10_words[2];       // verdict of the filter dedup's partitioned pass (a10.hip)
+    uint32_t n_found;            // occurrences the partition found: what a deferred batch's slots really hold
+};
+static_assert(sizeof(FinishTail) == 48, "tail block");
 
 // 15-bit tag of a dedup marker, never 0 (bit 0 set): what the scan over a k-mer's earlier occurrences compares first
 __device__ __forceinline__ uint32_t marker_tag(uint64_t m) { return (uint32_t)((m * 0x9E3779B97F4A7C15ull) >> 49) | 1u; }
@@ -61,21 +91,23 @@ __device__ __forceinline__ uint32_t marker_tag(uint64_t m) { return (uint32_t)((
 // arrival number whenever that difference fits in 54 bits (bm.composite, decided by the host; else — tiny samples — the
 // two-part comparison is spelled out).  Records are then written straight to their sorted slots.
 // Handles buckets with min_n < n <= CAP; larger ones bump `overflow` (when count_overflow) and are left to the caller.
-template <int CAP, int RTPB, bool LEAN>
-__device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
-                                                             const uint32_t* __restrict__ boff,
-                                                             const uint32_t* __restrict__ p_nv, int paired, int no_dedup,
-                                                             uint32_t cutoff, BucketMap bm, uint64_t* __restrict__ tmp_k,
-                                                             uint32_t* __restrict__ tmp_c, uint32_t* __restrict__ n_distinct,
-                                                             uint32_t* __restrict__ removed_b,
-                                                             uint32_t* __restrict__ overflow, uint32_t* __restrict__ mid_list,
-                                                             uint32_t* __restrict__ large_list,
-                                                             uint32_t* __restrict__ ovf_list, int dbg_stage) {
+template <int CAP, int RTPB>
+__device__ __forceinline__ void replay_bucket(const uint32_t b, const ReplayArgs& ra) {
+    const OccRec* __restrict__ recs = ra.recs;
+    const uint32_t* __restrict__ perm = ra.perm;
+    const uint32_t* __restrict__ boff = ra.boff;
+    uint64_t* __restrict__ tmp_k = ra.tmp_k;
+    uint32_t* __restrict__ tmp_c = ra.tmp_c;
+    uint32_t* __restrict__ n_distinct = ra.n_distinct;
+    uint32_t* __restrict__ mid_list = ra.mid_list;
+    const int paired = ra.paired, dbg_stage = ra.dbg_stage;
+    const uint32_t cutoff = ra.cutoff;
+    const BucketMap& bm = ra.bm;
     constexpr int ITEMS = CAP / RTPB;     // records per lane
-    // `no_dedup` arrives as a DEDUP_* mode.  DEDUP_FILTER (the reference's default for pairs, a10.hip): everything as in the exact
-    // mode except the marker test itself, which is the bit a10_mark left in the occurrence's record.
-    const bool filter = no_dedup == DEDUP_FILTER;
-    if (filter) no_dedup = 0;
+    // DEDUP_FILTER (the reference's default for pairs, a10.hip): everything as in the exact mode except the marker test itself,
+    // which is the bit a10_mark left in the occurrence's record.
+    const bool filter = ra.dedup == DEDUP_FILTER;
+    const int no_dedup = filter ? 0 : ra.dedup;
     __shared__ uint64_t s_hash[CAP], s_rid[CAP], s_m0[CAP], s_m1[CAP];
     __shared__ __attribute__((aligned(8))) uint16_t s_seg[CAP];   // first sorted position of the k-mer each sorted position belongs to
     __shared__ uint8_t s_fl[CAP];         // bit0 skip, bit1 would-be-dropped
@@ -84,16 +116,16 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     uint16_t* const s_b = s_ab + (CAP + 2);
     __shared__ uint32_t s_wave[RTPB / 64];
     const uint32_t tid = threadIdx.x;
-    const uint32_t nv = *p_nv;
+    const uint32_t nv = *ra.p_nv;
     const uint32_t first = boff[b], last = boff[b + 1];
     const uint32_t n = last - first;
-    if (last > nv || first > last) { if (tid == 0) atomicAdd(overflow, 1u); return; }   // defensive: inconsistent bounds
+    if (last > nv || first > last) { if (tid == 0) atomicAdd(ra.overflow, 1u); return; }   // defensive: inconsistent bounds
     if (n == 0) return;                   // (n_distinct was zeroed by the host)
     // too large for this configuration: queue it for the large one (large_list: [0] = count, [1..] = buckets), or for the
     // host, which sends the occurrences of such buckets through the device-wide path (ovf_list, same layout)
     if (n > CAP) {
         if (tid == 0) {
-            uint32_t* list = (CAP < CAP_MID && n <= (uint32_t)CAP_MID) ? mid_list : (CAP < CAP_LARGE && n <= (uint32_t)CAP_LARGE) ? large_list : ovf_list;
+            uint32_t* list = (CAP < CAP_MID && n <= (uint32_t)CAP_MID) ? mid_list : (CAP < CAP_LARGE && n <= (uint32_t)CAP_LARGE) ? ra.large_list : ra.ovf_list;
             list[1 + atomicAdd(&list[0], 1u)] = b;
         }
         return;
@@ -101,41 +133,27 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     // ---- gather (through the partition permutation, one 32 B sector per occurrence) + sort by (hash, file order) -------
     uint64_t* s_key = s_m0;               // keys live in s_m0 until the sorted records are written
     const bool composite = bm.composite != 0;
-    // lowest hash that maps to this bucket: hs >= ceil(b * 2^32 / mult)  (exact inverse of bucket_of)
-    const uint64_t lo_hash = composite ? (((((uint64_t)b << 32) + bm.mult - 1u) / bm.mult) << bm.sh) : 0ull;
+    const uint64_t lo_hash = composite ? bucket_lo_hash(b, bm.mult, bm.sh) : 0ull;
     OccRec r[ITEMS];
     uint32_t pidx[ITEMS], rank[ITEMS];
-    // LEAN, 256 slots: the rank loops below also count the members with a smaller HASH — the sorted position of the k-mer's first
+    // 256 slots: the rank loops below also count the members with a smaller HASH — the sorted position of the k-mer's first
     // occurrence, i.e. its segment head (equal hashes share a sub-range) — so that no scan has to find the heads afterwards
-    constexpr bool SEG_DIRECT = LEAN && CAP == CAP_SMALL;
+    constexpr bool SEG_DIRECT = CAP == CAP_SMALL;
     uint32_t seg0[ITEMS];
 #pragma unroll
     for (int q = 0; q < ITEMS; q++) seg0[q] = 0;
     uint32_t* const s_pidx = reinterpret_cast<uint32_t*>(s_rid);   // (s_rid is free until the sorted records are written)
     const int levels = (int)((n + RTPB - 1) / RTPB);   // lanes of level q hold a record iff q < levels (wave-uniform)
-    if constexpr (LEAN) {
-        // every load of the bucket before the first wait: a lane past the end loads the bucket's last entry again (one line for the
-        // whole wavefront), so there is no branch around the loads and the gather is two load latencies, not one per record
+    // every load of the bucket before the first wait: a lane past the end loads the bucket's last entry again (one line for the
+    // whole wavefront), so there is no branch around the loads and the gather is two load latencies, not one per record
 #pragma unroll
-        for (int q = 0; q < ITEMS; q++) pidx[q] = perm[first + min(tid + q * RTPB, n - 1u)];
+    for (int q = 0; q < ITEMS; q++) pidx[q] = perm[first + min(tid + q * RTPB, n - 1u)];
 #pragma unroll
-        for (int q = 0; q < ITEMS; q++) r[q] = recs[pidx[q]];
+    for (int q = 0; q < ITEMS; q++) r[q] = recs[pidx[q]];
 #pragma unroll
-        for (int q = 0; q < ITEMS; q++) {
-            rank[q] = 0;
-            if (tid + q * RTPB >= n) pidx[q] = 0xFFFFFFFFu;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < ITEMS; q++) {
-            const uint32_t i = tid + q * RTPB;
-            pidx[q] = 0xFFFFFFFFu;
-            rank[q] = 0;
-            if (i < n) {
-                pidx[q] = perm[first + i];
-                r[q] = recs[pidx[q]];
-            }
-        }
+    for (int q = 0; q < ITEMS; q++) {
+        rank[q] = 0;
+        if (tid + q * RTPB >= n) pidx[q] = 0xFFFFFFFFu;
     }
     if (composite) {
         // Sub-bin sort, linear in the bucket: the bucket's hashes are uniform over its narrow range, so CAP equal sub-ranges hold
@@ -156,8 +174,8 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         unsigned long long* const s_min = reinterpret_cast<unsigned long long*>(s_hash);
         unsigned long long* const s_max = reinterpret_cast<unsigned long long*>(s_rid);
         for (uint32_t t = tid; t <= (uint32_t)CAP; t += RTPB) s_cnt[t] = 0;
-        if constexpr (LEAN)      // (the placement's counters too: s_seg is not written before the segments)
-            for (uint32_t t = tid; t < (uint32_t)CAP / 2; t += RTPB) reinterpret_cast<uint32_t*>(s_seg)[t] = 0;
+        // (the placement's counters too: s_seg is not written before the segments)
+        for (uint32_t t = tid; t < (uint32_t)CAP / 2; t += RTPB) reinterpret_cast<uint32_t*>(s_seg)[t] = 0;
         if constexpr (TWO_LEVEL)
             for (uint32_t t = tid; t < (uint32_t)CAP; t += RTPB) { s_min[t] = ~0ull; s_max[t] = 0ull; }
         __syncthreads();
@@ -166,8 +184,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             const uint32_t i = tid + q * RTPB;
             sub[q] = 0;
             if (i < n) {
-                const uint32_t hsres = (uint32_t)((r[q].hash - lo_hash) >> bm.sh);          // < bm.range_hs
-                sub[q] = sub_mult ? min(__umulhi(hsres, sub_mult), (uint32_t)CAP - 1u) : min(hsres, (uint32_t)CAP - 1u);
+                sub[q] = sub_range_of((uint32_t)((r[q].hash - lo_hash) >> bm.sh), sub_mult, CAP);          // (the distance is < bm.range_hs)
                 atomicAdd(&s_cnt[sub[q]], 1u);
                 if constexpr (TWO_LEVEL) {
                     atomicMin(&s_min[sub[q]], (unsigned long long)r[q].hash);
@@ -176,16 +193,8 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             }
         }
         __syncthreads();
-        {   // exclusive scan of the CAP counters (CAP / RTPB per lane): s_cnt[t] = start of sub-range t, s_cnt[CAP] = n
-            constexpr int PER = CAP / RTPB;
-            uint32_t v[PER], sum = 0;
-#pragma unroll
-            for (int e = 0; e < PER; e++) { v[e] = s_cnt[tid * PER + e]; sum += v[e]; }
-            uint32_t run = block_excl_sum<RTPB>(sum, s_wave, nullptr);
-            bool deep = false;
-#pragma unroll
-            for (int e = 0; e < PER; e++) { s_cnt[tid * PER + e] = run; run += v[e]; deep |= v[e] >= SEG_LIMIT; }
-            if (tid == RTPB - 1) s_cnt[CAP] = run;
+        {   // s_cnt[t] = start of sub-range t, s_cnt[CAP] = n
+            const bool deep = scan_counters<CAP, RTPB>(s_cnt, s_cnt, s_wave) >= SEG_LIMIT;
             // A k-mer SEG_LIMIT deep fills its sub-range that far (equal hashes share a sub-range): such a bucket is for the
             // hashed marker test of the next configuration — pass it on now, before the placement, the ranking (as long as the k-mer
             // is deep, per occurrence) and the segment scans are spent on it here.  (A sub-range that full without a deep k-mer
@@ -226,16 +235,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
                     }
                 }
                 __syncthreads();
-                {
-                    constexpr int PER = CAP / RTPB;
-                    uint32_t v[PER], sum = 0;
-#pragma unroll
-                    for (int e = 0; e < PER; e++) { v[e] = s_c2[tid * PER + e]; sum += v[e]; }
-                    uint32_t run = block_excl_sum<RTPB>(sum, s_wave, nullptr);
-#pragma unroll
-                    for (int e = 0; e < PER; e++) { s_s2[tid * PER + e] = run; run += v[e]; }
-                    if (tid == RTPB - 1) s_s2[CAP] = run;
-                }
+                scan_counters<CAP, RTPB>(s_c2, s_s2, s_wave);
                 __syncthreads();
                 starts = s_s2;
             }
@@ -243,10 +243,6 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         // place (cursor = a second counter array would cost LDS: take places from the END of each sub-range instead, counting the
         // start words' neighbours down is not possible either — so the places come from s_seg, which is free until the segments)
         uint16_t* const s_fill = s_seg;                               // members placed so far per sub-range (<= CAP: 16 bits do)
-        if constexpr (!LEAN) {
-            for (uint32_t t = tid; t < (uint32_t)CAP; t += RTPB) s_fill[t] = 0;
-            __syncthreads();
-        }
         // ranking key of an occurrence inside its sub-range: (hash - a lower bound of the sub-range's hashes, index) in one word
         // when the host found room for both (rank_bits > 0), else the hash with the indices in a second array
         uint64_t rkey[ITEMS];
@@ -255,10 +251,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             const uint32_t i = tid + q * RTPB;
             rkey[q] = 0;
             if (i < n) {
-                // 16-bit LDS atomics do not exist: the counter pairs share a word; add 1 or 65536 to the word and take the half
-                uint32_t* const w = reinterpret_cast<uint32_t*>(s_fill) + (bin[q] >> 1);
-                const uint32_t old = atomicAdd(w, (bin[q] & 1u) ? 65536u : 1u);
-                const uint32_t place = starts[bin[q]] + ((bin[q] & 1u) ? (old >> 16) : (old & 0xFFFFu));
+                const uint32_t place = starts[bin[q]] + take_place(s_fill, bin[q]);
                 if (rank_bits) {
                     const uint64_t res = (r[q].hash - lo_hash) - ((uint64_t)(sub[q] * bm.sub_width[CFG]) << bm.sh);
                     rkey[q] = (res << rank_bits) | pidx[q];
@@ -362,8 +355,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     // lane owns `items` contiguous sorted positions; s_seg = running "last head seen" (segmented max-scan)
     const uint32_t items = (n + RTPB - 1) / RTPB;
     const uint32_t j0 = tid * items;
-    uint32_t heads = 0, last_head = 0;
-    bool has_head = false;
+    uint32_t heads = 0;
     uint8_t headbits = 0;
     if constexpr (SEG_DIRECT) {
         // s_seg came with the sorted records: a head is a position that is its own segment's start
@@ -373,48 +365,50 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             if ((uint32_t)s_seg[j] == j) { heads++; headbits |= (uint8_t)(1u << t); }
         }
     } else {
-    for (uint32_t t = 0; t < items; t++) {
-        const uint32_t j = j0 + t;
-        if (j >= n) break;
-        const bool hd = (j == 0) || (s_hash[j] != s_hash[j - 1]);
-        if (hd) { heads++; last_head = j; has_head = true; headbits |= (uint8_t)(1u << t); }
-    }
-    // inclusive max-scan of last_head over lanes (a lane without a head inherits from the left)
-    uint32_t carry = has_head ? last_head + 1 : 0;   // +1 so that 0 means "none"
-    {
-        const uint32_t lane = tid & 63, wave = tid >> 6;
-        uint32_t x = carry;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x = max(x, y);
-        }
-        __syncthreads();
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();
-        uint32_t left = 0;
-        for (uint32_t w = 0; w < wave; w++) left = max(left, s_wave[w]);
-        const uint32_t prev = max(left, __shfl_up(x, 1));   // inclusive result of the lane to the left
-        carry = (lane == 0) ? left : prev;
-    }
-    {
-        uint32_t cur = carry;   // last head (+1) before this lane's first position
+        uint32_t last_head = 0;
+        bool has_head = false;
         for (uint32_t t = 0; t < items; t++) {
             const uint32_t j = j0 + t;
             if (j >= n) break;
-            if (headbits & (1u << t)) cur = j + 1;
-            s_seg[j] = (uint16_t)(cur - 1);
+            const bool hd = (j == 0) || (s_hash[j] != s_hash[j - 1]);
+            if (hd) { heads++; last_head = j; has_head = true; headbits |= (uint8_t)(1u << t); }
         }
-    }
-    __syncthreads();
+        // inclusive max-scan of last_head over lanes (a lane without a head inherits from the left)
+        uint32_t carry = has_head ? last_head + 1 : 0;   // +1 so that 0 means "none"
+        {
+            const uint32_t lane = tid & 63, wave = tid >> 6;
+            uint32_t x = carry;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t y = __shfl_up(x, d);
+                if (lane >= (uint32_t)d) x = max(x, y);
+            }
+            __syncthreads();
+            if (lane == 63) s_wave[wave] = x;
+            __syncthreads();
+            uint32_t left = 0;
+            for (uint32_t w = 0; w < wave; w++) left = max(left, s_wave[w]);
+            const uint32_t prev = max(left, __shfl_up(x, 1));   // inclusive result of the lane to the left
+            carry = (lane == 0) ? left : prev;
+        }
+        {
+            uint32_t cur = carry;   // last head (+1) before this lane's first position
+            for (uint32_t t = 0; t < items; t++) {
+                const uint32_t j = j0 + t;
+                if (j >= n) break;
+                if (headbits & (1u << t)) cur = j + 1;
+                s_seg[j] = (uint16_t)(cur - 1);
+            }
+        }
+        __syncthreads();
     }
     constexpr bool HASHED = CAP != CAP_SMALL;
     constexpr uint32_t MARKER_TAB = 4 * CAP;    // slots of the marker table: 2 x (2 entries per occurrence)
     if constexpr (!HASHED) {
         // a long k-mer segment of occurrences that carry markers: not for the quadratic marker test below (reads above 400 bases
         // carry none — the test does not run for them, however deep the k-mer)
-        // (LEAN: a composite bucket got here only if no sub-range held SEG_LIMIT occurrences — every k-mer is shallower)
-        if (!no_dedup && !(LEAN && composite)) {
+        // (a composite bucket got here only if no sub-range held SEG_LIMIT occurrences — every k-mer is shallower)
+        if (!no_dedup && !composite) {
             __shared__ uint32_t s_longest;
             if (tid == 0) s_longest = 0;
             __syncthreads();
@@ -447,7 +441,6 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
         return true;
     };
     uint32_t* const s_tag = reinterpret_cast<uint32_t*>(s_ab);           // CAP words: fits the 2 x (CAP + 2) halfwords of s_a | s_b, which are written later
-    (void)s_tag;
     // ---- mate-2 skip (sketch.rs:852) and duplicate flags ----------------------------------------------------------
     for (uint32_t t = 0; t < items; t++) {
         const uint32_t j = j0 + t;
@@ -466,10 +459,8 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             }
         }
         s_fl[j] = fl;
-#if SYLPH_REPLAY_TAGS
         if constexpr (CAP == CAP_SMALL)
             s_tag[j] = (!fl && (s_rid[j] & RID_MARKER_BIT)) ? (marker_tag(s_m0[j]) | (marker_tag(s_m1[j]) << 16)) : 0u;
-#endif
     }
     __syncthreads();
     uint32_t my_u = 0;
@@ -538,7 +529,6 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
             } else if (!fl && !no_dedup && (s_rid[j] & RID_MARKER_BIT)) {
                 const uint64_t a = s_m0[j], bb = s_m1[j];
                 bool hit = false;
-#if SYLPH_REPLAY_TAGS
                 // Round 5: the scan over the k-mer's earlier occurrences reads ONE 32-bit word per occurrence — two 15-bit tags of its
                 // markers, 0 for an occurrence that put nothing into the set (skipped mate 2, no markers) — and looks at the 16 bytes of
                 // markers only where a tag matches (a real duplicate, or 4 x 2^-15 by chance).  Before: flag byte + record id + both
@@ -554,18 +544,6 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
                     }
                 }
                 if (j != (uint32_t)s_seg[j] && (hit || a == bb)) fl |= 2;
-#else
-                bool any_prev = false;
-                for (uint32_t q = s_seg[j]; q < j; q++) {
-                    if (s_fl[q] & 1) continue;
-                    any_prev = true;
-                    if (s_rid[q] & RID_MARKER_BIT) {
-                        const uint64_t x = s_m0[q], y = s_m1[q];
-                        if (x == a || y == a || x == bb || y == bb) { hit = true; break; }
-                    }
-                }
-                if (any_prev && (hit || a == bb)) fl |= 2;
-#endif
             }
             const bool u = !(fl & 1) && (no_dedup || !(fl & 2));
             if (u) { my_u++; ubits |= (uint8_t)(1u << t); }
@@ -576,7 +554,7 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     // ---- P_i = would-be-counted occurrences before i in its k-mer; counted_i (cut-off rule, sketch.rs:706) ------
     // two block scans in total: (would-count, heads) packed 16+16 bits here, (counted, removed) below; sums <= CAP
     uint32_t base_h = 0, total_heads = 0, total_removed = 0;
-    if (LEAN && CAP <= 512 && cutoff == 0) {
+    if (CAP <= 512 && cutoff == 0) {
         // pairs (no cut-off): counted = would-count, so ONE block scan of (would-count, heads, removed) packed 10+10+10 bits (sums <= CAP
         // <= 512) gives both the distinct indices and Ec; the per-k-mer prefix P is not needed
         uint32_t my_removed = 0;
@@ -685,20 +663,12 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const OccRec* __
     }
     // (per-bucket removed counts are summed by a separate kernel: one atomic per workgroup on a single word runs at ~88
     //  atomics/us on this chip and was bounding the whole kernel at ~0.2 ms for 2e4 buckets)
-    if (tid == 0) { n_distinct[b] = total_heads; removed_b[b] = total_removed; }
+    if (tid == 0) { n_distinct[b] = total_heads; ra.removed_b[b] = total_removed; }
 }
 
-template <int CAP, int RTPB, bool LEAN>
-__global__ __launch_bounds__(RTPB) void bucket_replay_kernel(const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
-                                                             const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv,
-                                                             int paired, int no_dedup, uint32_t cutoff, BucketMap bm,
-                                                             uint64_t* __restrict__ tmp_k, uint32_t* __restrict__ tmp_c,
-                                                             uint32_t* __restrict__ n_distinct, uint32_t* __restrict__ removed_b,
-                                                             uint32_t* __restrict__ overflow, uint32_t* __restrict__ mid_list,
-                                                             uint32_t* __restrict__ large_list, uint32_t* __restrict__ ovf_list,
-                                                             int dbg_stage) {
-    replay_bucket<CAP, RTPB, LEAN>(blockIdx.x, recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct, removed_b,
-                             overflow, mid_list, large_list, ovf_list, dbg_stage);
+template <int CAP, int RTPB>
+__global__ __launch_bounds__(RTPB) void bucket_replay_kernel(ReplayArgs ra) {
+    replay_bucket<CAP, RTPB>(blockIdx.x, ra);
 }
 
 // Marker-less samples (single-end; long reads or --no-dedup: sylph_sketch::n_plain): nothing is ever dropped, the table is the
@@ -707,30 +677,32 @@ __global__ __launch_bounds__(RTPB) void bucket_replay_kernel(const OccRec* __res
 // Buckets above CAP go to the next configuration's list (large_list), above that to ovf_list — the host writes the records of
 // the sample then (OccRec{hash, 0, 0, 0}) and sends those buckets the usual way.
 template <int CAP, int RTPB>
-__device__ __forceinline__ void count_bucket(const uint32_t b, const uint64_t* __restrict__ hash, const uint32_t* __restrict__ perm,
-                                             const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv, BucketMap bm,
-                                             uint64_t* __restrict__ tmp_k, uint32_t* __restrict__ tmp_c, uint32_t* __restrict__ n_distinct,
-                                             uint32_t* __restrict__ removed_b, uint32_t* __restrict__ overflow,
-                                             uint32_t* __restrict__ large_list, uint32_t* __restrict__ ovf_list) {
+__device__ __forceinline__ void count_bucket(const uint32_t b, const ReplayArgs& ra) {
+    const uint64_t* __restrict__ hash = ra.hash;
+    const uint32_t* __restrict__ perm = ra.perm;
+    const uint32_t* __restrict__ boff = ra.boff;
+    uint64_t* __restrict__ tmp_k = ra.tmp_k;
+    uint32_t* __restrict__ tmp_c = ra.tmp_c;
+    const BucketMap& bm = ra.bm;
     constexpr int ITEMS = CAP / RTPB;
     __shared__ uint64_t s_key[CAP], s_sorted[CAP];
     __shared__ uint32_t s_cnt[CAP + 1], s_mult[CAP];
     __shared__ __attribute__((aligned(8))) uint16_t s_fill[CAP];
     __shared__ uint32_t s_wave[RTPB / 64];
     const uint32_t tid = threadIdx.x;
-    const uint32_t nv = *p_nv;
+    const uint32_t nv = *ra.p_nv;
     const uint32_t first = boff[b], last = boff[b + 1];
     const uint32_t n = last - first;
-    if (last > nv || first > last) { if (tid == 0) atomicAdd(overflow, 1u); return; }
+    if (last > nv || first > last) { if (tid == 0) atomicAdd(ra.overflow, 1u); return; }
     if (n == 0) return;
     if (n > (uint32_t)CAP) {
         if (tid == 0) {
-            uint32_t* list = (CAP < CAP_LARGE && n <= (uint32_t)CAP_LARGE) ? large_list : ovf_list;
+            uint32_t* list = (CAP < CAP_LARGE && n <= (uint32_t)CAP_LARGE) ? ra.large_list : ra.ovf_list;
             list[1 + atomicAdd(&list[0], 1u)] = b;
         }
         return;
     }
-    const uint64_t lo_hash = ((((uint64_t)b << 32) + bm.mult - 1u) / bm.mult) << bm.sh;      // (bm.composite: checked by the host)
+    const uint64_t lo_hash = bucket_lo_hash(b, bm.mult, bm.sh);      // (bm.composite: checked by the host)
     const uint32_t sub_mult = bm.sub_mult[CAP == CAP_SMALL ? 0 : CAP == CAP_MID ? 1 : 2];
     uint64_t h[ITEMS];
     uint32_t sub[ITEMS], place[ITEMS];
@@ -747,30 +719,19 @@ __device__ __forceinline__ void count_bucket(const uint32_t b, const uint64_t* _
         const uint32_t i = tid + q * RTPB;
         sub[q] = 0;
         if (i < n) {
-            const uint32_t hsres = (uint32_t)((h[q] - lo_hash) >> bm.sh);
-            sub[q] = sub_mult ? min(__umulhi(hsres, sub_mult), (uint32_t)CAP - 1u) : min(hsres, (uint32_t)CAP - 1u);
+            sub[q] = sub_range_of((uint32_t)((h[q] - lo_hash) >> bm.sh), sub_mult, CAP);
             atomicAdd(&s_cnt[sub[q]], 1u);
         }
     }
     __syncthreads();
-    {
-        uint32_t v[ITEMS], sum = 0;
-#pragma unroll
-        for (int e = 0; e < ITEMS; e++) { v[e] = s_cnt[tid * ITEMS + e]; sum += v[e]; }
-        uint32_t run = block_excl_sum<RTPB>(sum, s_wave, nullptr);
-#pragma unroll
-        for (int e = 0; e < ITEMS; e++) { s_cnt[tid * ITEMS + e] = run; run += v[e]; }
-        if (tid == RTPB - 1) s_cnt[CAP] = run;
-    }
+    scan_counters<CAP, RTPB>(s_cnt, s_cnt, s_wave);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < ITEMS; q++) {
         const uint32_t i = tid + q * RTPB;
         place[q] = 0;
         if (i < n) {
-            uint32_t* const w = reinterpret_cast<uint32_t*>(s_fill) + (sub[q] >> 1);
-            const uint32_t old = atomicAdd(w, (sub[q] & 1u) ? 65536u : 1u);
-            place[q] = s_cnt[sub[q]] + ((sub[q] & 1u) ? (old >> 16) : (old & 0xFFFFu));
+            place[q] = s_cnt[sub[q]] + take_place(s_fill, sub[q]);
             s_key[place[q]] = h[q];
         }
     }
@@ -811,45 +772,26 @@ __device__ __forceinline__ void count_bucket(const uint32_t b, const uint64_t* _
         const uint32_t m = s_mult[j];
         if (m) { tmp_k[first + rh] = s_sorted[j]; tmp_c[first + rh] = m; rh++; }
     }
-    if (tid == 0) { n_distinct[b] = total_heads; removed_b[b] = 0; }
+    if (tid == 0) { ra.n_distinct[b] = total_heads; ra.removed_b[b] = 0; }
 }
 template <int CAP, int RTPB>
-__global__ __launch_bounds__(RTPB) void bucket_count_kernel(const uint64_t* __restrict__ hash, const uint32_t* __restrict__ perm,
-                                                            const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv, BucketMap bm,
-                                                            uint64_t* __restrict__ tmp_k, uint32_t* __restrict__ tmp_c,
-                                                            uint32_t* __restrict__ n_distinct, uint32_t* __restrict__ removed_b,
-                                                            uint32_t* __restrict__ overflow, uint32_t* __restrict__ large_list,
-                                                            uint32_t* __restrict__ ovf_list) {
-    count_bucket<CAP, RTPB>(blockIdx.x, hash, perm, boff, p_nv, bm, tmp_k, tmp_c, n_distinct, removed_b, overflow, large_list, ovf_list);
+__global__ __launch_bounds__(RTPB) void bucket_count_kernel(ReplayArgs ra) {
+    count_bucket<CAP, RTPB>(blockIdx.x, ra);
 }
+// the list-driven configurations: a fixed, small grid walks the (usually empty) list of buckets an earlier configuration queued
 template <int CAP, int RTPB>
-__global__ __launch_bounds__(RTPB) void bucket_count_list_kernel(const uint64_t* __restrict__ hash, const uint32_t* __restrict__ perm,
-                                                                 const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv,
-                                                                 BucketMap bm, uint64_t* __restrict__ tmp_k, uint32_t* __restrict__ tmp_c,
-                                                                 uint32_t* __restrict__ n_distinct, uint32_t* __restrict__ removed_b,
-                                                                 uint32_t* __restrict__ overflow, const uint32_t* __restrict__ my_list,
-                                                                 uint32_t* __restrict__ ovf_list) {
+__global__ __launch_bounds__(RTPB) void bucket_count_list_kernel(ReplayArgs ra, const uint32_t* __restrict__ my_list) {
     const uint32_t n_listed = my_list[0];
     for (uint32_t i = blockIdx.x; i < n_listed; i += gridDim.x) {
-        count_bucket<CAP, RTPB>(my_list[1 + i], hash, perm, boff, p_nv, bm, tmp_k, tmp_c, n_distinct, removed_b, overflow, nullptr, ovf_list);
+        count_bucket<CAP, RTPB>(my_list[1 + i], ra);
         __syncthreads();
     }
 }
-
-// second configuration: a fixed, small grid walks the (usually empty) list of buckets the first one queued
-template <int CAP, int RTPB, bool LEAN>
-__global__ __launch_bounds__(RTPB) void bucket_replay_list_kernel(const OccRec* __restrict__ recs, const uint32_t* __restrict__ perm,
-                                                                  const uint32_t* __restrict__ boff, const uint32_t* __restrict__ p_nv,
-                                                                  int paired, int no_dedup, uint32_t cutoff, BucketMap bm,
-                                                                  uint64_t* __restrict__ tmp_k, uint32_t* __restrict__ tmp_c,
-                                                                  uint32_t* __restrict__ n_distinct, uint32_t* __restrict__ removed_b,
-                                                                  uint32_t* __restrict__ overflow, const uint32_t* __restrict__ my_list,
-                                                                  uint32_t* __restrict__ large_list, uint32_t* __restrict__ ovf_list,
-                                                                  int dbg_stage) {
+template <int CAP, int RTPB>
+__global__ __launch_bounds__(RTPB) void bucket_replay_list_kernel(ReplayArgs ra, const uint32_t* __restrict__ my_list) {
     const uint32_t n_listed = my_list[0];
     for (uint32_t i = blockIdx.x; i < n_listed; i += gridDim.x) {
-        replay_bucket<CAP, RTPB, LEAN>(my_list[1 + i], recs, perm, boff, p_nv, paired, no_dedup, cutoff, bm, tmp_k, tmp_c, n_distinct,
-                                 removed_b, overflow, nullptr, large_list, ovf_list, dbg_stage);
+        replay_bucket<CAP, RTPB>(my_list[1 + i], ra);
         __syncthreads();   // the LDS arrays are reused by the next bucket
     }
 }
@@ -892,8 +834,7 @@ __global__ __launch_bounds__(SCAN_CHUNK) void table_scan_kernel(const uint32_t* 
     }
 }
 // out[rows before bucket b + i] = tmp[boff[b] + i] for i < n_distinct[b]; a workgroup walks buckets with its four wavefronts
-// (one bucket holds ~50 rows).  Also assembles the 48-byte tail block the host reads: {removed u64, overflow u32 (set by the
-// replay), n_seg u32, n_ovf u32, n_mid u32, n_large u32, seeding verdict 2 x u32}.
+// (one bucket holds ~50 rows).  Also fills the tail block the host reads (FinishTail).
 __global__ __launch_bounds__(256) void table_compact_kernel(const uint64_t* __restrict__ tmp_k, const uint32_t* __restrict__ tmp_c,
                                                             const uint32_t* __restrict__ boff, const uint32_t* __restrict__ d_loc,
                                                             const uint32_t* __restrict__ chunk_rows, const unsigned long long* __restrict__ chunk_removed,
@@ -901,7 +842,7 @@ __global__ __launch_bounds__(256) void table_compact_kernel(const uint64_t* __re
                                                             uint64_t* __restrict__ out_k, uint32_t* __restrict__ out_c,
                                                             const uint32_t* __restrict__ ovf_list, const uint32_t* __restrict__ mid_list,
                                                             const uint32_t* __restrict__ large_list, int skip_if_listed,
-                                                            uint32_t* __restrict__ tail, const uint32_t* __restrict__ verdict,
+                                                            FinishTail* __restrict__ tail, const uint32_t* __restrict__ verdict,
                                                             const uint32_t* __restrict__ a10_words, const uint32_t* __restrict__ p_nv) {
     __shared__ uint32_t s_base[257];
     __shared__ uint32_t s_wave[4];
@@ -920,13 +861,12 @@ __global__ __launch_bounds__(256) void table_compact_kernel(const uint64_t* __re
             if ((threadIdx.x & 63) == 0) s_rem[threadIdx.x >> 6] = rem;
             __syncthreads();
             if (threadIdx.x == 0) {
-                *reinterpret_cast<unsigned long long*>(tail) = s_rem[0] + s_rem[1] + s_rem[2] + s_rem[3];
-                tail[3] = tot; tail[4] = ovf_list[0]; tail[5] = mid_list[0]; tail[6] = large_list[0];
-                // deferred seeding verdict (reads.hip ReadsState: long_record, overflowing blocks) rides in the same block: one copy
-                tail[7] = verdict ? verdict[0] : 0u; tail[8] = verdict ? verdict[1] : 0u;
-                // ... and so do the verdict words of the filter dedup's partitioned pass (a10.hip)
-                tail[9] = a10_words ? a10_words[0] : 0u; tail[10] = a10_words ? a10_words[1] : 0u;
-                tail[11] = *p_nv;            // the occurrences the partition found: what a deferred batch's slots really hold
+                tail->removed = s_rem[0] + s_rem[1] + s_rem[2] + s_rem[3];
+                tail->n_seg = tot; tail->n_ovf = ovf_list[0]; tail->n_mid = mid_list[0]; tail->n_large = large_list[0];
+                // the deferred seeding verdict and the filter pass's verdict words ride in the same block: one copy
+                tail->verdict[0] = verdict ? verdict[0] : 0u; tail->verdict[1] = verdict ? verdict[1] : 0u;
+                tail->a10_words[0] = a10_words ? a10_words[0] : 0u; tail->a10_words[1] = a10_words ? a10_words[1] : 0u;
+                tail->n_found = *p_nv;
             }
         }
     }
@@ -1000,9 +940,8 @@ __global__ __launch_bounds__(256) void ovf_patch_kernel(const uint32_t* __restri
     // rows of bucket b = rows with k-mer in [smallest hash of bucket b, smallest hash of bucket b + 1) (inverse of bucket_of)
     __shared__ uint32_t s_lo, s_hi;
     if (threadIdx.x == 0) {
-        auto lo_hash = [&](uint32_t bb) { return ((((uint64_t)bb << 32) + bm.mult - 1u) / bm.mult) << bm.sh; };
-        s_lo = lower(lo_hash(b));
-        s_hi = (b + 1 < bm.B) ? lower(lo_hash(b + 1)) : n_sub_out;
+        s_lo = lower(bucket_lo_hash(b, bm.mult, bm.sh));
+        s_hi = (b + 1 < bm.B) ? lower(bucket_lo_hash(b + 1, bm.mult, bm.sh)) : n_sub_out;
     }
     __syncthreads();
     const uint32_t lo = s_lo, n = s_hi - s_lo, d = boff[b];
@@ -1063,11 +1002,8 @@ bool finish_bucketed(sylph_sketch* sk) {
     // not fit the sub-range arithmetic get their records written and take the usual kernels
     if (!slotted && sk->n_plain && !(sk->n_plain == sk->n_occ && bm.composite)) materialise_plain_records(sk);
     bool plain = !slotted && sk->n_plain != 0;
-    // Run-time shape switches (A/B of one build, profiles/r07_ab_tail.txt).  SYLPH_HIP_REPLAY_LEAN=0: round 6's replay (one load round trip
-    // per record of the gather, a max-scan for the segment heads, two block scans for pairs, the long-segment recheck).
-    // SYLPH_HIP_PART_TILE_BLOCKS / SYLPH_HIP_PART_STAGE_PAIRS: seeding blocks per partition tile and pairs the scatter stages in LDS for the
-    // slotted sample — round 6 had 16 / 4096 (36.7 KiB of LDS per scatter workgroup, which waits for room beside the seeding kernel).
-    static const bool lean = [] { const char* e = getenv("SYLPH_HIP_REPLAY_LEAN"); return e ? atoi(e) != 0 : true; }();
+    // Run-time shape knobs.  SYLPH_HIP_PART_TILE_BLOCKS / SYLPH_HIP_PART_STAGE_PAIRS: seeding blocks per partition tile and pairs the scatter stages
+    // in LDS for the slotted sample — round 6 had 16 / 4096 (36.7 KiB of LDS per scatter workgroup, which waits for room beside the seeding kernel).
     static const uint32_t tile_blocks = [] { const char* e = getenv("SYLPH_HIP_PART_TILE_BLOCKS"); return e ? (uint32_t)std::max(1, std::min(32, atoi(e))) : BLK_PER_TILE; }();
     // (2048 pairs: 16 KiB + the range counters, 20 KiB per workgroup; a tile holds ~3,000 occurrences, the rest goes out directly —
     //  pipelined exact set +0.4..0.9 % over 4096 on top of the lean replay, 1536 and 1024 within noise of it: profiles/r07_ab_tail.txt)
@@ -1104,7 +1040,7 @@ bool finish_bucketed(sylph_sketch* sk) {
     in.carry = plain ? 1 : 0;
     b_tmpk.reserve((size_t)n_cap * 8);
     b_tmpc.reserve((size_t)n_cap * 4);
-    b_small.reserve(64);
+    b_small.reserve(64);                                                // FinishTail (part_hist_kernel clears 16 words)
     // boff | large_list | ovf_list | n_distinct | removed | d_off | mid_list (each B+2) | chunk_rows (264) | chunk_removed (264 u64)
     b_bk.reserve((size_t)(B + 2) * 4 * 7 + 264 * 4 + 264 * 8 + 16);
     uint32_t* hist = b_hist.as<uint32_t>();
@@ -1118,8 +1054,7 @@ bool finish_bucketed(sylph_sketch* sk) {
     uint32_t* mid_list = d_off + (B + 2);       // buckets for the medium configuration (n <= CAP_MID, or a long k-mer segment)
     uint32_t* chunk_rows = mid_list + (B + 2) + ((B & 1u) ? 1 : 0);       // (8-byte aligned: 7 * (B + 2) words is odd for odd B)
     unsigned long long* chunk_removed = reinterpret_cast<unsigned long long*>(chunk_rows + 264);
-    unsigned long long* d_removed = b_small.as<unsigned long long>();
-    uint32_t* d_overflow = reinterpret_cast<uint32_t*>(b_small.as<uint8_t>() + 8);
+    FinishTail* d_tail = b_small.as<FinishTail>();
     const uint32_t* d_nv = boff + B;            // boff[B] = number of valid occurrences
     const uint32_t n_zero = (B + 2) * 2;                                            // n_distinct and removed (cleared by part_hist_kernel)
     // every launch below takes its sizes from device memory; the host synchronises ONCE, at the end (unless some buckets need
@@ -1128,6 +1063,14 @@ bool finish_bucketed(sylph_sketch* sk) {
     const uint32_t cutoff = sk->paired ? 0u : 4u;   // MAX_DEDUP_COUNT, constants.rs:14
     sk->out_k.reserve((size_t)n_cap * 8);          // upper bound: distinct k-mers <= occurrences
     sk->out_c.reserve((size_t)n_cap * 4);
+    ReplayArgs ra{};
+    if (plain) ra.hash = sorted_hash;
+    else { ra.recs = recs; ra.perm = b_perm.as<uint32_t>(); }
+    ra.boff = boff; ra.p_nv = d_nv;
+    ra.paired = sk->paired; ra.dedup = sk->dedup_mode(); ra.cutoff = cutoff; ra.bm = bm;
+    ra.tmp_k = b_tmpk.as<uint64_t>(); ra.tmp_c = b_tmpc.as<uint32_t>(); ra.n_distinct = n_distinct; ra.removed_b = removed_b;
+    ra.overflow = &d_tail->overflow;               // (an address on the device: not read here)
+    ra.mid_list = mid_list; ra.large_list = large_list; ra.ovf_list = ovf_list; ra.dbg_stage = dbg;
     {
         HostPhase ph(ctx, "finish(bucket): partition + LDS replay + compact");
         {
@@ -1137,19 +1080,11 @@ bool finish_bucketed(sylph_sketch* sk) {
         }
         {
             ScopedKernelTimer t(ctx, "replay");
-            if (plain)
-                hipLaunchKernelGGL((bucket_count_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream,
-                                   sorted_hash, (const uint32_t*)nullptr, boff, d_nv, bm, b_tmpk.as<uint64_t>(),
-                                   b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, large_list, ovf_list);
-            else
-                hipLaunchKernelGGL((lean ? bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, true> : bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, false>),
-                                   dim3(B), dim3(RTPB_SMALL), 0, ctx->stream,
-                                   recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired, sk->dedup_mode(), cutoff, bm,
-                                   b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, mid_list, large_list,
-                                   ovf_list, dbg);
+            if (plain) hipLaunchKernelGGL((bucket_count_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream, ra);
+            else hipLaunchKernelGGL((bucket_replay_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream, ra);
         }
     }
-    // removed counts, table offsets, compaction, and everything the host needs to know in one 28-byte block
+    // removed counts, table offsets, compaction, and everything the host needs to know in one block (FinishTail)
     auto close_table = [&](int skip_if_listed) {
         // two levels: chunks of 1024 x ipt buckets (at most 256 of them), then the compaction, which scans the chunk totals itself
         const uint32_t ipt = (B + (1u << 18) - 1) >> 18;
@@ -1159,37 +1094,30 @@ bool finish_bucketed(sylph_sketch* sk) {
         hipLaunchKernelGGL(table_compact_kernel, dim3(std::min<uint32_t>((B + 3) / 4, 1u << 15)), dim3(256), 0, ctx->stream,
                            b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), boff, d_off, chunk_rows, chunk_removed, n_distinct, B, ipt,
                            sk->out_k.as<uint64_t>(), sk->out_c.as<uint32_t>(), ovf_list, mid_list, large_list, skip_if_listed,
-                           b_small.as<uint32_t>(),
-                           deferred ? sk->slot_meta.as<uint32_t>() + (size_t)(sk->pend.n_blk + 1) * 4 : (const uint32_t*)nullptr,
+                           d_tail, deferred ? sk->slot_meta.as<uint32_t>() + (size_t)(sk->pend.n_blk + 1) * 4 : (const uint32_t*)nullptr,
                            sk->a10_state == 1 ? sk->a10_tail.as<uint32_t>() : (const uint32_t*)nullptr, d_nv);
         SY_HIP(hipGetLastError());
     };
-    struct { unsigned long long removed; uint32_t overflow, n_seg, n_ovf, n_mid, n_large; } host{};
-    uint32_t verdict[2] = {0, 0};                  // deferred: long_record flag, overflowing blocks of the seeding kernel
-    uint32_t a10_words[2] = {0, 0};                // filter dedup, partitioned pass: buckets it could not take, operations it found
-    uint32_t n_found = 0;                          // occurrences the partition found
+    FinishTail host{};
     auto read_tail = [&] {
-        SY_HIP(hipMemcpyAsync(ctx->pinned, d_removed, 48, hipMemcpyDeviceToHost, ctx->stream));
+        SY_HIP(hipMemcpyAsync(ctx->pinned, d_tail, sizeof host, hipMemcpyDeviceToHost, ctx->stream));
         SY_HIP(hipStreamSynchronize(ctx->stream));
-        memcpy(&host, ctx->pinned, 28);
-        if (deferred) memcpy(verdict, (const char*)ctx->pinned + 28, 8);   // (the two flag words of ReadsState, copied by table_compact_kernel)
-        memcpy(a10_words, (const char*)ctx->pinned + 36, 8);
-        memcpy(&n_found, (const char*)ctx->pinned + 44, 4);
+        memcpy(&host, ctx->pinned, sizeof host);
         if (!ctx->pending.empty()) profile_collect(ctx);
     };
     close_table(1);
     read_tail();
     if (deferred) {
-        if (verdict[0] || verdict[1]) {            // not a batch for the short-read kernel after all: the checked push, then from the top
+        if (host.verdict[0] || host.verdict[1]) {  // not a batch for the short-read kernel after all: the checked push, then from the top
             redo_deferred_batch(sk);
             a10_mark(sk);                          // (filter dedup: the marks went with the slots)
             return finish_bucketed(sk);
         }
         sk->pend.deferred = false;                 // the verdict is in: from here on an ordinary slotted sample ...
-        sk->pend.n = n_found;                      // ... whose occurrence count is known (whoever flushes the slots to the dense arrays needs it)
+        sk->pend.n = host.n_found;                 // ... whose occurrence count is known (whoever flushes the slots to the dense arrays needs it)
     }
     // filter dedup: were the partitioned pass's marks good (a10.hip)?  If not the phase walk has marked the records again, dense: from the top
-    if (!a10_verdict(sk, a10_words)) return finish_bucketed(sk);
+    if (!a10_verdict(sk, host.a10_words)) return finish_bucketed(sk);
     if (host.overflow) return false;             // inconsistent bounds (defensive): the generic path redoes the sample
     if (plain && host.n_ovf) {
         // k-mers more than a thousand deep in a marker-less sample: write the occurrence records after all and take the usual
@@ -1208,21 +1136,14 @@ bool finish_bucketed(sylph_sketch* sk) {
             if (plain) {
                 if (host.n_large)
                     hipLaunchKernelGGL((bucket_count_list_kernel<CAP_LARGE, RTPB_LARGE>), dim3(std::min<uint32_t>(host.n_large, 1536u)),
-                                       dim3(RTPB_LARGE), 0, ctx->stream, sorted_hash, (const uint32_t*)nullptr, boff, d_nv, bm,
-                                       b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b, d_overflow, large_list, ovf_list);
+                                       dim3(RTPB_LARGE), 0, ctx->stream, ra, large_list);
             } else {
-            if (host.n_mid)
-                hipLaunchKernelGGL((lean ? bucket_replay_list_kernel<CAP_MID, RTPB_MID, true> : bucket_replay_list_kernel<CAP_MID, RTPB_MID, false>),
-                                   dim3(std::min<uint32_t>(host.n_mid, 1280u)),
-                                   dim3(RTPB_MID), 0, ctx->stream, recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired,
-                                   sk->dedup_mode(), cutoff, bm, b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b,
-                                   d_overflow, mid_list, large_list, ovf_list, dbg);
-            if (host.n_large)
-                hipLaunchKernelGGL((lean ? bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE, true> : bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE, false>),
-                                   dim3(std::min<uint32_t>(host.n_large, 512u)),
-                                   dim3(RTPB_LARGE), 0, ctx->stream, recs, b_perm.as<uint32_t>(), boff, d_nv, sk->paired,
-                                   sk->dedup_mode(), cutoff, bm, b_tmpk.as<uint64_t>(), b_tmpc.as<uint32_t>(), n_distinct, removed_b,
-                                   d_overflow, large_list, large_list, ovf_list, dbg);
+                if (host.n_mid)
+                    hipLaunchKernelGGL((bucket_replay_list_kernel<CAP_MID, RTPB_MID>), dim3(std::min<uint32_t>(host.n_mid, 1280u)),
+                                       dim3(RTPB_MID), 0, ctx->stream, ra, mid_list);
+                if (host.n_large)
+                    hipLaunchKernelGGL((bucket_replay_list_kernel<CAP_LARGE, RTPB_LARGE>), dim3(std::min<uint32_t>(host.n_large, 512u)),
+                                       dim3(RTPB_LARGE), 0, ctx->stream, ra, large_list);
             }
         }
         close_table(0);

@@ -516,8 +516,8 @@ def test_device_fastq_route_equals_the_host_feed(data):
 
 def test_kernel_variants_behind_environment_knobs_give_the_same_sketches(data):
     """Round 6's A/B knobs select other kernels for the same work: the read kernel's 512-lane variant for ragged input
-    (SYLPH_HIP_READS_RAGGED_TPB=512, csrc/reads.hip), round 5's two-level filter pass (SYLPH_HIP_A10_LEVELS=2) and one / four workgroups
-    per range of the one-level pass (SYLPH_HIP_A10_RANGE_SPLIT, csrc/a10.hip).  Ragged pairs (trimmed to 35..151 bases, some with N),
+    (SYLPH_HIP_READS_RAGGED_TPB=512, csrc/reads.hip) and one / four workgroups per range of the filter pass
+    (SYLPH_HIP_A10_RANGE_SPLIT, csrc/a10.hip).  Ragged pairs (trimmed to 35..151 bases, some with N),
     through the host feed and through the device route, with sylph's default filter dedup: byte-identical .sylsp files."""
     d = data["dir"]
     rng = np.random.default_rng(77)
@@ -534,7 +534,7 @@ def test_kernel_variants_behind_environment_knobs_give_the_same_sketches(data):
             out += [t[m][4 * r], bytes(seq), b"+", b"I" * len(seq)]
         (d / f"rg_{m + 1}.fq").write_bytes(b"\n".join(out) + b"\n")
     got = {}
-    for name, env in (("default", {}), ("tpb512", {"SYLPH_HIP_READS_RAGGED_TPB": "512"}), ("two_levels", {"SYLPH_HIP_A10_LEVELS": "2"}),
+    for name, env in (("default", {}), ("tpb512", {"SYLPH_HIP_READS_RAGGED_TPB": "512"}),
                       ("split1", {"SYLPH_HIP_A10_RANGE_SPLIT": "1"}), ("split4_tpb512", {"SYLPH_HIP_A10_RANGE_SPLIT": "4", "SYLPH_HIP_READS_RAGGED_TPB": "512"})):
         o = d / f"variants_{name}"
         # two samples per command: the first goes the host feed, the second the device route

@@ -7,7 +7,7 @@
 #                              Illumina-like one (gzip -1 / -6, BGZF), per-wave statistics on
 #   gz-trace [Gbp]             tools/gz_e2e_trace.py: `sylph-hip sketch` on a plain / gzip pair with the feed's and the library's phase traces
 #   bench [bench.py args]      the bench line with every leg (bench.py --full) into bench/bench.json under the output folder (+ the rates summary on stdout)
-#   a10                        filter-dedup tests + the default-flag bench leg with one and with two partition levels
+#   a10                        filter-dedup tests + the default-flag bench leg, one / two / four workgroups per range
 #   a10-profile [--no-pmc]     rocprofv3 kernel trace (+ FETCH_SIZE / WRITE_SIZE) of the filter pass's kernels, one sample at a time
 #   ab-env cfg...              alternate environment configurations on the pipelined default-flag rate (AB_ROUNDS, AB_SECONDS, AB_FPR)
 #   ab-reads                   tools/r06_ab_reads.sh (build the variants first, here: tools/r06_build_reads_variants.sh)
@@ -33,18 +33,16 @@ case "$what" in
     timeout 1500 python bench.py --full "$@" > "$out/bench.json" 2> "$out/bench.err"; tail -c 400 "$out/bench.err"
     python -c "import json; o = json.load(open('$out/bench.json')); print(json.dumps({k: o.get(k) for k in ('value', 'value_default_flags', 'ms_per_step', 'rates_gbp_per_s')}, indent=1))" ;;
   a10)
-    # the filter dedup's pass with one partition level (default) and with round 5's two (SYLPH_HIP_A10_LEVELS=2): tests, then the default-flag leg
-    for lv in 1 2; do
-      SYLPH_HIP_A10_LEVELS=$lv timeout 900 python -m pytest tests -m gpu -x -q -k "filter or cuckoo or a10" > "$out/pytest_levels$lv.txt" 2>&1; tail -3 "$out/pytest_levels$lv.txt"
-    done
-    # configurations levels:split:pad — partition levels (1 | 2), workgroups per range of the one-level pass, extra LDS bytes per workgroup (footprint A/B)
-    for cfg in ${A10_CONFIGS:-1:2:0 2:2:0 1:1:0 1:4:0 1:2:24576 1:2:0 2:2:0}; do
-      lv=${cfg%%:*}; rest=${cfg#*:}; split=${rest%%:*}; pad=${rest##*:}; tpb=${split}_$pad
-      SYLPH_HIP_A10_LEVELS=$lv SYLPH_HIP_A10_RANGE_SPLIT=$split SYLPH_HIP_A10_RANGE_LDS_PAD=$pad timeout 600 python bench.py --full --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --all-kernel-timers "$@" > "$out/bench_levels${lv}_$tpb.json" 2> "$out/bench_levels${lv}_$tpb.err"
-      python - "$out/bench_levels${lv}_$tpb.json" $cfg <<'PY'
+    # the filter dedup's pass: tests, then the default-flag leg
+    timeout 900 python -m pytest tests -m gpu -x -q -k "filter or cuckoo or a10" > "$out/pytest.txt" 2>&1; tail -3 "$out/pytest.txt"
+    # configurations split:pad — workgroups per range of the pass, extra LDS bytes per workgroup (footprint A/B)
+    for cfg in ${A10_CONFIGS:-2:0 1:0 4:0 2:24576 2:0}; do
+      split=${cfg%%:*}; pad=${cfg##*:}; tpb=${split}_$pad
+      SYLPH_HIP_A10_RANGE_SPLIT=$split SYLPH_HIP_A10_RANGE_LDS_PAD=$pad timeout 600 python bench.py --full --no-files-leg --no-packed-leg --no-h2d --no-cpu-baseline --all-kernel-timers "$@" > "$out/bench_$tpb.json" 2> "$out/bench_$tpb.err"
+      python - "$out/bench_$tpb.json" $cfg <<'PY'
 import json, sys
 o = json.load(open(sys.argv[1])); f = o.get("default_pair_dedup", {})
-print("levels:split:pad", sys.argv[2], "value", o.get("value"), "default flags", o.get("value_default_flags"), "ms/sample pipelined", f.get("pipelined", {}).get("ms_per_sample"),
+print("split:pad", sys.argv[2], "value", o.get("value"), "default flags", o.get("value_default_flags"), "ms/sample pipelined", f.get("pipelined", {}).get("ms_per_sample"),
       "one at a time", f.get("one_step_at_a_time", {}).get("ms_per_sample"), "a10 alone", f.get("one_step_at_a_time", {}).get("kernel_ms", {}).get("a10"))
 PY
     done ;;
