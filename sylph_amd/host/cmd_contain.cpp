@@ -1,0 +1,572 @@
+// cmd_contain.cpp — the `query` / `profile` command (contain.rs:115-351): the database made resident on the device, raw samples
+// sketched and probed through the library's pipeline, the statistics on the containment results, the reference's TSV rows.
+#include <cmath>
+#include <condition_variable>
+#include <cstring>
+
+#include "host_internal.hpp"
+
+namespace sylph_host {
+
+namespace {
+
+// contain.rs:18-94
+void print_ani_result(const AniResult& r, const std::string& seq_name, const GenomeSketch& g, bool pseudotax, FILE* out,
+                      bool debug_f64 = false) {
+    if (debug_f64) {   // --debug-f64 (not in the reference): every float column as %.17g, unclamped, for 1e-6 parity checks
+        auto opt = [](const std::optional<double>& v) { char b[40]; if (v) snprintf(b, sizeof(b), "%.17g", *v); else snprintf(b, sizeof(b), "NA"); return std::string(b); };
+        fprintf(out, "%s\t%s\t", seq_name.c_str(), g.file_name.c_str());
+        if (pseudotax) fprintf(out, "%.17g\t%.17g\t", *r.rel_abund, *r.seq_abund);
+        fprintf(out, "%.17g\t%.17g\t%s-%s\t", r.final_est_ani * 100., r.final_est_cov, opt(r.ani_ci_lo).c_str(), opt(r.ani_ci_hi).c_str());
+        if (r.lambda_status == AdjustStatus::Lambda) fprintf(out, "%.17g\t", r.lambda);
+        else fprintf(out, "%s\t", r.lambda_status == AdjustStatus::High ? "HIGH" : "LOW");
+        fprintf(out, "%s-%s\t%.17g\t%.17g\t%zu/%zu\t%.17g\t", opt(r.lambda_ci_lo).c_str(), opt(r.lambda_ci_hi).c_str(), r.median_cov,
+                r.mean_cov, r.contain_count, r.n_kmers, r.naive_ani * 100.);
+        if (pseudotax) fprintf(out, "%zu\t", *r.kmers_lost);
+        fprintf(out, "%s\n", g.first_contig_name.c_str());
+        return;
+    }
+    char final_ani[64];
+    snprintf(final_ani, sizeof(final_ani), "%.2f", std::min(r.final_est_ani * 100., 100.));
+    char lambda_print[64];
+    if (r.lambda_status == AdjustStatus::Lambda) snprintf(lambda_print, sizeof(lambda_print), "%.3f", r.lambda);
+    else snprintf(lambda_print, sizeof(lambda_print), "%s", r.lambda_status == AdjustStatus::High ? "HIGH" : "LOW");
+    char ci_ani[64] = "NA-NA", ci_lambda[64] = "NA-NA";
+    if (r.ani_ci_lo && r.ani_ci_hi) snprintf(ci_ani, sizeof(ci_ani), "%.2f-%.2f", *r.ani_ci_lo * 100., *r.ani_ci_hi * 100.);
+    if (r.lambda_ci_lo && r.lambda_ci_hi) snprintf(ci_lambda, sizeof(ci_lambda), "%.2f-%.2f", *r.lambda_ci_lo, *r.lambda_ci_hi);
+    if (!pseudotax) {
+        fprintf(out, "%s\t%s\t%s\t%.3f\t%s\t%s\t%s\t%.0f\t%.3f\t%zu/%zu\t%.2f\t%s\n", seq_name.c_str(), g.file_name.c_str(),
+                final_ani, r.final_est_cov, ci_ani, lambda_print, ci_lambda, r.median_cov, r.mean_cov, r.contain_count, r.n_kmers,
+                r.naive_ani * 100., g.first_contig_name.c_str());
+    } else {
+        fprintf(out, "%s\t%s\t%.4f\t%.4f\t%s\t%.3f\t%s\t%s\t%s\t%.0f\t%.3f\t%zu/%zu\t%.2f\t%zu\t%s\n", seq_name.c_str(),
+                g.file_name.c_str(), *r.rel_abund, *r.seq_abund, final_ani, r.final_est_cov, ci_ani, lambda_print, ci_lambda,
+                r.median_cov, r.mean_cov, r.contain_count, r.n_kmers, r.naive_ani * 100., *r.kmers_lost,
+                g.first_contig_name.c_str());
+    }
+}
+
+void print_header(bool pseudotax, FILE* out, bool estimate_unknown) {         // contain.rs:461-480
+    if (!pseudotax)
+        fprintf(out, "Sample_file\tGenome_file\tAdjusted_ANI\tEff_cov\tANI_5-95_percentile\tEff_lambda\tLambda_5-95_percentile\t"
+                     "Median_cov\tMean_cov_geq1\tContainment_ind\tNaive_ANI\tContig_name\n");
+    else
+        fprintf(out, "Sample_file\tGenome_file\tTaxonomic_abundance\tSequence_abundance\tAdjusted_ANI\t%s\tANI_5-95_percentile\t"
+                     "Eff_lambda\tLambda_5-95_percentile\tMedian_cov\tMean_cov_geq1\tContainment_ind\tNaive_ANI\tkmers_reassigned\t"
+                     "Contig_name\n", estimate_unknown ? "True_cov" : "Eff_cov");
+}
+
+}  // namespace
+
+// --estimate-unknown (-u), contain.rs:901-951 get_kmer_identity: k-mer identity of the reads (identity ^ k) from the share of
+// multiplicity-1 k-mers.  The estimate itself (eps) is a sum over the table.  The reference's "continuous median" of the counts
+// above 1 is a walk over `kmer_counts.values()` in hashbrown's iteration order, which this host does not reproduce: here the
+// walk goes over the table in ascending k-mer order (an arbitrary order with respect to the counts, as the hash map's is).
+// It only decides whether a short-read sample counts as "depth < 3" and gets the fixed 99.5 % identity — a sample right at
+// that limit may take the other branch than `sylph profile -u` does; -I (contain.rs:275) bypasses the walk altogether.
+// The integer types are the reference's: `num_not1s` is a u32 that wraps in a release build.
+std::optional<double> get_kmer_identity(const SequencesSketch& S, bool estimate_unknown) {
+    if (!estimate_unknown) return std::nullopt;
+    uint32_t median = 0;
+    double mov_avg_median = 0., n = 1.;
+    for (const uint32_t count : S.counts) {
+        if (count > 1) {
+            if (count > median) median += 1; else median -= 1;
+            mov_avg_median += (double)median;
+            n += 1.;
+        }
+    }
+    mov_avg_median /= n;
+    int32_t num_1s = 0;
+    uint32_t num_not1s = 0;
+    for (const uint32_t count : S.counts) {
+        if (count == 1) num_1s += 1; else num_not1s += count;
+    }
+    const double eps = (double)num_not1s / ((double)num_not1s + (double)num_1s + 0.1);
+    {   // which branch the walk chose, and how close the call was (the walk's order is this host's, not hashbrown's: see above).
+        // The reference prints neither line: the first only under SYLPH_HIP_DEBUG, the warning only inside the 10 % band.
+        const bool near_limit = S.mean_read_length < 400. && std::fabs(mov_avg_median - MED_KMER_FOR_ID_EST) <= 0.1 * MED_KMER_FOR_ID_EST;
+        if (getenv("SYLPH_HIP_DEBUG")) {
+            char num[160];
+            snprintf(num, sizeof(num), " --estimate-unknown: running median of the counts above 1 = %.4f (limit %.1f, mean read length %.1f): ",
+                     mov_avg_median, MED_KMER_FOR_ID_EST, S.mean_read_length);
+            info(S.file_name + num + ((mov_avg_median < MED_KMER_FOR_ID_EST && S.mean_read_length < 400.) ? "fixed 99.5% read identity" : "read identity estimated from the table"));
+        }
+        if (near_limit)
+            warn(S.file_name + ": the sample's depth is within 10% of the limit that switches --estimate-unknown between the fixed 99.5% read identity and "
+                 "the estimated one; that decision depends on the order the table is walked in (ascending k-mers here, hash-map order in "
+                 "sylph), so True_cov / Sequence_abundance may differ from `sylph profile -u` for this sample: pass -I to fix the identity");
+    }
+    if (mov_avg_median < MED_KMER_FOR_ID_EST && S.mean_read_length < 400.) {
+        info(S.file_name + " short-read sample has high diversity compared to sequencing depth (approx. avg depth < 3). Using 99.5% as "
+             "read accuracy estimate instead of automatic detection for --estimate-unknown.");
+        return std::pow(0.995, (double)S.k);
+    }
+    return eps < 1. ? eps : 1.;
+}
+
+// contain.rs:377-390
+void estimate_true_cov(std::vector<AniResult>& results, std::optional<double> kmer_id_opt, bool estimate_unknown, double read_length,
+                       uint64_t k) {
+    double multiplier = 1.;
+    if (estimate_unknown) multiplier = read_length / (read_length - (double)k + 1.);
+    if (estimate_unknown && kmer_id_opt)
+        for (auto& r : results) r.final_est_cov = r.final_est_cov / *kmer_id_opt * multiplier;
+}
+
+// contain.rs:392-408: share of the sample's bases the profiled genomes account for
+double estimate_covered_bases(const std::vector<AniResult>& results, const std::vector<GenomeSketch>& genomes, const SequencesSketch& S,
+                              double read_length, uint64_t k) {
+    const double multiplier = read_length / (read_length - (double)k + 1.);
+    double num_covered_bases = 0.;
+    for (const auto& r : results) num_covered_bases += (double)genomes[r.genome_index].gn_size * r.final_est_cov;
+    uint64_t num_total_counts = 0;
+    for (const uint32_t count : S.counts) num_total_counts += count;
+    const double num_tentative_bases = (double)(S.c * num_total_counts) * multiplier;
+    if (num_tentative_bases == 0.) return 0.;
+    return std::min(num_covered_bases / num_tentative_bases, 1.);
+}
+
+namespace {
+struct UploadGuard { sylph_upload* u = nullptr; ~UploadGuard() { sylph_upload_destroy(u); } };
+// The genomes' k-mers (tracked: their pseudotax_tracked_nonused_kmers) go from where they lie — the mapped .syldb files (views), or
+// the vectors of genomes sketched in this run — through the library's page-locked upload chunks to the device, gathered by all
+// parse threads: no per-genome vector, no flat host copy, the copy of one chunk travels while the next is gathered (round 4;
+// rounds 1-3: 113,104 vectors + one 11 GB concatenation + a staged pageable copy).  off: the genomes' offsets in the flat array.
+const uint64_t* upload_gathered(sylph_ctx* ctx, const std::vector<GenomeSketch>& genome_sketches, bool tracked, std::vector<uint64_t>& off,
+                                UploadGuard& guard) {
+    off.assign(1, 0);
+    for (const auto& g : genome_sketches) off.push_back(off.back() + (tracked ? g.n_tracked() : g.n_kmers()));
+    const uint64_t total = off.back() * 8;
+    sylph_upload* up = nullptr;
+    hip_check(sylph_upload_begin(ctx, total, 256ull << 20, &up), "sylph_upload_begin");
+    guard.u = up;
+    const unsigned T = std::max(1u, parse_threads());
+    uint64_t at = 0;                                   // bytes of the flat array gathered so far
+    size_t g0 = 0;                                     // first genome that still has bytes to give
+    while (at < total) {
+        void* chunk = nullptr;
+        uint64_t cap = 0;
+        hip_check(sylph_upload_chunk(up, &chunk, &cap), "sylph_upload_chunk");
+        const uint64_t n = std::min<uint64_t>(cap & ~7ull, total - at);
+        std::vector<std::thread> th;
+        std::exception_ptr err;
+        auto piece = [&](unsigned w) {
+            const uint64_t b0 = at + n / T * w / 8 * 8, b1 = w + 1 == T ? at + n : at + n / T * (w + 1) / 8 * 8;
+            size_t g = (size_t)(std::upper_bound(off.begin() + (long)g0, off.end(), b0 / 8) - off.begin()) - 1;   // genome holding byte b0
+            for (uint64_t b = b0; b < b1;) {
+                while (off[g + 1] * 8 <= b) g++;
+                const GenomeSketch& gs = genome_sketches[g];
+                const uint8_t* src = tracked ? gs.tracked_bytes() : gs.kmers_bytes();
+                const uint64_t in_g = b - off[g] * 8, len = std::min<uint64_t>(off[g + 1] * 8 - b, b1 - b);
+                memcpy((uint8_t*)chunk + (b - at), src + in_g, len);
+                b += len;
+            }
+        };
+        for (unsigned w = 1; w < T; w++) th.emplace_back(piece, w);
+        piece(0);
+        for (auto& t : th) t.join();
+        hip_check(sylph_upload_commit(up, n), "sylph_upload_commit");
+        at += n;
+        while (g0 + 1 < off.size() && off[g0 + 1] * 8 <= at) g0++;
+    }
+    const void* dev = nullptr;
+    hip_check(sylph_upload_finish(up, &dev), "sylph_upload_finish");
+    return (const uint64_t*)dev;
+}
+// an offsets array travels the same way (a few hundred KB)
+const uint64_t* upload_offsets(sylph_ctx* ctx, const std::vector<uint64_t>& off, UploadGuard& guard) {
+    hip_check(sylph_upload_begin(ctx, off.size() * 8, 1u << 20, &guard.u), "sylph_upload_begin");
+    for (size_t i = 0; i < off.size();) {
+        void* chunk = nullptr;
+        uint64_t cap = 0;
+        hip_check(sylph_upload_chunk(guard.u, &chunk, &cap), "sylph_upload_chunk");
+        const size_t m = std::min<size_t>(off.size() - i, cap / 8);
+        memcpy(chunk, off.data() + i, m * 8);
+        hip_check(sylph_upload_commit(guard.u, m * 8), "sylph_upload_commit");
+        i += m;
+    }
+    const void* dev = nullptr;
+    hip_check(sylph_upload_finish(guard.u, &dev), "sylph_upload_finish");
+    return (const uint64_t*)dev;
+}
+
+// ---- one sample's results -> statistics -> (profile: reassignment pass) -> TSV rows.  `cc / coff / covs` are the first-pass
+// views (coverage values cov_width bytes each); the sample table is given where it lies (tk / tc / tn in tmem) for the
+// reassignment probe; S carries the metadata, and the counts on the host when -u needs them.
+struct ReportTo {   // what every sample's report shares
+    const ContainCmdArgs& args;
+    const std::vector<GenomeSketch>& genome_sketches;   // the database, in the order of its device-side index
+    FILE* out;
+};
+void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const uint32_t* cc, const uint64_t* coff, const void* covs,
+            uint32_t cov_width, const uint64_t* tk, const uint32_t* tc, uint64_t tn, int tmem, sylph_db* rdb) {
+    const ContainCmdArgs& args = to.args;
+    const std::vector<GenomeSketch>& genome_sketches = to.genome_sketches;
+    FILE* const out = to.out;
+    if (genome_sketches[0].k != S.k) throw Error{1, "k parameter for reads != k parameter for genome"};   // contain.rs:608-615
+    const std::string seq_name = S.sample_name ? *S.sample_name : S.file_name;   // :775-781
+    auto cov_vector = [&](const void* base, uint32_t width, uint64_t lo, uint64_t hi) {
+        std::vector<uint32_t> cv(hi - lo);
+        if (width == 4) memcpy(cv.data(), (const uint32_t*)base + lo, (hi - lo) * 4);
+        else if (width == 2) for (uint64_t i = lo; i < hi; i++) cv[i - lo] = ((const uint16_t*)base)[i];
+        else for (uint64_t i = lo; i < hi; i++) cv[i - lo] = ((const uint8_t*)base)[i];
+        return cv;
+    };
+    std::vector<AniResult> stats;
+    {   // the statistics of different genomes are independent (contain.rs:284 runs them on the rayon pool): -t threads,
+        // results gathered in genome order so that the output does not depend on the interleaving
+        std::vector<size_t> with_hits;
+        for (size_t g = 0; g < genome_sketches.size(); g++) {
+            if (genome_sketches[g].c < S.c) throw Error{1, "c parameter for reads > c parameter for genome"};   // :616-623
+            if (cc[g] != 0) with_hits.push_back(g);                  // :654
+        }
+        std::vector<std::optional<AniResult>> res(with_hits.size());
+        parallel_for(with_hits.size(), args.threads, [&](size_t i) {
+            const size_t g = with_hits[i];
+            res[i] = stats_from_covs(args, cov_vector(covs, cov_width, coff[g], coff[g + 1]), genome_sketches[g].n_kmers(), S.k, std::nullopt);
+            if (res[i]) res[i]->genome_index = g;
+        });
+        for (auto& r : res) if (r) stats.push_back(*r);
+    }
+    std::optional<double> kmer_id_opt;                               // contain.rs:274-281
+    if (args.seq_id) kmer_id_opt = std::pow(*args.seq_id / 100., (double)S.k);
+    else kmer_id_opt = get_kmer_identity(S, args.estimate_unknown);
+    estimate_true_cov(stats, kmer_id_opt, args.estimate_unknown, S.mean_read_length, S.k);   // :295
+    if (args.pseudotax) {
+        info(first_file + " taxonomic profiling; reassigning k-mers for " + std::to_string(stats.size()) + " genomes...");
+        // winner_table (contain.rs:410-430) + second get_stats pass with the winner map (:300-307, :637-646) on the
+        // device: one more probe of the resident postings (genome_kmers + tracked k-mers), passing genomes only.
+        std::vector<uint32_t> pg(stats.size());
+        std::vector<double> pa(stats.size());
+        for (size_t i = 0; i < stats.size(); i++) { pg[i] = (uint32_t)stats[i].genome_index; pa[i] = stats[i].final_est_ani; }
+        const uint32_t *cc2 = nullptr, *covs2 = nullptr, *lost2 = nullptr;
+        const uint64_t* coff2 = nullptr;
+        uint64_t ncov2 = 0;
+        hip_check(sylph_db_reassign_view(rdb, tk, tc, tn, tmem, pg.data(), pa.data(), (uint32_t)pg.size(), &cc2, &coff2, &covs2, &ncov2, &lost2),
+                  "sylph_db_reassign_view");
+        std::vector<AniResult> stats2;
+        std::vector<std::optional<AniResult>> res2(stats.size());
+        parallel_for(stats.size(), args.threads, [&](size_t i) {
+            const size_t g = stats[i].genome_index;
+            std::vector<uint32_t> cv(covs2 + coff2[g], covs2 + coff2[g + 1]);
+            res2[i] = stats_from_covs(args, std::move(cv), genome_sketches[g].n_kmers(), S.k, (size_t)lost2[g]);
+            if (res2[i]) res2[i]->genome_index = g;
+        });
+        for (size_t i = 0; i < stats.size(); i++) {
+            const auto& r = res2[i];
+            if (!r) continue;
+            // derep_if_reassign_threshold, contain.rs:353-375
+            const double thr = std::pow(args.redundant_ani / 100., (double)S.k) * (double)r->n_kmers;
+            if ((double)(stats[i].contain_count - r->contain_count) < thr) stats2.push_back(*r);
+        }
+        stats.swap(stats2);
+        estimate_true_cov(stats, kmer_id_opt, args.estimate_unknown, S.mean_read_length, S.k);   // :310
+        info(first_file + " has " + std::to_string(stats.size()) + " genomes passing profiling threshold. ");
+        double bases_explained = 1.;                                 // :313-317
+        if (args.estimate_unknown) {
+            bases_explained = estimate_covered_bases(stats, genome_sketches, S, S.mean_read_length, S.k);
+            char buf[64];
+            snprintf(buf, sizeof buf, "%.2f", bases_explained * 100.);
+            info(first_file + " has " + buf + "% of reads detected in database by profile");
+        }
+        double total_cov = 0, total_seq_cov = 0;                     // contain.rs:319-326
+        for (const auto& r : stats) { total_cov += r.final_est_cov; total_seq_cov += r.final_est_cov * (double)genome_sketches[r.genome_index].gn_size; }
+        for (auto& r : stats) r.rel_abund = r.final_est_cov / total_cov * 100.;
+        for (auto& r : stats) r.seq_abund = r.final_est_cov * (double)genome_sketches[r.genome_index].gn_size / total_seq_cov * 100. * bases_explained;
+        std::stable_sort(stats.begin(), stats.end(), [](const AniResult& x, const AniResult& y) { return *y.rel_abund < *x.rel_abund; });   // :330
+    } else {
+        std::stable_sort(stats.begin(), stats.end(), [](const AniResult& x, const AniResult& y) { return y.final_est_ani < x.final_est_ani; });   // :333
+    }
+    for (const auto& r : stats) print_ani_result(r, seq_name, genome_sketches[r.genome_index], args.pseudotax, out, args.debug_f64);
+}
+
+void finished(const std::vector<std::string>& files) {
+    info(std::string(files.size() > 1 ? "Finished paired sample " : "Finished sample ") + files[0] + ".");
+}
+
+// get_genome_sketches, contain.rs:482-541: the *.syldb files as they are, the genome files sketched here
+std::vector<GenomeSketch> load_genome_sketches(Engine& e, const ContainCmdArgs& args, const std::vector<std::string>& genome_sketch_files,
+                                               const std::vector<std::string>& genome_files) {
+    std::vector<GenomeSketch> genome_sketches;
+    std::optional<uint64_t> lowest_genome_c, current_k;
+    static const bool copy_load = getenv("SYLPH_HIP_DB_COPY_LOAD") != nullptr;   // A/B + tests: every genome copied into vectors first (rounds 1-3)
+    for (const auto& f : genome_sketch_files) {
+        auto v = copy_load ? read_syldb(f) : read_syldb_views(f);
+        if (v.empty()) continue;
+        const uint64_t c = v.front().c, k = v.front().k;
+        if (!lowest_genome_c || *lowest_genome_c < c) lowest_genome_c = c;
+        if (!current_k) current_k = k;
+        else if (*current_k != k) throw Error{1, "Query sketches have inconsistent -k. Exiting."};
+        for (auto& g : v) genome_sketches.push_back(std::move(g));
+    }
+    GenomeBatch batch(e, args.c, args.k, args.min_spacing_kmer, args.pseudotax, genome_sketches);
+    std::vector<std::string> genome_files_ok;
+    for (const auto& gf : genome_files) {
+        if (lowest_genome_c && *lowest_genome_c < args.c) { fprintf(stderr, "ERROR [sylph_hip] Value of -c for contain is %llu -- greater than the smallest value of -c for a genome sketch %llu. Continuing without sketching.\n", (unsigned long long)args.c, (unsigned long long)*lowest_genome_c); continue; }
+        if (current_k && *current_k != args.k) { fprintf(stderr, "ERROR [sylph_hip] -k %llu is not equal to -k %llu found in sketches. Continuing without sketching.\n", (unsigned long long)args.k, (unsigned long long)*current_k); continue; }
+        genome_files_ok.push_back(gf);
+    }
+    batch.add_files(genome_files_ok, args.individual, args.threads);
+    batch.flush();
+    info("Finished obtaining genome sketches.");
+    if (genome_sketches.empty()) throw Error{1, "No genome sketches found; see sylph query/profile -h for help. Exiting"};
+    if (!genome_sketches.front().has_tracked() && args.pseudotax)
+        throw Error{1, "Attempting profiling, but *.syldb was sketched with the --disable-profiling option. Exiting"};   // :234-237
+
+    return genome_sketches;
+}
+
+// (destroyed even on the fast way out: a 29 GB index left to the driver's own clean-up at process exit is released BEHIND the
+//  process — the next command's database load then took 2.7 s instead of 0.7: profiles/r05_db_load_with_forked_profile.txt)
+struct DbGuard { sylph_db* d = nullptr; ~DbGuard() { sylph_db_destroy(d); } };
+void upload_database(Engine& e, const std::vector<GenomeSketch>& genome_sketches, bool pseudotax, DbGuard& db) {
+    // database resident in HBM (replaces the per-genome probe loop of contain.rs:284-291)
+    const auto t_db0 = std::chrono::steady_clock::now();
+    sylph_ctx* const ctx = e.context();
+    std::vector<uint64_t> goff;
+    {
+        UploadGuard ug, og;
+        const uint64_t* d_k = upload_gathered(ctx, genome_sketches, false, goff, ug);
+        hip_check(sylph_db_upload(ctx, d_k, upload_offsets(ctx, goff, og), genome_sketches.size(), SYLPH_MEM_DEVICE, &db.d), "sylph_db_upload");
+    }
+    if (pseudotax) {   // the winner table also ranges over pseudotax_tracked_nonused_kmers (contain.rs:421-428)
+        UploadGuard ug, og;
+        std::vector<uint64_t> toff;
+        const uint64_t* d_t = upload_gathered(ctx, genome_sketches, true, toff, ug);
+        hip_check(sylph_db_attach_tracked(db.d, d_t, upload_offsets(ctx, toff, og), SYLPH_MEM_DEVICE), "sylph_db_attach_tracked");
+    }
+    if (getenv("SYLPH_HIP_FEED_TRACE") || getenv("SYLPH_HIP_DEBUG")) {
+        char b[200];
+        snprintf(b, sizeof(b), "timing: database of %zu genomes (%llu k-mers) uploaded and indexed in %.3f s", genome_sketches.size(),
+                 (unsigned long long)goff.back(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t_db0).count());
+        info(b);
+    }
+}
+
+// ---- raw read samples (contain.rs:239-291 sketches and profiles them chunk by chunk on the rayon pool).  Here: up to `-t`
+// sample threads, each with a GPU context of its own, read + index + pack + push their files into sessions, in input order;
+// the sessions go through a sylph_pipeline (finish on the device -> probe, tables never leave HBM), and this thread takes the
+// results in input order and does the statistics and the printing: the feed of sample j + 1 .. overlaps with the profile of
+// sample j and the statistics of sample j - 1.
+void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vector<std::vector<std::string>>& read_files, sylph_db* db,
+                         const ReportTo& to) {
+    const size_t n_raw = read_files.size();
+    const uint64_t genome_c = to.genome_sketches[0].c, genome_k = to.genome_sketches[0].k;
+    struct Prepared { std::optional<SequencesSketch> meta; sylph_sketch* session = nullptr; std::exception_ptr error; };
+    std::vector<std::promise<Prepared>> promises(n_raw);
+    std::vector<std::future<Prepared>> futures;
+    for (auto& p : promises) futures.push_back(p.get_future());
+    // --gpus N|all: the database replicated on N GPUs (index copied device to device), sample threads dealt to them in turn,
+    // one router pipeline over the replicas (sylph_pipeline_create_multi): the reference's sample loop spans the machine through
+    // its rayon pool (contain.rs:252-295), this is the same for the GPUs of a node.  One GPU: everything as before.
+    // (SYLPH_HIP_SHARE_GPUS=1: more replicas than devices — they wrap around; how the one-GPU test box runs `--gpus 2`)
+    int n_gpus = args.gpus < 0 ? sylph_device_count() : getenv("SYLPH_HIP_SHARE_GPUS") ? args.gpus : std::min(args.gpus, std::max(1, sylph_device_count()));
+    n_gpus = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_gpus), n_raw));
+    std::vector<std::unique_ptr<Engine>> replica_engines;            // (declared before the replicas: destroyed after them)
+    struct Replicas { std::vector<sylph_db*> v; ~Replicas() { for (size_t i = 1; i < v.size(); i++) sylph_db_destroy(v[i]); } } replicas;
+    std::vector<sylph_db*>& dbs = replicas.v;
+    dbs.push_back(db);
+    std::vector<int> replica_device{e.device};
+    {
+        int dev0 = e.device;
+        if (dev0 < 0) dev0 = 0;                                      // (Engine(-1) = the current device = 0 in a fresh process)
+        replica_device[0] = e.device;
+        const auto t_r0 = std::chrono::steady_clock::now();
+        for (int g = 1; g < n_gpus; g++) {
+            const int dev = (dev0 + g) % std::max(1, sylph_device_count());
+            replica_engines.emplace_back(new Engine(dev));
+            sylph_db* r = nullptr;
+            hip_check(sylph_db_replicate(db, replica_engines.back()->context(), &r), "sylph_db_replicate");
+            dbs.push_back(r);
+            replica_device.push_back(dev);
+        }
+        if (n_gpus > 1) {
+            char b[160];
+            snprintf(b, sizeof(b), "database replicated on %d GPUs (device to device) in %.3f s", n_gpus,
+                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_r0).count());
+            info(b);
+        }
+    }
+    std::atomic<size_t> worker_no{0};
+    const size_t n_workers = sample_workers(args.threads, (size_t)n_gpus, n_raw);
+    const size_t ahead_limit = n_workers + 2;                        // sessions that may wait, sketched, for the profile stage
+    std::vector<SampleFiles> job_files;
+    for (const auto& r : read_files) job_files.push_back({r[0], r.size() > 1 ? std::optional<std::string>(r[1]) : std::nullopt});
+    FeedShared feed(std::move(job_files), n_workers);
+    std::atomic<size_t> next_job{0}, released{0};
+    std::atomic<bool> cancel{false};
+    std::mutex gate_mu;
+    std::condition_variable gate_cv;
+    // contain.rs:591: raw pairs are sketched with the default filter (DEFAULT_FPR) — unless the exact set is asked for (not in the reference)
+    const double raw_pair_fpr = exact_dedup_accepted(args.exact_dedup) ? 0. : DEFAULT_FPR;
+    auto prepare = [&](Engine& eng, size_t j) {
+        Prepared pr;
+        try {
+            const auto& files = read_files[j];
+            if (genome_c < args.c) {
+                fprintf(stderr, "ERROR [sylph_hip] %s error: value of -c for contain = %llu -- greater than the smallest value of -c for a genome sketch = %llu. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.c, (unsigned long long)genome_c);
+            } else if (genome_k != args.k) {
+                fprintf(stderr, "ERROR [sylph_hip] %s -k %llu is not equal to -k %llu found in sketches. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.k, (unsigned long long)genome_k);
+            } else {
+                SampleRoute route(eng, feed, j, false);
+                SampleParams p;   // contain.rs:591: no sample name, duplicates always removed
+                p.c = args.c; p.k = args.k; p.dedup_fpr = raw_pair_fpr;
+                pr.meta = sketch_sample(eng, feed.ahead.files(j), p, route, &pr.session);
+            }
+        } catch (...) { pr.error = std::current_exception(); }
+        promises[j].set_value(std::move(pr));
+    };
+    auto worker = [&] {
+        // every sample thread brings its own context: the database's context (the caller's engine) stays free for the
+        // profile stage and the reassignment probes
+        std::unique_ptr<Engine> own;
+        Engine* eng = nullptr;
+        try { own.reset(new Engine(replica_device[worker_no++ % replica_device.size()])); eng = own.get(); }
+        catch (...) { eng = nullptr; }
+        for (;;) {
+            const size_t j = next_job++;
+            if (j >= n_raw) return;
+            {   // do not run further ahead of the consumer than ahead_limit samples (their sessions hold HBM)
+                std::unique_lock<std::mutex> lk(gate_mu);
+                gate_cv.wait(lk, [&] { return cancel.load() || j < released.load() + ahead_limit; });
+            }
+            if (cancel) { promises[j].set_value(Prepared{}); continue; }
+            if (!eng) { Prepared pr; pr.error = std::make_exception_ptr(Error{1, "could not create a GPU context for a sample thread"}); promises[j].set_value(std::move(pr)); continue; }
+            prepare(*eng, j);
+        }
+    };
+    sylph_pipeline* pipe = nullptr;
+    sylph_pipeline_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.struct_size = sizeof(cfg);
+    cfg.n_workers = 2;                       // (they only finish the sessions the sample threads pushed)
+    cfg.depth = (uint32_t)ahead_limit + 1;
+    cfg.max_batch = 4;
+    cfg.c = (uint32_t)args.c; cfg.k = (uint32_t)args.k;
+    cfg.reads_mode = SYLPH_READS_PAIRED; cfg.seed_mode = SYLPH_SEED_AVX2_COMPAT;
+    cfg.want_table = args.estimate_unknown ? 1 : 0;                 // -u walks the counts on the host
+    cfg.min_number_kmers = args.min_number_kmers;
+    if (n_gpus > 1) hip_check(sylph_pipeline_create_multi(dbs.data(), (uint32_t)dbs.size(), &cfg, &pipe), "sylph_pipeline_create_multi");
+    else hip_check(sylph_pipeline_create(db, &cfg, &pipe), "sylph_pipeline_create");
+    struct PipeGuard { sylph_pipeline* p; ~PipeGuard() { sylph_pipeline_destroy(p); } } pipe_guard{pipe};
+    std::vector<std::thread> pool;
+    size_t submitted = 0;
+    struct Unconsumed {   // (declared before PoolJoin: runs after the sample threads are joined) sessions nobody took over
+        std::vector<std::future<Prepared>>& futures; size_t& submitted;
+        ~Unconsumed() {
+            for (size_t j = submitted; j < futures.size(); j++) {
+                if (!futures[j].valid() || futures[j].wait_for(std::chrono::seconds(0)) != std::future_status::ready) continue;
+                try { Prepared pr = futures[j].get(); if (pr.session) sylph_sketch_destroy(pr.session); } catch (...) {}
+            }
+        }
+    } unconsumed{futures, submitted};
+    struct PoolJoin {   // on every way out: the sample threads stop taking work and are joined
+        std::vector<std::thread>& pool; std::atomic<bool>& cancel; std::mutex& mu; std::condition_variable& cv;
+        ~PoolJoin() {
+            { std::lock_guard<std::mutex> lk(mu); cancel = true; }
+            cv.notify_all();
+            for (auto& t : pool) if (t.joinable()) t.join();
+        }
+    } pool_join{pool, cancel, gate_mu, gate_cv};
+    for (size_t w = 0; w < n_workers; w++) pool.emplace_back(worker);
+    std::vector<std::optional<SequencesSketch>> metas(n_raw);
+    std::vector<char> submitted_ok(n_raw, 0);
+    size_t done = 0;
+    auto release_one = [&] { { std::lock_guard<std::mutex> lk(gate_mu); released++; } gate_cv.notify_all(); };
+    while (done < n_raw) {
+        // hand over every prepared sample that is ready, in input order (wait for one only when nothing is outstanding)
+        while (submitted < n_raw && sylph_pipeline_outstanding(pipe) < cfg.depth) {
+            const bool must_wait = sylph_pipeline_outstanding(pipe) == 0 && submitted == done;
+            if (!must_wait && futures[submitted].wait_for(std::chrono::seconds(0)) != std::future_status::ready) break;
+            Prepared pr = futures[submitted].get();
+            if (pr.error) { if (pr.session) sylph_sketch_destroy(pr.session); submitted++; std::rethrow_exception(pr.error); }
+            metas[submitted] = std::move(pr.meta);
+            if (metas[submitted] && pr.session) {
+                hip_check(sylph_pipeline_submit_session(pipe, pr.session, submitted), "sylph_pipeline_submit_session");
+                submitted_ok[submitted] = 1;
+            } else if (pr.session) sylph_sketch_destroy(pr.session);
+            submitted++;
+        }
+        const size_t j = done;
+        if (j >= submitted) continue;        // (the wait above guarantees progress)
+        if (submitted_ok[j]) {
+            sylph_pipeline_result r;
+            hip_check(sylph_pipeline_next(pipe, &r), "sylph_pipeline_next");
+            if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + read_files[j][0] + ": " + (r.error ? r.error : "GPU stage failed")};
+            SequencesSketch& S = *metas[j];
+            if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+            report(to, S, read_files[j][0], r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
+                   dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))]);
+        }
+        finished(read_files[j]);
+        metas[j].reset();
+        done++;
+        release_one();
+    }
+}
+
+// ---- samples given as sketches (*.sylsp): the table is on the host
+void profile_sketch_files(const ContainCmdArgs& args, const std::vector<std::string>& read_sketch_files, sylph_db* db, const ReportTo& to) {
+    const uint64_t genome_c = to.genome_sketches[0].c;
+    for (const auto& sf : read_sketch_files) {
+        const std::vector<std::string> files{sf};
+        // get_seq_sketch, contain.rs:544-599
+        std::optional<SequencesSketch> seq;
+        {
+            SequencesSketch s = read_sylsp(files[0]);
+            if (s.c > genome_c) { fprintf(stderr, "ERROR [sylph_hip] %s value of -c is %llu; this is greater than the smallest value of -c = %llu for a genome sketch. Exiting.\n", files[0].c_str(), (unsigned long long)s.c, (unsigned long long)genome_c); }
+            else seq = std::move(s);
+        }
+        if (seq) {
+            const SequencesSketch& S = *seq;
+            // first pass: GPU probe of every genome, then host statistics
+            const uint32_t* cc = nullptr; const uint64_t* coff = nullptr; const uint32_t* covs = nullptr; uint64_t ncov = 0;
+            hip_check(sylph_db_contain_view(db, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST,
+                                            args.min_number_kmers, &cc, &coff, &covs, &ncov), "sylph_db_contain_view");
+            report(to, S, files[0], cc, coff, covs, 4, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST, db);
+        }
+        finished(files);
+    }
+}
+}  // namespace
+
+// contain.rs:115-351
+int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
+    if (pseudotax_in) args.pseudotax = true;
+    std::vector<std::string> genome_sketch_files, genome_files, read_sketch_files;
+    std::vector<std::vector<std::string>> read_files;
+    std::vector<std::string> all_files = args.files;
+    if (args.file_list) parse_line_file(*args.file_list, all_files);
+    auto ends = [](const std::string& s, const char* suf) { const size_t n = strlen(suf); return s.size() >= n && s.compare(s.size() - n, n, suf) == 0; };
+    for (const auto& f : all_files) {                                        // contain.rs:165-198
+        if (ends(f, ".syldb") || ends(f, ".sylqueries")) genome_sketch_files.push_back(f);
+        else if (ends(f, ".sylsp") || ends(f, ".sylsample")) read_sketch_files.push_back(f);
+        else if (is_fasta(f)) genome_files.push_back(f);
+        else if (is_fastq(f)) read_files.push_back({f});
+        else warn(f + " file extension is not a sketch or a fasta/fastq file.");
+    }
+    if (args.first_pair.size() != args.second_pair.size())
+        throw Error{1, "Different number of paired sequences (-1, -2) for sketching. Exiting."};
+    for (size_t i = 0; i < args.first_pair.size(); i++) read_files.push_back({args.first_pair[i], args.second_pair[i]});
+    for (const auto& r : args.reads) read_files.push_back({r});
+    if (genome_sketch_files.empty() && genome_files.empty())
+        throw Error{1, "No genome files found; see sylph query/profile -h for help. Exiting"};
+    if (read_sketch_files.empty() && read_files.empty())
+        throw Error{1, "No read files found; see sylph query/profile -h for help. Exiting"};
+
+    const std::vector<GenomeSketch> genome_sketches = load_genome_sketches(e, args, genome_sketch_files, genome_files);
+    DbGuard db;
+    upload_database(e, genome_sketches, args.pseudotax, db);
+
+    print_header(args.pseudotax, out, args.estimate_unknown);
+    const ReportTo to{args, genome_sketches, out};
+    if (!read_files.empty()) profile_raw_samples(e, args, read_files, db.d, to);
+    profile_sketch_files(args, read_sketch_files, db.d, to);
+    fflush(out);
+    join_background();
+    info("sylph finished.");
+    return 0;
+}
+
+}  // namespace sylph_host

@@ -1,0 +1,273 @@
+// cmd_sketch.cpp — the `sketch` command (sketch.rs:276-479) and the genome batches behind it: parse records on the host, push
+// batches through the C ABI, write the reference's .sylsp / .syldb files.
+#include <cstring>
+
+#include "host_internal.hpp"
+
+namespace sylph_host {
+
+GenomeBatch::Parsed GenomeBatch::parse_file(const std::string& ref_file, bool individual) {
+    Parsed p;
+    p.file = ref_file;
+    std::unique_ptr<FastxReader> reader;
+    try { reader.reset(new FastxReader(ref_file)); }
+    catch (const Error&) { p.warnings.push_back(ref_file + " is not a valid fasta/fastq file; skipping."); return p; }
+    FastxRecord rec;
+    try {
+        while (reader->next(rec)) {
+            if (individual || p.ids.empty()) p.ids.push_back(rec.id);
+            p.bases.insert(p.bases.end(), rec.seq.begin(), rec.seq.end());
+            p.ends.push_back(p.bases.size());
+        }
+    } catch (const Error&) {                                             // :586-589: the whole file is dropped
+        p.warnings.push_back("File " + ref_file + " is not a valid fasta/fastq file");
+        return p;
+    }
+    p.ok = true;
+    return p;
+}
+
+void GenomeBatch::add_files(const std::vector<std::string>& files, bool individual, uint64_t threads) {
+    const size_t window = std::max<size_t>(1, std::min<size_t>(threads, 64)) * 2;
+    for (size_t lo = 0; lo < files.size(); lo += window) {
+        const size_t n = std::min(window, files.size() - lo);
+        std::vector<Parsed> parsed(n);
+        std::atomic<size_t> next{0};
+        auto work = [&] { for (size_t i = next++; i < n; i = next++) parsed[i] = parse_file(files[lo + i], individual); };
+        std::vector<std::thread> pool;
+        for (size_t w = 1; w < std::min<size_t>(std::max<uint64_t>(threads, 1), n); w++) pool.emplace_back(work);
+        work();
+        for (auto& t : pool) t.join();
+        for (auto& p : parsed) append(std::move(p), individual);
+    }
+}
+
+bool GenomeBatch::append(Parsed p, bool individual) {
+    for (const auto& w : p.warnings) warn(w);
+    if (!p.ok) return false;
+    const std::string& ref_file = p.file;
+    // one sylph_sketch_genomes call holds < 2^32 bases: a file that would push the batch over the limit starts a new batch,
+    // and a single genome beyond it is skipped with a warning instead of aborting the whole run
+    constexpr uint64_t LIMIT = (1ull << 32) - 4096;
+    if (p.bases.size() >= LIMIT) {
+        warn(ref_file + " holds " + std::to_string(p.bases.size()) + " bases, more than one device batch (2^32): skipping it");
+        return false;
+    }
+    if (bases.size() + p.bases.size() >= LIMIT) flush();
+    const uint64_t bases0 = bases.size();
+    bases.insert(bases.end(), p.bases.begin(), p.bases.end());
+    for (size_t r = 0; r < p.ends.size(); r++) {
+        off.push_back(bases0 + p.ends[r]);
+        if (individual) {
+            GenomeSketch g;
+            g.file_name = ref_file; g.first_contig_name = p.ids[r]; g.gn_size = p.ends[r] - (r ? p.ends[r - 1] : 0);
+            pending.push_back(std::move(g));
+            goff.push_back(off.size() - 1);
+        }
+    }
+    if (!individual) {
+        GenomeSketch whole;
+        whole.file_name = ref_file;
+        if (!p.ids.empty()) whole.first_contig_name = p.ids.front();
+        whole.gn_size = p.bases.size();
+        pending.push_back(std::move(whole));
+        goff.push_back(off.size() - 1);
+    }
+    if (bases.size() >= BATCH_BASES) flush();
+    return true;
+}
+
+void GenomeBatch::flush() {
+    if (pending.empty()) return;
+    const uint64_t G = pending.size();
+    std::vector<uint64_t> koff(G + 1), toff(G + 1);
+    uint64_t *gk = nullptr, *tr = nullptr;
+    hip_check(sylph_sketch_genomes(e.context(), bases.data(), off.data(), off.size() - 1, goff.data(), G, (uint32_t)c, (uint32_t)k,
+                                   SYLPH_SEED_AVX2_COMPAT, min_spacing, pseudotax ? 1 : 0, SYLPH_MEM_HOST, &gk, koff.data(), &tr,
+                                   toff.data()),
+              "sylph_sketch_genomes");
+    struct Free { uint64_t* p; ~Free() { sylph_free(p); } } f1{gk}, f2{tr};
+    for (uint64_t g = 0; g < G; g++) {
+        GenomeSketch& s = pending[g];
+        s.genome_kmers.assign(gk + koff[g], gk + koff[g + 1]);
+        if (pseudotax) s.pseudotax_tracked_nonused_kmers = std::vector<uint64_t>(tr + toff[g], tr + toff[g + 1]);
+        s.c = c; s.k = k; s.min_spacing = min_spacing;
+        out.push_back(std::move(s));
+    }
+    pending.clear(); bases.clear(); off.assign(1, 0); goff.assign(1, 0);
+}
+
+// sketch.rs:550-622
+std::optional<GenomeSketch> sketch_genome(Engine& e, uint64_t c, uint64_t k, const std::string& ref_file, uint64_t min_spacing,
+                                          bool pseudotax) {
+    std::vector<GenomeSketch> out;
+    GenomeBatch b(e, c, k, min_spacing, pseudotax, out);
+    if (!b.add_file(ref_file, false)) return std::nullopt;
+    b.flush();
+    return std::move(out.front());
+}
+
+// sketch.rs:481-548
+std::vector<GenomeSketch> sketch_genome_individual(Engine& e, uint64_t c, uint64_t k, const std::string& ref_file,
+                                                   uint64_t min_spacing, bool pseudotax) {
+    std::vector<GenomeSketch> out;
+    GenomeBatch b(e, c, k, min_spacing, pseudotax, out);
+    b.add_file(ref_file, true);
+    b.flush();
+    return out;
+}
+
+// sketch.rs:276-479
+int sketch(Engine& e, const SketchArgs& args) {
+    std::vector<std::string> read_inputs, genome_inputs, first_pairs, second_pairs;
+    const bool nothing = args.files.empty() && !args.list_sequence && args.first_pair.empty() && args.second_pair.empty() &&
+                         args.genomes.empty() && args.reads.empty() && !args.list_genomes && !args.list_reads &&
+                         !args.list_first_pair && !args.list_second_pair;
+    if (nothing) throw Error{1, "No input sequences found; see sylph sketch -h for help. Exiting."};   // :144-157
+    if (args.fpr < 0. || args.fpr >= 1.) throw Error{1, "Invalid FPR for sketching. Must be in [0,1)."};   // :158-161
+    std::vector<std::string> all_files;
+    if (args.list_sequence) parse_line_file(*args.list_sequence, all_files);
+    all_files.insert(all_files.end(), args.files.begin(), args.files.end());
+    for (const auto& f : all_files) {                                        // :164-189
+        if (is_fastq(f)) read_inputs.push_back(f);
+        else if (is_fasta(f)) genome_inputs.push_back(f);
+        else warn(f + " does not have a fasta/fastq/gzip type extension; skipping");
+    }
+    genome_inputs.insert(genome_inputs.end(), args.genomes.begin(), args.genomes.end());   // :191-216
+    read_inputs.insert(read_inputs.end(), args.reads.begin(), args.reads.end());
+    if (args.list_reads) parse_line_file(*args.list_reads, read_inputs);
+    if (args.list_genomes) parse_line_file(*args.list_genomes, genome_inputs);
+    if (args.first_pair.size() != args.second_pair.size()) throw Error{1, "Different number of paired sequences. Exiting."};
+    first_pairs = args.first_pair;
+    second_pairs = args.second_pair;
+    if (args.list_first_pair) parse_line_file(*args.list_first_pair, first_pairs);
+    if (args.list_second_pair) parse_line_file(*args.list_second_pair, second_pairs);
+    if (first_pairs.size() != second_pairs.size()) throw Error{1, "Different number of paired sequences. Exiting."};
+    std::optional<std::vector<std::string>> sample_names;                    // :260-274
+    if (args.list_sample_names) { sample_names.emplace(); parse_line_file(*args.list_sample_names, *sample_names); }
+    else if (args.sample_names) sample_names = args.sample_names;
+    if (sample_names && sample_names->size() != first_pairs.size() + read_inputs.size())
+        throw Error{1, "Sample name length is not equal to the number of reads. Exiting"};   // :288-292
+    // a10: pairs are deduplicated as the reference does — --fpr != 0 (default 1e-4, cmdline.rs:77): the set behind a cuckoo filter
+    // (sketch.rs:733-769; the session option "dedup_fpr"); --fpr 0: the exact set (:690-731).  --exact-dedup / SYLPH_HIP_EXACT_DEDUP=1
+    // (not in the reference) force the exact set whatever --fpr says.  (--no-dedup never consults the filter: sketch.rs:744.)
+    const double pair_fpr = exact_dedup_accepted(args.exact_dedup) ? 0. : args.fpr;
+
+    // Samples are independent (sketch.rs:313,371 runs them on the rayon pool, `-t`): a pool of `-t` worker threads, each with
+    // its own GPU context (calls on one context are serialised) and its own page-locked batch, takes them in input order.
+    // The parsing / inflating of different samples overlaps; the GPU work of one sample is ~2 ms per Gbp.
+    create_dir_all(args.sample_output_dir);
+    const size_t n_jobs = first_pairs.size() + read_inputs.size();
+    // (a command's first sample is gathered into pageable memory while the GPU runtime comes up and the device route's uploader serves the
+    //  samples BEHIND it: with one sample nobody ever wants the page-locked feed buffers — ~80 ms of hipHostMalloc beside the sample's own
+    //  push, and as much again when the process is torn down)
+    if (n_jobs <= 1) e.defer_pinned.store(true);
+    // --gpus N|all (round 6): the workers are dealt to the node's GPUs — worker w runs on device w mod N, with its own context, page-locked
+    // batch and uploader there; a sample never leaves its GPU, nothing is exchanged ("replicas only" for the sketch stage —
+    // what the reference's rayon pool does with the machine's cores, sketch.rs:313, :371).  At least one worker per GPU.
+    int n_gpus = 1;
+    if (args.gpus != 1) {
+        const int have = std::max(1, sylph_device_count());
+        n_gpus = args.gpus < 0 ? have : std::min(args.gpus, have);
+        if (args.gpus > have) warn("--gpus " + std::to_string(args.gpus) + ": this node has " + std::to_string(have) + " GPU(s); using them all");
+    }
+    // (tests on a one-GPU box: SYLPH_HIP_FAKE_GPUS=N deals the workers as for N GPUs and maps every one of them to device 0)
+    const char* fake = getenv("SYLPH_HIP_FAKE_GPUS");
+    const int n_deal = fake ? std::max(1, atoi(fake)) : n_gpus;
+    const size_t n_workers = sample_workers(args.threads, args.gpus != 1 || fake ? (size_t)n_deal : 1, n_jobs);
+    // the next sample of every worker is indexed while the current one is gathered and pushed
+    std::vector<SampleFiles> job_files;
+    for (size_t j = 0; j < first_pairs.size(); j++) job_files.push_back({first_pairs[j], second_pairs[j]});
+    for (const auto& r : read_inputs) job_files.push_back({r, std::nullopt});
+    FeedShared feed(std::move(job_files), n_workers);
+    // a finished sketch is written by the writers' thread while its worker takes the next sample; the first error is rethrown by the command
+    std::mutex write_mu;
+    std::optional<Error> write_error;
+    auto write_out = [&](const std::string& path, SequencesSketch&& sk, const std::string& what, std::function<void(const SequencesSketch&, const std::string&)> timing) {
+        auto keep = std::make_shared<SequencesSketch>(std::move(sk));
+        auto task = [&write_mu, &write_error, keep, path, what, timing] {
+            try {
+                write_sylsp(path, *keep);
+                trace_mark("sketch: .sylsp written");
+                info("Sketching " + path + " complete.");
+                timing(*keep, what);
+            } catch (const Error& er) {
+                std::lock_guard<std::mutex> lk(write_mu);
+                if (!write_error) write_error = er;
+            }
+        };
+        if (n_jobs > 1) write_behind(task); else task();
+    };
+    struct DrainWriters { ~DrainWriters() { drain_writers(); } } drain_on_exit;     // (also on the way out of an exception: the tasks refer to this frame)
+    auto run_job = [&](Engine& eng, size_t j) {
+        const SampleFiles& files = feed.ahead.files(j);
+        SampleRoute route(eng, feed, j, true);
+        const auto t_job = std::chrono::steady_clock::now();
+        auto timing = [t_job](const SequencesSketch& sk, const std::string& what) {   // (not a reference message: feed measurements)
+            const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_job).count();
+            uint64_t occ = 0;
+            for (uint32_t c : sk.counts) occ += c;
+            char b[256];
+            snprintf(b, sizeof(b), "timing: %s sketched + written in %.3f s (%zu distinct k-mers, %llu counted occurrences)", what.c_str(), sec,
+                     sk.kmers.size(), (unsigned long long)occ);
+            info(b);
+        };
+        const bool paired = files.second.has_value();                        // pairs :311-367, single files :369-420
+        SampleParams p;
+        p.c = args.c; p.k = args.k; p.no_dedup = args.no_dedup; p.dedup_fpr = pair_fpr;
+        if (sample_names) p.sample_name = (*sample_names)[j];
+        auto sk = sketch_sample(eng, files, p, route, nullptr);
+        if (!sk) return;
+        const std::string& name = sk->sample_name ? *sk->sample_name : sk->file_name;
+        const std::string path = path_join(args.sample_output_dir, basename_of(name)) + (paired ? ".paired" : "") + SAMPLE_FILE_SUFFIX;
+        if (paired) trace_mark("sketch: the pair is sketched (table on the host)");
+        write_out(path, std::move(*sk), files.first, timing);
+    };
+    if (n_workers <= 1) {
+        for (size_t j = 0; j < n_jobs; j++) run_job(e, j);
+    } else {
+        std::atomic<size_t> next{0};
+        std::mutex err_mu;
+        std::optional<Error> first_error;
+        std::atomic<size_t> worker_no{1};
+        auto worker = [&](Engine* eng) {
+            try {
+                std::unique_ptr<Engine> own;
+                if (!eng) {
+                    const size_t w = worker_no++;
+                    const int dev = n_deal > 1 ? (fake ? e.device : (int)(w % (size_t)n_deal)) : e.device;
+                    if (n_deal > 1) info("sketch worker " + std::to_string(w) + " runs on GPU " + std::to_string(fake ? (int)(w % (size_t)n_deal) : dev) + (fake ? " (SYLPH_HIP_FAKE_GPUS: device 0)" : ""));
+                    own.reset(new Engine(dev));
+                    eng = own.get();
+                }
+                for (size_t j = next++; j < n_jobs; j = next++) run_job(*eng, j);
+            } catch (const Error& er) {
+                std::lock_guard<std::mutex> lk(err_mu);
+                if (!first_error) first_error = er;
+                next = n_jobs;   // stop handing out work
+            }
+        };
+        std::vector<std::thread> pool;
+        for (size_t w = 1; w < n_workers; w++) pool.emplace_back(worker, nullptr);
+        worker(&e);
+        for (auto& t : pool) t.join();
+        if (first_error) throw *first_error;
+    }
+    drain_writers();
+    if (write_error) throw *write_error;
+    if (!genome_inputs.empty()) {                                            // :422-476
+        const std::string path = args.db_out_name + QUERY_FILE_SUFFIX;
+        create_dir_all(dirname_of(path));
+        std::vector<GenomeSketch> all;
+        GenomeBatch batch(e, args.c, args.k, args.min_spacing_kmer, !args.no_pseudotax, all);
+        batch.add_files(genome_inputs, args.individual, args.threads);
+        batch.flush();
+        if (all.empty()) warn("No valid genomes to sketch; " + path + " is not output");
+        else { write_syldb(path, all); info("Wrote all genome sketches to " + path); }
+    }
+    if (!fast_exit()) join_background();
+    info("Finished.");
+    return 0;
+}
+
+}  // namespace sylph_host

@@ -257,6 +257,13 @@ unsigned parse_threads() {
     return std::max(std::min(n, 2u), n / g_parse_share.load());
 }
 
+// inflating is pure compute per member / stretch: it takes more threads than the memory-bound index does — half the usable CPUs
+// (at most 64), unless SYLPH_HIP_PARSE_THREADS fixes the count
+static unsigned inflate_threads(unsigned threads) {
+    if (getenv("SYLPH_HIP_PARSE_THREADS")) return threads;
+    return std::max(threads, std::min(64u, std::max(1u, effective_cpus() / 2)));
+}
+
 namespace { std::atomic<size_t> g_index_budget{0}; }
 void set_index_memory_budget(size_t bytes) { g_index_budget = bytes; }
 size_t index_memory_budget() { return g_index_budget; }
@@ -501,10 +508,8 @@ FastqIndex::FastqIndex(const std::string& path, unsigned threads, bool build) : 
             // result (member CRC); otherwise the sequential reader (needletail does the same, one thread)
             uint8_t* buf = nullptr;
             size_t n_out = 0;
-            const unsigned hw = effective_cpus();
-            const unsigned tz = getenv("SYLPH_HIP_PARSE_THREADS") ? threads : std::max(threads, std::min(64u, std::max(1u, hw / 2)));
             size_t n_map = 0;
-            if (!parallel_gunzip(data, size, tz, &buf, &n_out, &n_map, index_memory_budget())) return;
+            if (!parallel_gunzip(data, size, inflate_threads(threads), &buf, &n_out, &n_map, index_memory_budget())) return;
             munmap((void*)data, size);
             data = buf;
             size = n_out;
@@ -520,9 +525,7 @@ FastqIndex::FastqIndex(const std::string& path, unsigned threads, bool build) : 
         size_t n_map = 0;
         void* buf = inflated_acquire(total, &n_map);                               // (a recycled buffer where there is one: no first touch)
         if (!buf) return;
-        // (inflating is pure compute per member: it takes more threads than the memory-bound index does)
-        const unsigned hw = effective_cpus();
-        const bool inflated = bgzf_inflate(data, blocks, (uint8_t*)buf, getenv("SYLPH_HIP_PARSE_THREADS") ? threads : std::max(threads, std::min(64u, std::max(1u, hw / 2))));
+        const bool inflated = bgzf_inflate(data, blocks, (uint8_t*)buf, inflate_threads(threads));
         munmap((void*)data, size);
         data = (const uint8_t*)buf;
         size = total;

@@ -8,14 +8,11 @@
 #include <cmath>
 #include <cstring>
 
-#include "sylph_host.hpp"
+#include "host_internal.hpp"
 
 namespace sylph_host {
 
 namespace {
-
-void warn(const std::string& m) { fprintf(stderr, "WARN  [sylph_hip] %s\n", m.c_str()); }
-void info(const std::string& m) { fprintf(stderr, "INFO  [sylph_hip] %s\n", m.c_str()); }
 
 bool ends_with(const std::string& s, const char* suf) {
     const size_t n = strlen(suf);

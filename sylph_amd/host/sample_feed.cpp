@@ -1,0 +1,449 @@
+// sample_feed.cpp — the roads one sample's reads can take to the device (the device route, the indexed host feed, the sequential
+// reader), the choice between them, and the per-sample function behind the sketch / query / profile drivers
+// (sketch.rs:771-959).
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <cstring>
+
+#include "host_internal.hpp"
+
+namespace sylph_host {
+
+bool exact_dedup_accepted(bool flag) {
+    const char* e = getenv("SYLPH_HIP_EXACT_DEDUP");
+    return flag || (e && *e && strcmp(e, "0") != 0);
+}
+Container container_of(const std::string& f) {
+    struct stat st;
+    if (stat(f.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return Container::Plain;
+    FILE* fp = fopen(f.c_str(), "rb");
+    if (!fp) return Container::Plain;
+    unsigned char h[2] = {0, 0};
+    const size_t n = fread(h, 1, 2, fp);
+    fclose(fp);
+    if (n == 2 && h[0] == 0x1f && h[1] == 0x8b) return Container::Gzip;
+    if (n == 2 && h[0] == 'B' && h[1] == 'Z') return Container::Bzip2;
+    return Container::Plain;
+}
+bool device_decode_enabled(Container c) {
+    auto on = [](const char* name) {
+        if (!device_feed_enabled()) return false;
+        if (const char* e = getenv(name)) return atoi(e) != 0;
+        return true;
+    };
+    static const bool gzip = on("SYLPH_HIP_INFLATE_DEVICE"), bzip2 = on("SYLPH_HIP_BUNZIP2_DEVICE");
+    return c == Container::Gzip ? gzip : c == Container::Bzip2 ? bzip2 : false;
+}
+
+namespace {
+// Uncompressed 4-line FASTQ (the common case): the files are indexed by parse_threads() workers, whole batches are gathered
+// into page-locked memory in parallel and pushed; the record loop of the reference shrinks to its one sequential piece, the
+// running mean of the read lengths (f64, file order: sketch.rs:941-943, :825-826), which runs on its own thread meanwhile.
+// index_inputs returns nothing when a file is not that simple (gzip, FASTA, blank lines, a malformed record anywhere): the
+// caller then runs the sequential reader with needletail's exact record/error semantics.  No GPU call happens before the
+// files are indexed, so the engine's background bring-up overlaps with it.
+// build = false: the files are mapped / inflated, not indexed — what the device-side route needs of a gzip file (finish_index does
+// the rest on the host when that route is not taken after all)
+std::optional<IndexedInput> index_inputs(const SampleFiles& files, bool build = true) {
+    if (getenv("SYLPH_HIP_SEQUENTIAL_FEED")) return std::nullopt;
+    const std::string& f1 = files.first;
+    const std::string* f2 = files.second ? &*files.second : nullptr;
+    const unsigned T = parse_threads();
+    IndexedInput in;
+    std::exception_ptr err_b;
+    std::thread tb;
+    ThreadJoiner jb{tb};
+    if (f2) tb = std::thread([&] {                        // the two mate files are indexed concurrently
+        try { in.b.reset(new FastqIndex(*f2, T, build)); } catch (...) { err_b = std::current_exception(); }
+    });
+    in.a.reset(new FastqIndex(f1, T, build));
+    if (tb.joinable()) tb.join();
+    if (err_b) std::rethrow_exception(err_b);
+    if (build ? (!in.a->ok || (f2 && !in.b->ok)) : (!in.a->text_ready || (f2 && !in.b->text_ready))) return std::nullopt;
+    return in;
+}
+bool finish_index(IndexedInput& in) {
+    const unsigned T = parse_threads();
+    std::exception_ptr err_b;
+    std::thread tb;
+    ThreadJoiner jb{tb};
+    if (in.b) tb = std::thread([&] { try { in.b->build_index(T); } catch (...) { err_b = std::current_exception(); } });
+    in.a->build_index(T);
+    if (tb.joinable()) tb.join();
+    if (err_b) std::rethrow_exception(err_b);
+    return in.a->ok && (!in.b || in.b->ok);
+}
+// Batches of whole records (pairs) of at most BATCH_BASES bases / BATCH_RECS records
+std::vector<std::pair<size_t, size_t>> cut_batches(size_t n, bool paired, const std::vector<uint64_t>& ca, const std::vector<uint64_t>& cb) {
+    std::vector<std::pair<size_t, size_t>> out;
+    size_t i0 = 0;
+    while (i0 < n) {
+        // largest i1 with at most BATCH_BASES bases and BATCH_RECS records in [i0, i1)
+        size_t lo = i0 + 1, hi = std::min(n, i0 + PinnedBatch::BATCH_RECS / (paired ? 2 : 1));
+        auto bases_upto = [&](size_t i) { return ca[i] - ca[i0] + (paired ? cb[i] - cb[i0] : 0); };
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo + 1) / 2;
+            if (bases_upto(mid) <= PinnedBatch::BATCH_BASES) lo = mid; else hi = mid - 1;
+        }
+        out.emplace_back(i0, lo);
+        i0 = lo;
+    }
+    return out;
+}
+// open_session: creates the sample's session — it waits for the engine's context, so it is called as late as possible: whatever
+// batches can be gathered and packed before the context is up (the first sample of a process: ~0.15 s of idle parse threads otherwise)
+// are gathered into pageable memory first (round 5)
+void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_session, const IndexedInput& in, double& mean_read_length) {
+    const unsigned T = parse_threads();
+    FeedLaps laps;
+    const FastqIndex& a = *in.a;
+    const FastqIndex* b = in.b.get();
+    const size_t n = b ? std::min(a.n_records(), b->n_records()) : a.n_records();   // lock-step readers: sketch.rs:813-815
+    static const std::vector<uint64_t> no_cum;
+    const std::vector<uint64_t>& ca = a.cum;                             // prefix sums of the read lengths, from the index workers
+    const std::vector<uint64_t>& cb = b ? b->cum : no_cum;
+    // the one sequential piece of the reference's record loop (f64, file order: sketch.rs:941-943, :825-826), on its own thread
+    // while the batches travel
+    double mean = 0.;
+    std::thread tm([&] { double counter = 0.; for (size_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a.seq_len[i] - mean) / counter; } });
+    ThreadJoiner jm{tm};
+    const auto batches = cut_batches(n, b != nullptr, ca, cb);
+    size_t early = 0;
+    constexpr size_t MAX_EARLY = 16;                                     // 4 Gbp = 1 GB of packed bases in pageable memory at most
+    while (!e.ready() && early < batches.size() && early < MAX_EARLY) {
+        e.batch.gather_packed_early(a, b, ca, b ? &cb : nullptr, batches[early].first, batches[early].second, T);
+        early++;
+    }
+    if (early) laps.lap("early batches: gather + pack (context still coming up)");
+    sylph_sketch* const sk = open_session();
+    e.batch.flush(sk);
+    if (early) {
+        e.batch.push_early(sk);
+        if (early < batches.size()) {
+            a.release_behind(a.seq_off[batches[early].first]);
+            if (b) b->release_behind(b->seq_off[batches[early].first]);
+        }
+        laps.lap("early batches: pushed");
+    }
+    // Batches are gathered AND packed to 2 bits per base by the parse threads into one of two page-locked slots while the other
+    // slot is on its way to the device: the push of batch i (PCIe + kernels) hides behind the gather of batch i + 1.
+    if (early < batches.size()) {
+        e.wait_pinned();
+        e.batch.gather_packed((int)(early & 1), a, b, ca, b ? &cb : nullptr, batches[early].first, batches[early].second, T);
+        laps.lap("batch: gather + pack");
+    }
+    for (size_t bi = early; bi < batches.size(); bi++) {
+        std::exception_ptr err;
+        std::thread tg;
+        ThreadJoiner jg{tg};
+        if (bi + 1 < batches.size())
+            tg = std::thread([&, bi] {
+                try { e.batch.gather_packed((int)((bi + 1) & 1), a, b, ca, b ? &cb : nullptr, batches[bi + 1].first, batches[bi + 1].second, T); }
+                catch (...) { err = std::current_exception(); }
+            });
+        e.batch.push_packed(sk, (int)(bi & 1));
+        if (tg.joinable()) tg.join();
+        if (err) std::rethrow_exception(err);
+        // everything before the next batch's first record has been gathered: an inflated copy gives those pages back
+        if (bi + 1 < batches.size()) {
+            a.release_behind(a.seq_off[batches[bi + 1].first]);
+            if (b) b->release_behind(b->seq_off[batches[bi + 1].first]);
+        }
+        laps.lap("batch: push || gather next");
+    }
+    tm.join();
+    mean_read_length = mean;
+    laps.lap("running mean (joined)");
+}
+
+// Round 5, the device-side route for plain FASTQ (csrc/fastq.hip): the files' TEXT goes to the device through the engine's uploader and
+// the library finds the records there; the host keeps the one sequential piece (the running mean of the mate-1 read lengths, from the
+// lengths the device hands back).  Taken for every sample whose engine is already up — a process's FIRST sample is indexed and gathered
+// on the host while the GPU runtime initialises, which no device can do — unless SYLPH_HIP_FEED_DEVICE=0 (feed.cpp device_feed_enabled).
+// Returns false, having pushed
+// nothing, when the files are not plain four-line FASTQ (SYLPH_ERR_FORMAT, gzip, FASTA): the caller takes the host route, whose
+// record and error semantics are needletail's.
+// `text`: the files' text where it lies in host memory already (the inflated copies of gzip files) instead of the files themselves
+// Round 6, gzip on the device (csrc/inflate.hip): a sample whose files are gzip sends their COMPRESSED bytes (0.4 B per base instead of
+// 2.1) and the library inflates them there — sylph_inflate; SYLPH_HIP_INFLATE_DEVICE=0 keeps the host's inflate.  What the library
+// declines (SYLPH_ERR_FORMAT: damaged, not gzip after all, a stream it does not take; SYLPH_ERR_NOMEM) goes the host way, whose
+// error semantics are needletail's.
+// bzip2 on the device (csrc/bunzip2.hip), the same way: the compressed bytes travel, sylph_bunzip2_files decodes them there;
+// SYLPH_HIP_BUNZIP2_DEVICE=0 keeps the host's reader (libbz2 in FastxReader).  What the library declines goes the host way.
+// `decode`: the container the device decodes (SampleRoute: both mates are of it, device_decode_enabled says yes); Plain: text travels.
+namespace {
+struct MappedFile {                       // the compressed bytes of one file (read-only mapping of the page cache)
+    const uint8_t* data = nullptr;
+    size_t size = 0;
+    explicit MappedFile(const std::string& path) {
+        const int fd = open(path.c_str(), O_RDONLY);
+        if (fd < 0) return;
+        struct stat st;
+        if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            void* p = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
+            if (p != MAP_FAILED) { data = (const uint8_t*)p; size = (size_t)st.st_size; }
+        }
+        close(fd);
+    }
+    MappedFile(const MappedFile&) = delete;
+    MappedFile& operator=(const MappedFile&) = delete;
+    ~MappedFile() { if (data) munmap(const_cast<uint8_t*>(data), size); }
+};
+struct InflatedText { sylph_inflated* h = nullptr; ~InflatedText() { sylph_inflated_destroy(h); } };
+}  // namespace
+
+bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const SampleFiles& sample, Container decode,
+                            double& mean_read_length, const IndexedInput* text = nullptr) {
+    if (!device_feed_enabled()) return false;
+    const std::string& f1 = sample.first;
+    const std::string* f2 = sample.second ? &*sample.second : nullptr;
+    const bool gz = !text && decode == Container::Gzip, bz = !text && decode == Container::Bzip2;
+    if (!gz && !bz && !e.ready()) return false;      // (a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that)
+    const bool trace = FeedLaps::on();
+    FeedLaps laps;
+    sylph_ctx* ctx = e.context();
+    std::vector<std::string> files{f1};
+    if (f2) files.push_back(*f2);
+    std::vector<TextUploader::Text> texts;
+    InflatedText inflated;                           // (destroyed behind the indexes that borrow its text: declared before them)
+    if (gz || bz) {
+        // both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files): one scan, one decode launch, one chain — the mates share a block's latency
+        std::vector<std::unique_ptr<MappedFile>> maps;
+        std::vector<const void*> ptrs;
+        std::vector<uint64_t> lens;
+        for (const auto& f : files) {
+            maps.emplace_back(new MappedFile(f));
+            if (!maps.back()->data) return false;
+            ptrs.push_back(maps.back()->data);
+            lens.push_back(maps.back()->size);
+        }
+        const int rc = gz ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h)
+                          : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
+        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", files[0].c_str(), sylph_last_error());
+            return false;
+        }
+        hip_check(rc, gz ? "sylph_inflate_files" : "sylph_bunzip2_files");
+        for (uint32_t i = 0; i < ptrs.size(); i++) {
+            const void* dev = nullptr;
+            uint64_t bytes = 0;
+            hip_check(sylph_inflated_file(inflated.h, i, &dev, &bytes), "sylph_inflated_file");
+            if (!bytes) return false;
+            texts.push_back(TextUploader::Text{(const uint8_t*)dev, bytes});
+        }
+        laps.lap(gz ? "device route: gzip inflated on the device" : "device route: bzip2 decoded on the device");
+    } else if (text) {
+        // The first text an engine sends pays for the route's device buffers (~40-90 ms of allocations, once); skipping the host's index
+        // and gather of an inflated copy buys that back only for a sample of some size: 0.45 against 0.53 s for a 1 Gbp gzip pair, 0.34
+        // against 0.30 s for its first mate alone (profiles/r05_feed_device_route.txt)
+        const uint64_t bytes = text->a->size + (f2 ? text->b->size : 0);
+        if (!e.text.warm() && bytes < (1500ull << 20)) return false;
+        std::vector<TextUploader::Mem> mem{{text->a->data, text->a->size}};
+        if (f2) mem.push_back({text->b->data, text->b->size});
+        if (!e.text.send(ctx, mem, parse_threads(), texts)) return false;
+    } else if (!e.text.send(ctx, files, parse_threads(), texts)) return false;
+    if (!gz && !bz) laps.lap("device route: text uploaded");
+    struct Fq { sylph_fastq* f = nullptr; ~Fq() { sylph_fastq_destroy(f); } } fa, fb;
+    auto index = [&](const TextUploader::Text& t, Fq& out) {
+        const int rc = sylph_fastq_index(ctx, t.dev, t.bytes, SYLPH_MEM_DEVICE, &out.f);
+        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) return false;   // not for this route / no room for it: the host feed
+        hip_check(rc, "sylph_fastq_index");
+        return true;
+    };
+    if (!index(texts[0], fa) || (f2 && !index(texts[1], fb))) return false;
+    uint64_t na = 0, nb = 0, bases_a = 0, bases_b = 0;
+    hip_check(sylph_fastq_counts(fa.f, &na, &bases_a), "sylph_fastq_counts");
+    if (f2) hip_check(sylph_fastq_counts(fb.f, &nb, &bases_b), "sylph_fastq_counts");
+    const uint64_t n = f2 ? std::min(na, nb) : na;                         // lock-step readers: sketch.rs:813-815
+    laps.lap("device route: records found");
+    std::vector<uint32_t> la(n), lb;
+    hip_check(sylph_fastq_lengths(fa.f, 0, n, la.data()), "sylph_fastq_lengths");
+    // the one sequential piece of the reference's record loop (f64, file order: sketch.rs:941-943, :825-826), on its own thread
+    double mean = 0.;
+    std::thread tm([&] { double counter = 0.; for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)la[i] - mean) / counter; } });
+    ThreadJoiner jm{tm};
+    // pushes of whole records (pairs) below 2^31 bases and 2^30 items: one for anything up to ~2 Gbp
+    std::vector<std::pair<uint64_t, uint64_t>> pushes;
+    if (bases_a + bases_b < (1ull << 31) && n < (1ull << 30)) {
+        if (n) pushes.emplace_back(0, n);
+    } else {
+        if (f2) { lb.resize(n); hip_check(sylph_fastq_lengths(fb.f, 0, n, lb.data()), "sylph_fastq_lengths"); }
+        uint64_t i0 = 0, sum = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t l = (uint64_t)la[i] + (f2 ? lb[i] : 0);
+            if (i > i0 && (sum + l >= (1ull << 31) || i - i0 >= (1ull << 30))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
+            sum += l;
+        }
+        if (n > i0) pushes.emplace_back(i0, n - i0);
+    }
+    sylph_sketch* const sk = open_session();
+    e.batch.flush(sk);
+    // one push: the batch is the session's own buffer, valid until finish — the seeding verdict may wait for it (one host round trip less)
+    if (pushes.size() == 1) hip_check(sylph_sketch_set_option(sk, "borrow_until_finish", "1"), "sylph_sketch_set_option");
+    for (const auto& p : pushes) {
+        const int rc = sylph_sketch_push_fastq(sk, fa.f, f2 ? fb.f : nullptr, p.first, p.second);
+        if (rc == SYLPH_ERR_NOMEM) {
+            // no room on the device for this route's batch (the whole sample in one piece, up to 2 Gbp): not an error — the host feed, which
+            // works through a sample in 256 Mbp batches, takes the sample from its start; the caller opens a fresh session
+            if (trace) fprintf(stderr, "[sylph_hip feed] device route: no room for the batch (%s): the host feed takes the sample\n", sylph_last_error());
+            tm.join();
+            return false;
+        }
+        hip_check(rc, "sylph_sketch_push_fastq");
+    }
+    laps.lap("device route: pushed");
+    tm.join();
+    mean_read_length = mean;
+    return true;
+}
+
+// MemAvailable of /proc/meminfo in bytes (0 if unknown)
+size_t mem_available() {
+    std::ifstream f("/proc/meminfo");
+    std::string key;
+    unsigned long long kb = 0;
+    while (f >> key) {
+        if (key == "MemAvailable:") { f >> kb; return (size_t)kb * 1024; }
+        f.ignore(1 << 20, '\n');
+    }
+    return 0;
+}
+// what ONE index may hold in anonymous memory when `concurrent` of them can be alive at the same time: half of what is available
+void set_feed_budget(size_t concurrent) {
+    if (const char* e = getenv("SYLPH_HIP_FEED_MEM_GB")) { set_index_memory_budget((size_t)(atof(e) * (1ull << 30))); return; }
+    const size_t avail = mem_available();
+    set_index_memory_budget(avail ? avail / 2 / std::max<size_t>(1, concurrent) : 0);
+}
+
+// The sequential reader: needletail's exact record and error semantics, for whatever the two parallel roads do not take.  Each
+// loop opens the sample's session once its files are open, pushes the records, and returns the running mean of the read lengths —
+// or nothing where the reference gives no sketch.
+std::optional<double> read_single_sequentially(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::string& read_file) {
+    std::unique_ptr<ChunkStream> reader;
+    try { reader.reset(new ChunkStream(read_file)); }
+    catch (const Error&) { warn(read_file + " is not a valid fasta/fastq file; skipping."); return std::nullopt; }   // sketch.rs:911-914
+    sylph_sketch* const sk = open_session();
+    double mean_read_length = 0., counter = 0.;
+    const uint8_t* seq = nullptr;
+    uint32_t len = 0;
+    for (;;) {
+        const ChunkStream::Kind kind = reader->next(seq, len);
+        if (kind == ChunkStream::ERR) { warn("File " + read_file + " is not a valid fasta/fastq file"); break; }   // :945
+        if (kind == ChunkStream::END) break;
+        e.batch.add(sk, seq, len, nullptr, 0, false);
+        counter += 1.;                                                       // :941-943
+        mean_read_length = mean_read_length + ((double)len - mean_read_length) / counter;
+    }
+    e.batch.flush(sk);
+    return mean_read_length;
+}
+std::optional<double> read_pair_sequentially(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::string& read_file1,
+                                             const std::string& read_file2) {
+    std::unique_ptr<ChunkStream> r1, r2;   // the two mate files are parsed/inflated concurrently by their reader threads
+    try { r1.reset(new ChunkStream(read_file1)); r2.reset(new ChunkStream(read_file2)); }
+    catch (const Error&) {
+        throw Error{1, "Paired end reading failed for '" + read_file1 + "' and '" + read_file2 +
+                           "'. Make sure the files are present or the sequences are valid."};   // sketch.rs:781-784
+    }
+    sylph_sketch* const sk = open_session();
+    double mean_read_length = 0., counter = 0.;
+    const uint8_t *s1 = nullptr, *s2 = nullptr;
+    uint32_t l1 = 0, l2 = 0;
+    for (;;) {
+        const ChunkStream::Kind k1 = r1->next(s1, l1);
+        if (k1 == ChunkStream::ERR) { e.batch.flush(sk); return std::nullopt; }   // :878-880
+        const ChunkStream::Kind k2 = r2->next(s2, l2);
+        if (k1 == ChunkStream::END) break;                                   // :881-883
+        if (k2 != ChunkStream::REC) continue;                                // mate 2 missing/invalid: pair skipped
+        e.batch.add(sk, s1, l1, s2, l2, true);
+        counter += 1.;                                                       // :824-826 (mate-1 length only)
+        mean_read_length = mean_read_length + ((double)l1 - mean_read_length) / counter;
+    }
+    e.batch.flush(sk);
+    return mean_read_length;
+}
+}  // namespace
+
+void IndexAhead::start(size_t j) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (j >= files_.size() || fut_.count(j)) return;
+    const SampleFiles f = files_[j];
+    fut_[j] = std::async(std::launch::async, [f] { return index_inputs(f); });
+}
+std::optional<IndexedInput> IndexAhead::get(size_t j) {
+    std::future<std::optional<IndexedInput>> f;
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = fut_.find(j);
+        if (it != fut_.end()) { f = std::move(it->second); fut_.erase(it); }
+    }
+    if (f.valid()) return f.get();
+    return index_inputs(files_.at(j));
+}
+
+FeedShared::FeedShared(std::vector<SampleFiles> files, size_t workers) : ahead(std::move(files)), n_workers(workers) {
+    set_parse_share((unsigned)n_workers);
+    set_feed_budget(4 * n_workers);            // two files per sample, the current and the next sample of every worker
+    set_no_more_inflates(false);
+}
+
+SampleRoute::SampleRoute(Engine& eng, FeedShared& feed, size_t j, bool first_use_hint) {
+    const SampleFiles& files = feed.ahead.files(j);
+    const bool feed_dev = device_feed_enabled();
+    const Container c1 = feed_dev ? container_of(files.first) : Container::Plain;
+    const bool compressed = c1 != Container::Plain;
+    const bool decoded = device_decode_enabled(c1);           // the compressed bytes travel, the device inflates / decodes (mate 1 decides the road)
+    dev = feed_dev && (decoded || (eng.ready() && !compressed));
+    // ... the device's decoder is the one to use if mate 2 is of the same container; if not, the device route declines the pair
+    if (decoded && (!files.second || container_of(*files.second) == c1)) decode = c1;
+    if (c1 == Container::Gzip && !decoded) pre = index_inputs(files, false);   // inflated on the host, its text then sent as it is
+    else if (!dev) pre = feed.ahead.get(j);
+    if (first_use_hint) {
+        if (decoded && !eng.ready()) { eng.defer_pinned.store(true); eng.warm_text_route.store(true); }
+        trace_mark(dev ? "sketch: the sample goes the device route" : "sketch: the sample's files are indexed (or not indexable)");
+    }
+    if (++feed.indexes_obtained == feed.ahead.size()) set_no_more_inflates(true);
+    if (!feed_dev) feed.ahead.start(j + feed.n_workers);
+}
+SampleRoute::~SampleRoute() {
+    if (pre) background([x = std::make_shared<std::optional<IndexedInput>>(std::move(pre))]() mutable { x.reset(); });
+}
+
+std::optional<SequencesSketch> sketch_sample(Engine& e, const SampleFiles& files, const SampleParams& p, SampleRoute& route, sylph_sketch** keep) {
+    const bool paired = files.second.has_value();
+    std::optional<Session> so;
+    const std::function<sylph_sketch*()> open_session = [&] { so.emplace(e, p.c, p.k, paired, p.no_dedup, p.dedup_fpr); return so->sk; };
+    auto sketched = [&](double mean_read_length) {
+        SequencesSketch out;
+        so->finish_or_keep(out, keep);
+        out.file_name = files.first; out.c = p.c; out.k = p.k; out.paired = paired;
+        out.sample_name = p.sample_name;
+        out.mean_read_length = mean_read_length;
+        return out;
+    };
+    double mean = 0.;
+    // `index`: the files' index if the route obtained it (an empty optional: the files are not for the block-parallel feed);
+    // nullptr: nobody has tried yet — the sample was meant for the device
+    std::optional<IndexedInput>* index = route.dev ? nullptr : &route.pre;
+    const bool text_only = index && *index && !(*index)->a->ok;
+    if (route.dev || text_only) {
+        if (sketch_fastq_on_device(e, open_session, files, route.decode, mean, text_only ? &**index : nullptr)) return sketched(mean);
+        // declined: the host feed takes the sample from its start, with a fresh session
+        if (text_only && !finish_index(**index)) index->reset();
+        so.reset();
+    }
+    std::optional<IndexedInput> own;
+    if (!index) { own = index_inputs(files); index = &own; }
+    if (*index) {   // uncompressed 4-line FASTQ: block-parallel feed
+        sketch_indexed(e, open_session, **index, mean);
+        return sketched(mean);
+    }
+    const std::optional<double> seq_mean = paired ? read_pair_sequentially(e, open_session, files.first, *files.second)
+                                                  : read_single_sequentially(e, open_session, files.first);
+    if (!seq_mean) return std::nullopt;
+    return sketched(*seq_mean);
+}
+
+}  // namespace sylph_host

@@ -259,7 +259,7 @@ void trace_mark(const char* what);   // SYLPH_HIP_FEED_TRACE: a line with the mi
 struct Engine {   // one GPU context shared by the drivers
     int device = -1;
     PinnedBatch batch;   // reused by every sample sketched through this engine
-    TextUploader text;   // ... and the uploader of the device-side FASTQ route (commands.cpp sketch_fastq_on_device)
+    TextUploader text;   // ... and the uploader of the device-side FASTQ route (sample_feed.cpp sketch_fastq_on_device)
     std::atomic<bool> warm_text_route{false};   // set before the bring-up's warm-up sample: it goes the device FASTQ route's way (the first sample will)
     std::atomic<bool> defer_pinned{false};   // set before the bring-up reaches them: `batch` and `text` page-lock their buffers at first use instead
     // GPU bring-up (runtime initialisation, context, page-locked batch, first-use loading of the sketch kernels: ~0.3 s) runs on a
@@ -278,12 +278,8 @@ struct Engine {   // one GPU context shared by the drivers
     struct Gate;                   // ready flag + condition variable
     std::unique_ptr<Gate> gate_;
 };
-// sketch.rs:897 / :771 / :550 / :481 — return nullopt where the reference returns None (warn + skip).
-std::optional<SequencesSketch> sketch_sequences_needle(Engine& e, const std::string& read_file, uint64_t c, uint64_t k,
-                                                       std::optional<std::string> sample_name, bool no_dedup);
-std::optional<SequencesSketch> sketch_pair_sequences(Engine& e, const std::string& read_file1, const std::string& read_file2,
-                                                     uint64_t c, uint64_t k, std::optional<std::string> sample_name,
-                                                     bool no_dedup, double dedup_fpr);
+// sketch.rs:550 / :481 — return nullopt where the reference returns None (warn + skip).  (Reads, sketch.rs:897 / :771: the drivers'
+// own sketch_sample, host_internal.hpp.)
 std::optional<GenomeSketch> sketch_genome(Engine& e, uint64_t c, uint64_t k, const std::string& ref_file, uint64_t min_spacing,
                                           bool pseudotax);
 std::vector<GenomeSketch> sketch_genome_individual(Engine& e, uint64_t c, uint64_t k, const std::string& ref_file,

@@ -463,7 +463,7 @@ def test_parallel_feed_equals_sequential_feed(data):
 
 def test_device_fastq_route_equals_the_host_feed(data):
     """SYLPH_HIP_FEED_DEVICE=1: every plain-FASTQ sample whose engine is already up sends its TEXT to the device, where the library finds
-    the records (csrc/fastq.hip; host/commands.cpp sketch_fastq_on_device); a process's first sample, gzip input and anything that is
+    the records (csrc/fastq.hip; host/sample_feed.cpp sketch_fastq_on_device); a process's first sample, gzip input and anything that is
     not plain four-line FASTQ go the host way — gzip files are inflated on the host and their TEXT then takes the same route.  Seven
     samples through one engine — a single-member gzip pair first, plain pairs, a CRLF copy, a pair whose mate 2 is longer, a blocked-gzip
     pair, a pair with a damaged record in the middle, a single-end file — must give byte-identical sketches and the same exit code
