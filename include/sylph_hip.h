@@ -94,7 +94,7 @@ void sylph_upload_destroy(sylph_upload *u);
  * "bucket" (error instead of falling back).  "seeds" = "auto" (default: the read-per-lane kernel for short-read batches, the
  * position kernel with per-tile ordered slots otherwise), "slots" (always the position kernel with ordered slots) or
  * "unordered" (position kernel with LDS-staged atomics + radix sort by position).  "bucket_target" = mean number of
- * occurrences per replay bucket aimed for, "16".."256".  "shard_reduce" = "alltoall" (default) or "allgather": how the hits of a
+ * occurrences per replay bucket aimed for, "16".."256" (default 96: nearly every bucket at most 128).  "shard_reduce" = "alltoall" (default) or "allgather": how the hits of a
  * sharded batch (sylph_db_contain_batch_sharded) reach the rank that owns the sample — one all-to-all of exactly the hits each rank
  * needs, or ONE all-gather of every rank's whole hit buffer padded to the longest (W x the bytes, one collective; set on the database's
  * context, or through sylph_pipeline_set_option).  "index_lambda" = postings per 64-byte bucket line of a database
@@ -128,7 +128,8 @@ int sylph_ctx_set_option(sylph_ctx *ctx, const char *key, const char *value);
  * bench.py's roofline object.  enable=1 starts collecting and clears the totals.  Families (time + launches): "seeds", "compact",
  * "annotate", "sort" (the bucket partition), "replay", "a10" (the filter dedup's passes), "probe", "assemble" (hits -> result rows),
  * "exchange", "db_index", "genome_filter", "seeds_spill", "replay_overflow"; counters only (launches = how often that road was
- * taken; the tests read them): "deferred", "deferred_redo", "a10_part", "a10_redo". */
+ * taken; the tests read them): "deferred", "deferred_redo", "a10_part", "a10_redo"; "replay_lane", "replay_general" (launches = buckets the
+ * 256-slot replay kernel ran with one occurrence per lane / with its general body, counted on the host while "replay" is timed). */
 int sylph_ctx_profile(sylph_ctx *ctx, int enable);
 int sylph_ctx_kernel_stats(sylph_ctx *ctx, const char *family, double *total_ms, uint64_t *launches);
 

@@ -135,13 +135,16 @@ struct KernelStat { double ms = 0; uint64_t launches = 0; };
 #ifndef SYLPH_READS_TAIL_PCT
 #define SYLPH_READS_TAIL_PCT 10     // (round 6; 0 until then: profiles/r06_ab_latency.txt — 5, 15, 20, 30 are all slower on the exact pair set)
 #endif
+#ifndef SYLPH_BUCKET_TARGET
+#define SYLPH_BUCKET_TARGET 96
+#endif
 struct sylph_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::mutex mu;                          // serialises calls on this ctx
     int finish_mode = 0;                    // 0 auto, 1 generic, 2 bucket-only (sylph_ctx_set_option "finish")
-    uint32_t bucket_target = 128;           // mean occurrences per replay bucket aimed for ("bucket_target")
+    uint32_t bucket_target = SYLPH_BUCKET_TARGET;           // mean occurrences per replay bucket aimed for ("bucket_target")
     uint32_t plain_records = 1;             // marker-less single-end batches keep no occurrence records ("plain_records" = 0: always write them)
     uint32_t shard_reduce = 0;              // "shard_reduce": 0 = the sharded batch's hits travel by all-to-all (default), 1 = by ONE all-gather (north_star's wording; shard_plan.h plan_hits_gather)
     uint32_t fail_next_peer_copy = 0;       // fault injection for the tests ("fail_next_peer_copy"): the next sylph_db_replicate INTO this context finds no device-to-device road

@@ -1,7 +1,8 @@
 // replay_lds.hip — finish() of a read-sketch session without device-wide sorts: bucket partition + in-LDS replay.
 //
 // FracMinHash survivors are uniformly distributed below the threshold (mm_hash64 is a bijection of canonical
-// k-mers), so the top bits of the hash split the sample's occurrences into B buckets of nearly equal size (~128).
+// k-mers), so the top bits of the hash split the sample's occurrences into B buckets of nearly equal size (~96: nearly all of them
+// at most 128, one occurrence per lane of the replay workgroup — replay_bucket_lane).
 // The PARTITION (round 3: hand-written, four small kernels, no library sort, no memset dispatches) only moves 8-byte
 // (bucket, occurrence index) pairs, in two levels: tiles of occurrences are histogrammed over <= 512 coarse hash ranges, a
 // scan turns the (range x tile) counts into offsets, the pairs are scattered range by range, and one workgroup per coarse
@@ -24,7 +25,7 @@
 namespace sylph {
 namespace {
 
-// Three configurations of the same kernel template.  Buckets of up to CAP_SMALL occurrences (all of them, for ordinary
+// Three configurations of the same kernel template (the first carries a second, leaner body for buckets of up to 128: LANE_CAP).  Buckets of up to CAP_SMALL occurrences (all of them, for ordinary
 // samples) run with 10 KiB of LDS per workgroup -> 16 workgroups = 32 wavefronts per CU, which is what hides the latency of
 // this barrier- and gather-heavy kernel (with a single 512-slot configuration occupancy was 14 wavefronts and the kernel 1.4x
 // slower).  Larger buckets, and buckets that hold a deep k-mer (SEG_LIMIT), are queued for the CAP_MID / CAP_LARGE
@@ -41,6 +42,10 @@ constexpr int IDX_BITS = 10;         // arrival index inside a bucket (< CAP_LAR
 // A bucket holding a k-mer with SEG_LIMIT or more occurrences (a genome at ~100x and above) is handed to the medium / large
 // configuration, whose marker test is a hash table in LDS: linear in the bucket size.
 constexpr uint32_t SEG_LIMIT = 96;
+constexpr uint32_t SINGLE_CUTOFF = 4;   // MAX_DEDUP_COUNT, constants.rs:14 (single-end; pairs have none)
+// The one-occurrence-per-lane body (replay_bucket_lane): buckets of up to LANE_CAP occurrences, LANE_CAP threads, LANE_CAP
+// sub-ranges — the fourth entry of BucketMap::sub_mult / sub_width / rank_bits.
+constexpr int LANE_CAP = 128, LANE_CFG = 3;
 
 
 // What a replay / count workgroup needs besides its bucket: filled once by finish_bucketed and passed to the kernels by value.
@@ -76,6 +81,17 @@ struct FinishTail {
 };
 static_assert(sizeof(FinishTail) == 48, "tail block");
 
+// The LDS of one replay workgroup.  The kernel owns it and hands it to the body that runs the bucket: the lane body works in the
+// first LANE_CAP entries of the 256-slot configuration's arrays, so the two bodies of one kernel cost the LDS of one.
+template <int CAP, int RTPB>
+struct ReplayLds {
+    uint64_t hash[CAP], rid[CAP], m0[CAP], m1[CAP];
+    __attribute__((aligned(8))) uint16_t seg[CAP];   // first sorted position of the k-mer each sorted position belongs to
+    uint8_t fl[CAP];                                 // bit0 skip, bit1 would-be-dropped
+    __attribute__((aligned(8))) uint16_t ab[2 * (CAP + 2)];   // exclusive counts <= CAP (s_a | s_b); before them: the marker tags
+    uint32_t wave[RTPB / 64];
+};
+
 // 15-bit tag of a dedup marker, never 0 (bit 0 set): what the scan over a k-mer's earlier occurrences compares first
 __device__ __forceinline__ uint32_t marker_tag(uint64_t m) { return (uint32_t)((m * 0x9E3779B97F4A7C15ull) >> 49) | 1u; }
 
@@ -92,7 +108,7 @@ __device__ __forceinline__ uint32_t marker_tag(uint64_t m) { return (uint32_t)((
 // two-part comparison is spelled out).  Records are then written straight to their sorted slots.
 // Handles buckets with min_n < n <= CAP; larger ones bump `overflow` (when count_overflow) and are left to the caller.
 template <int CAP, int RTPB>
-__device__ __forceinline__ void replay_bucket(const uint32_t b, const ReplayArgs& ra) {
+__device__ __forceinline__ void replay_bucket(const uint32_t b, const ReplayArgs& ra, ReplayLds<CAP, RTPB>& lds) {
     const OccRec* __restrict__ recs = ra.recs;
     const uint32_t* __restrict__ perm = ra.perm;
     const uint32_t* __restrict__ boff = ra.boff;
@@ -108,13 +124,13 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const ReplayArgs
     // which is the bit a10_mark left in the occurrence's record.
     const bool filter = ra.dedup == DEDUP_FILTER;
     const int no_dedup = filter ? 0 : ra.dedup;
-    __shared__ uint64_t s_hash[CAP], s_rid[CAP], s_m0[CAP], s_m1[CAP];
-    __shared__ __attribute__((aligned(8))) uint16_t s_seg[CAP];   // first sorted position of the k-mer each sorted position belongs to
-    __shared__ uint8_t s_fl[CAP];         // bit0 skip, bit1 would-be-dropped
-    __shared__ __attribute__((aligned(8))) uint16_t s_ab[2 * (CAP + 2)];   // exclusive counts <= CAP (s_a | s_b); before them: the marker tags
+    uint64_t* const s_hash = lds.hash, * const s_rid = lds.rid, * const s_m0 = lds.m0, * const s_m1 = lds.m1;
+    uint16_t* const s_seg = lds.seg;
+    uint8_t* const s_fl = lds.fl;
+    uint16_t* const s_ab = lds.ab;
     uint16_t* const s_a = s_ab;
     uint16_t* const s_b = s_ab + (CAP + 2);
-    __shared__ uint32_t s_wave[RTPB / 64];
+    uint32_t* const s_wave = lds.wave;
     const uint32_t tid = threadIdx.x;
     const uint32_t nv = *ra.p_nv;
     const uint32_t first = boff[b], last = boff[b + 1];
@@ -666,9 +682,209 @@ __device__ __forceinline__ void replay_bucket(const uint32_t b, const ReplayArgs
     if (tid == 0) { n_distinct[b] = total_heads; ra.removed_b[b] = total_removed; }
 }
 
-template <int CAP, int RTPB>
-__global__ __launch_bounds__(RTPB) void bucket_replay_kernel(ReplayArgs ra) {
-    replay_bucket<CAP, RTPB>(blockIdx.x, ra);
+// The common bucket — at most LANE_CAP occurrences, composite keys with a one-word ranking key (rank_bits > 0) — with ONE occurrence
+// per lane: the same steps in the same order as replay_bucket<256, 128> (gather with both loads in flight, sub-range count, counter
+// scan, hand-off of a bucket with a deep k-mer, placement, the rank loop that also yields the segment head, sorted write, mate-2 rule,
+// tags, marker test, one packed block scan for pairs / two for single-end, rows), but a lane's sorted position is its thread number:
+// no levels, no loops over a lane's positions, flags in registers, and what replay_bucket decides at run time — pairs or the
+// single-end cut-off, exact set / filter / no dedup — is a template parameter, so that the arms a sample cannot take are not in the
+// instance at all.  Writes what replay_bucket writes (tmp_k / tmp_c / n_distinct / removed_b: the sort is the same total order by
+// (hash, index), only found through 128 sub-ranges instead of 256).
+template <bool PAIRED, int DEDUP>
+__device__ __forceinline__ void replay_bucket_lane(const uint32_t b, const uint32_t first, const uint32_t n, const ReplayArgs& ra,
+                                                   ReplayLds<CAP_SMALL, LANE_CAP>& lds) {
+    const OccRec* __restrict__ recs = ra.recs;
+    const uint32_t* __restrict__ perm = ra.perm;
+    uint64_t* __restrict__ tmp_k = ra.tmp_k;
+    uint32_t* __restrict__ tmp_c = ra.tmp_c;
+    const BucketMap& bm = ra.bm;
+    constexpr bool filter = DEDUP == DEDUP_FILTER, no_dedup = DEDUP == DEDUP_NONE;
+    uint64_t* const s_hash = lds.hash, * const s_rid = lds.rid, * const s_m0 = lds.m0, * const s_m1 = lds.m1;
+    uint16_t* const s_seg = lds.seg;
+    uint16_t* const s_a = lds.ab;
+    uint16_t* const s_b = lds.ab + (CAP_SMALL + 2);
+    uint32_t* const s_wave = lds.wave;
+    const uint32_t tid = threadIdx.x;
+    const bool live = tid < n;
+    // ---- gather + sort by (hash, file order) ---------------------------------------------------------------------------
+    // (a lane past the end loads the bucket's last entry again: no branch around the loads, two load latencies in all)
+    const uint32_t pidx = perm[first + min(tid, n - 1u)];
+    const OccRec r = recs[pidx];
+    const uint64_t lo_hash = bucket_lo_key(b, bm.mult, bm.inv_mult) << bm.sh;      // = bucket_lo_hash(b, bm.mult, bm.sh)
+    const int rank_bits = bm.rank_bits[LANE_CFG];
+    uint64_t* const s_key = s_m0;                                  // keys live in s_m0 until the sorted records are written
+    uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(s_m1);     // LANE_CAP + 1 counters
+    uint16_t* const s_fill = s_seg;                                // members placed so far per sub-range
+    s_cnt[tid] = 0;
+    if (tid == 0) s_cnt[LANE_CAP] = 0;
+    if (tid < LANE_CAP / 2) reinterpret_cast<uint32_t*>(s_seg)[tid] = 0;
+    __syncthreads();
+    uint32_t sub = 0;
+    if (live) {
+        sub = sub_range_of((uint32_t)((r.hash - lo_hash) >> bm.sh), bm.sub_mult[LANE_CFG], LANE_CAP);
+        atomicAdd(&s_cnt[sub], 1u);
+    }
+    __syncthreads();
+    {   // s_cnt[t] = start of sub-range t, s_cnt[LANE_CAP] = n; a k-mer SEG_LIMIT deep fills its sub-range that far: the bucket is
+        // for the hashed marker test of the 512-slot configuration (as in replay_bucket, at the same point)
+        const bool deep = scan_counters<LANE_CAP, LANE_CAP>(s_cnt, s_cnt, s_wave) >= SEG_LIMIT;
+        if constexpr (!no_dedup) {
+            if (__syncthreads_or(deep)) {
+                if (tid == 0) ra.mid_list[1 + atomicAdd(&ra.mid_list[0], 1u)] = b;
+                return;
+            }
+        } else
+            __syncthreads();
+    }
+    uint64_t rkey = 0;
+    if (live) {
+        const uint32_t place = s_cnt[sub] + take_place(s_fill, sub);
+        const uint64_t res = (r.hash - lo_hash) - ((uint64_t)(sub * bm.sub_width[LANE_CFG]) << bm.sh);
+        rkey = (res << rank_bits) | pidx;
+        s_key[place] = rkey;
+    }
+    __syncthreads();
+    uint32_t rank = 0, seg0 = 0;
+    if (live) {
+        // sorted position = start of the sub-range + members with a smaller key; segment head = start + members with a smaller
+        // HASH (key < hkey <=> smaller hash: the index sits below rank_bits)
+        const uint32_t lo = s_cnt[sub], hi = s_cnt[sub + 1];
+        const uint64_t hkey = rkey & ~((1ull << rank_bits) - 1ull);
+        uint32_t smaller = 0, below = 0;
+        for (uint32_t p = lo; p < hi; p++) {
+            const uint64_t kp = s_key[p];
+            smaller += kp < rkey ? 1u : 0u;
+            below += kp < hkey ? 1u : 0u;
+        }
+        rank = lo + smaller;
+        seg0 = lo + below;
+    }
+    __syncthreads();                      // every lane is done with s_key (= s_m0) and the counters (= s_m1, s_seg)
+    if (live) {
+        s_hash[rank] = r.hash; s_rid[rank] = r.rid; s_m0[rank] = r.m0; s_m1[rank] = r.m1;
+        s_seg[rank] = (uint16_t)seg0;
+    }
+    __syncthreads();
+    // ---- sorted position j = tid: head, mate-2 skip (sketch.rs:852), tag -------------------------------------------------
+    const uint32_t j = tid;
+    const uint32_t seg = live ? (uint32_t)s_seg[j] : 0u;
+    const bool head = live && seg == j;
+    const uint64_t rid = live ? s_rid[j] : 0ull;
+    uint32_t* const s_tag = reinterpret_cast<uint32_t*>(lds.ab);   // (s_a | s_b are written after the marker test)
+    bool skip = false;                    // a mate 2 whose mate 1 holds the k-mer too
+    if (live) {
+        if constexpr (PAIRED) {
+            const uint64_t rec = rid & RID_MASK;
+            if (rec & 1) {
+                for (uint32_t q = j; q > seg;) {
+                    q--;
+                    const uint64_t rq = s_rid[q] & RID_MASK;
+                    if ((rq >> 1) != (rec >> 1)) break;
+                    if ((rq & 1) == 0) { skip = true; break; }
+                }
+            }
+        }
+        if constexpr (!filter && !no_dedup)
+            s_tag[j] = (!skip && (rid & RID_MARKER_BIT)) ? (marker_tag(s_m0[j]) | (marker_tag(s_m1[j]) << 16)) : 0u;
+    }
+    if constexpr (!filter && !no_dedup) __syncthreads();
+    // ---- duplicate flag -------------------------------------------------------------------------------------------------
+    bool dup = false;                     // would be dropped
+    if (live && !skip && (rid & RID_MARKER_BIT)) {
+        if constexpr (filter) {
+            // the filter's answer (the bit a10_mark left in the record), unless this is the first of the k-mer in the walk: the lowest
+            // emission rank among the segment's leading occurrences of the head's record (see replay_bucket)
+            if (rid & RID_A10_BIT) {
+                const uint64_t rec0 = s_rid[seg] & RID_MASK;
+                bool walk_first = (rid & RID_MASK) == rec0;
+                if (walk_first) {
+                    const uint64_t rank_j = (rid >> RID_RANK_SHIFT) & RID_RANK_MAX;
+                    for (uint32_t q = seg; q < n && (uint32_t)s_seg[q] == seg && (s_rid[q] & RID_MASK) == rec0; q++)
+                        if (q != j && ((s_rid[q] >> RID_RANK_SHIFT) & RID_RANK_MAX) < rank_j) { walk_first = false; break; }
+                }
+                dup = !walk_first;
+            }
+        } else if constexpr (!no_dedup) {
+            // the k-mer's earlier occurrences, one word of two 15-bit tags each; the markers themselves only where a tag matches
+            const uint64_t a = s_m0[j], bb = s_m1[j];
+            bool hit = false;
+            const uint32_t ta = marker_tag(a) * 0x00010001u, tb = marker_tag(bb) * 0x00010001u;
+            for (uint32_t q = seg; q < j; q++) {
+                const uint32_t w = s_tag[q], za = w ^ ta, zb = w ^ tb;
+                if ((((za - 0x00010001u) & ~za) | ((zb - 0x00010001u) & ~zb)) & 0x80008000u) {     // a zero halfword in either
+                    const uint64_t x = s_m0[q], y = s_m1[q];
+                    if (w && (x == a || y == a || x == bb || y == bb)) { hit = true; break; }
+                }
+            }
+            dup = j != seg && (hit || a == bb);
+        }
+    }
+    const bool u = live && !skip && (no_dedup || !dup);            // would count
+    // ---- counts (cut-off rule, sketch.rs:706) and rows --------------------------------------------------------------------
+    uint32_t base_h, total_heads, total_removed;
+    if constexpr (PAIRED) {
+        // no cut-off: counted = would-count, ONE block scan of (would-count, heads, removed) packed 10+10+10 bits
+        const bool removed = live && !skip && !u;
+        uint32_t tot = 0;
+        const uint32_t base = block_excl_sum<LANE_CAP>((u ? 1u : 0u) | (head ? 1u << 10 : 0u) | (removed ? 1u << 20 : 0u), s_wave, &tot);
+        base_h = (base >> 10) & 0x3FFu;
+        total_heads = (tot >> 10) & 0x3FFu;
+        total_removed = tot >> 20;
+        if (live) {
+            s_b[j] = (uint16_t)(base & 0x3FFu);                    // Ec[j] = Eu[j]
+            if (j + 1 == n) s_b[n] = (uint16_t)((base & 0x3FFu) + (u ? 1u : 0u));
+        }
+        __syncthreads();
+    } else {
+        // P = would-be-counted occurrences before j in its k-mer: counted from the cut-off on whatever the markers say
+        uint32_t tot_uh = 0;
+        const uint32_t base_uh = block_excl_sum<LANE_CAP>((u ? 1u : 0u) | (head ? 1u << 16 : 0u), s_wave, &tot_uh);
+        base_h = base_uh >> 16;
+        total_heads = tot_uh >> 16;
+        if (live) s_a[j] = (uint16_t)(base_uh & 0xFFFFu);          // Eu[j]
+        __syncthreads();
+        bool c = false;
+        if (live && !skip) c = ((uint32_t)s_a[j] - (uint32_t)s_a[seg] >= SINGLE_CUTOFF) ? true : u;
+        const bool removed = live && !skip && !c;
+        uint32_t tot_cr = 0;
+        const uint32_t base_c = block_excl_sum<LANE_CAP>((c ? 1u : 0u) | (removed ? 1u << 16 : 0u), s_wave, &tot_cr) & 0xFFFFu;
+        total_removed = tot_cr >> 16;
+        if (live) {
+            s_b[j] = (uint16_t)base_c;                             // Ec[j]
+            if (j + 1 == n) s_b[n] = (uint16_t)(base_c + (c ? 1u : 0u));
+        }
+        __syncthreads();
+    }
+    if (head) {
+        // segment end = next head or n: walk (segments here are shorter than SEG_LIMIT)
+        uint32_t e = j + 1;
+        while (e < n && s_seg[e] == j) e++;
+        tmp_k[first + base_h] = s_hash[j];
+        tmp_c[first + base_h] = (uint32_t)s_b[e] - (uint32_t)s_b[j];
+    }
+    if (tid == 0) { ra.n_distinct[b] = total_heads; ra.removed_b[b] = total_removed; }
+}
+
+// LANE: which instance of the lane body the kernel carries beside replay_bucket — LANE_OFF (none: replay_bucket runs every bucket, as
+// before round 10) or lane_mode(paired, dedup).  The choice per bucket is uniform over the workgroup: at most LANE_CAP occurrences,
+// consistent bounds, composite keys with a one-word ranking key -> the lane body; everything else (129 ... 256 occurrences, larger
+// ones queued, inconsistent bounds counted) -> replay_bucket, in the same launch and the same LDS.
+constexpr int LANE_OFF = -1;
+constexpr int lane_mode(bool paired, int dedup) { return (paired ? 1 : 0) | (dedup << 1); }
+// (num_sgpr: two bodies in one kernel take 101 scalar registers when left alone, one more than 8 wavefronts per SIMD leave each — and
+//  with the LDS admitting 15 workgroups per CU, 7.5 wavefronts per SIMD, the eighth counts; held to 100 nothing spills)
+template <int CAP, int RTPB, int LANE = LANE_OFF>
+__global__ __launch_bounds__(RTPB) __attribute__((amdgpu_num_sgpr(100))) void bucket_replay_kernel(ReplayArgs ra) {
+    __shared__ ReplayLds<CAP, RTPB> lds;
+    if constexpr (LANE != LANE_OFF) {
+        static_assert(CAP == CAP_SMALL && RTPB == LANE_CAP, "the lane body shares the 256-slot configuration's workgroup");
+        const uint32_t first = ra.boff[blockIdx.x], last = ra.boff[blockIdx.x + 1];
+        if (first < last && last <= *ra.p_nv && last - first <= (uint32_t)LANE_CAP && ra.bm.composite && ra.bm.rank_bits[LANE_CFG]) {
+            replay_bucket_lane<(LANE & 1) != 0, (LANE >> 1)>(blockIdx.x, first, last - first, ra, lds);
+            return;
+        }
+    }
+    replay_bucket<CAP, RTPB>(blockIdx.x, ra, lds);
 }
 
 // Marker-less samples (single-end; long reads or --no-dedup: sylph_sketch::n_plain): nothing is ever dropped, the table is the
@@ -790,8 +1006,9 @@ __global__ __launch_bounds__(RTPB) void bucket_count_list_kernel(ReplayArgs ra, 
 template <int CAP, int RTPB>
 __global__ __launch_bounds__(RTPB) void bucket_replay_list_kernel(ReplayArgs ra, const uint32_t* __restrict__ my_list) {
     const uint32_t n_listed = my_list[0];
+    __shared__ ReplayLds<CAP, RTPB> lds;
     for (uint32_t i = blockIdx.x; i < n_listed; i += gridDim.x) {
-        replay_bucket<CAP, RTPB>(my_list[1 + i], ra);
+        replay_bucket<CAP, RTPB>(my_list[1 + i], ra, lds);
         __syncthreads();   // the LDS arrays are reused by the next bucket
     }
 }
@@ -949,6 +1166,26 @@ __global__ __launch_bounds__(256) void ovf_patch_kernel(const uint32_t* __restri
     if (threadIdx.x == 0) n_distinct[b] = n;
 }
 
+// The 256-slot launch: the instance that carries the lane body for the sample's mode (pairs or single-end, exact set or filter —
+// the modes a sample can come in by default or by one flag); any other combination, a build with another workgroup size and the
+// stage cuts of SYLPH_REPLAY_STAGE (which the lane body does not have) take replay_bucket alone.
+void launch_replay(sylph_ctx* ctx, uint32_t B, const ReplayArgs& ra, bool paired, bool stage_cut) {
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(B), dim3(RTPB_SMALL), 0, ctx->stream, ra); };
+    if constexpr (RTPB_SMALL == LANE_CAP) {
+        if (!stage_cut) {
+            if (paired && ra.dedup == DEDUP_EXACT) return go(bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, lane_mode(true, DEDUP_EXACT)>);
+            if (paired && ra.dedup == DEDUP_FILTER) return go(bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, lane_mode(true, DEDUP_FILTER)>);
+            if (!paired && ra.dedup == DEDUP_EXACT) return go(bucket_replay_kernel<CAP_SMALL, RTPB_SMALL, lane_mode(false, DEDUP_EXACT)>);
+        }
+    }
+    go(bucket_replay_kernel<CAP_SMALL, RTPB_SMALL>);
+}
+// Which body a launch_replay of this map sends a bucket of n occurrences to (the kernel's own test, for the road counters)
+bool lane_road(const BucketMap& bm, uint32_t n, bool paired, int dedup, bool stage_cut) {
+    const bool instance = RTPB_SMALL == LANE_CAP && !stage_cut && (dedup == DEDUP_EXACT || (paired && dedup == DEDUP_FILTER));
+    return instance && n >= 1 && n <= (uint32_t)LANE_CAP && bm.composite && bm.rank_bits[LANE_CFG];
+}
+
 uint32_t grid_of(uint64_t n, uint32_t tpb = 256) { return (uint32_t)((n + tpb - 1) / tpb); }
 
 }  // namespace
@@ -974,19 +1211,20 @@ bool finish_bucketed(sylph_sketch* sk) {
     const uint64_t hs_max = thr >> bm.sh;                              // hashes are < thr
     bm.mult = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, ((uint64_t)B << 32) / (hs_max + 1));
     bm.B = B;
+    bm.inv_mult = bm.mult > 1 ? (uint64_t)(((unsigned __int128)1 << 64) / bm.mult) : ~0ull;
     // widest bucket in hs units is ceil(2^32 / mult) + 1; the key needs (range << sh) to fit in 64 - IDX_BITS bits
     const uint64_t range_hs = (0x100000000ull + bm.mult - 1) / std::max<uint32_t>(1, bm.mult) + 1;
     bm.composite = bm.mult >= 1 && bit_length(range_hs) + bm.sh <= 64 - IDX_BITS;
     bm.range_hs = (uint32_t)std::min<uint64_t>(range_hs, 0xFFFFFFFFull);
     {
-        const uint32_t caps[3] = {(uint32_t)CAP_SMALL, (uint32_t)CAP_MID, (uint32_t)CAP_LARGE};
-        for (int i = 0; i < 3; i++) bm.sub_mult[i] = range_hs > caps[i] ? (uint32_t)(((uint64_t)caps[i] << 32) / range_hs) : 0u;
+        const uint32_t caps[4] = {(uint32_t)CAP_SMALL, (uint32_t)CAP_MID, (uint32_t)CAP_LARGE, (uint32_t)LANE_CAP};   // ([LANE_CFG]: the lane body)
+        for (int i = 0; i < 4; i++) bm.sub_mult[i] = range_hs > caps[i] ? (uint32_t)(((uint64_t)caps[i] << 32) / range_hs) : 0u;
         // one-word ranking keys: sub-range s of configuration i (sub = floor(hs * sub_mult / 2^32), sub_mult rounded down) holds
         // hs values from s * width on (width = floor(range_hs / caps[i]) <= 2^32 / sub_mult) and below (s + 1) * 2^32 / sub_mult;
         // the distance between the two grows with s: the last sub-range gives the span every residue stays below
         const uint64_t max_index = slotted ? (uint64_t)sk->pend.n_blk * sk->pend.slot_cap : (uint64_t)n_all;
         const int index_bits = bit_length(max_index | 1);
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < 4; i++) {
             bm.sub_width[i] = bm.sub_mult[i] ? (uint32_t)(range_hs / caps[i]) : 1u;
             uint64_t span_hs = 1;
             if (bm.sub_mult[i]) {
@@ -1060,7 +1298,7 @@ bool finish_bucketed(sylph_sketch* sk) {
     // every launch below takes its sizes from device memory; the host synchronises ONCE, at the end (unless some buckets need
     // the list-driven configurations or the device-wide path)
     const int dbg = getenv("SYLPH_REPLAY_STAGE") ? atoi(getenv("SYLPH_REPLAY_STAGE")) : 0;
-    const uint32_t cutoff = sk->paired ? 0u : 4u;   // MAX_DEDUP_COUNT, constants.rs:14
+    const uint32_t cutoff = sk->paired ? 0u : SINGLE_CUTOFF;
     sk->out_k.reserve((size_t)n_cap * 8);          // upper bound: distinct k-mers <= occurrences
     sk->out_c.reserve((size_t)n_cap * 4);
     ReplayArgs ra{};
@@ -1081,7 +1319,7 @@ bool finish_bucketed(sylph_sketch* sk) {
         {
             ScopedKernelTimer t(ctx, "replay");
             if (plain) hipLaunchKernelGGL((bucket_count_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream, ra);
-            else hipLaunchKernelGGL((bucket_replay_kernel<CAP_SMALL, RTPB_SMALL>), dim3(B), dim3(RTPB_SMALL), 0, ctx->stream, ra);
+            else launch_replay(ctx, B, ra, sk->paired != 0, dbg != 0);
         }
     }
     // removed counts, table offsets, compaction, and everything the host needs to know in one block (FinishTail)
@@ -1119,6 +1357,21 @@ bool finish_bucketed(sylph_sketch* sk) {
     // filter dedup: were the partitioned pass's marks good (a10.hip)?  If not the phase walk has marked the records again, dense: from the top
     if (!a10_verdict(sk, host.a10_words)) return finish_bucketed(sk);
     if (host.overflow) return false;             // inconsistent bounds (defensive): the generic path redoes the sample
+    if (ctx->profile && !plain && (ctx->profile_only.empty() || ctx->profile_only.find(",replay,") != std::string::npos)) {
+        // road counters (tests and tools ask sylph_ctx_kernel_stats how many buckets took which body): from the bucket offsets, on the
+        // host — the kernel keeps no count.  Only where the replay family is timed at all: a region that times the seeding kernel
+        // alone (bench.py's quoted rate) pays no read-back.
+        std::vector<uint32_t> h_boff((size_t)B + 1);
+        ctx->d2h(h_boff.data(), boff, ((size_t)B + 1) * 4);
+        uint64_t n_lane = 0, n_general = 0;
+        for (uint32_t i = 0; i < B; i++) {
+            const uint32_t n_b = h_boff[i + 1] - h_boff[i];
+            if (lane_road(bm, n_b, sk->paired != 0, ra.dedup, dbg != 0)) n_lane++;
+            else if (n_b) n_general++;
+        }
+        ctx->stats["replay_lane"].launches += n_lane;
+        ctx->stats["replay_general"].launches += n_general;
+    }
     if (plain && host.n_ovf) {
         // k-mers more than a thousand deep in a marker-less sample: write the occurrence records after all and take the usual
         // kernels from the start (their overflow path works on records and on the index permutation)
