@@ -1,40 +1,17 @@
-// partition.h — the two-level MSD partition by hash range (round 3), shared by the replay (replay_lds.hip: occurrences by k-mer
-// hash) and the filter dedup (a10.hip: operations by class hash).  Kernels only move 8-byte pairs; see replay_lds.hip's header.
+// partition.h — the two-level MSD partition by hash range, shared by the replay (replay_lds.hip: occurrences by k-mer hash) and the
+// filter dedup (a10.hip: operations by class hash).  Kernels only move 8-byte pairs; see replay_lds.hip's header.  The map from a hash
+// to its bucket (BucketMap and its arithmetic) is replay_plan.h's, which compiles without HIP and is tested on the CPU.
 #pragma once
 #include "common.h"
 #include "device_common.h"
 #include "sketch_session.h"
+#include "replay_plan.h"
 
 namespace sylph {
 namespace {
 
-// Bucket of a hash: hs = hash >> sh (its 32 most significant bits below the threshold), b = (hs * mult) >> 32 — B
-// equal ranges for ANY B (not only powers of two), monotone in the hash.  Inverse used by the replay kernel: the
-// smallest hs of bucket b is ceil(b * 2^32 / mult).
-// range_hs = widest bucket in hs units; sub_mult[i] = floor(2^32 * CAP_i / range_hs) for the three replay configurations and, fourth,
-// the one-occurrence-per-lane body with its 128 sub-ranges (the sub-range of a hash inside its bucket, see replay_bucket /
-// replay_bucket_lane), 0 when a bucket is narrower than CAP_i hs units.
-// rank_bits[i] > 0: (hash - lowest hash the sub-range can hold) << rank_bits | gather index fits in 64 bits for configuration
-// i — the key the occurrences of a sub-range are ranked by with ONE compare; sub_width[i] = floor(range_hs / CAP_i) hs units (a
-// lower bound of where sub-range s begins: s * sub_width).  inv_mult = floor(2^64 / mult) (2^64 - 1 for mult = 1): bucket_lo_key.
-struct BucketMap { int sh; uint32_t mult; uint32_t B; int composite; uint32_t range_hs; uint32_t sub_mult[4]; uint32_t sub_width[4]; int rank_bits[4]; uint64_t inv_mult; };
+using namespace replay_plan;     // BucketMap, bucket_of_key, bucket_lo_hash / bucket_lo_key, sub_range_of: replay_plan.h
 
-__device__ __forceinline__ uint32_t bucket_of_key(uint32_t key, const BucketMap m) { return min(__umulhi(key, m.mult), m.B - 1u); }
-// lowest hash that maps to bucket b: key >= ceil(b * 2^32 / mult), the exact inverse of bucket_of_key
-__device__ __forceinline__ uint64_t bucket_lo_hash(uint32_t b, uint32_t mult, int sh) { return ((((uint64_t)b << 32) + mult - 1u) / mult) << sh; }
-// The same bound in key units — ceil(b * 2^32 / mult) — without the 64-bit division (about 130 scalar instructions per workgroup where
-// the operands are uniform): q = floor(b * inv / 2^32) with inv = floor(2^64 / mult) falls short of b * 2^32 / mult by less than
-// b / 2^32 < 1, so it is the true quotient's floor or one below; the remainder says which, and whether to round up.
-__device__ __forceinline__ uint64_t bucket_lo_key(uint32_t b, uint32_t mult, uint64_t inv) {
-    uint64_t q = (uint64_t)b * (uint32_t)(inv >> 32) + (((uint64_t)b * (uint32_t)inv) >> 32);
-    uint64_t r = ((uint64_t)b << 32) - q * mult;            // in [0, 2 * mult)
-    if (r >= mult) { q++; r -= mult; }
-    return q + (r ? 1u : 0u);
-}
-// sub-range (of `cap`) of a key's distance `res` to its bucket's lowest key; sub_mult = BucketMap::sub_mult of the configuration
-__device__ __forceinline__ uint32_t sub_range_of(uint32_t res, uint32_t sub_mult, uint32_t cap) {
-    return sub_mult ? min(__umulhi(res, sub_mult), cap - 1u) : min(res, cap - 1u);
-}
 // The place an entry takes inside its bin: how many took one there before it.  `fill` holds one 16-bit counter per bin, zeroed by the
 // caller (16-bit LDS atomics do not exist: the counter pairs share a word; add 1 or 65536 to the word and take the half).
 __device__ __forceinline__ uint32_t take_place(uint16_t* fill, uint32_t bin) {

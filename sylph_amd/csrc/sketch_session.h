@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "replay_plan.h"
 
 namespace sylph {
 // rid: bit 63 = the record (pair) has dedup markers; bit 62 = approximate dedup only (a10.hip): the filter reported one of the
@@ -23,8 +24,7 @@ struct alignas(32) OccRec { uint64_t hash, rid, m0, m1; };
 
 namespace sylph {
 void flush_pending_slots(sylph_sketch* sk);   // reads.hip
-// bits of a hash kept in the 32-bit bucket key of an occurrence: key = hash >> key_shift(c) (hashes are below u64::MAX / c)
-inline int key_shift(uint32_t c) { return std::max(0, bit_length(UINT64_MAX / (uint64_t)std::max<uint32_t>(c, 1)) - 32); }
+using replay_plan::key_shift;                 // replay_plan.h: key = hash >> key_shift(c), the 32-bit bucket key of an occurrence
 // dedup: DEDUP_EXACT (dup_removal_lsh_full_exact), DEDUP_NONE (--no-dedup), DEDUP_FILTER (dup_removal_lsh_full: the marker test is
 // the RID_A10_BIT a10_mark left in the records)
 constexpr int DEDUP_EXACT = 0, DEDUP_NONE = 1, DEDUP_FILTER = 2;

@@ -70,3 +70,40 @@ def bgzf_compress(data, block=65280, level=6):
         out += b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, bsize - 1)
         out += body + struct.pack("<II", zlib.crc32(chunk), len(chunk))
     return bytes(out)
+
+
+LANE_CAP, IDX_BITS = 128, 10      # replay_plan.h
+
+
+def occurrence_hashes(b, off, c):
+    """Every occurrence of a sampled k-mer in the reads: what the seeding kernel hands to the replay."""
+    from oracle import oracle as O
+    return np.concatenate([O.extract_markers(b[int(off[i]):int(off[i + 1])], c=c) for i in range(len(off) - 1)] + [np.zeros(0, np.uint64)])
+
+
+def bucket_roads(hashes, c, target):
+    """The bucket map of finish_bucketed (make_bucket_map, replay_plan.h; tests/test_replay_plan.py holds this copy against the
+    header) for `hashes` -> dict: B, composite, n (occurrences per bucket), bucket (of every hash), fill (per bucket: the fullest sub-range of the body that runs it — 128 sub-ranges up to 128 occurrences,
+    256 above)."""
+    n_all = len(hashes)
+    thr = (2**64 - 1) // c
+    sh = max(0, thr.bit_length() - 32)
+    B = min(max(1, n_all // target), 1 << 24)
+    hs_max = thr >> sh
+    mult = min(0xFFFFFFFF, (B << 32) // (hs_max + 1))
+    range_hs = (2**32 + mult - 1) // max(1, mult) + 1
+    composite = mult >= 1 and range_hs.bit_length() + sh <= 64 - IDX_BITS
+    hs = hashes >> np.uint64(sh)                                                    # < 2^32, like mult: the products fit 64 bits
+    bucket = np.minimum((hs * np.uint64(mult)) >> np.uint64(32), np.uint64(B - 1)).astype(np.int64)
+    n = np.bincount(bucket, minlength=B)
+    fill = np.zeros(B, dtype=np.int64)
+    if composite:
+        lo = np.array([((b << 32) + mult - 1) // mult for b in range(B)], dtype=np.uint64)      # lowest hs of every bucket
+        res = hs - lo[bucket]
+        for cap in (LANE_CAP, 256):
+            of_cap = (n[bucket] <= LANE_CAP) == (cap == LANE_CAP)
+            sub_mult = ((cap << 32) // range_hs) if range_hs > cap else 0
+            sub = np.minimum((res * np.uint64(sub_mult)) >> np.uint64(32) if sub_mult else res, np.uint64(cap - 1)).astype(np.int64)
+            per = np.bincount((bucket * 256 + sub)[of_cap], minlength=B * 256).reshape(B, 256).max(axis=1)
+            fill = np.maximum(fill, per)
+    return dict(B=B, composite=composite, n=n, bucket=bucket, fill=fill)

@@ -1,11 +1,11 @@
-"""The two bodies of the 256-slot replay kernel (replay_lds.hip): buckets of up to 128 occurrences run with one occurrence per lane
+"""The two bodies of the 256-slot replay kernel (replay_lds.hip, replay_bucket.h): buckets of up to 128 occurrences run with one occurrence per lane
 (replay_bucket_lane), larger ones with two levels per lane (replay_bucket), in one launch.  Samples and bucket sizes that send every
 bucket through the lane body, through both, through the general body only; a k-mer at the depth where the lane body hands its bucket
 to the 512-slot configuration; the mate rules; a sample too small for composite keys.  Every table against the oracle, and the road
 each bucket took from the library's counters ("replay_lane", "replay_general": buckets per body while profiling is on).
 
 Which road a bucket takes is decided by its size, so the share of buckets a case leaves on the other body is a property of the
-sample and the bucket map: `bucket_roads` recomputes the map of finish_bucketed on the CPU from the oracle's occurrence hashes, and
+sample and the bucket map: `helpers.bucket_roads` recomputes the map of finish_bucketed on the CPU from the oracle's occurrence hashes, and
 every case asserts its precondition there before it looks at the GPU's counters."""
 import numpy as np
 import pytest
@@ -13,45 +13,12 @@ import pytest
 import sylph_amd as S
 from oracle import oracle as O
 
-from .helpers import concat, random_seq, revcomp
+from .helpers import bucket_roads, concat, occurrence_hashes, random_seq, revcomp
 from .test_gpu_parity import _sketch_gpu_once, assert_same_sketch, make_reads
 
 pytestmark = pytest.mark.gpu
 
-LANE_CAP, SEG_LIMIT, IDX_BITS = 128, 96, 10      # replay_lds.hip
-
-
-def occurrence_hashes(b, off, c):
-    """Every occurrence of a sampled k-mer in the reads: what the seeding kernel hands to the replay."""
-    return np.concatenate([O.extract_markers(b[int(off[i]):int(off[i + 1])], c=c) for i in range(len(off) - 1)] + [np.zeros(0, np.uint64)])
-
-
-def bucket_roads(hashes, c, target):
-    """The bucket map of finish_bucketed (BucketMap, partition.h) for `hashes` -> dict: B, composite, n (occurrences per bucket),
-    bucket (of every hash), fill (per bucket: the fullest sub-range of the body that runs it — 128 sub-ranges up to 128 occurrences,
-    256 above)."""
-    n_all = len(hashes)
-    thr = (2**64 - 1) // c
-    sh = max(0, thr.bit_length() - 32)
-    B = min(max(1, n_all // target), 1 << 24)
-    hs_max = thr >> sh
-    mult = min(0xFFFFFFFF, (B << 32) // (hs_max + 1))
-    range_hs = (2**32 + mult - 1) // max(1, mult) + 1
-    composite = mult >= 1 and range_hs.bit_length() + sh <= 64 - IDX_BITS
-    hs = hashes >> np.uint64(sh)                                                    # < 2^32, like mult: the products fit 64 bits
-    bucket = np.minimum((hs * np.uint64(mult)) >> np.uint64(32), np.uint64(B - 1)).astype(np.int64)
-    n = np.bincount(bucket, minlength=B)
-    fill = np.zeros(B, dtype=np.int64)
-    if composite:
-        lo = np.array([((b << 32) + mult - 1) // mult for b in range(B)], dtype=np.uint64)      # lowest hs of every bucket
-        res = hs - lo[bucket]
-        for cap in (LANE_CAP, 256):
-            of_cap = (n[bucket] <= LANE_CAP) == (cap == LANE_CAP)
-            sub_mult = ((cap << 32) // range_hs) if range_hs > cap else 0
-            sub = np.minimum((res * np.uint64(sub_mult)) >> np.uint64(32) if sub_mult else res, np.uint64(cap - 1)).astype(np.int64)
-            per = np.bincount((bucket * 256 + sub)[of_cap], minlength=B * 256).reshape(B, 256).max(axis=1)
-            fill = np.maximum(fill, per)
-    return dict(B=B, composite=composite, n=n, bucket=bucket, fill=fill)
+LANE_CAP, SEG_LIMIT = 128, 96      # replay_plan.h
 
 
 class Roads:
