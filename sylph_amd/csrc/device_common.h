@@ -21,13 +21,28 @@ __device__ __forceinline__ uint64_t mm_hash64(uint64_t key) {
 // Same function with the instruction selection pinned for gfx950.  Left to itself the compiler folds every
 // "x + (x << n)" into a 64-bit multiply and lowers that to 2-3 v_mad_u64_u32 plus operand shuffling (~15 mads and
 // ~19 v_mov per k-mer).  Measured issue costs on MI355X (tools/valu_rates.hip; VOP2 32-bit op = 1): v_lshl_add_u64
-// 1.9, v_lshlrev/lshrrev_b64 1.6, v_mad_u64_u32 1.9, any VOP3 32-bit op 1.6.  v_lshl_add_u64 (shift <= 4) does
-// x*9, x*5 and x*21 in one/two instructions; the NOT of step 1 is folded into step 2 as one xor with a constant:
+// 1.9, v_lshlrev/lshrrev_b64 1.6, v_mad_u64_u32 1.9, v_mul_lo_u32 and any VOP3 32-bit op 1.6.  v_lshl_add_u64 (shift <= 4) does
+// x*5 and x*21 in one/two instructions and, behind one shift, the first and the last step.  * 265 is mul_const_u64: one v_mul_lo_u32
+// on the high word and ONE v_mad_u64_u32 where the chain (<< 8, + 9t) took three 64-bit instructions: 2.2 % on the sample rate.  * 21
+// the same way is two instructions for two and measured equal (tools/hash_variants.hip V4 / V5, profiles/r12_hash_mad.md), so it
+// keeps its chain.  The NOT of step 1 is folded into step 2 as one xor with a constant:
 //   ~t ^ (~t >> 24)  ==  (t ^ (t >> 24)) ^ 0xFFFFFF0000000000.
 template <int N>
 __device__ __forceinline__ uint64_t lshl_add_u64(uint64_t a, uint64_t b) {   // (a << N) + b, N in 0..4
     uint64_t d;
     asm("v_lshl_add_u64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(N), "v"(b));
+    return d;
+}
+// t * C (mod 2^64) for a 32-bit constant:  lo(t) * (C - 1)  +  { lo(t), hi(t) * C mod 2^32 }.  The mad's 64-bit addend is t itself
+// with its high word multiplied in place: no register has to be cleared or moved to form the pair.  The constants ride in SGPRs (the one
+// constant-bus operand of either instruction) and the mad's carry-out goes to an SGPR pair nobody reads — not to vcc, where the k-mer
+// loops keep their compares.
+template <uint32_t C>
+__device__ __forceinline__ uint64_t mul_const_u64(uint64_t t) {
+    uint32_t th;
+    asm("v_mul_lo_u32 %0, %1, %2" : "=v"(th) : "v"((uint32_t)(t >> 32)), "s"(C));
+    uint64_t d, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"((uint32_t)t), "s"(C - 1u), "v"(((uint64_t)th << 32) | (uint32_t)t));
     return d;
 }
 __device__ __forceinline__ uint64_t mm_hash64_gfx950(uint64_t key) {
@@ -39,7 +54,7 @@ __device__ __forceinline__ uint64_t mm_hash64_gfx950(uint64_t key) {
         asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(hi) : "v"((uint32_t)(t >> 32)), "v"((uint32_t)(sh >> 32)), "s"(0xFFFFFF00u));
         t = ((uint64_t)hi << 32) | ((uint32_t)t ^ (uint32_t)sh);
     }
-    t = lshl_add_u64<0>(t << 8, lshl_add_u64<3>(t, t));           // * 265 = (t << 8) + 9t
+    t = mul_const_u64<265>(t);                                    // (t + (t << 3)) + (t << 8)
     t = t ^ (t >> 14);
     t = lshl_add_u64<4>(t, lshl_add_u64<2>(t, t));                // * 21
     t = t ^ (t >> 28);
@@ -59,7 +74,7 @@ __device__ __forceinline__ uint32_t mm_hash64_gfx950_hi1(uint64_t key) {
         asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(hi) : "v"((uint32_t)(t >> 32)), "v"((uint32_t)(sh >> 32)), "s"(0xFFFFFF00u));
         t = ((uint64_t)hi << 32) | ((uint32_t)t ^ (uint32_t)sh);
     }
-    t = lshl_add_u64<0>(t << 8, lshl_add_u64<3>(t, t));
+    t = mul_const_u64<265>(t);
     t = t ^ (t >> 14);
     t = lshl_add_u64<4>(t, lshl_add_u64<2>(t, t));
     t = t ^ (t >> 28);

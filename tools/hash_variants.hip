@@ -1,13 +1,18 @@
 // hash_variants.hip — round 5, VERDICT r04 #3: the k-mer loop of reads_kernel (csrc/reads.hip: two window extracts, canonical choice,
-// mm_hash64, threshold mask) with the hash / threshold written four ways, timed alone on the whole chip (5 waves per SIMD, like the
+// mm_hash64, threshold mask) with the hash / threshold written seven ways, timed alone on the whole chip (5 waves per SIMD, like the
 // kernel) on synthetic stream words held in LDS.  Reports ms per 8e8 k-mers and, with rocprofv3 --pmc SQ_INSTS_VALU, instructions
 // per k-mer.  Build on the GPU box: hipcc --offload-arch=gfx950 -O3 -I sylph_amd/csrc tools/hash_variants.hip -o /tmp/hash_variants
 //   V0  mm_hash64 as the compiler lowers it (64-bit multiplies)
-//   V1  mm_hash64_gfx950: what reads_kernel runs (v_lshl_add_u64 chains, the NOT folded into a v_bitop3)
+//   V1  every "x + (x << n)" a v_lshl_add_u64 chain, the NOT folded into a v_bitop3: what reads_kernel ran up to round 11
 //   V2  V1 with the LAST step on the high word only — h < T needs hi(h) unless hi(h) == hi(T): the mask is a superset (hi' <= hi(T),
 //       carry from the low word ignored), the 1-in-200 candidates are re-hashed exactly anyway (the cooperative pass) and would have
 //       to be re-TESTED there (2 false candidates per 2^32 k-mers: a tombstone path that the slots do not have today)
 //   V3  every 64-bit step spelled out on 32-bit halves (v_alignbit / v_add_co / v_addc): exact
+//   V4  V1 with * 265 as mul_const_u64 (device_common.h): v_mul_lo_u32 on the high word + ONE v_mad_u64_u32 for three 64-bit
+//       instructions: mm_hash64_gfx950, what reads_kernel runs
+//   V5  V4 with * 21 the same way (two for two; the mad's rate against v_lshl_add_u64's)
+//   V6  V5 with the first step (* (2^21 + 1)) and the last (* (2^31 + 1)) the same way (two for two each)
+// Every arm prints the sum of its masks: the exact arms (all but V2) must agree.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -41,6 +46,24 @@ __device__ __forceinline__ uint64_t hash_halves(uint64_t key) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// mm_hash64 with each multiply step either as its shift-add chain or as mul_const_u64
+template <bool M265, bool M21, bool MENDS>
+__device__ __forceinline__ uint64_t hash_spelled(uint64_t key) {
+    uint64_t t = MENDS ? mul_const_u64<(1u << 21) + 1u>(key) : lshl_add_u64<0>(key << 21, key);
+    {
+        uint64_t sh;
+        asm("v_lshrrev_b64 %0, 24, %1" : "=v"(sh) : "v"(t));
+        uint32_t hi;
+        asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(hi) : "v"((uint32_t)(t >> 32)), "v"((uint32_t)(sh >> 32)), "s"(0xFFFFFF00u));
+        t = ((uint64_t)hi << 32) | ((uint32_t)t ^ (uint32_t)sh);
+    }
+    t = M265 ? mul_const_u64<265>(t) : lshl_add_u64<0>(t << 8, lshl_add_u64<3>(t, t));
+    t = t ^ (t >> 14);
+    t = M21 ? mul_const_u64<21>(t) : lshl_add_u64<4>(t, lshl_add_u64<2>(t, t));
+    t = t ^ (t >> 28);
+    return MENDS ? mul_const_u64<(1u << 31) + 1u>(t) : lshl_add_u64<0>(t << 31, t);
+}
+
 template <int V>
 __device__ __forceinline__ void hash_and_mask(uint64_t canon, uint64_t thr, uint32_t& mask) {
     if constexpr (V == 2) {
@@ -61,7 +84,8 @@ __device__ __forceinline__ void hash_and_mask(uint64_t canon, uint64_t thr, uint
         const uint32_t thi = (uint32_t)(thr >> 32) + 1u;
         asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(hi), "s"(thi) : "vcc");
     } else {
-        const uint64_t h = V == 0 ? mm_hash64(canon) : V == 1 ? mm_hash64_gfx950(canon) : hash_halves(canon);
+        const uint64_t h = V == 0 ? mm_hash64(canon) : V == 1 ? hash_spelled<false, false, false>(canon) : V == 3 ? hash_halves(canon)
+                         : V == 4 ? mm_hash64_gfx950(canon) : V == 5 ? hash_spelled<true, true, false>(canon) : hash_spelled<true, true, true>(canon);
         asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(h), "s"(thr) : "vcc");
     }
 }
@@ -133,15 +157,23 @@ void run(const char* what, uint32_t* out) {
         if (rep) best = ms < best ? ms : best;
     }
     const double kmers = (double)blocks * 256 * n_grp * 16;
-    printf("%-58s %7.4f ms per launch of %.3e k-mers = %7.4f ms per 8.0e8 k-mers (one 1 Gbp sample of 2 x 150 bp)\n", what, best, kmers, best * 8.0e8 / kmers);
+    static uint32_t* host = (uint32_t*)malloc((size_t)blocks * 256 * 4);
+    (void)hipMemcpy(host, out, (size_t)blocks * 256 * 4, hipMemcpyDeviceToHost);
+    uint64_t sum = 0;
+    for (size_t i = 0; i < (size_t)blocks * 256; i++) sum += host[i];
+    printf("%-58s %7.4f ms per launch of %.3e k-mers = %7.4f ms per 8.0e8 k-mers (one 1 Gbp sample of 2 x 150 bp)  masks %016llx\n", what, best, kmers,
+           best * 8.0e8 / kmers, (unsigned long long)sum);
 }
 
 int main() {
     uint32_t* out;
     (void)hipMalloc(&out, (size_t)26042 * 256 * 4);
     run<0>("V0 mm_hash64 (compiler's multiplies)", out);
-    run<1>("V1 mm_hash64_gfx950 (reads_kernel today)", out);
+    run<1>("V1 v_lshl_add_u64 chains (reads_kernel up to round 11)", out);
     run<2>("V2 V1, last step + threshold on the high word (superset)", out);
     run<3>("V3 32-bit halves throughout (exact)", out);
+    run<4>("V4 V1, * 265 as mul + mad: mm_hash64_gfx950 (the kernel)", out);
+    run<5>("V5 V4, * 21 as mul + mad too", out);
+    run<6>("V6 V5, first and last step too", out);
     return 0;
 }
