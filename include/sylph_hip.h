@@ -34,7 +34,7 @@ extern "C" {
 #define SYLPH_ERR_HIP (-2)       /* HIP runtime error */
 #define SYLPH_ERR_NOMEM (-3)
 #define SYLPH_ERR_STATE (-4)     /* call made in the wrong session state */
-#define SYLPH_ERR_FORMAT (-5)    /* the input is not what this entry point parses (sylph_fastq_index): read it with the host reader */
+#define SYLPH_ERR_FORMAT (-5)    /* the input is not what this entry point parses (sylph_fastq_index, sylph_fasta_index): read it with the host reader */
 
 /* Which k-mers of a sequence are hashed.
  * SYLPH_SEED_SCALAR      = seeding.rs:86-146 fmh_seeds (every k-mer).
@@ -229,6 +229,35 @@ int sylph_fastq_counts(const sylph_fastq *f, uint64_t *n_records, uint64_t *n_ba
 int sylph_fastq_lengths(sylph_fastq *f, uint64_t first, uint64_t n, uint32_t *out);
 int sylph_sketch_push_fastq(sylph_sketch *sk, sylph_fastq *a, sylph_fastq *b, uint64_t first, uint64_t n_items);
 void sylph_fastq_destroy(sylph_fastq *f);
+
+/* ---- FASTA text, its records found and joined on the device (csrc/fasta.hip) -------------------------------------------------
+ * Replaces the record loops of sketch.rs:488-492 / :557-563 (needletail parse_fastx_file + next() over a genome file) for FASTA text:
+ * the TEXT goes to the device (`mem` as for sylph_fastq_index: host text is copied by the call, SYLPH_MEM_DEVICE text — the pointer
+ * sylph_inflated_file / _text lends, for gzip and bzip2 alike — is borrowed until sylph_fasta_destroy and must be readable from 16 bytes
+ * below `text` rounded down to 16 up to 16 bytes past its end).  The very first byte is '>'; every line whose first byte is '>' is a
+ * header; a record's id is its header line without the '>' and without its line end; its sequence is every following non-header line,
+ * line ends removed, joined in order.  An empty line contributes nothing, a header directly followed by a header or by the end is a
+ * record of length 0 (kept), the last line needs no newline, and a '\r' directly in front of a '\n' or of the end of the text belongs to
+ * the line end.  Returns SYLPH_ERR_FORMAT — and nothing else happens — for an empty text, a first byte other than '>' (FASTQ-format
+ * genomes, a leading blank line), any other '\r', and a text of 2^32 - 4096 bytes or more: the caller then reads the file with its own
+ * reader, whose record and error semantics are the reference's.  sylph_fasta_counts: records, bases and bytes of all ids;
+ * sylph_fasta_lengths: the sequence lengths of records [first, first + n); sylph_fasta_ids: their ids side by side in `out` (room for
+ * `cap` bytes), id i = out[id_off[i] .. id_off[i + 1]), id_off has n + 1 entries; sylph_fasta_bases: their joined sequences side by side
+ * (tests, tools).  An index belongs to its context and must be destroyed before it.
+ * sylph_sketch_genomes_fasta joins the sequences of `files` side by side into one device batch and sketches it as sylph_sketch_genomes
+ * does: individual = 0 makes one genome per file (its records are the contigs), individual != 0 one genome per record (sketch.rs:481-548).
+ * kmer_off / tracked_off have (genomes + 1) entries; outputs, ownership and the batch limit (2^32 - 1 bases, else SYLPH_ERR_INVALID) are
+ * sylph_sketch_genomes'. */
+typedef struct sylph_fasta sylph_fasta;
+int sylph_fasta_index(sylph_ctx *ctx, const void *text, uint64_t n_bytes, int mem, sylph_fasta **out);
+int sylph_fasta_counts(const sylph_fasta *f, uint64_t *n_records, uint64_t *n_bases, uint64_t *id_bytes);
+int sylph_fasta_lengths(sylph_fasta *f, uint64_t first, uint64_t n, uint64_t *out);
+int sylph_fasta_ids(sylph_fasta *f, uint64_t first, uint64_t n, char *out, uint64_t cap, uint64_t *id_off);
+int sylph_fasta_bases(sylph_fasta *f, uint64_t first, uint64_t n, uint8_t *host_out);
+void sylph_fasta_destroy(sylph_fasta *f);
+int sylph_sketch_genomes_fasta(sylph_ctx *ctx, sylph_fasta *const *files, uint32_t n_files, int individual, uint32_t c, uint32_t k,
+                               int seed_mode, uint64_t min_spacing, int pseudotax, uint64_t **out_kmers, uint64_t *kmer_off,
+                               uint64_t **out_tracked, uint64_t *tracked_off);
 
 /* ---- gzip inflated on the device (csrc/inflate.hip, round 6) ------------------------------------------------------------------
  * The reference's normal input is gzip (README.md:51): parse_fastx_file (sketch.rs:780-781, :906; :491, :562 for genomes) hands the

@@ -6,6 +6,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphDb { _p: [u8; 0] }
 #[repr(C)] pub struct SylphComm { _p: [u8; 0] }
 #[repr(C)] pub struct SylphFastq { _p: [u8; 0] }
+#[repr(C)] pub struct SylphFasta { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
@@ -124,6 +125,16 @@ extern "C" {
     pub fn sylph_fastq_lengths(f: *mut SylphFastq, first: u64, n: u64, out: *mut u32) -> c_int;
     pub fn sylph_sketch_push_fastq(sk: *mut SylphSketch, a: *mut SylphFastq, b: *mut SylphFastq, first: u64, n_items: u64) -> c_int;
     pub fn sylph_fastq_destroy(f: *mut SylphFastq);
+    // FASTA text (genome files) indexed and joined on the device; ERR_FORMAT = -5: keep the needletail reader for this file
+    pub fn sylph_fasta_index(ctx: *mut SylphCtx, text: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphFasta) -> c_int;
+    pub fn sylph_fasta_counts(f: *const SylphFasta, n_records: *mut u64, n_bases: *mut u64, id_bytes: *mut u64) -> c_int;
+    pub fn sylph_fasta_lengths(f: *mut SylphFasta, first: u64, n: u64, out: *mut u64) -> c_int;
+    pub fn sylph_fasta_ids(f: *mut SylphFasta, first: u64, n: u64, out: *mut c_char, cap: u64, id_off: *mut u64) -> c_int;
+    pub fn sylph_fasta_bases(f: *mut SylphFasta, first: u64, n: u64, host_out: *mut u8) -> c_int;
+    pub fn sylph_fasta_destroy(f: *mut SylphFasta);
+    pub fn sylph_sketch_genomes_fasta(ctx: *mut SylphCtx, files: *const *mut SylphFasta, n_files: u32, individual: c_int, c: u32, k: u32,
+                                      seed_mode: c_int, min_spacing: u64, pseudotax: c_int, out_kmers: *mut *mut u64, kmer_off: *mut u64,
+                                      out_tracked: *mut *mut u64, tracked_off: *mut u64) -> c_int;
     // round 6: gzip inflated on the device (what flate2 does inside parse_fastx_file, sketch.rs:780-781 / :906): compressed bytes in,
     // text in HBM out (hand the pointer to sylph_fastq_index with MEM_DEVICE); ERR_FORMAT = -5: keep the flate2 reader for this file
     pub fn sylph_inflate(ctx: *mut SylphCtx, gz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;

@@ -39,6 +39,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_db_replicate", "sylph_pipeline_create_multi", "sylph_pipeline_replica_of_last", "sylph_device_count",
            "sylph_genome_shard_bounds", "sylph_db_upload_genome_shard",
            "sylph_fastq_index", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
+           "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
+           "sylph_sketch_genomes_fasta",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
            "sylph_bunzip2", "sylph_bunzip2_files"]
 
@@ -82,6 +84,14 @@ def load():
     L.sylph_sketch_push_fastq.argtypes = [vp, vp, vp, u64, u64]
     L.sylph_fastq_destroy.argtypes = [vp]
     L.sylph_fastq_destroy.restype = None
+    L.sylph_fasta_index.argtypes = [vp, vp, u64, i32, P(vp)]
+    L.sylph_fasta_counts.argtypes = [vp, P(u64), P(u64), P(u64)]
+    L.sylph_fasta_lengths.argtypes = [vp, u64, u64, vp]
+    L.sylph_fasta_ids.argtypes = [vp, u64, u64, vp, u64, vp]
+    L.sylph_fasta_bases.argtypes = [vp, u64, u64, vp]
+    L.sylph_fasta_destroy.argtypes = [vp]
+    L.sylph_fasta_destroy.restype = None
+    L.sylph_sketch_genomes_fasta.argtypes = [vp, P(vp), u32, i32, u32, u32, i32, u64, i32, P(vp), vp, P(vp), vp]
     L.sylph_inflate.argtypes = [vp, vp, u64, i32, P(vp)]
     L.sylph_inflated_text.argtypes = [vp, P(vp), P(u64)]
     L.sylph_inflate_files.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, P(vp)]
@@ -249,6 +259,17 @@ class Context:
                                            int(pseudotax), mem, C.byref(ok), _ptr(koff), C.byref(ot), _ptr(toff)))
         return _take(ok, int(koff[-1]), np.uint64), koff, _take(ot, int(toff[-1]), np.uint64), toff
 
+    # the same batch from FASTA texts indexed on the device (FastaText): their sequences are joined on the device, no base visits the host
+    def sketch_genomes_fasta(self, files, individual=False, c=200, k=31, seed_mode=SEED_AVX2_COMPAT, min_spacing=30, pseudotax=True):
+        """-> (kmers, kmer_off, tracked, tracked_off) as sketch_genomes: one genome per file, or (individual) one per record."""
+        G = sum(f.n_records for f in files) if individual else len(files)
+        koff, toff = np.zeros(G + 1, dtype=np.uint64), np.zeros(G + 1, dtype=np.uint64)
+        ok, ot = C.c_void_p(), C.c_void_p()
+        hs = (C.c_void_p * max(1, len(files)))(*[f._h.value for f in files])
+        _check(load().sylph_sketch_genomes_fasta(self._h, hs, len(files), int(bool(individual)), c, k, seed_mode, min_spacing, int(pseudotax),
+                                                 C.byref(ok), _ptr(koff), C.byref(ot), _ptr(toff)))
+        return _take(ok, int(koff[-1]), np.uint64), koff, _take(ot, int(toff[-1]), np.uint64), toff
+
 
 def pack_2bit(ascii_bases):
     """sylph_pack_2bit: BYTE_TO_SEQ codes, 4 bases per byte, first base in the top bits (host function, no GPU needed)."""
@@ -365,6 +386,59 @@ class FastqText:
     def close(self):
         if self._h:
             load().sylph_fastq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FastaText:
+    """sylph_fasta_*: FASTA text whose records the DEVICE finds and joins (csrc/fasta.hip).  `text`: bytes / a uint8 array (MEM_HOST), or
+    an integer address with n_bytes (MEM_HOST_PINNED / MEM_DEVICE; device text — what Inflated / Bunzipped lend — is borrowed until
+    close()).  Raises SylphHipError with code ERR_FORMAT when the text is not FASTA this index takes: parse it on the host then."""
+
+    def __init__(self, ctx, text, mem=MEM_HOST, n_bytes=None):
+        self._h = None
+        h = C.c_void_p()
+        if mem == MEM_HOST:
+            self._keep = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else _np(text, np.uint8)
+            _check(load().sylph_fasta_index(ctx._h, _ptr(self._keep) if len(self._keep) else None, len(self._keep), mem, C.byref(h)))
+            self._keep = None
+        else:
+            _check(load().sylph_fasta_index(ctx._h, C.c_void_p(int(text)), int(n_bytes), mem, C.byref(h)))
+        self._h = h
+        nr, nb, ni = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(load().sylph_fasta_counts(self._h, C.byref(nr), C.byref(nb), C.byref(ni)))
+        self.n_records, self.n_bases, self.id_bytes = int(nr.value), int(nb.value), int(ni.value)
+
+    def lengths(self, first=0, n=None):
+        n = self.n_records - first if n is None else n
+        out = np.zeros(n, dtype=np.uint64)
+        _check(load().sylph_fasta_lengths(self._h, int(first), int(n), _ptr(out)))
+        return out
+
+    def ids(self, first=0, n=None):
+        """the ids of records [first, first + n) as a list of bytes"""
+        n = self.n_records - first if n is None else n
+        out, off = np.zeros(max(1, self.id_bytes), dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+        _check(load().sylph_fasta_ids(self._h, int(first), int(n), _ptr(out), self.id_bytes, _ptr(off)))
+        raw = out.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+    def bases(self, first=0, n=None):
+        """the joined sequences of records [first, first + n), side by side (uint8 array)"""
+        n = self.n_records - first if n is None else n
+        total = int(self.lengths(first, n).sum()) if n else 0
+        out = np.zeros(total, dtype=np.uint8)
+        _check(load().sylph_fasta_bases(self._h, int(first), int(n), _ptr(out) if total else None))
+        return out
+
+    def close(self):
+        if self._h:
+            load().sylph_fasta_destroy(self._h)
             self._h = None
 
     def __del__(self):

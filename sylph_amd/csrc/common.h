@@ -244,6 +244,7 @@ struct ReadsState { uint32_t long_record; SpillState spill; };   // reads.hip: a
 void sort_keys_u32(sylph_ctx* ctx, const uint32_t* kin, uint32_t* kout, size_t n, int begin_bit, int end_bit);
 void sort_keys_u64(sylph_ctx* ctx, const uint64_t* kin, uint64_t* kout, size_t n, int begin_bit, int end_bit);
 void exclusive_sum_u32(sylph_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);   // out[i] = sum in[0..i)
+void exclusive_sum_u64(sylph_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n);   // (two packed 32-bit sums: fasta.hip)
 void inclusive_max_u32(sylph_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
 
 inline int bit_length(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }

@@ -69,6 +69,13 @@ void exclusive_sum_u32(sylph_ctx* ctx, const uint32_t* in, uint32_t* out, size_t
     });
 }
 
+void exclusive_sum_u64(sylph_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n) {
+    if (n == 0) return;
+    with_temp(ctx, [&](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), ctx->stream);
+    });
+}
+
 void inclusive_max_u32(sylph_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n) {
     if (n == 0) return;
     with_temp(ctx, [&](void* tmp, size_t& bytes) {

@@ -1,5 +1,6 @@
-// cmd_sketch.cpp — the `sketch` command (sketch.rs:276-479) and the genome batches behind it: parse records on the host, push
-// batches through the C ABI, write the reference's .sylsp / .syldb files.
+// cmd_sketch.cpp — the `sketch` command (sketch.rs:276-479) and the genome batches behind it: genome files indexed and joined on the
+// device (or, where the device declines, parsed on the host), batches pushed through the C ABI, the reference's .sylsp / .syldb files
+// written.
 #include <cstring>
 
 #include "host_internal.hpp"
@@ -27,10 +28,185 @@ GenomeBatch::Parsed GenomeBatch::parse_file(const std::string& ref_file, bool in
     return p;
 }
 
+bool fasta_device_enabled() {
+    static const bool on = [] {
+        if (!device_feed_enabled()) return false;
+        // opt-in: with the files read, decoded and indexed window by window on the engine's thread the command is not yet faster than the
+        // host road's `-t` threads (profiles/fasta_device_db_build.txt)
+        if (const char* e = getenv("SYLPH_HIP_FASTA_DEVICE")) return atoi(e) != 0;
+        return false;
+    }();
+    return on;
+}
+
+namespace {
+
+// the bytes of a regular file as they lie on disk (never a pipe: its bytes would be gone for the host reader); false: not for this road
+bool read_raw(const std::string& path, std::vector<uint8_t>& out) {
+    struct stat st;
+    if (stat(path.c_str(), &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0) return false;
+    FILE* fp = fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    out.resize((size_t)st.st_size);
+    const size_t got = fread(out.data(), 1, out.size(), fp);
+    fclose(fp);
+    return got == out.size();
+}
+Container container_of_bytes(const std::vector<uint8_t>& b) {
+    if (b.size() >= 2 && b[0] == 0x1f && b[1] == 0x8b) return Container::Gzip;
+    if (b.size() >= 2 && b[0] == 'B' && b[1] == 'Z') return Container::Bzip2;
+    return Container::Plain;
+}
+bool declined(int rc) { return rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM; }
+
+// f(i) for i in [0, n) on up to `threads` threads
+template <class F>
+void on_threads(size_t n, uint64_t threads, F&& f) {
+    std::atomic<size_t> next{0};
+    auto work = [&] { for (size_t i = next++; i < n; i = next++) f(i); };
+    std::vector<std::thread> pool;
+    for (size_t w = 1; w < std::min<size_t>(std::max<uint64_t>(threads, 1), n); w++) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+}
+
+}  // namespace
+
+void GenomeBatch::add_window_device(const std::vector<std::string>& files, size_t lo, size_t n, bool individual, uint64_t threads) {
+    FeedLaps laps;
+    sylph_ctx* ctx = e.context();
+    // the threads only read bytes
+    std::vector<std::vector<uint8_t>> raw(n);
+    std::vector<char> readable(n, 0);
+    on_threads(n, threads, [&](size_t i) { readable[i] = read_raw(files[lo + i], raw[i]) ? 1 : 0; });
+    // this thread decodes and indexes.  Compressed files of one container that follow each other are decoded by ONE call (bounded well
+    // below the decoders' 3 GiB of compressed bytes, so that text and batch stay within about 2 x BATCH_BASES); a call that is declined
+    // is retried file by file, and a file declined alone is the host reader's.
+    constexpr uint64_t DECODE_CALL_BYTES = 256ull << 20;
+    std::vector<DeviceGenomeFile> dv(n);
+    std::vector<char> ok(n, 0);
+    auto index = [&](size_t i, const void* text, uint64_t bytes, int mem) {
+        sylph_fasta* f = nullptr;
+        const int rc = sylph_fasta_index(ctx, text, bytes, mem, &f);
+        if (declined(rc)) return;
+        hip_check(rc, "sylph_fasta_index");
+        dv[i].fa.reset(f);
+        dv[i].file = files[lo + i];
+        dv[i].text_bytes = bytes;
+        hip_check(sylph_fasta_counts(f, &dv[i].n_records, &dv[i].n_bases, &dv[i].id_bytes), "sylph_fasta_counts");
+        ok[i] = 1;
+    };
+    auto decode = [&](Container c, size_t first, size_t count) {          // true: files [first, first + count) decoded and indexed
+        std::vector<const void*> ptrs;
+        std::vector<uint64_t> lens;
+        for (size_t i = first; i < first + count; i++) { ptrs.push_back(raw[i].data()); lens.push_back(raw[i].size()); }
+        sylph_inflated* h = nullptr;
+        const int rc = c == Container::Gzip ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)count, SYLPH_MEM_HOST, &h)
+                                            : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)count, SYLPH_MEM_HOST, &h);
+        if (declined(rc)) return false;
+        hip_check(rc, c == Container::Gzip ? "sylph_inflate_files" : "sylph_bunzip2_files");
+        std::shared_ptr<sylph_inflated> text(h, sylph_inflated_destroy);
+        for (size_t i = first; i < first + count; i++) {
+            const void* dev = nullptr;
+            uint64_t bytes = 0;
+            hip_check(sylph_inflated_file(h, (uint32_t)(i - first), &dev, &bytes), "sylph_inflated_file");
+            dv[i].text = text;
+            if (bytes) index(i, dev, bytes, SYLPH_MEM_DEVICE);
+            if (!ok[i]) dv[i].text.reset();
+        }
+        return true;
+    };
+    for (size_t i = 0; i < n;) {
+        if (!readable[i]) { i++; continue; }
+        const Container c = container_of_bytes(raw[i]);
+        if (c == Container::Plain) { index(i, raw[i].data(), raw[i].size(), SYLPH_MEM_HOST); i++; continue; }
+        if (!device_decode_enabled(c)) { i++; continue; }
+        size_t count = 0;
+        uint64_t bytes = 0;
+        while (i + count < n && readable[i + count] && container_of_bytes(raw[i + count]) == c && (count == 0 || bytes + raw[i + count].size() <= DECODE_CALL_BYTES)) {
+            bytes += raw[i + count].size();
+            count++;
+        }
+        if (!decode(c, i, count) && count > 1)
+            for (size_t j = i; j < i + count; j++) (void)decode(c, j, 1);
+        i += count;
+    }
+    raw.clear();
+    // what the device declined is read on the host, on the threads
+    std::vector<size_t> host_files;
+    for (size_t i = 0; i < n; i++) if (!ok[i]) host_files.push_back(i);
+    std::vector<Parsed> parsed(n);
+    on_threads(host_files.size(), threads, [&](size_t j) { parsed[host_files[j]] = parse_file(files[lo + host_files[j]], individual); });
+    // in file order; the batch of the other road is flushed first
+    constexpr uint64_t LIMIT = (1ull << 32) - 4096;
+    for (size_t i = 0; i < n; i++) {
+        if (!ok[i]) { flush_device(); append(std::move(parsed[i]), individual); continue; }
+        flush();
+        if (!dev_group.empty() && (dev_bases + dv[i].n_bases >= LIMIT || dev_text_bytes + dv[i].text_bytes >= BATCH_BASES)) flush_device();
+        dev_individual = individual;
+        dev_bases += dv[i].n_bases;
+        dev_text_bytes += dv[i].text_bytes;
+        dev_group.push_back(std::move(dv[i]));
+    }
+    flush_device();
+    if (FeedLaps::on()) {
+        char what[96];
+        snprintf(what, sizeof(what), "genomes fasta-device files=%zu declined=%zu", n, host_files.size());
+        laps.lap(what);
+    }
+}
+
+void GenomeBatch::flush_device() {
+    if (dev_group.empty()) return;
+    std::vector<DeviceGenomeFile> group;
+    group.swap(dev_group);
+    dev_text_bytes = dev_bases = 0;
+    const bool individual = dev_individual;
+    uint64_t G = 0;
+    std::vector<sylph_fasta*> hs;
+    for (const auto& f : group) { hs.push_back(f.fa.get()); G += individual ? f.n_records : 1; }
+    std::vector<uint64_t> koff(G + 1), toff(G + 1);
+    uint64_t *gk = nullptr, *tr = nullptr;
+    const int rc = sylph_sketch_genomes_fasta(e.context(), hs.data(), (uint32_t)hs.size(), individual ? 1 : 0, (uint32_t)c, (uint32_t)k,
+                                              SYLPH_SEED_AVX2_COMPAT, min_spacing, pseudotax ? 1 : 0, &gk, koff.data(), &tr, toff.data());
+    if (rc == SYLPH_ERR_NOMEM) {                                          // no room for text and batch side by side: the host road for these files
+        std::vector<std::string> names;
+        for (const auto& f : group) names.push_back(f.file);
+        group.clear();
+        for (const auto& f : names) append(parse_file(f, individual), individual);
+        flush();
+        return;
+    }
+    hip_check(rc, "sylph_sketch_genomes_fasta");
+    struct Free { uint64_t* p; ~Free() { sylph_free(p); } } f1{gk}, f2{tr};
+    uint64_t g = 0;
+    for (const auto& f : group) {
+        // names and sizes back from the index: the first record's id only unless `individual`
+        const uint64_t n_ids = individual ? f.n_records : std::min<uint64_t>(1, f.n_records);
+        std::vector<uint64_t> id_off(n_ids + 1, 0), len(f.n_records);
+        std::vector<char> ids(f.id_bytes + 1);
+        hip_check(sylph_fasta_ids(f.fa.get(), 0, n_ids, ids.data(), f.id_bytes, id_off.data()), "sylph_fasta_ids");
+        hip_check(sylph_fasta_lengths(f.fa.get(), 0, f.n_records, len.data()), "sylph_fasta_lengths");
+        const uint64_t n_genomes = individual ? f.n_records : 1;
+        for (uint64_t r = 0; r < n_genomes; r++, g++) {
+            GenomeSketch s;
+            s.file_name = f.file;
+            if (r < n_ids) s.first_contig_name.assign(ids.data() + id_off[r], ids.data() + id_off[r + 1]);
+            s.gn_size = individual ? len[r] : f.n_bases;
+            s.genome_kmers.assign(gk + koff[g], gk + koff[g + 1]);
+            if (pseudotax) s.pseudotax_tracked_nonused_kmers = std::vector<uint64_t>(tr + toff[g], tr + toff[g + 1]);
+            s.c = c; s.k = k; s.min_spacing = min_spacing;
+            out.push_back(std::move(s));
+        }
+    }
+}
+
 void GenomeBatch::add_files(const std::vector<std::string>& files, bool individual, uint64_t threads) {
     const size_t window = std::max<size_t>(1, std::min<size_t>(threads, 64)) * 2;
+    const bool device_road = fasta_device_enabled();
     for (size_t lo = 0; lo < files.size(); lo += window) {
         const size_t n = std::min(window, files.size() - lo);
+        if (device_road) { add_window_device(files, lo, n, individual, threads); continue; }
         std::vector<Parsed> parsed(n);
         std::atomic<size_t> next{0};
         auto work = [&] { for (size_t i = next++; i < n; i = next++) parsed[i] = parse_file(files[lo + i], individual); };

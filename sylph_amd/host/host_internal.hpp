@@ -197,9 +197,22 @@ struct SampleRoute {
 std::optional<SequencesSketch> sketch_sample(Engine& e, const SampleFiles& files, const SampleParams& p, SampleRoute& route, sylph_sketch** keep);
 
 // ---- cmd_sketch.cpp ----
-// A batch of parsed genomes sketched by ONE sylph_sketch_genomes call (seeding, genome-wide duplicate removal and the spacing
-// filter all run on the device; sketch.rs:550-622 / :481-548 per genome).  Files are parsed on the host and appended until
-// the batch holds BATCH_BASES; results are split back into GenomeSketch records in input order.
+// SYLPH_HIP_FASTA_DEVICE=1: genome files take the device road (csrc/fasta.hip: the file's bytes travel, the device decodes them, finds
+// the FASTA records and joins the sequences); unset or 0 keeps the host reader.  The road needs device_feed_enabled().
+bool fasta_device_enabled();
+// One genome file on the device road: its FASTA index and, for a compressed file, the decoded text the index borrows (shared by the
+// files of one decode call; an index goes before its text)
+struct DeviceGenomeFile {
+    std::string file;
+    std::shared_ptr<sylph_inflated> text;
+    std::unique_ptr<sylph_fasta, void (*)(sylph_fasta*)> fa{nullptr, sylph_fasta_destroy};
+    uint64_t text_bytes = 0, n_records = 0, n_bases = 0, id_bytes = 0;
+};
+// A batch of genomes sketched by ONE sylph_sketch_genomes call (seeding, genome-wide duplicate removal and the spacing
+// filter all run on the device; sketch.rs:550-622 / :481-548 per genome).  On the host road files are parsed on the host and appended
+// until the batch holds BATCH_BASES; on the device road (add_files) indexed files are collected and sketched by ONE
+// sylph_sketch_genomes_fasta call.  A batch is all-host or all-device: whichever road a file takes, the other road's batch is flushed
+// first, so results come out in input order.
 struct GenomeBatch {
     static constexpr uint64_t BATCH_BASES = 1ull << 30;
     Engine& e;
@@ -229,6 +242,13 @@ struct GenomeBatch {
     void add_files(const std::vector<std::string>& files, bool individual, uint64_t threads);
     bool append(Parsed p, bool individual);
     void flush();
+    // the device road: files [lo, lo + n) read by the threads, decoded and indexed by this thread; what the device declines is parsed on
+    // the host as before.  A group of indexed files is bounded by BATCH_BASES bytes of text and by the batch limit of bases.
+    std::vector<DeviceGenomeFile> dev_group;
+    uint64_t dev_text_bytes = 0, dev_bases = 0;
+    bool dev_individual = false;
+    void add_window_device(const std::vector<std::string>& files, size_t lo, size_t n, bool individual, uint64_t threads);
+    void flush_device();
 };
 
 }  // namespace sylph_host
