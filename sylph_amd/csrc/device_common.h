@@ -81,6 +81,32 @@ __device__ __forceinline__ uint32_t mm_hash64_gfx950_hi1(uint64_t key) {
     return (uint32_t)(t >> 32) + __builtin_amdgcn_alignbit((uint32_t)(t >> 32), (uint32_t)t, 1) + 1u;
 }
 
+// min of two values < 2^62 as unsigned integers: as doubles both are non-negative and finite (exponent <= 0x3FF: no NaN, no Inf),
+// where double order == unsigned order; f64 denormals are preserved (kernel descriptor FLOAT_DENORM_MODE_16_64 = 3)
+__device__ __forceinline__ uint64_t min_u62(uint64_t a, uint64_t b) { uint64_t d; asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+
+// (the read kernel's window extracts, csrc/reads.hip kmer_step; tools/hash_variants.hip V8 uses the same)
+// 32 stream bits from bit P (counted MSB first) of the forward words A0:A1:A2 / from bit Q (counted LSB first) of the little-endian
+// multiword B2:B1:B0 of their reverse-complement images: a register as it is or one v_alignbit_b32 at a compile-time shift
+template <int P>
+__device__ __forceinline__ uint32_t fword(uint32_t A0, uint32_t A1, uint32_t A2) {
+    static_assert(P >= 0 && P <= 64);
+    if constexpr (P == 0) return A0;
+    else if constexpr (P < 32) return __builtin_amdgcn_alignbit(A0, A1, 32 - P);
+    else if constexpr (P == 32) return A1;
+    else if constexpr (P < 64) return __builtin_amdgcn_alignbit(A1, A2, 64 - P);
+    else return A2;
+}
+template <int Q>
+__device__ __forceinline__ uint32_t rword(uint32_t B0, uint32_t B1, uint32_t B2) {
+    static_assert(Q >= 0 && Q <= 64);
+    if constexpr (Q == 0) return B0;
+    else if constexpr (Q < 32) return __builtin_amdgcn_alignbit(B1, B0, Q);
+    else if constexpr (Q == 32) return B1;
+    else if constexpr (Q < 64) return __builtin_amdgcn_alignbit(B2, B1, Q - 32);
+    else return B2;
+}
+
 // types.rs:50-59 BYTE_TO_SEQ for one byte, computed instead of looked up:
 // A/a=0 C/c=1 G/g=2 T/t/U/u=3; raw bytes 1,2,3 -> 1,2,3; everything else (N, IUPAC, gaps, ...) -> 0.
 __device__ __forceinline__ uint32_t byte_to_seq(uint32_t b) {

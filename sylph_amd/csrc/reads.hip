@@ -13,10 +13,10 @@
 // as a 2-bit big-endian stream F (input may already BE 2-bit: SYLPH_ENC_2BIT, a quarter of the PCIe bytes).  Each lane then
 // walks ITS record with no rolling state at all: it keeps three lane-aligned stream words A(g..g+2) (16 bases each, refilled
 // from LDS once per 16 k-mers) and their reverse-complement images B = ~pairswap(bitreverse(A)); the forward k-mer t of the
-// group and its reverse complement are funnel-shift extracts (v_alignbit_b32) of those registers at COMPILE-TIME shifts,
-// both left-aligned in 64 bits with a few garbage bits below (the next base / the complement of the previous one), which
-// cannot change which of the two is smaller; one shift drops the garbage from the winner.  4 instructions per k-mer
-// instead of the 8 of a rolling update (r01), then the same hash / threshold sequences as the position kernel.
+// group and its reverse complement are funnel-shift and bit-field extracts (v_alignbit_b32, v_bfe_u32) of those registers at
+// COMPILE-TIME shifts, both right-aligned in 64 bits with clean tops, and the smaller of the two is ONE v_min_f64 (kmer_step):
+// 6 instructions per k-mer for both windows and the canonical choice, then the same hash / threshold sequences as the
+// position kernel.
 // Hits are accumulated as bit masks (one bit per k-mer, 32 k-mers per LDS word), counted, scanned across the workgroup —
 // lanes are in record order, so the scan gives file order — and only then re-hashed and written.
 #include <cstddef>
@@ -77,22 +77,27 @@ __device__ __forceinline__ void evenodd16(uint64_t x, uint32_t& ev, uint32_t& od
 }
 
 // One k-mer of a group of 16: T = index inside the group.  A0..A2: the lane-aligned forward words of the group and the two
-// behind it; Bm, B0..B2: reverse-complement images of the word before the group and of A0..A2.  Forward window = bases
-// [T, T + 32) of A0:A1:A2; reverse-complement window = bits [2T - D, 2T - D + 64) of the little-endian multiword Bm:B0:B1:B2
-// counted from B0's bit 0, D = 64 - 2K: both hold their k-mer in the top 2K bits.
+// behind it; B0..B2: their reverse-complement images.  Forward k-mer = stream bits [2T, 2T + 2K) of A0:A1:A2 counted from A0's
+// bit 31; its reverse complement = bits [2T, 2T + 2K) of the little-endian multiword B2:B1:B0 counted from B0's bit 0.  Both are
+// built RIGHT-ALIGNED with the top 64 - 2K bits zero: the low word is one funnel shift, the high word's 2K - 32 bits are a
+// v_bfe_u32 out of A0 / B1 where the field lies inside that word, else out of a 32-bit cut that the k-mers T0 = T & ~1 and T0 + 1 share
+// (2.5 instructions per window at most).  Two values below
+// 2^62 take their minimum in ONE v_min_f64 (min_u62, device_common.h) where compare + two selects + the shift of the winner
+// took four.
 template <int K, int T, int HV>
-__device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t Bm, uint32_t B0, uint32_t B1, uint32_t B2,
+__device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
                                           uint64_t thr, uint32_t& mask) {
-    constexpr int D = 64 - 2 * K;
-    uint32_t fhi, flo, rhi, rlo;
-    if constexpr (T == 0) { fhi = A0; flo = A1; }
-    else { fhi = __builtin_amdgcn_alignbit(A0, A1, 32 - 2 * T); flo = __builtin_amdgcn_alignbit(A1, A2, 32 - 2 * T); }
-    constexpr int OFF = 2 * T - D;
-    if constexpr (OFF < 0) { rlo = __builtin_amdgcn_alignbit(B0, Bm, OFF + 32); rhi = __builtin_amdgcn_alignbit(B1, B0, OFF + 32); }
-    else if constexpr (OFF == 0) { rlo = B0; rhi = B1; }
-    else { rlo = __builtin_amdgcn_alignbit(B1, B0, OFF); rhi = __builtin_amdgcn_alignbit(B2, B1, OFF); }
-    const uint64_t f = ((uint64_t)fhi << 32) | flo, rc = ((uint64_t)rhi << 32) | rlo;
-    const uint64_t canon = (f < rc ? f : rc) >> D;                                      // seeding.rs:134-139
+    static_assert(2 * K <= 62 && 2 * K > 32, "min_u62 wants both windows below 2^62; the high word holds 2K - 32 bits");
+    constexpr int HB = 2 * K - 32, T0 = T & ~1;
+    uint32_t fhi, rhi;
+    if constexpr (2 * T + HB <= 32) {                                                                // the field lies inside A0 / B1: no cut
+        fhi = __builtin_amdgcn_ubfe(A0, 32 - HB - 2 * T, HB); rhi = __builtin_amdgcn_ubfe(B1, 2 * T, HB);
+    } else {
+        const uint32_t cf = fword<2 * T0>(A0, A1, A2), cr = rword<2 * T0 + 32>(B0, B1, B2);          // shared by k-mers T0 and T0 + 1
+        fhi = __builtin_amdgcn_ubfe(cf, 32 - HB - 2 * (T - T0), HB); rhi = __builtin_amdgcn_ubfe(cr, 2 * (T - T0), HB);
+    }
+    const uint32_t flo = fword<2 * T + HB>(A0, A1, A2), rlo = rword<2 * T>(B0, B1, B2);
+    const uint64_t canon = min_u62(((uint64_t)fhi << 32) | flo, ((uint64_t)rhi << 32) | rlo);       // seeding.rs:134-139
     if constexpr (HV == 2) {
         // candidate test on the HIGH word: u = hi(h) + 1 - (the low word's carry), `thr` holds hi(T) + 1 here (reads_kernel)
         const uint32_t u = mm_hash64_gfx950_hi1(canon);
@@ -103,16 +108,16 @@ __device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2,
     }
 }
 template <int K, int T0, int HV>
-__device__ __forceinline__ void kmer_steps8(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t Bm, uint32_t B0, uint32_t B1, uint32_t B2,
+__device__ __forceinline__ void kmer_steps8(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
                                             uint64_t thr, uint32_t& mask) {
-    kmer_step<K, T0 + 0, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 1, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 2, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 3, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 4, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 5, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 6, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 7, HV>(A0, A1, A2, Bm, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 0, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 1, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 2, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 3, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 4, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 5, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 6, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 7, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
 }
 
 // blk_rec[b] = first record whose aligned start coordinate (off + bias) is >= b * rt, for b in [0, n_blk]
@@ -302,7 +307,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 
                     return a;
                 };
                 uint32_t A0 = next_word(0), A1 = next_word(1), A2 = next_word(2);
-                uint32_t Bm = 0, B0 = rcword(A0), B1 = rcword(A1), B2 = rcword(A2);  // (Bm only feeds garbage bits of group 0)
+                uint32_t B0 = rcword(A0), B1 = rcword(A1), B2 = rcword(A2);
                 const uint32_t n_half = (nh_max + 7) >> 3;                           // half-groups of 8 k-mers (uniform per wave)
                 // k-mer i <-> bit 31 - (i & 31) of word i >> 5: a group of 16 is one 16-bit half of its word, even groups the
                 // upper half.  Stored as halves (ds_write_b16): no "is the word complete" bookkeeping in the loop; whatever a
@@ -314,15 +319,15 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 
                 // extra register moves per k-mer)
                 for (uint32_t g = 0; g < n_grp; g++) {
                     uint32_t mask = 0;
-                    kmer_steps8<K, 0, HV>(A0, A1, A2, Bm, B0, B1, B2, thr_loop, mask);
-                    kmer_steps8<K, 8, HV>(A0, A1, A2, Bm, B0, B1, B2, thr_loop, mask);
+                    kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+                    kmer_steps8<K, 8, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
                     A0 = A1; A1 = A2; A2 = next_word(g + 3);
-                    Bm = B0; B0 = B1; B1 = B2; B2 = rcword(A2);
+                    B0 = B1; B1 = B2; B2 = rcword(A2);
                     mask_half[((g >> 1) * RTPB * 2) + ((g & 1u) ^ 1u)] = (uint16_t)mask;
                 }
                 if (n_half & 1u) {                                                   // a last half-group: its 8 k-mers are the top byte
                     uint32_t mask = 0;
-                    kmer_steps8<K, 0, HV>(A0, A1, A2, Bm, B0, B1, B2, thr_loop, mask);
+                    kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
                     mask_half[((n_grp >> 1) * RTPB * 2) + ((n_grp & 1u) ^ 1u)] = (uint16_t)(mask << 8);
                 }
             }

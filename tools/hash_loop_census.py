@@ -8,7 +8,7 @@ import collections, re, subprocess, sys
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 flt = sys.argv[sys.argv.index("--filter") + 1] if "--filter" in sys.argv else ""
 args = [a for a in args if a != flt]
-WATCH = ("v_mov_b32", "v_mad_u64_u32", "v_mul_lo_u32", "v_lshl_add_u64", "v_lshlrev_b64", "v_lshrrev_b64", "v_bitop3_b32", "v_cmp_lt_u64", "v_cmp_lt_u32", "s_nop")
+WATCH = ("v_mov_b32", "v_mad_u64_u32", "v_mul_lo_u32", "v_lshl_add_u64", "v_lshlrev_b64", "v_lshrrev_b64", "v_bitop3_b32", "v_cmp_lt_u64", "v_cmp_lt_u32", "v_min_f64", "v_bfe_u32", "v_cndmask_b32", "s_nop")
 
 
 def demangle(n):

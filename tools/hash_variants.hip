@@ -1,5 +1,5 @@
 // hash_variants.hip — round 5, VERDICT r04 #3: the k-mer loop of reads_kernel (csrc/reads.hip: two window extracts, canonical choice,
-// mm_hash64, threshold mask) with the hash / threshold written seven ways, timed alone on the whole chip (5 waves per SIMD, like the
+// mm_hash64, threshold mask) with the hash / threshold written seven ways and the canonical choice three ways, timed alone on the whole chip (5 waves per SIMD, like the
 // kernel) on synthetic stream words held in LDS.  Reports ms per 8e8 k-mers and, with rocprofv3 --pmc SQ_INSTS_VALU, instructions
 // per k-mer.  Build on the GPU box: hipcc --offload-arch=gfx950 -O3 -I sylph_amd/csrc tools/hash_variants.hip -o /tmp/hash_variants
 //   V0  mm_hash64 as the compiler lowers it (64-bit multiplies)
@@ -12,6 +12,10 @@
 //       instructions: mm_hash64_gfx950, what reads_kernel runs
 //   V5  V4 with * 21 the same way (two for two; the mad's rate against v_lshl_add_u64's)
 //   V6  V5 with the first step (* (2^21 + 1)) and the last (* (2^31 + 1)) the same way (two for two each)
+//   V7  V4 with the canonical choice as two v_lshrrev_b64 (each left-aligned window down to its clean right-aligned form) + ONE v_min_f64
+//       (min_u62, device_common.h) where V0-V6 spend v_cmp_lt_u64 + two v_cndmask_b32 + one shift: the fallback of round 13
+//   V8  V4 with both windows BUILT right-aligned with clean tops (v_alignbit_b32 low word, v_bfe_u32 high word out of a cut that two
+//       neighbouring k-mers share) + v_min_f64: what reads_kernel runs since round 13 (profiles/r13_canon_min.md)
 // Every arm prints the sum of its masks: the exact arms (all but V2) must agree.
 #include <hip/hip_runtime.h>
 
@@ -90,9 +94,19 @@ __device__ __forceinline__ void hash_and_mask(uint64_t canon, uint64_t thr, uint
     }
 }
 
+// (Bm, the image of the word in front of the group, is read by the left-aligned extracts of V0-V7 only; fword / rword: device_common.h)
 template <int K, int T, int V>
 __device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t Bm, uint32_t B0, uint32_t B1, uint32_t B2, uint64_t thr, uint32_t& mask) {
     constexpr int D = 64 - 2 * K;
+    static_assert(2 * K <= 62, "min_u62");
+    if constexpr (V == 8) {
+        constexpr int HB = 2 * K - 32, T0 = T & ~1;
+        const uint32_t cf = fword<2 * T0>(A0, A1, A2), cr = rword<2 * T0 + 32>(B0, B1, B2);
+        const uint32_t fhi = __builtin_amdgcn_ubfe(cf, 32 - HB - 2 * (T - T0), HB), rhi = __builtin_amdgcn_ubfe(cr, 2 * (T - T0), HB);
+        const uint32_t flo = fword<2 * T + HB>(A0, A1, A2), rlo = rword<2 * T>(B0, B1, B2);
+        hash_and_mask<4>(min_u62(((uint64_t)fhi << 32) | flo, ((uint64_t)rhi << 32) | rlo), thr, mask);
+        return;
+    }
     uint32_t fhi, flo, rhi, rlo;
     if constexpr (T == 0) { fhi = A0; flo = A1; }
     else { fhi = __builtin_amdgcn_alignbit(A0, A1, 32 - 2 * T); flo = __builtin_amdgcn_alignbit(A1, A2, 32 - 2 * T); }
@@ -101,7 +115,14 @@ __device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2,
     else if constexpr (OFF == 0) { rlo = B0; rhi = B1; }
     else { rlo = __builtin_amdgcn_alignbit(B1, B0, OFF); rhi = __builtin_amdgcn_alignbit(B2, B1, OFF); }
     const uint64_t f = ((uint64_t)fhi << 32) | flo, rc = ((uint64_t)rhi << 32) | rlo;
-    hash_and_mask<V>((f < rc ? f : rc) >> D, thr, mask);
+    if constexpr (V == 7) {
+        uint64_t fs, rs;
+        asm("v_lshrrev_b64 %0, %1, %2" : "=v"(fs) : "n"(D), "v"(f));
+        asm("v_lshrrev_b64 %0, %1, %2" : "=v"(rs) : "n"(D), "v"(rc));
+        hash_and_mask<4>(min_u62(fs, rs), thr, mask);
+    } else {
+        hash_and_mask<V>((f < rc ? f : rc) >> D, thr, mask);
+    }
 }
 template <int K, int T0, int V>
 __device__ __forceinline__ void steps8(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t Bm, uint32_t B0, uint32_t B1, uint32_t B2, uint64_t thr, uint32_t& mask) {
@@ -172,8 +193,13 @@ int main() {
     run<1>("V1 v_lshl_add_u64 chains (reads_kernel up to round 11)", out);
     run<2>("V2 V1, last step + threshold on the high word (superset)", out);
     run<3>("V3 32-bit halves throughout (exact)", out);
-    run<4>("V4 V1, * 265 as mul + mad: mm_hash64_gfx950 (the kernel)", out);
+    run<4>("V4 V1, * 265 as mul + mad: mm_hash64_gfx950 (the kernel of round 12)", out);
     run<5>("V5 V4, * 21 as mul + mad too", out);
     run<6>("V6 V5, first and last step too", out);
+    run<7>("V7 V4, canonical choice: 2 x v_lshrrev_b64 + v_min_f64", out);
+    run<8>("V8 V4, clean right-aligned windows + v_min_f64 (the kernel)", out);
+    run<4>("V4 again (clocks settled)", out);
+    run<7>("V7 again", out);
+    run<8>("V8 again", out);
     return 0;
 }

@@ -32,6 +32,11 @@ DEFK(k_cmp_lt_u64, asm volatile("v_cmp_lt_u64 vcc, %0, %1\n v_cndmask_b32 %4, %4
 DEFK(k_add3_u32, asm volatile("v_add3_u32 %0, %4, %0, %1\n v_add3_u32 %1, %5, %1, %2\n v_add3_u32 %2, %6, %2, %3\n v_add3_u32 %3, %7, %3, %0" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));)
 DEFK(k_perm, asm volatile("v_perm_b32 %0, %4, %0, %1\n v_perm_b32 %1, %5, %1, %2\n v_perm_b32 %2, %6, %2, %3\n v_perm_b32 %3, %7, %3, %0" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));)
 
+// round 13: the canonical choice as one FP64 min (min_u62, csrc/device_common.h) and the bit-field extracts of its clean windows
+DEFK(k_min_f64, asm volatile("v_min_f64 %0, %0, %1\n v_min_f64 %1, %1, %2\n v_min_f64 %2, %2, %3\n v_min_f64 %3, %3, %0" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));)
+DEFK(k_bfe_u32, asm volatile("v_bfe_u32 %0, %4, 2, 30\n v_bfe_u32 %1, %5, 0, 30\n v_bfe_u32 %2, %6, 22, 10\n v_bfe_u32 %3, %7, 20, 10" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));)
+DEFK(k_lshrrev_b32, asm volatile("v_lshrrev_b32 %0, 2, %4\n v_lshrrev_b32 %1, 2, %5\n v_lshrrev_b32 %2, 22, %6\n v_lshrrev_b32 %3, 20, %7" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "v"(y0), "v"(y1), "v"(y2), "v"(y3));)
+
 template <class K>
 void run(const char* name, K kern, int n_instr_per_rep) {
     uint64_t *out, *cyc;
@@ -68,5 +73,8 @@ int main() {
     run("cmp_lt_u64+cnd", k_cmp_lt_u64, 4);
     run("v_add3_u32", k_add3_u32, 4);
     run("v_perm_b32", k_perm, 4);
+    run("v_min_f64", k_min_f64, 4);
+    run("v_bfe_u32", k_bfe_u32, 4);
+    run("v_lshrrev_b32", k_lshrrev_b32, 4);
     return 0;
 }
