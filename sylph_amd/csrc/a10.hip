@@ -584,7 +584,7 @@ static void a10_mark_partitioned(sylph_sketch* sk) {
     in.carry = 1;
     uint32_t n_tiles;
     if (slotted) {
-        const uint32_t* blk_count = sk->slot_meta.as<uint32_t>() + (sk->pend.n_blk + 1);      // (layout: reads.hip SlotMeta)
+        const uint32_t* blk_count = slot_meta_of(sk, sk->pend.n_blk).blk_count;
         oin.recs = sk->slot_rec.as<OccRec>(); oin.blk_count = blk_count; oin.n_blk = sk->pend.n_blk; oin.slot_cap = sk->pend.slot_cap; oin.slotted = 1;
         static const uint32_t env_bpt = [] { const char* e = getenv("SYLPH_HIP_A10_BLK_PER_TILE"); return e ? (uint32_t)std::max(1, std::min(32, atoi(e))) : OPS_BLK_PER_TILE; }();
         in.slotted = 2; in.blk_count = blk_count; in.n_blk = sk->pend.n_blk; in.slot_cap = sk->pend.slot_cap; in.blk_per_tile = env_bpt;

@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sylph_hip.h"
@@ -240,6 +241,44 @@ void sort_pairs_u32_u32(sylph_ctx* ctx, const uint32_t* kin, uint32_t* kout, con
 constexpr uint32_t SPILL_MAX_TILES = 256;
 struct SpillState { uint32_t n_tiles; uint32_t tiles[SPILL_MAX_TILES]; };
 struct ReadsState { uint32_t long_record; SpillState spill; };   // reads.hip: a record too long for the short-read kernel was seen
+// What one lane leaves behind a block (read kernel) or tile (ordered position kernel) whose survivors went to slot region `it`.
+// First pass: the true count — a unit above slot_cap is redone into a spill region, and joins the list of those.  Redo pass (redo:
+// `it` indexes that list): where the unit's spill region is.
+__device__ __forceinline__ void close_slots(bool redo, uint32_t unit, uint32_t it, uint32_t count, uint32_t slot_cap, uint32_t* unit_count,
+                                            SpillState* spill, uint32_t* spill_slot_of_unit) {
+    if (redo) {
+        spill_slot_of_unit[unit] = it;
+    } else {
+        unit_count[unit] = count;
+        if (count > slot_cap) {
+            const uint32_t n = atomicAdd(&spill->n_tiles, 1u);
+            if (n < SPILL_MAX_TILES) spill->tiles[n] = unit;
+        }
+    }
+}
+
+// The k-mer loops' hash / threshold spelling asked for by SYLPH_HIP_HASH_VARIANT (a tuning knob), else dflt: 0 the compiler's own,
+// 1 mm_hash64_gfx950 + exact 64-bit test, 2 (read kernel only) the last hash step and the test on the high word only
+inline int hash_variant_env(int dflt) {
+    static const char* const e = getenv("SYLPH_HIP_HASH_VARIANT");
+    static const int v = e ? atoi(e) : 0;
+    return e ? v : dflt;
+}
+// f(integral_constant<int, K>, integral_constant<int, HV>) for k in {21, 31} (avx2_seeding.rs:46-52) and the spelling among
+// HV_LO..HV_HI that hv asks for (2 where there is one, else any non-zero is 1); false, having called nothing, for another k
+template <int HV_LO, int HV_HI, class F>
+bool with_k_hv(uint32_t k, int hv, F&& f) {
+    static_assert(HV_LO >= 0 && HV_LO <= 1 && HV_HI >= 1 && HV_HI <= 2, "spellings 0..2; every kernel has spelling 1");
+    auto with_hv = [&](auto kc) {
+        if (HV_HI == 2 && hv == 2) f(kc, std::integral_constant<int, HV_HI>{});
+        else if (HV_LO == 1 || hv) f(kc, std::integral_constant<int, 1>{});
+        else f(kc, std::integral_constant<int, HV_LO>{});
+    };
+    if (k == 31) with_hv(std::integral_constant<int, 31>{});
+    else if (k == 21) with_hv(std::integral_constant<int, 21>{});
+    else return false;
+    return true;
+}
 
 void sort_keys_u32(sylph_ctx* ctx, const uint32_t* kin, uint32_t* kout, size_t n, int begin_bit, int end_bit);
 void sort_keys_u64(sylph_ctx* ctx, const uint64_t* kin, uint64_t* kout, size_t n, int begin_bit, int end_bit);

@@ -234,7 +234,6 @@ __device__ __forceinline__ uint64_t find_record(const uint64_t* __restrict__ off
 // every row to the row behind it and lane 31 to the upper half (row_bcast:15 / :31, the gfx9 wave-scan idiom) — six v_add_u32 with a
 // dpp modifier.  The __shfl_up loop it replaces (round 6, VERDICT r05 #4b) is a ds_bpermute, a compare, a select and an add per step.
 __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
-#ifndef SYLPH_NO_DPP_SCAN
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);   // row_shr:1
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);   // row_shr:2
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);   // row_shr:4
@@ -242,15 +241,27 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1 and 3
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
     return x;
-#else
-    const uint32_t lane = threadIdx.x & 63;
+}
+
+// Exclusive prefix sum of one value per lane across a workgroup of TPB lanes (s_wave: TPB / 64 words of LDS, free again behind the
+// call); the workgroup's total through *total.  The one workgroup scan of the library: the seeding kernels, the partition, the replay
+// and the text-line kernels call it.  (Its first barrier keeps a second call's s_wave from the readers of the call before.)
+template <int TPB>
+__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t x = wave_inclusive_sum(v);
+    __syncthreads();
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
+    for (int w = 0; w < TPB / 64; w++) {
+        const uint32_t t = s_wave[w];
+        if ((uint32_t)w < wave) base += t;
+        tot += t;
     }
-    return x;
-#endif
+    if (total) *total = tot;
+    return base + x - v;
 }
 
 }  // namespace sylph

@@ -24,7 +24,6 @@
 #include "common.h"
 #include "device_common.h"
 #include "sketch_session.h"
-#include "partition.h"
 #include "text_lines.h"
 #include "fasta_plan.h"
 

@@ -21,7 +21,6 @@
 #include "common.h"
 #include "device_common.h"
 #include "sketch_session.h"
-#include "partition.h"
 #include "text_lines.h"
 
 struct sylph_fastq {

@@ -6,6 +6,7 @@
 #include "device_common.h"
 #include "sketch_session.h"
 #include "replay_plan.h"
+#include "seed_plan.h"
 
 namespace sylph {
 namespace {
@@ -46,8 +47,7 @@ constexpr uint32_t STAGE_PAIRS = SYLPH_STAGE_PAIRS;    // pairs a scatter workgr
 // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): give every XCD one contiguous eighth of the tiles, so
 // that the runs two neighbouring tiles append to the same coarse range — adjacent in memory — meet in the same L2.
 __device__ __forceinline__ uint32_t xcd_tile(uint32_t n_tiles) {
-    const uint32_t per_xcd = (n_tiles + 7) / 8;
-    return (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);      // may be >= n_tiles for the padding of the last XCD's range
+    return seed_plan::xcd_deal(blockIdx.x, n_tiles);             // may be >= n_tiles for the padding of the last XCD's range
 }
 
 // f(key, index, hash) for every occurrence of tile t (any order; all threads of the workgroup take part; hash = 0 from slots).  Slotted: eight groups of
@@ -103,10 +103,6 @@ __global__ __launch_bounds__(PART_TPB) void part_hist_kernel(PartIn in, BucketMa
     __syncthreads();
     for (uint32_t c = threadIdx.x; c < C; c += PART_TPB) hist[(size_t)c * n_tiles + t] = s_h[c];
 }
-
-// exclusive prefix sum of one value per lane across the workgroup; total returned through *total
-template <int RTPB>
-__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_wave, uint32_t* total);
 
 // one workgroup per coarse range: hist row -> exclusive offsets of the tiles inside the range; total[c] = size of the range
 // (round 6: rows of up to SCAN_ROW_LDS tiles go through LDS — read and written with consecutive lanes on consecutive words; with every
@@ -251,30 +247,6 @@ __global__ __launch_bounds__(TPB) void part_fine_kernel(const uint2* __restrict_
                 perm[atomicAdd(&s_cnt[v[u].x - b0], 1u)] = v[u].y;
         }
     }
-}
-
-// exclusive prefix sum of one value per lane across the workgroup (4 waves); total returned through *total
-template <int RTPB>
-__device__ __forceinline__ uint32_t block_excl_sum(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) s_wave[wave] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < RTPB / 64; w++) {
-        const uint32_t t = s_wave[w];
-        if ((uint32_t)w < wave) base += t;
-        tot += t;
-    }
-    if (total) *total = tot;
-    return base + x - v;
 }
 
 // Exclusive scan of CAP counters in LDS, CAP / TPB consecutive ones per lane: start[t] = sum of cnt[0 .. t), start[CAP] = their total

@@ -1,0 +1,434 @@
+// reads_block.h — the steps of the short-read seeding kernel (reads.hip reads_kernel: one lane per record), in the order the kernel
+// runs them for every pass of a block: load_stream, stage_offsets | record_geometry, deal_by_length, hash_record, count_hits,
+// publish_markers, list_survivors, finish_survivors | close_slots (common.h: shared with the position kernel).  The LDS they share is ReadsLds; which stream words, mask bits and
+// records belong to a block is seed_plan.h's arithmetic (free of HIP, tested on the CPU).  Every value of the hash loop lives in named
+// locals of hash_record: the steps pass scalars, never per-lane state in a struct.
+// What the compiler makes of the steps was held against the one-body kernel they came from (profiles/seed_steps_census.txt); three things
+// in their signatures come from that: ReadsLds travels by value and its pointers are LDS-typed, the steps' global pointers carry no
+// __restrict__ (the kernel's arguments do: a second set of alias scopes changed the schedule and spilled in two instances), and
+// stage_offsets gets its first index by value.
+#pragma once
+#include "common.h"
+#include "device_common.h"
+#include "seed_plan.h"
+#include "sketch_session.h"
+
+namespace sylph {
+namespace {
+
+using namespace seed_plan;
+
+template <int K>
+struct KC {
+    static constexpr uint64_t MASK = (1ull << (2 * K)) - 1;
+};
+
+// The workgroup's LDS.  Two arrays take over the place of two others, and nowhere else:
+//   * m0 / m1, the records' markers, lie over the staged offsets `off`: the lanes hold their offsets in registers by then (a block
+//     with several passes keeps its offsets in global memory instead);
+//   * hist, the dealing's histogram, lies over `first`, which is not in use before count_hits.
+// (The pointers carry the LDS address space in their type: every access through them is an LDS instruction whatever the optimiser makes
+//  of the code around it — with plain pointers the two arms of record_geometry, staged and global offsets, were merged into flat loads.)
+#define SY_LDS __attribute__((address_space(3)))
+template <int TPB>
+struct ReadsLds {
+    SY_LDS uint32_t* sF;                   // the block's stream: lds_words(rt) words (dynamic)
+    SY_LDS uint64_t* off;                  // staged record offsets: offs_staged(TPB) + 4
+    SY_LDS uint64_t *m0, *m1;              // per lane: the record's markers                                          (over off)
+    SY_LDS uint32_t (*mask)[TPB];          // [MASKW][TPB] hit masks, one column per record; the free rows hold the survivors' list
+    SY_LDS uint32_t* wave;                 // the scan's wave totals
+    SY_LDS uint32_t* first;                // per lane: its first hit of the pass (bit 31: has markers); [TPB] = the pass's total
+    SY_LDS uint32_t* hist;                 // 64 bins of the dealing                                                  (over first)
+    SY_LDS uint32_t* rel;                  // per lane: its record's stream base
+    SY_LDS uint16_t *perm, *nh;            // the dealing: lane -> record slot it hashes; per lane: its record's hashed k-mers
+    SY_LDS uint32_t *redo, *redo_deal;     // HV == 2: a candidate failed the exact test; the pass is ragged
+};
+template <int TPB>
+__device__ __forceinline__ ReadsLds<TPB> reads_lds() {
+    constexpr int OFFS = offs_staged(TPB);
+    extern __shared__ uint32_t sF[];
+    __shared__ uint64_t s_off[OFFS + 4];
+    __shared__ uint32_t s_mask[MASKW][TPB];
+    __shared__ uint32_t s_wave[TPB / 64];
+    __shared__ uint32_t s_first[TPB + 1], s_rel[TPB];
+    __shared__ uint16_t s_perm[TPB], s_nh[TPB];
+    __shared__ uint32_t s_redo, s_redo_deal;
+    static_assert((OFFS + 4) >= 2 * TPB, "the marker arrays alias the staged offsets");
+    static_assert(TPB + 1 >= 64, "the histogram aliases s_first");
+    using W = SY_LDS uint32_t*; using D = SY_LDS uint64_t*; using H = SY_LDS uint16_t*;
+    return ReadsLds<TPB>{(W)sF, (D)s_off, (D)s_off, (D)s_off + TPB, (SY_LDS uint32_t(*)[TPB])s_mask, (W)s_wave, (W)s_first, (W)s_first, (W)s_rel,
+                         (H)s_perm, (H)s_nh, (W)&s_redo, (W)&s_redo_deal};
+}
+
+// 64-bit window of 32 bases starting at stream base `b`: base b in bits 63:62
+__device__ __forceinline__ uint64_t win64(const SY_LDS uint32_t* sF, uint32_t b) {
+    const uint32_t j = b >> 4, ph = (b & 15u) * 2u;
+    const uint64_t x = ((uint64_t)sF[j] << 32) | sF[j + 1];
+    return (x << ph) | ((uint64_t)sF[j + 2] >> (32u - ph));   // ph = 0: second term shifts a 32-bit value by 32 -> 0
+}
+
+// reverse complement of the k-mer in the top 2K bits of x (anything below is ignored): field order reversed by a 64-bit
+// bit reversal, the two bits of every field swapped back, complement = bitwise NOT of a 2-bit code
+template <int K>
+__device__ __forceinline__ uint64_t revcomp_top(uint64_t x) {
+    const uint64_t rev = __brevll(x);
+    const uint64_t y = ((rev & 0x5555555555555555ull) << 1) | ((rev >> 1) & 0x5555555555555555ull);
+    return (~y) & KC<K>::MASK;
+}
+
+// every other base of a 32-base window, first base most significant (the order pair_kmer builds its 16-mers in): ev = bases
+// 0, 2, .., 30, od = bases 1, 3, .., 31.  Done on the two 32-bit halves: two shift-or steps bring the wanted fields of every
+// byte pair side by side (bytes 3 and 1 then hold four bases each), and ONE v_perm_b32 picks those bytes out of both halves —
+// 9-11 instructions per 16-mer where five 64-bit shift/or/and stages took about 25.
+__device__ __forceinline__ uint32_t even_fields_to_bytes31(uint32_t w) {
+    uint32_t t = w & 0xCCCCCCCCu;
+    t = (t | (t << 2)) & 0xF0F0F0F0u;
+    return t | (t << 4);                       // byte 3 = bases 0,2,4,6 of the half, byte 1 = bases 8,10,12,14
+}
+__device__ __forceinline__ void evenodd16(uint64_t x, uint32_t& ev, uint32_t& od) {
+    const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
+    // __builtin_amdgcn_perm(a, b, sel): selector 0-3 = bytes of b, 4-7 = bytes of a
+    ev = __builtin_amdgcn_perm(even_fields_to_bytes31(hi), even_fields_to_bytes31(lo), 0x07050301u);
+    od = __builtin_amdgcn_perm(even_fields_to_bytes31(hi << 2), even_fields_to_bytes31(lo << 2), 0x07050301u);
+}
+
+// One k-mer of a group of 16: T = index inside the group.  A0..A2: the lane-aligned forward words of the group and the two
+// behind it; B0..B2: their reverse-complement images.  Forward k-mer = stream bits [2T, 2T + 2K) of A0:A1:A2 counted from A0's
+// bit 31; its reverse complement = bits [2T, 2T + 2K) of the little-endian multiword B2:B1:B0 counted from B0's bit 0.  Both are
+// built RIGHT-ALIGNED with the top 64 - 2K bits zero: the low word is one funnel shift, the high word's 2K - 32 bits are a
+// v_bfe_u32 out of A0 / B1 where the field lies inside that word, else out of a 32-bit cut that the k-mers T0 = T & ~1 and T0 + 1 share
+// (2.5 instructions per window at most).  Two values below
+// 2^62 take their minimum in ONE v_min_f64 (min_u62, device_common.h) where compare + two selects + the shift of the winner
+// took four.
+template <int K, int T, int HV>
+__device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
+                                          uint64_t thr, uint32_t& mask) {
+    static_assert(2 * K <= 62 && 2 * K > 32, "min_u62 wants both windows below 2^62; the high word holds 2K - 32 bits");
+    constexpr int HB = 2 * K - 32, T0 = T & ~1;
+    uint32_t fhi, rhi;
+    if constexpr (2 * T + HB <= 32) {                                                                // the field lies inside A0 / B1: no cut
+        fhi = __builtin_amdgcn_ubfe(A0, 32 - HB - 2 * T, HB); rhi = __builtin_amdgcn_ubfe(B1, 2 * T, HB);
+    } else {
+        const uint32_t cf = fword<2 * T0>(A0, A1, A2), cr = rword<2 * T0 + 32>(B0, B1, B2);          // shared by k-mers T0 and T0 + 1
+        fhi = __builtin_amdgcn_ubfe(cf, 32 - HB - 2 * (T - T0), HB); rhi = __builtin_amdgcn_ubfe(cr, 2 * (T - T0), HB);
+    }
+    const uint32_t flo = fword<2 * T + HB>(A0, A1, A2), rlo = rword<2 * T>(B0, B1, B2);
+    const uint64_t canon = min_u62(((uint64_t)fhi << 32) | flo, ((uint64_t)rhi << 32) | rlo);       // seeding.rs:134-139
+    if constexpr (HV == 2) {
+        // candidate test on the HIGH word: u = hi(h) + 1 - (the low word's carry), `thr` holds hi(T) + 1 here (reads_kernel)
+        const uint32_t u = mm_hash64_gfx950_hi1(canon);
+        asm("v_cmp_ge_u32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(u), "s"((uint32_t)thr) : "vcc");
+    } else {
+        const uint64_t h = HV ? mm_hash64_gfx950(canon) : mm_hash64(canon);
+        asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(h), "s"(thr) : "vcc");
+    }
+}
+template <int K, int T0, int HV>
+__device__ __forceinline__ void kmer_steps8(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
+                                            uint64_t thr, uint32_t& mask) {
+    kmer_step<K, T0 + 0, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 1, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 2, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 3, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 4, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 5, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 6, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+    kmer_step<K, T0 + 7, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+}
+
+// 1. The block's stream words [0, n_words) from the aligned coordinate a0 on, as a 2-bit big-endian stream.  Only the first and the
+// last block of a batch reach outside [0, n_al): every other block loads unconditionally.
+template <int ENC, int TPB>
+__device__ __forceinline__ void load_stream(SY_LDS uint32_t* sF, const uint8_t* bases_al, uint64_t n_al, int64_t a0, uint32_t n_words) {
+    const uint32_t tid = threadIdx.x;
+    const bool interior = a0 >= 0 && (uint64_t)(a0 + (int64_t)n_words * 16) <= n_al;
+    if (interior) {
+        if constexpr (ENC == 0) {
+            const uint4* src = reinterpret_cast<const uint4*>(bases_al + a0);
+            for (uint32_t ci = tid; ci < n_words; ci += TPB) sF[ci] = pack16_fwd(src[ci]);
+        } else {
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(bases_al + (a0 >> 2));
+            for (uint32_t ci = tid; ci < n_words; ci += TPB) sF[ci] = __builtin_amdgcn_perm(0u, src[ci], 0x00010203u);
+        }
+    } else {
+        for (uint32_t ci = tid; ci < n_words; ci += TPB) {
+            const int64_t a = a0 + (int64_t)ci * 16;              // aligned base coordinate of this word's first base
+            if constexpr (ENC == 0) {                              // ASCII: 16 bytes -> one word
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (a >= 0 && (uint64_t)a < n_al) v = *reinterpret_cast<const uint4*>(bases_al + a);
+                sF[ci] = pack16_fwd(v);
+            } else {                                               // packed input: 4 bytes, first base in bits 7:6 of byte 0
+                uint32_t w = 0;
+                if (a >= 0 && (uint64_t)a < n_al) w = *reinterpret_cast<const uint32_t*>(bases_al + (a >> 2));
+                sF[ci] = __builtin_amdgcn_perm(0u, w, 0x00010203u);
+            }
+        }
+    }
+}
+
+// 2. The offsets of the block's records [R0, R1) (+ the mate-1 offset in front of a block that starts with a mate 2, + two behind) into
+// LDS, from index w_lo on.  False — nothing staged — where they do not fit or the block takes several passes.
+template <int TPB>
+__device__ __forceinline__ bool stage_offsets(const ReadsLds<TPB> s, const uint64_t* off, uint64_t n_rec, uint64_t R0, uint64_t R1,
+                                              uint64_t w_lo) {
+    const uint64_t w_hi = min(R1 + 2, n_rec);                   // last offset index needed
+    const bool in_lds = (w_hi - w_lo + 1) <= (uint64_t)(offs_staged(TPB) + 4) && (R1 - R0) <= (uint64_t)TPB;
+    if (in_lds)
+        for (uint64_t t = threadIdx.x; t <= w_hi - w_lo; t += TPB) s.off[t] = off[w_lo + t];
+    return in_lds;
+}
+
+// 3. The lane's record r (if r < R1): its length, the three offsets of its pair, the k-mers the reference hashes of it and its stream
+// base.  True: the record (or a mate of its pair) is longer than the halo — the host reruns the batch through the position kernel.
+template <int K, int TPB>
+__device__ __forceinline__ bool record_geometry(const ReadsLds<TPB> s, const uint64_t* off, bool in_lds, uint64_t w_lo, uint64_t r,
+                                                uint64_t R1, int paired, uint32_t bias, int64_t a0, int avx2_compat, uint64_t& L,
+                                                uint64_t& s1, uint64_t& s2, uint64_t& e2, uint32_t& nh, uint32_t& rel) {
+    const bool active = r < R1;
+    uint64_t start = 0;
+    L = 0; s1 = 0; s2 = 0; e2 = 0;
+    if (active) {
+        if (in_lds) {
+            start = s.off[r - w_lo];
+            L = s.off[r + 1 - w_lo] - start;
+            if (paired) { const uint64_t r1 = (r & ~1ull) - w_lo; s1 = s.off[r1]; s2 = s.off[r1 + 1]; e2 = s.off[r1 + 2]; }
+        } else {
+            start = off[r];
+            L = off[r + 1] - start;
+            if (paired) { const uint64_t r1 = r & ~1ull; s1 = off[r1]; s2 = off[r1 + 1]; e2 = off[r1 + 2]; }
+        }
+    }
+    const bool too_long = active && (L > (uint64_t)RH || (paired && (s2 - s1 > (uint64_t)RH || e2 - s2 > (uint64_t)RH)));
+    nh = (active && !too_long) ? (uint32_t)n_hashed_kmers(L, K, avx2_compat, 0) : 0u;
+    rel = active ? record_rel(start, bias, a0) : 0u;
+    return too_long;
+}
+
+// 4. A wavefront walks as many k-mer groups as its LONGEST record has: deal the pass's records to the lanes in order of
+// length (counting sort by the number of half-groups, longest first; ties in any order), so that trimmed reads of
+// 35..151 bp cost a wavefront what its own quartile needs instead of what the longest read of 64 needs.  Only the
+// hash loop runs in this order — hit masks are stored under the record's own slot and everything after the loop is
+// indexed by record again, so the output does not depend on the dealing.  A pass of equally long records (every
+// lane in one bin) is hashed as it lies.
+// Gives the record slot this lane hashes with that record's stream base and k-mers, and the mask rows the pass's longest record
+// reaches; returns whether the pass was dealt (uniform over the workgroup).
+template <int TPB>
+__device__ __forceinline__ bool deal_by_length(const ReadsLds<TPB> s, uint32_t nh, uint32_t rel, uint32_t& slot, uint32_t& rel_h, uint32_t& nh_h,
+                                               uint32_t& rows) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    if (tid < 64) s.hist[tid] = 0;
+    s.rel[tid] = rel;
+    s.nh[tid] = (uint16_t)nh;
+    // Round 6 (VERDICT r05 #4a): whether the pass needs dealing at all is asked FIRST — one compare with the first record's count and
+    // one LDS word — and a pass of equally long records (every pass of an untrimmed 2 x 150 bp sample) skips the histogram: its 256
+    // atomic adds all went to ONE counter (the LDS serialises them), then a scan and a barrier, to find that nothing moves.
+    if (tid == 0) *s.redo_deal = 0;
+    __syncthreads();
+    if (__ballot(nh != (uint32_t)s.nh[0]) && lane == 0) *s.redo_deal = 1;
+    __syncthreads();
+    const bool dealt = *s.redo_deal != 0;                      // uniform over the workgroup
+    const uint32_t bin = deal_bin(nh);                         // nh <= RH - 20: at most 48 half-groups
+    uint32_t hg_max = half_groups(nh), arrival = 0, hc = 0;
+    if (dealt) {
+        arrival = atomicAdd((uint32_t*)&s.hist[bin], 1u);
+        __syncthreads();
+        hc = s.hist[lane];
+        // the longest record of the pass (uniform over the workgroup: every wavefront reads the same histogram): its lowest
+        // non-empty bin; the mask rows above its words are free in this pass (see list_survivors)
+        const uint64_t bins_used = __ballot(hc != 0u);
+        hg_max = bins_used ? 63u - (uint32_t)(__ffsll((unsigned long long)bins_used) - 1) : 0u;   // half-groups of 8 k-mers
+    }
+    rows = rows_used(hg_max);
+    if (dealt) {
+        const uint32_t incl = wave_inclusive_sum(hc);
+        s.perm[(uint32_t)__shfl((int)(incl - hc), (int)bin) + arrival] = (uint16_t)tid;
+        __syncthreads();
+    }
+    slot = dealt ? s.perm[tid] : tid;
+    rel_h = dealt ? s.rel[slot] : rel;
+    nh_h = dealt ? s.nh[slot] : nh;
+    return dealt;
+}
+
+// 5. The hit masks of record slot `slot` (stream base rel_h, nh_h k-mers): every lane of the wavefront walks the groups of the
+// wavefront's longest record (seed_plan.h hash_hi_word: how far that reads).
+template <int K, int HV, int TPB>
+__device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot, uint32_t rel_h, uint32_t nh_h, uint64_t thr_loop) {
+    const SY_LDS uint32_t* const sF = s.sF;
+    uint32_t nh_max = nh_h;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) nh_max = max(nh_max, (uint32_t)__shfl_xor((int)nh_max, d));
+    if (nh_max) {
+        // lane-aligned stream words A(j) = bases [rel + 16 j, rel + 16 j + 16): one LDS read and one 64-bit shift each
+        const uint32_t w0 = rel_h >> 4, sh = 32u - (rel_h & 15u) * 2u;      // sh in [2, 32]
+        uint32_t raw = sF[w0], nxt = sF[w0 + 1];
+        auto next_word = [&](uint32_t j) {                                   // A(j), advancing the raw pair to j + 1
+            const uint32_t a = (uint32_t)((((uint64_t)raw << 32) | nxt) >> sh);
+            raw = nxt;
+            nxt = sF[w0 + j + 2];
+            return a;
+        };
+        uint32_t A0 = next_word(0), A1 = next_word(1), A2 = next_word(2);
+        uint32_t B0 = rcword(A0), B1 = rcword(A1), B2 = rcword(A2);
+        const uint32_t n_half = half_groups(nh_max);                         // half-groups of 8 k-mers (uniform per wave)
+        // k-mer i <-> bit 31 - (i & 31) of word i >> 5: a group of 16 is one 16-bit half of its word, even groups the
+        // upper half (seed_plan.h group_half).  Stored as halves (ds_write_b16): no "is the word complete" bookkeeping in the loop;
+        // whatever a half that was never written holds lies beyond nh and is cleared with the tail in count_hits.
+        SY_LDS uint16_t* const mask_half = (SY_LDS uint16_t*)&s.mask[0][slot];
+        const uint32_t n_grp = n_half >> 1;
+        // whole groups of 16: one straight-line block (the odd half-group of a record's tail is done after the loop —
+        // with the test inside the loop the second half of every group lived in its own basic block and took two
+        // extra register moves per k-mer)
+        for (uint32_t g = 0; g < n_grp; g++) {
+            uint32_t mask = 0;
+            kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+            kmer_steps8<K, 8, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+            A0 = A1; A1 = A2; A2 = next_word(g + 3);
+            B0 = B1; B1 = B2; B2 = rcword(A2);
+            mask_half[group_half(g, TPB)] = (uint16_t)mask;
+        }
+        if (n_half & 1u) {                                                   // a last half-group: its 8 k-mers are the top byte
+            uint32_t mask = 0;
+            kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+            mask_half[group_half(n_grp, TPB)] = (uint16_t)(mask << 8);
+        }
+    }
+}
+
+// 6. The real hits of the lane's own record (k-mer i < nh; the bits beyond are cleared from its last word), scanned over the
+// workgroup: lanes are in record order, so `first` — the hits in front of this lane's — is file order.  Returns the lane's count.
+template <int TPB>
+__device__ __forceinline__ uint32_t count_hits(const ReadsLds<TPB> s, uint32_t nh, uint32_t& first, uint32_t& total) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t cnt = 0;
+    const uint32_t nw = mask_words(nh);
+    for (uint32_t w = 0; w + 1 < nw; w++) cnt += __popc(s.mask[w][tid]);
+    if (nw) {                                                   // the record's last word: bits beyond k-mer nh - 1 are not its own
+        const uint32_t m = s.mask[nw - 1][tid] & tail_mask(nh);
+        s.mask[nw - 1][tid] = m;
+        cnt += __popc(m);
+    }
+    first = block_excl_sum<TPB>(cnt, (uint32_t*)s.wave, &total);
+    return cnt;
+}
+
+// 7. Survivors (1 in c k-mers) are finished COOPERATIVELY: lanes publish where their hits start in the pass and their
+// record's markers; then the pass's hits are dealt one per lane (finish_survivors).  (Each lane looping over its own hits made every
+// wavefront run the ~95-instruction body as often as its busiest lane had hits: 3-4 times for ~0.6 hits per lane.)
+template <int TPB>
+__device__ __forceinline__ void publish_markers(const ReadsLds<TPB> s, uint32_t cnt, uint32_t first, uint32_t total, int want_markers, int paired,
+                                                uint64_t L, uint64_t s1, uint64_t s2, uint64_t e2, uint32_t rel, uint32_t bias, int64_t a0) {
+    const uint32_t tid = threadIdx.x;
+    uint64_t m0 = 0, m1 = 0;
+    uint32_t has = 0;
+    if (cnt && want_markers) {
+        uint32_t ba = 0, bb = 0;
+        if (!paired) {
+            if (L >= 66 && L <= 400) { has = 1; ba = rel; bb = rel + (uint32_t)(L / 2); }       // sketch.rs:625-656, :923
+        } else if (s2 - s1 >= 33 && e2 - s2 >= 33) {                                             // sketch.rs:659-688
+            has = 1;
+            ba = record_rel(s1, bias, a0);
+            bb = record_rel(s2, bias, a0);
+        }
+        if (has) {
+            const uint64_t wa64 = win64(s.sF, ba), wb64 = win64(s.sF, bb);
+            uint32_t ea, oa, eb, ob;
+            evenodd16(wa64, ea, oa);
+            evenodd16(wb64, eb, ob);
+            m0 = (uint64_t)ea | ((uint64_t)eb << 32);
+            m1 = (uint64_t)oa | ((uint64_t)ob << 32);
+        }
+    }
+    s.m0[tid] = m0;
+    s.m1[tid] = m1;
+    s.first[tid] = first | (has << 31);
+    if (tid == 0) s.first[TPB] = total;
+}
+
+// 8. The pass's survivors as a list, hit number -> (lane, k-mer index), written by the lanes that own them (a lane has
+// 0.6 hits on average: a short loop over its own mask words) into the mask rows no record of this pass reaches.
+// Without room for the whole list (records near READ_HALO, or c so small that a pass has thousands of hits) finish_survivors finds
+// owner and k-mer by a search over the lanes' start offsets and a walk over the owner's masks instead — what it always did before
+// round 3: ~150 instructions per wavefront and pass more.  Returns whether the list was written (uniform over the workgroup).
+template <int TPB>
+__device__ __forceinline__ bool list_survivors(const ReadsLds<TPB> s, uint32_t nh, uint32_t cnt, uint32_t first, uint32_t total, uint32_t rows) {
+    const uint32_t tid = threadIdx.x;
+    SY_LDS uint32_t* const s_owner = &s.mask[0][0] + rows * TPB;
+    const bool is_listed = listed(total, rows, TPB);
+    if (is_listed && cnt) {
+        uint32_t p = first;
+        for (uint32_t w = 0; w < mask_words(nh); w++) {
+            uint32_t m = s.mask[w][tid];
+            while (m) {
+                const uint32_t bpos = (uint32_t)__clz((int)m);
+                s_owner[p++] = tid | ((w * 32 + bpos) << OWNER_LANE_BITS);
+                m &= ~(0x80000000u >> bpos);
+            }
+        }
+    }
+    return is_listed;
+}
+
+// 9. The pass's hits, one per lane — owner and k-mer index from the list, or by a search over the TPB start offsets and the owner's
+// hit masks — re-hashed from the LDS stream and written as finished 32 B records, consecutive lanes to consecutive slots.
+// HV == 2: the loop's test yields a superset; a candidate that fails the exact test is struck from its record's mask and *s.redo set —
+// the caller redoes the pass's bookkeeping from count_hits on.
+template <int K, int HV, int TPB>
+__device__ __forceinline__ void finish_survivors(const ReadsLds<TPB> s, bool is_listed, uint32_t rows, uint32_t total, uint32_t base_prev,
+                                                 uint32_t slot_cap, uint64_t thr, uint64_t rec_base, uint64_t pass, int paired, int avx2_compat,
+                                                 uint64_t out0, OccRec* slot_rec, uint32_t* slot_key, int key_sh) {
+    const SY_LDS uint32_t* const s_owner = &s.mask[0][0] + rows * TPB;
+    for (uint32_t hix = threadIdx.x; hix < total; hix += TPB) {
+        uint32_t lo, i = 0, f;
+        if (is_listed) {
+            const uint32_t ow = s_owner[hix];
+            lo = ow & ((1u << OWNER_LANE_BITS) - 1u);
+            i = ow >> OWNER_LANE_BITS;
+            f = s.first[lo];
+        } else {
+            lo = 0;
+            uint32_t hi = TPB;                                          // owner: the last lane whose first hit is <= hix
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if ((s.first[mid] & 0x7FFFFFFFu) <= hix) lo = mid; else hi = mid;
+            }
+            // (lanes without hits share the start offset of the next lane with hits: the LAST lane with that offset that
+            //  actually owns hix is the one whose successor starts beyond it — the search above returns exactly that lane)
+            f = s.first[lo];
+            uint32_t j = hix - (f & 0x7FFFFFFFu);                       // the j-th hit of lane `lo`
+            for (uint32_t w = 0; w < MASKW; w++) {
+                uint32_t m = s.mask[w][lo];
+                const uint32_t c = (uint32_t)__popc(m);
+                if (j >= c) { j -= c; continue; }
+                for (; j; j--) m &= ~(0x80000000u >> __clz((int)m));   // drop the j highest set bits
+                i = w * 32 + (uint32_t)__clz((int)m);
+                break;
+            }
+        }
+        const uint32_t o = base_prev + hix;
+        if (o < slot_cap) {
+            const uint64_t ft = win64(s.sF, s.rel[lo] + i);
+            const uint64_t fk = ft >> (64 - 2 * K), rk = revcomp_top<K>(ft);
+            const uint64_t h = mm_hash64_gfx950(fk < rk ? fk : rk);      // (round 6, VERDICT r05 #4d: the spelling the loop uses — v_lshl_add_u64, v_bitop3)
+            if constexpr (HV == 2) {
+                if (h >= thr) {                                          // not a hit after all: out of its record's mask
+                    atomicAnd((uint32_t*)&s.mask[kmer_word(i)][lo], ~(1u << kmer_bit(i)));
+                    *s.redo = 1u;
+                    continue;
+                }
+            }
+            uint64_t rid = rec_base + pass + lo;
+            if (f >> 31) {
+                rid |= RID_MARKER_BIT;
+                if (paired) rid |= min(emission_rank(i, s.nh[lo], avx2_compat), RID_RANK_MAX) << RID_RANK_SHIFT;   // (sketch_session.h)
+            }
+            slot_rec[out0 + o] = OccRec{h, rid, s.m0[lo], s.m1[lo]};
+            if (slot_key) slot_key[out0 + o] = (uint32_t)(h >> key_sh);   // what finish() partitions by (replay_lds.hip)
+        }
+    }
+}
+
+#undef SY_LDS
+
+}  // namespace
+}  // namespace sylph

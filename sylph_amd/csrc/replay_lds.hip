@@ -300,7 +300,7 @@ struct FinishPass {
         hipLaunchKernelGGL(table_compact_kernel, dim3(std::min<uint32_t>((B + 3) / 4, 1u << 15)), dim3(256), 0, ctx->stream,
                            ra.tmp_k, ra.tmp_c, w.boff, w.d_off, w.chunk_rows, w.chunk_removed, w.n_distinct, B, ipt,
                            sk->out_k.as<uint64_t>(), sk->out_c.as<uint32_t>(), w.ovf_list, w.mid_list, w.large_list, skip_if_listed,
-                           d_tail, deferred ? sk->slot_meta.as<uint32_t>() + (size_t)(sk->pend.n_blk + 1) * 4 : (const uint32_t*)nullptr,
+                           d_tail, deferred ? slot_meta_of(sk, sk->pend.n_blk).state_words : (const uint32_t*)nullptr,
                            sk->a10_state == 1 ? sk->a10_tail.as<uint32_t>() : (const uint32_t*)nullptr, ra.p_nv);
         SY_HIP(hipGetLastError());
     }
@@ -424,7 +424,7 @@ bool finish_bucketed(sylph_sketch* sk) {
         in.slot_key = sk->slot_key.as<uint32_t>();
         in.n_blk = sk->pend.n_blk;
         in.slot_cap = sk->pend.slot_cap;
-        in.blk_count = sk->slot_meta.as<uint32_t>() + (sk->pend.n_blk + 1);   // (layout: reads.hip SlotMeta)
+        in.blk_count = slot_meta_of(sk, sk->pend.n_blk).blk_count;
         in.blk_per_tile = tile_blocks;
         in.stage_pairs = stage_pairs;
         n_tiles = (in.n_blk + tile_blocks - 1) / tile_blocks;

@@ -16,19 +16,13 @@
 // Pure integer work, no MFMA.  Algorithmic HBM traffic: 1 B per base in, 12 B per survivor out.
 #include "common.h"
 #include "device_common.h"
+#include "seed_plan.h"        // TPB, WPT, TILE_*, HALO_WORDS, STAGE_CAP, FLUSH_AT, LIST_CAP and what they promise each other
 
 namespace sylph {
 
 namespace {
 
-constexpr int TPB = 256;
-constexpr int WPT = 4;                        // packed dwords (16 bases each) per lane
-constexpr int TILE_WORDS = TPB * WPT;         // 1024
-constexpr int TILE_BASES = TILE_WORDS * 16;   // 16384
-constexpr int HALO_WORDS = 2;                 // k-1 <= 31 bases beyond the tile
-constexpr int STAGE_CAP = 1024;               // LDS survivor staging (12 KiB)
-constexpr int FLUSH_AT = 512;
-constexpr int LIST_CAP = 2048;                // survivors of a tile finished cooperatively (ordered-slots kernel); 16384 / c expected
+using namespace seed_plan;
 
 template <int S>
 __device__ __forceinline__ uint64_t shr96(uint32_t hi, uint32_t mid, uint32_t lo) {
@@ -57,6 +51,8 @@ __device__ __forceinline__ uint64_t hash_at(uint32_t f0, uint32_t f1, uint32_t f
     constexpr int SF = 96 - 2 * O - 2 * K;                 // forward: top-justified big-endian stream
     const uint64_t f = shr96<SF>(f0, f1, f2) & KmerConsts<K>::MASK;
     const uint64_t r = shr96<2 * O>(r2, r1, r0) & KmerConsts<K>::MASK;   // reverse complement: little-endian stream
+    // (f < r ? f : r, not min_u62: measured with the read kernel's v_min_f64, the one instruction there costs seeds_slots_kernel<31, 1>
+    //  a wavefront per SIMD here — the compare and selects schedule into the funnel shifts)
     const uint64_t canon = f < r ? f : r;                  // seeding.rs:134-139
     return HV ? mm_hash64_gfx950(canon) : mm_hash64(canon);
 }
@@ -107,6 +103,45 @@ __device__ __forceinline__ void emit_hits(uint32_t mask, uint32_t f0, uint32_t f
     }
 }
 
+// The front of both position kernels for the tile at tile_base: load + pack into the LDS streams sF / sR (16 B per lane, coalesced;
+// chunks that start at or beyond n_bases are never read), the lane's 6 + 6 words, and per_dword(j, mask) for the hit mask of each of its
+// WPT dwords as soon as it is known (k-mer O of dword j <-> bit 15 - O).  Positions at or beyond n_bases can never be valid: whole
+// dwords of them are skipped, per_dword is not called for them (wave-uniform except in the single boundary wave).
+template <int K, int HV, class F>
+__device__ __forceinline__ void tile_front(const uint8_t* bases, uint32_t n_bases, uint64_t tile_base, uint64_t thr, uint32_t* sF,
+                                           uint32_t* sR, uint32_t (&fw)[6], uint32_t (&rw)[6], F&& per_dword) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll
+    for (int j = 0; j <= WPT; j++) {
+        const uint32_t ci = tid + j * TPB;
+        if (j == WPT && tid >= HALO_WORDS) break;
+        const uint64_t b0 = tile_base + (uint64_t)ci * 16;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (b0 < n_bases) v = *reinterpret_cast<const uint4*>(bases + b0);
+        uint32_t F_, R_;
+        pack16(v, F_, R_);
+        sF[ci] = F_;
+        sR[ci] = R_;
+    }
+    __syncthreads();
+    const uint32_t w0 = tid * WPT;
+    const uint4 fa = *reinterpret_cast<const uint4*>(&sF[w0]);
+    const uint2 fb = *reinterpret_cast<const uint2*>(&sF[w0 + 4]);
+    const uint4 ra = *reinterpret_cast<const uint4*>(&sR[w0]);
+    const uint2 rb = *reinterpret_cast<const uint2*>(&sR[w0 + 4]);
+    fw[0] = fa.x; fw[1] = fa.y; fw[2] = fa.z; fw[3] = fa.w; fw[4] = fb.x; fw[5] = fb.y;
+    rw[0] = ra.x; rw[1] = ra.y; rw[2] = ra.z; rw[3] = ra.w; rw[4] = rb.x; rw[5] = rb.y;
+    const uint32_t p0 = (uint32_t)tile_base + w0 * 16;
+#pragma unroll
+    for (int j = 0; j < WPT; j++) {
+        if ((uint64_t)p0 + (uint64_t)j * 16 < n_bases) {
+            uint32_t mask = 0;
+            Unroll16<K, 0, HV>::run(fw[j], fw[j + 1], fw[j + 2], rw[j], rw[j + 1], rw[j + 2], thr, mask);
+            per_dword(j, mask);
+        }
+    }
+}
+
 // K1.  n_bases < 2^32.  `bases` 16-byte aligned; chunks that start at or beyond n_bases are never read.
 template <int K, int HV>
 __global__ __launch_bounds__(TPB) void seeds_kernel(const uint8_t* __restrict__ bases, uint32_t n_bases, uint64_t thr,
@@ -122,43 +157,13 @@ __global__ __launch_bounds__(TPB) void seeds_kernel(const uint8_t* __restrict__ 
 
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t tile_base = (uint64_t)tile * TILE_BASES;
-        // ---- load + pack ------------------------------------------------------------------------------
-#pragma unroll
-        for (int j = 0; j <= WPT; j++) {
-            const uint32_t ci = tid + j * TPB;
-            if (j == WPT && tid >= HALO_WORDS) break;
-            const uint64_t b0 = tile_base + (uint64_t)ci * 16;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (b0 < n_bases) v = *reinterpret_cast<const uint4*>(bases + b0);
-            uint32_t F, R;
-            pack16(v, F, R);
-            sF[ci] = F;
-            sR[ci] = R;
-        }
-        __syncthreads();
-        // ---- hash ---------------------------------------------------------------------------------------
-        {
-            const uint32_t w0 = tid * WPT;
-            const uint4 fa = *reinterpret_cast<const uint4*>(&sF[w0]);
-            const uint2 fb = *reinterpret_cast<const uint2*>(&sF[w0 + 4]);
-            const uint4 ra = *reinterpret_cast<const uint4*>(&sR[w0]);
-            const uint2 rb = *reinterpret_cast<const uint2*>(&sR[w0 + 4]);
-            const uint32_t fw[6] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y};
-            const uint32_t rw[6] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y};
-            const uint32_t p0 = (uint32_t)tile_base + w0 * 16;
-#pragma unroll
-            for (int j = 0; j < WPT; j++) {
-                // positions at or beyond n_bases can never be valid; skip whole dwords of them (wave-uniform
-                // except in the single boundary wave)
-                if ((uint64_t)p0 + (uint64_t)j * 16 < n_bases) {
-                    uint32_t mask = 0;
-                    Unroll16<K, 0, HV>::run(fw[j], fw[j + 1], fw[j + 2], rw[j], rw[j + 1], rw[j + 2], thr, mask);
-                    if (mask)
-                        emit_hits<K>(mask, fw[j], fw[j + 1], fw[j + 2], rw[j], rw[j + 1], rw[j + 2], p0 + j * 16, st, &s_cnt,
-                                     out_hash, out_pos, out_cap, out_count);
-                }
-            }
-        }
+        uint32_t fw[6], rw[6];
+        const uint32_t p0 = (uint32_t)tile_base + tid * WPT * 16;
+        tile_front<K, HV>(bases, n_bases, tile_base, thr, sF, sR, fw, rw, [&](int j, uint32_t mask) {
+            if (mask)
+                emit_hits<K>(mask, fw[j], fw[j + 1], fw[j + 2], rw[j], rw[j + 1], rw[j + 2], p0 + j * 16, st, &s_cnt, out_hash, out_pos, out_cap,
+                             out_count);
+        });
         __syncthreads();
         // ---- flush staged survivors ----------------------------------------------------------------------
         const bool last = (tile + gridDim.x >= n_tiles);
@@ -195,59 +200,17 @@ __global__ __launch_bounds__(TPB) void seeds_slots_kernel(const uint8_t* __restr
     __shared__ __attribute__((aligned(16))) uint32_t sR[TILE_WORDS + 8];
     __shared__ uint32_t s_wave[TPB / 64];
     __shared__ uint16_t s_list[LIST_CAP];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     // first pass: it = tile; redo pass (tile_list != nullptr): it = index into the list of tiles that overflowed their slots,
     // which now get a slot region of TILE_BASES entries each (n_tiles = length of the list)
     for (uint32_t it = blockIdx.x; it < n_tiles; it += gridDim.x) {
         const uint32_t tile = tile_list ? tile_list[it] : it;
         const uint64_t tile_base = (uint64_t)tile * TILE_BASES;
-#pragma unroll
-        for (int j = 0; j <= WPT; j++) {
-            const uint32_t ci = tid + j * TPB;
-            if (j == WPT && tid >= HALO_WORDS) break;
-            const uint64_t b0 = tile_base + (uint64_t)ci * 16;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (b0 < n_bases) v = *reinterpret_cast<const uint4*>(bases + b0);
-            uint32_t F, R;
-            pack16(v, F, R);
-            sF[ci] = F;
-            sR[ci] = R;
-        }
-        __syncthreads();
-        const uint32_t w0 = tid * WPT;
-        const uint4 fa = *reinterpret_cast<const uint4*>(&sF[w0]);
-        const uint2 fb = *reinterpret_cast<const uint2*>(&sF[w0 + 4]);
-        const uint4 ra = *reinterpret_cast<const uint4*>(&sR[w0]);
-        const uint2 rb = *reinterpret_cast<const uint2*>(&sR[w0 + 4]);
-        const uint32_t fw[6] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y};
-        const uint32_t rw[6] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y};
-        const uint32_t p0 = (uint32_t)tile_base + w0 * 16;
-        uint32_t masks[WPT];
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int j = 0; j < WPT; j++) {
-            masks[j] = 0;
-            if ((uint64_t)p0 + (uint64_t)j * 16 < n_bases)
-                Unroll16<K, 0, HV>::run(fw[j], fw[j + 1], fw[j + 2], rw[j], rw[j + 1], rw[j + 2], thr, masks[j]);
-            cnt += __popc(masks[j]);
-        }
-        // workgroup exclusive scan of cnt
-        uint32_t x = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63) s_wave[wave] = x;
-        __syncthreads();   // also: every lane has finished reading sF/sR of this tile
-        uint32_t base = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; w++) {
-            const uint32_t t = s_wave[w];
-            if ((uint32_t)w < wave) base += t;
-            total += t;
-        }
-        uint32_t o = base + x - cnt;
+        uint32_t fw[6], rw[6], masks[WPT] = {}, cnt = 0;
+        tile_front<K, HV>(bases, n_bases, tile_base, thr, sF, sR, fw, rw, [&](int j, uint32_t mask) { masks[j] = mask; cnt += __popc(mask); });
+        const uint32_t w0 = tid * WPT, p0 = (uint32_t)tile_base + w0 * 16;
+        uint32_t total;
+        uint32_t o = block_excl_sum<TPB>(cnt, s_wave, &total);   // (its barriers: every lane has finished reading its words of this tile)
         const uint64_t out0 = (uint64_t)it * slot_cap;
         if (total <= (uint32_t)LIST_CAP) {
             // The tile's survivors are finished COOPERATIVELY (round 3, as in the read-per-lane kernel): the lanes that own them
@@ -289,18 +252,8 @@ __global__ __launch_bounds__(TPB) void seeds_slots_kernel(const uint8_t* __restr
                 }
             }
         }
-        if (tid == 0) {
-            if (tile_list) {
-                spill_slot_of_tile[tile] = it;
-            } else {
-                tile_count[tile] = total;          // the true count: a tile above slot_cap is redone into a spill region
-                if (total > slot_cap) {
-                    const uint32_t s = atomicAdd(&spill->n_tiles, 1u);
-                    if (s < SPILL_MAX_TILES) spill->tiles[s] = tile;
-                }
-            }
-        }
-        __syncthreads();   // s_wave is rewritten by the next tile
+        if (tid == 0) close_slots(tile_list != nullptr, tile, it, total, slot_cap, tile_count, spill, spill_slot_of_tile);
+        __syncthreads();   // sF / sR are rewritten by the next tile
     }
 }
 
@@ -336,26 +289,20 @@ void launch_seeds(sylph_ctx* ctx, const uint8_t* d_bases, uint32_t n_bases, uint
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 8);   // looping workgroups: the staging area is flushed with one global atomic per flush
-    static const int hv = getenv("SYLPH_HIP_HASH_VARIANT") ? atoi(getenv("SYLPH_HIP_HASH_VARIANT")) : 1;   // tuning knob
     ctx->seed_gate();
     ScopedKernelTimer t(ctx, "seeds");
-#define SY_LAUNCH_SEEDS(KK, HH)                                                                                         \
-    hipLaunchKernelGGL((seeds_kernel<KK, HH>), dim3(grid), dim3(TPB), 0, ctx->stream, d_bases, n_bases, thr, n_tiles, \
-                       d_out_hash, d_out_pos, out_cap, d_count)
-    if (k == 31) { if (hv) SY_LAUNCH_SEEDS(31, 1); else SY_LAUNCH_SEEDS(31, 0); }
-    else if (k == 21) { if (hv) SY_LAUNCH_SEEDS(21, 1); else SY_LAUNCH_SEEDS(21, 0); }
-    else throw ArgError{"k must be 21 or 31 (avx2_seeding.rs:46-52)"};
-#undef SY_LAUNCH_SEEDS
+    const bool known = with_k_hv<0, 1>(k, hash_variant_env(1), [&](auto kc, auto hc) {
+        hipLaunchKernelGGL((seeds_kernel<decltype(kc)::value, decltype(hc)::value>), dim3(grid), dim3(TPB), 0, ctx->stream, d_bases, n_bases, thr, n_tiles,
+                           d_out_hash, d_out_pos, out_cap, d_count);
+    });
+    if (!known) throw ArgError{"k must be 21 or 31 (avx2_seeding.rs:46-52)"};
     SY_HIP(hipGetLastError());
     ctx->seed_done();
 }
 
 
 // Ordered K1: fills scratch slots + tile counts; the caller scans tile_count and calls launch_compact_slots.
-uint32_t seeds_slot_capacity(uint32_t c) {
-    const uint64_t expect = (uint64_t)TILE_BASES / c;
-    return (uint32_t)std::min<uint64_t>(TILE_BASES, expect + expect * 3 / 4 + 48);
-}
+uint32_t seeds_slot_capacity(uint32_t c) { return slot_capacity(TILE_BASES, (uint64_t)TILE_BASES / c); }
 uint32_t seeds_n_tiles(uint64_t n_bases) { return (uint32_t)((n_bases + TILE_BASES - 1) / TILE_BASES); }
 
 // tile_list == nullptr: first pass over all tiles of the batch.  Otherwise: redo pass over `n_list` overflowed tiles with
@@ -369,16 +316,13 @@ void launch_seeds_slots(sylph_ctx* ctx, const uint8_t* d_bases, uint32_t n_bases
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
     const uint32_t grid = ctx->reads_wg_per_cu ? (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * ctx->reads_wg_per_cu) : n_tiles;
-    static const int hv = getenv("SYLPH_HIP_HASH_VARIANT") ? atoi(getenv("SYLPH_HIP_HASH_VARIANT")) : 1;   // tuning knob
     ctx->seed_gate();
     ScopedKernelTimer t(ctx, "seeds");
-#define SY_LAUNCH_SLOTS(KK, HH)                                                                                              \
-    hipLaunchKernelGGL((seeds_slots_kernel<KK, HH>), dim3(grid), dim3(TPB), 0, ctx->stream, d_bases, n_bases, thr, n_tiles, \
-                       slot_cap, d_slot_hash, d_slot_pos, d_tile_count, d_spill, d_tile_list, d_spill_slot_of_tile)
-    if (k == 31) { if (hv) SY_LAUNCH_SLOTS(31, 1); else SY_LAUNCH_SLOTS(31, 0); }
-    else if (k == 21) { if (hv) SY_LAUNCH_SLOTS(21, 1); else SY_LAUNCH_SLOTS(21, 0); }
-    else throw ArgError{"k must be 21 or 31 (avx2_seeding.rs:46-52)"};
-#undef SY_LAUNCH_SLOTS
+    const bool known = with_k_hv<0, 1>(k, hash_variant_env(1), [&](auto kc, auto hc) {
+        hipLaunchKernelGGL((seeds_slots_kernel<decltype(kc)::value, decltype(hc)::value>), dim3(grid), dim3(TPB), 0, ctx->stream, d_bases, n_bases, thr,
+                           n_tiles, slot_cap, d_slot_hash, d_slot_pos, d_tile_count, d_spill, d_tile_list, d_spill_slot_of_tile);
+    });
+    if (!known) throw ArgError{"k must be 21 or 31 (avx2_seeding.rs:46-52)"};
     SY_HIP(hipGetLastError());
     if (!d_tile_list) ctx->seed_done();
 }

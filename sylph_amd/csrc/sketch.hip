@@ -537,6 +537,7 @@ static void process_batch(sylph_sketch* sk, const uint8_t* d_bases, uint32_t pha
     }
     if (!plain) materialise_plain_records(sk);
     if (short_batch) done = push_short_reads(sk, d_bases, phase, d_off, n_records, n_bases, enc);
+    if (ctx->profile) ctx->stats[done ? "short_reads" : "position_road"].launches++;     // (tests ask sylph_ctx_kernel_stats which kernel took the batch)
     if (!done && enc == SYLPH_ENC_2BIT) {   // the position kernel and the marker loads of annotate read ASCII
         sk->batch_ascii.reserve(n_bases + 64);
         if (n_bases)

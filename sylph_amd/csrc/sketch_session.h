@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "replay_plan.h"
+#include "seed_plan.h"
 
 namespace sylph {
 // rid: bit 63 = the record (pair) has dedup markers; bit 62 = approximate dedup only (a10.hip): the filter reported one of the
@@ -98,3 +99,7 @@ struct sylph_sketch {
           slot_rec(cx), slot_key(cx), slot_meta(cx), batch_ascii(cx), fq_bases(cx), fq_off(cx), out_k(cx), out_c(cx), counters(cx), a10_tail(cx) {}
 };
 
+namespace sylph {
+// the block tables the short-read kernel left in the session's slot_meta buffer (seed_plan.h SlotMeta)
+inline seed_plan::SlotMeta slot_meta_of(sylph_sketch* sk, uint32_t n_blk) { return seed_plan::SlotMeta(sk->slot_meta.as<uint32_t>(), n_blk); }
+}  // namespace sylph

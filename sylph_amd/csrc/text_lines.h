@@ -4,7 +4,6 @@
 #pragma once
 #include "common.h"
 #include "device_common.h"
-#include "partition.h"
 
 namespace sylph {
 namespace {

@@ -10,7 +10,6 @@
 #   a10                        filter-dedup tests + the default-flag bench leg, one / two / four workgroups per range
 #   a10-profile [--no-pmc]     rocprofv3 kernel trace (+ FETCH_SIZE / WRITE_SIZE) of the filter pass's kernels, one sample at a time
 #   ab-env cfg...              alternate environment configurations on the pipelined default-flag rate (AB_ROUNDS, AB_SECONDS, AB_FPR)
-#   ab-reads                   tools/r06_ab_reads.sh (build the variants first, here: tools/r06_build_reads_variants.sh)
 #   inflate-profile            tools/r06_inflate_profile.sh (rocprofv3 kernel trace + counters of the inflate kernels)
 #   round-profile              tools/r05_profile.sh (the whole-pipeline rocprofv3 recipe of round 5, unchanged)
 set -u
@@ -87,7 +86,6 @@ for l in open(sys.argv[1]):
 for k, x in v.items(): print(f"{k:60s} n {len(x)} median {statistics.median(x):8.1f} min {min(x):8.1f} max {max(x):8.1f} Gbp/s")
 PY
     ;;
-  ab-reads) bash tools/r06_ab_reads.sh ;;
   inflate-profile) bash tools/r06_inflate_profile.sh ;;
   round-profile) bash tools/r05_profile.sh ;;
   *) echo "unknown: $what"; exit 2 ;;
