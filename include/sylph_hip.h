@@ -120,6 +120,9 @@ void sylph_upload_destroy(sylph_upload *u);
  * "stream_priority" = "high" | "normal" | "low": the context's OWN stream is recreated at that priority (an error on a context that
  * runs on the caller's stream: create that stream at the priority wanted); no measurable effect on a pipeline's rate or its
  * completion intervals (profiles/r06_ab_stream_priority.txt).
+ * "bootstrap_shape" = "gather" (default) | "table": how sylph_bootstrap_counts gets from a drawn index to its value — a load of the
+ * coverage value, or a run of compares against a per-item table of boundaries (same counts; profiles/bootstrap_device.txt).
+ * "bootstrap_bins" = "2".."64" (default 64; tests lower it): an item with a kept value of this or more declines.
  * "fail_next_shard_probe" = "1": fault injection for the tests — the next sylph_db_contain_batch_sharded on this context fails
  * in its probe, between the collectives (every rank of the batch must then return the same error, nobody may hang). */
 int sylph_ctx_set_option(sylph_ctx *ctx, const char *key, const char *value);
@@ -382,6 +385,33 @@ int sylph_db_reassign_view(sylph_db *db, const uint64_t *sample_kmers, const uin
                            uint64_t *out_n_covs, const uint32_t **kmers_lost);
 void sylph_db_destroy(sylph_db *db);
 uint64_t sylph_db_index_bytes(const sylph_db *db);   /* HBM taken by the postings index (lines + overflow runs) */
+
+/* ---- bootstrap confidence intervals: the resampling on the device (csrc/bootstrap.hip) --------------------------------------------
+ * bootstrap_interval (contain.rs:849-898) resamples a genome's `full_covs` — n_total - keep zeros followed by the first `keep` of its
+ * ascending coverage values (:679-684) — `iters` (the reference: 100) times with replacement, from a fastrand stream it reseeds per
+ * genome (`seed`, the reference: 7), and runs ratio_lambda (inference.rs:207-242) and ani_from_lambda (contain.rs:817-847) on every
+ * resample.  This call makes the draws and the counting for n_items genomes in one launch and returns, per resample, the five
+ * counts those two functions read: out[i * iters + r] for item i, resample r.  Lambda, ANI, the sort and the percentiles stay with the
+ * caller (f64; host/inference.cpp finish_ci), so the intervals are bit for bit what the host's loop gives.
+ * covs / cov_off are what sylph_db_contain_view[_packed], a sylph_pipeline_result and sylph_db_reassign_view hand out: values of
+ * cov_width = 1, 2 or 4 bytes in `mem` (host or device); item i uses covs[cov_off[i] .. cov_off[i] + keep[i]) (its row may be longer:
+ * cov_off has n_items + 1 entries).  cov_off, keep, n_total, out (n_items * iters entries) and declined (n_items) are host arrays,
+ * borrowed for the call; the library keeps no state between calls; calls on one context are serialised like every other.
+ * An item DECLINES as a whole — declined[i] = 1, its summaries unspecified, never an error — when fastrand would have rejected one of
+ * its draws (Lemire's rejection step, about n_total in 2^64 per draw: it shifts every later draw) or when one of its kept values is
+ * 64 or more (the bins of the device's histogram; a genome that gets a lambda has a median coverage of at most 2): the caller runs
+ * its own loop for that item.  SYLPH_ERR_INVALID for keep[i] > n_total[i], keep[i] > cov_off[i + 1] - cov_off[i], n_total[i] == 0,
+ * a width other than 1, 2, 4 or iters == 0; n_items == 0 is SYLPH_OK. */
+typedef struct sylph_bootstrap_summary {
+    uint32_t n_nonzero;    /* drawn values != 0 */
+    uint32_t n_distinct;   /* distinct non-zero values drawn, saturating at 2 */
+    uint32_t mode;         /* the non-zero value drawn most often; ties go to the larger value (inference.rs:228-230) */
+    uint32_t mode_count;
+    uint32_t next_count;   /* how often mode + 1 was drawn; 0 if never */
+} sylph_bootstrap_summary;
+int sylph_bootstrap_counts(sylph_ctx *ctx, const void *covs, uint32_t cov_width, const uint64_t *cov_off, const uint32_t *keep,
+                           const uint32_t *n_total, uint32_t n_items, int mem, uint64_t seed, uint32_t iters,
+                           sylph_bootstrap_summary *out, uint8_t *declined);
 
 /* ---- batched containment: S samples per call --------------------------------------------------------------------- */
 

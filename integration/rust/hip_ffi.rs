@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
+#[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
 #[repr(C)] pub struct SylphCommOps {   // caller-supplied collectives on device buffers (stream = hipStream_t); 0 = success
     pub all_gather: extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: u64, stream: *mut c_void) -> c_int,
     pub all_to_all: extern "C" fn(user: *mut c_void, send: *const c_void, send_off: *const u64, recv: *mut c_void,
@@ -151,6 +152,11 @@ extern "C" {
     pub fn sylph_bunzip2(ctx: *mut SylphCtx, bz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;
     pub fn sylph_bunzip2_files(ctx: *mut SylphCtx, bz: *const *const c_void, n_bytes: *const u64, n_files: u32, mem: c_int,
                                out: *mut *mut SylphInflated) -> c_int;   // the two mates of a pair in one pass
+    // the resampling of bootstrap_interval (contain.rs:849-898) for n_items genomes in one launch: per resample the five counts
+    // ratio_lambda / ani_from_lambda read; lambda, ANI and the percentiles stay here.  declined[i] != 0: run the crate's own loop for item i
+    pub fn sylph_bootstrap_counts(ctx: *mut SylphCtx, covs: *const c_void, cov_width: u32, cov_off: *const u64, keep: *const u32,
+                                  n_total: *const u32, n_items: u32, mem: c_int, seed: u64, iters: u32,
+                                  out: *mut SylphBootstrapSummary, declined: *mut u8) -> c_int;
     // k-mer-range shards: bounds for `world` GPUs, upload of this rank's range, communicator, the collective batch call
     pub fn sylph_shard_bounds(max_kmer: u64, world: u32, bounds: *mut u64) -> c_int;
     pub fn sylph_db_upload_shard(ctx: *mut SylphCtx, kmers: *const u64, genome_off: *const u64, n_genomes: u64, mem: c_int,

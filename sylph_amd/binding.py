@@ -42,7 +42,7 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
            "sylph_sketch_genomes_fasta",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
-           "sylph_bunzip2", "sylph_bunzip2_files"]
+           "sylph_bunzip2", "sylph_bunzip2_files", "sylph_bootstrap_counts"]
 
 
 def load():
@@ -149,6 +149,7 @@ def load():
     L.sylph_device_count.restype = i32
     L.sylph_genome_shard_bounds.argtypes = [vp, u64, u32, vp]
     L.sylph_db_upload_genome_shard.argtypes = [vp, vp, vp, u64, i32, vp, u32, u32, P(vp)]
+    L.sylph_bootstrap_counts.argtypes = [vp, vp, u32, vp, vp, vp, u32, i32, u64, u32, vp, vp]
     _LIB = L
     return L
 
@@ -269,6 +270,25 @@ class Context:
         _check(load().sylph_sketch_genomes_fasta(self._h, hs, len(files), int(bool(individual)), c, k, seed_mode, min_spacing, int(pseudotax),
                                                  C.byref(ok), _ptr(koff), C.byref(ot), _ptr(toff)))
         return _take(ok, int(koff[-1]), np.uint64), koff, _take(ot, int(toff[-1]), np.uint64), toff
+
+
+BOOTSTRAP_SUMMARY = np.dtype([("n_nonzero", np.uint32), ("n_distinct", np.uint32), ("mode", np.uint32), ("mode_count", np.uint32),
+                              ("next_count", np.uint32)])
+
+
+def bootstrap_counts(ctx, covs, cov_off, keep, n_total, seed=7, iters=100, cov_width=None):
+    """sylph_bootstrap_counts: -> (summaries[n_items, iters] of BOOTSTRAP_SUMMARY, declined[n_items]).  covs: a uint8 / uint16 / uint32 array
+    (MEM_HOST), or the integer address of device memory with cov_width given (MEM_DEVICE)."""
+    off, kp, nt = _np(cov_off, np.uint64), _np(keep, np.uint32), _np(n_total, np.uint32)
+    n = len(kp)
+    out, declined = np.zeros((n, int(iters)), dtype=BOOTSTRAP_SUMMARY), np.zeros(n, dtype=np.uint8)
+    if cov_width is None:
+        a = np.ascontiguousarray(covs)
+        ptr, width, mem = (_ptr(a) if len(a) else None), a.dtype.itemsize, MEM_HOST
+    else:
+        ptr, width, mem = C.c_void_p(int(covs)), int(cov_width), MEM_DEVICE
+    _check(load().sylph_bootstrap_counts(ctx._h, ptr, width, _ptr(off), _ptr(kp), _ptr(nt), n, mem, int(seed), int(iters), _ptr(out), _ptr(declined)))
+    return out, declined
 
 
 def pack_2bit(ascii_bases):

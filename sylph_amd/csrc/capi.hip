@@ -434,6 +434,14 @@ int sylph_ctx_set_option(sylph_ctx* ctx, const char* key, const char* value) {
             if (!strcmp(value, "alltoall")) ctx->shard_reduce = 0;
             else if (!strcmp(value, "allgather")) ctx->shard_reduce = 1;
             else SY_REQUIRE(false, "shard_reduce must be alltoall|allgather");
+        } else if (!strcmp(key, "bootstrap_shape")) {
+            if (!strcmp(value, "gather")) ctx->bootstrap_shape = 0;
+            else if (!strcmp(value, "table")) ctx->bootstrap_shape = 1;
+            else SY_REQUIRE(false, "bootstrap_shape must be gather|table");
+        } else if (!strcmp(key, "bootstrap_bins")) {
+            const long v = atol(value);
+            SY_REQUIRE(v >= 2 && v <= 64, "bootstrap_bins must be 2..64");
+            ctx->bootstrap_bins = (uint32_t)v;
         } else if (!strcmp(key, "stream_priority")) {
             // The context's own stream is made again at another priority (hipStreamCreateWithPriority): "high" lets the small kernels of a
             // profile context through where the sketch contexts' seeding kernels keep the chip full (pipeline.hip).

@@ -42,6 +42,50 @@ int sylph_host_stats(const uint32_t* covs, uint64_t n, uint64_t n_genome_kmers, 
     return 1;
 }
 
+static void fill_stats(const AniResult& r, SylphHostStats* out) {
+    out->passed = 1;
+    out->naive_ani = r.naive_ani; out->final_est_ani = r.final_est_ani; out->final_est_cov = r.final_est_cov;
+    out->mean_cov = r.mean_cov; out->median_cov = r.median_cov; out->lambda = r.lambda;
+    out->lambda_status = r.lambda_status == AdjustStatus::Low ? 0 : (r.lambda_status == AdjustStatus::High ? 1 : 2);
+    if (r.ani_ci_lo) { out->has_ci = 1; out->ani_ci_lo = *r.ani_ci_lo; out->ani_ci_hi = *r.ani_ci_hi; out->lambda_ci_lo = *r.lambda_ci_lo; out->lambda_ci_hi = *r.lambda_ci_hi; }
+    out->contain_count = r.contain_count; out->n_kmers = r.n_kmers;
+}
+
+// The batch form of sylph_host_stats, the way `profile` / `query` run it: genome i has the coverage values covs[cov_off[i] ..
+// cov_off[i + 1]) (any order) and n_genome_kmers[i] k-mers; the first halves on the host, the resampling of every interval in one
+// device call on ctx (route: 0 the host's loop, 1 the device with the host's loop for what it declines, 2 device only), the second
+// halves on the host.  out[i] as sylph_host_stats fills it; *on_host = intervals whose resampling ran on the host.  -1 on an Error.
+int sylph_host_stats_batch(sylph_ctx* ctx, const uint32_t* covs, const uint64_t* cov_off, const uint64_t* n_genome_kmers, uint64_t n_items,
+                           uint64_t k, double min_count_correct, double minimum_ani_or_neg, int pseudotax, int no_ci, int no_adj,
+                           int mean_coverage, int route, SylphHostStats* out, uint64_t* on_host) {
+    ContainArgs a;
+    a.min_count_correct = min_count_correct;
+    if (minimum_ani_or_neg >= 0) a.minimum_ani = minimum_ani_or_neg;
+    a.pseudotax = pseudotax; a.no_ci = no_ci; a.no_adj = no_adj; a.mean_coverage = mean_coverage;
+    try {
+        std::vector<uint32_t> sorted(covs, covs + cov_off[n_items]);          // the rows where they are, each sorted by its head
+        std::vector<StatsHead> heads(n_items);
+        std::vector<CiItem> ci;
+        for (uint64_t i = 0; i < n_items; i++) {
+            std::vector<uint32_t> cv(covs + cov_off[i], covs + cov_off[i + 1]);
+            heads[i] = stats_head(a, cv, n_genome_kmers[i], k, std::nullopt);
+            std::copy(cv.begin(), cv.end(), sorted.begin() + (long)cov_off[i]);
+            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, cov_off[i], cov_off[i + 1], heads[i].keep, heads[i].n_total});
+        }
+        const uint64_t h = bootstrap_batch(ctx, route == 0 ? BootstrapRoute::Host : route == 1 ? BootstrapRoute::Device : BootstrapRoute::DeviceOnly, a, k,
+                                           sorted.data(), 4, ci, 1);
+        if (on_host) *on_host = h;
+        for (uint64_t i = 0; i < n_items; i++) {
+            memset(&out[i], 0, sizeof(out[i]));
+            if (heads[i].result) fill_stats(*heads[i].result, &out[i]);
+        }
+        return 0;
+    } catch (const Error& e) {
+        fprintf(stderr, "ERROR [sylph_hip] %s\n", e.msg.c_str());
+        return -1;
+    }
+}
+
 // -u: read k-mer identity of a sample table given in the order it is walked (contain.rs:901-951), and the share of the sample's
 // bases that genomes of sizes gn_size[i] at coverages cov[i] explain (contain.rs:392-408)
 double sylph_host_kmer_identity(const uint32_t* counts, uint64_t n, uint64_t k, double mean_read_length) {

@@ -198,6 +198,7 @@ struct ReportTo {   // what every sample's report shares
     const ContainCmdArgs& args;
     const std::vector<GenomeSketch>& genome_sketches;   // the database, in the order of its device-side index
     FILE* out;
+    sylph_ctx* ctx;                                     // the command's own context: the genomes' confidence intervals are resampled on it
 };
 void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const uint32_t* cc, const uint64_t* coff, const void* covs,
             uint32_t cov_width, const uint64_t* tk, const uint32_t* tc, uint64_t tn, int tmem, sylph_db* rdb) {
@@ -213,21 +214,34 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         else for (uint64_t i = lo; i < hi; i++) cv[i - lo] = ((const uint8_t*)base)[i];
         return cv;
     };
+    // The statistics of different genomes are independent (contain.rs:284 runs them on the rayon pool): -t threads, results in the
+    // order of `gs` so that the output does not depend on the interleaving.  Between the two halves of a genome's statistics lies its
+    // confidence interval: the genomes that want one are resampled together (bootstrap_batch: one device call, or the host's loop).
+    const BootstrapRoute ci_route = args.no_ci ? BootstrapRoute::Host : bootstrap_route();
+    auto run_stats = [&](const std::vector<size_t>& gs, const void* base, uint32_t width, const uint64_t* off, const uint32_t* lost) {
+        std::vector<StatsHead> heads(gs.size());
+        parallel_for(gs.size(), args.threads, [&](size_t i) {
+            const size_t g = gs[i];
+            std::vector<uint32_t> cv = cov_vector(base, width, off[g], off[g + 1]);
+            heads[i] = stats_head(args, cv, genome_sketches[g].n_kmers(), S.k, lost ? std::optional<size_t>((size_t)lost[g]) : std::nullopt);
+            if (heads[i].result) heads[i].result->genome_index = g;
+        });
+        std::vector<CiItem> ci;                                      // (gs ascends, and with it the rows of the coverage values)
+        for (size_t i = 0; i < gs.size(); i++)
+            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, off[gs[i]], off[gs[i] + 1], heads[i].keep, heads[i].n_total});
+        bootstrap_batch(to.ctx, ci_route, args, S.k, base, width, ci, args.threads);
+        std::vector<std::optional<AniResult>> res(gs.size());
+        for (size_t i = 0; i < gs.size(); i++) res[i] = std::move(heads[i].result);
+        return res;
+    };
     std::vector<AniResult> stats;
-    {   // the statistics of different genomes are independent (contain.rs:284 runs them on the rayon pool): -t threads,
-        // results gathered in genome order so that the output does not depend on the interleaving
+    {
         std::vector<size_t> with_hits;
         for (size_t g = 0; g < genome_sketches.size(); g++) {
             if (genome_sketches[g].c < S.c) throw Error{1, "c parameter for reads > c parameter for genome"};   // :616-623
             if (cc[g] != 0) with_hits.push_back(g);                  // :654
         }
-        std::vector<std::optional<AniResult>> res(with_hits.size());
-        parallel_for(with_hits.size(), args.threads, [&](size_t i) {
-            const size_t g = with_hits[i];
-            res[i] = stats_from_covs(args, cov_vector(covs, cov_width, coff[g], coff[g + 1]), genome_sketches[g].n_kmers(), S.k, std::nullopt);
-            if (res[i]) res[i]->genome_index = g;
-        });
-        for (auto& r : res) if (r) stats.push_back(*r);
+        for (auto& r : run_stats(with_hits, covs, cov_width, coff, nullptr)) if (r) stats.push_back(*r);
     }
     std::optional<double> kmer_id_opt;                               // contain.rs:274-281
     if (args.seq_id) kmer_id_opt = std::pow(*args.seq_id / 100., (double)S.k);
@@ -246,13 +260,9 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         hip_check(sylph_db_reassign_view(rdb, tk, tc, tn, tmem, pg.data(), pa.data(), (uint32_t)pg.size(), &cc2, &coff2, &covs2, &ncov2, &lost2),
                   "sylph_db_reassign_view");
         std::vector<AniResult> stats2;
-        std::vector<std::optional<AniResult>> res2(stats.size());
-        parallel_for(stats.size(), args.threads, [&](size_t i) {
-            const size_t g = stats[i].genome_index;
-            std::vector<uint32_t> cv(covs2 + coff2[g], covs2 + coff2[g + 1]);
-            res2[i] = stats_from_covs(args, std::move(cv), genome_sketches[g].n_kmers(), S.k, (size_t)lost2[g]);
-            if (res2[i]) res2[i]->genome_index = g;
-        });
+        std::vector<size_t> passing(stats.size());               // (in genome order still: ascending)
+        for (size_t i = 0; i < stats.size(); i++) passing[i] = stats[i].genome_index;
+        const std::vector<std::optional<AniResult>> res2 = run_stats(passing, covs2, 4, coff2, lost2);
         for (size_t i = 0; i < stats.size(); i++) {
             const auto& r = res2[i];
             if (!r) continue;
@@ -560,7 +570,7 @@ int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
     upload_database(e, genome_sketches, args.pseudotax, db);
 
     print_header(args.pseudotax, out, args.estimate_unknown);
-    const ReportTo to{args, genome_sketches, out};
+    const ReportTo to{args, genome_sketches, out, e.context()};
     if (!read_files.empty()) profile_raw_samples(e, args, read_files, db.d, to);
     profile_sketch_files(args, read_sketch_files, db.d, to);
     fflush(out);

@@ -41,75 +41,88 @@ static double gamma_q(double a, double x) {
 }
 double poisson_cdf(double lambda, uint64_t x) { return gamma_q((double)x + 1.0, lambda); }
 
-// inference.rs:207-242
-std::optional<double> ratio_lambda(const std::vector<uint32_t>& full_covs, double min_count_correct) {
-    size_t num_zero = 0;
-    std::map<uint64_t, uint64_t> count_map;
-    for (uint32_t x : full_covs) {
-        if (x == 0) num_zero++;
-        else count_map[x]++;
+// A histogram of coverage values -> what ratio_lambda and ani_from_lambda read off it (csrc/bootstrap_plan.h: the device counts the
+// resamples of the bootstrap into the same five numbers)
+using bootstrap_plan::Summary;
+namespace {
+// hist[v] = how often v occurs; one bin beyond the largest value, so that hist[mode + 1] is there
+Summary summary_of(const std::vector<uint32_t>& hist) { return bootstrap_plan::summary_of_histogram(hist.data(), (uint32_t)hist.size()); }
+Summary summary_of_values(const uint32_t* v, size_t n) {
+    uint32_t top = 0;
+    for (size_t i = 0; i < n; i++) top = std::max(top, v[i]);
+    if (top < (1u << 16)) {
+        std::vector<uint32_t> hist((size_t)top + 2, 0);
+        for (size_t i = 0; i < n; i++) hist[v[i]]++;
+        return summary_of(hist);
     }
-    if (count_map.size() == 1) return std::nullopt;                          // :221
-    if (full_covs.size() - num_zero < SAMPLE_SIZE_CUTOFF) return std::nullopt;   // :225
-    // :228-230: sort (count, value) descending and take the first
-    uint64_t best_count = 0, most_ind = 0;
-    for (const auto& kv : count_map)
-        if (kv.second > best_count || (kv.second == best_count && kv.first > most_ind)) { best_count = kv.second; most_ind = kv.first; }
-    const auto it = count_map.find(most_ind + 1);
-    if (it == count_map.end()) return std::nullopt;                          // :231
-    const double count_p1 = (double)it->second, count = (double)best_count;
+    std::map<uint32_t, uint32_t> count_map;                                  // (values no histogram should be sized for)
+    Summary s{0, 0, 0, 0, 0};
+    for (size_t i = 0; i < n; i++) if (v[i]) count_map[v[i]]++;
+    for (const auto& kv : count_map) {
+        s.n_nonzero += kv.second;
+        if (s.n_distinct < 2) s.n_distinct++;
+        if (kv.second >= s.mode_count) { s.mode = kv.first; s.mode_count = kv.second; }
+    }
+    const auto it = s.mode_count ? count_map.find(s.mode + 1) : count_map.end();
+    s.next_count = it == count_map.end() ? 0 : it->second;
+    return s;
+}
+}  // namespace
+
+// inference.rs:207-242
+std::optional<double> lambda_from_summary(const Summary& s, double min_count_correct) {
+    if (s.n_distinct == 1) return std::nullopt;                              // :221
+    if (s.n_nonzero < SAMPLE_SIZE_CUTOFF) return std::nullopt;               // :225
+    // :228-230: sort (count, value) descending and take the first = the mode, ties to the larger value
+    if (s.next_count == 0) return std::nullopt;                              // :231
+    const double count_p1 = (double)s.next_count, count = (double)s.mode_count;
     if (count_p1 < min_count_correct || count < min_count_correct) return std::nullopt;   // :236
-    return count_p1 / count * (double)(most_ind + 1);                        // :239
+    return count_p1 / count * (double)((uint64_t)s.mode + 1);                // :239
+}
+std::optional<double> ratio_lambda(const std::vector<uint32_t>& full_covs, double min_count_correct) {
+    return lambda_from_summary(summary_of_values(full_covs.data(), full_covs.size()), min_count_correct);
 }
 
 // contain.rs:817-847
-std::optional<double> ani_from_lambda(std::optional<double> lambda, double k, const std::vector<uint32_t>& full_cov) {
+std::optional<double> ani_from_counts(std::optional<double> lambda, double k, size_t contain_count, size_t n_total) {
     if (!lambda) return std::nullopt;
-    size_t contain_count = 0;
-    for (uint32_t x : full_cov) if (x != 0) contain_count++;
-    const double adj_index = (double)contain_count / (1. - std::exp(-*lambda)) / (double)full_cov.size();
+    const double adj_index = (double)contain_count / (1. - std::exp(-*lambda)) / (double)n_total;
     const double ani = std::pow(adj_index, 1. / k);
     if (ani < 0. || std::isnan(ani)) return std::nullopt;
     return ani;
 }
+std::optional<double> ani_from_lambda(std::optional<double> lambda, double k, const std::vector<uint32_t>& full_cov) {
+    if (!lambda) return std::nullopt;
+    size_t contain_count = 0;
+    for (uint32_t x : full_cov) if (x != 0) contain_count++;
+    return ani_from_counts(lambda, k, contain_count, full_cov.size());
+}
 
-// fastrand 2.1.1 (third party): WyRand step + Lemire bounded integers; `fastrand::seed(7)` (contain.rs:854).
+// fastrand 2.1.1 (third party): WyRand step + Lemire bounded integers; `fastrand::seed(7)` (contain.rs:854).  The step and the
+// bounded integer are bootstrap_plan.h's; the loop that draws again after a rejection is the host's alone.
 namespace {
 struct WyRand {
     uint64_t s;
     uint64_t next() {
-        s += 0x2d358dccaa6c78a5ULL;
-        const unsigned __int128 t = (unsigned __int128)s * (unsigned __int128)(s ^ 0x8bb84b93962eacc9ULL);
-        return (uint64_t)t ^ (uint64_t)(t >> 64);
+        s += bootstrap_plan::WY_ADD;
+        return bootstrap_plan::wyrand_output(s);
     }
     uint64_t below(uint64_t n) {   // usize(..n)
-        uint64_t r = next();
-        unsigned __int128 m = (unsigned __int128)r * n;
-        uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-        if (lo < n) {
-            const uint64_t t = (0 - n) % n;
-            while (lo < t) {
-                r = next();
-                m = (unsigned __int128)r * n;
-                hi = (uint64_t)(m >> 64);
-                lo = (uint64_t)m;
-            }
-        }
+        bool rejected;
+        uint64_t hi = bootstrap_plan::bounded(next(), n, &rejected);
+        while (rejected) hi = bootstrap_plan::bounded(next(), n, &rejected);
         return hi;
     }
 };
 }  // namespace
 
-// contain.rs:849-898 (default estimator only)
-static void bootstrap_interval(const std::vector<uint32_t>& covs_full, double k, const ContainArgs& args, AniResult& out) {
-    WyRand rng{7};
-    const size_t num_samp = covs_full.size();
+// contain.rs:849-898 (default estimator only), behind the resampling: lambda and ANI of every resample from its counts, the 5th and
+// 95th percentile of those that have both
+void finish_ci(const Summary* summaries, size_t iters, size_t n_total, double k, const ContainArgs& args, AniResult& out) {
     std::vector<double> res_ani, res_lambda;
-    std::vector<uint32_t> rand_vec(num_samp);
-    for (int it = 0; it < 100; it++) {
-        for (size_t i = 0; i < num_samp; i++) rand_vec[i] = covs_full[rng.below(num_samp)];
-        const auto lambda = ratio_lambda(rand_vec, args.min_count_correct);
-        const auto ani = ani_from_lambda(lambda, k, rand_vec);
+    for (size_t it = 0; it < iters; it++) {
+        const auto lambda = lambda_from_summary(summaries[it], args.min_count_correct);
+        const auto ani = ani_from_counts(lambda, k, summaries[it].n_nonzero, n_total);
         if (ani && lambda && !std::isnan(*ani) && !std::isnan(*lambda)) { res_ani.push_back(*ani); res_lambda.push_back(*lambda); }
     }
     std::sort(res_ani.begin(), res_ani.end());
@@ -122,14 +135,37 @@ static void bootstrap_interval(const std::vector<uint32_t>& covs_full, double k,
     out.lambda_ci_hi = res_lambda[suc * 95 / 100 - 1];
 }
 
-// contain.rs:657-813
-std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<uint32_t> covs, size_t n_genome_kmers, uint64_t k,
-                                         std::optional<size_t> kmers_lost) {
-    if (covs.empty()) return std::nullopt;                                   // :654
+// the resampling on the host: one stream seeded with BOOTSTRAP_SEED, BOOTSTRAP_ITERS resamples of n_total draws each
+void bootstrap_host(const uint32_t* kept, size_t keep, size_t n_total, double k, const ContainArgs& args, AniResult& out) {
+    WyRand rng{BOOTSTRAP_SEED};
+    uint32_t top = 0;
+    for (size_t i = 0; i < keep; i++) top = std::max(top, kept[i]);
+    std::vector<Summary> summaries(BOOTSTRAP_ITERS);
+    if (top < (1u << 16)) {
+        std::vector<uint32_t> hist((size_t)top + 2);
+        for (auto& s : summaries) {
+            std::fill(hist.begin(), hist.end(), 0u);
+            for (size_t i = 0; i < n_total; i++) hist[bootstrap_plan::value_of_draw(rng.below(n_total), n_total, keep, kept)]++;
+            s = summary_of(hist);
+        }
+    } else {
+        std::vector<uint32_t> rand_vec(n_total);
+        for (auto& s : summaries) {
+            for (size_t i = 0; i < n_total; i++) rand_vec[i] = bootstrap_plan::value_of_draw(rng.below(n_total), n_total, keep, kept);
+            s = summary_of_values(rand_vec.data(), n_total);
+        }
+    }
+    finish_ci(summaries.data(), summaries.size(), n_total, k, args, out);
+}
+
+// contain.rs:657-813 up to the decision about the confidence interval
+StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost) {
+    StatsHead h;
+    if (covs.empty()) return h;                                              // :654
     const size_t contain_count = covs.size();
     AniResult r;
     r.naive_ani = std::pow((double)contain_count / (double)n_genome_kmers, 1. / (double)k);   // :657-660
-    std::sort(covs.begin(), covs.end());                                     // :661 (already sorted when they come from the GPU)
+    if (!std::is_sorted(covs.begin(), covs.end())) std::sort(covs.begin(), covs.end());   // :661 (already sorted when they come from the GPU)
     const double median_cov = (double)covs[covs.size() / 2];                 // :663
     double max_cov = 1.7976931348623157e308;                                 // f64::MAX
     if (median_cov < 30.) {                                                  // :666-675
@@ -138,17 +174,19 @@ std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<ui
             else break;
         }
     }
-    std::vector<uint32_t> full_covs(n_genome_kmers - contain_count, 0);      // :679
-    for (uint32_t c : covs) if ((double)c <= max_cov) full_covs.push_back(c);   // :680-684
+    // full_covs (:679-684) = n_genome_kmers - contain_count zeros, then the values up to max_cov: a prefix of the sorted values
+    size_t keep = 0;
+    while (keep < covs.size() && (double)covs[keep] <= max_cov) keep++;
+    const size_t n_total = n_genome_kmers - contain_count + keep;
     uint32_t sum = 0;
-    for (uint32_t x : full_covs) sum += x;                                   // iter().sum::<u32>()
-    const double mean_cov = (double)sum / (double)full_covs.size();          // :689
+    for (size_t i = 0; i < keep; i++) sum += covs[i];                        // iter().sum::<u32>()
     const double geq1_mean_cov = (double)sum / (double)covs.size();          // :690
-    (void)mean_cov;
+    Summary whole{0, 0, 0, 0, 0};                                            // of full_covs; read only where a lambda is estimated
     std::optional<double> test_lambda;
     if (median_cov > MEDIAN_ANI_THRESHOLD) r.lambda_status = AdjustStatus::High;   // :692-694
     else {
-        test_lambda = ratio_lambda(full_covs, args.min_count_correct);       // :695-713 (default estimator)
+        whole = summary_of_values(covs.data(), keep);
+        test_lambda = lambda_from_summary(whole, args.min_count_correct);    // :695-713 (default estimator)
         r.lambda_status = test_lambda ? AdjustStatus::Lambda : AdjustStatus::Low;
         if (test_lambda) r.lambda = *test_lambda;
     }
@@ -157,17 +195,28 @@ std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<ui
     else r.final_est_cov = args.mean_coverage ? geq1_mean_cov : median_cov;
     std::optional<double> opt_lambda;                                        // :730-735
     if (r.lambda_status == AdjustStatus::Lambda) opt_lambda = r.final_est_cov;
-    const auto opt_est_ani = ani_from_lambda(opt_lambda, (double)k, full_covs);   // :737
+    const auto opt_est_ani = ani_from_counts(opt_lambda, (double)k, whole.n_nonzero, n_total);   // :737
     r.final_est_ani = (!opt_lambda || !opt_est_ani || args.no_adj) ? r.naive_ani : *opt_est_ani;   // :739-744
     const double min_ani = args.minimum_ani ? *args.minimum_ani / 100. : (args.pseudotax ? MIN_ANI_P_DEF : MIN_ANI_DEF);
-    if (r.final_est_ani < min_ani) return std::nullopt;                      // :746-764
-    if (!args.no_ci && opt_lambda) bootstrap_interval(full_covs, (double)k, args, r);   // :766-773
+    if (r.final_est_ani < min_ani) return h;                                 // :746-764
+    h.want_ci = !args.no_ci && opt_lambda;                                   // :766-773
+    h.keep = keep;
+    h.n_total = n_total;
     r.mean_cov = geq1_mean_cov;                                              // AniResult.mean_cov (:795)
     r.median_cov = median_cov;
     r.contain_count = contain_count;
     r.n_kmers = n_genome_kmers;
     r.kmers_lost = kmers_lost;
-    return r;
+    h.result = r;
+    return h;
+}
+
+// contain.rs:657-813
+std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<uint32_t> covs, size_t n_genome_kmers, uint64_t k,
+                                         std::optional<size_t> kmers_lost) {
+    StatsHead h = stats_head(args, covs, n_genome_kmers, k, kmers_lost);
+    if (h.result && h.want_ci) bootstrap_host(covs.data(), h.keep, h.n_total, (double)k, args, *h.result);
+    return h.result;
 }
 
 }  // namespace sylph_host

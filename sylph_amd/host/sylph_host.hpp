@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/sylph_hip.h"
+#include "../csrc/bootstrap_plan.h"
 
 namespace sylph_host {
 
@@ -313,6 +314,30 @@ double poisson_cdf(double lambda, uint64_t x);   // statrs Poisson::cdf = Q(x+1,
 // in the sample (any order), n_genome_kmers = genome_kmers.len(), kmers_lost = Some(..) in the winner pass.
 std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<uint32_t> covs, size_t n_genome_kmers, uint64_t k,
                                          std::optional<size_t> kmers_lost);
+// The same in two halves with the confidence interval (bootstrap_interval, contain.rs:849-898) between them, so that the resampling
+// of many genomes can run in one device call (csrc/bootstrap.hip; bootstrap_batch below).  stats_head: everything up to the decision
+// about the interval; sorts covs in place.  result is empty where get_stats returns None; want_ci: the interval is due; keep: the
+// length of the prefix of the sorted values that went into full_covs, n_total = full_covs.len().  finish_ci: the resamples' counts ->
+// lambda and ANI of every resample -> the percentiles, into out.  bootstrap_host: the host's own resampling in front of finish_ci
+// (kept = the first `keep` sorted values).  stats_from_covs is stats_head + bootstrap_host.
+namespace bootstrap_plan = ::sylph::bootstrap_plan;
+constexpr uint64_t BOOTSTRAP_SEED = 7;      // fastrand::seed(7), contain.rs:854
+constexpr uint32_t BOOTSTRAP_ITERS = 100;   // contain.rs:857
+struct StatsHead { std::optional<AniResult> result; bool want_ci = false; size_t keep = 0, n_total = 0; };
+StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost);
+std::optional<double> lambda_from_summary(const bootstrap_plan::Summary& s, double min_count_correct);                 // inference.rs:207
+std::optional<double> ani_from_counts(std::optional<double> lambda, double k, size_t contain_count, size_t n_total);   // contain.rs:817
+void finish_ci(const bootstrap_plan::Summary* summaries, size_t iters, size_t n_total, double k, const ContainArgs& args, AniResult& out);
+void bootstrap_host(const uint32_t* kept, size_t keep, size_t n_total, double k, const ContainArgs& args, AniResult& out);
+// The intervals of a batch of genomes.  items: ascending and disjoint rows [cov_lo, cov_hi) of `covs` (host memory, `width` bytes per
+// value, ascending inside a row), of which the first `keep` values are the kept ones.  Device / DeviceOnly: ONE sylph_bootstrap_counts
+// call on ctx, then finish_ci per item on up to `threads` threads; an item the device declines runs bootstrap_host (DeviceOnly: Error).
+// Host: bootstrap_host for every item.  bootstrap_route(): SYLPH_HIP_BOOTSTRAP_DEVICE = 1 (default) | 0 | only.
+enum class BootstrapRoute { Host, Device, DeviceOnly };
+BootstrapRoute bootstrap_route();
+struct CiItem { AniResult* result; uint64_t cov_lo, cov_hi; size_t keep, n_total; };
+size_t bootstrap_batch(sylph_ctx* ctx, BootstrapRoute route, const ContainArgs& args, uint64_t k, const void* covs, uint32_t width,
+                       const std::vector<CiItem>& items, uint64_t threads);   // -> items that ran on the host
 
 // ---- commands ----
 struct SketchArgs {   // cmdline.rs:28-86
