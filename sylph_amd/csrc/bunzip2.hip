@@ -1,8 +1,9 @@
 // bunzip2.hip — bzip2 (.fastq.bz2 / .fasta.bz2, one stream or many) decoded ON THE DEVICE.
 //
 // The reference reads a bzip2 file through needletail -> libbz2 on the one thread that sketches the sample.  Here the COMPRESSED bytes
-// travel and the device does the rest; the bookkeeping and the proof of it are bunzip2_plan.h.  A bzip2 block is self-contained (no
-// window reaches into the block before it), so the blocks are decoded side by side; what is left are the serial chains inside a block:
+// travel and the device does the rest; the bookkeeping and the proof of it are bunzip2_plan.h, the host scaffold shared with inflate.hip
+// is decode_host.h.  A bzip2 block is self-contained (no window reaches into the block before it), so the blocks are decoded side by
+// side; what is left are the serial chains inside a block:
 //
 //   scan_kernel       every bit position of the file: the 48-bit block magic -> the CANDIDATES (true block starts + ~0)
 //   decode_kernel     one WAVEFRONT per candidate: symbol map, selectors (MTF over the groups, kept in global memory), code lengths,
@@ -28,15 +29,13 @@
 #include <algorithm>
 
 #include "bunzip2_plan.h"
-#include "common.h"
-#include "inflated.h"
+#include "decode_host.h"
 
 namespace sylph {
 namespace {
 
 using namespace bunzip2_plan;
-
-struct FormatDecline { std::string msg; };
+using namespace decode_host;
 
 constexpr uint32_t PAD_BYTES = 64;                 // zero bytes behind the compressed bytes on the device
 constexpr uint32_t CHUNK = 4096;                   // bytes per histogram chunk
@@ -50,7 +49,6 @@ constexpr uint32_t RLE_W = 8;                      // words per run-length chunk
 constexpr uint32_t PIECE = 4096;                   // bytes per CRC piece
 
 __device__ inline uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-__device__ inline uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // =================================================================================================================================
 // scan: the block magic at every bit position
@@ -548,175 +546,161 @@ uint32_t batch_size() {
     return 1024;
 }
 
-struct TextBuf {                                   // the text: grows (copying) as blocks come in
-    void* p = nullptr;
-    size_t cap = 0;                                // bytes of text it holds (+512 of padding)
-    ~TextBuf() { if (p) (void)hipFree(p); }         // (a declined call)
-    void grow(size_t need, size_t used, hipStream_t s) {
-        if (need <= cap) return;
-        const size_t c = std::max(need, cap * 2);
-        void* q = nullptr;
-        const hipError_t e = hipMalloc(&q, c + 512);
-        if (e != hipSuccess) { (void)hipGetLastError(); throw HipError{e, "hipMalloc (bzip2 text)", __FILE__, __LINE__}; }
-        SY_HIP(hipMemsetAsync(q, 0, 256, s));
-        if (p && used) SY_HIP(hipMemcpyAsync((uint8_t*)q + 256, (uint8_t*)p + 256, used, hipMemcpyDeviceToDevice, s));
-        if (p) { SY_HIP(hipStreamSynchronize(s)); (void)hipFree(p); }
-        p = q;
-        cap = c;
-    }
-};
-
-void bunzip2_impl(sylph_inflated* t, const void* const* bzs, const uint64_t* n_bytes, uint32_t n_files) {
-    sylph_ctx* ctx = t->ctx;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard dg(ctx->device);
-    hipStream_t s = ctx->stream;
-    Segments S;
-    S.base.push_back(0);
-    for (uint32_t i = 0; i < n_files; i++) {
-        S.ptr.push_back((const uint8_t*)bzs[i]);
-        S.base.push_back(S.base.back() + n_bytes[i]);
-        if (!stream_level((const uint8_t*)bzs[i], n_bytes[i], 0)) throw FormatDecline{"file " + std::to_string(i) + " does not begin with a bzip2 stream header"};
-    }
-    const uint64_t total = S.base.back();
-    const uint64_t n_words = (total + 3) / 4;
-    DevBuf d_in(ctx), d_cand(ctx), d_count(ctx), d_ll(ctx), d_sel(ctx), d_rep(ctx), d_tt(ctx), d_hist(ctx), d_succ(ctx), d_seg(ctx), d_offs(ctx),
-        d_rle(ctx), d_jobs(ctx), d_jstat(ctx), d_raw(ctx), d_tab(ctx), d_x2n(ctx);
-    // ---- the compressed bytes, back to back, and the candidates
-    d_in.reserve(n_words * 4 + PAD_BYTES);
-    SY_HIP(hipMemsetAsync((uint8_t*)d_in.p + n_words * 4 - 4, 0, 4 + PAD_BYTES, s));
-    for (uint32_t i = 0; i < n_files; i++) if (n_bytes[i]) ctx->h2d((uint8_t*)d_in.p + S.base[i], bzs[i], n_bytes[i]);
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(total / 8 + 64, 0xFFFFFFF0ull);
-    d_cand.reserve((size_t)cap * 8);
-    d_count.reserve(4);
-    uint32_t n_cand = 0;
-    {
-        ScopedKernelTimer kt(ctx, "bunzip2_scan");
-        HostPhase hp(ctx, "bunzip2: scan");
-        SY_HIP(hipMemsetAsync(d_count.p, 0, 4, s));
-        hipLaunchKernelGGL(scan_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, d_in.as<uint32_t>(), n_words, total * 8,
-                           d_cand.as<unsigned long long>(), cap, d_count.as<uint32_t>());
-        SY_HIP(hipGetLastError());
-        ctx->read_back(&n_cand, d_count.p, 4);
-    }
-    if (n_cand > cap) throw FormatDecline{"more block magics than the candidate list holds"};
-    std::vector<uint64_t> cand(n_cand);
-    if (n_cand) ctx->d2h(cand.data(), d_cand.p, (size_t)n_cand * 8);
-    std::sort(cand.begin(), cand.end());
-    if (n_cand) ctx->h2d(d_cand.p, cand.data(), (size_t)n_cand * 8);
-    // ---- batches of candidates in bit order; the chain is walked as their reports come in
-    const uint32_t B = std::max<uint32_t>(1, std::min<uint32_t>(batch_size(), std::max<uint32_t>(n_cand, 1)));
-    uint32_t x2n[64], table[256];
-    crc_x2n_table(x2n);
-    crc_byte_table(table);
-    d_x2n.reserve(sizeof(x2n));
-    d_tab.reserve(sizeof(table));
-    ctx->h2d(d_x2n.p, x2n, sizeof(x2n));
-    ctx->h2d(d_tab.p, table, sizeof(table));
-    std::vector<BlockReport> rep(n_cand);
+// One call's state, and its phases in the order bunzip2_impl runs them.  The candidates are decoded in batches, in bit order, and the
+// chain is walked as their reports come in: each turn finishes the chain blocks of the batch in hand, then decodes the next batch.
+struct Bunzip2Call {
+    sylph_inflated* t;
+    sylph_ctx* ctx;
+    hipStream_t s;
+    const Segments segs;
+    const uint64_t total, n_words;                      // compressed bytes, and the words that hold them
+    DevBuf d_in{ctx}, d_cand{ctx}, d_count{ctx}, d_ll{ctx}, d_sel{ctx}, d_rep{ctx}, d_tt{ctx}, d_hist{ctx}, d_succ{ctx}, d_seg{ctx}, d_offs{ctx}, d_rle{ctx}, d_jobs{ctx},
+        d_jstat{ctx}, d_raw{ctx}, d_tab{ctx}, d_x2n{ctx};
+    std::vector<uint64_t> cand;                         // sorted candidate bits
+    uint32_t B = 1;                                     // candidates per batch
+    uint32_t x2n[64];
+    std::vector<BlockReport> rep;                       // per candidate; those of [0, have) are known
     ChainWalk walk;
-    walk.start(&S, &cand);
     size_t have = 0, batch_first = 0, done_blocks = 0;
     std::vector<uint64_t> blk_off, blk_len;             // every chain block's text
-    TextBuf text;
-    text.grow(std::max<uint64_t>(total * 5, 1u << 20), 0, s);
+    TextBuf text{"hipMalloc (bzip2 text)"};
     uint64_t used = 0;
-    for (;;) {
-        const bool fin = walk.step(rep.data(), have);
-        if (!walk.why.empty()) throw FormatDecline{walk.why};
-        // ---- the chain blocks of the batch in hand: inverse BWT, run-length decode, CRC
-        const size_t nb = walk.blocks.size() - done_blocks;
-        if (nb) {
-            const uint32_t J = (uint32_t)nb;
-            std::vector<Job> jobs(J);
-            for (uint32_t j = 0; j < J; j++) {
-                const ChainBlock& cb = walk.blocks[done_blocks + j];
-                jobs[j] = Job{(uint32_t)(cb.cand - batch_first), cb.n, rep[cb.cand].orig_ptr, 0, 0};
-            }
-            d_jobs.reserve((size_t)J * sizeof(Job));
-            d_jstat.reserve((size_t)J * 4);
-            d_raw.reserve((size_t)J * 4);
-            d_hist.reserve((size_t)B * NCH * 256 * 4);
-            d_tt.reserve((size_t)B * MAX_BLOCK * 4);
-            d_succ.reserve((size_t)B * MK * 4);
-            d_seg.reserve((size_t)B * MK * 4);
-            d_offs.reserve((size_t)B * MK * 4);
-            d_rle.reserve((size_t)B * NRC * RLE_W * 4);
-            ctx->h2d(d_jobs.p, jobs.data(), (size_t)J * sizeof(Job));
-            SY_HIP(hipMemsetAsync(d_jstat.p, 0, (size_t)J * 4, s));
-            Job* dj = d_jobs.as<Job>();
-            {
-                ScopedKernelTimer kt(ctx, "bunzip2_bwt");
-                HostPhase hp(ctx, "bunzip2: LF mapping");
-                hipLaunchKernelGGL(hist_kernel, dim3(NCH, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_hist.as<uint32_t>());
-                hipLaunchKernelGGL(cft_kernel, dim3(J), dim3(256), 0, s, dj, d_hist.as<uint32_t>());
-                hipLaunchKernelGGL(scatter_kernel, dim3((NCH + 3) / 4, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_hist.as<uint32_t>(), d_tt.as<uint32_t>());
-                SY_HIP(hipGetLastError());
-            }
-            {
-                ScopedKernelTimer kt(ctx, "bunzip2_walk");
-                HostPhase hp(ctx, "bunzip2: walks");
-                hipLaunchKernelGGL(walk1_kernel, dim3((MK + 255) / 256, J), dim3(256), 0, s, dj, d_tt.as<uint32_t>(), d_succ.as<uint32_t>(), d_seg.as<uint32_t>(),
-                                   d_jstat.as<uint32_t>());
-                hipLaunchKernelGGL(rank_kernel, dim3(J), dim3(256), 0, s, dj, d_succ.as<uint32_t>(), d_seg.as<uint32_t>(), d_offs.as<uint32_t>(), d_jstat.as<uint32_t>());
-                hipLaunchKernelGGL(walk2_kernel, dim3((MK + 255) / 256, J), dim3(256), 0, s, dj, d_tt.as<uint32_t>(), d_seg.as<uint32_t>(), d_offs.as<uint32_t>(),
-                                   d_jstat.as<uint32_t>(), d_ll.as<uint8_t>());
-                SY_HIP(hipGetLastError());
-            }
-            {
-                ScopedKernelTimer kt(ctx, "bunzip2_rle");
-                HostPhase hp(ctx, "bunzip2: run lengths");
-                hipLaunchKernelGGL(rlefn_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_jstat.as<uint32_t>(), d_rle.as<uint32_t>());
-                hipLaunchKernelGGL(rlescan_kernel, dim3(J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), d_jstat.as<uint32_t>());
-                SY_HIP(hipGetLastError());
-            }
-            std::vector<uint32_t> jstat(J);
-            ctx->d2h(jstat.data(), d_jstat.p, (size_t)J * 4);
-            ctx->d2h(jobs.data(), d_jobs.p, (size_t)J * sizeof(Job));
-            uint32_t max_len = 0;
-            for (uint32_t j = 0; j < J; j++) {
-                if (jstat[j]) throw FormatDecline{"block " + std::to_string(done_blocks + j) + ": inverse BWT / run lengths do not add up (" + std::to_string(jstat[j]) + ")"};
-                jobs[j].out_off = used;
-                blk_off.push_back(used);
-                blk_len.push_back(jobs[j].out_len);
-                used += jobs[j].out_len;
-                max_len = std::max(max_len, jobs[j].out_len);
-            }
-            text.grow(used, blk_off[done_blocks], s);
-            ctx->h2d(d_jobs.p, jobs.data(), (size_t)J * sizeof(Job));
-            uint8_t* tx = (uint8_t*)text.p + 256;
-            {
-                ScopedKernelTimer kt(ctx, "bunzip2_rle");
-                HostPhase hp(ctx, "bunzip2: text");
-                hipLaunchKernelGGL(rlewrite_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), tx);
-                SY_HIP(hipGetLastError());
-            }
-            std::vector<uint32_t> raw(J);
-            {
-                ScopedKernelTimer kt(ctx, "bunzip2_crc");
-                HostPhase hp(ctx, "bunzip2: crc");
-                SY_HIP(hipMemsetAsync(d_raw.p, 0, (size_t)J * 4, s));
-                const uint32_t gx = (uint32_t)(((uint64_t)max_len + (uint64_t)PIECE * 256 - 1) / ((uint64_t)PIECE * 256));
-                if (gx) {
-                    hipLaunchKernelGGL(crc_kernel, dim3(gx, J), dim3(256), 0, s, dj, tx, d_tab.as<uint32_t>(), d_x2n.as<uint32_t>(), d_raw.as<uint32_t>());
-                    SY_HIP(hipGetLastError());
-                }
-                ctx->d2h(raw.data(), d_raw.p, (size_t)J * 4);
-            }
-            for (uint32_t j = 0; j < J; j++) {
-                const ChainBlock& cb = walk.blocks[done_blocks + j];
-                const uint32_t got = crc_finish(x2n, raw[j], jobs[j].out_len);
-                if (got != rep[cb.cand].crc) {
-                    char msg[160];
-                    snprintf(msg, sizeof(msg), "block %zu: CRC %08x, the stream says %08x", done_blocks + j, got, rep[cb.cand].crc);
-                    throw FormatDecline{msg};
-                }
-            }
-            done_blocks = walk.blocks.size();
+    std::vector<Job> jobs;                              // the chain blocks of the batch in hand
+    uint32_t max_len = 0;                               // the longest of their texts
+
+    Bunzip2Call(sylph_inflated* t_, Segments&& g)
+        : t(t_), ctx(t_->ctx), s(t_->ctx->stream), segs(std::move(g)), total(segs.total()), n_words((total + 3) / 4) {}
+
+    // ---- the compressed bytes, back to back, and the candidates
+    void find_candidates() {
+        d_in.reserve(n_words * 4 + PAD_BYTES);
+        upload_segments(ctx, (uint8_t*)d_in.p, segs, PAD_BYTES);
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(total / 8 + 64, 0xFFFFFFF0ull);
+        d_cand.reserve((size_t)cap * 8);
+        d_count.reserve(4);
+        {
+            ScopedKernelTimer kt(ctx, "bunzip2_scan");
+            HostPhase hp(ctx, "bunzip2: scan");
+            SY_HIP(hipMemsetAsync(d_count.p, 0, 4, s));
+            hipLaunchKernelGGL(scan_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, d_in.as<uint32_t>(), n_words, total * 8,
+                               d_cand.as<unsigned long long>(), cap, d_count.as<uint32_t>());
+            SY_HIP(hipGetLastError());
+            cand = fetch_candidates(ctx, d_cand.p, d_count.as<uint32_t>(), cap, "more block magics than the candidate list holds");
         }
-        if (fin) break;
-        // ---- the next batch of candidates
-        const uint32_t cnt = (uint32_t)std::min<size_t>(B, n_cand - have);
+        if (!cand.empty()) ctx->h2d(d_cand.p, cand.data(), cand.size() * 8);
+        rep.resize(cand.size());
+        B = std::max<uint32_t>(1, std::min<uint32_t>(batch_size(), std::max<uint32_t>((uint32_t)cand.size(), 1)));
+    }
+
+    void upload_crc_tables() {
+        uint32_t table[256];
+        crc_x2n_table(x2n);
+        crc_byte_table(table);
+        d_x2n.reserve(sizeof(x2n));
+        d_tab.reserve(sizeof(table));
+        ctx->h2d(d_x2n.p, x2n, sizeof(x2n));
+        ctx->h2d(d_tab.p, table, sizeof(table));
+    }
+
+    // ---- the chain blocks of the batch in hand: inverse BWT (LF mapping, walks) and the run-length functions -> every block's length
+    void invert_batch() {
+        const uint32_t J = (uint32_t)(walk.blocks.size() - done_blocks);
+        jobs.resize(J);
+        for (uint32_t j = 0; j < J; j++) {
+            const ChainBlock& cb = walk.blocks[done_blocks + j];
+            jobs[j] = Job{(uint32_t)(cb.cand - batch_first), cb.n, rep[cb.cand].orig_ptr, 0, 0};
+        }
+        d_jobs.reserve((size_t)J * sizeof(Job));
+        d_jstat.reserve((size_t)J * 4);
+        d_raw.reserve((size_t)J * 4);
+        d_hist.reserve((size_t)B * NCH * 256 * 4);
+        d_tt.reserve((size_t)B * MAX_BLOCK * 4);
+        d_succ.reserve((size_t)B * MK * 4);
+        d_seg.reserve((size_t)B * MK * 4);
+        d_offs.reserve((size_t)B * MK * 4);
+        d_rle.reserve((size_t)B * NRC * RLE_W * 4);
+        ctx->h2d(d_jobs.p, jobs.data(), (size_t)J * sizeof(Job));
+        SY_HIP(hipMemsetAsync(d_jstat.p, 0, (size_t)J * 4, s));
+        Job* dj = d_jobs.as<Job>();
+        {
+            ScopedKernelTimer kt(ctx, "bunzip2_bwt");
+            HostPhase hp(ctx, "bunzip2: LF mapping");
+            hipLaunchKernelGGL(hist_kernel, dim3(NCH, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_hist.as<uint32_t>());
+            hipLaunchKernelGGL(cft_kernel, dim3(J), dim3(256), 0, s, dj, d_hist.as<uint32_t>());
+            hipLaunchKernelGGL(scatter_kernel, dim3((NCH + 3) / 4, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_hist.as<uint32_t>(), d_tt.as<uint32_t>());
+            SY_HIP(hipGetLastError());
+        }
+        {
+            ScopedKernelTimer kt(ctx, "bunzip2_walk");
+            HostPhase hp(ctx, "bunzip2: walks");
+            hipLaunchKernelGGL(walk1_kernel, dim3((MK + 255) / 256, J), dim3(256), 0, s, dj, d_tt.as<uint32_t>(), d_succ.as<uint32_t>(), d_seg.as<uint32_t>(),
+                               d_jstat.as<uint32_t>());
+            hipLaunchKernelGGL(rank_kernel, dim3(J), dim3(256), 0, s, dj, d_succ.as<uint32_t>(), d_seg.as<uint32_t>(), d_offs.as<uint32_t>(), d_jstat.as<uint32_t>());
+            hipLaunchKernelGGL(walk2_kernel, dim3((MK + 255) / 256, J), dim3(256), 0, s, dj, d_tt.as<uint32_t>(), d_seg.as<uint32_t>(), d_offs.as<uint32_t>(),
+                               d_jstat.as<uint32_t>(), d_ll.as<uint8_t>());
+            SY_HIP(hipGetLastError());
+        }
+        {
+            ScopedKernelTimer kt(ctx, "bunzip2_rle");
+            HostPhase hp(ctx, "bunzip2: run lengths");
+            hipLaunchKernelGGL(rlefn_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_jstat.as<uint32_t>(), d_rle.as<uint32_t>());
+            hipLaunchKernelGGL(rlescan_kernel, dim3(J), dim3(256), 0, s, dj, d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), d_jstat.as<uint32_t>());
+            SY_HIP(hipGetLastError());
+        }
+        std::vector<uint32_t> jstat(J);
+        ctx->d2h(jstat.data(), d_jstat.p, (size_t)J * 4);
+        ctx->d2h(jobs.data(), d_jobs.p, (size_t)J * sizeof(Job));
+        for (uint32_t j = 0; j < J; j++)
+            if (jstat[j]) throw FormatDecline{"block " + std::to_string(done_blocks + j) + ": inverse BWT / run lengths do not add up (" + std::to_string(jstat[j]) + ")"};
+    }
+
+    // ---- every block of the batch gets its place behind the text so far, and is written there
+    void write_batch_text() {
+        const uint32_t J = (uint32_t)jobs.size();
+        max_len = 0;
+        for (uint32_t j = 0; j < J; j++) {
+            jobs[j].out_off = used;
+            blk_off.push_back(used);
+            blk_len.push_back(jobs[j].out_len);
+            used += jobs[j].out_len;
+            max_len = std::max(max_len, jobs[j].out_len);
+        }
+        text.grow(used, blk_off[done_blocks], s);
+        ctx->h2d(d_jobs.p, jobs.data(), (size_t)J * sizeof(Job));
+        ScopedKernelTimer kt(ctx, "bunzip2_rle");
+        HostPhase hp(ctx, "bunzip2: text");
+        hipLaunchKernelGGL(rlewrite_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, d_jobs.as<Job>(), d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), text.text());
+        SY_HIP(hipGetLastError());
+    }
+
+    // ---- CRC-32/BZIP2 of every block of the batch, against the one its header stores
+    void check_batch_crcs() {
+        const uint32_t J = (uint32_t)jobs.size();
+        std::vector<uint32_t> raw(J);
+        {
+            ScopedKernelTimer kt(ctx, "bunzip2_crc");
+            HostPhase hp(ctx, "bunzip2: crc");
+            SY_HIP(hipMemsetAsync(d_raw.p, 0, (size_t)J * 4, s));
+            const uint32_t gx = (uint32_t)(((uint64_t)max_len + (uint64_t)PIECE * 256 - 1) / ((uint64_t)PIECE * 256));
+            if (gx) {
+                hipLaunchKernelGGL(crc_kernel, dim3(gx, J), dim3(256), 0, s, d_jobs.as<Job>(), text.text(), d_tab.as<uint32_t>(), d_x2n.as<uint32_t>(), d_raw.as<uint32_t>());
+                SY_HIP(hipGetLastError());
+            }
+            ctx->d2h(raw.data(), d_raw.p, (size_t)J * 4);
+        }
+        for (uint32_t j = 0; j < J; j++) {
+            const uint32_t stored = rep[walk.blocks[done_blocks + j].cand].crc, got = crc_finish(x2n, raw[j], jobs[j].out_len);
+            if (got != stored) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "block %zu: CRC %08x, the stream says %08x", done_blocks + j, got, stored);
+                throw FormatDecline{msg};
+            }
+        }
+    }
+
+    // ---- the next batch of candidates: one wavefront each, the BWT columns and the reports
+    void decode_next_batch() {
+        const uint32_t cnt = (uint32_t)std::min<size_t>(B, cand.size() - have);
         if (!cnt) throw FormatDecline{"the chain needs a candidate that is not there"};
         batch_first = have;
         d_ll.reserve((size_t)B * MAX_BLOCK);
@@ -732,26 +716,55 @@ void bunzip2_impl(sylph_inflated* t, const void* const* bzs, const uint64_t* n_b
         ctx->d2h(rep.data() + batch_first, d_rep.p, (size_t)cnt * sizeof(BlockReport));
         have += cnt;
     }
-    // ---- the handle
-    SY_HIP(hipMemsetAsync((uint8_t*)text.p + 256 + used, 0, 256, s));
-    t->buf = text.p;
-    text.p = nullptr;
-    t->n = used;
-    t->n_members = walk.n_streams;
-    t->n_blocks = walk.blocks.size();
-    t->n_candidates = have;
-    t->n_host_members = 0;
-    t->files.assign(n_files, {0, 0});
-    {
+
+    // ---- the handle: the text, the counts, every file's range (a file's blocks are consecutive in the chain)
+    void fill_handle() {
+        SY_HIP(hipMemsetAsync(text.text() + used, 0, 256, s));
+        t->buf = text.release();
+        t->n = used;
+        t->n_members = walk.n_streams;
+        t->n_blocks = walk.blocks.size();
+        t->n_candidates = have;
+        t->n_host_members = 0;
+        t->files.assign(segs.ptr.size(), {0, 0});
         uint64_t at = 0;
         size_t bi = 0;
-        for (uint32_t f = 0; f < n_files; f++) {
+        for (uint32_t f = 0; f < segs.ptr.size(); f++) {
             const uint64_t begin = at;
             while (bi < walk.blocks.size() && walk.blocks[bi].file == f) { at = blk_off[bi] + blk_len[bi]; bi++; }
             t->files[f] = {begin, at};
         }
     }
-    SY_HIP(hipStreamSynchronize(s));
+};
+
+void bunzip2_impl(sylph_inflated* t, const void* const* bzs, const uint64_t* n_bytes, uint32_t n_files) {
+    sylph_ctx* ctx = t->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard dg(ctx->device);
+    Segments segs = segments_of(bzs, n_bytes, n_files);
+    for (uint32_t i = 0; i < n_files; i++) {
+        if (!n_bytes[i]) throw FormatDecline{"file " + std::to_string(i) + " is empty"};
+        if (!stream_level(segs.ptr[i], n_bytes[i], 0)) throw FormatDecline{"file " + std::to_string(i) + " does not begin with a bzip2 stream header"};
+    }
+    Bunzip2Call c(t, std::move(segs));
+    c.find_candidates();
+    c.upload_crc_tables();
+    c.walk.start(&c.segs, &c.cand);
+    c.text.grow(std::max<uint64_t>(c.total * 5, 1u << 20), 0, c.s);
+    for (;;) {
+        const bool fin = c.walk.step(c.rep.data(), c.have);
+        if (!c.walk.why.empty()) throw FormatDecline{c.walk.why};
+        if (c.walk.blocks.size() > c.done_blocks) {
+            c.invert_batch();
+            c.write_batch_text();
+            c.check_batch_crcs();
+            c.done_blocks = c.walk.blocks.size();
+        }
+        if (fin) break;
+        c.decode_next_batch();
+    }
+    c.fill_handle();
+    SY_HIP(hipStreamSynchronize(c.s));
 }
 
 }  // namespace
@@ -762,32 +775,7 @@ using namespace sylph;
 extern "C" {
 
 int sylph_bunzip2_files(sylph_ctx* ctx, const void* const* bz, const uint64_t* n_bytes, uint32_t n_files, int mem, sylph_inflated** out) {
-    if (!ctx || !out || !bz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    for (uint32_t i = 0; i < n_files; i++) if (!bz[i] && n_bytes[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_bunzip2: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
-    *out = nullptr;
-    ctx->refs.fetch_add(1);
-    sylph_inflated* t = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        t = new sylph_inflated();
-        t->ctx = ctx;
-        try { bunzip2_impl(t, bz, n_bytes, n_files); }
-        catch (const FormatDecline& e) { set_error("sylph_bunzip2: declined: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        {
-            std::lock_guard<std::mutex> lock(ctx->mu);
-            DeviceGuard dg(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-            if (t && t->buf) (void)hipFree(t->buf);
-            delete t;
-        }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = t;
-    return SYLPH_OK;
+    return decode_entry("sylph_bunzip2", true, ctx, bz, n_bytes, n_files, mem, out, bunzip2_impl);
 }
 
 int sylph_bunzip2(sylph_ctx* ctx, const void* bz, uint64_t n_bytes, int mem, sylph_inflated** out) {

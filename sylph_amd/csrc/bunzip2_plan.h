@@ -11,8 +11,9 @@
 //     block ended -> ... -> the end-of-stream magic -> the combined CRC -> the next stream's header -> ...; a candidate that is not
 //     on the chain was never a block start;
 //   * the block CRCs (CRC-32 with polynomial 0x04C11DB7, MSB first: the non-reflected form, unlike gzip's) are put together from
-//     the CRCs of pieces computed anywhere on the device (crc_shift below: the CRC is linear over GF(2)), and the run-length
-//     decode of a block is a scan of small state-transfer functions (RleFn).
+//     the CRCs of pieces computed anywhere on the device (crc_shift: the CRC is linear over GF(2); the arithmetic is stream_plan.h's,
+//     shared with gzip's bit order, as is Segments, the files of a call), and the run-length decode of a block is a scan of small
+//     state-transfer functions (RleFn).
 // Anything that does not add up makes the whole call decline (SYLPH_ERR_FORMAT): the caller decodes the file with libbz2 as before.
 #pragma once
 #include <cstddef>
@@ -20,11 +21,7 @@
 #include <string>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define SYLPH_HD __host__ __device__
-#else
-#define SYLPH_HD
-#endif
+#include "stream_plan.h"
 
 namespace sylph {
 namespace bunzip2_plan {
@@ -34,56 +31,18 @@ constexpr uint64_t EOS_MAGIC = 0x177245385090ull;
 constexpr uint32_t MAX_BLOCK = 900000;        // bytes of BWT column in a block at level 9
 constexpr uint32_t MAX_SELECTORS = 18002;     // what libbz2 1.0.8 keeps (2 + 900 000 / 50); a block that sends more is declined
 
-// ---- CRC-32/BZIP2 as polynomial arithmetic over GF(2) ------------------------------------------------------------------------
-// Bit 31 of a word is the coefficient of x^31, bit 0 that of x^0; the implicit x^32 of the polynomial is left out.
-constexpr uint32_t CRC_POLY = 0x04C11DB7u;
-
-// a * b mod P
-SYLPH_HD inline uint32_t crc_multmodp(uint32_t a, uint32_t b) {
-    uint32_t p = 0;
-    for (int i = 31; i >= 0; i--) {
-        p = (p & 0x80000000u) ? (p << 1) ^ CRC_POLY : p << 1;
-        if ((a >> i) & 1) p ^= b;
-    }
-    return p;
-}
-// x2n[k] = x^(2^k) mod P, k = 0 .. 63
-inline void crc_x2n_table(uint32_t t[64]) {
-    uint32_t p = 2u;                              // x^1
-    t[0] = p;
-    for (int k = 1; k < 64; k++) t[k] = p = crc_multmodp(p, p);
-}
-// x^(8 n) mod P
-SYLPH_HD inline uint32_t crc_x8n(const uint32_t* x2n, unsigned long long n_bytes) {
-    uint32_t p = 1u;                              // x^0
-    unsigned k = 3;
-    while (n_bytes) {
-        if (n_bytes & 1) p = crc_multmodp(x2n[k & 63], p);
-        n_bytes >>= 1;
-        k++;
-    }
-    return p;
-}
-// the register of the CRC loop (no initial or final inversion) after n more zero bytes
-SYLPH_HD inline uint32_t crc_shift(const uint32_t* x2n, uint32_t reg, unsigned long long n_bytes) {
-    return n_bytes ? crc_multmodp(crc_x8n(x2n, n_bytes), reg) : reg;
-}
-// a block's CRC from `raw` = XOR over its pieces of crc_shift(register of the piece started at 0, bytes behind the piece in the
-// block): the initial 0xFFFFFFFF travels through all n bytes, the final inversion is on top
-inline uint32_t crc_finish(const uint32_t* x2n, uint32_t raw, unsigned long long n_bytes) {
-    return ~(raw ^ crc_shift(x2n, 0xFFFFFFFFu, n_bytes));
-}
-inline void crc_byte_table(uint32_t t[256]) {
-    for (uint32_t i = 0; i < 256; i++) {
-        uint32_t c = i << 24;
-        for (int k = 0; k < 8; k++) c = (c & 0x80000000u) ? (c << 1) ^ CRC_POLY : c << 1;
-        t[i] = c;
-    }
-}
-SYLPH_HD inline uint32_t crc_raw(const uint32_t* t, uint32_t reg, const uint8_t* p, size_t n) {
-    for (size_t i = 0; i < n; i++) reg = (reg << 8) ^ t[(reg >> 24) ^ p[i]];
-    return reg;
-}
+// ---- CRC-32/BZIP2 (polynomial 0x04C11DB7, MSB first): stream_plan.h's family in the bit order that is not reflected ------------
+// a block's CRC = crc_finish(XOR over its pieces of crc_shift(register of the piece started at 0, bytes behind the piece in the
+// block), the block's length)
+using Crc = stream_plan::Crc32<false>;
+constexpr uint32_t CRC_POLY = Crc::POLY;
+SYLPH_HD inline uint32_t crc_multmodp(uint32_t a, uint32_t b) { return Crc::multmodp(a, b); }
+inline void crc_x2n_table(uint32_t t[64]) { Crc::x2n_table(t); }
+SYLPH_HD inline uint32_t crc_x8n(const uint32_t* x2n, unsigned long long n_bytes) { return Crc::x8n(x2n, n_bytes); }
+SYLPH_HD inline uint32_t crc_shift(const uint32_t* x2n, uint32_t reg, unsigned long long n_bytes) { return Crc::shift(x2n, reg, n_bytes); }
+inline uint32_t crc_finish(const uint32_t* x2n, uint32_t raw, unsigned long long n_bytes) { return Crc::finish(x2n, raw, n_bytes); }
+inline void crc_byte_table(uint32_t t[256]) { Crc::byte_table(t); }
+SYLPH_HD inline uint32_t crc_raw(const uint32_t* t, uint32_t reg, const uint8_t* p, size_t n) { return Crc::raw(t, reg, p, n); }
 // a stream's combined CRC, block after block
 inline uint32_t combine_stream(uint32_t c, uint32_t block_crc) { return ((c << 1) | (c >> 31)) ^ block_crc; }
 
@@ -154,10 +113,7 @@ struct BlockReport {
 };
 
 // ---- the chain ------------------------------------------------------------------------------------------------------------------
-struct Segments {                 // the files of one call: each its own bytes; in the device's buffer they lie back to back
-    std::vector<const uint8_t*> ptr;
-    std::vector<uint64_t> base;   // base[i] = byte offset of file i; base.back() = the total
-};
+using stream_plan::Segments;      // the files of one call: each its own bytes; in the device's buffer they lie back to back
 // the k <= 48 bits at `bit` (MSB-first) of d[0, n), zero beyond n bytes
 inline uint64_t bits_at(const uint8_t* d, uint64_t n, uint64_t bit, unsigned k) {
     uint64_t v = 0;

@@ -3,7 +3,8 @@
 // The reference reads its normal input — gzip files (README.md:51; sketch.rs:780-781, :906 through needletail -> flate2) — with one
 // thread per file: ~0.4 Gbp/s.  Rounds 4-5 inflated on the host with all parse threads (host/pgunzip.cpp): 1.6-2.0 Gbp/s per
 // command on the GPU box, the slowest road of the feed although compressed bytes (0.4 B per base) are the cheapest thing to move
-// over PCIe.  Here the COMPRESSED bytes travel and the device does the rest (bookkeeping and the proof of it: inflate_plan.h):
+// over PCIe.  Here the COMPRESSED bytes travel and the device does the rest (bookkeeping and the proof of it: inflate_plan.h; the host
+// scaffold shared with bunzip2.hip: decode_host.h):
 //
 //   scan1_kernel      every bit position of the file: "BTYPE = dynamic, HLIT/HDIST in range, the code-length code is complete"
 //                     (one 17-bit test + a Kraft sum over the 3-bit lengths from a 512-entry LDS table) -> ~0.1 % survive
@@ -32,17 +33,14 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "decode_host.h"
 #include "inflate_plan.h"
-
-#include "inflated.h"
 
 namespace sylph {
 namespace {
 
 using namespace inflate_plan;
-
-struct FormatDecline { std::string msg; };
+using namespace decode_host;
 
 constexpr int LIT_ROOT = 10, DIST_ROOT = 8, PRE_ROOT = 7;
 constexpr uint32_t T_LONG = 0xFFFFu;
@@ -218,8 +216,6 @@ struct WaveTables {
 // has to live in SGPRs for the loop to run on the scalar unit: a value that came out of LDS or global memory is "divergent" to the
 // compiler until it has been through v_readfirstlane, and one divergent value in a loop condition drags the whole state into VGPRs
 // behind exec masks (the first build of this file: 7,900 lines of s_and_saveexec).
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
 struct WaveBits {                                  // the same reader, but everything in it is wave-uniform (SGPRs)
     const uint32_t* w;
     uint64_t acc, wpos, wlimit, cbase;
@@ -380,8 +376,7 @@ __device__ __forceinline__ uint32_t decode_long(uint32_t bits, uint32_t root, ui
 // the ring at least a chunk ago, so the stores are issued; the same wave's loads see them).  The first version kept nothing on the
 // chip and every match waited for the acknowledgement of all earlier stores and for its own load — vmcnt counts both —, ~5,000
 // cycles per match: 35 ms for a block of 16 K matches, whatever the literals cost.
-// one candidate for a wavefront: where its block starts, where its cells go (offset into the cells buffer) and how many fit
-struct DecodeJob { unsigned long long start_bit, region; uint32_t cap, have_window; };
+// (DecodeJob — one candidate for a wavefront — and where its region lies: inflate_plan.h)
 // the spill arena behind the candidates' regions: SPILL_SLOTS regions of SPILL_CELLS cells, handed out by an atomic counter (next)
 struct Spill { unsigned long long base; uint32_t slots; };
 constexpr uint32_t SPILL_CELLS = 1u << 20, SPILL_SLOTS = 96;
@@ -986,271 +981,229 @@ bool zlib_member(const uint8_t* gz, size_t n, size_t p, size_t* end, std::vector
 // Several files in one call are ONE stream of gzip members to everything below (`cat a.gz b.gz` is a gzip file): their bytes lie back
 // to back on the device, one scan, one decode launch, one chain — the two mates of a pair share the latency of a block's wavefront
 // (~15 ms whatever the file's size) instead of paying it one after the other.
-void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_bytes, uint32_t n_files) {
-    sylph_ctx* ctx = t->ctx;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard dg(ctx->device);
-    hipStream_t s = ctx->stream;
-    Segments segs;
-    segs.base.push_back(0);
-    for (uint32_t i = 0; i < n_files; i++) {
-        if (!member_body((const uint8_t*)gzs[i], (size_t)n_bytes[i], 0)) throw FormatDecline{"not a gzip file"};
-        segs.ptr.push_back((const uint8_t*)gzs[i]);
-        segs.base.push_back(segs.base.back() + (size_t)n_bytes[i]);
-    }
-    const uint64_t n = segs.total();
-    const size_t body0 = member_body(segs.ptr[0], (size_t)n_bytes[0], 0);
-    if (n >= (3ull << 30)) throw FormatDecline{"3 GiB of gzip bytes or more: the host reader takes them"};
-    const uint64_t byte_end = n;                    // (trailers and later headers are scanned too: no harm, and members end anywhere)
+// One call's state, and its phases in the order inflate_impl runs them.
+struct InflateCall {
+    sylph_inflated* t;
+    sylph_ctx* ctx;
+    hipStream_t s;
+    InflateScratch& S;
+    const Segments segs;
+    const uint64_t n, n_words;                      // compressed bytes, and the words that hold them
+    const uint64_t body0;                           // the first member's first deflate byte
+    std::vector<uint64_t> cand;                     // sorted candidate bits; cand[0] = body0 * 8
+    uint32_t K = 0;
+    CellsLayout cells{};
+    std::vector<BlockResult> res;                   // per candidate
+    std::vector<std::vector<uint8_t>> host_bytes;   // per Chain::host piece
+    Chain chain;
+    Raw cells2;                                     // the cells of the blocks decoded again
+    RedoPlan redo;
+    TextBuf text{"hipMalloc (inflated text)"};
+
+    InflateCall(sylph_inflated* t_, InflateScratch& S_, Segments&& g)
+        : t(t_), ctx(t_->ctx), s(t_->ctx->stream), S(S_), segs(std::move(g)), n(segs.total()), n_words((n + 3) / 4),
+          body0(member_body(segs.ptr[0], (size_t)segs.base[1], 0)) {}
+
     // ---- the compressed bytes, padded with zero words
-    const uint64_t n_words = (n + 3) / 4;
-    DeviceScratch& DS = device_scratch(ctx->device);
-    std::lock_guard<std::mutex> turn(DS.mu);                       // one inflate per device at a time: they share the scratch
-    InflateScratch& S = DS.s;
-    // (on every way out — a decline included — the stream is idle before the next call may touch the scratch; destroyed before `turn`)
-    struct Done { InflateScratch& s; hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); if (s.bytes() > SCRATCH_KEEP) s.release(); } } done{S, s};
-    Raw& d_gz = S.gz;
-    d_gz.reserve((n_words + GZ_PAD_WORDS) * 4);
-    {
+    void upload() {
+        S.gz.reserve((n_words + GZ_PAD_WORDS) * 4);
         HostPhase hp(ctx, "inflate: upload");
-        SY_HIP(hipMemsetAsync(d_gz.as<uint8_t>() + (n & ~(uint64_t)3), 0, (n_words + GZ_PAD_WORDS) * 4 - (n & ~(uint64_t)3), s));
-        for (uint32_t i = 0; i < n_files; i++) ctx->h2d(d_gz.as<uint8_t>() + segs.base[i], segs.ptr[i], (size_t)n_bytes[i]);
+        upload_segments(ctx, S.gz.as<uint8_t>(), segs, GZ_PAD_WORDS * 4);
     }
-    // ---- candidates
-    const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
-    Raw &d_c1 = S.c1, &d_c2 = S.c2, &d_cnt = S.cnt;
-    d_c1.reserve(cap1 * 8);
-    d_c2.reserve(cap2 * 8);
-    d_cnt.reserve(64);
-    SY_HIP(hipMemsetAsync(d_cnt.p, 0, 64, s));
-    unsigned long long* cnt = d_cnt.as<unsigned long long>();
-    unsigned long long n1 = 0, n2 = 0;
-    {
-        ScopedKernelTimer kt(ctx, "inflate_scan");
-        HostPhase hp(ctx, "inflate: scan");
-        const uint64_t span = byte_end - body0;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>((span + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
-        hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, d_gz.as<uint32_t>(), (uint64_t)body0, byte_end, d_c1.as<uint64_t>(), cnt, cap1);
-        SY_HIP(hipGetLastError());
-        ctx->read_back(&n1, cnt, 8);
-        if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
-        if (n1) {
-            hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, d_gz.as<uint32_t>(), n * 8, d_c1.as<uint64_t>(),
-                               cnt, cap1, d_c2.as<uint64_t>(), cnt + 1, cap2);
+
+    // ---- candidates (trailers and later headers are scanned too: no harm, and members end anywhere)
+    void find_candidates() {
+        const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
+        S.c1.reserve(cap1 * 8);
+        S.c2.reserve(cap2 * 8);
+        S.cnt.reserve(64);
+        SY_HIP(hipMemsetAsync(S.cnt.p, 0, 64, s));
+        unsigned long long* cnt = S.cnt.as<unsigned long long>();
+        {
+            ScopedKernelTimer kt(ctx, "inflate_scan");
+            HostPhase hp(ctx, "inflate: scan");
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((n - body0 + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
+            hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, S.gz.as<uint32_t>(), body0, n, S.c1.as<uint64_t>(), cnt, cap1);
             SY_HIP(hipGetLastError());
+            unsigned long long n1 = 0;
+            ctx->read_back(&n1, cnt, 8);
+            if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
+            if (n1) {
+                hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, S.gz.as<uint32_t>(), n * 8, S.c1.as<uint64_t>(),
+                                   cnt, cap1, S.c2.as<uint64_t>(), cnt + 1, cap2);
+                SY_HIP(hipGetLastError());
+            }
+            cand = fetch_candidates(ctx, S.c2.p, cnt + 1, cap2, "more block-start candidates than the scan has room for");
         }
-        ctx->read_back(&n2, cnt + 1, 8);
-        if (n2 > cap2) throw FormatDecline{"more block-start candidates than the scan has room for"};
+        cand.insert(std::lower_bound(cand.begin(), cand.end(), body0 * 8), body0 * 8);      // the stream's first block, whatever its type
+        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+        if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
+        t->n_candidates = K = (uint32_t)cand.size();
     }
-    std::vector<uint64_t> cand(n2 + 1);
-    if (n2) ctx->d2h(cand.data(), d_c2.p, n2 * 8);
-    cand[n2] = (uint64_t)body0 * 8;                 // the stream's first block, whatever its type
-    std::sort(cand.begin(), cand.end());
-    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-    const uint32_t K = (uint32_t)cand.size();
-    if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
-    t->n_candidates = K;
-    // ---- decode every candidate
-    // (SYLPH_HIP_INFLATE_REGION_RATIO: the tests' way to make every block outgrow its region)
-    const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
-    // A single-member file says how well it deflates (ISIZE in its trailer): its blocks get 1.5 x that + 1 cells per compressed byte instead
-    // of the flat REGION_RATIO (bench.py's mate file: 5.3 -> 9: 7 GB of cells for a 1 Gbp pair instead of 12.7) — less to allocate, and less
-    // for the process to hand back when it ends.  Several members (BGZF ends with an empty one), a wrapped ISIZE: the flat ratio.
-    uint64_t auto_ratio = REGION_RATIO;
-    {
-        double worst = 0;
-        bool known = true;
-        for (uint32_t i = 0; i < n_files && known; i++) {
-            const uint8_t* tr = segs.ptr[i] + n_bytes[i] - 4;
-            const double isize = (double)(tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24), r = isize / (double)n_bytes[i];
-            if (r < 1.5 || r > 40) known = false;
-            worst = std::max(worst, r);
-        }
-        if (known) auto_ratio = std::min<uint64_t>(REGION_RATIO, (uint64_t)(worst * 1.5) + 2);
-    }
-    const uint64_t region_ratio = rr_env ? std::max(1, std::min(64, atoi(rr_env))) : auto_ratio;
-    const uint64_t n_cells = (byte_end - body0) * region_ratio + (uint64_t)K * REGION_SLACK + 64;
-    Raw &d_cells = S.cells, &d_res = S.res, &d_jobs = S.jobs;
-    const uint64_t spill_base = (n_cells + 63) & ~(uint64_t)63;
-    d_cells.reserve((spill_base + (uint64_t)SPILL_SLOTS * SPILL_CELLS + 64) * 2);
-    d_res.reserve((size_t)K * sizeof(BlockResult));
-    d_jobs.reserve((size_t)K * sizeof(DecodeJob));
-    SY_HIP(hipMemsetAsync(cnt + 2, 0, 8, s));                                 // the spill arena's counter
-    const Spill spill{spill_base, SPILL_SLOTS}, no_spill{0, 0};
-    uint32_t* const spill_next = reinterpret_cast<uint32_t*>(cnt + 2);
-    std::vector<BlockResult> res(K);
-    int n_cu = 256;
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-    auto launch_decode = [&](const DecodeJob* jobs, uint32_t n_jobs, uint16_t* cells, const Spill& sp, BlockResult* out) {
+
+    void launch_decode(const DecodeJob* jobs, uint32_t n_jobs, uint16_t* out_cells, const Spill& sp, BlockResult* out) {
+        int n_cu = 256;
+        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
+        uint32_t* const spill_next = reinterpret_cast<uint32_t*>(S.cnt.as<unsigned long long>() + 2);
         // the larger ring while all blocks' wavefronts fit on the chip beside each other with it (LDS: ~13 KB per wavefront -> 12 per CU)
         if (n_jobs <= (uint32_t)n_cu * 12 && !getenv("SYLPH_HIP_INFLATE_SMALL_RING"))
-            hipLaunchKernelGGL(decode_kernel<4096>, dim3(n_jobs), dim3(64), 0, s, d_gz.as<uint32_t>(), n_words, jobs, cells, sp, spill_next, out);
+            hipLaunchKernelGGL(decode_kernel<4096>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
         else
-            hipLaunchKernelGGL(decode_kernel<2048>, dim3(n_jobs), dim3(64), 0, s, d_gz.as<uint32_t>(), n_words, jobs, cells, sp, spill_next, out);
+            hipLaunchKernelGGL(decode_kernel<2048>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
         SY_HIP(hipGetLastError());
-    };
-    {
-        ScopedKernelTimer kt(ctx, "inflate_decode");
-        HostPhase hp(ctx, "inflate: decode");
-        // a candidate's region: REGION_RATIO cells per compressed byte up to the next candidate, + REGION_SLACK
-        std::vector<DecodeJob> jobs(K);
-        for (uint32_t i = 0; i < K; i++) {
-            const uint64_t b0 = cand[i] >> 3, b1 = i + 1 < K ? cand[i + 1] >> 3 : byte_end;
-            jobs[i].start_bit = cand[i];
-            jobs[i].region = (b0 - body0) * region_ratio + (uint64_t)i * REGION_SLACK;
-            jobs[i].cap = (uint32_t)std::min<uint64_t>(0xFFFFFF00u, (b1 - b0) * region_ratio + REGION_SLACK);
-            jobs[i].have_window = i != 0;
-        }
-        ctx->h2d(d_jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
-        launch_decode(d_jobs.as<DecodeJob>(), K, d_cells.as<uint16_t>(), spill, d_res.as<BlockResult>());
     }
-    ctx->d2h(res.data(), d_res.p, (size_t)K * sizeof(BlockResult));
-    if (getenv("SYLPH_HIP_INFLATE_STATS")) {
-        uint64_t sym = 0, far = 0, tb = 0, tt = 0, tmax = 0, cells_out = 0;
-        for (const BlockResult& r : res) { sym += r.stats[0]; far += r.stats[1]; tb += r.stats[2]; tt += r.stats[3]; tmax = std::max<uint64_t>(tmax, r.stats[3]); cells_out += r.n_out; }
-        uint64_t moved_n = 0, dry_n = 0;
-        for (const BlockResult& r : res) { moved_n += r.region >= spill_base; dry_n += (r.flags & 2) != 0; }
+
+    // ---- decode every candidate into its region: `ratio` cells per compressed byte up to the next candidate, + REGION_SLACK.  The ratio
+    // comes from the files' ISIZE where it can (bench.py's mate file: 5.3 -> 9: 7 GB of cells for a 1 Gbp pair instead of 12.7 — less
+    // to allocate, and less for the process to hand back when it ends)
+    void decode_candidates() {
+        // (SYLPH_HIP_INFLATE_REGION_RATIO: the tests' way to make every block outgrow its region)
+        const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
+        const uint64_t ratio = rr_env ? std::max(1, std::min(64, atoi(rr_env))) : region_ratio_from_isize(segs, REGION_RATIO);
+        cells = cells_layout(n - body0, K, ratio, REGION_SLACK, SPILL_SLOTS, SPILL_CELLS);
+        S.cells.reserve(cells.total * 2);
+        S.res.reserve((size_t)K * sizeof(BlockResult));
+        S.jobs.reserve((size_t)K * sizeof(DecodeJob));
+        SY_HIP(hipMemsetAsync(S.cnt.as<unsigned long long>() + 2, 0, 8, s));      // the spill arena's counter
+        res.resize(K);
+        {
+            ScopedKernelTimer kt(ctx, "inflate_decode");
+            HostPhase hp(ctx, "inflate: decode");
+            std::vector<DecodeJob> jobs(K);
+            for (uint32_t i = 0; i < K; i++) jobs[i] = decode_job(i, cand.data(), K, body0, n, ratio, REGION_SLACK);
+            ctx->h2d(S.jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
+            launch_decode(S.jobs.as<DecodeJob>(), K, S.cells.as<uint16_t>(), Spill{cells.spill_base, SPILL_SLOTS}, S.res.as<BlockResult>());
+        }
+        ctx->d2h(res.data(), S.res.p, (size_t)K * sizeof(BlockResult));
+        if (getenv("SYLPH_HIP_INFLATE_STATS")) print_stats();
+    }
+
+    void print_stats() const {
+        uint64_t sym = 0, far = 0, tb = 0, tt = 0, tmax = 0, cells_out = 0, moved_n = 0, dry_n = 0;
+        for (const BlockResult& r : res) {
+            sym += r.stats[0]; far += r.stats[1]; tb += r.stats[2]; tt += r.stats[3]; tmax = std::max<uint64_t>(tmax, r.stats[3]); cells_out += r.n_out;
+            moved_n += r.region >= cells.spill_base; dry_n += (r.flags & 2) != 0;
+        }
         fprintf(stderr, "[sylph_hip inflate] %llu candidates moved to the spill arena, %llu ran dry\n", (unsigned long long)moved_n, (unsigned long long)dry_n);
         fprintf(stderr, "[sylph_hip inflate] %u candidates: %llu symbol-loop turns, %llu copies from global memory, %llu cells; per wave: %.0f k-cycles mean (%.0f on headers + tables), %llu max\n",
                 K, (unsigned long long)sym, (unsigned long long)far, (unsigned long long)cells_out, (double)tt / K, (double)tb / K, (unsigned long long)tmax);
     }
-    // ---- the chain
-    std::vector<std::vector<uint8_t>> host_bytes;
-    Chain chain = chain_walk(segs, cand, res.data(), [&](size_t p, size_t* end, uint64_t* n_out) {
-        std::vector<uint8_t> o;
-        const size_t si = segs.find(p), gb = segs.base[si];
-        if (!zlib_member(segs.ptr[si], segs.base[si + 1] - gb, p - gb, end, o)) return false;
-        *end += gb;
-        *n_out = o.size();
-        if (!o.empty()) host_bytes.push_back(std::move(o));
-        return true;
-    });
-    if (!chain.why.empty()) throw FormatDecline{chain.why};
-    const uint32_t KB = (uint32_t)chain.blocks.size();
-    const uint32_t NM = (uint32_t)chain.members.size();
-    t->n_blocks = KB;
-    t->n_members = NM;
-    t->n_host_members = 0;
-    for (const Member& m : chain.members) t->n_host_members += m.on_host;
-    t->n = chain.total;
-    t->files.assign(n_files, {~0ull, 0});
-    for (const Member& m : chain.members) {                   // a file's text: from its first member's first byte to its last member's end
-        auto& f = t->files[m.file];
-        f.first = std::min<uint64_t>(f.first, m.out_begin);
-        f.second = std::max<uint64_t>(f.second, m.out_end);
+
+    // ---- the chain: which candidates are the stream, the members, every file's range in the text
+    void walk_chain() {
+        chain = chain_walk(segs, cand, res.data(), [&](size_t p, size_t* end, uint64_t* n_out) {
+            std::vector<uint8_t> o;
+            const size_t si = segs.find(p), gb = segs.base[si];
+            if (!zlib_member(segs.ptr[si], segs.base[si + 1] - gb, p - gb, end, o)) return false;
+            *end += gb;
+            *n_out = o.size();
+            if (!o.empty()) host_bytes.push_back(std::move(o));
+            return true;
+        });
+        if (!chain.why.empty()) throw FormatDecline{chain.why};
+        t->n_blocks = chain.blocks.size();
+        t->n_members = chain.members.size();
+        t->n_host_members = 0;
+        for (const Member& m : chain.members) t->n_host_members += m.on_host;
+        t->n = chain.total;
+        t->files.assign(segs.ptr.size(), {~0ull, 0});
+        for (const Member& m : chain.members) {                   // a file's text: from its first member's first byte to its last member's end
+            auto& f = t->files[m.file];
+            f.first = std::min<uint64_t>(f.first, m.out_begin);
+            f.second = std::max<uint64_t>(f.second, m.out_end);
+        }
+        for (auto& f : t->files) if (f.first == ~0ull) throw FormatDecline{"a file without a gzip member"};
     }
-    for (auto& f : t->files) if (f.first == ~0ull) throw FormatDecline{"a file without a gzip member"};
+
     // ---- blocks of the chain that outgrew their region (BlockResult::flags bit 1): once more, each into a region of exactly its size
-    Raw d_cells2;
-    std::vector<uint64_t> redo_region(KB, ~0ull);
-    {
-        std::vector<DecodeJob> jobs;
-        std::vector<uint32_t> which;
-        uint64_t at = 0;
-        for (uint32_t i = 0; i < KB; i++) {
-            const ChainBlock& cb = chain.blocks[i];
-            if (!(cb.flags & 2)) continue;
-            DecodeJob j;
-            j.start_bit = cand[cb.cand];
-            j.region = at;
-            j.cap = cb.n_out;
-            j.have_window = cb.cand != 0;
-            redo_region[i] = at;
-            at += ((uint64_t)cb.n_out + 63) & ~(uint64_t)63;       // (regions start 128-byte aligned: the ring leaves in 16-byte stores)
-            jobs.push_back(j);
-            which.push_back(i);
-        }
-        t->n_redone = jobs.size();
-        if (!jobs.empty()) {
-            ScopedKernelTimer kt(ctx, "inflate_decode");
-            HostPhase hp(ctx, "inflate: decode again");
-            Raw d_jobs2, d_res2;
-            d_cells2.alloc((at + 64) * 2);
-            d_jobs2.alloc(jobs.size() * sizeof(DecodeJob));
-            d_res2.alloc(jobs.size() * sizeof(BlockResult));
-            ctx->h2d(d_jobs2.p, jobs.data(), jobs.size() * sizeof(DecodeJob));
-            launch_decode(d_jobs2.as<DecodeJob>(), (uint32_t)jobs.size(), d_cells2.as<uint16_t>(), no_spill, d_res2.as<BlockResult>());
-            std::vector<BlockResult> res2(jobs.size());
-            ctx->d2h(res2.data(), d_res2.p, jobs.size() * sizeof(BlockResult));
-            for (size_t q = 0; q < jobs.size(); q++) {
-                const ChainBlock& cb = chain.blocks[which[q]];
-                const BlockResult& a = res[cb.cand];
-                const BlockResult& b2 = res2[q];
-                if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
-                    throw FormatDecline{"a block decoded a second time came out differently"};
-            }
+    void decode_outgrown() {
+        redo = redo_plan(chain.blocks, cand.data());
+        const size_t J = redo.jobs.size();
+        t->n_redone = J;
+        if (!J) return;
+        ScopedKernelTimer kt(ctx, "inflate_decode");
+        HostPhase hp(ctx, "inflate: decode again");
+        Raw d_jobs2, d_res2;
+        cells2.alloc((redo.cells + 64) * 2);
+        d_jobs2.alloc(J * sizeof(DecodeJob));
+        d_res2.alloc(J * sizeof(BlockResult));
+        ctx->h2d(d_jobs2.p, redo.jobs.data(), J * sizeof(DecodeJob));
+        launch_decode(d_jobs2.as<DecodeJob>(), (uint32_t)J, cells2.as<uint16_t>(), Spill{0, 0}, d_res2.as<BlockResult>());
+        std::vector<BlockResult> res2(J);
+        ctx->d2h(res2.data(), d_res2.p, J * sizeof(BlockResult));
+        for (size_t q = 0; q < J; q++) {
+            const BlockResult& a = res[chain.blocks[redo.which[q]].cand];
+            const BlockResult& b2 = res2[q];
+            if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
+                throw FormatDecline{"a block decoded a second time came out differently"};
         }
     }
-    // ---- the text
-    {
-        const hipError_t e = hipMalloc(&t->buf, chain.total + 512);
-        if (e != hipSuccess) { t->buf = nullptr; (void)hipGetLastError(); throw HipError{e, "hipMalloc (inflated text)", __FILE__, __LINE__}; }
-    }
-    uint8_t* text = (uint8_t*)t->buf + 256;
-    SY_HIP(hipMemsetAsync(t->buf, 0, 256, s));
-    SY_HIP(hipMemsetAsync(text + chain.total, 0, 256, s));
-    for (size_t i = 0; i < chain.host.size(); i++) ctx->h2d(text + chain.host[i].out_off, host_bytes[i].data(), host_bytes[i].size());
-    if (KB) {
+
+    // ---- the text: the host's pieces copied in; the windows resolved down the chain in groups; cells -> bytes
+    void write_text() {
+        const uint32_t KB = (uint32_t)chain.blocks.size();
+        text.grow(chain.total, 0, s);
+        SY_HIP(hipMemsetAsync(text.text() + chain.total, 0, 256, s));
+        for (size_t i = 0; i < chain.host.size(); i++) ctx->h2d(text.text() + chain.host[i].out_off, host_bytes[i].data(), host_bytes[i].size());
+        if (!KB) return;
         std::vector<PlanBlock> plan(KB);
         bool any_window = false;
         for (uint32_t i = 0; i < KB; i++) {
             const ChainBlock& cb = chain.blocks[i];
-            plan[i].cells = redo_region[i] != ~0ull ? d_cells2.as<uint16_t>() + redo_region[i] : d_cells.as<uint16_t>() + res[cb.cand].region;
+            plan[i].cells = redo.region[i] != ~0ull ? cells2.as<uint16_t>() + redo.region[i] : S.cells.as<uint16_t>() + res[cb.cand].region;
             plan[i].out_off = cb.out_off;
             plan[i].n_out = cb.n_out;
             plan[i].flags = cb.flags;
             any_window |= (cb.flags & 1) != 0;
         }
-        Raw &d_plan = S.plan, &d_sfn = S.sfn, &d_ffn = S.ffn, &d_rwin = S.rwin;
-        d_plan.reserve((size_t)KB * sizeof(PlanBlock));
-        ctx->h2d(d_plan.p, plan.data(), (size_t)KB * sizeof(PlanBlock));
-        uint32_t G = 1;
-        while ((uint64_t)G * G < KB) G++;
-        G = std::max(G, 8u);
-        const uint32_t NG = (KB + G - 1) / G;
+        S.plan.reserve((size_t)KB * sizeof(PlanBlock));
+        ctx->h2d(S.plan.p, plan.data(), (size_t)KB * sizeof(PlanBlock));
+        const uint32_t G = window_group(KB), NG = (KB + G - 1) / G;
         if (any_window) {
             ScopedKernelTimer kt(ctx, "inflate_windows");
             HostPhase hp(ctx, "inflate: windows");
-            d_sfn.reserve((size_t)KB * WINDOW * 2);
-            d_ffn.reserve((size_t)NG * WINDOW * 2);
-            d_rwin.reserve((size_t)NG * WINDOW);
+            S.sfn.reserve((size_t)KB * WINDOW * 2);
+            S.ffn.reserve((size_t)NG * WINDOW * 2);
+            S.rwin.reserve((size_t)NG * WINDOW);
             static std::once_flag once;
             std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
-            hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, d_plan.as<PlanBlock>(), KB, G, d_sfn.as<uint16_t>(), d_ffn.as<uint16_t>());
+            hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>(), KB, G, S.sfn.as<uint16_t>(), S.ffn.as<uint16_t>());
             SY_HIP(hipGetLastError());
-            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, d_ffn.as<uint16_t>(), NG, d_rwin.as<uint8_t>());
-            SY_HIP(hipGetLastError());
-        }
-        {
-            ScopedKernelTimer kt(ctx, "inflate_translate");
-            HostPhase hp(ctx, "inflate: translate");
-            hipLaunchKernelGGL(translate_kernel, dim3(KB), dim3(TR_TPB), 0, s, d_plan.as<PlanBlock>(), G, d_sfn.as<uint16_t>(), d_rwin.as<uint8_t>(), text);
+            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, S.ffn.as<uint16_t>(), NG, S.rwin.as<uint8_t>());
             SY_HIP(hipGetLastError());
         }
-        // ---- CRC-32 of every member
+        ScopedKernelTimer kt(ctx, "inflate_translate");
+        HostPhase hp(ctx, "inflate: translate");
+        hipLaunchKernelGGL(translate_kernel, dim3(KB), dim3(TR_TPB), 0, s, S.plan.as<PlanBlock>(), G, S.sfn.as<uint16_t>(), S.rwin.as<uint8_t>(), text.text());
+        SY_HIP(hipGetLastError());
+    }
+
+    // ---- CRC-32 of every member the device decoded, against its trailer (a chain without a block is zlib's alone, and checked)
+    void check_crcs() {
+        if (chain.blocks.empty()) return;
+        const uint32_t NM = (uint32_t)chain.members.size();
         std::vector<unsigned long long> m_end(NM);
         for (uint32_t i = 0; i < NM; i++) m_end[i] = chain.members[i].out_end;
         uint32_t x2n[64];
         crc_x2n_table(x2n);
-        Raw &d_mend = S.mend, &d_x2n = S.x2n, &d_raw = S.raw;
-        d_mend.reserve((size_t)NM * 8);
-        d_x2n.reserve(256);
-        d_raw.reserve((size_t)NM * 4);
+        S.mend.reserve((size_t)NM * 8);
+        S.x2n.reserve(256);
+        S.raw.reserve((size_t)NM * 4);
         std::vector<uint32_t> raw(NM);
         {
             ScopedKernelTimer kt(ctx, "inflate_crc");
             HostPhase hp(ctx, "inflate: crc");
-            ctx->h2d(d_mend.p, m_end.data(), (size_t)NM * 8);
-            ctx->h2d(d_x2n.p, x2n, 256);
-            SY_HIP(hipMemsetAsync(d_raw.p, 0, (size_t)NM * 4, s));
+            ctx->h2d(S.mend.p, m_end.data(), (size_t)NM * 8);
+            ctx->h2d(S.x2n.p, x2n, 256);
+            SY_HIP(hipMemsetAsync(S.raw.p, 0, (size_t)NM * 4, s));
             if (chain.total) {
                 const uint64_t waves = (chain.total + CRC_SPAN - 1) / CRC_SPAN;
-                hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text, chain.total, d_mend.as<unsigned long long>(), NM,
-                                   d_x2n.as<uint32_t>(), d_raw.as<uint32_t>());
+                hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text.text(), chain.total,
+                                   S.mend.as<unsigned long long>(), NM, S.x2n.as<uint32_t>(), S.raw.as<uint32_t>());
                 SY_HIP(hipGetLastError());
             }
         }
-        ctx->d2h(raw.data(), d_raw.p, (size_t)NM * 4);
+        ctx->d2h(raw.data(), S.raw.p, (size_t)NM * 4);
         for (uint32_t i = 0; i < NM; i++) {
             const Member& m = chain.members[i];
             if (m.on_host) continue;
@@ -1262,7 +1215,30 @@ void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_b
             }
         }
     }
-    SY_HIP(hipStreamSynchronize(s));      // the scratch is freed on the way out
+};
+
+void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_bytes, uint32_t n_files) {
+    sylph_ctx* ctx = t->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard dg(ctx->device);
+    Segments segs = segments_of(gzs, n_bytes, n_files);
+    for (uint32_t i = 0; i < n_files; i++)
+        if (!member_body(segs.ptr[i], (size_t)n_bytes[i], 0)) throw FormatDecline{"not a gzip file"};
+    if (segs.total() >= (3ull << 30)) throw FormatDecline{"3 GiB of gzip bytes or more: the host reader takes them"};
+    DeviceScratch& DS = device_scratch(ctx->device);
+    std::lock_guard<std::mutex> turn(DS.mu);                       // one inflate per device at a time: they share the scratch
+    // (on every way out — a decline included — the stream is idle before the next call may touch the scratch; destroyed before `turn`)
+    struct Done { InflateScratch& s; hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); if (s.bytes() > SCRATCH_KEEP) s.release(); } } done{DS.s, ctx->stream};
+    InflateCall c(t, DS.s, std::move(segs));
+    c.upload();
+    c.find_candidates();
+    c.decode_candidates();
+    c.walk_chain();
+    c.decode_outgrown();
+    c.write_text();
+    c.check_crcs();
+    t->buf = c.text.release();
+    SY_HIP(hipStreamSynchronize(ctx->stream));      // the scratch is freed on the way out
 }
 
 }  // namespace
@@ -1273,32 +1249,7 @@ using namespace sylph;
 extern "C" {
 
 int sylph_inflate_files(sylph_ctx* ctx, const void* const* gz, const uint64_t* n_bytes, uint32_t n_files, int mem, sylph_inflated** out) {
-    if (!ctx || !out || !gz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    for (uint32_t i = 0; i < n_files; i++) if (!gz[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_inflate: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
-    *out = nullptr;
-    ctx->refs.fetch_add(1);
-    sylph_inflated* t = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        t = new sylph_inflated();
-        t->ctx = ctx;
-        try { inflate_impl(t, gz, n_bytes, n_files); }
-        catch (const FormatDecline& e) { set_error("sylph_inflate: declined: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        {
-            std::lock_guard<std::mutex> lock(ctx->mu);
-            DeviceGuard dg(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-            if (t && t->buf) (void)hipFree(t->buf);
-            delete t;
-        }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = t;
-    return SYLPH_OK;
+    return decode_entry("sylph_inflate", false, ctx, gz, n_bytes, n_files, mem, out, inflate_impl);
 }
 
 int sylph_inflate(sylph_ctx* ctx, const void* gz, uint64_t n_bytes, int mem, sylph_inflated** out) {

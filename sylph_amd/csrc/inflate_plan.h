@@ -12,7 +12,9 @@
 //     are not on the chain were never block starts and are dropped with their output;
 //   * the windows are resolved down the chain in groups (inflate.hip) and the cells become bytes;
 //   * CRC-32 and ISIZE of every member are checked: the CRC of a member is put together from the CRCs of 1 KiB pieces computed
-//     anywhere on the device (crc32 is linear over GF(2): crc_shift below).
+//     anywhere on the device (crc32 is linear over GF(2): crc_shift, from stream_plan.h, which also holds the files of a call).
+// Where every candidate's cells go — its region and how much fits, the buffer's size, the packing of the blocks decoded a second time,
+// the window groups — is arithmetic at the end of this file (decode_job and its neighbours): inflate.hip only calls it.
 // Anything that does not add up — a chain that breaks, a block whose output did not fit its region, a CRC that differs — makes
 // the whole call decline (SYLPH_ERR_FORMAT) and the caller inflates the file with zlib as before: this road can make a file
 // faster, never different.
@@ -24,11 +26,7 @@
 #include <string>
 #include <vector>
 
-#if defined(__HIPCC__)
-#define SYLPH_HD __host__ __device__
-#else
-#define SYLPH_HD
-#endif
+#include "stream_plan.h"
 
 namespace sylph {
 namespace inflate_plan {
@@ -58,60 +56,19 @@ struct BlockResult {
                            // kilo-cycles spent on headers + tables, kilo-cycles in all
 };
 
-// ---- CRC-32 (reflected, polynomial 0xEDB88320) as polynomial arithmetic over GF(2) ----------------------------------------------
-// Bit 31 of a word is the coefficient of x^0 (zlib's convention in crc32.c: multmodp / x2nmodp).
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
-
-SYLPH_HD inline uint32_t crc_multmodp(uint32_t a, uint32_t b) {
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-// x2n[k] = x^(2^k) mod P, k = 0 .. 63 (filled by crc_x2n_table)
-inline void crc_x2n_table(uint32_t t[64]) {
-    uint32_t p = 1u << 30;                       // x^1
-    t[0] = p;
-    for (int k = 1; k < 64; k++) t[k] = p = crc_multmodp(p, p);
-}
-// x^(8 n) mod P
-SYLPH_HD inline uint32_t crc_x8n(const uint32_t* x2n, unsigned long long n_bytes) {
-    uint32_t p = 1u << 31;                       // x^0
-    unsigned k = 3;
-    while (n_bytes) {
-        if (n_bytes & 1) p = crc_multmodp(x2n[k & 63], p);
-        n_bytes >>= 1;
-        k++;
-    }
-    return p;
-}
-// The register of the CRC loop (no initial or final inversion) after n more zero bytes
-SYLPH_HD inline uint32_t crc_shift(const uint32_t* x2n, uint32_t crc, unsigned long long n_bytes) {
-    return n_bytes ? crc_multmodp(crc_x8n(x2n, n_bytes), crc) : crc;
-}
-// zlib's crc32() of a member from `raw` = XOR over its pieces of crc_shift(raw register of the piece started at 0, bytes behind the
-// piece in the member): the initial 0xFFFFFFFF travels through all n bytes, the final inversion is on top
-inline uint32_t crc_finish(const uint32_t* x2n, uint32_t raw, unsigned long long n_bytes) {
-    return raw ^ crc_shift(x2n, 0xFFFFFFFFu, n_bytes) ^ 0xFFFFFFFFu;
-}
-// byte-at-a-time table and the raw register update (host reference for the tests; the device builds its slicing tables from this)
-inline void crc_byte_table(uint32_t t[256]) {
-    for (uint32_t i = 0; i < 256; i++) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
-        t[i] = c;
-    }
-}
-inline uint32_t crc_raw(const uint32_t* t, uint32_t reg, const uint8_t* p, size_t n) {
-    for (size_t i = 0; i < n; i++) reg = t[(reg ^ p[i]) & 0xFF] ^ (reg >> 8);
-    return reg;
-}
+// ---- CRC-32 (reflected, polynomial 0xEDB88320): stream_plan.h's family in zlib's bit order --------------------------------------
+// zlib's crc32() of a member = crc_finish(XOR over its pieces of crc_shift(raw register of the piece started at 0, bytes behind the
+// piece in the member), the member's length); crc_byte_table / crc_raw: host reference for the tests (the device builds its slicing
+// tables from the same recurrence)
+using Crc = stream_plan::Crc32<true>;
+constexpr uint32_t CRC_POLY = Crc::POLY;
+SYLPH_HD inline uint32_t crc_multmodp(uint32_t a, uint32_t b) { return Crc::multmodp(a, b); }
+inline void crc_x2n_table(uint32_t t[64]) { Crc::x2n_table(t); }
+SYLPH_HD inline uint32_t crc_x8n(const uint32_t* x2n, unsigned long long n_bytes) { return Crc::x8n(x2n, n_bytes); }
+SYLPH_HD inline uint32_t crc_shift(const uint32_t* x2n, uint32_t crc, unsigned long long n_bytes) { return Crc::shift(x2n, crc, n_bytes); }
+inline uint32_t crc_finish(const uint32_t* x2n, uint32_t raw, unsigned long long n_bytes) { return Crc::finish(x2n, raw, n_bytes); }
+inline void crc_byte_table(uint32_t t[256]) { Crc::byte_table(t); }
+inline uint32_t crc_raw(const uint32_t* t, uint32_t reg, const uint8_t* p, size_t n) { return Crc::raw(t, reg, p, n); }
 
 // ---- gzip member header (RFC 1952) ----------------------------------------------------------------------------------------------
 // -> offset of the first deflate byte of the member at d[p..), or 0 when there is no well-formed header there
@@ -155,13 +112,8 @@ struct Chain {
 
 // The compressed bytes: one file, or several taken as ONE stream of gzip members (the two mates of a pair: a member never crosses from
 // one file into the next, so every header, trailer and small member is read inside one segment).
-struct Segments {
-    std::vector<const uint8_t*> ptr;
-    std::vector<size_t> base;                 // base[i] = offset of file i in the stream; base.back() = its total length
-    size_t total() const { return base.back(); }
-    size_t find(size_t pos) const { return (size_t)(std::upper_bound(base.begin(), base.end() - 1, pos) - base.begin()) - 1; }
-};
-inline Segments one_segment(const uint8_t* gz, size_t n) { return Segments{{gz}, {0, n}}; }
+using stream_plan::Segments;
+using stream_plan::one_segment;
 
 // cand_bits: sorted, unique candidate start bits (the first member's first block is among them whatever its type);
 // res[i]: the report of candidate i.
@@ -225,6 +177,69 @@ Chain chain_walk(const Segments& S, const std::vector<uint64_t>& cand_bits, cons
         // member — needletail (flate2 MultiGzDecoder) errors; either way not this road's business
         if (p < gb + gn && !member_body(gz, gn, p - gb)) { c.why = "trailing bytes behind the last member"; return c; }
     }
+}
+
+// ---- where the cells go ---------------------------------------------------------------------------------------------------------
+// one candidate for a wavefront: where its block starts, where its cells go (offset into the cells buffer) and how many fit
+struct DecodeJob { unsigned long long start_bit, region; uint32_t cap, have_window; };
+constexpr uint32_t MAX_BLOCK_CELLS = 0xFFFFFF00u;      // a block of more cells is not even countable (ST_OVERFLOW)
+
+// A single-member file says how well it deflates (ISIZE in its trailer): its blocks get 1.5 x that + 2 cells per compressed byte
+// instead of the flat ratio.  Several members (BGZF ends with an empty one), a wrapped ISIZE, a ratio outside [1.5, 40] in any
+// file: the flat ratio.  Every file holds a member (>= 18 bytes).
+inline uint64_t region_ratio_from_isize(const Segments& files, uint64_t flat) {
+    double worst = 0;
+    for (size_t i = 0; i + 1 < files.base.size(); i++) {
+        const uint64_t n_bytes = files.base[i + 1] - files.base[i];
+        const uint8_t* tr = files.ptr[i] + n_bytes - 4;
+        const double isize = (double)(tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24), r = isize / (double)n_bytes;
+        if (r < 1.5 || r > 40) return flat;
+        worst = std::max(worst, r);
+    }
+    return std::min<uint64_t>(flat, (uint64_t)(worst * 1.5) + 2);
+}
+// candidate i of K (cand: their sorted start bits; the first block's body starts at byte body0, the bytes end at byte_end): its
+// region lies `ratio` cells per compressed byte from the buffer's start + `slack` per candidate in front of it, and holds `ratio`
+// cells per byte up to the next candidate + `slack`
+inline DecodeJob decode_job(uint32_t i, const uint64_t* cand, uint32_t K, uint64_t body0, uint64_t byte_end, uint64_t ratio, uint64_t slack) {
+    const uint64_t b0 = cand[i] >> 3, b1 = i + 1 < K ? cand[i + 1] >> 3 : byte_end;
+    return DecodeJob{cand[i], (b0 - body0) * ratio + (uint64_t)i * slack, (uint32_t)std::min<uint64_t>(MAX_BLOCK_CELLS, (b1 - b0) * ratio + slack), i != 0};
+}
+// the cells buffer: the K candidates' regions, then (from a multiple of 64 cells) the spill arena's spill_slots regions of spill_cells
+struct CellsLayout { uint64_t n_cells, spill_base, total; };
+inline CellsLayout cells_layout(uint64_t span_bytes, uint32_t K, uint64_t ratio, uint64_t slack, uint64_t spill_slots, uint64_t spill_cells) {
+    CellsLayout l;
+    l.n_cells = span_bytes * ratio + (uint64_t)K * slack + 64;
+    l.spill_base = (l.n_cells + 63) & ~(uint64_t)63;
+    l.total = l.spill_base + spill_slots * spill_cells + 64;
+    return l;
+}
+// Blocks of the chain that outgrew their region (BlockResult::flags bit 1) are decoded once more, each into a region of exactly its
+// size in a buffer of their own: regions start at multiples of 64 cells (128 bytes: the ring leaves in 16-byte stores).
+struct RedoPlan {
+    std::vector<DecodeJob> jobs;
+    std::vector<uint32_t> which;          // jobs[q] is chain block which[q]
+    std::vector<uint64_t> region;         // per chain block: its region in that buffer, ~0 = it is not decoded again
+    uint64_t cells = 0;                   // the buffer's size (+ 64 of slack when allocated)
+};
+inline RedoPlan redo_plan(const std::vector<ChainBlock>& blocks, const uint64_t* cand) {
+    RedoPlan p;
+    p.region.assign(blocks.size(), ~0ull);
+    for (uint32_t i = 0; i < blocks.size(); i++) {
+        const ChainBlock& cb = blocks[i];
+        if (!(cb.flags & 2)) continue;
+        p.jobs.push_back(DecodeJob{cand[cb.cand], p.cells, cb.n_out, cb.cand != 0});
+        p.which.push_back(i);
+        p.region[i] = p.cells;
+        p.cells += ((uint64_t)cb.n_out + 63) & ~(uint64_t)63;
+    }
+    return p;
+}
+// windows are resolved in groups of G chain blocks: the smallest G with G * G >= KB, at least 8
+inline uint32_t window_group(uint32_t KB) {
+    uint32_t G = 1;
+    while ((uint64_t)G * G < KB) G++;
+    return std::max(G, 8u);
 }
 
 }  // namespace inflate_plan

@@ -107,3 +107,17 @@ def bucket_roads(hashes, c, target):
             per = np.bincount((bucket * 256 + sub)[of_cap], minlength=B * 256).reshape(B, 256).max(axis=1)
             fill = np.maximum(fill, per)
     return dict(B=B, composite=composite, n=n, bucket=bucket, fill=fill)
+
+
+def build_path(stem, deps, suffix=""):
+    """Where a test keeps what it compiles from `deps` (sources first, then the headers they include): a file in the temporary
+    directory named after the CONTENTS of deps, so that a binary left there by another commit's sources is never taken for this one's.
+    -> (path, whether it has to be built)"""
+    import hashlib
+    import tempfile
+    h = hashlib.sha256()
+    for p in deps:
+        with open(p, "rb") as f:
+            h.update(f.read())
+    out = os.path.join(tempfile.gettempdir(), f"{stem}_{os.getuid()}_{h.hexdigest()[:16]}{suffix}")
+    return out, not os.path.exists(out)

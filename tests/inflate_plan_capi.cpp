@@ -1,5 +1,5 @@
 // C wrapper around sylph_amd/csrc/inflate_plan.h for tests/test_inflate_plan.py (g++ -lz, no HIP): the very header inflate.hip includes
-// — CRC-32 assembled from shifted pieces, gzip member headers, the chain walk — driven by a plain CPU MODEL of what the device
+// — CRC-32 assembled from shifted pieces, gzip member headers, the chain walk, where every candidate's cells go — driven by a plain CPU MODEL of what the device
 // kernels report (every bit position tested for a dynamic block header with the same acceptance rule as scan1/scan2_kernel; each
 // candidate decoded without its window into 16-bit cells the way decode_kernel does, puff-style, one bit at a time; windows
 // resolved down the chain).  Test infrastructure: the product never runs this.
@@ -199,6 +199,40 @@ uint32_t ip_crc_shift(uint32_t reg, uint64_t n_bytes) {
     return crc_shift(x2n, reg, n_bytes);
 }
 
+// ---- where the cells go: inflate_plan.h's layout functions, as inflate.hip calls them
+uint64_t ip_region_ratio(const uint8_t* const* files, const uint64_t* sizes, uint32_t n_files, uint64_t flat) {
+    Segments S;
+    S.base.push_back(0);
+    for (uint32_t i = 0; i < n_files; i++) { S.ptr.push_back(files[i]); S.base.push_back(S.base.back() + sizes[i]); }
+    return region_ratio_from_isize(S, flat);
+}
+// out: start_bit, region, cap, have_window
+void ip_decode_job(uint32_t i, const uint64_t* cand, uint32_t K, uint64_t body0, uint64_t byte_end, uint64_t ratio, uint64_t slack, uint64_t* out) {
+    const DecodeJob j = decode_job(i, cand, K, body0, byte_end, ratio, slack);
+    out[0] = j.start_bit; out[1] = j.region; out[2] = j.cap; out[3] = j.have_window;
+}
+// out: n_cells, spill_base, total
+void ip_cells_layout(uint64_t span_bytes, uint32_t K, uint64_t ratio, uint64_t slack, uint64_t spill_slots, uint64_t spill_cells, uint64_t* out) {
+    const CellsLayout l = cells_layout(span_bytes, K, ratio, slack, spill_slots, spill_cells);
+    out[0] = l.n_cells; out[1] = l.spill_base; out[2] = l.total;
+}
+uint32_t ip_window_group(uint32_t KB) { return window_group(KB); }
+// chain blocks of n_out[i] cells with flags[i], block i being candidate i -> the redo buffer's cells; region[i] (~0: not decoded
+// again) and, for the blocks that are, cap[i] and start[i] (cand[i] = 100 + i)
+uint64_t ip_redo_plan(const uint32_t* n_out, const uint32_t* flags, uint32_t KB, uint64_t* region, uint32_t* cap, uint64_t* start, uint32_t* have_window) {
+    std::vector<ChainBlock> blocks(KB);
+    std::vector<uint64_t> cand(KB);
+    for (uint32_t i = 0; i < KB; i++) { blocks[i] = ChainBlock{i, 0, 0, n_out[i], flags[i]}; cand[i] = 100 + i; }
+    const RedoPlan p = redo_plan(blocks, cand.data());
+    for (uint32_t i = 0; i < KB; i++) region[i] = p.region[i];
+    for (size_t q = 0; q < p.jobs.size(); q++) {
+        const uint32_t i = p.which[q];
+        if (p.jobs[q].region != p.region[i]) return ~0ull;
+        cap[i] = p.jobs[q].cap; start[i] = p.jobs[q].start_bit; have_window[i] = p.jobs[q].have_window;
+    }
+    return p.cells;
+}
+
 // The whole road on the CPU.  -> bytes written to out (<= out_cap), or -1 with the reason in err.  info: members, chain blocks,
 // candidates, members inflated by zlib.  ratio / slack: the region rule of decode_kernel (cells per compressed byte up to the next
 // candidate + slack).
@@ -211,9 +245,9 @@ long long ip_model_inflate(const uint8_t* gz, uint64_t n, uint8_t* out, uint64_t
         if (p != (uint64_t)body0 * 8 && header_like(gz, (size_t)n, p)) cand.push_back(p);
     std::vector<BlockResult> res(cand.size());
     std::vector<std::vector<uint16_t>> cells(cand.size());
-    for (size_t k = 0; k < cand.size(); k++) {
-        const uint64_t next_byte = k + 1 < cand.size() ? cand[k + 1] >> 3 : n;
-        res[k] = model_decode(gz, (size_t)n, cand[k], k != 0, (size_t)((next_byte - (cand[k] >> 3)) * ratio + slack), cells[k]);
+    for (uint32_t k = 0; k < cand.size(); k++) {
+        const DecodeJob j = decode_job(k, cand.data(), (uint32_t)cand.size(), body0, n, ratio, slack);
+        res[k] = model_decode(gz, (size_t)n, j.start_bit, j.have_window != 0, j.cap, cells[k]);
     }
     std::vector<std::vector<uint8_t>> host_bytes;
     Chain c = chain_walk(one_segment(gz, (size_t)n), cand, res.data(), [&](size_t p, size_t* end, uint64_t* n_out) {
@@ -232,15 +266,16 @@ long long ip_model_inflate(const uint8_t* gz, uint64_t n, uint8_t* out, uint64_t
     });
     if (!c.why.empty()) { put_err(c.why, err, errn); return -1; }
     if (c.total > out_cap) { put_err("output buffer too small", err, errn); return -1; }
-    uint64_t redone = 0;
-    for (const ChainBlock& b : c.blocks) {                 // blocks of the chain that outgrew their region: again, with room for all of it
-        if (!(b.flags & 2)) continue;
-        const BlockResult again = model_decode(gz, (size_t)n, cand[b.cand], b.cand != 0, b.n_out, cells[b.cand]);
+    const RedoPlan redo = redo_plan(c.blocks, cand.data());  // blocks of the chain that outgrew their region: again, with room for all of it
+    const uint64_t redone = redo.jobs.size();
+    for (size_t q = 0; q < redo.jobs.size(); q++) {
+        const ChainBlock& b = c.blocks[redo.which[q]];
+        const DecodeJob& j = redo.jobs[q];
+        const BlockResult again = model_decode(gz, (size_t)n, j.start_bit, j.have_window != 0, j.cap, cells[b.cand]);
         if (again.status != res[b.cand].status || again.n_out != b.n_out || again.end_bit != res[b.cand].end_bit || (again.flags & 2)) {
             put_err("a block decoded a second time came out differently", err, errn);
             return -1;
         }
-        redone++;
     }
     for (size_t i = 0; i < c.host.size(); i++) memcpy(out + c.host[i].out_off, host_bytes[i].data(), host_bytes[i].size());
     std::vector<uint8_t> win(WINDOW, 0);

@@ -9,12 +9,11 @@ import ctypes as C
 import gzip
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from .helpers import golden_bytes
+from .helpers import build_path, golden_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -29,10 +28,9 @@ def host():
 
 @pytest.fixture(scope="module")
 def plan():
-    out = os.path.join(tempfile.gettempdir(), f"sylph_bunzip2_plan_{os.getuid()}.so")
     src = os.path.join(HERE, "bunzip2_plan_capi.cpp")
-    hdr = os.path.join(ROOT, "sylph_amd", "csrc", "bunzip2_plan.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    out, stale = build_path("sylph_bunzip2_plan", [src] + [os.path.join(ROOT, "sylph_amd", "csrc", h) for h in ("bunzip2_plan.h", "stream_plan.h")], ".so")
+    if stale:
         tmp = out + f".{os.getpid()}"
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src])
         os.replace(tmp, out)

@@ -6,23 +6,21 @@ import gzip
 import os
 import struct
 import subprocess
-import tempfile
 import zlib
 
 import numpy as np
 import pytest
 
-from .helpers import bgzf_compress, golden_bytes
+from .helpers import bgzf_compress, build_path, golden_bytes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def L():
-    out = os.path.join(tempfile.gettempdir(), f"sylph_inflate_plan_{os.getuid()}.so")
     src = os.path.join(HERE, "inflate_plan_capi.cpp")
-    hdr = os.path.join(HERE, "..", "sylph_amd", "csrc", "inflate_plan.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    out, stale = build_path("sylph_inflate_plan", [src] + [os.path.join(HERE, "..", "sylph_amd", "csrc", h) for h in ("inflate_plan.h", "stream_plan.h")], ".so")
+    if stale:
         tmp = out + f".{os.getpid()}"
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src, "-lz"])
         os.replace(tmp, out)
@@ -34,6 +32,15 @@ def L():
     lib.ip_crc_shift.argtypes = [C.c_uint32, C.c_uint64]
     lib.ip_model_inflate.restype = C.c_longlong
     lib.ip_model_inflate.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t]
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    lib.ip_region_ratio.restype = C.c_uint64
+    lib.ip_region_ratio.argtypes = [C.POINTER(C.c_char_p), u64p, C.c_uint32, C.c_uint64]
+    lib.ip_decode_job.argtypes = [C.c_uint32, u64p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+    lib.ip_cells_layout.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+    lib.ip_window_group.restype = C.c_uint32
+    lib.ip_window_group.argtypes = [C.c_uint32]
+    lib.ip_redo_plan.restype = C.c_uint64
+    lib.ip_redo_plan.argtypes = [u32p, u32p, C.c_uint32, u64p, u32p, u64p, u32p]
     return lib
 
 
@@ -158,3 +165,87 @@ def test_reference_fasta_gz_through_the_model(L):
     cut = want[:600000]
     got, why, info = model(L, gz_level(cut, 6), len(cut) + 16)
     assert why == "" and got == cut and info["blocks"] >= 3
+
+
+# ---- where the cells go (inflate_plan.h: region_ratio_from_isize, decode_job, cells_layout, redo_plan, window_group), against the rules
+# restated here
+
+SLACK, SPILL_SLOTS, SPILL_CELLS = 1024, 96, 1 << 20
+
+
+def decode_jobs(L, cand, body0, byte_end, ratio, slack=SLACK):
+    c = (C.c_uint64 * len(cand))(*cand)
+    out = (C.c_uint64 * 4)()
+    jobs = []
+    for i in range(len(cand)):
+        L.ip_decode_job(i, c, len(cand), body0, byte_end, ratio, slack, out)
+        jobs.append(tuple(out))
+    return jobs
+
+
+@pytest.mark.parametrize("ratio", [1, 9, 16])
+def test_candidate_regions_follow_the_rule_and_never_overlap(L, ratio):
+    body0, n = 10, 5000
+    cand = [8 * body0, 8 * body0 + 3, 8 * (body0 + 1), 8 * (n - 1) + 7]
+    jobs = decode_jobs(L, cand, body0, n, ratio)
+    for i, (start, region, cap, have_window) in enumerate(jobs):
+        b0, b1 = cand[i] // 8, (cand[i + 1] // 8 if i + 1 < len(cand) else n)
+        assert start == cand[i] and have_window == (i != 0)
+        assert region == (b0 - body0) * ratio + i * SLACK
+        assert cap == min(0xFFFFFF00, (b1 - b0) * ratio + SLACK)
+    for (_, region, cap, _), (_, next_region, _, _) in zip(jobs, jobs[1:]):
+        assert region + cap <= next_region
+    out = (C.c_uint64 * 3)()
+    L.ip_cells_layout(n - body0, len(cand), ratio, SLACK, SPILL_SLOTS, SPILL_CELLS, out)
+    n_cells, spill_base, total = out
+    assert n_cells == (n - body0) * ratio + len(cand) * SLACK + 64 and jobs[-1][1] + jobs[-1][2] <= n_cells
+    assert spill_base == (n_cells + 63) // 64 * 64 and total == spill_base + SPILL_SLOTS * SPILL_CELLS + 64
+
+
+def test_a_region_holds_no_more_cells_than_a_block_may_have(L):
+    body0 = 10
+    cand = [8 * body0, 8 * (body0 + (1 << 28))]
+    jobs = decode_jobs(L, cand, body0, body0 + (1 << 28) + 100, 16)
+    assert (1 << 28) * 16 + SLACK > 0xFFFFFF00 and jobs[0][2] == 0xFFFFFF00
+    assert jobs[1][1] == (1 << 28) * 16 + SLACK and jobs[1][2] == 100 * 16 + SLACK
+
+
+def region_ratio(L, files, flat):
+    ptrs = (C.c_char_p * len(files))(*files)
+    sizes = (C.c_uint64 * len(files))(*[len(f) for f in files])
+    return L.ip_region_ratio(ptrs, sizes, len(files), flat)
+
+
+def test_region_ratio_from_isize(L):
+    def file_of(n_bytes, isize):
+        return b"\x1f\x8b\x08" + b"\xAA" * (n_bytes - 7) + struct.pack("<I", isize)
+    for flat in (16, 100):
+        for isize, want in ((1490, flat), (1500, 4), (5300, 9), (40000, 62), (40010, flat)):       # r = 1.49, 1.5, 5.3, 40, 40.01 of 1000 bytes
+            r = isize / 1000
+            assert want == (flat if r < 1.5 or r > 40 else int(r * 1.5) + 2)
+            assert region_ratio(L, [file_of(1000, isize)], flat) == min(flat, want), (flat, isize)
+        assert region_ratio(L, [file_of(1000, 5300), file_of(500, 4000)], flat) == min(flat, 14)    # the worst file: r = 8
+        assert region_ratio(L, [file_of(1000, 5300), file_of(1000, 1000)], flat) == flat            # one file out of range
+        assert region_ratio(L, [file_of(1000, 50000), file_of(1000, 5300)], flat) == flat
+
+
+def test_window_group(L):
+    for KB, want in ((1, 8), (63, 8), (64, 8), (65, 9), (10000, 100)):
+        G = L.ip_window_group(KB)
+        assert G == want and G >= 8 and G * G >= KB and (G == 8 or (G - 1) * (G - 1) < KB)
+
+
+def test_blocks_decoded_again_are_packed_at_multiples_of_64_cells(L):
+    n_out = [1, 5000, 63, 64, 7, 65, 1]
+    flags = [2, 1, 2, 3, 0, 2, 2]
+    KB = len(n_out)
+    region, cap, start, win = (C.c_uint64 * KB)(), (C.c_uint32 * KB)(), (C.c_uint64 * KB)(), (C.c_uint32 * KB)()
+    cells = L.ip_redo_plan((C.c_uint32 * KB)(*n_out), (C.c_uint32 * KB)(*flags), KB, region, cap, start, win)
+    at = 0
+    for i in range(KB):
+        if not flags[i] & 2:
+            assert region[i] == 0xFFFFFFFFFFFFFFFF
+            continue
+        assert region[i] == at and at % 64 == 0 and cap[i] == n_out[i] and start[i] == 100 + i and win[i] == (i != 0)
+        at += (n_out[i] + 63) // 64 * 64
+    assert cells == at == 64 + 64 + 64 + 128 + 64
