@@ -289,5 +289,6 @@ void exclusive_sum_u64(sylph_ctx* ctx, const uint64_t* in, uint64_t* out, size_t
 void inclusive_max_u32(sylph_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n);
 
 inline int bit_length(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
+inline uint32_t grid_for64(uint64_t n, uint32_t tpb = 256) { return (uint32_t)((n + tpb - 1) / tpb); }   // workgroups of tpb lanes for n items
 
 }  // namespace sylph

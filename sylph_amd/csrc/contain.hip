@@ -4,16 +4,9 @@
 // probes per sample at GTDB-R220 scale.  Here the database lives in HBM as an inverted index, k-mer -> genomes, and the
 // (much smaller, already sorted) sample tables are streamed against it: O(sample) work per sample instead of O(database).
 //
-// Index layout ("line index", contain_index.h): the k-mer space [base, max_kmer] is cut into n_buckets equal ranges of `div`
-// consecutive values, about 3 postings per bucket, and every bucket owns ONE 64-byte line of 8 slots — the HBM access
-// granule — so a probe is exactly one line read:
-//     slot = ((kmer - base) % div) << (gb + 1)  |  flag << gb  |  genome id        (gb = bit length of the genome count)
-// The bucket number fixes the high part of the k-mer, the slot keeps only the remainder (the 8 + 4 bytes of a
-// {k-mer, genome} posting in two arrays become 8 bytes in one), and the genome id rides with the key.  Unused slots are
-// all-ones.  A bucket with more than 8 postings (a k-mer shared by many genomes) keeps its first 7 in the line and puts a
-// descriptor (flag = 1, remainder field = start) in slot 7 that points at the rest in an overflow array: a run sorted by
-// (remainder, genome), closed by an all-ones slot.  Round 1 kept db_kmer[] u64 + db_gid[] u32 + bucket_start[] u32 and
-// touched three to four lines per probe (180 B fetched per probe, measured); this is 64 B.
+// Index layout: the "line index" (contain_index.h, built by line_index.hip, arithmetic in index_plan.h) — every bucket of the k-mer
+// space owns ONE 64-byte line of 8 slots, the HBM access granule, so a probe is exactly one line read; crowded buckets continue in
+// an overflow run.
 //
 // Hits are (row = sample * G + genome, count) keys, radix-sorted: that yields contain_count[sample][genome] and every
 // coverage vector already in the ascending order the reference sorts it into (contain.rs:661).  A batch of S samples is ONE
@@ -31,141 +24,6 @@
 
 namespace sylph {
 namespace {
-
-// gid[i] = genome of posting i: one workgroup per genome streams its id over the genome's range
-__global__ __launch_bounds__(256) void fill_gid_kernel(const uint64_t* __restrict__ genome_off, uint64_t n_genomes,
-                                                       uint32_t* __restrict__ gid) {
-    for (uint64_t g = blockIdx.x; g < n_genomes; g += gridDim.x) {
-        const uint64_t b = genome_off[g], e = genome_off[g + 1];
-        for (uint64_t i = b + threadIdx.x; i < e; i += blockDim.x) gid[i] = (uint32_t)g;
-    }
-}
-
-// glen[g] = number of k-mers of genome g (the WHOLE genome, also on a k-mer-range shard: contain.rs:627 tests
-// genome_kmers.len()); *min_len = smallest of them
-__global__ __launch_bounds__(256) void genome_len_kernel(const uint64_t* __restrict__ genome_off, uint64_t n_genomes,
-                                                         uint32_t* __restrict__ glen, uint32_t* __restrict__ min_len) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_genomes) return;
-    const uint32_t l = (uint32_t)(genome_off[g + 1] - genome_off[g]);
-    glen[g] = l;
-    atomicMin(min_len, l);
-}
-
-// stat[0] = largest k-mer inside [lo, hi), stat[1] = number of k-mers inside [lo, hi)      (hi == 0: no upper bound)
-__device__ __forceinline__ bool in_range(uint64_t k, uint64_t lo, uint64_t hi) { return k >= lo && (hi == 0 || k < hi); }
-__global__ __launch_bounds__(256) void range_stats_kernel(const uint64_t* __restrict__ kmers, uint64_t n, uint64_t lo, uint64_t hi,
-                                                          unsigned long long* __restrict__ stat) {
-    unsigned long long mx = 0, cnt = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t k = kmers[i];
-        if (in_range(k, lo, hi)) { mx = max(mx, (unsigned long long)k); cnt++; }
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        mx = max(mx, (unsigned long long)__shfl_xor(mx, d));
-        cnt += (unsigned long long)__shfl_xor(cnt, d);
-    }
-    if ((threadIdx.x & 63) == 0 && cnt) { atomicMax(&stat[0], mx); atomicAdd(&stat[1], cnt); }
-}
-
-// ---- stable compaction of the postings whose k-mer falls into [lo, hi): counts per workgroup, scan, scatter -------------
-constexpr int FILT_TPB = 256, FILT_ITEMS = 8, FILT_TILE = FILT_TPB * FILT_ITEMS;
-
-__global__ __launch_bounds__(FILT_TPB) void filter_count_kernel(const uint64_t* __restrict__ kmers, uint64_t n, uint64_t lo, uint64_t hi,
-                                                                uint32_t* __restrict__ wg_count) {
-    __shared__ uint32_t s_cnt;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * FILT_TILE;
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < FILT_ITEMS; j++) {
-        const uint64_t i = base + (uint64_t)j * FILT_TPB + threadIdx.x;
-        if (i < n) c += in_range(kmers[i], lo, hi) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0) atomicAdd(&s_cnt, c);
-    __syncthreads();
-    if (threadIdx.x == 0) wg_count[blockIdx.x] = s_cnt;
-}
-
-__global__ __launch_bounds__(FILT_TPB) void filter_scatter_kernel(const uint64_t* __restrict__ kmers, const uint32_t* __restrict__ gid,
-                                                                  uint64_t n, uint64_t lo, uint64_t hi, const uint32_t* __restrict__ wg_off,
-                                                                  uint64_t* __restrict__ out_k, uint32_t* __restrict__ out_g) {
-    __shared__ uint32_t s_wave[FILT_TPB / 64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * FILT_TILE;
-    uint32_t run = wg_off[blockIdx.x];
-    for (int j = 0; j < FILT_ITEMS; j++) {              // rows of 256 consecutive postings: the order of i is preserved
-        const uint64_t i = base + (uint64_t)j * FILT_TPB + threadIdx.x;
-        uint64_t k = 0;
-        bool in = false;
-        if (i < n) { k = kmers[i]; in = in_range(k, lo, hi); }
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(m);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < FILT_TPB / 64; w++) { const uint32_t t = s_wave[w]; if ((uint32_t)w < wave) before += t; total += t; }
-        if (in) {
-            const uint32_t o = run + before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            out_k[o] = k;
-            out_g[o] = gid[i];
-        }
-        run += total;
-        __syncthreads();
-    }
-}
-
-// bfirst[b - b0] = first sorted posting whose bucket ((k - base) / div) is >= b, for b in [b0, b1]
-__global__ __launch_bounds__(256) void bucket_first_kernel(const uint64_t* __restrict__ keys, uint32_t m, uint64_t base, uint64_t div,
-                                                           uint32_t b0, uint32_t b1, uint32_t* __restrict__ bfirst) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > m) return;
-    const uint64_t lo = (i == 0) ? (uint64_t)b0 : (keys[i - 1] - base) / div + 1;   // first bucket not yet started
-    const uint64_t hi = (i == m) ? (uint64_t)b1 : (keys[i] - base) / div;          // last bucket that starts at i
-    for (uint64_t b = lo; b <= hi && b <= b1; b++) bfirst[b - b0] = i;
-}
-
-// overflow slots a bucket needs: its postings from the 8th on, the 8th itself (slot 7 becomes the descriptor) and the
-// closing sentinel
-__global__ __launch_bounds__(256) void ovf_need_kernel(const uint32_t* __restrict__ bfirst, uint32_t nb, uint32_t* __restrict__ need) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b > nb) return;
-    if (b == nb) { need[b] = 0; return; }
-    const uint32_t c = bfirst[b + 1] - bfirst[b];
-    need[b] = c > LINE_SLOTS ? (c - (LINE_SLOTS - 1)) + 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void write_lines_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ gids,
-                                                          const uint32_t* __restrict__ bfirst, const uint32_t* __restrict__ ovf_off,
-                                                          uint32_t b0, uint32_t nb, uint64_t base, uint64_t div, int gshift,
-                                                          uint64_t ovf_base, uint64_t* __restrict__ lines, uint64_t* __restrict__ ovf) {
-    const uint32_t bi = blockIdx.x * blockDim.x + threadIdx.x;
-    if (bi >= nb) return;
-    const uint64_t b = (uint64_t)b0 + bi;
-    const uint32_t first = bfirst[bi], c = bfirst[bi + 1] - first;
-    const uint64_t kbase = base + b * div;
-    auto slot_of = [&](uint32_t j) { return ((keys[first + j] - kbase) << gshift) | (uint64_t)gids[first + j]; };
-    uint64_t s[LINE_SLOTS];
-    const uint32_t inl = c > LINE_SLOTS ? LINE_SLOTS - 1 : c;
-#pragma unroll
-    for (int j = 0; j < LINE_SLOTS; j++) s[j] = (uint32_t)j < inl ? slot_of(j) : SLOT_EMPTY;
-    if (c > LINE_SLOTS) {
-        const uint64_t start = ovf_base + ovf_off[bi];
-        const uint64_t run = c - (LINE_SLOTS - 1), gmask = (1ull << (gshift - 1)) - 1;
-        s[LINE_SLOTS - 1] = (start << gshift) | (1ull << (gshift - 1)) | (run < gmask ? run : gmask);   // descriptor: flag + run length
-        uint64_t* o = ovf + start;
-        for (uint32_t j = LINE_SLOTS - 1; j < c; j++) *o++ = slot_of(j);
-        *o = SLOT_EMPTY;
-    }
-    uint4* lp = reinterpret_cast<uint4*>(lines + b * LINE_SLOTS);
-#pragma unroll
-    for (int t = 0; t < LINE_QUADS; t++)
-        lp[t] = make_uint4((uint32_t)s[2 * t], (uint32_t)(s[2 * t] >> 32), (uint32_t)s[2 * t + 1], (uint32_t)(s[2 * t + 1] >> 32));
-}
 
 // ---- probe -----------------------------------------------------------------------------------------------------------
 // One lane per sample k-mer, persistent workgroups striding over 256-k-mer chunks of the concatenated batch.  Hits are
@@ -228,19 +86,12 @@ __device__ __forceinline__ void probe_long_run(HitStage& st, const LineView& v, 
                                                const uint32_t* __restrict__ glen, double min_number_kmers, int check_len,
                                                uint64_t* __restrict__ hits, uint32_t hit_cap, uint32_t* __restrict__ hit_count) {
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t flag = 1ull << (v.gshift - 1), gmask = flag - 1;
-    // one step: 64 entries from `base`; -> this lane's entry matches; *ended: the relevant part of the run ends inside the step
+    // one step: 64 entries from `base`; -> this lane's entry matches and its genome is long enough; ended: the run ends inside the step
     auto step = [&](uint64_t base, uint32_t& g, bool& ended) {
-        const uint64_t idx = base + lane;
-        const uint64_t y = idx < v.n_ovf ? v.ovf[idx] : SLOT_EMPTY;
-        const uint64_t r = y >> v.gshift;
-        const unsigned long long stop = __ballot(y == SLOT_EMPTY || r > rem);          // the run is sorted by (remainder, genome)
-        const uint32_t first_stop = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u;
-        g = (uint32_t)(y & gmask);
-        ended = stop != 0;
-        bool match = lane < first_stop && r == rem;
-        if (match && check_len && (double)glen[g] < min_number_kmers) match = false;   // contain.rs:627
-        return match;
+        const LongRunStep r = long_run_step(v, base, rem);
+        g = r.g;
+        ended = r.ended;
+        return r.match && !(check_len && (double)glen[g] < min_number_kmers);          // contain.rs:627
     };
     // room for `total` hits: in the workgroup's stage as far as it reaches (ONE LDS atomic; the stage is flushed with one
     // global atomic per ~2048 hits), the rest straight in the hit array (one global atomic — a single word sustains ~90/us)
@@ -261,7 +112,7 @@ __device__ __forceinline__ void probe_long_run(HitStage& st, const LineView& v, 
     auto put = [&](bool match, unsigned long long mm, uint32_t g, uint32_t at) {   // at: matches of the run before this step
         if (!match) return;
         const uint32_t p = at + (uint32_t)__popcll(mm & ((1ull << lane) - 1ull));
-        const uint64_t hit = ((row0 + g) << 32) | cnt;
+        const uint64_t hit = index_plan::hit_key(row0 + g, cnt);
         if (p < n_stage) st.stage[stage_at + p] = hit;
         else { const uint32_t o = global_at + (p - n_stage); if (o < hit_cap) hits[o] = hit; }
     };
@@ -333,15 +184,11 @@ __global__ __launch_bounds__(PROBE_TPB) void probe_kernel(const SampleRef* __res
             const uint32_t c_e = cnt[e];
             line_scan(v, lf[e], [&](uint32_t g) {
                 if (check_len && (double)glen[g] < min_number_kmers) return;     // contain.rs:627
-                hit_stage_push(st, ((row0 + g) << 32) | c_e, hits, hit_cap, hit_count);
+                hit_stage_push(st, index_plan::hit_key(row0 + g, c_e), hits, hit_cap, hit_count);
             }, &long_start, &long_rem);
-            // long overflow runs, one after the other, by the whole wavefront (uniform loop: the ballot is the same in every lane)
-            for (unsigned long long todo = __ballot(long_start != ~0ull); todo; todo &= todo - 1) {
-                const int src = __ffsll((long long)todo) - 1;
-                const uint64_t rs = ((uint64_t)(uint32_t)__shfl((int)(long_start >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)long_start, src);
-                const uint64_t rm = ((uint64_t)(uint32_t)__shfl((int)(long_rem >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)long_rem, src);
+            for_each_long_run(long_start, long_rem, [&](int src, uint64_t rs, uint64_t rm) {   // by the whole wavefront
                 probe_long_run(st, v, rs, rm, row0, (uint32_t)__shfl((int)c_e, src), glen, min_number_kmers, check_len, hits, hit_cap, hit_count);
-            }
+            });
         }
         hit_stage_flush(st, chunk + gridDim.x >= n_chunks, hits, hit_cap, hit_count);
     }
@@ -352,24 +199,16 @@ __global__ __launch_bounds__(PROBE_TPB) void probe_kernel(const SampleRef* __res
 // hold it in genome_kmers or in pseudotax_tracked_nonused_kmers; ties go to the genome that comes first in the passing
 // list (the reference replaces only on strictly greater ANI, :417).  For every passing genome, sample k-mers of its
 // genome_kmers that it does not own count as kmers_lost, the others yield (genome, count) hits as in the first pass.
+//
 // every matching posting of a long overflow run, 64 entries per step, for the whole wavefront (same arguments in every lane):
 // f(genome id) is called by the lane that holds the match
 template <class F>
 __device__ __forceinline__ void long_run_for_each(const LineView& v, uint64_t start, uint64_t rem, F&& f) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t gmask = (1ull << (v.gshift - 1)) - 1;
     for (uint64_t base = start;; base += 64) {
-        const uint64_t idx = base + lane;
-        const uint64_t y = idx < v.n_ovf ? v.ovf[idx] : SLOT_EMPTY;
-        const uint64_t r = y >> v.gshift;
-        const unsigned long long stop = __ballot(y == SLOT_EMPTY || r > rem);              // the run is sorted by (remainder, genome)
-        const uint32_t first_stop = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u;
-        if (lane < first_stop && r == rem) f((uint32_t)(y & gmask));
-        if (stop) break;
+        const LongRunStep r = long_run_step(v, base, rem);
+        if (r.match) f(r.g);
+        if (r.ended) break;
     }
-}
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t x, int src) {
-    return ((uint64_t)(uint32_t)__shfl((int)(x >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)x, src);
 }
 
 __global__ __launch_bounds__(PROBE_TPB) void reassign_kernel(const uint64_t* __restrict__ s_kmers, const uint32_t* __restrict__ s_counts,
@@ -400,11 +239,10 @@ __global__ __launch_bounds__(PROBE_TPB) void reassign_kernel(const uint64_t* __r
         // pass begins.
         uint64_t ls = ~0ull, lr = 0;
         if (cnt != 0) for_each_posting(kept, km, [&](uint32_t g) { n_kept++; consider(g, best_ani, best_rank); }, &ls, &lr);
-        for (unsigned long long todo = __ballot(ls != ~0ull); todo; todo &= todo - 1) {
-            const int src = __ffsll((long long)todo) - 1;
+        for_each_long_run(ls, lr, [&](int src, uint64_t rs, uint64_t rm) {
             uint32_t c_l = 0, r_l = 0xFFFFFFFFu;
             double a_l = -1.0;
-            long_run_for_each(kept, shfl_u64(ls, src), shfl_u64(lr, src), [&](uint32_t g) { c_l++; consider(g, a_l, r_l); });
+            long_run_for_each(kept, rs, rm, [&](uint32_t g) { c_l++; consider(g, a_l, r_l); });
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) {
                 const uint32_t c_o = (uint32_t)__shfl_xor((int)c_l, d), r_o = (uint32_t)__shfl_xor((int)r_l, d);
@@ -416,14 +254,13 @@ __global__ __launch_bounds__(PROBE_TPB) void reassign_kernel(const uint64_t* __r
                 n_kept += c_l;
                 if (a_l > best_ani || (a_l == best_ani && r_l < best_rank)) { best_ani = a_l; best_rank = r_l; }
             }
-        }
+        });
         uint64_t lts = ~0ull, ltr = 0;
         if (n_kept && have_tracked) for_each_posting(tracked, km, [&](uint32_t g) { consider(g, best_ani, best_rank); }, &lts, &ltr);
-        for (unsigned long long todo = __ballot(lts != ~0ull); todo; todo &= todo - 1) {
-            const int src = __ffsll((long long)todo) - 1;
+        for_each_long_run(lts, ltr, [&](int src, uint64_t rs, uint64_t rm) {
             uint32_t r_l = 0xFFFFFFFFu;
             double a_l = -1.0;
-            long_run_for_each(tracked, shfl_u64(lts, src), shfl_u64(ltr, src), [&](uint32_t g) { consider(g, a_l, r_l); });
+            long_run_for_each(tracked, rs, rm, [&](uint32_t g) { consider(g, a_l, r_l); });
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) {
                 const uint32_t r_o = (uint32_t)__shfl_xor((int)r_l, d);
@@ -431,180 +268,55 @@ __global__ __launch_bounds__(PROBE_TPB) void reassign_kernel(const uint64_t* __r
                 if (a_o > a_l || (a_o == a_l && r_o < r_l)) { a_l = a_o; r_l = r_o; }
             }
             if (lane == src && (a_l > best_ani || (a_l == best_ani && r_l < best_rank))) { best_ani = a_l; best_rank = r_l; }
-        }
+        });
         auto settle = [&](uint32_t g, uint32_t winner, uint32_t c) {
             const uint32_t r = rank[g];
             if (r == 0xFFFFFFFFu) return;                                            // not in remaining_genomes
             if (r != winner) { atomicAdd(&lost[g], 1u); return; }                    // contain.rs:639-642
-            hit_stage_push(st, ((uint64_t)g << 32) | c, hits, hit_cap, hit_count);
+            hit_stage_push(st, index_plan::hit_key(g, c), hits, hit_cap, hit_count);
         };
         uint64_t ls3 = ~0ull, lr3 = 0;
         if (n_kept) for_each_posting(kept, km, [&](uint32_t g) { settle(g, best_rank, cnt); }, &ls3, &lr3);
-        for (unsigned long long todo = __ballot(ls3 != ~0ull); todo; todo &= todo - 1) {
-            const int src = __ffsll((long long)todo) - 1;
+        for_each_long_run(ls3, lr3, [&](int src, uint64_t rs, uint64_t rm) {
             const uint32_t winner = (uint32_t)__shfl((int)best_rank, src), c_s = (uint32_t)__shfl((int)cnt, src);
-            long_run_for_each(kept, shfl_u64(ls3, src), shfl_u64(lr3, src), [&](uint32_t g) { settle(g, winner, c_s); });
-        }
+            long_run_for_each(kept, rs, rm, [&](uint32_t g) { settle(g, winner, c_s); });
+        });
         hit_stage_flush(st, chunk + gridDim.x >= n_chunks, hits, hit_cap, hit_count);
     }
 }
 
-// cov_off[r] = first sorted hit with row >= r; covs[i] = low 32 bits of hit i
-__global__ __launch_bounds__(256) void hit_offsets_kernel(const uint64_t* __restrict__ hits, uint32_t n_hits, uint32_t n_rows,
+// Sorted hit keys of type K = (row << shift) | count -> cov_off[r] = first hit with row >= r, contain_count[r] = hits of row r.
+// 64-bit keys have shift 32; compact 32-bit keys (index_plan::compact_key) have shift cb, the bit length of the largest count:
+// the radix sort of the hit list then moves 4-byte keys through 3-4 passes instead of 8-byte keys through 8.
+template <class K>
+__global__ __launch_bounds__(256) void hit_offsets_kernel(const K* __restrict__ keys, uint32_t n_hits, uint32_t n_rows, int shift,
                                                           uint64_t* __restrict__ cov_off, uint32_t* __restrict__ contain_count) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g > n_rows) return;
-    auto lower = [&](uint64_t key) {
+    auto lower = [&](uint64_t key) {   // first hit whose key is >= key
         uint32_t lo = 0, hi = n_hits;
         while (lo < hi) {
             const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (hits[mid] < key) lo = mid + 1; else hi = mid;
+            if ((uint64_t)keys[mid] < key) lo = mid + 1; else hi = mid;
         }
         return lo;
     };
-    const uint32_t a = lower((uint64_t)g << 32);
+    const uint32_t a = lower((uint64_t)g << shift);
     cov_off[g] = a;
-    if (g < n_rows) contain_count[g] = lower(((uint64_t)g + 1) << 32) - a;
+    if (g < n_rows) contain_count[g] = lower(((uint64_t)g + 1) << shift) - a;
 }
-
-// Compact hit keys: (row << 32 | count) -> 32-bit (row << cb | count) with cb = bit_length(max count), whenever
-// bit_length(rows) + cb <= 32: the radix sort of the hit list then moves 4-byte keys through 3-4 passes instead of 8-byte
-// keys through 8.  Otherwise the 64-bit keys are sorted as they are.
 __global__ __launch_bounds__(256) void pack_hits32_kernel(const uint64_t* __restrict__ hits, uint32_t n, int cb, uint32_t* __restrict__ k32) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const uint64_t h = hits[i]; k32[i] = ((uint32_t)(h >> 32) << cb) | (uint32_t)h; }
 }
-template <class T>
-__global__ __launch_bounds__(256) void narrow32_kernel(const uint32_t* __restrict__ k32, uint32_t n, int cb, T* __restrict__ covs) {
+// covs[i] = the count of sorted key i (its low `shift` bits), as T
+template <class K, class T>
+__global__ __launch_bounds__(256) void narrow_kernel(const K* __restrict__ keys, uint32_t n, int shift, T* __restrict__ covs) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) covs[i] = (T)(k32[i] & ((1u << cb) - 1u));
+    if (i < n) covs[i] = (T)(keys[i] & (((K)1 << shift) - 1));
 }
-__global__ __launch_bounds__(256) void hit_offsets32_kernel(const uint32_t* __restrict__ k32, uint32_t n_hits, uint32_t n_rows, int cb,
-                                                            uint64_t* __restrict__ cov_off, uint32_t* __restrict__ contain_count) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > n_rows) return;
-    auto lower = [&](uint64_t key) {   // first hit whose (row << cb | count) >= key
-        uint32_t lo = 0, hi = n_hits;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if ((uint64_t)k32[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        return lo;
-    };
-    const uint32_t a = lower((uint64_t)g << cb);
-    cov_off[g] = a;
-    if (g < n_rows) contain_count[g] = lower(((uint64_t)g + 1) << cb) - a;
-}
-__global__ __launch_bounds__(256) void narrow_kernel(const uint64_t* __restrict__ hits, uint32_t n, uint32_t* __restrict__ covs) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) covs[i] = (uint32_t)hits[i];
-}
-
-uint32_t grid_for64(uint64_t n, uint32_t tpb = 256) { return (uint32_t)((n + tpb - 1) / tpb); }
 
 }  // namespace
-
-// ---- index build -------------------------------------------------------------------------------------------------------
-// Builds the line index over the postings of genome-major device arrays whose k-mer lies in [kmer_lo, kmer_hi) (kmer_hi == 0:
-// no upper bound).  The bucket range is processed in passes of about ctx->index_pass_max postings (filter -> stable radix
-// sort by k-mer -> lines), so neither the number of postings of a shard nor the temporary memory is tied to a 32-bit index.
-void build_line_index(sylph_ctx* ctx, const uint64_t* d_kmers, const uint32_t* d_gid, uint64_t n, uint64_t n_genomes, uint64_t kmer_lo,
-                      uint64_t kmer_hi, LineIndex& ix) {
-    ScopedKernelTimer t(ctx, "db_index");
-    ix.lines.release();
-    ix.ovf.release();
-    ix.base = kmer_lo; ix.div = 1; ix.magic = 0; ix.n_postings = 0; ix.n_ovf = 0; ix.n_buckets = 0; ix.gshift = 2;
-    if (!n) return;
-    DevBuf b_stat(ctx);
-    b_stat.reserve(64);
-    auto range_stats = [&](uint64_t lo, uint64_t hi, uint64_t out[2]) {
-        SY_HIP(hipMemsetAsync(b_stat.p, 0, 16, ctx->stream));
-        hipLaunchKernelGGL(range_stats_kernel, dim3((uint32_t)std::min<uint64_t>(grid_for64(n), 4096)), dim3(256), 0, ctx->stream, d_kmers, n,
-                           lo, hi, b_stat.as<unsigned long long>());
-        ctx->read_back(out, b_stat.p, 16);
-    };
-    uint64_t st[2] = {0, 0};
-    range_stats(kmer_lo, kmer_hi, st);
-    const uint64_t max_key = st[0], m_total = st[1];
-    ix.n_postings = m_total;
-    if (!m_total) return;
-    // slot = remainder << gshift | flag << gb | genome: gb bits of genome id, 63 - gb bits of remainder
-    const int gb = std::max(1, bit_length(n_genomes ? n_genomes - 1 : 0));
-    SY_REQUIRE(gb <= 30, "at most 2^30 genomes per shard");
-    ix.gshift = gb + 1;
-    const uint64_t div_cap = (1ull << (63 - gb)) - 1;                       // remainder < div keeps the all-ones pattern free
-    const uint64_t span = max_key - kmer_lo + 1;                            // bucket 0 starts at kmer_lo     (span >= 1)
-    const uint64_t want_buckets = std::max<uint64_t>(1, m_total / (ctx->index_lambda ? ctx->index_lambda : DEFAULT_INDEX_LAMBDA));
-    uint64_t div = span / want_buckets + (span % want_buckets ? 1 : 0);
-    if (span == 0) div = div_cap;                                           // (max_key - kmer_lo + 1 wrapped: the full 2^64 range)
-    div = std::min(std::max<uint64_t>(div, 1), div_cap);
-    const uint64_t nb64 = (max_key - kmer_lo) / div + 1;
-    SY_REQUIRE(nb64 < (1ull << 32) - 1, "index would need %llu buckets", (unsigned long long)nb64);
-    ix.div = div;
-    ix.magic = div > 1 ? (uint64_t)((((unsigned __int128)1) << 64) / div) : 0;
-    ix.n_buckets = (uint32_t)nb64;
-    ix.lines.reserve((size_t)nb64 * LINE_SLOTS * 8);
-    const uint64_t pass_max = std::max<uint64_t>(1, ctx->index_pass_max);
-    const uint32_t n_pass = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nb64, (m_total + pass_max - 1) / pass_max));
-    const bool whole = n_pass == 1 && m_total == n;                         // nothing to filter: sort the input directly
-    DevBuf b_fk(ctx), b_fg(ctx), b_sk(ctx), b_sg(ctx), b_wg(ctx), b_bf(ctx), b_need(ctx);
-    uint64_t ovf_total = 0;
-    for (uint32_t p = 0; p < n_pass; p++) {
-        const uint32_t b0 = (uint32_t)(nb64 * p / n_pass), b1 = (uint32_t)(nb64 * (p + 1) / n_pass);
-        const uint32_t nbp = b1 - b0;
-        const uint64_t klo = kmer_lo + (uint64_t)b0 * div;
-        uint64_t khi = kmer_hi;                                             // last pass: up to the shard's own bound
-        if (p + 1 < n_pass) khi = kmer_lo + (uint64_t)b1 * div;             // (b1 * div <= max_key - kmer_lo: no overflow)
-        const uint64_t* fk = d_kmers;
-        const uint32_t* fg = d_gid;
-        uint64_t m = n;
-        if (!whole) {
-            uint64_t cnt[2] = {0, 0};
-            range_stats(klo, khi, cnt);
-            m = cnt[1];
-            SY_REQUIRE(m < (1ull << 32) - 1, "index pass holds %llu postings: lower index_pass_max", (unsigned long long)m);
-            if (m) {
-                const uint32_t n_wg = grid_for64(n, FILT_TILE);
-                b_wg.reserve(((size_t)n_wg + 1) * 8);
-                uint32_t* wg_count = b_wg.as<uint32_t>();
-                uint32_t* wg_off = wg_count + (n_wg + 1);
-                SY_HIP(hipMemsetAsync(wg_count + n_wg, 0, 4, ctx->stream));
-                hipLaunchKernelGGL(filter_count_kernel, dim3(n_wg), dim3(FILT_TPB), 0, ctx->stream, d_kmers, n, klo, khi, wg_count);
-                exclusive_sum_u32(ctx, wg_count, wg_off, (size_t)n_wg + 1);
-                b_fk.reserve(m * 8);
-                b_fg.reserve(m * 4);
-                hipLaunchKernelGGL(filter_scatter_kernel, dim3(n_wg), dim3(FILT_TPB), 0, ctx->stream, d_kmers, d_gid, n, klo, khi, wg_off,
-                                   b_fk.as<uint64_t>(), b_fg.as<uint32_t>());
-            }
-            fk = b_fk.as<uint64_t>();
-            fg = b_fg.as<uint32_t>();
-        } else {
-            SY_REQUIRE(m < (1ull << 32) - 1, "internal: single pass with %llu postings", (unsigned long long)m);
-        }
-        b_sk.reserve(std::max<uint64_t>(m, 1) * 8);
-        b_sg.reserve(std::max<uint64_t>(m, 1) * 4);
-        if (m) sort_pairs_u64_u32(ctx, fk, b_sk.as<uint64_t>(), fg, b_sg.as<uint32_t>(), m, 0, 64);   // stable: genome ids stay ascending
-        b_bf.reserve(((size_t)nbp + 2) * 4);
-        b_need.reserve(((size_t)nbp + 2) * 8);
-        uint32_t* bfirst = b_bf.as<uint32_t>();
-        uint32_t* need = b_need.as<uint32_t>();
-        uint32_t* ovf_off = need + (nbp + 1);
-        hipLaunchKernelGGL(bucket_first_kernel, dim3(grid_for64((uint64_t)m + 1)), dim3(256), 0, ctx->stream, b_sk.as<uint64_t>(),
-                           (uint32_t)m, kmer_lo, div, b0, b1, bfirst);
-        hipLaunchKernelGGL(ovf_need_kernel, dim3(grid_for64((uint64_t)nbp + 1)), dim3(256), 0, ctx->stream, bfirst, nbp, need);
-        exclusive_sum_u32(ctx, need, ovf_off, (size_t)nbp + 1);
-        uint32_t ovf_pass = 0;
-        ctx->read_back(&ovf_pass, ovf_off + nbp, 4);
-        ix.ovf.grow_keep((ovf_total + ovf_pass + 1) * 8, ovf_total * 8, ctx->stream);
-        hipLaunchKernelGGL(write_lines_kernel, dim3(grid_for64(nbp)), dim3(256), 0, ctx->stream, b_sk.as<uint64_t>(), b_sg.as<uint32_t>(),
-                           bfirst, ovf_off, b0, nbp, kmer_lo, div, ix.gshift, ovf_total, ix.lines.as<uint64_t>(), ix.ovf.as<uint64_t>());
-        SY_HIP(hipGetLastError());
-        ovf_total += ovf_pass;
-        SY_REQUIRE(ovf_total < (1ull << (62 - gb)), "overflow area too large for the slot format");
-    }
-    ix.n_ovf = ovf_total;
-    SY_HIP(hipStreamSynchronize(ctx->stream));   // the temporaries and the caller's staging buffers are released on return
-}
 
 static uint32_t probe_grid() {
     static const uint32_t g = getenv("SYLPH_HIP_PROBE_GRID") ? (uint32_t)atoi(getenv("SYLPH_HIP_PROBE_GRID")) : PROBE_GRID;
@@ -660,26 +372,31 @@ static void probe_launch(sylph_db* db, const std::vector<SampleRef>& refs, const
     SY_HIP(hipGetLastError());
 }
 
+// A kernel that counts its hits into db->counter ([0] = hits, [1] = largest count), launched by launch(cap, attempt) with a hit array
+// of `cap` entries: waits for the two words and, when the array was too small, launches once more with room for all the hits.
+// Returns the number of hits.
+template <class L>
+static uint32_t launch_until_hits_fit(sylph_db* db, uint64_t cap, uint32_t* max_count, L&& launch) {
+    uint32_t hc[2] = {0, 0};
+    for (int attempt = 0; attempt < 2; attempt++) {
+        launch(cap, attempt);
+        db->ctx->read_back(hc, db->counter.p, 8);
+        if (hc[0] <= cap) break;
+        SY_REQUIRE(attempt == 0, "hit buffer overflow persisted");
+        cap = hc[0];
+    }
+    *max_count = hc[1];
+    return hc[0];
+}
+
 uint32_t probe_batch(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint32_t* max_count) {
-    sylph_ctx* ctx = db->ctx;
     uint64_t total = 0, ilp = 2;
     RefPack pack{};
     const uint64_t chunks = probe_prepare(db, refs, &total, &pack, &ilp);
     *max_count = 0;
     if (!chunks) return 0;
-    uint64_t cap = std::max<uint64_t>(total * 2, 1u << 20);
-    uint32_t n_hits = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        probe_launch(db, refs, pack, chunks, ilp, min_number_kmers, cap);
-        uint32_t hc[2] = {0, 0};
-        ctx->read_back(hc, db->counter.p, 8);
-        n_hits = hc[0];
-        *max_count = hc[1];
-        if (n_hits <= cap) break;
-        SY_REQUIRE(attempt == 0, "hit buffer overflow persisted");
-        cap = n_hits;
-    }
-    return n_hits;
+    return launch_until_hits_fit(db, std::max<uint64_t>(total * 2, 1u << 20), max_count,
+                                 [&](uint64_t cap, int) { probe_launch(db, refs, pack, chunks, ilp, min_number_kmers, cap); });
 }
 
 bool probe_batch_async(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t want_cap, uint64_t* cap) {
@@ -696,61 +413,8 @@ bool probe_batch_async(sylph_db* db, std::vector<SampleRef>& refs, double min_nu
     return true;
 }
 
-// cov_width: nullptr = coverage values as u32; else in/out — the values are stored with the narrowest of 1, 2 or 4 bytes
-// that holds the batch's largest count (7.4 MB -> 1.9 MB over PCIe per sample at GTDB scale) and the width is returned.
-static void finish_hits_sorted(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_rows, uint32_t* cov_width, bool with_lost, HostBlock* dst) {
-    sylph_ctx* ctx = db->ctx;
-    const uint64_t G = db->n_genomes;
-    SY_REQUIRE(n_rows < (1ull << 32) - 1, "too many result rows");
-    const int cb = std::max(1, bit_length(max_count)), rb = std::max(1, bit_length(n_rows));
-    uint32_t width = 4;
-    if (cov_width && n_hits && cb + rb <= 32) width = cb <= 8 ? 1 : cb <= 16 ? 2 : 4;
-    const ResultLayout lay(n_rows, n_hits, width, with_lost ? G : 0);
-    if (!dst) { db->lay = lay; db->last_rows = n_rows; }   // the database's own block; a caller's block carries its layout itself
-    db->res.reserve(lay.lost + 64);
-    char* d_res = db->res.as<char>();
-    uint64_t* d_cov_off = reinterpret_cast<uint64_t*>(d_res);
-    uint32_t* d_ccount = reinterpret_cast<uint32_t*>(d_res + lay.ccount);
-    void* d_covs = d_res + lay.covs;
-    if (n_hits && cb + rb <= 32) {
-        db->hits_sorted.reserve((size_t)n_hits * 8);   // two u32 arrays: packed keys, sorted keys
-        uint32_t* k32 = db->hits_sorted.as<uint32_t>();
-        uint32_t* k32s = k32 + n_hits;
-        hipLaunchKernelGGL(pack_hits32_kernel, dim3(grid_for64(n_hits)), dim3(256), 0, ctx->stream, db->hits.as<uint64_t>(), n_hits, cb, k32);
-        sort_keys_u32(ctx, k32, k32s, n_hits, 0, cb + rb);
-        if (width == 1) hipLaunchKernelGGL(narrow32_kernel<uint8_t>, dim3(grid_for64(n_hits)), dim3(256), 0, ctx->stream, k32s, n_hits, cb, (uint8_t*)d_covs);
-        else if (width == 2) hipLaunchKernelGGL(narrow32_kernel<uint16_t>, dim3(grid_for64(n_hits)), dim3(256), 0, ctx->stream, k32s, n_hits, cb, (uint16_t*)d_covs);
-        else hipLaunchKernelGGL(narrow32_kernel<uint32_t>, dim3(grid_for64(n_hits)), dim3(256), 0, ctx->stream, k32s, n_hits, cb, (uint32_t*)d_covs);
-        hipLaunchKernelGGL(hit_offsets32_kernel, dim3(grid_for64(n_rows + 1)), dim3(256), 0, ctx->stream, k32s, n_hits, (uint32_t)n_rows, cb,
-                           d_cov_off, d_ccount);
-    } else {
-        const uint64_t* d_sorted = nullptr;
-        if (n_hits) {
-            db->hits_sorted.reserve((size_t)n_hits * 8);
-            sort_keys_u64(ctx, db->hits.as<uint64_t>(), db->hits_sorted.as<uint64_t>(), n_hits, 0, 64);
-            d_sorted = db->hits_sorted.as<uint64_t>();
-            hipLaunchKernelGGL(narrow_kernel, dim3(grid_for64(n_hits)), dim3(256), 0, ctx->stream, d_sorted, n_hits, (uint32_t*)d_covs);
-        }
-        hipLaunchKernelGGL(hit_offsets_kernel, dim3(grid_for64(n_rows + 1)), dim3(256), 0, ctx->stream, d_sorted, n_hits, (uint32_t)n_rows,
-                           d_cov_off, d_ccount);
-    }
-    SY_HIP(hipGetLastError());
-    // straight into pinned host memory (the db's own block or the caller's; no staging copy, nothing pageable registered with HIP)
-    if (!dst) dst = &db->h_block;
-    dst->ensure(lay.end + 64);
-    dst->lay = lay;
-    char* h = (char*)dst->p;
-    SY_HIP(hipMemcpyAsync(h, d_res, lay.covs + (size_t)n_hits * width, hipMemcpyDeviceToHost, ctx->stream));   // one copy
-    if (with_lost && G) SY_HIP(hipMemcpyAsync(h + lay.lost, db->lost.p, G * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (cov_width) *cov_width = width;
-    SY_HIP(hipStreamSynchronize(ctx->stream));
-    if (!ctx->pending.empty()) profile_collect(ctx);
-}
-
-// width of the coverage values the row assembly stores (hits.hip applies the same rule to the same word on the device)
-static uint32_t narrow_width(bool want_narrow, uint32_t max_count) { return !want_narrow ? 4u : max_count < 256u ? 1u : max_count < 65536u ? 2u : 4u; }
-
-// copies the assembled block out (one copy; + kmers_lost) and waits for it
+// copies the block assembled in db->res out — straight into pinned host memory (the db's own block or the caller's, which carries its
+// layout itself; no staging copy, nothing pageable registered with HIP), one copy, + kmers_lost — and waits for it
 static void copy_out_rows(sylph_db* db, uint32_t n_hits, uint32_t width, uint64_t n_rows, bool with_lost, HostBlock* dst) {
     sylph_ctx* ctx = db->ctx;
     const uint64_t G = db->n_genomes;
@@ -763,6 +427,47 @@ static void copy_out_rows(sylph_db* db, uint32_t n_hits, uint32_t width, uint64_
     if (with_lost && G) SY_HIP(hipMemcpyAsync(h + lay.lost, db->lost.p, G * 4, hipMemcpyDeviceToHost, ctx->stream));
     SY_HIP(hipStreamSynchronize(ctx->stream));
     if (!ctx->pending.empty()) profile_collect(ctx);
+}
+
+// The sorted finish: the hit list radix-sorted by (row, count), offsets by binary search.
+// cov_width: nullptr = coverage values as u32; else in/out — the values are stored with the narrowest of 1, 2 or 4 bytes
+// that holds the batch's largest count (7.4 MB -> 1.9 MB over PCIe per sample at GTDB scale) and the width is returned.
+static void finish_hits_sorted(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_rows, uint32_t* cov_width, bool with_lost, HostBlock* dst) {
+    sylph_ctx* ctx = db->ctx;
+    SY_REQUIRE(n_rows < (1ull << 32) - 1, "too many result rows");
+    const index_plan::CompactKey ck = index_plan::compact_key(max_count, n_rows);
+    const bool compact = n_hits && ck.fits;
+    const uint32_t width = index_plan::coverage_width(cov_width && compact, max_count);   // (64-bit hit keys report u32)
+    const ResultLayout lay(n_rows, n_hits, width, with_lost ? db->n_genomes : 0);
+    db->res.reserve(lay.lost + 64);
+    char* d_res = db->res.as<char>();
+    uint64_t* d_cov_off = reinterpret_cast<uint64_t*>(d_res);
+    uint32_t* d_ccount = reinterpret_cast<uint32_t*>(d_res + lay.ccount);
+    void* d_covs = d_res + lay.covs;
+    const dim3 g_hits(grid_for64(n_hits)), g_rows(grid_for64(n_rows + 1)), tpb(256);
+    if (compact) {
+        db->hits_sorted.reserve((size_t)n_hits * 8);   // two u32 arrays: packed keys, sorted keys
+        uint32_t* k32 = db->hits_sorted.as<uint32_t>();
+        uint32_t* k32s = k32 + n_hits;
+        hipLaunchKernelGGL(pack_hits32_kernel, g_hits, tpb, 0, ctx->stream, db->hits.as<uint64_t>(), n_hits, ck.cb, k32);
+        sort_keys_u32(ctx, k32, k32s, n_hits, 0, ck.cb + ck.rb);
+        if (width == 1) hipLaunchKernelGGL((narrow_kernel<uint32_t, uint8_t>), g_hits, tpb, 0, ctx->stream, k32s, n_hits, ck.cb, (uint8_t*)d_covs);
+        else if (width == 2) hipLaunchKernelGGL((narrow_kernel<uint32_t, uint16_t>), g_hits, tpb, 0, ctx->stream, k32s, n_hits, ck.cb, (uint16_t*)d_covs);
+        else hipLaunchKernelGGL((narrow_kernel<uint32_t, uint32_t>), g_hits, tpb, 0, ctx->stream, k32s, n_hits, ck.cb, (uint32_t*)d_covs);
+        hipLaunchKernelGGL(hit_offsets_kernel<uint32_t>, g_rows, tpb, 0, ctx->stream, k32s, n_hits, (uint32_t)n_rows, ck.cb, d_cov_off, d_ccount);
+    } else {
+        const uint64_t* d_sorted = nullptr;
+        if (n_hits) {
+            db->hits_sorted.reserve((size_t)n_hits * 8);
+            sort_keys_u64(ctx, db->hits.as<uint64_t>(), db->hits_sorted.as<uint64_t>(), n_hits, 0, 64);
+            d_sorted = db->hits_sorted.as<uint64_t>();
+            hipLaunchKernelGGL((narrow_kernel<uint64_t, uint32_t>), g_hits, tpb, 0, ctx->stream, d_sorted, n_hits, 32, (uint32_t*)d_covs);
+        }
+        hipLaunchKernelGGL(hit_offsets_kernel<uint64_t>, g_rows, tpb, 0, ctx->stream, d_sorted, n_hits, (uint32_t)n_rows, 32, d_cov_off, d_ccount);
+    }
+    SY_HIP(hipGetLastError());
+    if (cov_width) *cov_width = width;
+    copy_out_rows(db, n_hits, width, n_rows, with_lost, dst);
 }
 
 // Host-known hit count (the reassignment pass, the sharded exchange): row assembly when the values fit its histogram, else the
@@ -780,7 +485,7 @@ void finish_hits(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_r
                                     lay0.ccount);
     }
     if (!taken) { finish_hits_sorted(db, n_hits, max_count, n_rows, cov_width, with_lost, dst); return; }
-    const uint32_t width = narrow_width(cov_width != nullptr, max_count);
+    const uint32_t width = index_plan::coverage_width(cov_width != nullptr, max_count);
     if (cov_width) *cov_width = width;
     copy_out_rows(db, n_hits, width, n_rows, with_lost, dst);
 }
@@ -826,7 +531,7 @@ uint32_t probe_and_finish(sylph_db* db, std::vector<SampleRef>& refs, double min
             return n_hits;
         }
         db->cnt_dirty = false;                                // rows_sort_kernel's last workgroup zeroes the counter
-        const uint32_t width = narrow_width(cov_width != nullptr, max_count);
+        const uint32_t width = index_plan::coverage_width(cov_width != nullptr, max_count);
         if (cov_width) *cov_width = width;
         copy_out_rows(db, n_hits, width, n_rows, false, dst);
         return n_hits;
@@ -837,120 +542,6 @@ uint32_t probe_and_finish(sylph_db* db, std::vector<SampleRef>& refs, double min
 }  // namespace sylph
 
 using namespace sylph;
-
-// Stages genome-major (k-mers, offsets) on the device if they are host arrays; returns the device pointers and the total.
-static uint64_t stage_genome_major(sylph_ctx* ctx, const uint64_t* kmers, const uint64_t* off, uint64_t n_genomes, int mem,
-                                   DevBuf& d_off_buf, DevBuf& d_in, const uint64_t*& d_off, const uint64_t*& d_kmers) {
-    uint64_t n = 0;
-    d_off = nullptr;
-    d_kmers = nullptr;
-    if (!n_genomes) return 0;
-    if (mem == SYLPH_MEM_HOST) {
-        SY_REQUIRE(off[0] == 0, "offsets[0] must be 0");
-        n = off[n_genomes];
-        d_off_buf.reserve((n_genomes + 1) * 8);
-        ctx->h2d(d_off_buf.p, off, (n_genomes + 1) * 8);
-        d_off = d_off_buf.as<uint64_t>();
-        if (n) {
-            SY_REQUIRE(kmers, "null kmers");
-            d_in.reserve(n * 8);
-            ctx->h2d(d_in.p, kmers, n * 8);
-            d_kmers = d_in.as<uint64_t>();
-        }
-    } else {
-        ctx->read_back(&n, off + n_genomes, 8);
-        d_off = off;
-        d_kmers = kmers;
-    }
-    return n;
-}
-
-// genome-major device arrays -> line index over the k-mers in [lo, hi)
-static void index_genome_major(sylph_ctx* ctx, const uint64_t* d_kmers, const uint64_t* d_off, uint64_t n_genomes, uint64_t n, uint64_t lo,
-                               uint64_t hi, LineIndex& ix) {
-    DevBuf gid(ctx);
-    gid.reserve(std::max<uint64_t>(n, 1) * 4);
-    if (n)
-        hipLaunchKernelGGL(fill_gid_kernel, dim3((uint32_t)std::min<uint64_t>(n_genomes, 1u << 20)), dim3(256), 0, ctx->stream, d_off, n_genomes,
-                           gid.as<uint32_t>());
-    build_line_index(ctx, d_kmers, gid.as<uint32_t>(), n, n_genomes, lo, hi, ix);
-    SY_HIP(hipStreamSynchronize(ctx->stream));
-}
-
-// off3[g] = clamp(off[g], a, b) - a: the offsets of the genome range whose k-mers lie in [a, b) of the genome-major array, every
-// other genome empty, ids unchanged
-__global__ __launch_bounds__(256) void clamp_offsets_kernel(const uint64_t* __restrict__ off, uint64_t n_entries, uint64_t a, uint64_t b,
-                                                            uint64_t* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_entries) out[i] = min(max(off[i], a), b) - a;
-}
-
-static void db_upload_impl(sylph_ctx* ctx, const uint64_t* kmers, const uint64_t* genome_off, uint64_t n_genomes, int mem,
-                           const uint64_t* bounds, uint32_t world, uint32_t rank, sylph_db** out, const uint64_t* g_bounds = nullptr) {
-    SY_REQUIRE(ctx && out, "null argument");
-    SY_REQUIRE(mem == SYLPH_MEM_HOST || mem == SYLPH_MEM_DEVICE, "bad mem kind %d", mem);
-    SY_REQUIRE(n_genomes < (1ull << 30), "at most 2^30-1 genomes per shard");
-    SY_REQUIRE(n_genomes == 0 || genome_off, "null genome_off");
-    SY_REQUIRE(world >= 1 && rank < world, "bad rank %u of %u", rank, world);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard dg(ctx->device);
-    std::unique_ptr<sylph_db> db(new sylph_db(ctx));
-    db->n_genomes = n_genomes;
-    db->world = world;
-    db->rank = rank;
-    if (bounds) {
-        db->bounds.assign(bounds, bounds + world + 1);
-        for (uint32_t r = 0; r < world; r++) SY_REQUIRE(db->bounds[r] <= db->bounds[r + 1], "shard bounds must be non-decreasing");
-        SY_REQUIRE(db->bounds[0] == 0, "bounds[0] must be 0");
-    }
-    db->counter.reserve(64);
-    DevBuf d_off_buf(ctx), d_in(ctx);
-    const uint64_t* d_off = nullptr;
-    const uint64_t* d_kmers_in = nullptr;
-    const uint64_t n = stage_genome_major(ctx, kmers, genome_off, n_genomes, mem, d_off_buf, d_in, d_off, d_kmers_in);
-    db->glen.reserve(std::max<uint64_t>(1, n_genomes) * 4);
-    uint32_t min_len = 0;
-    if (n_genomes) {
-        uint32_t* d_min = db->counter.as<uint32_t>() + 4;
-        SY_HIP(hipMemsetAsync(d_min, 0xFF, 4, ctx->stream));
-        hipLaunchKernelGGL(genome_len_kernel, dim3(grid_for64(n_genomes)), dim3(256), 0, ctx->stream, d_off, n_genomes, db->glen.as<uint32_t>(),
-                           d_min);
-        ctx->read_back(&min_len, d_min, 4);
-    }
-    db->min_glen = min_len;
-    if (g_bounds) {
-        // shard by GENOME: all k-mers of the genomes [g0, g1), global genome ids, the lengths of ALL genomes (contain.rs:627 looks at
-        // the whole genome); the exchange treats every table as one slice for every shard (shard_plan.h Meta::whole)
-        db->by_genome = true;
-        db->g_bounds.assign(g_bounds, g_bounds + world + 1);
-        SY_REQUIRE(db->g_bounds[0] == 0 && db->g_bounds[world] == n_genomes, "genome bounds must run from 0 to n_genomes");
-        for (uint32_t r = 0; r < world; r++) SY_REQUIRE(db->g_bounds[r] <= db->g_bounds[r + 1], "genome bounds must be non-decreasing");
-        db->bounds.assign((size_t)world + 1, UINT64_MAX);
-        db->bounds[0] = 0;
-        const uint64_t g0 = db->g_bounds[rank], g1 = db->g_bounds[rank + 1];
-        uint64_t ab[2] = {0, 0};
-        if (n_genomes) { ctx->read_back(&ab[0], d_off + g0, 8); ctx->read_back(&ab[1], d_off + g1, 8); }
-        if (ab[1] > ab[0]) {
-            DevBuf d_off3(ctx);
-            d_off3.reserve((n_genomes + 1) * 8);
-            hipLaunchKernelGGL(clamp_offsets_kernel, dim3(grid_for64(n_genomes + 1)), dim3(256), 0, ctx->stream, d_off, n_genomes + 1, ab[0], ab[1],
-                               d_off3.as<uint64_t>());
-            SY_HIP(hipGetLastError());
-            index_genome_major(ctx, d_kmers_in + ab[0], d_off3.as<uint64_t>(), n_genomes, ab[1] - ab[0], 0, 0, db->kept);
-        }
-        db->n_kmers = db->kept.n_postings;
-        ctx->refs++;
-        *out = db.release();
-        return;
-    }
-    const uint64_t lo = bounds ? db->bounds[rank] : 0, hi = bounds ? db->bounds[rank + 1] : 0;
-    const bool last = !bounds || rank + 1 == world;   // the last shard is open-ended (hi == 0 means "no upper bound" in the build)
-    if (last || hi > lo) index_genome_major(ctx, d_kmers_in, d_off, n_genomes, n, lo, last ? 0 : hi, db->kept);
-    else db->kept.base = lo;                         // an empty range (more ranks than k-mer values)
-    db->n_kmers = db->kept.n_postings;
-    ctx->refs++;
-    *out = db.release();
-}
 
 struct ReassignArgs { const uint32_t* passing_gids; const double* passing_ani; uint32_t n_passing; };
 
@@ -978,7 +569,6 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
         if (n) SY_REQUIRE(d_k && d_c, "null sample");
         std::vector<SampleRef> refs(1);
         refs[0].k = d_k; refs[0].c = d_c; refs[0].n = n;
-        (void)max_count;
         return probe_and_finish(db, refs, min_number_kmers, G, cov_width, nullptr);
     }
     // rank[g] = position of genome g in the passing list (or ~0), ani[rank], lost[g] = 0
@@ -997,30 +587,20 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
     SY_HIP(hipMemsetAsync(db->lost.p, 0, rank.size() * 4, ctx->stream));
     if (n && db->kept.n_postings && re->n_passing) {
         SY_REQUIRE(d_k && d_c, "null sample");
-        uint64_t cap = std::max<uint64_t>(n * 2, 1u << 20);
         uint32_t* d_cnt = db->counter.as<uint32_t>();
-        for (int attempt = 0; attempt < 2; attempt++) {
+        n_hits = launch_until_hits_fit(db, std::max<uint64_t>(n * 2, 1u << 20), &max_count, [&](uint64_t cap, int attempt) {
             SY_REQUIRE(cap < (1ull << 32), "more than 2^32-1 hits for one sample");
             db->hits.reserve(cap * 8);
             SY_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
             db->cnt_dirty = true;                             // (this pass counts into the probe's words and nobody zeroes them after it)
             if (attempt) SY_HIP(hipMemsetAsync(db->lost.p, 0, std::max<uint64_t>(1, G) * 4, ctx->stream));
-            {
-                ScopedKernelTimer t(ctx, "probe");
-                hipLaunchKernelGGL(reassign_kernel, dim3(std::min<uint32_t>(grid_for64(n, PROBE_TPB), probe_grid())), dim3(PROBE_TPB), 0, ctx->stream,
-                                   d_k, d_c, (uint32_t)n, db->kept.view(), db->tracked.view(), db->tracked.n_postings ? 1 : 0,
-                                   db->rank_of.as<uint32_t>(), db->ani.as<double>(), db->lost.as<uint32_t>(), db->hits.as<uint64_t>(),
-                                   (uint32_t)cap, d_cnt);
-                SY_HIP(hipGetLastError());
-            }
-            uint32_t hc[2] = {0, 0};
-            ctx->read_back(hc, d_cnt, 8);
-            n_hits = hc[0];
-            max_count = hc[1];
-            if (n_hits <= cap) break;
-            SY_REQUIRE(attempt == 0, "hit buffer overflow persisted");
-            cap = n_hits;
-        }
+            ScopedKernelTimer t(ctx, "probe");
+            hipLaunchKernelGGL(reassign_kernel, dim3(std::min<uint32_t>(grid_for64(n, PROBE_TPB), probe_grid())), dim3(PROBE_TPB), 0, ctx->stream,
+                               d_k, d_c, (uint32_t)n, db->kept.view(), db->tracked.view(), db->tracked.n_postings ? 1 : 0,
+                               db->rank_of.as<uint32_t>(), db->ani.as<double>(), db->lost.as<uint32_t>(), db->hits.as<uint64_t>(),
+                               (uint32_t)cap, d_cnt);
+            SY_HIP(hipGetLastError());
+        });
     }
     finish_hits(db, n_hits, max_count, G, cov_width, true);
     return n_hits;
@@ -1064,140 +644,17 @@ uint32_t sylph::contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples
     return n_hits;
 }
 
+// the three result pointers into the database's own block
+template <class T>
+static void own_views(const sylph_db* db, const uint64_t** cov_off, const uint32_t** contain_count, const T** covs) {
+    ResultViews v;
+    fill_views(db->h_block, &v);
+    *cov_off = v.cov_off;
+    *contain_count = v.contain_count;
+    *covs = (const T*)v.covs;
+}
+
 extern "C" {
-
-int sylph_db_upload(sylph_ctx* ctx, const uint64_t* kmers, const uint64_t* genome_off, uint64_t n_genomes, int mem,
-                    sylph_db** out) {
-    return guarded([&] { db_upload_impl(ctx, kmers, genome_off, n_genomes, mem, nullptr, 1, 0, out); });
-}
-
-int sylph_shard_bounds(uint64_t max_kmer, uint32_t world, uint64_t* bounds) {
-    return guarded([&] {
-        SY_REQUIRE(bounds && world >= 1, "bad argument");
-        const unsigned __int128 span = (unsigned __int128)max_kmer + 1;
-        for (uint32_t r = 0; r < world; r++) bounds[r] = (uint64_t)(span * r / world);
-        bounds[world] = max_kmer == UINT64_MAX ? UINT64_MAX : max_kmer + 1;
-    });
-}
-
-int sylph_db_upload_shard(sylph_ctx* ctx, const uint64_t* kmers, const uint64_t* genome_off, uint64_t n_genomes, int mem,
-                          const uint64_t* bounds, uint32_t world, uint32_t rank, sylph_db** out) {
-    return guarded([&] {
-        SY_REQUIRE(bounds, "null bounds");
-        db_upload_impl(ctx, kmers, genome_off, n_genomes, mem, bounds, world, rank, out);
-    });
-}
-
-int sylph_genome_shard_bounds(const uint64_t* genome_off, uint64_t n_genomes, uint32_t world, uint64_t* g_bounds) {
-    return guarded([&] {
-        SY_REQUIRE(genome_off && g_bounds && world >= 1, "bad argument");
-        shardplan::genome_bounds(genome_off, n_genomes, world, g_bounds);
-    });
-}
-
-int sylph_db_upload_genome_shard(sylph_ctx* ctx, const uint64_t* kmers, const uint64_t* genome_off, uint64_t n_genomes, int mem,
-                                 const uint64_t* g_bounds, uint32_t world, uint32_t rank, sylph_db** out) {
-    return guarded([&] {
-        SY_REQUIRE(g_bounds, "null genome bounds");
-        db_upload_impl(ctx, kmers, genome_off, n_genomes, mem, nullptr, world, rank, out, g_bounds);
-    });
-}
-
-int sylph_db_attach_tracked(sylph_db* db, const uint64_t* tracked_kmers, const uint64_t* tracked_off, int mem) {
-    return guarded([&] {
-        SY_REQUIRE(db && tracked_off, "null argument");
-        SY_REQUIRE(mem == SYLPH_MEM_HOST || mem == SYLPH_MEM_DEVICE, "bad mem kind %d", mem);
-        SY_REQUIRE(db->world == 1, "reassignment runs on an unsharded database");
-        sylph_ctx* ctx = db->ctx;
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        DevBuf d_off_buf(ctx), d_in(ctx);
-        const uint64_t* d_off = nullptr;
-        const uint64_t* d_k = nullptr;
-        const uint64_t n = stage_genome_major(ctx, tracked_kmers, tracked_off, db->n_genomes, mem, d_off_buf, d_in, d_off, d_k);
-        index_genome_major(ctx, d_k, d_off, db->n_genomes, n, 0, 0, db->tracked);
-    });
-}
-
-// A copy of an unsharded database on another context (normally: another GPU of the node).  The line index, the overflow runs, the
-// tracked index and the genome lengths travel device to device — hipMemcpyPeer, i.e. over xGMI between two GPUs — instead of being
-// uploaded from the host and built again per GPU: the counterpart of the reference's one `Vec<GenomeSketch>` shared by all rayon
-// workers (contain.rs:252-295), for N GPUs behind one sample loop (sylph_pipeline_create_multi).
-int sylph_db_replicate(sylph_db* src, sylph_ctx* dst_ctx, sylph_db** out) {
-    return guarded([&] {
-        SY_REQUIRE(src && dst_ctx && out, "null argument");
-        SY_REQUIRE(src->world == 1 && src->bounds.empty(), "only an unsharded database can be replicated");
-        sylph_ctx* sctx = src->ctx;
-        // (two context locks, always in address order: two threads replicating in opposite directions cannot deadlock)
-        std::unique_lock<std::mutex> l1(sctx < dst_ctx ? sctx->mu : dst_ctx->mu, std::defer_lock), l2(sctx < dst_ctx ? dst_ctx->mu : sctx->mu, std::defer_lock);
-        l1.lock();
-        if (sctx != dst_ctx) l2.lock();
-        {   // everything queued on the source's stream (the index build) must have landed
-            DeviceGuard dg(sctx->device);
-            SY_HIP(hipStreamSynchronize(sctx->stream));
-        }
-        DeviceGuard dg(dst_ctx->device);
-        std::unique_ptr<sylph_db> db(new sylph_db(dst_ctx));
-        db->n_genomes = src->n_genomes;
-        db->n_kmers = src->n_kmers;
-        db->min_glen = src->min_glen;
-        db->counter.reserve(64);
-        // Device to device where the two GPUs can reach each other (hipMemcpyPeer: xGMI inside a node).  Where they cannot — no peer
-        // access between the two devices, a copy engine that refuses — the buffer takes the long way: source -> the library's page-locked
-        // staging chunks -> destination, 32 MiB at a time (round 6; VERDICT r05 #9: the peer copy used to be the only road, and threw).
-        // "fail_next_peer_copy" on the DESTINATION context is the tests' way of taking that road on one GPU.
-        bool bounced = false;
-        struct Pinned { void* p = nullptr; ~Pinned() { if (p) (void)hipHostFree(p); } } via;      // the bounce's own page-locked chunk
-        auto bounce = [&](void* d, const void* s_, size_t bytes) {
-            if (!via.p) SY_HIP(hipHostMalloc(&via.p, sylph_ctx::STAGE_BYTES, hipHostMallocDefault));
-            for (size_t at = 0; at < bytes; at += sylph_ctx::STAGE_BYTES) {
-                const size_t n = std::min(bytes - at, (size_t)sylph_ctx::STAGE_BYTES);
-                {
-                    DeviceGuard sg(sctx->device);
-                    SY_HIP(hipMemcpyAsync(via.p, (const uint8_t*)s_ + at, n, hipMemcpyDeviceToHost, sctx->stream));
-                    SY_HIP(hipStreamSynchronize(sctx->stream));
-                }
-                SY_HIP(hipMemcpyAsync((uint8_t*)d + at, via.p, n, hipMemcpyHostToDevice, dst_ctx->stream));
-                SY_HIP(hipStreamSynchronize(dst_ctx->stream));
-            }
-        };
-        auto copy = [&](DevBuf& d, const DevBuf& s_, size_t bytes) {
-            if (!bytes) return;
-            d.reserve(bytes);
-            hipError_t e = hipSuccess;
-            if (dst_ctx->fail_next_peer_copy) { dst_ctx->fail_next_peer_copy = 0; e = hipErrorInvalidDevice; }
-            else if (bounced) e = hipErrorInvalidDevice;                 // (one refusal: the other buffers take the same road)
-            else if (sctx->device == dst_ctx->device) e = hipMemcpyAsync(d.p, s_.p, bytes, hipMemcpyDeviceToDevice, dst_ctx->stream);
-            else e = hipMemcpyPeerAsync(d.p, dst_ctx->device, s_.p, sctx->device, bytes, dst_ctx->stream);
-            if (e == hipSuccess) return;
-            if (e == hipErrorOutOfMemory) SY_HIP(e);
-            (void)hipGetLastError();
-            if (!bounced) fprintf(stderr, "[sylph_hip] sylph_db_replicate: no device-to-device copy from GPU %d to GPU %d (%s): the index travels through host memory\n",
-                                  sctx->device, dst_ctx->device, hipGetErrorString(e));
-            bounced = true;
-            bounce(d.p, s_.p, bytes);
-        };
-        auto copy_index = [&](LineIndex& d, const LineIndex& s_) {
-            d.base = s_.base; d.div = s_.div; d.magic = s_.magic; d.n_postings = s_.n_postings; d.n_ovf = s_.n_ovf;
-            d.n_buckets = s_.n_buckets; d.gshift = s_.gshift;
-            copy(d.lines, s_.lines, (size_t)s_.n_buckets * LINE_SLOTS * 8);
-            copy(d.ovf, s_.ovf, s_.ovf.p ? std::min<size_t>(s_.ovf.cap, ((size_t)s_.n_ovf + 64) * 8) : 0);   // (+64: the wavefront-wide walk of a long run reads 64 entries at a time)
-        };
-        copy_index(db->kept, src->kept);
-        copy_index(db->tracked, src->tracked);
-        copy(db->glen, src->glen, std::max<uint64_t>(1, src->n_genomes) * 4);
-        SY_HIP(hipStreamSynchronize(dst_ctx->stream));
-        dst_ctx->refs++;
-        *out = db.release();
-    });
-}
-
-uint64_t sylph_db_n_genomes(const sylph_db* db) { return db ? db->n_genomes : 0; }
-uint64_t sylph_db_n_kmers(const sylph_db* db) { return db ? db->n_kmers : 0; }
-uint64_t sylph_db_index_bytes(const sylph_db* db) {
-    if (!db) return 0;
-    return ((uint64_t)db->kept.n_buckets + db->tracked.n_buckets) * LINE_SLOTS * 8 + (db->kept.n_ovf + db->tracked.n_ovf) * 8;
-}
 
 int sylph_db_contain_view(sylph_db* db, const uint64_t* sample_kmers, const uint32_t* sample_counts, uint64_t n, int mem,
                           double min_number_kmers, const uint32_t** contain_count, const uint64_t** cov_off,
@@ -1207,11 +664,7 @@ int sylph_db_contain_view(sylph_db* db, const uint64_t* sample_kmers, const uint
         std::lock_guard<std::mutex> lock(db->ctx->mu);
         DeviceGuard dg(db->ctx->device);
         const uint32_t n_hits = contain_impl(db, sample_kmers, sample_counts, n, mem, min_number_kmers);
-        const ResultLayout& lay = db->lay;
-        const char* h = (const char*)db->h_block.p;
-        *cov_off = (const uint64_t*)h;
-        *contain_count = (const uint32_t*)(h + lay.ccount);
-        *covs = (const uint32_t*)(h + lay.covs);
+        own_views(db, cov_off, contain_count, covs);
         if (out_n_covs) *out_n_covs = n_hits;
     });
 }
@@ -1224,11 +677,7 @@ int sylph_db_contain_view_packed(sylph_db* db, const uint64_t* sample_kmers, con
         std::lock_guard<std::mutex> lock(db->ctx->mu);
         DeviceGuard dg(db->ctx->device);
         const uint32_t n_hits = contain_impl(db, sample_kmers, sample_counts, n, mem, min_number_kmers, nullptr, cov_width);
-        const ResultLayout& lay = db->lay;
-        const char* h = (const char*)db->h_block.p;
-        *cov_off = (const uint64_t*)h;
-        *contain_count = (const uint32_t*)(h + lay.ccount);
-        *covs = h + lay.covs;
+        own_views(db, cov_off, contain_count, covs);
         if (out_n_covs) *out_n_covs = n_hits;
     });
 }
@@ -1257,12 +706,8 @@ int sylph_db_reassign_view(sylph_db* db, const uint64_t* sample_kmers, const uin
         DeviceGuard dg(db->ctx->device);
         ReassignArgs re{passing_gids, passing_ani, n_passing};
         const uint32_t n_hits = contain_impl(db, sample_kmers, sample_counts, n, mem, 0.0, &re);
-        const ResultLayout& lay = db->lay;
-        const char* h = (const char*)db->h_block.p;
-        *cov_off = (const uint64_t*)h;
-        *contain_count = (const uint32_t*)(h + lay.ccount);
-        *covs = (const uint32_t*)(h + lay.covs);
-        *kmers_lost = (const uint32_t*)(h + lay.lost);
+        own_views(db, cov_off, contain_count, covs);
+        *kmers_lost = (const uint32_t*)((const char*)db->h_block.p + db->lay.lost);
         if (out_n_covs) *out_n_covs = n_hits;
     });
 }
@@ -1275,13 +720,13 @@ int sylph_db_contain(sylph_db* db, const uint64_t* sample_kmers, const uint32_t*
         DeviceGuard dg(db->ctx->device);
         const uint32_t n_hits = contain_impl(db, sample_kmers, sample_counts, n, mem, min_number_kmers);
         const uint64_t G = db->n_genomes;
-        const ResultLayout& lay = db->lay;
-        const char* h = (const char*)db->h_block.p;
+        ResultViews v;
+        fill_views(db->h_block, &v);
         uint32_t* hcov = (uint32_t*)malloc(std::max<size_t>(1, n_hits) * 4);
         if (!hcov) throw std::bad_alloc();
-        memcpy(cov_off, h, (G + 1) * 8);
-        if (G) memcpy(contain_count, h + lay.ccount, G * 4);
-        if (n_hits) memcpy(hcov, h + lay.covs, (size_t)n_hits * 4);
+        memcpy(cov_off, v.cov_off, (G + 1) * 8);
+        if (G) memcpy(contain_count, v.contain_count, G * 4);
+        if (n_hits) memcpy(hcov, v.covs, (size_t)n_hits * 4);
         *out_covs = hcov;
     });
 }
@@ -1297,3 +742,4 @@ void sylph_db_destroy(sylph_db* db) {
 }
 
 }  // extern "C"
+

@@ -1,26 +1,20 @@
-// contain_index.h — the k-mer -> genomes "line index" of a database (shard) and the database object, shared by contain.hip
-// (build, probe, result assembly) and shard.hip (multi-GPU exchange).  Internal, not part of the ABI.
+// contain_index.h — the k-mer -> genomes "line index" of a database (shard) and the database object, shared by line_index.hip
+// (build, upload), contain.hip (probe, reassignment, finish), hits.hip (row assembly) and shard.hip (multi-GPU exchange).  The
+// index's arithmetic is index_plan.h.  Internal, not part of the ABI.
 #pragma once
 #include "common.h"
+#include "index_plan.h"
 
 namespace sylph {
 
-// Slots per bucket line: 8 (a 64-byte line, lambda = 4 postings aimed at per line) or 4 (round 5: a 32-byte half-line, lambda = 2 —
-// the same index bytes, twice the buckets; random 32 B reads come back at 1.8x the rate of random 64 B reads on this chip,
-// profiles/r05_random_line_rates.txt).  A compile-time choice: the probe's loads and the slot scan are unrolled over it.
-#ifndef SYLPH_LINE_SLOTS
-#define SYLPH_LINE_SLOTS 8
-#endif
-constexpr int LINE_SLOTS = SYLPH_LINE_SLOTS;   // x 8 B per bucket line
-static_assert(LINE_SLOTS == 8 || LINE_SLOTS == 4, "a bucket line is 64 or 32 bytes");
-constexpr int LINE_QUADS = LINE_SLOTS / 2;     // 16-byte loads per line
-constexpr uint32_t DEFAULT_INDEX_LAMBDA = LINE_SLOTS / 2;
-constexpr uint64_t SLOT_EMPTY = ~0ull;
+using index_plan::LINE_SLOTS;
+using index_plan::LINE_QUADS;
+using index_plan::SLOT_EMPTY;
+using index_plan::LONG_RUN_MIN;
+using index_plan::DEFAULT_INDEX_LAMBDA;
 
 // What the kernels need to probe an index (POD, passed by value).
-//   bucket(km) = (km - base) / div;   slot = ((km - base) % div) << gshift | flag << (gshift - 1) | genome id
-//   descriptor (slot 7 of a bucket with more than 8 postings) = first entry of its overflow run << gshift | flag | min(length of
-//   the run, 2^(gshift-1) - 1) in the genome field
+//   bucket(km) = (km - base) / div, remainder = (km - base) % div (index_plan::bucket_rem); slots and descriptors: index_plan.h
 struct LineView {
     const uint64_t* lines;   // n_buckets x LINE_SLOTS
     const uint64_t* ovf;     // overflow runs, each closed by SLOT_EMPTY
@@ -53,74 +47,40 @@ constexpr uint32_t REFS_INLINE = 8;
 struct RefPack { SampleRef r[REFS_INLINE]; };
 
 #ifdef __HIPCC__
-// Calls f(genome id) for every posting of k-mer `km`.  One 64 B line read (4 x global_load_dwordx4); the overflow run of
-// a crowded bucket is walked only when the 7 postings kept in the line do not already exceed the remainder looked for.
-// LONG_RUN > 0: an overflow run of at least LONG_RUN entries is not walked here; its first entry is returned through
-// *long_start (else ~0) with the remainder in *long_rem, for the caller's wavefront-wide walk (probe_long_run).
-constexpr uint32_t LONG_RUN_MIN = 48;
-template <class F>
-__device__ __forceinline__ void for_each_posting(const LineView& v, uint64_t km, F&& f, uint64_t* long_start = nullptr,
-                                                 uint64_t* long_rem = nullptr) {
-    if (long_start) *long_start = ~0ull;
-    if (km < v.base) return;
-    const uint64_t x = km - v.base;
-    uint64_t q, rem;
-    if (v.div == 1) { q = x; rem = 0; }
-    else {
-        q = __umul64hi(x, v.magic);                       // floor(x * floor(2^64/div) / 2^64) is q or q - 1
-        rem = x - q * v.div;
-        if (rem >= v.div) { rem -= v.div; q++; }
-    }
-    if (q >= v.n_buckets) return;
-    const uint4* lp = reinterpret_cast<const uint4*>(v.lines + q * LINE_SLOTS);
-    uint4 qd[LINE_QUADS];
-#pragma unroll
-    for (int t = 0; t < LINE_QUADS; t++) qd[t] = lp[t];
-    uint64_t s[LINE_SLOTS];
-#pragma unroll
-    for (int t = 0; t < LINE_QUADS; t++) { s[2 * t] = ((uint64_t)qd[t].y << 32) | qd[t].x; s[2 * t + 1] = ((uint64_t)qd[t].w << 32) | qd[t].z; }
-    const uint64_t flag = 1ull << (v.gshift - 1), gmask = flag - 1;
-#pragma unroll
-    for (int j = 0; j < LINE_SLOTS; j++)
-        if ((s[j] >> v.gshift) == rem && !(s[j] & flag)) f((uint32_t)(s[j] & gmask));
-    const uint64_t last = s[LINE_SLOTS - 1];
-    if ((last & flag) && last != SLOT_EMPTY && (s[LINE_SLOTS - 2] >> v.gshift) <= rem) {   // descriptor: rest of the bucket
-        if (long_start && (last & gmask) >= LONG_RUN_MIN) { *long_start = last >> v.gshift; *long_rem = rem; return; }
-        for (uint64_t i = last >> v.gshift;; i++) {
-            const uint64_t y = v.ovf[i];
-            if (y == SLOT_EMPTY) break;
-            const uint64_t r = y >> v.gshift;
-            if (r > rem) break;                            // the run is sorted by (remainder, genome)
-            if (r == rem) f((uint32_t)(y & gmask));
-        }
-    }
-}
-
-// The same in two halves, so that a lane can have the lines of several k-mers in flight before it looks at any of them (the
-// probe is latency-bound: random 64 B reads): line_fetch computes the bucket and issues the four loads, line_scan walks the
-// slots (and the short overflow run) exactly as for_each_posting does.
+// A k-mer's postings in two halves, so that a lane can have the lines of several k-mers in flight before it looks at any of them
+// (the probe is latency-bound: random 64 B reads): line_fetch computes the bucket and issues the LINE_QUADS 16-byte loads of its
+// line; line_scan calls f(genome id) for every posting of the k-mer (index_plan::scan_slots: the line, then the overflow run of a
+// crowded bucket when the postings kept in the line do not already exceed the remainder looked for).  An overflow run of at least
+// LONG_RUN_MIN entries is not walked by the lane: its first entry is returned through *long_start (else ~0) with the remainder in
+// *long_rem, and the caller's wavefront walks it, 64 entries per long_run_step (for_each_long_run hands the runs over).
 struct LineFetch {
     uint4 v[LINE_QUADS];
     uint64_t rem;
     bool live;
 };
+// the bucket line of k-mer km and its remainder there; false: the index has no bucket for it
+__device__ __forceinline__ bool line_locate(const LineView& v, uint64_t km, const uint4*& line, uint64_t& rem) {
+    if (km < v.base) return false;
+    uint64_t q;
+    index_plan::bucket_rem(km - v.base, v.div, v.magic, q, rem);
+    if (q >= v.n_buckets) return false;
+    line = reinterpret_cast<const uint4*>(v.lines + q * LINE_SLOTS);
+    return true;
+}
+// the slots of a line read as LINE_QUADS 16-byte quads (global_load_dwordx4)
+__device__ __forceinline__ void line_unpack(const uint4 (&qd)[LINE_QUADS], uint64_t (&s)[LINE_SLOTS]) {
+#pragma unroll
+    for (int t = 0; t < LINE_QUADS; t++) { s[2 * t] = ((uint64_t)qd[t].y << 32) | qd[t].x; s[2 * t + 1] = ((uint64_t)qd[t].w << 32) | qd[t].z; }
+}
 __device__ __forceinline__ LineFetch line_fetch(const LineView& v, uint64_t km, bool wanted) {
     LineFetch f;
     f.live = false;
     f.rem = 0;
 #pragma unroll
     for (int t = 0; t < LINE_QUADS; t++) f.v[t] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    if (!wanted || km < v.base) return f;
-    const uint64_t x = km - v.base;
-    uint64_t q, rem;
-    if (v.div == 1) { q = x; rem = 0; }
-    else {
-        q = __umul64hi(x, v.magic);                       // floor(x * floor(2^64/div) / 2^64) is q or q - 1
-        rem = x - q * v.div;
-        if (rem >= v.div) { rem -= v.div; q++; }
-    }
-    if (q >= v.n_buckets) return f;
-    const uint4* lp = reinterpret_cast<const uint4*>(v.lines + q * LINE_SLOTS);
+    const uint4* lp;
+    uint64_t rem;
+    if (!wanted || !line_locate(v, km, lp, rem)) return f;
 #pragma unroll
     for (int t = 0; t < LINE_QUADS; t++) f.v[t] = lp[t];
     f.rem = rem;
@@ -129,27 +89,54 @@ __device__ __forceinline__ LineFetch line_fetch(const LineView& v, uint64_t km, 
 }
 template <class F>
 __device__ __forceinline__ void line_scan(const LineView& v, const LineFetch& l, F&& f, uint64_t* long_start, uint64_t* long_rem) {
-    *long_start = ~0ull;
+    *long_start = index_plan::NO_LONG_RUN;
     if (!l.live) return;
-    const uint64_t rem = l.rem;
     uint64_t s[LINE_SLOTS];
+    line_unpack(l.v, s);
+    index_plan::scan_slots(s, l.rem, v.gshift, v.ovf, f, long_start, long_rem);
+}
+// The same steps in one go, for a caller with nothing to overlap the line read with (the reassignment pass; written without the
+// LineFetch in between: carrying the line through it cost that kernel 7 VGPRs, profiles/index_plan_census.txt).
+template <class F>
+__device__ __forceinline__ void for_each_posting(const LineView& v, uint64_t km, F&& f, uint64_t* long_start, uint64_t* long_rem) {
+    *long_start = index_plan::NO_LONG_RUN;
+    const uint4* lp;
+    uint64_t rem;
+    if (!line_locate(v, km, lp, rem)) return;
+    uint4 qd[LINE_QUADS];
 #pragma unroll
-    for (int t = 0; t < LINE_QUADS; t++) { s[2 * t] = ((uint64_t)l.v[t].y << 32) | l.v[t].x; s[2 * t + 1] = ((uint64_t)l.v[t].w << 32) | l.v[t].z; }
-    const uint64_t flag = 1ull << (v.gshift - 1), gmask = flag - 1;
-#pragma unroll
-    for (int j = 0; j < LINE_SLOTS; j++)
-        if ((s[j] >> v.gshift) == rem && !(s[j] & flag)) f((uint32_t)(s[j] & gmask));
-    const uint64_t last = s[LINE_SLOTS - 1];
-    if ((last & flag) && last != SLOT_EMPTY && (s[LINE_SLOTS - 2] >> v.gshift) <= rem) {   // descriptor: rest of the bucket
-        if ((last & gmask) >= LONG_RUN_MIN) { *long_start = last >> v.gshift; *long_rem = rem; return; }
-        for (uint64_t i = last >> v.gshift;; i++) {
-            const uint64_t y = v.ovf[i];
-            if (y == SLOT_EMPTY) break;
-            const uint64_t r = y >> v.gshift;
-            if (r > rem) break;                            // the run is sorted by (remainder, genome)
-            if (r == rem) f((uint32_t)(y & gmask));
-        }
+    for (int t = 0; t < LINE_QUADS; t++) qd[t] = lp[t];
+    uint64_t s[LINE_SLOTS];
+    line_unpack(qd, s);
+    index_plan::scan_slots(s, rem, v.gshift, v.ovf, f, long_start, long_rem);
+}
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t x, int src) {
+    return ((uint64_t)(uint32_t)__shfl((int)(x >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)x, src);
+}
+// The long runs the lanes of a wavefront came back from line_scan with, one after the other: f(lane that owns the run, first entry,
+// remainder) with the same arguments in every lane (a uniform loop: the ballot is the same in every lane).
+template <class F>
+__device__ __forceinline__ void for_each_long_run(uint64_t long_start, uint64_t long_rem, F&& f) {
+    for (unsigned long long todo = __ballot(long_start != index_plan::NO_LONG_RUN); todo; todo &= todo - 1) {
+        const int src = __ffsll((long long)todo) - 1;
+        f(src, shfl_u64(long_start, src), shfl_u64(long_rem, src));
     }
+}
+// One step of the wavefront's walk of an overflow run: the 64 entries from `base`, one per lane.  match: this lane's entry is a
+// posting of the remainder looked for (genome in g); ended: the relevant part of the run ends inside the step.
+struct LongRunStep { bool match, ended; uint32_t g; };
+__device__ __forceinline__ LongRunStep long_run_step(const LineView& v, uint64_t base, uint64_t rem) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t idx = base + lane;
+    const uint64_t y = idx < v.n_ovf ? v.ovf[idx] : SLOT_EMPTY;
+    const unsigned long long stop = __ballot(index_plan::run_stops(y, rem, v.gshift));   // the run is sorted by (remainder, genome)
+    const uint32_t first_stop = stop ? (uint32_t)__ffsll((long long)stop) - 1 : 64u;
+    LongRunStep r;
+    r.g = index_plan::slot_genome(y, v.gshift);
+    r.ended = stop != 0;
+    r.match = lane < first_stop && index_plan::slot_rem(y, v.gshift) == rem;
+    return r;
 }
 #endif
 
@@ -181,9 +168,6 @@ struct HostBlock {
         cap = need + need / 2;
     }
 };
-
-void build_line_index(sylph_ctx* ctx, const uint64_t* d_kmers, const uint32_t* d_gid, uint64_t n, uint64_t n_genomes, uint64_t kmer_lo,
-                      uint64_t kmer_hi, LineIndex& ix);
 
 }  // namespace sylph
 

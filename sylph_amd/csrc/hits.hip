@@ -289,8 +289,7 @@ __global__ __launch_bounds__(256) void rows_sort_kernel(const uint32_t* __restri
     if (probe_counter && blockIdx.x == 0 && threadIdx.x < 2) probe_counter[threadIdx.x] = 0;
     const uint32_t n_small = lists[0], n_big = lists[1];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t width = 4;
-    if (want_narrow) width = mx < 256u ? 1u : mx < 65536u ? 2u : 4u;
+    const uint32_t width = index_plan::coverage_width(want_narrow != 0, mx);
     // ---- rows of at most one wavefront of values: one wavefront each, every value ranked against the row's others
     const uint32_t n_waves = gridDim.x * 4;
     for (uint32_t e = blockIdx.x * 4 + wave; e < n_small; e += n_waves) {

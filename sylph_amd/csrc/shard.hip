@@ -214,7 +214,6 @@ __global__ __launch_bounds__(256) void owner_scatter_kernel(const uint64_t* __re
     }
 }
 
-uint32_t grid_for64(uint64_t n, uint32_t tpb = 256) { return (uint32_t)((n + tpb - 1) / tpb); }
 
 }  // namespace
 }  // namespace sylph

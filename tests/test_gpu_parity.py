@@ -763,6 +763,39 @@ def flat_db(genomes):
     return np.concatenate(genomes), goff
 
 
+BOUNDARY_JS = (1, 7, 8, 9, 54, 55, 71, 72, 135, 136, 207)
+
+
+def boundary_db(extremes):
+    """The deterministic boundary database: 210 genomes; k-mer j << 40 is held by the genomes 0 .. j - 1 for j in BOUNDARY_JS.  Without the
+    extreme keys every such k-mer has a bucket of its own at index_lambda 4 and 2 (asserted below with the build's formula,
+    index_plan.h geometry), of exactly j postings: runs of 0, 0, 0, 2, 47, 48, 64, 65, 128, 129 and 200 entries behind the 64-byte
+    line — both sides of LONG_RUN_MIN, of one and of two 64-entry steps.  With the keys 0 and 2^64 - 1 (in genome 3) the span
+    wraps, div is its cap 2^55 - 1 and the whole database is ONE bucket with an overflow run of thousands of entries and hundreds of
+    remainders.  The genomes 190 .. 209 have fewer than 5 k-mers, the others at least 10: min_number_kmers = 5 filters inside the runs.
+    -> genomes, k-mers for a sample"""
+    rng = np.random.default_rng(40)
+    own = (np.uint64(208) << np.uint64(40)) + np.unique(rng.integers(0, 122 << 40, size=2200, dtype=np.uint64))[:1930]
+    rng.shuffle(own)
+    genomes = []
+    for g in range(210):
+        mine = own[g * 10:(g + 1) * 10] if g < 190 else own[1900 + (g - 190):1900 + (g - 190) + 1 + g % 3]
+        parts = [np.array([j << 40 for j in BOUNDARY_JS if g < j], dtype=np.uint64), mine]
+        if extremes and g == 3:
+            parts.append(np.array([0, 2**64 - 1], dtype=np.uint64))
+        genomes.append(np.concatenate(parts))
+        assert len(genomes[g]) >= 10 if g < 190 else 1 <= len(genomes[g]) < 5
+    if not extremes:
+        n = sum(len(g) for g in genomes)
+        for lam in (4, 2):
+            span = int(max(g.max() for g in genomes)) + 1
+            div = -(-span // (n // lam))
+            assert div < 1 << 39 and int(own.min()) // div > (207 << 40) // div      # neighbours apart, nothing else in their buckets
+    sample = np.concatenate([np.array([j << 40 for j in BOUNDARY_JS] + [0, 2**64 - 1, 5, (208 << 40) - 1], dtype=np.uint64), own[::3],
+                             (np.uint64(3) << np.uint64(40)) + np.arange(5, dtype=np.uint64)])
+    return genomes, np.unique(sample)
+
+
 def test_contain_crowded_buckets_and_index_shapes(ctx):
     """The line index under every shape the build can take: 1..8 postings per bucket aimed for, one pass and several
     (index_pass_max lowered so that the filter -> sort -> lines passes really split the bucket range), overflow runs."""
@@ -779,6 +812,19 @@ def test_contain_crowded_buckets_and_index_shapes(ctx):
             cc = check_contain(ctx, db, goff, sk, sc, min_kmers=0.0)
             assert cc.max() > 300            # the shared k-mers hit
             check_contain(ctx, db, goff, sk, sc, min_kmers=100.0)
+        for extremes in (False, True):
+            genomes_b, sk_b = boundary_db(extremes)
+            db_b, goff_b = flat_db(genomes_b)
+            sc_b = rng.integers(0, 300, size=len(sk_b)).astype(np.uint32)
+            sc_b[np.isin(sk_b, np.array([j << 40 for j in BOUNDARY_JS], dtype=np.uint64))] = np.arange(1, len(BOUNDARY_JS) + 1)
+            sc_b[[0, -1]] = 7                                                        # (the keys 0 and 2^64 - 1)
+            for lam, pass_max in ((4, 1 << 30), (2, 777)):
+                ctx.set_option("index_lambda", str(lam))
+                ctx.set_option("index_pass_max", str(pass_max))
+                cc = check_contain(ctx, db_b, goff_b, sk_b, sc_b, min_kmers=0.0)
+                assert cc[0] >= len(BOUNDARY_JS) and cc[206] >= 1 and cc[209] <= 3
+                cc = check_contain(ctx, db_b, goff_b, sk_b, sc_b, min_kmers=5.0)
+                assert cc[0] >= len(BOUNDARY_JS) and cc[190:].sum() == 0             # filtered inside the runs
     finally:
         ctx.set_option("index_lambda", "4")
         ctx.set_option("index_pass_max", str(1 << 30))
@@ -1134,34 +1180,17 @@ def test_reassign_on_device_matches_reference_semantics(ctx):
     db.close()
 
 
-def test_reassign_with_kmers_shared_by_hundreds_of_genomes(ctx):
-    """The winner pass when 400 strains hold (almost) the same k-mers in genome_kmers AND in their tracked sets: overflow runs of
-    hundreds of postings in both indexes, walked by the whole wavefront; winner = highest first-pass ANI, ties to the first in
-    the passing list; strains outside the passing list neither win nor lose; every genome's kept coverages and kmers_lost
-    against a direct restatement of winner_table + the winner pass (contain.rs:410-430, :637-646)."""
-    rng = np.random.default_rng(123)
-    thr = O.threshold(200)
-    core = np.unique(rng.integers(0, thr, size=250, dtype=np.uint64))
-    tcore = np.unique(rng.integers(0, thr, size=120, dtype=np.uint64))
-    G = 460
-    genomes, tracked = [], []
-    for g in range(G):
-        if g < 400:
-            genomes.append(np.concatenate([core[rng.random(len(core)) < 0.95], rng.integers(0, thr, size=20, dtype=np.uint64)]))
-            # tracked sets: the shared tracked core + some of the OTHER strains' genome k-mers (they can steal ownership)
-            tracked.append(np.concatenate([tcore[rng.random(len(tcore)) < 0.9], core[rng.random(len(core)) < 0.05]]))
-        else:
-            genomes.append(np.concatenate([rng.integers(0, thr, size=200, dtype=np.uint64), tcore[:30], core[:5]]))
-            tracked.append(np.zeros(0, dtype=np.uint64))
+def check_reassign(ctx, genomes, tracked, sk, sc, rng, min_passing, min_lost):
+    """sylph_db_reassign_view over three passing lists (the first with every ANI tied) against a direct restatement of winner_table +
+    the winner pass (contain.rs:410-430, :637-646): every genome's kept coverages and kmers_lost"""
+    G = len(genomes)
     db_k, goff = flat_db(genomes)
     t_k, toff = flat_db(tracked)
-    sk = np.unique(np.concatenate([core, tcore, rng.integers(0, thr, size=3000, dtype=np.uint64)] + [g[-20:] for g in genomes[:50]]))
-    sc = rng.integers(0, 5, size=len(sk)).astype(np.uint32)
     smap = dict(zip(sk.tolist(), sc.tolist()))
     db = S.Database(ctx, db_k, goff)
     db.attach_tracked(t_k, toff)
     for trial in range(3):
-        passing = rng.permutation(G)[: int(rng.integers(250, G + 1))]
+        passing = rng.permutation(G)[: int(rng.integers(min_passing, G + 1))]
         ani = rng.choice([0.95, 0.96, 0.97, 0.97, 0.99], size=len(passing)) if trial else np.full(len(passing), 0.97)   # trial 0: all tied
         winner = {}
         for r, g in enumerate(passing):
@@ -1186,8 +1215,41 @@ def test_reassign_with_kmers_shared_by_hundreds_of_genomes(ctx):
                     exp.append(c)
             assert cc[g] == len(exp) and lost[g] == exp_lost, (trial, g)
             assert np.array_equal(got, np.sort(np.array(exp, dtype=np.uint32)))
-        assert int(lost.sum()) > 10000
+        assert int(lost.sum()) > min_lost
     db.close()
+
+
+def test_reassign_with_kmers_shared_by_hundreds_of_genomes(ctx):
+    """The winner pass when 400 strains hold (almost) the same k-mers in genome_kmers AND in their tracked sets: overflow runs of
+    hundreds of postings in both indexes, walked by the whole wavefront; winner = highest first-pass ANI, ties to the first in
+    the passing list; strains outside the passing list neither win nor lose; every genome's kept coverages and kmers_lost
+    against a direct restatement of winner_table + the winner pass (contain.rs:410-430, :637-646)."""
+    rng = np.random.default_rng(123)
+    thr = O.threshold(200)
+    core = np.unique(rng.integers(0, thr, size=250, dtype=np.uint64))
+    tcore = np.unique(rng.integers(0, thr, size=120, dtype=np.uint64))
+    G = 460
+    genomes, tracked = [], []
+    for g in range(G):
+        if g < 400:
+            genomes.append(np.concatenate([core[rng.random(len(core)) < 0.95], rng.integers(0, thr, size=20, dtype=np.uint64)]))
+            # tracked sets: the shared tracked core + some of the OTHER strains' genome k-mers (they can steal ownership)
+            tracked.append(np.concatenate([tcore[rng.random(len(tcore)) < 0.9], core[rng.random(len(core)) < 0.05]]))
+        else:
+            genomes.append(np.concatenate([rng.integers(0, thr, size=200, dtype=np.uint64), tcore[:30], core[:5]]))
+            tracked.append(np.zeros(0, dtype=np.uint64))
+    sk = np.unique(np.concatenate([core, tcore, rng.integers(0, thr, size=3000, dtype=np.uint64)] + [g[-20:] for g in genomes[:50]]))
+    sc = rng.integers(0, 5, size=len(sk)).astype(np.uint32)
+    check_reassign(ctx, genomes, tracked, sk, sc, rng, min_passing=250, min_lost=10000)
+    # the boundary database: runs of every length around LONG_RUN_MIN and the 64-entry step in the kept index, tracked sets among
+    # the genomes that do NOT hold a shared k-mer (they can steal it), separate buckets and the one wrapped bucket
+    for extremes in (False, True):
+        genomes, sk = boundary_db(extremes)
+        tracked = [np.array([j << 40 for j in BOUNDARY_JS if j <= g and (g + j) % 3 == 0], dtype=np.uint64) for g in range(len(genomes))]
+        sc = rng.integers(0, 5, size=len(sk)).astype(np.uint32)
+        sc[sk == np.uint64(207 << 40)] = 2
+        # (at least 100 of the 210 genomes pass, 207 of them hold k-mer 207 << 40 and one wins it: 96 or more lose it)
+        check_reassign(ctx, genomes, tracked, sk, sc, rng, min_passing=100, min_lost=95)
 
 
 # ---------------------------------------------------------------------------------------------- fuzz over read shapes

@@ -6,7 +6,7 @@ name=$1; flags=$2; shift 2
 cd "$(dirname "$0")/../sylph_amd/csrc" || exit 1
 make -j8 > /dev/null || exit 1
 SRC="$PWD"; tmp=/tmp/sylph_variant_$name; mkdir -p $tmp
-all="capi prims seeds sketch replay_lds a10 contain hits shard genomes reads pipeline fastq inflate"
+all="capi prims seeds sketch replay_lds a10 line_index contain hits shard genomes reads pipeline fastq inflate"
 objs=""
 for f in $all; do
   if [[ " $* " == *" $f.hip "* ]]; then
