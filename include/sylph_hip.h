@@ -232,6 +232,17 @@ int sylph_fastq_counts(const sylph_fastq *f, uint64_t *n_records, uint64_t *n_ba
 int sylph_fastq_lengths(sylph_fastq *f, uint64_t first, uint64_t n, uint32_t *out);
 int sylph_sketch_push_fastq(sylph_sketch *sk, sylph_fastq *a, sylph_fastq *b, uint64_t first, uint64_t n_items);
 void sylph_fastq_destroy(sylph_fastq *f);
+/* The records of a WINDOW of a text that arrives in pieces (sylph_inflate_stream_next).  final == 0: the COMPLETE four-line records
+ * of the text are indexed — only a line that ends in a newline inside the text counts as complete — and *consumed says where they
+ * end: the start of the first line that belongs to no complete record (the caller keeps the text from there for the next window).
+ * Zero records is not an error (*consumed = 0), neither is an empty text.  final != 0: exactly sylph_fastq_index (*consumed = n_bytes).
+ * Kernels, acceptance rule and refusals are sylph_fastq_index's. */
+int sylph_fastq_index_window(sylph_ctx *ctx, const void *text, uint64_t n_bytes, int mem, int final, sylph_fastq **out,
+                             uint64_t *consumed);
+/* Where record `record` of such an index begins in its text (its '@'); record == the number of records: where the text behind the last
+ * record begins (final == 0: *consumed; final != 0: one past the text without its trailing blank space).  A caller that pushes fewer
+ * records than a window holds keeps the text from there. */
+int sylph_fastq_record_offset(sylph_fastq *f, uint64_t record, uint64_t *offset);
 
 /* ---- FASTA text, its records found and joined on the device (csrc/fasta.hip) -------------------------------------------------
  * Replaces the record loops of sketch.rs:488-492 / :557-563 (needletail parse_fastx_file + next() over a genome file) for FASTA text:
@@ -289,6 +300,33 @@ int sylph_inflated_info(const sylph_inflated *t, uint64_t *n_members, uint64_t *
                         uint64_t *n_host_members, uint64_t *n_decoded_again);
 int sylph_inflated_read(sylph_inflated *t, uint64_t first, uint64_t n, void *host_out);
 void sylph_inflated_destroy(sylph_inflated *t);
+/* sylph_inflate_files declines this many gzip bytes (all files of the call together) or more; such a sample is streamed. */
+#define SYLPH_INFLATE_WHOLE_MAX_BYTES (3ull << 30)
+
+/* ---- gzip streamed through the device inflate in bounded memory (csrc/inflate.hip, inflate_stream_plan.h) -----------------------
+ * sylph_inflate_files uploads a file whole and reserves 32 B of scratch per compressed byte.  A stream runs the same phases over ONE
+ * SLICE of every advancing file's compressed bytes per call (slice_bytes each, plus a short overlap; 0 = the context's
+ * "inflate_slice_bytes", else the default; at least 64 KiB) and carries the chain's state, the member's CRC register and the last
+ * 32 KiB of text across the cut: scratch and text are a function of the slice, not of the file.  gz[i] is host memory that holds file i
+ * whole (a mapping is fine) and stays valid until the stream is destroyed.
+ * One step, sylph_inflate_stream_next: file i with advance[i] != 0 (NULL = all) is decoded one slice further.  The new window of file i
+ * = bytes [keep_from[i], end) of its previous window (NULL / first call: nothing) followed by the newly inflated bytes.  *window is a
+ * sylph_inflated (sylph_inflated_file(t, i, ..) gives file i's text; sylph_inflated_info counts the slice's members and blocks); the
+ * caller destroys it.  The previous window must be alive during this call and may be destroyed after it.  finished[i] = 1 once file i
+ * has no more bytes to give.
+ * Anything that does not add up in any slice — a broken chain, a CRC or ISIZE that differs, garbage behind a member, a block that fits
+ * no slice — makes the call return SYLPH_ERR_FORMAT (no room: SYLPH_ERR_NOMEM): the stream is dead then, the context is fine, and
+ * the caller reads the files with its own reader from their start.  A stream never hands out a byte that zlib would not have produced
+ * before that point.  sylph_inflate_stream_info: slices decoded, text bytes handed out (kept bytes not counted), the largest scratch
+ * (bytes) any call reserved, the largest window.  A stream belongs to its context and must be destroyed before it. */
+typedef struct sylph_inflate_stream sylph_inflate_stream;
+int sylph_inflate_stream_open(sylph_ctx *ctx, const void *const *gz, const uint64_t *n_bytes, uint32_t n_files, int mem,
+                              uint64_t slice_bytes, sylph_inflate_stream **out);
+int sylph_inflate_stream_next(sylph_inflate_stream *st, const uint8_t *advance, const uint64_t *keep_from, sylph_inflated **window,
+                              uint8_t *finished);
+int sylph_inflate_stream_info(const sylph_inflate_stream *st, uint64_t *n_slices, uint64_t *text_bytes, uint64_t *peak_scratch_bytes,
+                              uint64_t *peak_window_bytes);
+void sylph_inflate_stream_destroy(sylph_inflate_stream *st);
 
 /* ---- bzip2 decoded on the device (csrc/bunzip2.hip) ------------------------------------------------------------------------------
  * The reference reads a .bz2 file through needletail -> libbz2 on the thread that sketches it.  sylph_bunzip2 takes the COMPRESSED

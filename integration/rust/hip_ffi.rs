@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphFastq { _p: [u8; 0] }
 #[repr(C)] pub struct SylphFasta { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
+#[repr(C)] pub struct SylphInflateStream { _p: [u8; 0] }
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
@@ -126,6 +127,9 @@ extern "C" {
     pub fn sylph_fastq_lengths(f: *mut SylphFastq, first: u64, n: u64, out: *mut u32) -> c_int;
     pub fn sylph_sketch_push_fastq(sk: *mut SylphSketch, a: *mut SylphFastq, b: *mut SylphFastq, first: u64, n_items: u64) -> c_int;
     pub fn sylph_fastq_destroy(f: *mut SylphFastq);
+    // the complete four-line records of one window of a streamed text (final = 0; *consumed: where they end) — final != 0: sylph_fastq_index
+    pub fn sylph_fastq_index_window(ctx: *mut SylphCtx, text: *const c_void, n_bytes: u64, mem: c_int, is_final: c_int, out: *mut *mut SylphFastq, consumed: *mut u64) -> c_int;
+    pub fn sylph_fastq_record_offset(f: *mut SylphFastq, record: u64, offset: *mut u64) -> c_int;   // where a record of a window's index begins
     // FASTA text (genome files) indexed and joined on the device; ERR_FORMAT = -5: keep the needletail reader for this file
     pub fn sylph_fasta_index(ctx: *mut SylphCtx, text: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphFasta) -> c_int;
     pub fn sylph_fasta_counts(f: *const SylphFasta, n_records: *mut u64, n_bases: *mut u64, id_bytes: *mut u64) -> c_int;
@@ -147,6 +151,12 @@ extern "C" {
                                n_host_members: *mut u64, n_decoded_again: *mut u64) -> c_int;
     pub fn sylph_inflated_read(t: *mut SylphInflated, first: u64, n: u64, host_out: *mut c_void) -> c_int;
     pub fn sylph_inflated_destroy(t: *mut SylphInflated);
+    // gzip streamed through the device inflate in bounded memory: one slice of every advancing file per call; the window = the kept tail
+    // of the previous window + the new bytes (a SylphInflated, destroyed by the caller); ERR_FORMAT: the stream is dead, read on the host
+    pub fn sylph_inflate_stream_open(ctx: *mut SylphCtx, gz: *const *const c_void, n_bytes: *const u64, n_files: u32, mem: c_int, slice_bytes: u64, out: *mut *mut SylphInflateStream) -> c_int;
+    pub fn sylph_inflate_stream_next(st: *mut SylphInflateStream, advance: *const u8, keep_from: *const u64, window: *mut *mut SylphInflated, finished: *mut u8) -> c_int;
+    pub fn sylph_inflate_stream_info(st: *const SylphInflateStream, n_slices: *mut u64, text_bytes: *mut u64, peak_scratch_bytes: *mut u64, peak_window_bytes: *mut u64) -> c_int;
+    pub fn sylph_inflate_stream_destroy(st: *mut SylphInflateStream);
     // bzip2 decoded on the device (what needletail's BzDecoder does inside parse_fastx_file): the same handle as sylph_inflate's;
     // ERR_FORMAT = -5: keep the libbz2 reader for this file
     pub fn sylph_bunzip2(ctx: *mut SylphCtx, bz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;

@@ -38,10 +38,11 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_upload_begin", "sylph_upload_chunk", "sylph_upload_commit", "sylph_upload_finish", "sylph_upload_restart", "sylph_upload_destroy",
            "sylph_db_replicate", "sylph_pipeline_create_multi", "sylph_pipeline_replica_of_last", "sylph_device_count",
            "sylph_genome_shard_bounds", "sylph_db_upload_genome_shard",
-           "sylph_fastq_index", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
+           "sylph_fastq_index", "sylph_fastq_index_window", "sylph_fastq_record_offset", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
            "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
            "sylph_sketch_genomes_fasta",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
+           "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
            "sylph_bunzip2", "sylph_bunzip2_files", "sylph_bootstrap_counts"]
 
 
@@ -79,6 +80,8 @@ def load():
     L.sylph_sketch_push_n.argtypes = [vp, vp, vp, u64, u64, i32]
     L.sylph_sketch_push_enc.argtypes = [vp, vp, vp, u64, u64, i32, i32]
     L.sylph_fastq_index.argtypes = [vp, vp, u64, i32, P(vp)]
+    L.sylph_fastq_index_window.argtypes = [vp, vp, u64, i32, i32, P(vp), P(u64)]
+    L.sylph_fastq_record_offset.argtypes = [vp, u64, P(u64)]
     L.sylph_fastq_counts.argtypes = [vp, P(u64), P(u64)]
     L.sylph_fastq_lengths.argtypes = [vp, u64, u64, vp]
     L.sylph_sketch_push_fastq.argtypes = [vp, vp, vp, u64, u64]
@@ -100,6 +103,11 @@ def load():
     L.sylph_inflated_read.argtypes = [vp, u64, u64, vp]
     L.sylph_inflated_destroy.argtypes = [vp]
     L.sylph_inflated_destroy.restype = None
+    L.sylph_inflate_stream_open.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, u64, P(vp)]
+    L.sylph_inflate_stream_next.argtypes = [vp, P(C.c_uint8), P(u64), P(vp), P(C.c_uint8)]
+    L.sylph_inflate_stream_info.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+    L.sylph_inflate_stream_destroy.argtypes = [vp]
+    L.sylph_inflate_stream_destroy.restype = None
     L.sylph_bunzip2.argtypes = [vp, vp, u64, i32, P(vp)]
     L.sylph_bunzip2_files.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, P(vp)]
     L.sylph_pack_2bit.argtypes = [vp, u64, vp]
@@ -372,6 +380,73 @@ class Inflated:
 
 
 
+class InflateWindow(Inflated):
+    """One window of an InflateStream: .files[i] = (dev_ptr, n_bytes) of file i's text — the kept tail of its previous window, then the
+    newly inflated bytes.  The same handle as Inflated's (read(), close())."""
+
+    def __init__(self, handle, n_files):
+        self._h = handle
+        self.files = []
+        for i in range(n_files):
+            fp, fn = C.c_void_p(), C.c_uint64(0)
+            _check(load().sylph_inflated_file(self._h, i, C.byref(fp), C.byref(fn)))
+            self.files.append((int(fp.value or 0), int(fn.value)))
+        p, n = C.c_void_p(), C.c_uint64(0)
+        _check(load().sylph_inflated_text(self._h, C.byref(p), C.byref(n)))
+        self.dev_ptr, self.n_bytes = int(p.value or 0), int(n.value)
+        a, b, c, d, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(load().sylph_inflated_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
+        self.n_members, self.n_blocks, self.n_candidates, self.n_host_members, self.n_decoded_again = (int(x.value) for x in (a, b, c, d, e))
+
+    def read_file(self, i):
+        """file i's text of this window, on the host"""
+        first = self.files[i][0] - self.dev_ptr
+        return self.read(first, self.files[i][1]).tobytes()
+
+
+class InflateStream:
+    """sylph_inflate_stream_*: gzip files (a list of bytes / uint8 arrays, host memory, kept alive here) inflated on the device one slice
+    of compressed bytes at a time, in memory bounded by the slice (csrc/inflate.hip, inflate_stream_plan.h).  next(advance, keep_from)
+    -> InflateWindow; .finished[i] says when file i has given everything.  The previous window must be open during next().  Raises
+    SylphHipError with code ERR_FORMAT when a slice does not add up: the stream is dead then, inflate on the host."""
+
+    def __init__(self, ctx, gz, slice_bytes=0):
+        self._h = None
+        self._keeps = [np.frombuffer(g, dtype=np.uint8) if isinstance(g, (bytes, bytearray, memoryview)) else _np(g, np.uint8) for g in gz]
+        ptrs = (C.c_void_p * len(self._keeps))(*[k.ctypes.data for k in self._keeps])
+        lens = (C.c_uint64 * len(self._keeps))(*[len(k) for k in self._keeps])
+        h = C.c_void_p()
+        _check(load().sylph_inflate_stream_open(ctx._h, ptrs, lens, len(self._keeps), MEM_HOST, int(slice_bytes), C.byref(h)))
+        self._h = h
+        self.n_files = len(self._keeps)
+        self.finished = [False] * self.n_files
+
+    def next(self, advance=None, keep_from=None):
+        adv = (C.c_uint8 * self.n_files)(*[1 if a else 0 for a in advance]) if advance is not None else None
+        keep = (C.c_uint64 * self.n_files)(*[int(k) for k in keep_from]) if keep_from is not None else None
+        fin = (C.c_uint8 * self.n_files)()
+        w = C.c_void_p()
+        _check(load().sylph_inflate_stream_next(self._h, adv, keep, C.byref(w), fin))
+        self.finished = [bool(x) for x in fin]
+        return InflateWindow(w, self.n_files)
+
+    def info(self):
+        a, b, c, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(load().sylph_inflate_stream_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(n_slices=int(a.value), text_bytes=int(b.value), peak_scratch_bytes=int(c.value), peak_window_bytes=int(d.value))
+
+    def close(self):
+        if self._h:
+            load().sylph_inflate_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Bunzipped(Inflated):
     """sylph_bunzip2: the bytes of one bzip2 file (or a list of them: sylph_bunzip2_files) decoded on the device (csrc/bunzip2.hip),
     the same handle as Inflated's.  n_members = streams, n_blocks = bzip2 blocks, n_candidates = block magics decoded.  Raises
@@ -383,15 +458,24 @@ class FastqText:
     (MEM_HOST), or an integer address with n_bytes (MEM_HOST_PINNED / MEM_DEVICE; device text is borrowed until close()).
     Raises SylphHipError with code ERR_FORMAT when the text is not exactly that: parse it on the host then."""
 
-    def __init__(self, ctx, text, mem=MEM_HOST, n_bytes=None):
+    def __init__(self, ctx, text, mem=MEM_HOST, n_bytes=None, final=None):
+        """final: None = sylph_fastq_index; 0 / 1 = sylph_fastq_index_window (the complete records of a window of a longer text;
+        .consumed = where they end)"""
         self._h = None
         h = C.c_void_p()
+        used = C.c_uint64(0)
         if mem == MEM_HOST:
             self._keep = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else _np(text, np.uint8)
-            _check(load().sylph_fastq_index(ctx._h, _ptr(self._keep) if len(self._keep) else None, len(self._keep), mem, C.byref(h)))
-            self._keep = None
+            ptr, n = (_ptr(self._keep) if len(self._keep) else None), len(self._keep)
         else:
-            _check(load().sylph_fastq_index(ctx._h, C.c_void_p(int(text)), int(n_bytes), mem, C.byref(h)))
+            ptr, n = C.c_void_p(int(text)), int(n_bytes)
+        if final is None:
+            _check(load().sylph_fastq_index(ctx._h, ptr, n, mem, C.byref(h)))
+        else:
+            _check(load().sylph_fastq_index_window(ctx._h, ptr, n, mem, int(final), C.byref(h), C.byref(used)))
+        self.consumed = int(used.value) if final is not None else n
+        if mem == MEM_HOST:
+            self._keep = None
         self._h = h
         nr, nb = C.c_uint64(0), C.c_uint64(0)
         _check(load().sylph_fastq_counts(self._h, C.byref(nr), C.byref(nb)))
@@ -402,6 +486,12 @@ class FastqText:
         out = np.zeros(n, dtype=np.uint32)
         _check(load().sylph_fastq_lengths(self._h, int(first), int(n), _ptr(out)))
         return out
+
+    def record_offset(self, record):
+        """sylph_fastq_record_offset (an index made with final=0 / 1): where the record begins in the text"""
+        v = C.c_uint64(0)
+        _check(load().sylph_fastq_record_offset(self._h, int(record), C.byref(v)))
+        return int(v.value)
 
     def close(self):
         if self._h:

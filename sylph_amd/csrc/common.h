@@ -150,6 +150,8 @@ struct sylph_ctx {
     uint32_t shard_reduce = 0;              // "shard_reduce": 0 = the sharded batch's hits travel by all-to-all (default), 1 = by ONE all-gather (north_star's wording; shard_plan.h plan_hits_gather)
     uint32_t bootstrap_shape = 0;           // "bootstrap_shape": how sylph_bootstrap_counts gets a drawn index's value, 0 = gather (default), 1 = table of boundaries (bootstrap.hip)
     uint32_t bootstrap_bins = 64;           // "bootstrap_bins" (tests lower it): an item of sylph_bootstrap_counts with a kept value of this or more declines
+    uint64_t inflate_slice_bytes = 0;       // "inflate_slice_bytes" (tests lower it): compressed bytes per slice of a sylph_inflate_stream opened with slice_bytes 0; 0 = the default (inflate_stream_plan.h)
+    uint64_t inflate_whole_max_bytes = SYLPH_INFLATE_WHOLE_MAX_BYTES;   // "inflate_whole_max_bytes" (tests lower it): sylph_inflate_files declines this many gzip bytes or more
     uint32_t fail_next_peer_copy = 0;       // fault injection for the tests ("fail_next_peer_copy"): the next sylph_db_replicate INTO this context finds no device-to-device road
     uint32_t fail_next_shard_probe = 0;     // fault injection for the tests ("fail_next_shard_probe"): the next sharded probe on this context throws
     uint32_t index_lambda = 0;              // 0 = the default for the line size (contain_index.h DEFAULT_INDEX_LAMBDA: 4 per 64-byte line); postings per bucket line of a database index aimed for ("index_lambda"; r04: 3 -> 4, 38.5 -> 29.1 GB at GTDB scale for +3 % probe time alone)

@@ -29,8 +29,10 @@ struct sylph_fastq {
     const uint8_t* text = nullptr;        // device pointer to byte 0
     uint64_t n = 0;                       // bytes without the trailing blank space
     sylph::DevBuf seq_start, seq_len;     // u64 / u32 per record
+    sylph::DevBuf rec_start;              // sylph_fastq_index_window only: u64 per record + one, where its '@' line starts (the last: behind the records)
+    bool has_starts = false;
     uint64_t n_rec = 0, n_bases = 0;
-    explicit sylph_fastq(sylph_ctx* c) : ctx(c), text_own(c), seq_start(c), seq_len(c) {}
+    explicit sylph_fastq(sylph_ctx* c) : ctx(c), text_own(c), seq_start(c), seq_len(c), rec_start(c) {}
 };
 
 namespace sylph {
@@ -121,9 +123,14 @@ __global__ __launch_bounds__(256) void fq_gather_kernel(const uint8_t* __restric
 
 struct FormatError { std::string msg; };
 
+// rec_start[r] = line_start[4 r], r = 0 .. n_rec: where every record begins, and where the text behind the last one does
+__global__ void fq_record_starts_kernel(const uint64_t* __restrict__ line_start, uint64_t n_rec, uint64_t* __restrict__ rec_start) {
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_rec; r += (uint64_t)gridDim.x * blockDim.x) rec_start[r] = line_start[4 * r];
+}
+
 uint32_t grid1(uint64_t n, uint32_t tpb = 256, uint32_t cap = 1u << 20) { return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, (n + tpb - 1) / tpb)); }
 
-void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem) {
+void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem, bool want_starts = false) {
     sylph_ctx* ctx = f->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
@@ -174,6 +181,80 @@ void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int me
     ctx->read_back(&hw, d_w, sizeof(hw));
     if (hw.bad_rec != ~0ull) throw FormatError{"record " + std::to_string(hw.bad_rec) + " is not a four-line record ('@' line, sequence, '+' line, quality of the sequence's length)"};
     f->n_bases = hw.n_bases;
+    if (want_starts) {                                                    // (a window's index: line_start[4 n_rec] = n + 1, the virtual newline's)
+        f->rec_start.reserve((f->n_rec + 1) * 8);
+        hipLaunchKernelGGL(fq_record_starts_kernel, dim3(grid1(f->n_rec + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_lines.as<uint64_t>(), f->n_rec,
+                           f->rec_start.as<uint64_t>());
+        SY_HIP(hipGetLastError());
+        f->has_starts = true;
+    }
+}
+
+// The COMPLETE records of a window of a text that goes on behind it (sylph_fastq_index_window, final == 0): nothing is trimmed, a line
+// is one that ends in a newline inside the text, the records are the whole groups of four such lines, and *consumed is where the first
+// line behind them starts.  The kernels are fastq_index_impl's: with n_lines = 4 * n_rec + 1 the line kernel writes the starts of lines
+// 0 .. 4 * n_rec — the last of them is `consumed`, and the end of the last record's quality line + 1, as between two records of a
+// whole text.
+void fastq_window_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem, uint64_t* consumed) {
+    sylph_ctx* ctx = f->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard dg(ctx->device);
+    *consumed = 0;
+    f->n = 0;
+    if (!n_bytes) return;
+    if (mem == SYLPH_MEM_DEVICE) {
+        f->text = (const uint8_t*)text;
+    } else {
+        f->text_own.reserve(n_bytes + 64);
+        if (mem == SYLPH_MEM_HOST_PINNED) SY_HIP(hipMemcpyAsync(f->text_own.p, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+        else ctx->h2d(f->text_own.p, text, n_bytes);
+        f->text = f->text_own.as<uint8_t>();
+    }
+    const uint32_t bias = (uint32_t)((uintptr_t)f->text & 15);
+    const uint8_t* al = f->text - bias;
+    const uint64_t n_tiles = (n_bytes + bias + FQ_TILE - 1) / FQ_TILE;
+    SY_REQUIRE(n_tiles < (1ull << 31), "sylph_fastq_index_window: text too large for one index (%llu bytes)", (unsigned long long)n_bytes);
+    DevBuf& b_words = ctx->scratch[0];
+    DevBuf& b_cnt = ctx->scratch[1];
+    DevBuf& b_base = ctx->scratch[2];
+    DevBuf& b_lines = ctx->scratch[3];
+    b_words.reserve(sizeof(FqWords));
+    b_cnt.reserve((n_tiles + 1) * 4);
+    b_base.reserve((n_tiles + 1) * 4);
+    FqWords* d_w = b_words.as<FqWords>();
+    FqWords hw{n_bytes, ~0ull, 0, 0, 0};
+    ctx->h2d(d_w, &hw, sizeof(hw));
+    SY_HIP(hipMemsetAsync(b_cnt.as<uint32_t>() + n_tiles, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(fq_count_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_cnt.as<uint32_t>());
+    SY_HIP(hipGetLastError());
+    exclusive_sum_u32(ctx, b_cnt.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles + 1);
+    uint32_t n_nl = 0;
+    ctx->read_back(&n_nl, b_base.as<uint32_t>() + n_tiles, 4);
+    ctx->read_back(&hw, d_w, sizeof(hw));
+    if (hw.n_nl != (unsigned long long)n_nl) throw FormatError{std::to_string(hw.n_nl) + " lines: at most 2^32 - 1 per index"};
+    f->n_rec = n_nl / 4;
+    if (!f->n_rec) return;
+    const uint64_t n_lines = 4 * f->n_rec + 1;
+    b_lines.reserve((n_lines + 1) * 8);
+    f->seq_start.reserve(f->n_rec * 8);
+    f->seq_len.reserve(f->n_rec * 4 + 4);
+    hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_base.as<uint32_t>(), n_lines,
+                       b_lines.as<uint64_t>());
+    hipLaunchKernelGGL(fq_records_kernel, dim3(grid1(f->n_rec, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, b_lines.as<uint64_t>(), f->n_rec,
+                       f->seq_start.as<uint64_t>(), f->seq_len.as<uint32_t>(), d_w);
+    SY_HIP(hipGetLastError());
+    ctx->read_back(&hw, d_w, sizeof(hw));
+    if (hw.bad_rec != ~0ull) throw FormatError{"record " + std::to_string(hw.bad_rec) + " is not a four-line record ('@' line, sequence, '+' line, quality of the sequence's length)"};
+    unsigned long long end = 0;
+    ctx->read_back(&end, b_lines.as<uint64_t>() + 4 * f->n_rec, 8);
+    f->rec_start.reserve((f->n_rec + 1) * 8);
+    hipLaunchKernelGGL(fq_record_starts_kernel, dim3(grid1(f->n_rec + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_lines.as<uint64_t>(), f->n_rec,
+                       f->rec_start.as<uint64_t>());
+    SY_HIP(hipGetLastError());
+    f->has_starts = true;
+    f->n_bases = hw.n_bases;
+    f->n = end;
+    *consumed = end;
 }
 
 }  // namespace
@@ -203,6 +284,46 @@ int sylph_fastq_index(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int me
     }
     *out = f;
     return SYLPH_OK;
+}
+
+int sylph_fastq_index_window(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, int final, sylph_fastq** out, uint64_t* consumed) {
+    if (!ctx || !out || !consumed || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    *out = nullptr;
+    *consumed = 0;
+    if (final && n_bytes == 0) { set_error("sylph_fastq_index: no text"); return SYLPH_ERR_FORMAT; }
+    ctx->refs.fetch_add(1);
+    sylph_fastq* f = nullptr;
+    int format = 0;
+    const int rc = guarded([&] {
+        f = new sylph_fastq(ctx);
+        try {
+            if (final) { fastq_index_impl(f, text, n_bytes, mem, true); *consumed = n_bytes; }      // sylph_fastq_index's code, + the records' starts
+            else fastq_window_impl(f, text, n_bytes, mem, consumed);
+        } catch (const FormatError& e) { set_error("%s: not plain four-line FASTQ: %s", final ? "sylph_fastq_index" : "sylph_fastq_index_window", e.msg.c_str()); format = 1; }
+    });
+    if (rc != SYLPH_OK || format) {
+        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); delete f; }
+        ctx_unref(ctx);
+        *consumed = 0;
+        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
+    }
+    *out = f;
+    return SYLPH_OK;
+}
+
+int sylph_fastq_record_offset(sylph_fastq* f, uint64_t record, uint64_t* offset) {
+    return guarded([&] {
+        SY_REQUIRE(f && offset, "null argument");
+        SY_REQUIRE(f->has_starts || f->n_rec == 0, "sylph_fastq_record_offset: only an index made by sylph_fastq_index_window knows where its records start");
+        SY_REQUIRE(record <= f->n_rec, "sylph_fastq_record_offset: record %llu of %llu", (unsigned long long)record, (unsigned long long)f->n_rec);
+        if (!f->has_starts) { *offset = f->n; return; }
+        std::lock_guard<std::mutex> lock(f->ctx->mu);
+        DeviceGuard dg(f->ctx->device);
+        unsigned long long v = 0;
+        f->ctx->d2h(&v, f->rec_start.as<uint64_t>() + record, 8);
+        *offset = v;
+    });
 }
 
 int sylph_fastq_counts(const sylph_fastq* f, uint64_t* n_records, uint64_t* n_bases) {

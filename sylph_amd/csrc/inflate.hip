@@ -35,6 +35,23 @@
 
 #include "decode_host.h"
 #include "inflate_plan.h"
+#include "inflate_stream_plan.h"
+
+// What a stream holds between two calls: every file's carry, its last 32 KiB of text (two buffers per file, taking turns), and where the
+// window it handed out last lies (the caller keeps that alive for the next call: its kept tail is copied from there).
+struct sylph_inflate_stream {
+    sylph_ctx* ctx = nullptr;
+    std::vector<const uint8_t*> gz;
+    std::vector<uint64_t> n_bytes;
+    uint64_t slice_bytes = 0, ratio = 0;
+    std::vector<sylph::inflate_stream_plan::Carry> carry;
+    uint8_t* win = nullptr;                       // [n_files][2][WINDOW]
+    std::vector<uint8_t> win_cur;                 // which of a file's two buffers is current
+    std::vector<const uint8_t*> prev_text;        // file i's text in the window handed out last
+    std::vector<uint64_t> prev_len;
+    bool dead = false;
+    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+};
 
 namespace sylph {
 namespace {
@@ -443,12 +460,14 @@ struct DecodeOut {                       // n, flushed, cap: wave-uniform
 };
 
 template <uint32_t RING>
-__global__ __launch_bounds__(64) void decode_kernel(const uint32_t* __restrict__ gzw, uint64_t n_words, const DecodeJob* __restrict__ jobs, uint16_t* __restrict__ cells,
+__global__ __launch_bounds__(64) void decode_kernel(const uint32_t* __restrict__ gzw, uint64_t n_words_all, const DecodeJob* __restrict__ jobs, uint16_t* __restrict__ cells,
                                                     Spill spill, uint32_t* __restrict__ spill_next, BlockResult* __restrict__ res) {
     constexpr uint32_t RING_MASK = RING - 1;
     __shared__ WaveTables<RING> T;
     const uint32_t k = blockIdx.x, lane = threadIdx.x;
     const DecodeJob job = jobs[k];
+    // the words this block may read: all of the launch's, or (a slice of the stream, which ends where another file's slice begins) fewer
+    const uint64_t n_words = job.limit_words ? min((uint64_t)job.limit_words, n_words_all) : n_words_all;
     const uint64_t start = job.start_bit;
     const uint64_t region = job.region;
     DecodeOut<RING> o;
@@ -778,11 +797,13 @@ __global__ __launch_bounds__(WIN_TPB) void winfn_kernel(const PlanBlock* __restr
 }
 
 // the real window in front of every group, one group after the other
-__global__ __launch_bounds__(WIN_TPB) void winchain_kernel(const uint16_t* __restrict__ ffn, uint32_t n_groups, uint8_t* __restrict__ rwin) {
+// (entry: the 32 KiB in front of the chain's first block — the text the stream's earlier slices gave this file; null = nothing)
+__global__ __launch_bounds__(WIN_TPB) void winchain_kernel(const uint16_t* __restrict__ ffn, uint32_t n_groups, uint8_t* __restrict__ rwin,
+                                                           const uint8_t* __restrict__ entry) {
     __shared__ uint8_t R[2][WINDOW];
     uint8_t* cur = R[0];
     uint8_t* nxt = R[1];
-    for (uint32_t j = threadIdx.x; j < WINDOW; j += WIN_TPB) cur[j] = 0;
+    for (uint32_t j = threadIdx.x; j < WINDOW; j += WIN_TPB) cur[j] = entry ? entry[j] : (uint8_t)0;
     __syncthreads();
     for (uint32_t g = 0; g < n_groups; g++) {
         uint8_t* dst = rwin + (uint64_t)g * WINDOW;
@@ -794,6 +815,15 @@ __global__ __launch_bounds__(WIN_TPB) void winchain_kernel(const uint16_t* __res
         }
         __syncthreads();
         uint8_t* sw = cur; cur = nxt; nxt = sw;
+    }
+}
+
+// the window behind a slice: the last 32 KiB of (the window in front of it ++ the n_new bytes it gave)
+__global__ __launch_bounds__(WIN_TPB) void window_tail_kernel(const uint8_t* __restrict__ old_win, const uint8_t* __restrict__ fresh, uint64_t n_new,
+                                                              uint8_t* __restrict__ new_win) {
+    for (uint32_t j = blockIdx.x * WIN_TPB + threadIdx.x; j < WINDOW; j += gridDim.x * WIN_TPB) {
+        const uint64_t back = WINDOW - j;                                        // byte j lies `back` bytes in front of the end
+        new_win[j] = back <= n_new ? fresh[n_new - back] : old_win[j + n_new];
     }
 }
 
@@ -978,6 +1008,21 @@ bool zlib_member(const uint8_t* gz, size_t n, size_t p, size_t* end, std::vector
     return ok;
 }
 
+// one wavefront per job over the compressed words in S.gz (the spill arena's counter: S.cnt, word 2)
+void launch_decode_jobs(sylph_ctx* ctx, InflateScratch& S, uint64_t n_words, const DecodeJob* jobs, uint32_t n_jobs, uint16_t* out_cells, const Spill& sp,
+                        BlockResult* out) {
+    hipStream_t s = ctx->stream;
+    int n_cu = 256;
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    uint32_t* const spill_next = reinterpret_cast<uint32_t*>(S.cnt.as<unsigned long long>() + 2);
+    // the larger ring while all blocks' wavefronts fit on the chip beside each other with it (LDS: ~13 KB per wavefront -> 12 per CU)
+    if (n_jobs <= (uint32_t)n_cu * 12 && !getenv("SYLPH_HIP_INFLATE_SMALL_RING"))
+        hipLaunchKernelGGL(decode_kernel<4096>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
+    else
+        hipLaunchKernelGGL(decode_kernel<2048>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
+    SY_HIP(hipGetLastError());
+}
+
 // Several files in one call are ONE stream of gzip members to everything below (`cat a.gz b.gz` is a gzip file): their bytes lie back
 // to back on the device, one scan, one decode launch, one chain — the two mates of a pair share the latency of a block's wavefront
 // (~15 ms whatever the file's size) instead of paying it one after the other.
@@ -1042,15 +1087,7 @@ struct InflateCall {
     }
 
     void launch_decode(const DecodeJob* jobs, uint32_t n_jobs, uint16_t* out_cells, const Spill& sp, BlockResult* out) {
-        int n_cu = 256;
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        uint32_t* const spill_next = reinterpret_cast<uint32_t*>(S.cnt.as<unsigned long long>() + 2);
-        // the larger ring while all blocks' wavefronts fit on the chip beside each other with it (LDS: ~13 KB per wavefront -> 12 per CU)
-        if (n_jobs <= (uint32_t)n_cu * 12 && !getenv("SYLPH_HIP_INFLATE_SMALL_RING"))
-            hipLaunchKernelGGL(decode_kernel<4096>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
-        else
-            hipLaunchKernelGGL(decode_kernel<2048>, dim3(n_jobs), dim3(64), 0, s, S.gz.as<uint32_t>(), n_words, jobs, out_cells, sp, spill_next, out);
-        SY_HIP(hipGetLastError());
+        launch_decode_jobs(ctx, S, n_words, jobs, n_jobs, out_cells, sp, out);
     }
 
     // ---- decode every candidate into its region: `ratio` cells per compressed byte up to the next candidate, + REGION_SLACK.  The ratio
@@ -1169,7 +1206,7 @@ struct InflateCall {
             std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
             hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>(), KB, G, S.sfn.as<uint16_t>(), S.ffn.as<uint16_t>());
             SY_HIP(hipGetLastError());
-            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, S.ffn.as<uint16_t>(), NG, S.rwin.as<uint8_t>());
+            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, S.ffn.as<uint16_t>(), NG, S.rwin.as<uint8_t>(), (const uint8_t*)nullptr);
             SY_HIP(hipGetLastError());
         }
         ScopedKernelTimer kt(ctx, "inflate_translate");
@@ -1224,7 +1261,8 @@ void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_b
     Segments segs = segments_of(gzs, n_bytes, n_files);
     for (uint32_t i = 0; i < n_files; i++)
         if (!member_body(segs.ptr[i], (size_t)n_bytes[i], 0)) throw FormatDecline{"not a gzip file"};
-    if (segs.total() >= (3ull << 30)) throw FormatDecline{"3 GiB of gzip bytes or more: the host reader takes them"};
+    if (segs.total() >= SYLPH_INFLATE_WHOLE_MAX_BYTES) throw FormatDecline{"3 GiB of gzip bytes or more: the host reader takes them"};
+    if (segs.total() >= ctx->inflate_whole_max_bytes) throw FormatDecline{"more gzip bytes than \"inflate_whole_max_bytes\" allows in one piece"};
     DeviceScratch& DS = device_scratch(ctx->device);
     std::lock_guard<std::mutex> turn(DS.mu);                       // one inflate per device at a time: they share the scratch
     // (on every way out — a decline included — the stream is idle before the next call may touch the scratch; destroyed before `turn`)
@@ -1241,6 +1279,401 @@ void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_b
     SY_HIP(hipStreamSynchronize(ctx->stream));      // the scratch is freed on the way out
 }
 
+// =================================================================================================================================
+// the stream: InflateCall's phases over one slice per advancing file (bookkeeping: inflate_stream_plan.h)
+// =================================================================================================================================
+using namespace inflate_stream_plan;
+constexpr uint64_t SLICE_ALIGN = 256;               // a file's slice begins at a multiple of this in the upload (zero bytes between them)
+
+struct StreamCall {
+    sylph_inflate_stream* st;
+    sylph_inflated* t;
+    sylph_ctx* ctx;
+    hipStream_t s;
+    InflateScratch& S;
+    const uint8_t* advance;
+    const uint64_t* keep_from;
+    struct FileSlice { uint32_t file; SliceCut sc; uint64_t off; };      // off: where the slice's bytes lie in the upload
+    std::vector<FileSlice> slices;
+    std::vector<uint64_t> entries;                  // per slice: entry_bit
+    uint64_t n = 0, n_words = 0;
+    std::vector<uint64_t> cand;                     // sorted candidate bits of the upload
+    uint32_t K = 0;
+    std::vector<DecodeJob> jobs;
+    CellsLayout cells{};
+    std::vector<BlockResult> res;
+    std::vector<SliceWalk> walks;                   // per slice
+    std::vector<std::vector<std::vector<uint8_t>>> host_bytes;   // per slice, per host piece
+    std::vector<ChainBlock> blocks;                 // all slices' chain blocks, out_off in the window's text
+    std::vector<uint32_t> first_block;              // per slice: its first block in `blocks` (+ one behind the last)
+    Raw cells2;
+    RedoPlan redo;
+    TextBuf text{"hipMalloc (inflated window)"};
+    std::vector<uint64_t> kept, text_off;           // per file: kept bytes of the previous window; where the file's window begins
+    uint64_t total = 0;
+    uint64_t scratch = 0;                           // bytes of scratch this call asked for
+    uint32_t x2n[64];
+
+    StreamCall(sylph_inflate_stream* st_, sylph_inflated* t_, InflateScratch& S_, const uint8_t* adv, const uint64_t* keep)
+        : st(st_), t(t_), ctx(st_->ctx), s(st_->ctx->stream), S(S_), advance(adv), keep_from(keep) { crc_x2n_table(x2n); }
+
+    void need(Raw& r, size_t bytes) { r.reserve(bytes); scratch += bytes; }
+    uint32_t n_files() const { return (uint32_t)st->gz.size(); }
+
+    void plan_slices(uint64_t slice_bytes) {
+        slices.clear();
+        uint64_t at = 0;
+        for (uint32_t f = 0; f < n_files(); f++) {
+            if ((advance && !advance[f]) || st->carry[f].finished) continue;
+            const SliceCut sc = slice_cut(st->carry[f], st->n_bytes[f], slice_bytes);
+            at = (at + SLICE_ALIGN - 1) / SLICE_ALIGN * SLICE_ALIGN;
+            slices.push_back(FileSlice{f, sc, at});
+            at += sc.end - sc.pos;
+        }
+        n = at;
+        n_words = (n + 3) / 4;
+    }
+
+    void upload() {
+        need(S.gz, (n_words + GZ_PAD_WORDS) * 4);
+        HostPhase hp(ctx, "inflate stream: upload");
+        SY_HIP(hipMemsetAsync(S.gz.p, 0, (n_words + GZ_PAD_WORDS) * 4, s));
+        for (const FileSlice& fs : slices)
+            if (fs.sc.end > fs.sc.pos) ctx->h2d(S.gz.as<uint8_t>() + fs.off, st->gz[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
+    }
+
+    // the bit of the upload where the slice's chain enters a block nobody may have found: the file's very first block, whatever its
+    // type, or the block the carry stands in front of.  ~0: none.
+    uint64_t entry_bit(const FileSlice& fs) const {
+        const Carry& c = st->carry[fs.file];
+        uint64_t file_bit;
+        if (c.in_member) file_bit = c.bit;
+        else if (c.bit == 0) {
+            const size_t body = member_body(st->gz[fs.file], (size_t)st->n_bytes[fs.file], 0);
+            if (!body || body >= fs.sc.end) return ~0ull;
+            file_bit = (uint64_t)body * 8;
+        } else return ~0ull;
+        return file_bit - fs.sc.pos * 8 + fs.off * 8;
+    }
+
+    void find_candidates() {
+        const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
+        need(S.c1, cap1 * 8);
+        need(S.c2, cap2 * 8);
+        need(S.cnt, 64);
+        SY_HIP(hipMemsetAsync(S.cnt.p, 0, 64, s));
+        unsigned long long* cnt = S.cnt.as<unsigned long long>();
+        {
+            ScopedKernelTimer kt(ctx, "inflate_scan");
+            HostPhase hp(ctx, "inflate stream: scan");
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
+            hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, S.gz.as<uint32_t>(), (uint64_t)0, n, S.c1.as<uint64_t>(), cnt, cap1);
+            SY_HIP(hipGetLastError());
+            unsigned long long n1 = 0;
+            ctx->read_back(&n1, cnt, 8);
+            if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
+            if (n1) {
+                hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, S.gz.as<uint32_t>(), n * 8, S.c1.as<uint64_t>(),
+                                   cnt, cap1, S.c2.as<uint64_t>(), cnt + 1, cap2);
+                SY_HIP(hipGetLastError());
+            }
+            cand = fetch_candidates(ctx, S.c2.p, cnt + 1, cap2, "more block-start candidates than the scan has room for");
+        }
+        entries.clear();
+        for (const FileSlice& fs : slices) {
+            const uint64_t e = entry_bit(fs);
+            entries.push_back(e);
+            if (e != ~0ull) cand.insert(std::lower_bound(cand.begin(), cand.end(), e), e);
+        }
+        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+        if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
+        K = (uint32_t)cand.size();
+        t->n_candidates += K;
+    }
+
+    // the slice that holds byte `b` of the upload (the last one that begins at or in front of it)
+    size_t slice_of(uint64_t b) const {
+        size_t i = 0;
+        while (i + 1 < slices.size() && slices[i + 1].off <= b) i++;
+        return i;
+    }
+
+    void decode_candidates() {
+        jobs.assign(K, DecodeJob{});
+        res.assign(K, BlockResult{});
+        if (!K) return;
+        cells = cells_layout(n, K, st->ratio, REGION_SLACK, SPILL_SLOTS, SPILL_CELLS);
+        need(S.cells, cells.total * 2);
+        need(S.res, (size_t)K * sizeof(BlockResult));
+        need(S.jobs, (size_t)K * sizeof(DecodeJob));
+        SY_HIP(hipMemsetAsync(S.cnt.as<unsigned long long>() + 2, 0, 8, s));
+        {
+            ScopedKernelTimer kt(ctx, "inflate_decode");
+            HostPhase hp(ctx, "inflate stream: decode");
+            for (uint32_t i = 0; i < K; i++) {
+                DecodeJob j = decode_job(i, cand.data(), K, 0, n, st->ratio, REGION_SLACK);
+                const size_t si = slice_of(cand[i] >> 3);
+                const FileSlice& fs = slices[si];
+                j.limit_words = (fs.off + (fs.sc.end - fs.sc.pos) + 3) / 4;       // (the zero bytes behind a slice are nobody's input)
+                j.have_window = cand[i] == entries[si] ? (st->carry[fs.file].have_window ? 1u : 0u) : 1u;
+                jobs[i] = j;
+            }
+            ctx->h2d(S.jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
+            launch_decode_jobs(ctx, S, n_words, S.jobs.as<DecodeJob>(), K, S.cells.as<uint16_t>(), Spill{cells.spill_base, SPILL_SLOTS}, S.res.as<BlockResult>());
+        }
+        ctx->d2h(res.data(), S.res.p, (size_t)K * sizeof(BlockResult));
+    }
+
+    // -> false: a slice's first block did not fit (the caller doubles the slice)
+    bool walk_chains() {
+        walks.clear();
+        host_bytes.assign(slices.size(), {});
+        for (size_t si = 0; si < slices.size(); si++) {
+            const FileSlice& fs = slices[si];
+            const uint8_t* gz = st->gz[fs.file];
+            const uint64_t fn = st->n_bytes[fs.file], lo = fs.off * 8, hi = (fs.off + (fs.sc.end - fs.sc.pos)) * 8;
+            const int64_t shift = (int64_t)(fs.sc.pos * 8) - (int64_t)lo;
+            std::vector<uint64_t> bits;
+            std::vector<uint32_t> res_of;
+            for (auto it = std::lower_bound(cand.begin(), cand.end(), lo); it != cand.end() && *it < hi; ++it) {
+                bits.push_back((uint64_t)((int64_t)*it + shift));
+                res_of.push_back((uint32_t)(it - cand.begin()));
+            }
+            walks.push_back(slice_walk(gz, fn, st->carry[fs.file], fs.sc, bits, res_of.data(), res.data(), shift, [&](size_t p, size_t* end, uint64_t* n_out) {
+                std::vector<uint8_t> o;
+                if (!zlib_member(gz, (size_t)fn, p, end, o)) return false;
+                *n_out = o.size();
+                if (!o.empty()) host_bytes[si].push_back(std::move(o));
+                return true;
+            }));
+            if (!walks.back().why.empty()) throw FormatDecline{walks.back().why};
+            if (walks.back().grow) return false;
+        }
+        return true;
+    }
+
+    // ---- where everything goes in the window's text: per file, the kept tail of its previous window, then the slice's new bytes
+    void lay_out_text() {
+        const uint32_t F = n_files();
+        kept.assign(F, 0);
+        text_off.assign(F + 1, 0);
+        std::vector<uint64_t> fresh(F, 0);
+        for (size_t si = 0; si < slices.size(); si++) fresh[slices[si].file] = walks[si].total;
+        for (uint32_t f = 0; f < F; f++) {
+            if (keep_from) {
+                SY_REQUIRE(keep_from[f] <= st->prev_len[f], "sylph_inflate_stream_next: keep_from[%u] = %llu lies behind the previous window (%llu bytes)", f,
+                           (unsigned long long)keep_from[f], (unsigned long long)st->prev_len[f]);
+                kept[f] = st->prev_len[f] - keep_from[f];
+            }
+            text_off[f + 1] = text_off[f] + kept[f] + fresh[f];
+        }
+        total = text_off[F];
+        blocks.clear();
+        first_block.clear();
+        for (size_t si = 0; si < slices.size(); si++) {
+            first_block.push_back((uint32_t)blocks.size());
+            const uint64_t base = text_off[slices[si].file] + kept[slices[si].file];
+            for (ChainBlock cb : walks[si].blocks) { cb.out_off += base; blocks.push_back(cb); }
+        }
+        first_block.push_back((uint32_t)blocks.size());
+        t->n = total;
+        t->files.clear();
+        for (uint32_t f = 0; f < F; f++) t->files.push_back({text_off[f], text_off[f + 1]});
+        t->n_blocks = blocks.size();
+        for (const SliceWalk& w : walks) for (const SliceMember& m : w.members) { t->n_members++; t->n_host_members += m.on_host; }
+    }
+
+    void decode_outgrown() {
+        redo = redo_plan(blocks, cand.data());
+        const size_t J = redo.jobs.size();
+        t->n_redone = J;
+        if (!J) return;
+        for (size_t q = 0; q < J; q++) {                                            // (the first pass's window and limit, not redo_plan's guess)
+            const DecodeJob& first = jobs[blocks[redo.which[q]].cand];
+            redo.jobs[q].have_window = first.have_window;
+            redo.jobs[q].limit_words = first.limit_words;
+        }
+        ScopedKernelTimer kt(ctx, "inflate_decode");
+        HostPhase hp(ctx, "inflate stream: decode again");
+        Raw d_jobs2, d_res2;
+        cells2.alloc((redo.cells + 64) * 2);
+        d_jobs2.alloc(J * sizeof(DecodeJob));
+        d_res2.alloc(J * sizeof(BlockResult));
+        scratch += cells2.cap + d_jobs2.cap + d_res2.cap;
+        ctx->h2d(d_jobs2.p, redo.jobs.data(), J * sizeof(DecodeJob));
+        launch_decode_jobs(ctx, S, n_words, d_jobs2.as<DecodeJob>(), (uint32_t)J, cells2.as<uint16_t>(), Spill{0, 0}, d_res2.as<BlockResult>());
+        std::vector<BlockResult> res2(J);
+        ctx->d2h(res2.data(), d_res2.p, J * sizeof(BlockResult));
+        for (size_t q = 0; q < J; q++) {
+            const BlockResult& a = res[blocks[redo.which[q]].cand];
+            const BlockResult& b2 = res2[q];
+            if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
+                throw FormatDecline{"a block decoded a second time came out differently"};
+        }
+    }
+
+    void write_text() {
+        const uint32_t KB = (uint32_t)blocks.size();
+        text.grow(total, 0, s);
+        SY_HIP(hipMemsetAsync(text.text() + total, 0, 256, s));
+        for (uint32_t f = 0; f < n_files(); f++)
+            if (kept[f]) SY_HIP(hipMemcpyAsync(text.text() + text_off[f], st->prev_text[f] + keep_from[f], kept[f], hipMemcpyDeviceToDevice, s));
+        for (size_t si = 0; si < slices.size(); si++) {
+            const uint64_t base = text_off[slices[si].file] + kept[slices[si].file];
+            for (size_t i = 0; i < walks[si].host.size(); i++)
+                ctx->h2d(text.text() + base + walks[si].host[i].out_off, host_bytes[si][i].data(), host_bytes[si][i].size());
+        }
+        if (!KB) return;
+        std::vector<PlanBlock> plan(KB);
+        for (uint32_t i = 0; i < KB; i++) {
+            const ChainBlock& cb = blocks[i];
+            plan[i].cells = redo.region[i] != ~0ull ? cells2.as<uint16_t>() + redo.region[i] : S.cells.as<uint16_t>() + res[cb.cand].region;
+            plan[i].out_off = cb.out_off;
+            plan[i].n_out = cb.n_out;
+            plan[i].flags = cb.flags;
+        }
+        need(S.plan, (size_t)KB * sizeof(PlanBlock));
+        ctx->h2d(S.plan.p, plan.data(), (size_t)KB * sizeof(PlanBlock));
+        // every file's chain has its own groups, and the window its earlier slices left in front of its first block
+        uint64_t n_groups = 0;
+        for (size_t si = 0; si < slices.size(); si++) { const uint32_t kb = first_block[si + 1] - first_block[si]; if (kb) n_groups += (kb + window_group(kb) - 1) / window_group(kb); }
+        need(S.sfn, (size_t)KB * WINDOW * 2);
+        need(S.ffn, (size_t)n_groups * WINDOW * 2);
+        need(S.rwin, (size_t)n_groups * WINDOW);
+        static std::once_flag once;
+        std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
+        uint64_t g0 = 0;
+        for (size_t si = 0; si < slices.size(); si++) {
+            const uint32_t b0 = first_block[si], kb = first_block[si + 1] - b0;
+            if (!kb) continue;
+            const uint32_t G = window_group(kb), NG = (kb + G - 1) / G, f = slices[si].file;
+            bool any_window = false;
+            for (uint32_t i = 0; i < kb; i++) any_window |= (blocks[b0 + i].flags & 1) != 0;
+            uint16_t* sfn = S.sfn.as<uint16_t>() + (uint64_t)b0 * WINDOW;
+            uint16_t* ffn = S.ffn.as<uint16_t>() + g0 * WINDOW;
+            uint8_t* rwin = S.rwin.as<uint8_t>() + g0 * WINDOW;
+            if (any_window) {
+                ScopedKernelTimer kt(ctx, "inflate_windows");
+                HostPhase hp(ctx, "inflate stream: windows");
+                hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>() + b0, kb, G, sfn, ffn);
+                SY_HIP(hipGetLastError());
+                hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, ffn, NG, rwin, (const uint8_t*)(st->win + ((uint64_t)f * 2 + st->win_cur[f]) * WINDOW));
+                SY_HIP(hipGetLastError());
+            }
+            ScopedKernelTimer kt(ctx, "inflate_translate");
+            HostPhase hp(ctx, "inflate stream: translate");
+            hipLaunchKernelGGL(translate_kernel, dim3(kb), dim3(TR_TPB), 0, s, S.plan.as<PlanBlock>() + b0, G, sfn, rwin, text.text());
+            SY_HIP(hipGetLastError());
+            g0 += NG;
+        }
+    }
+
+    // ---- CRC-32: the pieces crc_kernel sees tile the window's text — per file its kept bytes (nobody's), then the slice's members, the
+    // first of which may have begun in an earlier slice (its register is continued) and the last of which may end in a later one
+    void check_crcs() {
+        struct Piece { uint64_t end; int slice, member; };
+        std::vector<Piece> pieces;
+        std::vector<int> slice_of_file(n_files(), -1);
+        for (size_t si = 0; si < slices.size(); si++) slice_of_file[slices[si].file] = (int)si;
+        for (uint32_t f = 0; f < n_files(); f++) {
+            if (kept[f]) pieces.push_back(Piece{text_off[f] + kept[f], -1, -1});
+            const int si = slice_of_file[f];
+            if (si < 0) continue;
+            for (size_t m = 0; m < walks[si].members.size(); m++) pieces.push_back(Piece{text_off[f] + kept[f] + walks[si].members[m].out_end, si, (int)m});
+        }
+        const uint32_t NM = (uint32_t)pieces.size();
+        std::vector<uint32_t> raw(NM, 0);
+        if (total && NM && !blocks.empty()) {
+            std::vector<unsigned long long> m_end(NM);
+            for (uint32_t i = 0; i < NM; i++) m_end[i] = pieces[i].end;
+            need(S.mend, (size_t)NM * 8);
+            need(S.x2n, 256);
+            need(S.raw, (size_t)NM * 4);
+            ScopedKernelTimer kt(ctx, "inflate_crc");
+            HostPhase hp(ctx, "inflate stream: crc");
+            ctx->h2d(S.mend.p, m_end.data(), (size_t)NM * 8);
+            ctx->h2d(S.x2n.p, x2n, 256);
+            SY_HIP(hipMemsetAsync(S.raw.p, 0, (size_t)NM * 4, s));
+            const uint64_t waves = (total + CRC_SPAN - 1) / CRC_SPAN;
+            hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text.text(), total,
+                               S.mend.as<unsigned long long>(), NM, S.x2n.as<uint32_t>(), S.raw.as<uint32_t>());
+            SY_HIP(hipGetLastError());
+            ctx->d2h(raw.data(), S.raw.p, (size_t)NM * 4);
+        }
+        for (uint32_t i = 0; i < NM; i++) {
+            if (pieces[i].slice < 0) continue;
+            SliceWalk& w = walks[pieces[i].slice];
+            const SliceMember& m = w.members[pieces[i].member];
+            if (m.on_host) continue;
+            const uint64_t n_new = m.out_end - m.out_begin;
+            const uint32_t reg = crc_continue(x2n, m.crc_before, raw[i], n_new);
+            if (!m.ends) { w.next.crc_raw = reg; continue; }
+            const uint32_t got = crc_finish(x2n, reg, m.len_before + n_new);
+            if (got != m.crc) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "file %u, member ending at text byte %llu of the window: CRC-32 %08x, the trailer says %08x", slices[pieces[i].slice].file,
+                         (unsigned long long)pieces[i].end, got, m.crc);
+                throw FormatDecline{msg};
+            }
+        }
+    }
+
+    // ---- what the next call needs: every advanced file's last 32 KiB of text and its carry
+    void commit() {
+        for (size_t si = 0; si < slices.size(); si++) {
+            const uint32_t f = slices[si].file;
+            const uint64_t n_new = walks[si].total;
+            if (n_new) {
+                uint8_t* base = st->win + (uint64_t)f * 2 * WINDOW;
+                hipLaunchKernelGGL(window_tail_kernel, dim3(WINDOW / WIN_TPB), dim3(WIN_TPB), 0, s, base + (uint64_t)st->win_cur[f] * WINDOW,
+                                   text.text() + text_off[f] + kept[f], n_new, base + (uint64_t)(st->win_cur[f] ^ 1) * WINDOW);
+                SY_HIP(hipGetLastError());
+                st->win_cur[f] ^= 1;
+            }
+            st->carry[f] = walks[si].next;
+            st->n_slices++;
+            st->text_bytes += n_new;
+        }
+        st->peak_scratch = std::max(st->peak_scratch, scratch);
+        st->peak_window = std::max(st->peak_window, total);
+    }
+};
+
+void stream_next_impl(sylph_inflate_stream* st, sylph_inflated* t, const uint8_t* advance, const uint64_t* keep_from) {
+    sylph_ctx* ctx = st->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard dg(ctx->device);
+    DeviceScratch& DS = device_scratch(ctx->device);
+    std::lock_guard<std::mutex> turn(DS.mu);                       // the device's one scratch, for this call and not between calls
+    struct Done { InflateScratch& s; hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); if (s.bytes() > SCRATCH_KEEP) s.release(); } } done{DS.s, ctx->stream};
+    uint64_t slice_bytes = st->slice_bytes;
+    for (uint32_t attempt = 0;; attempt++) {
+        StreamCall c(st, t, DS.s, advance, keep_from);
+        t->n_candidates = 0;
+        c.plan_slices(slice_bytes);
+        if (!c.slices.empty()) {
+            c.upload();
+            c.find_candidates();
+            c.decode_candidates();
+            if (!c.walk_chains()) {
+                if (attempt >= MAX_GROW) throw FormatDecline{"a deflate block does not fit the slice, however often it was doubled"};
+                SY_HIP(hipStreamSynchronize(ctx->stream));
+                slice_bytes *= 2;
+                continue;
+            }
+        }
+        c.lay_out_text();
+        c.decode_outgrown();
+        c.write_text();
+        c.check_crcs();
+        c.commit();
+        t->buf = c.text.release();
+        SY_HIP(hipStreamSynchronize(ctx->stream));
+        for (uint32_t f = 0; f < c.n_files(); f++) { st->prev_text[f] = t->text() + c.text_off[f]; st->prev_len[f] = c.text_off[f + 1] - c.text_off[f]; }
+        return;
+    }
+}
+
 }  // namespace
 }  // namespace sylph
 
@@ -1254,6 +1687,95 @@ int sylph_inflate_files(sylph_ctx* ctx, const void* const* gz, const uint64_t* n
 
 int sylph_inflate(sylph_ctx* ctx, const void* gz, uint64_t n_bytes, int mem, sylph_inflated** out) {
     return sylph_inflate_files(ctx, &gz, &n_bytes, 1, mem, out);
+}
+
+int sylph_inflate_stream_open(sylph_ctx* ctx, const void* const* gz, const uint64_t* n_bytes, uint32_t n_files, int mem, uint64_t slice_bytes,
+                              sylph_inflate_stream** out) {
+    if (!ctx || !out || !gz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_files; i++) if (!gz[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_inflate_stream_open: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
+    *out = nullptr;
+    for (uint32_t i = 0; i < n_files; i++)
+        if (!inflate_plan::member_body((const uint8_t*)gz[i], (size_t)n_bytes[i], 0)) { set_error("sylph_inflate_stream_open: declined: not a gzip file"); return SYLPH_ERR_FORMAT; }
+    sylph_inflate_stream* st = nullptr;
+    const int rc = guarded([&] {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        st = new sylph_inflate_stream();
+        st->ctx = ctx;
+        for (uint32_t i = 0; i < n_files; i++) { st->gz.push_back((const uint8_t*)gz[i]); st->n_bytes.push_back(n_bytes[i]); }
+        if (!slice_bytes) slice_bytes = ctx->inflate_slice_bytes ? ctx->inflate_slice_bytes : inflate_stream_plan::DEFAULT_SLICE;
+        st->slice_bytes = std::max<uint64_t>(slice_bytes, inflate_stream_plan::MIN_SLICE);
+        const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
+        st->ratio = rr_env ? std::max(1, std::min(64, atoi(rr_env))) : region_ratio_from_isize(segments_of(gz, n_bytes, n_files), REGION_RATIO);
+        st->carry.assign(n_files, inflate_stream_plan::Carry{});
+        st->win_cur.assign(n_files, 0);
+        st->prev_text.assign(n_files, nullptr);
+        st->prev_len.assign(n_files, 0);
+        const hipError_t e = hipMalloc((void**)&st->win, (size_t)n_files * 2 * WINDOW);
+        if (e != hipSuccess) { st->win = nullptr; (void)hipGetLastError(); throw HipError{e, "hipMalloc (inflate stream windows)", __FILE__, __LINE__}; }
+        SY_HIP(hipMemsetAsync(st->win, 0, (size_t)n_files * 2 * WINDOW, ctx->stream));
+    });
+    if (rc != SYLPH_OK) {
+        if (st) { std::lock_guard<std::mutex> lock(ctx->mu); DeviceGuard dg(ctx->device); if (st->win) (void)hipFree(st->win); delete st; }
+        return rc;
+    }
+    ctx->refs.fetch_add(1);
+    *out = st;
+    return SYLPH_OK;
+}
+
+int sylph_inflate_stream_next(sylph_inflate_stream* st, const uint8_t* advance, const uint64_t* keep_from, sylph_inflated** window, uint8_t* finished) {
+    if (!st || !window) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    *window = nullptr;
+    if (st->dead) { set_error("sylph_inflate_stream_next: the stream was given up by an earlier call"); return SYLPH_ERR_FORMAT; }
+    sylph_ctx* ctx = st->ctx;
+    ctx->refs.fetch_add(1);
+    sylph_inflated* t = nullptr;
+    int format = 0;
+    const int rc = guarded([&] {
+        t = new sylph_inflated();
+        t->ctx = ctx;
+        try { stream_next_impl(st, t, advance, keep_from); }
+        catch (const FormatDecline& e) { set_error("sylph_inflate_stream_next: declined: %s", e.msg.c_str()); format = 1; }
+    });
+    if (rc != SYLPH_OK || format) {
+        st->dead = true;
+        {
+            std::lock_guard<std::mutex> lock(ctx->mu);
+            DeviceGuard dg(ctx->device);
+            (void)hipStreamSynchronize(ctx->stream);
+            if (t && t->buf) (void)hipFree(t->buf);
+            delete t;
+        }
+        ctx_unref(ctx);
+        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
+    }
+    if (finished) for (size_t i = 0; i < st->carry.size(); i++) finished[i] = st->carry[i].finished ? 1 : 0;
+    *window = t;
+    return SYLPH_OK;
+}
+
+int sylph_inflate_stream_info(const sylph_inflate_stream* st, uint64_t* n_slices, uint64_t* text_bytes, uint64_t* peak_scratch_bytes, uint64_t* peak_window_bytes) {
+    if (!st) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (n_slices) *n_slices = st->n_slices;
+    if (text_bytes) *text_bytes = st->text_bytes;
+    if (peak_scratch_bytes) *peak_scratch_bytes = st->peak_scratch;
+    if (peak_window_bytes) *peak_window_bytes = st->peak_window;
+    return SYLPH_OK;
+}
+
+void sylph_inflate_stream_destroy(sylph_inflate_stream* st) {
+    if (!st) return;
+    sylph_ctx* ctx = st->ctx;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        if (st->win) (void)hipFree(st->win);
+        delete st;
+    }
+    ctx_unref(ctx);
 }
 
 int sylph_inflated_file(const sylph_inflated* t, uint32_t i, const void** dev_text, uint64_t* n_bytes) {

@@ -181,7 +181,8 @@ Chain chain_walk(const Segments& S, const std::vector<uint64_t>& cand_bits, cons
 
 // ---- where the cells go ---------------------------------------------------------------------------------------------------------
 // one candidate for a wavefront: where its block starts, where its cells go (offset into the cells buffer) and how many fit
-struct DecodeJob { unsigned long long start_bit, region; uint32_t cap, have_window; };
+// limit_words (0: all the words of the launch): the words of the compressed bytes this block may read — a slice of the stream ends there
+struct DecodeJob { unsigned long long start_bit, region; uint32_t cap, have_window; unsigned long long limit_words; };
 constexpr uint32_t MAX_BLOCK_CELLS = 0xFFFFFF00u;      // a block of more cells is not even countable (ST_OVERFLOW)
 
 // A single-member file says how well it deflates (ISIZE in its trailer): its blocks get 1.5 x that + 2 cells per compressed byte
@@ -203,7 +204,7 @@ inline uint64_t region_ratio_from_isize(const Segments& files, uint64_t flat) {
 // cells per byte up to the next candidate + `slack`
 inline DecodeJob decode_job(uint32_t i, const uint64_t* cand, uint32_t K, uint64_t body0, uint64_t byte_end, uint64_t ratio, uint64_t slack) {
     const uint64_t b0 = cand[i] >> 3, b1 = i + 1 < K ? cand[i + 1] >> 3 : byte_end;
-    return DecodeJob{cand[i], (b0 - body0) * ratio + (uint64_t)i * slack, (uint32_t)std::min<uint64_t>(MAX_BLOCK_CELLS, (b1 - b0) * ratio + slack), i != 0};
+    return DecodeJob{cand[i], (b0 - body0) * ratio + (uint64_t)i * slack, (uint32_t)std::min<uint64_t>(MAX_BLOCK_CELLS, (b1 - b0) * ratio + slack), i != 0, 0};
 }
 // the cells buffer: the K candidates' regions, then (from a multiple of 64 cells) the spill arena's spill_slots regions of spill_cells
 struct CellsLayout { uint64_t n_cells, spill_base, total; };
@@ -228,7 +229,7 @@ inline RedoPlan redo_plan(const std::vector<ChainBlock>& blocks, const uint64_t*
     for (uint32_t i = 0; i < blocks.size(); i++) {
         const ChainBlock& cb = blocks[i];
         if (!(cb.flags & 2)) continue;
-        p.jobs.push_back(DecodeJob{cand[cb.cand], p.cells, cb.n_out, cb.cand != 0});
+        p.jobs.push_back(DecodeJob{cand[cb.cand], p.cells, cb.n_out, cb.cand != 0, 0});
         p.which.push_back(i);
         p.region[i] = p.cells;
         p.cells += ((uint64_t)cb.n_out + 63) & ~(uint64_t)63;

@@ -192,6 +192,123 @@ struct MappedFile {                       // the compressed bytes of one file (r
     ~MappedFile() { if (data) munmap(const_cast<uint8_t*>(data), size); }
 };
 struct InflatedText { sylph_inflated* h = nullptr; ~InflatedText() { sylph_inflated_destroy(h); } };
+
+// SYLPH_HIP_INFLATE_STREAM: "auto" (default: the stream takes what the whole-file road declines for size or for room), "1" always, "0" never
+enum class StreamMode { Auto, Always, Never };
+StreamMode stream_mode() {
+    const char* e = getenv("SYLPH_HIP_INFLATE_STREAM");
+    if (!e || !*e || !strcmp(e, "auto")) return StreamMode::Auto;
+    return atoi(e) != 0 ? StreamMode::Always : StreamMode::Never;
+}
+uint64_t env_bytes(const char* name, uint64_t otherwise) {
+    const char* e = getenv(name);
+    if (!e || !*e) return otherwise;
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    return v ? (uint64_t)v : otherwise;
+}
+// gzip bytes (both mates together) from which sylph_inflate_files declines (SYLPH_HIP_INFLATE_WHOLE_MAX lowers it: the tests)
+uint64_t inflate_whole_max() { return std::min<uint64_t>(env_bytes("SYLPH_HIP_INFLATE_WHOLE_MAX", SYLPH_INFLATE_WHOLE_MAX_BYTES), SYLPH_INFLATE_WHOLE_MAX_BYTES); }
+
+// The stream route for gzip samples (csrc/inflate.hip sylph_inflate_stream_*): the compressed bytes go to the device one slice per mate
+// at a time, the records of every window are found there and pushed, and what a window holds beyond its last pushed record is kept for
+// the next one — memory is a function of the slice, not of the sample (the reference streams records in O(batch) memory too:
+// sketch.rs:780-781, :806-815, :906).  Per step: next; index each mate's window (final = the file's finished flag); push
+// min(complete records of mate 1, of mate 2) pairs; keep every mate's text from its first record that was not pushed; advance only the
+// mate with fewer records waiting (both when they are level), which bounds the carried text.  Surplus records of the longer mate are
+// dropped at the end (lock-step readers, sketch.rs:813-815); the running mean of the mate-1 lengths is the same f64 recurrence in
+// file order, continued across windows.  false: declined at some step (the session is the caller's to drop: the host feed takes the
+// sample from its start).
+bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::vector<const void*>& ptrs, const std::vector<uint64_t>& lens,
+                          const char* name, double& mean_read_length) {
+    const bool trace = FeedLaps::on();
+    FeedLaps laps;
+    sylph_ctx* ctx = e.context();
+    const uint32_t F = (uint32_t)ptrs.size();
+    struct Stream { sylph_inflate_stream* h = nullptr; ~Stream() { sylph_inflate_stream_destroy(h); } } st;
+    auto declined = [&](int rc, const char* what) {
+        if (rc != SYLPH_ERR_FORMAT && rc != SYLPH_ERR_NOMEM) hip_check(rc, what);
+        if (trace) fprintf(stderr, "[sylph_hip feed] stream route declined %s at %s: %s\n", name, what, sylph_last_error());
+        return false;
+    };
+    int rc = sylph_inflate_stream_open(ctx, ptrs.data(), lens.data(), F, SYLPH_MEM_HOST, env_bytes("SYLPH_HIP_INFLATE_SLICE", 0), &st.h);
+    if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_open");
+    sylph_sketch* const sk = open_session();
+    e.batch.flush(sk);
+    struct Fq { sylph_fastq* f = nullptr; ~Fq() { sylph_fastq_destroy(f); } };
+    std::unique_ptr<InflatedText> prev;                        // the window of the step before: its kept tail is copied out of it by `next`
+    std::vector<uint8_t> advance(F, 1), finished(F, 0);
+    std::vector<uint64_t> keep(F, 0);
+    std::vector<uint32_t> la, lb;
+    double mean = 0., counter = 0.;
+    uint64_t pairs = 0;
+    for (bool first = true;; first = false) {
+        std::unique_ptr<InflatedText> win(new InflatedText());
+        rc = sylph_inflate_stream_next(st.h, advance.data(), first ? nullptr : keep.data(), &win->h, finished.data());
+        if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_next");
+        prev.reset();                                          // (its indexes went with the previous step's scope)
+        std::vector<Fq> fq(F);
+        std::vector<uint64_t> n_rec(F, 0), bytes(F, 0), bases(F, 0);
+        for (uint32_t i = 0; i < F; i++) {
+            const void* dev = nullptr;
+            hip_check(sylph_inflated_file(win->h, i, &dev, &bytes[i]), "sylph_inflated_file");
+            if (finished[i] && !bytes[i]) continue;            // nothing left of a finished file: no records
+            uint64_t consumed = 0;
+            rc = sylph_fastq_index_window(ctx, dev, bytes[i], SYLPH_MEM_DEVICE, finished[i] ? 1 : 0, &fq[i].f, &consumed);
+            if (rc != SYLPH_OK) return declined(rc, "sylph_fastq_index_window");
+            hip_check(sylph_fastq_counts(fq[i].f, &n_rec[i], &bases[i]), "sylph_fastq_counts");
+        }
+        const uint64_t n = F == 2 ? std::min(n_rec[0], n_rec[1]) : n_rec[0];
+        if (n) {
+            la.resize(n);
+            hip_check(sylph_fastq_lengths(fq[0].f, 0, n, la.data()), "sylph_fastq_lengths");
+            for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)la[i] - mean) / counter; }      // sketch.rs:941-943, :825-826
+            // pushes of whole records (pairs) below 2^31 bases and 2^30 items
+            std::vector<std::pair<uint64_t, uint64_t>> pushes;
+            if (bases[0] + (F == 2 ? bases[1] : 0) < (1ull << 31) && n < (1ull << 30)) pushes.emplace_back(0, n);
+            else {
+                if (F == 2) { lb.resize(n); hip_check(sylph_fastq_lengths(fq[1].f, 0, n, lb.data()), "sylph_fastq_lengths"); }
+                uint64_t i0 = 0, sum = 0;
+                for (uint64_t i = 0; i < n; i++) {
+                    const uint64_t l = (uint64_t)la[i] + (F == 2 ? lb[i] : 0);
+                    if (i > i0 && (sum + l >= (1ull << 31) || i - i0 >= (1ull << 30))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
+                    sum += l;
+                }
+                if (n > i0) pushes.emplace_back(i0, n - i0);
+            }
+            for (const auto& p : pushes) {
+                rc = sylph_sketch_push_fastq(sk, fq[0].f, F == 2 ? fq[1].f : nullptr, p.first, p.second);
+                if (rc == SYLPH_ERR_NOMEM) return declined(rc, "sylph_sketch_push_fastq");
+                hip_check(rc, "sylph_sketch_push_fastq");
+            }
+            pairs += n;
+        }
+        bool all_done = true;
+        for (uint32_t i = 0; i < F; i++) {
+            keep[i] = bytes[i];
+            if (fq[i].f) { hip_check(sylph_fastq_record_offset(fq[i].f, n, &keep[i]), "sylph_fastq_record_offset"); keep[i] = std::min(keep[i], bytes[i]); }
+            all_done = all_done && finished[i];
+        }
+        // a finished mate with nothing waiting ends the lock-step reading: the other mate's surplus is dropped (sketch.rs:813-815)
+        bool starved = false;
+        for (uint32_t i = 0; i < F; i++) starved = starved || (finished[i] && n_rec[i] == n);
+        if (all_done || starved) break;
+        const uint64_t waiting0 = n_rec[0] - n, waiting1 = F == 2 ? n_rec[1] - n : 0;
+        advance[0] = !finished[0] && (F == 1 || waiting0 <= waiting1 || finished[1]);
+        if (F == 2) advance[1] = !finished[1] && (waiting1 <= waiting0 || finished[0]);
+        fq.clear();                                            // the indexes borrow the window's text: they go first
+        prev = std::move(win);
+    }
+    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+    hip_check(sylph_inflate_stream_info(st.h, &n_slices, &text_bytes, &peak_scratch, &peak_window), "sylph_inflate_stream_info");
+    if (trace) {
+        char what[192];
+        snprintf(what, sizeof(what), "stream route: gzip inflated on the device in %llu slices (%llu records, %llu text bytes, peak scratch %llu, peak window %llu)",
+                 (unsigned long long)n_slices, (unsigned long long)pairs, (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
+        laps.lap(what);
+    }
+    mean_read_length = mean;
+    return true;
+}
 }  // namespace
 
 bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const SampleFiles& sample, Container decode,
@@ -219,8 +336,33 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             ptrs.push_back(maps.back()->data);
             lens.push_back(maps.back()->size);
         }
-        const int rc = gz ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h)
-                          : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
+        // gzip: the whole-file road, or — for what it declines for size or for room, or when asked — the stream (sketch_gzip_streamed)
+        bool streamed = false;
+        if (gz) {
+            uint64_t gz_bytes = 0;
+            for (const uint64_t l : lens) gz_bytes += l;
+            const StreamMode mode = stream_mode();
+            const bool too_large = gz_bytes >= inflate_whole_max();
+            streamed = mode == StreamMode::Always || (mode == StreamMode::Auto && too_large);
+            if (!streamed && too_large) {
+                if (trace) fprintf(stderr, "[sylph_hip feed] device inflate declined %s: %llu gzip bytes, and the stream is off\n", files[0].c_str(), (unsigned long long)gz_bytes);
+                return false;
+            }
+        }
+        int rc = SYLPH_OK;
+        if (!streamed) {
+            rc = gz ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h)
+                    : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
+            if (gz && rc == SYLPH_ERR_NOMEM && stream_mode() == StreamMode::Auto) {
+                if (trace) fprintf(stderr, "[sylph_hip feed] device inflate has no room for %s in one piece (%s): the stream takes it\n", files[0].c_str(), sylph_last_error());
+                streamed = true;
+            }
+        }
+        if (streamed) {
+            if (!sketch_gzip_streamed(e, open_session, ptrs, lens, files[0].c_str(), mean_read_length)) return false;
+            laps.lap("device route: gzip streamed through the device inflate");
+            return true;
+        }
         if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
             if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", files[0].c_str(), sylph_last_error());
             return false;
