@@ -272,6 +272,24 @@ void sylph_fasta_destroy(sylph_fasta *f);
 int sylph_sketch_genomes_fasta(sylph_ctx *ctx, sylph_fasta *const *files, uint32_t n_files, int individual, uint32_t c, uint32_t k,
                                int seed_mode, uint64_t min_spacing, int pseudotax, uint64_t **out_kmers, uint64_t *kmer_off,
                                uint64_t **out_tracked, uint64_t *tracked_off);
+/* FASTA text as a SAMPLE's reads (sketch.rs:780-781, :906: needletail takes FASTA and FASTQ alike), the twin of sylph_sketch_push_fastq.
+ * sylph_sketch_push_fasta gathers the sequences of records [first, first + n_items) of `a` into a batch of the session and sketches it (a
+ * paired session takes the two mates' texts: item i = record i of `a`, then record i of `b`; the caller pushes min(n_a, n_b) items).  A
+ * record of length 0 stays a record.  The first push from an index joins the text's bases once into a buffer the index keeps until
+ * sylph_fasta_destroy; every push gathers from there.  Limits, argument checks (SYLPH_ERR_INVALID) and SYLPH_ERR_NOMEM — returned before
+ * anything of the session is touched — are sylph_sketch_push_fastq's, and so is "borrow_until_finish".
+ * sylph_fasta_index_window: the records of a WINDOW of a text that arrives in pieces.  final == 0: a record is complete once the NEXT
+ * header has been seen, so the index holds every record but the last, *consumed is where the last header's '>' lies (the caller keeps
+ * the text from there for the next window), and counts, lengths, ids, bases and pushes see the complete records only.  One header alone
+ * gives zero records and *consumed = 0; that is not an error, neither is an empty text.  A '\r' as the window's last byte is accepted as
+ * at the end of a text: it lies in the kept tail and is judged again in the next window.  final != 0: exactly sylph_fasta_index, and
+ * *consumed = n_bytes.  The refusals are sylph_fasta_index's.
+ * sylph_fasta_record_offset: where record `record` begins in its text (its '>'); record == the number of records: *consumed of a
+ * window's index, n_bytes of any other.  A caller that pushes fewer records than a window holds keeps the text from there. */
+int sylph_sketch_push_fasta(sylph_sketch *sk, sylph_fasta *a, sylph_fasta *b, uint64_t first, uint64_t n_items);
+int sylph_fasta_index_window(sylph_ctx *ctx, const void *text, uint64_t n_bytes, int mem, int final, sylph_fasta **out,
+                             uint64_t *consumed);
+int sylph_fasta_record_offset(sylph_fasta *f, uint64_t record, uint64_t *offset);
 
 /* ---- gzip inflated on the device (csrc/inflate.hip, round 6) ------------------------------------------------------------------
  * The reference's normal input is gzip (README.md:51): parse_fastx_file (sketch.rs:780-781, :906; :491, :562 for genomes) hands the

@@ -137,6 +137,9 @@ extern "C" {
     pub fn sylph_fasta_ids(f: *mut SylphFasta, first: u64, n: u64, out: *mut c_char, cap: u64, id_off: *mut u64) -> c_int;
     pub fn sylph_fasta_bases(f: *mut SylphFasta, first: u64, n: u64, host_out: *mut u8) -> c_int;
     pub fn sylph_fasta_destroy(f: *mut SylphFasta);
+    pub fn sylph_sketch_push_fasta(sk: *mut SylphSketch, a: *mut SylphFasta, b: *mut SylphFasta, first: u64, n_items: u64) -> c_int;   // FASTA-format reads: the twin of sylph_sketch_push_fastq
+    pub fn sylph_fasta_index_window(ctx: *mut SylphCtx, text: *const c_void, n_bytes: u64, mem: c_int, is_final: c_int, out: *mut *mut SylphFasta, consumed: *mut u64) -> c_int;
+    pub fn sylph_fasta_record_offset(f: *mut SylphFasta, record: u64, offset: *mut u64) -> c_int;   // where a record's '>' lies
     pub fn sylph_sketch_genomes_fasta(ctx: *mut SylphCtx, files: *const *mut SylphFasta, n_files: u32, individual: c_int, c: u32, k: u32,
                                       seed_mode: c_int, min_spacing: u64, pseudotax: c_int, out_kmers: *mut *mut u64, kmer_off: *mut u64,
                                       out_tracked: *mut *mut u64, tracked_off: *mut u64) -> c_int;

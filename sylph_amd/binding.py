@@ -40,6 +40,7 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_genome_shard_bounds", "sylph_db_upload_genome_shard",
            "sylph_fastq_index", "sylph_fastq_index_window", "sylph_fastq_record_offset", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
            "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
+           "sylph_sketch_push_fasta", "sylph_fasta_index_window", "sylph_fasta_record_offset",
            "sylph_sketch_genomes_fasta",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
            "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
@@ -93,6 +94,9 @@ def load():
     L.sylph_fasta_ids.argtypes = [vp, u64, u64, vp, u64, vp]
     L.sylph_fasta_bases.argtypes = [vp, u64, u64, vp]
     L.sylph_fasta_destroy.argtypes = [vp]
+    L.sylph_sketch_push_fasta.argtypes = [vp, vp, vp, u64, u64]
+    L.sylph_fasta_index_window.argtypes = [vp, vp, u64, i32, i32, P(vp), P(u64)]
+    L.sylph_fasta_record_offset.argtypes = [vp, u64, P(u64)]
     L.sylph_fasta_destroy.restype = None
     L.sylph_sketch_genomes_fasta.argtypes = [vp, P(vp), u32, i32, u32, u32, i32, u64, i32, P(vp), vp, P(vp), vp]
     L.sylph_inflate.argtypes = [vp, vp, u64, i32, P(vp)]
@@ -510,15 +514,24 @@ class FastaText:
     an integer address with n_bytes (MEM_HOST_PINNED / MEM_DEVICE; device text — what Inflated / Bunzipped lend — is borrowed until
     close()).  Raises SylphHipError with code ERR_FORMAT when the text is not FASTA this index takes: parse it on the host then."""
 
-    def __init__(self, ctx, text, mem=MEM_HOST, n_bytes=None):
+    def __init__(self, ctx, text, mem=MEM_HOST, n_bytes=None, final=None):
+        """final: None = sylph_fasta_index; 0 / 1 = sylph_fasta_index_window (the complete records of a window of a longer text;
+        .consumed = where they end)"""
         self._h = None
         h = C.c_void_p()
+        used = C.c_uint64(0)
         if mem == MEM_HOST:
             self._keep = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else _np(text, np.uint8)
-            _check(load().sylph_fasta_index(ctx._h, _ptr(self._keep) if len(self._keep) else None, len(self._keep), mem, C.byref(h)))
-            self._keep = None
+            ptr, n = (_ptr(self._keep) if len(self._keep) else None), len(self._keep)
         else:
-            _check(load().sylph_fasta_index(ctx._h, C.c_void_p(int(text)), int(n_bytes), mem, C.byref(h)))
+            ptr, n = C.c_void_p(int(text)), int(n_bytes)
+        if final is None:
+            _check(load().sylph_fasta_index(ctx._h, ptr, n, mem, C.byref(h)))
+        else:
+            _check(load().sylph_fasta_index_window(ctx._h, ptr, n, mem, int(final), C.byref(h), C.byref(used)))
+        self.consumed = int(used.value) if final is not None else n
+        if mem == MEM_HOST:
+            self._keep = None
         self._h = h
         nr, nb, ni = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         _check(load().sylph_fasta_counts(self._h, C.byref(nr), C.byref(nb), C.byref(ni)))
@@ -545,6 +558,12 @@ class FastaText:
         out = np.zeros(total, dtype=np.uint8)
         _check(load().sylph_fasta_bases(self._h, int(first), int(n), _ptr(out) if total else None))
         return out
+
+    def record_offset(self, record):
+        """sylph_fasta_record_offset: where the record's '>' lies in the text; record == n_records: where the text behind the records begins"""
+        v = C.c_uint64(0)
+        _check(load().sylph_fasta_record_offset(self._h, int(record), C.byref(v)))
+        return int(v.value)
 
     def close(self):
         if self._h:
@@ -612,6 +631,12 @@ class ReadSketcher:
         if n_items is None:
             n_items = (min(a.n_records, b.n_records) if b is not None else a.n_records) - first
         _check(load().sylph_sketch_push_fastq(self._h, a._h, b._h if b is not None else None, int(first), int(n_items)))
+
+    def push_fasta(self, a, b=None, first=0, n_items=None):
+        """sylph_sketch_push_fasta: records [first, first + n_items) of the FastaText `a` (and of `b`, the mates, in a paired session)."""
+        if n_items is None:
+            n_items = (min(a.n_records, b.n_records) if b is not None else a.n_records) - first
+        _check(load().sylph_sketch_push_fasta(self._h, a._h, b._h if b is not None else None, int(first), int(n_items)))
 
     def finish(self):
         ok, oc, n, d = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)

@@ -19,6 +19,16 @@
 //                       from the line table.  No lane looks at more than its 16 bytes: a text of 1-byte lines and a chromosome on one
 //                       line run through the same code at the same cost per byte.
 //
+// The same text as a SAMPLE's reads (sylph_sketch_push_fasta; fasta_reads_plan.h):
+//
+//   fa_join_kernel      once per index, into a buffer of the index: the file's bases side by side
+//   fa_batch_lens_kernel, exclusive scan    the 32-bit offsets of the batch's records (pairs interleaved: mate 1, mate 2)
+//   fa_batch_kernel     per 4 KiB tile of the BATCH: a lane finds the record of its first output byte by a binary search in the offsets,
+//                       walks over the record boundaries inside its 16 bytes, cuts every piece out of two aligned 16-byte loads of the
+//                       file's joined bases and writes one aligned 16-byte store.  No lane loops over a record.
+//
+// sylph_fasta_index_window indexes a window of a text that goes on: all its records but the last, whose end nobody has seen yet.
+//
 // An empty text, a first byte other than '>', a stray '\r', a text of 2^32 - 4096 bytes or more: sylph_fasta_index returns
 // SYLPH_ERR_FORMAT and nothing else happens; the caller reads the file with its host reader.  Nothing here guesses.
 #include "common.h"
@@ -26,6 +36,7 @@
 #include "sketch_session.h"
 #include "text_lines.h"
 #include "fasta_plan.h"
+#include "fasta_reads_plan.h"
 
 #include <algorithm>
 
@@ -38,8 +49,13 @@ struct sylph_fasta {
     sylph::DevBuf line_start, scan;       // u64 per line (+ 1): first byte; headers << 32 | sequence bytes in front of the line
     sylph::DevBuf rec_off, id_pos, id_len;   // u64 per record (+ 1): first base; u64: first byte of the id; u32: its length
     uint64_t n_tiles = 0, n_lines = 0, n_rec = 0, n_bases = 0, id_bytes = 0;
+    // a window's index (sylph_fasta_index_window, final == 0) holds the records in front of the last header: `end` is that header's '>'
+    // (else the text's size), and the join reads the text in front of it only
+    uint64_t end = 0, join_tiles = 0;
+    sylph::DevBuf joined;                 // sylph_sketch_push_fasta: the bases of all records side by side, joined at the first push
+    bool joined_ready = false;
     explicit sylph_fasta(sylph_ctx* c)
-        : ctx(c), text_own(c), tile_base(c), line_start(c), scan(c), rec_off(c), id_pos(c), id_len(c) {}
+        : ctx(c), text_own(c), tile_base(c), line_start(c), scan(c), rec_off(c), id_pos(c), id_len(c), joined(c) {}
 };
 
 namespace sylph {
@@ -52,6 +68,7 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
 namespace {
 
 namespace fp = fasta_plan;
+namespace rp = fasta_reads_plan;
 static_assert(FQ_TILE == (int)fp::TILE_BYTES && FQ_TPB == (int)fp::TILE_LANES, "text_lines.h and fasta_plan.h cut the same tiles");
 
 // q: what text_lines.h's kernels read and write (n_eff = bytes of the text: a FASTA text is not trimmed; flags: 1 = the first byte is not
@@ -194,11 +211,54 @@ __global__ __launch_bounds__(256) void fa_ids_kernel(const uint8_t* __restrict__
     }
 }
 
+// lengths of a batch's records in batch order (pairs interleaved), one sentinel 0 behind them for the scan; their 64-bit sum in *total
+// (the scan is a 32-bit one: the caller checks the sum before it trusts the offsets)
+__global__ void fa_batch_lens_kernel(const uint64_t* __restrict__ ra, const uint64_t* __restrict__ rb, uint64_t first, uint64_t n_rec_batch,
+                                     uint32_t* __restrict__ out, unsigned long long* __restrict__ total) {
+    unsigned long long sum = 0;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= n_rec_batch; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t l = j == n_rec_batch ? 0u : rp::batch_len(ra, rb, first, j);
+        out[j] = l;
+        sum += l;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
+}
+__global__ void fa_widen_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ out) {
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) out[j] = in[j];
+}
+
+// One workgroup per 4 KiB tile of the batch, one lane per 16 output bytes (fasta_reads_plan.h lane_walk).  ja / jb: the joined bases of
+// the two files (16-byte aligned, readable 32 bytes past their last base; jb = nullptr: single-end), ra / rb: their record offsets;
+// off: the batch's offsets, n_rec of them + 1, off[n_rec] = total; bases: 16-byte aligned, room for total rounded up to 16.
+__global__ __launch_bounds__(FQ_TPB) void fa_batch_kernel(const uint8_t* __restrict__ ja, const uint64_t* __restrict__ ra,
+                                                          const uint8_t* __restrict__ jb, const uint64_t* __restrict__ rb, uint64_t first,
+                                                          uint64_t n_rec, const uint32_t* __restrict__ off, uint64_t total,
+                                                          uint8_t* __restrict__ bases) {
+    const uint64_t o = (uint64_t)blockIdx.x * rp::TILE_BYTES + (uint64_t)threadIdx.x * rp::LANE_BYTES;
+    if (o >= total) return;
+    uint64_t out_lo = 0, out_hi = 0;
+    rp::lane_walk(off, n_rec, total, o, [&](uint64_t j, uint64_t p, uint32_t b0, uint32_t len) {
+        const uint8_t* src = (rp::mate_of(j, rb != nullptr) ? jb : ja) + rp::source_of(off, ra, rb, first, j, p);
+        const uint32_t sh = (uint32_t)((uintptr_t)src & 15);
+        const uint4* al = reinterpret_cast<const uint4*>(src - sh);
+        const uint4 a = al[0], b = al[1];
+        uint64_t lo, hi;
+        rp::cut16((uint64_t)a.x | (uint64_t)a.y << 32, (uint64_t)a.z | (uint64_t)a.w << 32, (uint64_t)b.x | (uint64_t)b.y << 32,
+                  (uint64_t)b.z | (uint64_t)b.w << 32, sh, lo, hi);
+        rp::lay16(lo, hi, b0, len, out_lo, out_hi);
+    });
+    *reinterpret_cast<uint4*>(bases + o) = make_uint4((uint32_t)out_lo, (uint32_t)(out_lo >> 32), (uint32_t)out_hi, (uint32_t)(out_hi >> 32));
+}
+
 struct FormatError { std::string msg; };
 
 uint32_t grid1(uint64_t n, uint32_t tpb = 256, uint32_t cap = 1u << 30) { return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, (n + tpb - 1) / tpb)); }
 
-void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int mem) {
+// window: the text goes on behind its last byte (sylph_fasta_index_window, final == 0) — the same kernels over the same bytes, and then
+// the last header's record is taken off the index again (fasta_reads_plan.h window_records)
+void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int mem, bool window = false) {
     sylph_ctx* ctx = f->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
@@ -258,6 +318,27 @@ void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int me
     SY_HIP(hipGetLastError());
     ctx->read_back(&hw, d_w, sizeof(hw));
     f->id_bytes = hw.id_bytes;
+    f->end = n_bytes;
+    f->join_tiles = n_tiles;
+    if (!window) return;
+    const uint64_t headers = f->n_rec;
+    uint64_t last_at = 0;
+    if (headers >= 2) {
+        uint64_t last_base = 0, last_id = 0;
+        uint32_t last_id_len = 0;
+        ctx->read_back(&last_base, f->rec_off.as<uint64_t>() + headers - 1, 8);
+        ctx->read_back(&last_id, f->id_pos.as<uint64_t>() + headers - 1, 8);
+        ctx->read_back(&last_id_len, f->id_len.as<uint32_t>() + headers - 1, 4);
+        last_at = last_id - 1;
+        f->n_bases = last_base;
+        f->id_bytes -= last_id_len;
+    } else {
+        f->n_bases = 0;
+        f->id_bytes = 0;
+    }
+    f->n_rec = rp::window_records(headers, false);
+    f->end = rp::window_consumed(headers, false, n_bytes, last_at);
+    f->join_tiles = f->end ? (f->end + bias + FQ_TILE - 1) / FQ_TILE : 0;
 }
 
 // the text's sequences joined to out[0, n_bases) (device memory, any alignment); the caller holds the context's lock.  d_err: one zeroed word
@@ -265,7 +346,8 @@ void fasta_join(sylph_fasta* f, uint8_t* out, uint32_t* d_err) {
     sylph_ctx* ctx = f->ctx;
     const uint32_t bias = (uint32_t)((uintptr_t)f->text & 15);
     ScopedKernelTimer t(ctx, "fasta_join");
-    hipLaunchKernelGGL(fa_join_kernel, dim3((uint32_t)f->n_tiles), dim3(FQ_TPB), 0, ctx->stream, f->text - bias, bias, f->n, f->tile_base.as<uint32_t>(),
+    if (!f->join_tiles) return;
+    hipLaunchKernelGGL(fa_join_kernel, dim3((uint32_t)f->join_tiles), dim3(FQ_TPB), 0, ctx->stream, f->text - bias, bias, f->end, f->tile_base.as<uint32_t>(),
                        f->line_start.as<uint64_t>(), f->scan.as<uint64_t>(), out, (uint32_t)f->n_bases, d_err);
     SY_HIP(hipGetLastError());
 }
@@ -307,6 +389,129 @@ int sylph_fasta_index(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int me
     }
     *out = f;
     return SYLPH_OK;
+}
+
+int sylph_fasta_index_window(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, int final, sylph_fasta** out, uint64_t* consumed) {
+    if (!ctx || !out || !consumed || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    *out = nullptr;
+    *consumed = 0;
+    if (final) {                                                         // exactly sylph_fasta_index
+        const int rc = sylph_fasta_index(ctx, text, n_bytes, mem, out);
+        if (rc == SYLPH_OK) *consumed = n_bytes;
+        return rc;
+    }
+    if (n_bytes && !fasta_plan::text_size_ok(n_bytes)) {
+        set_error("sylph_fasta_index_window: %llu bytes of text: fewer than 2^32 - 4096 per index", (unsigned long long)n_bytes);
+        return SYLPH_ERR_FORMAT;
+    }
+    ctx->refs.fetch_add(1);
+    sylph_fasta* f = nullptr;
+    int format = 0;
+    const int rc = guarded([&] {
+        f = new sylph_fasta(ctx);
+        if (!n_bytes) return;                                            // no text yet: no records, nothing consumed
+        try { fasta_index_impl(f, text, n_bytes, mem, true); }
+        catch (const FormatError& e) { set_error("sylph_fasta_index_window: not FASTA text this index takes: %s", e.msg.c_str()); format = 1; }
+    });
+    if (rc != SYLPH_OK || format) {
+        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); DeviceGuard dg(ctx->device); (void)hipStreamSynchronize(ctx->stream); delete f; }
+        ctx_unref(ctx);
+        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
+    }
+    *out = f;
+    *consumed = f->end;
+    return SYLPH_OK;
+}
+
+int sylph_fasta_record_offset(sylph_fasta* f, uint64_t record, uint64_t* offset) {
+    return guarded([&] {
+        SY_REQUIRE(f && offset, "null argument");
+        SY_REQUIRE(record <= f->n_rec, "sylph_fasta_record_offset: record %llu of %llu", (unsigned long long)record, (unsigned long long)f->n_rec);
+        if (record == f->n_rec) { *offset = f->end; return; }
+        std::lock_guard<std::mutex> lock(f->ctx->mu);
+        DeviceGuard dg(f->ctx->device);
+        unsigned long long v = 0;
+        f->ctx->d2h(&v, f->id_pos.as<uint64_t>() + record, 8);
+        *offset = v - 1;                                                 // the id begins behind the '>'
+    });
+}
+
+int sylph_sketch_push_fasta(sylph_sketch* sk, sylph_fasta* a, sylph_fasta* b, uint64_t first, uint64_t n_items) {
+    if (!sk || !a) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    uint64_t n_rec_batch = 0, n_bases = 0;
+    const int rc = guarded([&] {
+        sylph_ctx* ctx = sk->ctx;
+        SY_REQUIRE(a->ctx == ctx && (!b || b->ctx == ctx), "sylph_sketch_push_fasta: the index lives on another context than the session");
+        SY_REQUIRE((b != nullptr) == (sk->paired != 0), "sylph_sketch_push_fasta: a paired session takes two texts, a single-end session one");
+        SY_REQUIRE(first <= a->n_rec && n_items <= a->n_rec - first && (!b || (first <= b->n_rec && n_items <= b->n_rec - first)),
+                   "sylph_sketch_push_fasta: records [%llu, +%llu) are not all there", (unsigned long long)first, (unsigned long long)n_items);
+        if (!n_items) return;
+        n_rec_batch = fasta_reads_plan::batch_records(n_items, b != nullptr);
+        SY_REQUIRE(n_rec_batch < (1ull << 31), "sylph_sketch_push_fasta: at most 2^31 - 1 records per push");
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        // a deferred batch of this session reads sk->fq_bases until its verdict is in: settle it before the buffer is written again
+        resolve_deferred_slots(sk);
+        DevBuf& b_len = ctx->scratch[0];
+        DevBuf& b_off = ctx->scratch[1];
+        DevBuf& b_tot = ctx->scratch[2];
+        b_len.reserve((n_rec_batch + 1) * 4);
+        b_off.reserve((n_rec_batch + 1) * 4);
+        b_tot.reserve(8);
+        const uint64_t* ra = a->rec_off.as<uint64_t>();
+        const uint64_t* rb = b ? b->rec_off.as<uint64_t>() : nullptr;
+        SY_HIP(hipMemsetAsync(b_tot.p, 0, 8, ctx->stream));
+        hipLaunchKernelGGL(fa_batch_lens_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, ra, rb, first, n_rec_batch,
+                           b_len.as<uint32_t>(), b_tot.as<unsigned long long>());
+        SY_HIP(hipGetLastError());
+        exclusive_sum_u32(ctx, b_len.as<uint32_t>(), b_off.as<uint32_t>(), n_rec_batch + 1);
+        unsigned long long total = 0;
+        ctx->read_back(&total, b_tot.p, 8);
+        SY_REQUIRE(total < (1ull << 32) - 64, "sylph_sketch_push_fasta: %llu bases in one push (at most 2^32 - 65: push fewer records at a time)", total);
+        n_bases = total;
+        // no room for the joined files, the gathered batch and its seeding?  Say so BEFORE anything of the session is touched, as
+        // sylph_sketch_push_fastq does
+        uint64_t to_join = 0;
+        for (sylph_fasta* f : {a, b}) if (f && !f->joined_ready) to_join += f->n_bases + 64;
+        if (n_bases + 64 > sk->fq_bases.cap || to_join) {
+            size_t free_b = 0, total_b = 0;
+            size_t pooled = 0;                                  // blocks the context's pool holds and hands out again
+            for (const auto& blk : ctx->pool_free) pooled += blk.first;
+            const uint64_t batch_need = n_bases + 64 > sk->fq_bases.cap ? n_bases + n_bases / 2 + (256u << 20) : 0;
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + pooled < batch_need + to_join + to_join / 4)
+                throw HipError{hipErrorOutOfMemory, "sylph_sketch_push_fasta: no room for the batch", __FILE__, __LINE__};
+        }
+        // (a) the join, once per index: the file's bases side by side in a buffer of the index
+        ctx->counters.reserve(64);
+        bool joined_now = false;
+        for (sylph_fasta* f : {a, b}) {
+            if (!f || f->joined_ready) continue;
+            f->joined.reserve(f->n_bases + 64);
+            if (!joined_now) SY_HIP(hipMemsetAsync(ctx->counters.p, 0, 4, ctx->stream));
+            if (f->n_bases) fasta_join(f, f->joined.as<uint8_t>(), ctx->counters.as<uint32_t>());
+            joined_now = true;
+        }
+        if (joined_now) {
+            check_join(ctx, ctx->counters.as<uint32_t>());
+            for (sylph_fasta* f : {a, b}) if (f) f->joined_ready = true;
+        }
+        // (b) the gather, cut by output bytes
+        sk->fq_bases.reserve(n_bases + 64);
+        sk->fq_off.reserve((n_rec_batch + 1) * 8);
+        hipLaunchKernelGGL(fa_widen_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_off.as<uint32_t>(), n_rec_batch + 1,
+                           sk->fq_off.as<uint64_t>());
+        if (n_bases) {
+            ScopedKernelTimer t(ctx, "fasta_batch");
+            hipLaunchKernelGGL(fa_batch_kernel, dim3((uint32_t)((n_bases + fasta_reads_plan::TILE_BYTES - 1) / fasta_reads_plan::TILE_BYTES)), dim3(FQ_TPB), 0,
+                               ctx->stream, a->joined.as<uint8_t>(), ra, b ? b->joined.as<uint8_t>() : nullptr, rb, first, n_rec_batch, b_off.as<uint32_t>(),
+                               n_bases, sk->fq_bases.as<uint8_t>());
+        }
+        SY_HIP(hipMemsetAsync(sk->fq_bases.as<uint8_t>() + n_bases, 0, 64, ctx->stream));
+        SY_HIP(hipGetLastError());
+    });
+    if (rc != SYLPH_OK || !n_rec_batch) return rc;
+    return sylph_sketch_push_enc(sk, sk->fq_bases.as<uint8_t>(), sk->fq_off.as<uint64_t>(), n_rec_batch, n_bases, SYLPH_MEM_DEVICE, SYLPH_ENC_ASCII);
 }
 
 int sylph_fasta_counts(const sylph_fasta* f, uint64_t* n_records, uint64_t* n_bases, uint64_t* id_bytes) {

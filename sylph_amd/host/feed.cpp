@@ -716,7 +716,7 @@ bool TextUploader::send(sylph_ctx* ctx, const std::vector<std::string>& files, u
         fds[i].fd = open(files[i].c_str(), O_RDONLY);
         if (fds[i].fd < 0 || fstat(fds[i].fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size < 4) return false;
         uint8_t head[2];
-        if (pread(fds[i].fd, head, 2, 0) != 2 || head[0] != '@') return false;      // (gzip: 0x1f 0x8b; FASTA: '>')
+        if (pread(fds[i].fd, head, 2, 0) != 2 || (head[0] != '@' && head[0] != '>')) return false;      // FASTQ or FASTA text (gzip: 0x1f 0x8b)
         src.push_back(Src{fds[i].fd, nullptr, (uint64_t)st.st_size});
     }
     return send_sources(ctx, src, threads, out);
@@ -724,7 +724,7 @@ bool TextUploader::send(sylph_ctx* ctx, const std::vector<std::string>& files, u
 bool TextUploader::send(sylph_ctx* ctx, const std::vector<Mem>& texts, unsigned threads, std::vector<Text>& out) {
     std::vector<Src> src;
     for (const Mem& m : texts) {
-        if (!m.p || m.bytes < 4 || m.p[0] != '@') return false;
+        if (!m.p || m.bytes < 4 || (m.p[0] != '@' && m.p[0] != '>')) return false;
         src.push_back(Src{-1, m.p, m.bytes});
     }
     return send_sources(ctx, src, threads, out);

@@ -163,8 +163,12 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
 // lengths the device hands back).  Taken for every sample whose engine is already up — a process's FIRST sample is indexed and gathered
 // on the host while the GPU runtime initialises, which no device can do — unless SYLPH_HIP_FEED_DEVICE=0 (feed.cpp device_feed_enabled).
 // Returns false, having pushed
-// nothing, when the files are not plain four-line FASTQ (SYLPH_ERR_FORMAT, gzip, FASTA): the caller takes the host route, whose
+// nothing, when the files are not text the device indexes (SYLPH_ERR_FORMAT): the caller takes the host route, whose
 // record and error semantics are needletail's.
+// FASTA-format reads (csrc/fasta.hip sylph_sketch_push_fasta): the first byte of each mate's TEXT says which index finds its records
+// ('@': sylph_fastq_*, '>': sylph_fasta_*; ReadIndex below holds the two behind one set of calls); mates of different kinds, and
+// FASTA reads with SYLPH_HIP_FASTA_READS_DEVICE=0, are declined.  A plain FASTA sample waits for the engine even as a process's
+// first: its host road is the sequential reader.
 // `text`: the files' text where it lies in host memory already (the inflated copies of gzip files) instead of the files themselves
 // Round 6, gzip on the device (csrc/inflate.hip): a sample whose files are gzip sends their COMPRESSED bytes (0.4 B per base instead of
 // 2.1) and the library inflates them there — sylph_inflate; SYLPH_HIP_INFLATE_DEVICE=0 keeps the host's inflate.  What the library
@@ -193,6 +197,101 @@ struct MappedFile {                       // the compressed bytes of one file (r
 };
 struct InflatedText { sylph_inflated* h = nullptr; ~InflatedText() { sylph_inflated_destroy(h); } };
 
+// The two kinds of read text the device indexes (csrc/fastq.hip, csrc/fasta.hip) behind one set of calls: a route is written once and
+// asks the text's first byte which kind it is ('@': four-line FASTQ, '>': FASTA; needletail decides the same way).
+struct ReadIndex {
+    bool fasta = false;
+    sylph_fastq* q = nullptr;
+    sylph_fasta* a = nullptr;
+    ReadIndex() = default;
+    ReadIndex(const ReadIndex&) = delete;
+    ReadIndex& operator=(const ReadIndex&) = delete;
+    ~ReadIndex() { sylph_fastq_destroy(q); sylph_fasta_destroy(a); }
+    bool made() const { return q || a; }
+    const char* index_name() const { return fasta ? "sylph_fasta_index" : "sylph_fastq_index"; }
+    int index(sylph_ctx* ctx, const void* dev, uint64_t bytes) {
+        return fasta ? sylph_fasta_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &a) : sylph_fastq_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &q);
+    }
+    int index_window(sylph_ctx* ctx, const void* dev, uint64_t bytes, int final, uint64_t* consumed) {
+        return fasta ? sylph_fasta_index_window(ctx, dev, bytes, SYLPH_MEM_DEVICE, final, &a, consumed)
+                     : sylph_fastq_index_window(ctx, dev, bytes, SYLPH_MEM_DEVICE, final, &q, consumed);
+    }
+    void counts(uint64_t& n_rec, uint64_t& bases) const {
+        hip_check(fasta ? sylph_fasta_counts(a, &n_rec, &bases, nullptr) : sylph_fastq_counts(q, &n_rec, &bases), "sylph_fastx_counts");
+    }
+    uint64_t record_offset(uint64_t record) const {
+        uint64_t at = 0;
+        hip_check(fasta ? sylph_fasta_record_offset(a, record, &at) : sylph_fastq_record_offset(q, record, &at), "sylph_fastx_record_offset");
+        return at;
+    }
+    static int push(sylph_sketch* sk, const ReadIndex& m1, const ReadIndex* m2, uint64_t first, uint64_t n_items) {
+        return m1.fasta ? sylph_sketch_push_fasta(sk, m1.a, m2 ? m2->a : nullptr, first, n_items)
+                        : sylph_sketch_push_fastq(sk, m1.q, m2 ? m2->q : nullptr, first, n_items);
+    }
+};
+// the sequence lengths of records [0, n) of an index (u32 from the FASTQ index, u64 from the FASTA one), for the one sequential piece
+// of the reference's record loop: the running mean of the mate-1 read lengths (f64, file order: sketch.rs:941-943, :825-826)
+struct ReadLengths {
+    std::vector<uint32_t> q;
+    std::vector<uint64_t> a;
+    bool fasta = false;
+    void fetch(const ReadIndex& x, uint64_t n) {
+        fasta = x.fasta;
+        if (fasta) { a.resize(n); hip_check(sylph_fasta_lengths(x.a, 0, n, a.data()), "sylph_fasta_lengths"); }
+        else { q.resize(n); hip_check(sylph_fastq_lengths(x.q, 0, n, q.data()), "sylph_fastq_lengths"); }
+    }
+    uint64_t at(uint64_t i) const { return fasta ? a[i] : q[i]; }
+    void continue_mean(uint64_t n, double& mean, double& counter) const {
+        if (fasta) for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a[i] - mean) / counter; }
+        else for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)q[i] - mean) / counter; }
+    }
+};
+// pushes of whole records (pairs) below 2^31 bases and 2^30 items: one for anything up to ~2 Gbp
+std::vector<std::pair<uint64_t, uint64_t>> cut_pushes(const ReadIndex* m2, const ReadLengths& l1, uint64_t n, uint64_t bases) {
+    std::vector<std::pair<uint64_t, uint64_t>> pushes;
+    if (bases < (1ull << 31) && n < (1ull << 30)) {
+        if (n) pushes.emplace_back(0, n);
+        return pushes;
+    }
+    ReadLengths l2;
+    if (m2) l2.fetch(*m2, n);
+    uint64_t i0 = 0, sum = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t l = l1.at(i) + (m2 ? l2.at(i) : 0);
+        if (i > i0 && (sum + l >= (1ull << 31) || i - i0 >= (1ull << 30))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
+        sum += l;
+    }
+    if (n > i0) pushes.emplace_back(i0, n - i0);
+    return pushes;
+}
+// FASTA-format reads take the device routes unless SYLPH_HIP_FASTA_READS_DEVICE=0 keeps them on the host reader: every kind of sample
+// (plain, gzip, bzip2, gzip streamed) measured 2.4 to 9.4 times faster there (profiles/fasta_reads_device.txt)
+bool fasta_reads_on_device() {
+    static const bool on = [] { const char* e = getenv("SYLPH_HIP_FASTA_READS_DEVICE"); return !(e && *e) || atoi(e) != 0; }();
+    return on;
+}
+// a text of this many bytes or more is not indexed in one piece by sylph_fasta_index (include/sylph_hip.h)
+constexpr uint64_t FASTA_INDEX_MAX_TEXT = (1ull << 32) - 4096;
+// the first byte of a decoded file's text, which lies on the device
+uint8_t first_byte_of(sylph_inflated* t, const void* dev_file) {
+    const void* base = nullptr;
+    uint8_t c = 0;
+    hip_check(sylph_inflated_text(t, &base, nullptr), "sylph_inflated_text");
+    hip_check(sylph_inflated_read(t, (uint64_t)((const uint8_t*)dev_file - (const uint8_t*)base), 1, &c), "sylph_inflated_read");
+    return c;
+}
+// ... of a regular file (0 for anything else: a pipe can be read once, front to back, and nothing may peek at it)
+uint8_t first_byte_of(const std::string& file) {
+    uint8_t c = 0;
+    struct stat st;
+    if (stat(file.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) return 0;
+    const int fd = open(file.c_str(), O_RDONLY);
+    if (fd < 0) return 0;
+    if (pread(fd, &c, 1, 0) != 1) c = 0;
+    close(fd);
+    return c;
+}
+
 // SYLPH_HIP_INFLATE_STREAM: "auto" (default: the stream takes what the whole-file road declines for size or for room), "1" always, "0" never
 enum class StreamMode { Auto, Always, Never };
 StreamMode stream_mode() {
@@ -212,7 +311,7 @@ uint64_t inflate_whole_max() { return std::min<uint64_t>(env_bytes("SYLPH_HIP_IN
 // The stream route for gzip samples (csrc/inflate.hip sylph_inflate_stream_*): the compressed bytes go to the device one slice per mate
 // at a time, the records of every window are found there and pushed, and what a window holds beyond its last pushed record is kept for
 // the next one — memory is a function of the slice, not of the sample (the reference streams records in O(batch) memory too:
-// sketch.rs:780-781, :806-815, :906).  Per step: next; index each mate's window (final = the file's finished flag); push
+// sketch.rs:780-781, :806-815, :906).  Per step: next; index each mate's window (final = the file's finished flag; the FASTQ or the FASTA index, by the first byte of the mate's text); push
 // min(complete records of mate 1, of mate 2) pairs; keep every mate's text from its first record that was not pushed; advance only the
 // mate with fewer records waiting (both when they are level), which bounds the carried text.  Surplus records of the longer mate are
 // dropped at the end (lock-step readers, sketch.rs:813-815); the running mean of the mate-1 lengths is the same f64 recurrence in
@@ -230,62 +329,59 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
         if (trace) fprintf(stderr, "[sylph_hip feed] stream route declined %s at %s: %s\n", name, what, sylph_last_error());
         return false;
     };
+    auto not_taken = [&](const char* why) {
+        if (trace) fprintf(stderr, "[sylph_hip feed] stream route declined %s: %s\n", name, why);
+        return false;
+    };
     int rc = sylph_inflate_stream_open(ctx, ptrs.data(), lens.data(), F, SYLPH_MEM_HOST, env_bytes("SYLPH_HIP_INFLATE_SLICE", 0), &st.h);
     if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_open");
     sylph_sketch* const sk = open_session();
     e.batch.flush(sk);
-    struct Fq { sylph_fastq* f = nullptr; ~Fq() { sylph_fastq_destroy(f); } };
     std::unique_ptr<InflatedText> prev;                        // the window of the step before: its kept tail is copied out of it by `next`
     std::vector<uint8_t> advance(F, 1), finished(F, 0);
     std::vector<uint64_t> keep(F, 0);
-    std::vector<uint32_t> la, lb;
+    ReadLengths la;
     double mean = 0., counter = 0.;
     uint64_t pairs = 0;
+    std::vector<int> kind(F, -1);                              // 1: the mate's text is FASTA, 0: it is not, -1: no byte of it seen yet
     for (bool first = true;; first = false) {
         std::unique_ptr<InflatedText> win(new InflatedText());
         rc = sylph_inflate_stream_next(st.h, advance.data(), first ? nullptr : keep.data(), &win->h, finished.data());
         if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_next");
         prev.reset();                                          // (its indexes went with the previous step's scope)
-        std::vector<Fq> fq(F);
+        std::vector<ReadIndex> fq(F);
         std::vector<uint64_t> n_rec(F, 0), bytes(F, 0), bases(F, 0);
+        std::vector<const void*> dev(F, nullptr);
+        for (uint32_t i = 0; i < F; i++) hip_check(sylph_inflated_file(win->h, i, &dev[i], &bytes[i]), "sylph_inflated_file");
         for (uint32_t i = 0; i < F; i++) {
-            const void* dev = nullptr;
-            hip_check(sylph_inflated_file(win->h, i, &dev, &bytes[i]), "sylph_inflated_file");
+            if (kind[i] >= 0 || !bytes[i]) continue;           // asked once, of the first text a mate shows
+            kind[i] = first_byte_of(win->h, dev[i]) == '>';
+            if (kind[i] && !fasta_reads_on_device()) return not_taken("FASTA reads stay on the host reader");
+        }
+        if (F == 2 && kind[0] >= 0 && kind[1] >= 0 && kind[0] != kind[1]) return not_taken("one mate is FASTA, the other is not");
+        for (uint32_t i = 0; i < F; i++) {
             if (finished[i] && !bytes[i]) continue;            // nothing left of a finished file: no records
             uint64_t consumed = 0;
-            rc = sylph_fastq_index_window(ctx, dev, bytes[i], SYLPH_MEM_DEVICE, finished[i] ? 1 : 0, &fq[i].f, &consumed);
-            if (rc != SYLPH_OK) return declined(rc, "sylph_fastq_index_window");
-            hip_check(sylph_fastq_counts(fq[i].f, &n_rec[i], &bases[i]), "sylph_fastq_counts");
+            fq[i].fasta = kind[i] > 0;
+            rc = fq[i].index_window(ctx, dev[i], bytes[i], finished[i] ? 1 : 0, &consumed);
+            if (rc != SYLPH_OK) return declined(rc, fq[i].fasta ? "sylph_fasta_index_window" : "sylph_fastq_index_window");
+            fq[i].counts(n_rec[i], bases[i]);
         }
         const uint64_t n = F == 2 ? std::min(n_rec[0], n_rec[1]) : n_rec[0];
         if (n) {
-            la.resize(n);
-            hip_check(sylph_fastq_lengths(fq[0].f, 0, n, la.data()), "sylph_fastq_lengths");
-            for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)la[i] - mean) / counter; }      // sketch.rs:941-943, :825-826
-            // pushes of whole records (pairs) below 2^31 bases and 2^30 items
-            std::vector<std::pair<uint64_t, uint64_t>> pushes;
-            if (bases[0] + (F == 2 ? bases[1] : 0) < (1ull << 31) && n < (1ull << 30)) pushes.emplace_back(0, n);
-            else {
-                if (F == 2) { lb.resize(n); hip_check(sylph_fastq_lengths(fq[1].f, 0, n, lb.data()), "sylph_fastq_lengths"); }
-                uint64_t i0 = 0, sum = 0;
-                for (uint64_t i = 0; i < n; i++) {
-                    const uint64_t l = (uint64_t)la[i] + (F == 2 ? lb[i] : 0);
-                    if (i > i0 && (sum + l >= (1ull << 31) || i - i0 >= (1ull << 30))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
-                    sum += l;
-                }
-                if (n > i0) pushes.emplace_back(i0, n - i0);
-            }
-            for (const auto& p : pushes) {
-                rc = sylph_sketch_push_fastq(sk, fq[0].f, F == 2 ? fq[1].f : nullptr, p.first, p.second);
-                if (rc == SYLPH_ERR_NOMEM) return declined(rc, "sylph_sketch_push_fastq");
-                hip_check(rc, "sylph_sketch_push_fastq");
+            la.fetch(fq[0], n);
+            la.continue_mean(n, mean, counter);                // sketch.rs:941-943, :825-826
+            for (const auto& p : cut_pushes(F == 2 ? &fq[1] : nullptr, la, n, bases[0] + (F == 2 ? bases[1] : 0))) {
+                rc = ReadIndex::push(sk, fq[0], F == 2 ? &fq[1] : nullptr, p.first, p.second);
+                if (rc == SYLPH_ERR_NOMEM) return declined(rc, fq[0].fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
+                hip_check(rc, fq[0].fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
             }
             pairs += n;
         }
         bool all_done = true;
         for (uint32_t i = 0; i < F; i++) {
             keep[i] = bytes[i];
-            if (fq[i].f) { hip_check(sylph_fastq_record_offset(fq[i].f, n, &keep[i]), "sylph_fastq_record_offset"); keep[i] = std::min(keep[i], bytes[i]); }
+            if (fq[i].made()) keep[i] = std::min(fq[i].record_offset(n), bytes[i]);
             all_done = all_done && finished[i];
         }
         // a finished mate with nothing waiting ends the lock-step reading: the other mate's surplus is dropped (sketch.rs:813-815)
@@ -302,8 +398,8 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
     hip_check(sylph_inflate_stream_info(st.h, &n_slices, &text_bytes, &peak_scratch, &peak_window), "sylph_inflate_stream_info");
     if (trace) {
         char what[192];
-        snprintf(what, sizeof(what), "stream route: gzip inflated on the device in %llu slices (%llu records, %llu text bytes, peak scratch %llu, peak window %llu)",
-                 (unsigned long long)n_slices, (unsigned long long)pairs, (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
+        snprintf(what, sizeof(what), "stream route: gzip inflated on the device in %llu slices (%llu %s records, %llu text bytes, peak scratch %llu, peak window %llu)",
+                 (unsigned long long)n_slices, (unsigned long long)pairs, kind[0] > 0 ? "FASTA" : "FASTQ", (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
         laps.lap(what);
     }
     mean_read_length = mean;
@@ -317,13 +413,31 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     const std::string& f1 = sample.first;
     const std::string* f2 = sample.second ? &*sample.second : nullptr;
     const bool gz = !text && decode == Container::Gzip, bz = !text && decode == Container::Bzip2;
-    if (!gz && !bz && !e.ready()) return false;      // (a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that)
+    std::vector<std::string> files{f1};
+    if (f2) files.push_back(*f2);
+    std::vector<uint8_t> heads;                      // the first byte of every mate's TEXT: '@' FASTQ, '>' FASTA
+    if (!gz && !bz && !text) for (const auto& f : files) heads.push_back(first_byte_of(f));
+    // a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that — and so does plain FASTA, whose host
+    // road is the sequential reader
+    const bool plain_fasta = !heads.empty() && heads[0] == '>' && fasta_reads_on_device();
+    if (!gz && !bz && !plain_fasta && !e.ready()) return false;
     const bool trace = FeedLaps::on();
     FeedLaps laps;
     sylph_ctx* ctx = e.context();
-    std::vector<std::string> files{f1};
-    if (f2) files.push_back(*f2);
     std::vector<TextUploader::Text> texts;
+    auto same_kind = [](const std::vector<uint8_t>& h) { return h.size() < 2 || ((h[0] == '>') == (h[1] == '>')); };
+    // FASTA reads that stay on the host reader, mates of different kinds: declined before anything travels
+    auto taken = [&] {
+        if (!same_kind(heads)) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: one mate is FASTA, the other is not\n", files[0].c_str());
+            return false;
+        }
+        if (heads[0] == '>' && !fasta_reads_on_device()) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: FASTA reads stay on the host reader\n", files[0].c_str());
+            return false;
+        }
+        return true;
+    };
     InflatedText inflated;                           // (destroyed behind the indexes that borrow its text: declared before them)
     if (gz || bz) {
         // both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files): one scan, one decode launch, one chain — the mates share a block's latency
@@ -374,8 +488,21 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             hip_check(sylph_inflated_file(inflated.h, i, &dev, &bytes), "sylph_inflated_file");
             if (!bytes) return false;
             texts.push_back(TextUploader::Text{(const uint8_t*)dev, bytes});
+            heads.push_back(first_byte_of(inflated.h, dev));
         }
         laps.lap(gz ? "device route: gzip inflated on the device" : "device route: bzip2 decoded on the device");
+        // a gzip FASTA text too long for one FASTA index: the stream's windows are smaller
+        bool fasta_too_long = false;
+        for (size_t i = 0; i < texts.size(); i++) fasta_too_long = fasta_too_long || (heads[i] == '>' && texts[i].bytes >= FASTA_INDEX_MAX_TEXT);
+        if (gz && fasta_too_long && same_kind(heads) && stream_mode() == StreamMode::Auto && fasta_reads_on_device()) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device route: a FASTA text of %s is too long for one index: the stream takes it\n", files[0].c_str());
+            texts.clear();
+            sylph_inflated_destroy(inflated.h);
+            inflated.h = nullptr;
+            if (!sketch_gzip_streamed(e, open_session, ptrs, lens, files[0].c_str(), mean_read_length)) return false;
+            laps.lap("device route: gzip streamed through the device inflate");
+            return true;
+        }
     } else if (text) {
         // The first text an engine sends pays for the route's device buffers (~40-90 ms of allocations, once); skipping the host's index
         // and gather of an inflated copy buys that back only for a sample of some size: 0.45 against 0.53 s for a 1 Gbp gzip pair, 0.34
@@ -384,48 +511,46 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
         if (!e.text.warm() && bytes < (1500ull << 20)) return false;
         std::vector<TextUploader::Mem> mem{{text->a->data, text->a->size}};
         if (f2) mem.push_back({text->b->data, text->b->size});
+        for (const auto& m : mem) heads.push_back(m.p && m.bytes ? m.p[0] : 0);
+        if (!taken()) return false;
         if (!e.text.send(ctx, mem, parse_threads(), texts)) return false;
-    } else if (!e.text.send(ctx, files, parse_threads(), texts)) return false;
-    if (!gz && !bz) laps.lap("device route: text uploaded");
-    struct Fq { sylph_fastq* f = nullptr; ~Fq() { sylph_fastq_destroy(f); } } fa, fb;
-    auto index = [&](const TextUploader::Text& t, Fq& out) {
-        const int rc = sylph_fastq_index(ctx, t.dev, t.bytes, SYLPH_MEM_DEVICE, &out.f);
-        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) return false;   // not for this route / no room for it: the host feed
-        hip_check(rc, "sylph_fastq_index");
+    } else {
+        if (!taken()) return false;
+        if (!e.text.send(ctx, files, parse_threads(), texts)) return false;
+    }
+    if (gz || bz) { if (!taken()) return false; }
+    else laps.lap("device route: text uploaded");
+    const bool fasta = heads[0] == '>';
+    ReadIndex fa, fb;
+    fa.fasta = fb.fasta = fasta;
+    auto index = [&](const TextUploader::Text& t, ReadIndex& out) {
+        const int rc = out.index(ctx, t.dev, t.bytes);
+        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {               // not for this route / no room for it: the host feed
+            if (trace && fasta) fprintf(stderr, "[sylph_hip feed] device route declined %s: %s\n", files[0].c_str(), sylph_last_error());
+            return false;
+        }
+        hip_check(rc, out.index_name());
         return true;
     };
     if (!index(texts[0], fa) || (f2 && !index(texts[1], fb))) return false;
     uint64_t na = 0, nb = 0, bases_a = 0, bases_b = 0;
-    hip_check(sylph_fastq_counts(fa.f, &na, &bases_a), "sylph_fastq_counts");
-    if (f2) hip_check(sylph_fastq_counts(fb.f, &nb, &bases_b), "sylph_fastq_counts");
+    fa.counts(na, bases_a);
+    if (f2) fb.counts(nb, bases_b);
     const uint64_t n = f2 ? std::min(na, nb) : na;                         // lock-step readers: sketch.rs:813-815
-    laps.lap("device route: records found");
-    std::vector<uint32_t> la(n), lb;
-    hip_check(sylph_fastq_lengths(fa.f, 0, n, la.data()), "sylph_fastq_lengths");
+    laps.lap(fasta ? "device route: FASTA records found" : "device route: records found");
+    ReadLengths la;
+    la.fetch(fa, n);
     // the one sequential piece of the reference's record loop (f64, file order: sketch.rs:941-943, :825-826), on its own thread
     double mean = 0.;
-    std::thread tm([&] { double counter = 0.; for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)la[i] - mean) / counter; } });
+    std::thread tm([&] { double counter = 0.; la.continue_mean(n, mean, counter); });
     ThreadJoiner jm{tm};
-    // pushes of whole records (pairs) below 2^31 bases and 2^30 items: one for anything up to ~2 Gbp
-    std::vector<std::pair<uint64_t, uint64_t>> pushes;
-    if (bases_a + bases_b < (1ull << 31) && n < (1ull << 30)) {
-        if (n) pushes.emplace_back(0, n);
-    } else {
-        if (f2) { lb.resize(n); hip_check(sylph_fastq_lengths(fb.f, 0, n, lb.data()), "sylph_fastq_lengths"); }
-        uint64_t i0 = 0, sum = 0;
-        for (uint64_t i = 0; i < n; i++) {
-            const uint64_t l = (uint64_t)la[i] + (f2 ? lb[i] : 0);
-            if (i > i0 && (sum + l >= (1ull << 31) || i - i0 >= (1ull << 30))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
-            sum += l;
-        }
-        if (n > i0) pushes.emplace_back(i0, n - i0);
-    }
+    const auto pushes = cut_pushes(f2 ? &fb : nullptr, la, n, bases_a + bases_b);
     sylph_sketch* const sk = open_session();
     e.batch.flush(sk);
     // one push: the batch is the session's own buffer, valid until finish — the seeding verdict may wait for it (one host round trip less)
     if (pushes.size() == 1) hip_check(sylph_sketch_set_option(sk, "borrow_until_finish", "1"), "sylph_sketch_set_option");
     for (const auto& p : pushes) {
-        const int rc = sylph_sketch_push_fastq(sk, fa.f, f2 ? fb.f : nullptr, p.first, p.second);
+        const int rc = ReadIndex::push(sk, fa, f2 ? &fb : nullptr, p.first, p.second);
         if (rc == SYLPH_ERR_NOMEM) {
             // no room on the device for this route's batch (the whole sample in one piece, up to 2 Gbp): not an error — the host feed, which
             // works through a sample in 256 Mbp batches, takes the sample from its start; the caller opens a fresh session
@@ -433,7 +558,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             tm.join();
             return false;
         }
-        hip_check(rc, "sylph_sketch_push_fastq");
+        hip_check(rc, fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
     }
     laps.lap("device route: pushed");
     tm.join();
@@ -537,13 +662,15 @@ SampleRoute::SampleRoute(Engine& eng, FeedShared& feed, size_t j, bool first_use
     const Container c1 = feed_dev ? container_of(files.first) : Container::Plain;
     const bool compressed = c1 != Container::Plain;
     const bool decoded = device_decode_enabled(c1);           // the compressed bytes travel, the device inflates / decodes (mate 1 decides the road)
-    dev = feed_dev && (decoded || (eng.ready() && !compressed));
+    // plain FASTA reads: the host road is the sequential reader, so the sample waits for the engine as a compressed one does
+    const bool plain_fasta = feed_dev && !compressed && fasta_reads_on_device() && first_byte_of(files.first) == '>';
+    dev = feed_dev && (decoded || plain_fasta || (eng.ready() && !compressed));
     // ... the device's decoder is the one to use if mate 2 is of the same container; if not, the device route declines the pair
     if (decoded && (!files.second || container_of(*files.second) == c1)) decode = c1;
     if (c1 == Container::Gzip && !decoded) pre = index_inputs(files, false);   // inflated on the host, its text then sent as it is
     else if (!dev) pre = feed.ahead.get(j);
     if (first_use_hint) {
-        if (decoded && !eng.ready()) { eng.defer_pinned.store(true); eng.warm_text_route.store(true); }
+        if ((decoded || plain_fasta) && !eng.ready()) { eng.defer_pinned.store(true); eng.warm_text_route.store(true); }
         trace_mark(dev ? "sketch: the sample goes the device route" : "sketch: the sample's files are indexed (or not indexable)");
     }
     if (++feed.indexes_obtained == feed.ahead.size()) set_no_more_inflates(true);

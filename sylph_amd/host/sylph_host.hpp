@@ -233,7 +233,7 @@ class TextUploader {
     ~TextUploader();
     void prepare(sylph_ctx* ctx);   // page-locks the two chunks ahead of the first send (the engine's background bring-up)
     bool warm() const { return sent_.load(); }   // a text has travelled before: the device-side buffers of the route exist
-    // false: some file is not a candidate (not a regular file, empty, gzip magic, does not begin with '@') — nothing was sent
+    // false: some file is not a candidate (not a regular file, empty, gzip magic, begins with neither '@' nor '>') — nothing was sent
     bool send(sylph_ctx* ctx, const std::vector<std::string>& files, unsigned threads, std::vector<Text>& out);
     // the same for texts that lie in host memory already (the inflated copies of gzip files)
     struct Mem { const uint8_t* p; uint64_t bytes; };
