@@ -22,7 +22,7 @@
 // The same text as a SAMPLE's reads (sylph_sketch_push_fasta; fasta_reads_plan.h):
 //
 //   fa_join_kernel      once per index, into a buffer of the index: the file's bases side by side
-//   fa_batch_lens_kernel, exclusive scan    the 32-bit offsets of the batch's records (pairs interleaved: mate 1, mate 2)
+//   batch_lens_kernel, exclusive scan       the 32-bit offsets of the batch's records (pairs interleaved: mate 1, mate 2)
 //   fa_batch_kernel     per 4 KiB tile of the BATCH: a lane finds the record of its first output byte by a binary search in the offsets,
 //                       walks over the record boundaries inside its 16 bytes, cuts every piece out of two aligned 16-byte loads of the
 //                       file's joined bases and writes one aligned 16-byte store.  No lane loops over a record.
@@ -35,6 +35,7 @@
 #include "device_common.h"
 #include "sketch_session.h"
 #include "text_lines.h"
+#include "read_text.h"
 #include "fasta_plan.h"
 #include "fasta_reads_plan.h"
 
@@ -211,23 +212,11 @@ __global__ __launch_bounds__(256) void fa_ids_kernel(const uint8_t* __restrict__
     }
 }
 
-// lengths of a batch's records in batch order (pairs interleaved), one sentinel 0 behind them for the scan; their 64-bit sum in *total
-// (the scan is a 32-bit one: the caller checks the sum before it trusts the offsets)
-__global__ void fa_batch_lens_kernel(const uint64_t* __restrict__ ra, const uint64_t* __restrict__ rb, uint64_t first, uint64_t n_rec_batch,
-                                     uint32_t* __restrict__ out, unsigned long long* __restrict__ total) {
-    unsigned long long sum = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= n_rec_batch; j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t l = j == n_rec_batch ? 0u : rp::batch_len(ra, rb, first, j);
-        out[j] = l;
-        sum += l;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
-}
-__global__ void fa_widen_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ out) {
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) out[j] = in[j];
-}
+// how a batch's record j reads its length (read_text.h batch_lens_kernel): from its file's record offsets (fasta_reads_plan.h batch_len)
+struct FaLen {
+    const uint64_t *ra, *rb;
+    __device__ uint32_t operator()(uint64_t first, uint64_t j) const { return rp::batch_len(ra, rb, first, j); }
+};
 
 // One workgroup per 4 KiB tile of the batch, one lane per 16 output bytes (fasta_reads_plan.h lane_walk).  ja / jb: the joined bases of
 // the two files (16-byte aligned, readable 32 bytes past their last base; jb = nullptr: single-end), ra / rb: their record offsets;
@@ -252,29 +241,15 @@ __global__ __launch_bounds__(FQ_TPB) void fa_batch_kernel(const uint8_t* __restr
     *reinterpret_cast<uint4*>(bases + o) = make_uint4((uint32_t)out_lo, (uint32_t)(out_lo >> 32), (uint32_t)out_hi, (uint32_t)(out_hi >> 32));
 }
 
-struct FormatError { std::string msg; };
-
-uint32_t grid1(uint64_t n, uint32_t tpb = 256, uint32_t cap = 1u << 30) { return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, (n + tpb - 1) / tpb)); }
-
 // window: the text goes on behind its last byte (sylph_fasta_index_window, final == 0) — the same kernels over the same bytes, and then
 // the last header's record is taken off the index again (fasta_reads_plan.h window_records)
 void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int mem, bool window = false) {
     sylph_ctx* ctx = f->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
-    if (mem == SYLPH_MEM_DEVICE) {
-        f->text = (const uint8_t*)text;
-    } else {
-        if (((const uint8_t*)text)[0] != '>') throw FormatError{"the first byte is not '>'"};
-        f->text_own.reserve(n_bytes + 64);
-        if (mem == SYLPH_MEM_HOST_PINNED) SY_HIP(hipMemcpyAsync(f->text_own.p, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-        else ctx->h2d(f->text_own.p, text, n_bytes);
-        f->text = f->text_own.as<uint8_t>();
-    }
+    if (mem != SYLPH_MEM_DEVICE && ((const uint8_t*)text)[0] != '>') throw FormatError{"the first byte is not '>'"};   // (before anything travels)
+    const auto [al, bias, n_tiles] = take_text(ctx, f->text_own, &f->text, text, n_bytes, mem);
     f->n = n_bytes;
-    const uint32_t bias = (uint32_t)((uintptr_t)f->text & 15);
-    const uint8_t* al = f->text - bias;
-    const uint64_t n_tiles = (n_bytes + bias + FQ_TILE - 1) / FQ_TILE;
     f->n_tiles = n_tiles;
     DevBuf& b_words = ctx->scratch[0];
     DevBuf& b_cnt = ctx->scratch[1];
@@ -302,7 +277,7 @@ void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int me
     b_val.reserve((n_lines + 1) * 8);
     hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, &d_w->q, f->tile_base.as<uint32_t>(), n_lines,
                        f->line_start.as<uint64_t>());
-    hipLaunchKernelGGL(fa_values_kernel, dim3(grid1(n_lines + 1)), dim3(256), 0, ctx->stream, f->text, f->line_start.as<uint64_t>(), n_lines,
+    hipLaunchKernelGGL(fa_values_kernel, dim3(grid1(n_lines + 1, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, f->line_start.as<uint64_t>(), n_lines,
                        b_val.as<uint64_t>());
     SY_HIP(hipGetLastError());
     exclusive_sum_u64(ctx, b_val.as<uint64_t>(), f->scan.as<uint64_t>(), n_lines + 1);
@@ -313,7 +288,7 @@ void fasta_index_impl(sylph_fasta* f, const void* text, uint64_t n_bytes, int me
     f->rec_off.reserve((f->n_rec + 1) * 8);
     f->id_pos.reserve(f->n_rec * 8 + 8);
     f->id_len.reserve(f->n_rec * 4 + 4);
-    hipLaunchKernelGGL(fa_records_kernel, dim3(grid1(n_lines + 1)), dim3(256), 0, ctx->stream, f->text, f->line_start.as<uint64_t>(),
+    hipLaunchKernelGGL(fa_records_kernel, dim3(grid1(n_lines + 1, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, f->line_start.as<uint64_t>(),
                        f->scan.as<uint64_t>(), n_lines, f->n_rec, f->rec_off.as<uint64_t>(), f->id_pos.as<uint64_t>(), f->id_len.as<uint32_t>(), d_w);
     SY_HIP(hipGetLastError());
     ctx->read_back(&hw, d_w, sizeof(hw));
@@ -367,33 +342,19 @@ extern "C" {
 
 int sylph_fasta_index(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, sylph_fasta** out) {
     if (!ctx || !out || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    if (!mem_kind_ok(mem)) return SYLPH_ERR_INVALID;
     *out = nullptr;
     if (n_bytes == 0) { set_error("sylph_fasta_index: no text"); return SYLPH_ERR_FORMAT; }
     if (!fasta_plan::text_size_ok(n_bytes)) {
         set_error("sylph_fasta_index: %llu bytes of text: fewer than 2^32 - 4096 per index", (unsigned long long)n_bytes);
         return SYLPH_ERR_FORMAT;
     }
-    ctx->refs.fetch_add(1);
-    sylph_fasta* f = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        f = new sylph_fasta(ctx);
-        try { fasta_index_impl(f, text, n_bytes, mem); }
-        catch (const FormatError& e) { set_error("sylph_fasta_index: not FASTA text this index takes: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); DeviceGuard dg(ctx->device); (void)hipStreamSynchronize(ctx->stream); delete f; }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = f;
-    return SYLPH_OK;
+    return make_index(ctx, "sylph_fasta_index", "not FASTA text this index takes", out, [&](sylph_fasta* f) { fasta_index_impl(f, text, n_bytes, mem); });
 }
 
 int sylph_fasta_index_window(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, int final, sylph_fasta** out, uint64_t* consumed) {
     if (!ctx || !out || !consumed || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    if (!mem_kind_ok(mem)) return SYLPH_ERR_INVALID;
     *out = nullptr;
     *consumed = 0;
     if (final) {                                                         // exactly sylph_fasta_index
@@ -405,23 +366,11 @@ int sylph_fasta_index_window(sylph_ctx* ctx, const void* text, uint64_t n_bytes,
         set_error("sylph_fasta_index_window: %llu bytes of text: fewer than 2^32 - 4096 per index", (unsigned long long)n_bytes);
         return SYLPH_ERR_FORMAT;
     }
-    ctx->refs.fetch_add(1);
-    sylph_fasta* f = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        f = new sylph_fasta(ctx);
-        if (!n_bytes) return;                                            // no text yet: no records, nothing consumed
-        try { fasta_index_impl(f, text, n_bytes, mem, true); }
-        catch (const FormatError& e) { set_error("sylph_fasta_index_window: not FASTA text this index takes: %s", e.msg.c_str()); format = 1; }
+    const int rc = make_index(ctx, "sylph_fasta_index_window", "not FASTA text this index takes", out, [&](sylph_fasta* f) {
+        if (n_bytes) fasta_index_impl(f, text, n_bytes, mem, true);      // (no text yet: no records, nothing consumed)
     });
-    if (rc != SYLPH_OK || format) {
-        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); DeviceGuard dg(ctx->device); (void)hipStreamSynchronize(ctx->stream); delete f; }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = f;
-    *consumed = f->end;
-    return SYLPH_OK;
+    if (rc == SYLPH_OK) *consumed = (*out)->end;
+    return rc;
 }
 
 int sylph_fasta_record_offset(sylph_fasta* f, uint64_t record, uint64_t* offset) {
@@ -439,79 +388,38 @@ int sylph_fasta_record_offset(sylph_fasta* f, uint64_t record, uint64_t* offset)
 
 int sylph_sketch_push_fasta(sylph_sketch* sk, sylph_fasta* a, sylph_fasta* b, uint64_t first, uint64_t n_items) {
     if (!sk || !a) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    uint64_t n_rec_batch = 0, n_bases = 0;
-    const int rc = guarded([&] {
-        sylph_ctx* ctx = sk->ctx;
-        SY_REQUIRE(a->ctx == ctx && (!b || b->ctx == ctx), "sylph_sketch_push_fasta: the index lives on another context than the session");
-        SY_REQUIRE((b != nullptr) == (sk->paired != 0), "sylph_sketch_push_fasta: a paired session takes two texts, a single-end session one");
-        SY_REQUIRE(first <= a->n_rec && n_items <= a->n_rec - first && (!b || (first <= b->n_rec && n_items <= b->n_rec - first)),
-                   "sylph_sketch_push_fasta: records [%llu, +%llu) are not all there", (unsigned long long)first, (unsigned long long)n_items);
-        if (!n_items) return;
-        n_rec_batch = fasta_reads_plan::batch_records(n_items, b != nullptr);
-        SY_REQUIRE(n_rec_batch < (1ull << 31), "sylph_sketch_push_fasta: at most 2^31 - 1 records per push");
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        // a deferred batch of this session reads sk->fq_bases until its verdict is in: settle it before the buffer is written again
-        resolve_deferred_slots(sk);
-        DevBuf& b_len = ctx->scratch[0];
-        DevBuf& b_off = ctx->scratch[1];
-        DevBuf& b_tot = ctx->scratch[2];
-        b_len.reserve((n_rec_batch + 1) * 4);
-        b_off.reserve((n_rec_batch + 1) * 4);
-        b_tot.reserve(8);
-        const uint64_t* ra = a->rec_off.as<uint64_t>();
-        const uint64_t* rb = b ? b->rec_off.as<uint64_t>() : nullptr;
-        SY_HIP(hipMemsetAsync(b_tot.p, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(fa_batch_lens_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, ra, rb, first, n_rec_batch,
-                           b_len.as<uint32_t>(), b_tot.as<unsigned long long>());
-        SY_HIP(hipGetLastError());
-        exclusive_sum_u32(ctx, b_len.as<uint32_t>(), b_off.as<uint32_t>(), n_rec_batch + 1);
-        unsigned long long total = 0;
-        ctx->read_back(&total, b_tot.p, 8);
-        SY_REQUIRE(total < (1ull << 32) - 64, "sylph_sketch_push_fasta: %llu bases in one push (at most 2^32 - 65: push fewer records at a time)", total);
-        n_bases = total;
-        // no room for the joined files, the gathered batch and its seeding?  Say so BEFORE anything of the session is touched, as
-        // sylph_sketch_push_fastq does
-        uint64_t to_join = 0;
-        for (sylph_fasta* f : {a, b}) if (f && !f->joined_ready) to_join += f->n_bases + 64;
-        if (n_bases + 64 > sk->fq_bases.cap || to_join) {
-            size_t free_b = 0, total_b = 0;
-            size_t pooled = 0;                                  // blocks the context's pool holds and hands out again
-            for (const auto& blk : ctx->pool_free) pooled += blk.first;
-            const uint64_t batch_need = n_bases + 64 > sk->fq_bases.cap ? n_bases + n_bases / 2 + (256u << 20) : 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + pooled < batch_need + to_join + to_join / 4)
-                throw HipError{hipErrorOutOfMemory, "sylph_sketch_push_fasta: no room for the batch", __FILE__, __LINE__};
-        }
-        // (a) the join, once per index: the file's bases side by side in a buffer of the index
-        ctx->counters.reserve(64);
-        bool joined_now = false;
-        for (sylph_fasta* f : {a, b}) {
-            if (!f || f->joined_ready) continue;
-            f->joined.reserve(f->n_bases + 64);
-            if (!joined_now) SY_HIP(hipMemsetAsync(ctx->counters.p, 0, 4, ctx->stream));
-            if (f->n_bases) fasta_join(f, f->joined.as<uint8_t>(), ctx->counters.as<uint32_t>());
-            joined_now = true;
-        }
-        if (joined_now) {
-            check_join(ctx, ctx->counters.as<uint32_t>());
-            for (sylph_fasta* f : {a, b}) if (f) f->joined_ready = true;
-        }
-        // (b) the gather, cut by output bytes
-        sk->fq_bases.reserve(n_bases + 64);
-        sk->fq_off.reserve((n_rec_batch + 1) * 8);
-        hipLaunchKernelGGL(fa_widen_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_off.as<uint32_t>(), n_rec_batch + 1,
-                           sk->fq_off.as<uint64_t>());
-        if (n_bases) {
+    sylph_ctx* ctx = sk->ctx;
+    const uint64_t* ra = a->rec_off.as<uint64_t>();
+    const uint64_t* rb = b ? b->rec_off.as<uint64_t>() : nullptr;
+    return push_read_text(
+        "sylph_sketch_push_fasta", sk, a, b, first, n_items, FaLen{ra, rb},
+        [&] {                                                            // room for the files that are not joined yet
+            uint64_t to_join = 0;
+            for (sylph_fasta* f : {a, b}) if (f && !f->joined_ready) to_join += f->n_bases + 64;
+            return to_join;
+        },
+        [&] {                                                            // (a) the join, once per index: the file's bases side by side in a buffer of the index
+            ctx->counters.reserve(64);
+            bool joined_now = false;
+            for (sylph_fasta* f : {a, b}) {
+                if (!f || f->joined_ready) continue;
+                f->joined.reserve(f->n_bases + 64);
+                if (!joined_now) SY_HIP(hipMemsetAsync(ctx->counters.p, 0, 4, ctx->stream));
+                if (f->n_bases) fasta_join(f, f->joined.as<uint8_t>(), ctx->counters.as<uint32_t>());
+                joined_now = true;
+            }
+            if (joined_now) {
+                check_join(ctx, ctx->counters.as<uint32_t>());
+                for (sylph_fasta* f : {a, b}) if (f) f->joined_ready = true;
+            }
+        },
+        [&](const uint32_t* off, uint64_t n_rec_batch, uint64_t n_bases) {   // (b) the gather, cut by output bytes
+            if (!n_bases) return;
             ScopedKernelTimer t(ctx, "fasta_batch");
-            hipLaunchKernelGGL(fa_batch_kernel, dim3((uint32_t)((n_bases + fasta_reads_plan::TILE_BYTES - 1) / fasta_reads_plan::TILE_BYTES)), dim3(FQ_TPB), 0,
-                               ctx->stream, a->joined.as<uint8_t>(), ra, b ? b->joined.as<uint8_t>() : nullptr, rb, first, n_rec_batch, b_off.as<uint32_t>(),
-                               n_bases, sk->fq_bases.as<uint8_t>());
-        }
-        SY_HIP(hipMemsetAsync(sk->fq_bases.as<uint8_t>() + n_bases, 0, 64, ctx->stream));
-        SY_HIP(hipGetLastError());
-    });
-    if (rc != SYLPH_OK || !n_rec_batch) return rc;
-    return sylph_sketch_push_enc(sk, sk->fq_bases.as<uint8_t>(), sk->fq_off.as<uint64_t>(), n_rec_batch, n_bases, SYLPH_MEM_DEVICE, SYLPH_ENC_ASCII);
+            hipLaunchKernelGGL(fa_batch_kernel, dim3((uint32_t)((n_bases + rp::TILE_BYTES - 1) / rp::TILE_BYTES)), dim3(FQ_TPB), 0, ctx->stream,
+                               a->joined.as<uint8_t>(), ra, b ? b->joined.as<uint8_t>() : nullptr, rb, first, n_rec_batch, off, n_bases,
+                               sk->fq_bases.as<uint8_t>());
+        });
 }
 
 int sylph_fasta_counts(const sylph_fasta* f, uint64_t* n_records, uint64_t* n_bases, uint64_t* id_bytes) {

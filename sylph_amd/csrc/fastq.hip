@@ -22,6 +22,7 @@
 #include "device_common.h"
 #include "sketch_session.h"
 #include "text_lines.h"
+#include "read_text.h"
 
 struct sylph_fastq {
     sylph_ctx* ctx = nullptr;
@@ -90,24 +91,6 @@ __global__ __launch_bounds__(256) void fq_records_kernel(const uint8_t* __restri
     if (threadIdx.x == 0) atomicAdd(&w->n_bases, s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
 }
 
-// lengths of a batch's records in batch order (pairs interleaved), one sentinel 0 behind them for the scan; their 64-bit sum in *total
-// (the scan is a 32-bit one: the caller checks the sum before it trusts the offsets)
-__global__ void fq_batch_lens_kernel(const uint32_t* __restrict__ la, const uint32_t* __restrict__ lb, uint64_t first, uint64_t n_items,
-                                     uint32_t* __restrict__ out, unsigned long long* __restrict__ total) {
-    const uint64_t n = lb ? 2 * n_items : n_items;
-    unsigned long long sum = 0;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= n; j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t l = j == n ? 0u : (lb ? ((j & 1) ? lb[first + (j >> 1)] : la[first + (j >> 1)]) : la[first + j]);
-        out[j] = l;
-        sum += l;
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
-}
-__global__ void fq_widen_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ out) {
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) out[j] = in[j];
-}
 // one wavefront per record: its bytes from the text to their place in the batch
 __global__ __launch_bounds__(256) void fq_gather_kernel(const uint8_t* __restrict__ ta, const uint64_t* __restrict__ sa, const uint8_t* __restrict__ tb,
                                                         const uint64_t* __restrict__ sb, uint64_t first, uint64_t n_rec_batch,
@@ -121,99 +104,35 @@ __global__ __launch_bounds__(256) void fq_gather_kernel(const uint8_t* __restric
     }
 }
 
-struct FormatError { std::string msg; };
-
 // rec_start[r] = line_start[4 r], r = 0 .. n_rec: where every record begins, and where the text behind the last one does
 __global__ void fq_record_starts_kernel(const uint64_t* __restrict__ line_start, uint64_t n_rec, uint64_t* __restrict__ rec_start) {
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_rec; r += (uint64_t)gridDim.x * blockDim.x) rec_start[r] = line_start[4 * r];
 }
 
-uint32_t grid1(uint64_t n, uint32_t tpb = 256, uint32_t cap = 1u << 20) { return (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, (n + tpb - 1) / tpb)); }
+// how a batch's record j reads its length (read_text.h batch_lens_kernel): from the index of its mate (pairs interleaved: mate 1, mate 2)
+struct FqLen {
+    const uint32_t *la, *lb;
+    __device__ uint32_t operator()(uint64_t first, uint64_t j) const { return lb ? ((j & 1) ? lb[first + (j >> 1)] : la[first + (j >> 1)]) : la[first + j]; }
+};
 
-void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem, bool want_starts = false) {
-    sylph_ctx* ctx = f->ctx;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard dg(ctx->device);
-    if (mem == SYLPH_MEM_DEVICE) {
-        f->text = (const uint8_t*)text;
-    } else {
-        f->text_own.reserve(n_bytes + 64);
-        if (mem == SYLPH_MEM_HOST_PINNED) SY_HIP(hipMemcpyAsync(f->text_own.p, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-        else ctx->h2d(f->text_own.p, text, n_bytes);
-        f->text = f->text_own.as<uint8_t>();
-    }
-    const uint32_t bias = (uint32_t)((uintptr_t)f->text & 15);
-    const uint8_t* al = f->text - bias;
-    const uint64_t n_tiles = (n_bytes + bias + FQ_TILE - 1) / FQ_TILE;
-    SY_REQUIRE(n_tiles < (1ull << 31), "sylph_fastq_index: text too large for one index (%llu bytes)", (unsigned long long)n_bytes);
-    DevBuf& b_words = ctx->scratch[0];
-    DevBuf& b_cnt = ctx->scratch[1];
-    DevBuf& b_base = ctx->scratch[2];
-    DevBuf& b_lines = ctx->scratch[3];
-    b_words.reserve(sizeof(FqWords));
-    b_cnt.reserve((n_tiles + 1) * 4);
-    b_base.reserve((n_tiles + 1) * 4);
-    FqWords* d_w = b_words.as<FqWords>();
-    hipLaunchKernelGGL(fq_trim_kernel, dim3(1), dim3(1), 0, ctx->stream, f->text, n_bytes, d_w);
-    SY_HIP(hipMemsetAsync(b_cnt.as<uint32_t>() + n_tiles, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(fq_count_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_cnt.as<uint32_t>());
-    SY_HIP(hipGetLastError());
-    exclusive_sum_u32(ctx, b_cnt.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles + 1);
-    FqWords hw;
-    uint32_t n_nl = 0;
-    ctx->read_back(&n_nl, b_base.as<uint32_t>() + n_tiles, 4);     // (synchronises the stream)
-    ctx->read_back(&hw, d_w, sizeof(hw));
-    if (hw.flags & 1ull) throw FormatError{"more than 64 KiB of blank space behind the last line"};
-    f->n = hw.n_eff;
-    if (f->n == 0) throw FormatError{"no text"};
-    if (hw.n_nl != (unsigned long long)n_nl) throw FormatError{std::to_string(hw.n_nl) + " lines: at most 2^32 - 1 per index"};
-    const uint64_t n_lines = (uint64_t)n_nl + 1;                   // the last line is unterminated (its newline was trimmed)
-    if (n_lines % 4) throw FormatError{"the number of lines (" + std::to_string(n_lines) + ") is not a multiple of four"};
-    f->n_rec = n_lines / 4;
-    b_lines.reserve((n_lines + 1) * 8);
-    f->seq_start.reserve(f->n_rec * 8);
-    f->seq_len.reserve(f->n_rec * 4 + 4);
-    hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_base.as<uint32_t>(), n_lines,
-                       b_lines.as<uint64_t>());
-    hipLaunchKernelGGL(fq_records_kernel, dim3(grid1(f->n_rec, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, b_lines.as<uint64_t>(), f->n_rec,
-                       f->seq_start.as<uint64_t>(), f->seq_len.as<uint32_t>(), d_w);
-    SY_HIP(hipGetLastError());
-    ctx->read_back(&hw, d_w, sizeof(hw));
-    if (hw.bad_rec != ~0ull) throw FormatError{"record " + std::to_string(hw.bad_rec) + " is not a four-line record ('@' line, sequence, '+' line, quality of the sequence's length)"};
-    f->n_bases = hw.n_bases;
-    if (want_starts) {                                                    // (a window's index: line_start[4 n_rec] = n + 1, the virtual newline's)
-        f->rec_start.reserve((f->n_rec + 1) * 8);
-        hipLaunchKernelGGL(fq_record_starts_kernel, dim3(grid1(f->n_rec + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_lines.as<uint64_t>(), f->n_rec,
-                           f->rec_start.as<uint64_t>());
-        SY_HIP(hipGetLastError());
-        f->has_starts = true;
-    }
-}
-
-// The COMPLETE records of a window of a text that goes on behind it (sylph_fastq_index_window, final == 0): nothing is trimmed, a line
-// is one that ends in a newline inside the text, the records are the whole groups of four such lines, and *consumed is where the first
-// line behind them starts.  The kernels are fastq_index_impl's: with n_lines = 4 * n_rec + 1 the line kernel writes the starts of lines
+// What there is to index.  Whole: a whole text (sylph_fastq_index).  WholeWithStarts: the same, and where every record starts
+// (sylph_fastq_index_window, final != 0).  Window: the COMPLETE records of a window of a text that goes on behind it (final == 0):
+// nothing is trimmed, a line is one that ends in a newline inside the text, the records are the whole groups of four such lines, and
+// *consumed is where the first line behind them starts.  With n_lines = 4 * n_rec + 1 the line kernel writes the starts of lines
 // 0 .. 4 * n_rec — the last of them is `consumed`, and the end of the last record's quality line + 1, as between two records of a
 // whole text.
-void fastq_window_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem, uint64_t* consumed) {
+enum class FqText { Whole, WholeWithStarts, Window };
+const char* entry_of(FqText what) { return what == FqText::Window ? "sylph_fastq_index_window" : "sylph_fastq_index"; }
+
+void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int mem, FqText what, uint64_t* consumed = nullptr) {
     sylph_ctx* ctx = f->ctx;
+    const bool window = what == FqText::Window;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
-    *consumed = 0;
-    f->n = 0;
-    if (!n_bytes) return;
-    if (mem == SYLPH_MEM_DEVICE) {
-        f->text = (const uint8_t*)text;
-    } else {
-        f->text_own.reserve(n_bytes + 64);
-        if (mem == SYLPH_MEM_HOST_PINNED) SY_HIP(hipMemcpyAsync(f->text_own.p, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-        else ctx->h2d(f->text_own.p, text, n_bytes);
-        f->text = f->text_own.as<uint8_t>();
-    }
-    const uint32_t bias = (uint32_t)((uintptr_t)f->text & 15);
-    const uint8_t* al = f->text - bias;
-    const uint64_t n_tiles = (n_bytes + bias + FQ_TILE - 1) / FQ_TILE;
-    SY_REQUIRE(n_tiles < (1ull << 31), "sylph_fastq_index_window: text too large for one index (%llu bytes)", (unsigned long long)n_bytes);
+    if (window && !n_bytes) return;                                        // no text yet: no records, nothing consumed
+    const DeviceText t = take_text(ctx, f->text_own, &f->text, text, n_bytes, mem);
+    const uint64_t n_tiles = t.n_tiles;
+    SY_REQUIRE(n_tiles < (1ull << 31), "%s: text too large for one index (%llu bytes)", entry_of(what), (unsigned long long)n_bytes);
     DevBuf& b_words = ctx->scratch[0];
     DevBuf& b_cnt = ctx->scratch[1];
     DevBuf& b_base = ctx->scratch[2];
@@ -223,38 +142,48 @@ void fastq_window_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int m
     b_base.reserve((n_tiles + 1) * 4);
     FqWords* d_w = b_words.as<FqWords>();
     FqWords hw{n_bytes, ~0ull, 0, 0, 0};
-    ctx->h2d(d_w, &hw, sizeof(hw));
+    if (window) ctx->h2d(d_w, &hw, sizeof(hw));                            // a window is not trimmed
+    else hipLaunchKernelGGL(fq_trim_kernel, dim3(1), dim3(1), 0, ctx->stream, f->text, n_bytes, d_w);
     SY_HIP(hipMemsetAsync(b_cnt.as<uint32_t>() + n_tiles, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(fq_count_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(fq_count_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, t.al, t.bias, d_w, b_cnt.as<uint32_t>());
     SY_HIP(hipGetLastError());
     exclusive_sum_u32(ctx, b_cnt.as<uint32_t>(), b_base.as<uint32_t>(), n_tiles + 1);
     uint32_t n_nl = 0;
-    ctx->read_back(&n_nl, b_base.as<uint32_t>() + n_tiles, 4);
+    ctx->read_back(&n_nl, b_base.as<uint32_t>() + n_tiles, 4);     // (synchronises the stream)
     ctx->read_back(&hw, d_w, sizeof(hw));
+    if (hw.flags & 1ull) throw FormatError{"more than 64 KiB of blank space behind the last line"};
+    if (!window && hw.n_eff == 0) throw FormatError{"no text"};
     if (hw.n_nl != (unsigned long long)n_nl) throw FormatError{std::to_string(hw.n_nl) + " lines: at most 2^32 - 1 per index"};
-    f->n_rec = n_nl / 4;
-    if (!f->n_rec) return;
-    const uint64_t n_lines = 4 * f->n_rec + 1;
+    // the last line is unterminated: its newline was trimmed — or, of a window, it is not a whole line yet, nor are the up to three before it a record
+    const uint64_t n_lines = window ? 4 * (uint64_t)(n_nl / 4) + 1 : (uint64_t)n_nl + 1;
+    if (!window && n_lines % 4) throw FormatError{"the number of lines (" + std::to_string(n_lines) + ") is not a multiple of four"};
+    f->n_rec = n_lines / 4;
+    if (window && !f->n_rec) return;
+    f->n = hw.n_eff;
     b_lines.reserve((n_lines + 1) * 8);
     f->seq_start.reserve(f->n_rec * 8);
     f->seq_len.reserve(f->n_rec * 4 + 4);
-    hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, al, bias, d_w, b_base.as<uint32_t>(), n_lines,
+    hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, t.al, t.bias, d_w, b_base.as<uint32_t>(), n_lines,
                        b_lines.as<uint64_t>());
     hipLaunchKernelGGL(fq_records_kernel, dim3(grid1(f->n_rec, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, b_lines.as<uint64_t>(), f->n_rec,
                        f->seq_start.as<uint64_t>(), f->seq_len.as<uint32_t>(), d_w);
     SY_HIP(hipGetLastError());
     ctx->read_back(&hw, d_w, sizeof(hw));
     if (hw.bad_rec != ~0ull) throw FormatError{"record " + std::to_string(hw.bad_rec) + " is not a four-line record ('@' line, sequence, '+' line, quality of the sequence's length)"};
-    unsigned long long end = 0;
-    ctx->read_back(&end, b_lines.as<uint64_t>() + 4 * f->n_rec, 8);
-    f->rec_start.reserve((f->n_rec + 1) * 8);
-    hipLaunchKernelGGL(fq_record_starts_kernel, dim3(grid1(f->n_rec + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_lines.as<uint64_t>(), f->n_rec,
-                       f->rec_start.as<uint64_t>());
-    SY_HIP(hipGetLastError());
-    f->has_starts = true;
     f->n_bases = hw.n_bases;
-    f->n = end;
-    *consumed = end;
+    if (window) {                                                          // the text ends, for this index, behind its last record
+        unsigned long long end = 0;
+        ctx->read_back(&end, b_lines.as<uint64_t>() + 4 * f->n_rec, 8);
+        f->n = end;
+    }
+    if (consumed) *consumed = window ? f->n : n_bytes;
+    if (what != FqText::Whole) {                                           // (a whole text's line_start[4 n_rec] = n + 1, the virtual newline's)
+        f->rec_start.reserve((f->n_rec + 1) * 8);
+        hipLaunchKernelGGL(fq_record_starts_kernel, dim3(grid1(f->n_rec + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_lines.as<uint64_t>(), f->n_rec,
+                           f->rec_start.as<uint64_t>());
+        SY_HIP(hipGetLastError());
+        f->has_starts = true;
+    }
 }
 
 }  // namespace
@@ -266,50 +195,22 @@ extern "C" {
 
 int sylph_fastq_index(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, sylph_fastq** out) {
     if (!ctx || !out || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    if (!mem_kind_ok(mem)) return SYLPH_ERR_INVALID;
     *out = nullptr;
     if (n_bytes == 0) { set_error("sylph_fastq_index: no text"); return SYLPH_ERR_FORMAT; }
-    ctx->refs.fetch_add(1);
-    sylph_fastq* f = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        f = new sylph_fastq(ctx);
-        try { fastq_index_impl(f, text, n_bytes, mem); }
-        catch (const FormatError& e) { set_error("sylph_fastq_index: not plain four-line FASTQ: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); delete f; }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = f;
-    return SYLPH_OK;
+    return make_index(ctx, "sylph_fastq_index", "not plain four-line FASTQ", out, [&](sylph_fastq* f) { fastq_index_impl(f, text, n_bytes, mem, FqText::Whole); });
 }
 
 int sylph_fastq_index_window(sylph_ctx* ctx, const void* text, uint64_t n_bytes, int mem, int final, sylph_fastq** out, uint64_t* consumed) {
     if (!ctx || !out || !consumed || (!text && n_bytes)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_DEVICE && mem != SYLPH_MEM_HOST_PINNED) { set_error("bad mem kind %d", mem); return SYLPH_ERR_INVALID; }
+    if (!mem_kind_ok(mem)) return SYLPH_ERR_INVALID;
     *out = nullptr;
     *consumed = 0;
     if (final && n_bytes == 0) { set_error("sylph_fastq_index: no text"); return SYLPH_ERR_FORMAT; }
-    ctx->refs.fetch_add(1);
-    sylph_fastq* f = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        f = new sylph_fastq(ctx);
-        try {
-            if (final) { fastq_index_impl(f, text, n_bytes, mem, true); *consumed = n_bytes; }      // sylph_fastq_index's code, + the records' starts
-            else fastq_window_impl(f, text, n_bytes, mem, consumed);
-        } catch (const FormatError& e) { set_error("%s: not plain four-line FASTQ: %s", final ? "sylph_fastq_index" : "sylph_fastq_index_window", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        if (f) { std::lock_guard<std::mutex> lock(ctx->mu); delete f; }
-        ctx_unref(ctx);
-        *consumed = 0;
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    *out = f;
-    return SYLPH_OK;
+    const FqText what = final ? FqText::WholeWithStarts : FqText::Window;    // final: sylph_fastq_index's code, + the records' starts
+    const int rc = make_index(ctx, entry_of(what), "not plain four-line FASTQ", out, [&](sylph_fastq* f) { fastq_index_impl(f, text, n_bytes, mem, what, consumed); });
+    if (rc != SYLPH_OK) *consumed = 0;
+    return rc;
 }
 
 int sylph_fastq_record_offset(sylph_fastq* f, uint64_t record, uint64_t* offset) {
@@ -359,56 +260,13 @@ void sylph_fastq_destroy(sylph_fastq* f) {
 
 int sylph_sketch_push_fastq(sylph_sketch* sk, sylph_fastq* a, sylph_fastq* b, uint64_t first, uint64_t n_items) {
     if (!sk || !a) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    uint64_t n_rec_batch = 0, n_bases = 0;
-    const int rc = guarded([&] {
-        sylph_ctx* ctx = sk->ctx;
-        SY_REQUIRE(a->ctx == ctx && (!b || b->ctx == ctx), "sylph_sketch_push_fastq: the index lives on another context than the session");
-        SY_REQUIRE((b != nullptr) == (sk->paired != 0), "sylph_sketch_push_fastq: a paired session takes two texts, a single-end session one");
-        SY_REQUIRE(first <= a->n_rec && n_items <= a->n_rec - first && (!b || (first <= b->n_rec && n_items <= b->n_rec - first)),
-                   "sylph_sketch_push_fastq: records [%llu, +%llu) are not all there", (unsigned long long)first, (unsigned long long)n_items);
-        if (!n_items) return;
-        n_rec_batch = b ? 2 * n_items : n_items;
-        SY_REQUIRE(n_rec_batch < (1ull << 31), "sylph_sketch_push_fastq: at most 2^31 - 1 records per push");
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        // a deferred batch of this session reads sk->fq_bases until its verdict is in: settle it before the buffer is written again
-        resolve_deferred_slots(sk);
-        DevBuf& b_len = ctx->scratch[0];
-        DevBuf& b_off = ctx->scratch[1];
-        DevBuf& b_tot = ctx->scratch[2];
-        b_len.reserve((n_rec_batch + 1) * 4);
-        b_off.reserve((n_rec_batch + 1) * 4);
-        b_tot.reserve(8);
-        SY_HIP(hipMemsetAsync(b_tot.p, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(fq_batch_lens_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, a->seq_len.as<uint32_t>(),
-                           b ? b->seq_len.as<uint32_t>() : nullptr, first, n_items, b_len.as<uint32_t>(), b_tot.as<unsigned long long>());
-        SY_HIP(hipGetLastError());
-        exclusive_sum_u32(ctx, b_len.as<uint32_t>(), b_off.as<uint32_t>(), n_rec_batch + 1);
-        unsigned long long total = 0;
-        ctx->read_back(&total, b_tot.p, 8);
-        SY_REQUIRE(total < (1ull << 32) - 64, "sylph_sketch_push_fastq: %llu bases in one push (at most 2^32 - 65: push fewer records at a time)", total);
-        n_bases = total;
-        // no room for the gathered batch and its seeding?  Say so BEFORE anything of the session is touched (round 6): the caller
-        // pushes fewer records at a time, or takes its host feed, which works through a sample in 256 Mbp batches
-        if (n_bases + 64 > sk->fq_bases.cap) {
-            size_t free_b = 0, total_b = 0;
-            size_t pooled = 0;                                  // blocks the context's pool holds and hands out again
-            for (const auto& blk : ctx->pool_free) pooled += blk.first;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + pooled < n_bases + n_bases / 2 + (256u << 20))
-                throw HipError{hipErrorOutOfMemory, "sylph_sketch_push_fastq: no room for the batch", __FILE__, __LINE__};
-        }
-        sk->fq_bases.reserve(n_bases + 64);
-        sk->fq_off.reserve((n_rec_batch + 1) * 8);
-        hipLaunchKernelGGL(fq_widen_kernel, dim3(grid1(n_rec_batch + 1, 256, 4096)), dim3(256), 0, ctx->stream, b_off.as<uint32_t>(), n_rec_batch + 1,
-                           sk->fq_off.as<uint64_t>());
-        hipLaunchKernelGGL(fq_gather_kernel, dim3(grid1(n_rec_batch, 4, 1u << 16)), dim3(256), 0, ctx->stream, a->text, a->seq_start.as<uint64_t>(),
-                           b ? b->text : nullptr, b ? b->seq_start.as<uint64_t>() : nullptr, first, n_rec_batch, b_off.as<uint32_t>(),
-                           sk->fq_bases.as<uint8_t>());
-        SY_HIP(hipMemsetAsync(sk->fq_bases.as<uint8_t>() + n_bases, 0, 64, ctx->stream));
-        SY_HIP(hipGetLastError());
-    });
-    if (rc != SYLPH_OK || !n_rec_batch) return rc;
-    return sylph_sketch_push_enc(sk, sk->fq_bases.as<uint8_t>(), sk->fq_off.as<uint64_t>(), n_rec_batch, n_bases, SYLPH_MEM_DEVICE, SYLPH_ENC_ASCII);
+    return push_read_text(
+        "sylph_sketch_push_fastq", sk, a, b, first, n_items, FqLen{a->seq_len.as<uint32_t>(), b ? b->seq_len.as<uint32_t>() : nullptr},
+        [] { return uint64_t(0); }, [] {},
+        [&](const uint32_t* off, uint64_t n_rec_batch, uint64_t) {
+            hipLaunchKernelGGL(fq_gather_kernel, dim3(grid1(n_rec_batch, 4, 1u << 16)), dim3(256), 0, sk->ctx->stream, a->text, a->seq_start.as<uint64_t>(),
+                               b ? b->text : nullptr, b ? b->seq_start.as<uint64_t>() : nullptr, first, n_rec_batch, off, sk->fq_bases.as<uint8_t>());
+        });
 }
 
 }  // extern "C"

@@ -209,6 +209,8 @@ struct ReadIndex {
     ~ReadIndex() { sylph_fastq_destroy(q); sylph_fasta_destroy(a); }
     bool made() const { return q || a; }
     const char* index_name() const { return fasta ? "sylph_fasta_index" : "sylph_fastq_index"; }
+    const char* index_window_name() const { return fasta ? "sylph_fasta_index_window" : "sylph_fastq_index_window"; }
+    const char* push_name() const { return fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq"; }
     int index(sylph_ctx* ctx, const void* dev, uint64_t bytes) {
         return fasta ? sylph_fasta_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &a) : sylph_fastq_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &q);
     }
@@ -270,6 +272,8 @@ bool fasta_reads_on_device() {
     static const bool on = [] { const char* e = getenv("SYLPH_HIP_FASTA_READS_DEVICE"); return !(e && *e) || atoi(e) != 0; }();
     return on;
 }
+// mates of one kind: both FASTA or neither (h: the first byte of every mate's text)
+bool same_kind(const std::vector<uint8_t>& h) { return h.size() < 2 || ((h[0] == '>') == (h[1] == '>')); }
 // a text of this many bytes or more is not indexed in one piece by sylph_fasta_index (include/sylph_hip.h)
 constexpr uint64_t FASTA_INDEX_MAX_TEXT = (1ull << 32) - 4096;
 // the first byte of a decoded file's text, which lies on the device
@@ -364,7 +368,7 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
             uint64_t consumed = 0;
             fq[i].fasta = kind[i] > 0;
             rc = fq[i].index_window(ctx, dev[i], bytes[i], finished[i] ? 1 : 0, &consumed);
-            if (rc != SYLPH_OK) return declined(rc, fq[i].fasta ? "sylph_fasta_index_window" : "sylph_fastq_index_window");
+            if (rc != SYLPH_OK) return declined(rc, fq[i].index_window_name());
             fq[i].counts(n_rec[i], bases[i]);
         }
         const uint64_t n = F == 2 ? std::min(n_rec[0], n_rec[1]) : n_rec[0];
@@ -373,8 +377,8 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
             la.continue_mean(n, mean, counter);                // sketch.rs:941-943, :825-826
             for (const auto& p : cut_pushes(F == 2 ? &fq[1] : nullptr, la, n, bases[0] + (F == 2 ? bases[1] : 0))) {
                 rc = ReadIndex::push(sk, fq[0], F == 2 ? &fq[1] : nullptr, p.first, p.second);
-                if (rc == SYLPH_ERR_NOMEM) return declined(rc, fq[0].fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
-                hip_check(rc, fq[0].fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
+                if (rc == SYLPH_ERR_NOMEM) return declined(rc, fq[0].push_name());
+                hip_check(rc, fq[0].push_name());
             }
             pairs += n;
         }
@@ -407,132 +411,127 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
 }
 }  // namespace
 
-bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const SampleFiles& sample, Container decode,
-                            double& mean_read_length, const IndexedInput* text = nullptr) {
-    if (!device_feed_enabled()) return false;
-    const std::string& f1 = sample.first;
-    const std::string* f2 = sample.second ? &*sample.second : nullptr;
-    const bool gz = !text && decode == Container::Gzip, bz = !text && decode == Container::Bzip2;
-    std::vector<std::string> files{f1};
-    if (f2) files.push_back(*f2);
-    std::vector<uint8_t> heads;                      // the first byte of every mate's TEXT: '@' FASTQ, '>' FASTA
-    if (!gz && !bz && !text) for (const auto& f : files) heads.push_back(first_byte_of(f));
-    // a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that — and so does plain FASTA, whose host
-    // road is the sequential reader
-    const bool plain_fasta = !heads.empty() && heads[0] == '>' && fasta_reads_on_device();
-    if (!gz && !bz && !plain_fasta && !e.ready()) return false;
-    const bool trace = FeedLaps::on();
-    FeedLaps laps;
-    sylph_ctx* ctx = e.context();
+// The texts of a sample whose compressed files the device decodes, both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files:
+// one scan, one decode launch, one chain — the mates share a block's latency).  gzip: the whole-file road, or — when asked, for what
+// that road declines for size or for room, and for a FASTA text too long for one index — the stream (sketch_gzip_streamed).
+enum class Decoded { OnDevice, Streamed, Declined };      // the texts lie on the device / the sample is sketched already / the host feed's
+struct RouteTexts {
+    InflatedText owner;                              // of decoded texts (destroyed behind the indexes that borrow them: declared before them)
     std::vector<TextUploader::Text> texts;
-    auto same_kind = [](const std::vector<uint8_t>& h) { return h.size() < 2 || ((h[0] == '>') == (h[1] == '>')); };
-    // FASTA reads that stay on the host reader, mates of different kinds: declined before anything travels
-    auto taken = [&] {
-        if (!same_kind(heads)) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: one mate is FASTA, the other is not\n", files[0].c_str());
-            return false;
-        }
-        if (heads[0] == '>' && !fasta_reads_on_device()) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: FASTA reads stay on the host reader\n", files[0].c_str());
-            return false;
-        }
-        return true;
-    };
-    InflatedText inflated;                           // (destroyed behind the indexes that borrow its text: declared before them)
-    if (gz || bz) {
-        // both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files): one scan, one decode launch, one chain — the mates share a block's latency
-        std::vector<std::unique_ptr<MappedFile>> maps;
-        std::vector<const void*> ptrs;
-        std::vector<uint64_t> lens;
-        for (const auto& f : files) {
-            maps.emplace_back(new MappedFile(f));
-            if (!maps.back()->data) return false;
-            ptrs.push_back(maps.back()->data);
-            lens.push_back(maps.back()->size);
-        }
-        // gzip: the whole-file road, or — for what it declines for size or for room, or when asked — the stream (sketch_gzip_streamed)
-        bool streamed = false;
-        if (gz) {
-            uint64_t gz_bytes = 0;
-            for (const uint64_t l : lens) gz_bytes += l;
-            const StreamMode mode = stream_mode();
-            const bool too_large = gz_bytes >= inflate_whole_max();
-            streamed = mode == StreamMode::Always || (mode == StreamMode::Auto && too_large);
-            if (!streamed && too_large) {
-                if (trace) fprintf(stderr, "[sylph_hip feed] device inflate declined %s: %llu gzip bytes, and the stream is off\n", files[0].c_str(), (unsigned long long)gz_bytes);
-                return false;
-            }
-        }
-        int rc = SYLPH_OK;
-        if (!streamed) {
-            rc = gz ? sylph_inflate_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h)
-                    : sylph_bunzip2_files(ctx, ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &inflated.h);
-            if (gz && rc == SYLPH_ERR_NOMEM && stream_mode() == StreamMode::Auto) {
-                if (trace) fprintf(stderr, "[sylph_hip feed] device inflate has no room for %s in one piece (%s): the stream takes it\n", files[0].c_str(), sylph_last_error());
-                streamed = true;
-            }
-        }
-        if (streamed) {
-            if (!sketch_gzip_streamed(e, open_session, ptrs, lens, files[0].c_str(), mean_read_length)) return false;
-            laps.lap("device route: gzip streamed through the device inflate");
-            return true;
-        }
-        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", files[0].c_str(), sylph_last_error());
-            return false;
-        }
-        hip_check(rc, gz ? "sylph_inflate_files" : "sylph_bunzip2_files");
+    std::vector<uint8_t> heads;                      // the first byte of every mate's TEXT: '@' FASTQ, '>' FASTA
+};
+Decoded decode_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::vector<std::string>& files, bool gz, FeedLaps& laps,
+                         RouteTexts& out, double& mean_read_length) {
+    const bool trace = FeedLaps::on();
+    const char* name = files[0].c_str();
+    std::vector<std::unique_ptr<MappedFile>> maps;
+    std::vector<const void*> ptrs;
+    std::vector<uint64_t> lens;
+    uint64_t packed_bytes = 0;
+    for (const auto& f : files) {
+        maps.emplace_back(new MappedFile(f));
+        if (!maps.back()->data) return Decoded::Declined;
+        ptrs.push_back(maps.back()->data);
+        lens.push_back(maps.back()->size);
+        packed_bytes += maps.back()->size;
+    }
+    const bool may_stream = gz && stream_mode() == StreamMode::Auto;
+    const bool too_large = gz && packed_bytes >= inflate_whole_max();
+    bool streamed = gz && (stream_mode() == StreamMode::Always || (may_stream && too_large));
+    if (!streamed && too_large) {
+        if (trace) fprintf(stderr, "[sylph_hip feed] device inflate declined %s: %llu gzip bytes, and the stream is off\n", name, (unsigned long long)packed_bytes);
+        return Decoded::Declined;
+    }
+    if (!streamed) {
+        const int rc = gz ? sylph_inflate_files(e.context(), ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &out.owner.h)
+                          : sylph_bunzip2_files(e.context(), ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &out.owner.h);
+        if (rc == SYLPH_ERR_NOMEM && may_stream) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device inflate has no room for %s in one piece (%s): the stream takes it\n", name, sylph_last_error());
+            streamed = true;
+        } else if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", name, sylph_last_error());
+            return Decoded::Declined;
+        } else hip_check(rc, gz ? "sylph_inflate_files" : "sylph_bunzip2_files");
+    }
+    if (!streamed) {
+        bool fasta_too_long = false;
         for (uint32_t i = 0; i < ptrs.size(); i++) {
             const void* dev = nullptr;
             uint64_t bytes = 0;
-            hip_check(sylph_inflated_file(inflated.h, i, &dev, &bytes), "sylph_inflated_file");
-            if (!bytes) return false;
-            texts.push_back(TextUploader::Text{(const uint8_t*)dev, bytes});
-            heads.push_back(first_byte_of(inflated.h, dev));
+            hip_check(sylph_inflated_file(out.owner.h, i, &dev, &bytes), "sylph_inflated_file");
+            if (!bytes) return Decoded::Declined;
+            out.texts.push_back(TextUploader::Text{(const uint8_t*)dev, bytes});
+            out.heads.push_back(first_byte_of(out.owner.h, dev));
+            fasta_too_long = fasta_too_long || (out.heads[i] == '>' && bytes >= FASTA_INDEX_MAX_TEXT);
         }
         laps.lap(gz ? "device route: gzip inflated on the device" : "device route: bzip2 decoded on the device");
         // a gzip FASTA text too long for one FASTA index: the stream's windows are smaller
-        bool fasta_too_long = false;
-        for (size_t i = 0; i < texts.size(); i++) fasta_too_long = fasta_too_long || (heads[i] == '>' && texts[i].bytes >= FASTA_INDEX_MAX_TEXT);
-        if (gz && fasta_too_long && same_kind(heads) && stream_mode() == StreamMode::Auto && fasta_reads_on_device()) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device route: a FASTA text of %s is too long for one index: the stream takes it\n", files[0].c_str());
-            texts.clear();
-            sylph_inflated_destroy(inflated.h);
-            inflated.h = nullptr;
-            if (!sketch_gzip_streamed(e, open_session, ptrs, lens, files[0].c_str(), mean_read_length)) return false;
-            laps.lap("device route: gzip streamed through the device inflate");
-            return true;
+        if (may_stream && fasta_too_long && same_kind(out.heads) && fasta_reads_on_device()) {
+            if (trace) fprintf(stderr, "[sylph_hip feed] device route: a FASTA text of %s is too long for one index: the stream takes it\n", name);
+            out.texts.clear();
+            sylph_inflated_destroy(out.owner.h);
+            out.owner.h = nullptr;
+            streamed = true;
         }
-    } else if (text) {
-        // The first text an engine sends pays for the route's device buffers (~40-90 ms of allocations, once); skipping the host's index
-        // and gather of an inflated copy buys that back only for a sample of some size: 0.45 against 0.53 s for a 1 Gbp gzip pair, 0.34
-        // against 0.30 s for its first mate alone (profiles/r05_feed_device_route.txt)
-        const uint64_t bytes = text->a->size + (f2 ? text->b->size : 0);
-        if (!e.text.warm() && bytes < (1500ull << 20)) return false;
-        std::vector<TextUploader::Mem> mem{{text->a->data, text->a->size}};
+    }
+    if (!streamed) return Decoded::OnDevice;
+    if (!sketch_gzip_streamed(e, open_session, ptrs, lens, name, mean_read_length)) return Decoded::Declined;
+    laps.lap("device route: gzip streamed through the device inflate");
+    return Decoded::Streamed;
+}
+
+// obtain the texts, decide the kind once, index, push
+bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const SampleFiles& sample, Container decode,
+                            double& mean_read_length, const IndexedInput* text = nullptr) {
+    if (!device_feed_enabled()) return false;
+    const std::string* f2 = sample.second ? &*sample.second : nullptr;
+    const bool decoded = !text && (decode == Container::Gzip || decode == Container::Bzip2);
+    std::vector<std::string> files{sample.first};
+    if (f2) files.push_back(*f2);
+    RouteTexts t;
+    std::vector<uint8_t>& heads = t.heads;           // of host text and of plain files here, of decoded text once it is there
+    std::vector<TextUploader::Mem> mem;
+    if (text) {
+        mem.push_back({text->a->data, text->a->size});
         if (f2) mem.push_back({text->b->data, text->b->size});
         for (const auto& m : mem) heads.push_back(m.p && m.bytes ? m.p[0] : 0);
-        if (!taken()) return false;
-        if (!e.text.send(ctx, mem, parse_threads(), texts)) return false;
-    } else {
-        if (!taken()) return false;
-        if (!e.text.send(ctx, files, parse_threads(), texts)) return false;
+    } else if (!decoded) for (const auto& f : files) heads.push_back(first_byte_of(f));
+    // a gzip or bzip2 sample waits for the engine: nothing on the host side is faster than that — and so does plain FASTA, whose host
+    // road is the sequential reader
+    const bool plain_fasta = !text && !decoded && heads[0] == '>' && fasta_reads_on_device();
+    if (!decoded && !plain_fasta && !e.ready()) return false;
+    const bool trace = FeedLaps::on();
+    FeedLaps laps;
+    sylph_ctx* ctx = e.context();
+    // The first text an engine sends pays for the route's device buffers (~40-90 ms of allocations, once); skipping the host's index
+    // and gather of an inflated copy buys that back only for a sample of some size: 0.45 against 0.53 s for a 1 Gbp gzip pair, 0.34
+    // against 0.30 s for its first mate alone (profiles/r05_feed_device_route.txt)
+    if (text && !e.text.warm() && text->a->size + (f2 ? text->b->size : 0) < (1500ull << 20)) return false;
+    if (decoded) {
+        const Decoded got = decode_on_device(e, open_session, files, decode == Container::Gzip, laps, t, mean_read_length);
+        if (got != Decoded::OnDevice) return got == Decoded::Streamed;
     }
-    if (gz || bz) { if (!taken()) return false; }
-    else laps.lap("device route: text uploaded");
+    // FASTA reads that stay on the host reader, mates of different kinds: declined — for host text and plain files, before anything travels
+    auto declined = [&](const char* why) {
+        if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: %s\n", files[0].c_str(), why);
+        return false;
+    };
+    if (!same_kind(heads)) return declined("one mate is FASTA, the other is not");
     const bool fasta = heads[0] == '>';
+    if (fasta && !fasta_reads_on_device()) return declined("FASTA reads stay on the host reader");
+    if (!decoded) {
+        if (!(text ? e.text.send(ctx, mem, parse_threads(), t.texts) : e.text.send(ctx, files, parse_threads(), t.texts))) return false;
+        laps.lap("device route: text uploaded");
+    }
     ReadIndex fa, fb;
     fa.fasta = fb.fasta = fasta;
-    auto index = [&](const TextUploader::Text& t, ReadIndex& out) {
-        const int rc = out.index(ctx, t.dev, t.bytes);
-        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {               // not for this route / no room for it: the host feed
-            if (trace && fasta) fprintf(stderr, "[sylph_hip feed] device route declined %s: %s\n", files[0].c_str(), sylph_last_error());
-            return false;
-        }
+    auto index = [&](const TextUploader::Text& x, ReadIndex& out) {
+        const int rc = out.index(ctx, x.dev, x.bytes);
+        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) return fasta ? declined(sylph_last_error()) : false;   // not for this route / no room for it: the host feed
         hip_check(rc, out.index_name());
         return true;
     };
-    if (!index(texts[0], fa) || (f2 && !index(texts[1], fb))) return false;
+    if (!index(t.texts[0], fa) || (f2 && !index(t.texts[1], fb))) return false;
     uint64_t na = 0, nb = 0, bases_a = 0, bases_b = 0;
     fa.counts(na, bases_a);
     if (f2) fb.counts(nb, bases_b);
@@ -558,7 +557,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             tm.join();
             return false;
         }
-        hip_check(rc, fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq");
+        hip_check(rc, fa.push_name());
     }
     laps.lap("device route: pushed");
     tm.join();

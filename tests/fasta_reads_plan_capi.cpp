@@ -11,7 +11,7 @@
 namespace rp = sylph::fasta_reads_plan;
 
 namespace {
-// the batch's 32-bit offsets, as fa_batch_lens_kernel + the exclusive scan make them; false: 2^32 - 64 bases or more
+// the batch's 32-bit offsets, as batch_lens_kernel (csrc/read_text.h) + the exclusive scan make them; false: 2^32 - 64 bases or more
 bool batch_offsets(const uint64_t* ro_a, const uint64_t* ro_b, uint64_t first, uint64_t n_items, std::vector<uint32_t>& off) {
     const uint64_t n_rec = rp::batch_records(n_items, ro_b != nullptr);
     off.assign(n_rec + 1, 0);

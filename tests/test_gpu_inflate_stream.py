@@ -405,3 +405,66 @@ def test_fastq_index_window_final_is_fastq_index(ctx):
     f = S.FastqText(ctx, good, final=0)                                      # ... and the context is none the worse for it
     assert f.n_records == len(recs)
     f.close()
+
+
+def _window_is_python_split(ctx, t, tag):
+    want_len, want_consumed = python_split(t)
+    f = S.FastqText(ctx, t, final=0)
+    try:
+        assert f.n_records == len(want_len) and f.consumed == want_consumed, tag
+        assert f.lengths().tolist() == want_len and f.n_bases == sum(want_len), tag
+        for r in sorted({0, f.n_records // 2, f.n_records}):
+            assert f.record_offset(r) == sum(len(l) + 1 for l in t.split(b"\n")[:4 * r]), (tag, r)
+    finally:
+        f.close()
+
+
+def test_fastq_index_window_of_crlf_text(ctx):
+    text = fastq_text(np.random.default_rng(21), 300).replace(b"\n", b"\r\n")
+    starts = [0]
+    for line in text.split(b"\n")[:-1]:
+        starts.append(starts[-1] + len(line) + 1)
+    assert len(starts) == 1201 and python_split(text) == (python_split(text.replace(b"\r", b""))[0], len(text))
+    for name, cut in {"mid-record": starts[30], "mid-line": starts[29] + 5, "behind a newline": starts[32], "between '\\r' and '\\n'": starts[33] - 1}.items():
+        _window_is_python_split(ctx, text[:cut], name)
+
+
+def test_fastq_index_window_is_not_trimmed(ctx):
+    text = fastq_text(np.random.default_rng(21), 300)
+    for tail in (b"\n", b"\n\n\n"):                        # blank lines are lines: fewer than four of them are no record yet
+        f = S.FastqText(ctx, text + tail, final=0)
+        assert f.n_records == 300 and f.consumed == len(text), tail
+        assert f.record_offset(300) == len(text)
+        f.close()
+    with pytest.raises(SylphHipError) as ei:               # four of them are a complete record that is none
+        S.FastqText(ctx, text + b"\n\n\n\n", final=0)
+    assert ei.value.code == ERR_FORMAT
+    for tail in (b"\n", b"\n\n\n", b"\n\n\n\n"):           # the end of the text: trailing blank space is trimmed, as sylph_fastq_index does
+        f = S.FastqText(ctx, text + tail, final=1)
+        assert f.n_records == 300 and f.consumed == len(text + tail), tail
+        f.close()
+
+
+def test_a_window_index_pushes_like_a_whole_one(ctx):
+    from .test_gpu_parity import assert_same_sketch
+    text, mate2 = fastq_text(np.random.default_rng(21), 300), fastq_text(np.random.default_rng(22), 300)
+
+    def sketch(*fs):
+        sk = S.ReadSketcher(ctx, c=5, paired=len(fs) == 2)
+        try:
+            sk.push_fastq(*fs)
+            return sk.finish()
+        finally:
+            sk.close()
+    idx = {final: S.FastqText(ctx, text, final=final) for final in (None, 1, 0)}
+    whole2 = S.FastqText(ctx, mate2)
+    try:
+        assert [f.n_records for f in idx.values()] == [300, 300, 300] and idx[0].consumed == len(text)
+        want = sketch(idx[None])
+        assert len(want["kmers"]) > 1000
+        for final in (1, 0):
+            assert_same_sketch(sketch(idx[final]), want, final)
+        assert_same_sketch(sketch(idx[0], whole2), sketch(idx[None], whole2), "pair: mate 1 from a window")
+    finally:
+        for f in list(idx.values()) + [whole2]:
+            f.close()

@@ -13,10 +13,16 @@ baseline's by more than the two spreads together.
 binding, on the same pair's text already in device memory; GB/s against their algorithmic bytes: join 1 B read + 1 B written per base,
 gather 1 B read + 1 B written per base + 4 B of offsets per record.
 
-GPU box: python tools/fasta_reads_bench.py [--parent DIR] [--out FILE];  python tools/fasta_reads_bench.py --kernels [--out FILE]"""
+--same-route (with --parent; profiles/read_text_refactor.txt): for a change that must leave speed alone.  The baseline binary runs
+with the device routes ON too, the kinds fastq_plain, fastq_gzip and fastq_gzip_streamed (the same pair as FASTQ, bench.py's files leg
+and the stream's) join the list, and every `[sylph_hip feed]` lap of every run is kept: whole commands carry the GPU runtime's
+start-up, which varies by 0.1 s; the laps do not.
+
+GPU box: python tools/fasta_reads_bench.py [--parent DIR [--same-route]] [--out FILE];  python tools/fasta_reads_bench.py --kernels [--out FILE]"""
 import argparse
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -53,10 +59,16 @@ def make_pair(d, mbp, width, seed, kinds):
     L = 150
     n = int(mbp * 1e6) // L
     for m in (1, 2):
-        write_fasta(f"{d}/s_{m}.fa", np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n * L)], L, width)
+        seqs = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n * L)]
+        write_fasta(f"{d}/s_{m}.fa", seqs, L, width)
+        if any(k.startswith("fastq") for k in kinds):
+            from feed_bench import write_fastq
+            write_fastq(f"{d}/s_{m}.fq", seqs, L)
     jobs = []
     if "gzip" in kinds or "gzip_streamed" in kinds:
         jobs += [subprocess.Popen(["gzip", "-1", "-k", "-f", f"{d}/s_{m}.fa"]) for m in (1, 2)]
+    if "fastq_gzip" in kinds or "fastq_gzip_streamed" in kinds:
+        jobs += [subprocess.Popen(["gzip", "-1", "-k", "-f", f"{d}/s_{m}.fq"]) for m in (1, 2)]
     if "bzip2" in kinds:
         jobs += [subprocess.Popen(["bzip2", "-9", "-k", "-f", f"{d}/s_{m}.fa"]) for m in (1, 2)]
     while any(j.poll() is None for j in jobs):
@@ -67,7 +79,7 @@ def make_pair(d, mbp, width, seed, kinds):
 
 
 def commands(a, emit):
-    kinds = a.kinds.split(",")
+    kinds = a.kinds.split(",") + (["fastq_plain", "fastq_gzip", "fastq_gzip_streamed"] if a.same_route and a.kinds == ap_default_kinds else [])
     d = tempfile.mkdtemp(prefix="sylph_fasta_reads_")
     try:
         n = make_pair(d, a.mbp, a.width, 1, kinds)
@@ -76,36 +88,45 @@ def commands(a, emit):
         base_exe = os.path.join(a.parent, "sylph-hip") if a.parent else new_exe
         emit(dict(what="FASTA read pair", pairs=n, gbp=round(gbp, 4), line_width=a.width or "one line per record", reps=a.reps, settle_seconds=a.settle,
                   bytes={k: os.path.getsize(f"{d}/s_1.fa{s}") for k, s in (("plain", ""), ("gzip", ".gz"), ("bzip2", ".bz2")) if os.path.exists(f"{d}/s_1.fa{s}")},
-                  baseline="the parent commit's binary (host reader)" if a.parent else "this tree's binary with SYLPH_HIP_FASTA_READS_DEVICE=0 (host reader)"))
-        suffix = {"plain": "", "gzip": ".gz", "bzip2": ".bz2", "gzip_streamed": ".gz"}
+                  baseline=("the parent commit's binary, device routes on" if a.same_route else "the parent commit's binary (host reader)") if a.parent
+                  else "this tree's binary with SYLPH_HIP_FASTA_READS_DEVICE=0 (host reader)"))
+        suffix = {"plain": "fa", "gzip": "fa.gz", "bzip2": "fa.bz2", "gzip_streamed": "fa.gz", "fastq_plain": "fq", "fastq_gzip": "fq.gz", "fastq_gzip_streamed": "fq.gz"}
+        laps = {}
 
         def run(exe, kind, device):
             env = dict(os.environ, SYLPH_HIP_FEED_TRACE="1", SYLPH_HIP_FASTA_READS_DEVICE=device)
             env.pop("SYLPH_HIP_EXACT_DEDUP", None)
             env.pop("SYLPH_HIP_INFLATE_STREAM", None)
-            if kind == "gzip_streamed":
+            if kind.endswith("gzip_streamed"):
                 env["SYLPH_HIP_INFLATE_STREAM"] = "1"
+            out = f"{d}/out_{'new' if exe == new_exe else 'base'}_{device}"
             time.sleep(a.settle)
             t = time.perf_counter()
-            p = subprocess.run([exe, "sketch", "-1", f"{d}/s_1.fa{suffix[kind]}", "-2", f"{d}/s_2.fa{suffix[kind]}", "-d", f"{d}/out_{device}"],
+            p = subprocess.run([exe, "sketch", "-1", f"{d}/s_1.{suffix[kind]}", "-2", f"{d}/s_2.{suffix[kind]}", "-d", out],
                                capture_output=True, text=True, env=env, timeout=1200)
             dt = time.perf_counter() - t
             if p.returncode != 0:
                 raise RuntimeError(p.stderr[-800:])
-            route = "FASTA device route" if ("FASTA records" in p.stderr) else "host reader"
-            with open(f"{d}/out_{device}/s_1.fa{suffix[kind]}.paired.sylsp", "rb") as f:
+            route = "FASTA device route" if ("FASTA records" in p.stderr) else "device route" if "device route:" in p.stderr else "host reader"
+            laps.setdefault((kind, exe), []).append({m.group(1).strip(): float(m.group(2)) for m in re.finditer(r"\[sylph_hip feed\] (.*?)\s+([0-9.]+) ms", p.stderr)})
+            with open(f"{out}/s_1.{suffix[kind]}.paired.sylsp", "rb") as f:
                 return dt, route, f.read()
 
         run(new_exe, "plain", "1")                                           # untimed: the binary, the libraries and the runtime's files come off the disk
+        laps.clear()
         for kind in kinds:
             new, base, routes, same = [], [], set(), True
             for rep in range(a.reps):
-                dt, route, sk_new = run(new_exe, kind, "1")
+                first_new = not (a.same_route and rep % 2)                   # --same-route: which binary goes first alternates too
+                if first_new:
+                    dt, route, sk_new = run(new_exe, kind, "1")
+                dt_b, route_b, sk_base = run(base_exe, kind, "1" if a.same_route else "0")
+                if not first_new:
+                    dt, route, sk_new = run(new_exe, kind, "1")
                 new.append(dt)
                 routes.add(route)
-                dt, route_b, sk_base = run(base_exe, kind, "0")
-                base.append(dt)
-                assert route_b == "host reader"
+                base.append(dt_b)
+                assert route_b == (route if a.same_route else "host reader")
                 same = same and sk_new == sk_base
                 print(f"# {kind} rep {rep}: {new[-1]:.3f} s against {base[-1]:.3f} s", flush=True)
             med_n, med_b = float(np.median(new)), float(np.median(base))
@@ -113,7 +134,9 @@ def commands(a, emit):
             emit(dict(kind=kind, route=sorted(routes), device_seconds=[round(x, 3) for x in new], baseline_seconds=[round(x, 3) for x in base],
                       device_median=round(med_n, 3), device_spread=round(spread_n, 3), baseline_median=round(med_b, 3), baseline_spread=round(spread_b, 3),
                       device_gbp_per_s=round(gbp / med_n, 3), baseline_gbp_per_s=round(gbp / med_b, 3), speedup=round(med_b / med_n, 2),
-                      sketches_byte_identical=same, on_by_default=bool(routes == {"FASTA device route"} and same and med_n + spread_n + spread_b < med_b)))
+                      sketches_byte_identical=same, on_by_default=bool(routes == {"FASTA device route"} and same and med_n + spread_n + spread_b < med_b),
+                      **(dict(device_median_within_baseline_min_max=bool(min(base) <= med_n <= max(base)), device_laps_ms=laps[(kind, new_exe)],
+                              baseline_laps_ms=laps[(kind, base_exe)]) if a.same_route else {})))
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
@@ -163,14 +186,18 @@ def kernels(a, emit):
     ctx.close()
 
 
+ap_default_kinds = "plain,gzip,bzip2,gzip_streamed"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mbp", type=float, default=500, help="bases per mate (bench.py's pair: 500)")
     ap.add_argument("--width", type=int, default=0, help="bases per FASTA line (0: one line per record)")
-    ap.add_argument("--kinds", default="plain,gzip,bzip2,gzip_streamed")
+    ap.add_argument("--kinds", default=ap_default_kinds)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--settle", type=float, default=2.0)
     ap.add_argument("--parent", default="", help="directory with the parent commit's sylph-hip, libsylph_host.so and libsylph_hip.so")
+    ap.add_argument("--same-route", action="store_true", help="the baseline binary takes the device routes too, FASTQ kinds are added, laps are kept")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--out", default="", help="append the JSON lines to this file too")
     a = ap.parse_args()
