@@ -17,7 +17,8 @@
 // COMPILE-TIME shifts, both right-aligned in 64 bits with clean tops, and the smaller of the two is ONE v_min_f64 (kmer_step):
 // 6 instructions per k-mer for both windows and the canonical choice, then the same hash / threshold sequences as the
 // position kernel.
-// Hits are accumulated as bit masks (one bit per k-mer, 32 k-mers per LDS word), counted, scanned across the workgroup —
+// Hits are accumulated as bit masks (one bit per k-mer, 32 k-mers per LDS word; the 256-lane instances set the bit with an LDS xor under
+// the threshold compare's own lane mask instead of transposing it on the VALU: reads_block.h kmer_step), counted, scanned across the workgroup —
 // lanes are in record order, so the scan gives file order — and only then re-hashed and written.
 #include <cstddef>
 
@@ -49,6 +50,10 @@ __global__ __launch_bounds__(256) void block_records_kernel(const uint64_t* __re
 #ifndef SYLPH_READS_WAVES
 #define SYLPH_READS_WAVES 5
 #endif
+// Which instances set their hit bits by LDS atomics (reads_block.h kmer_step, LB): the 256-lane ones.  The 512-lane A/B variant keeps
+// v_cmp + v_addc_co_u32: 17 more registers do not fit its budget of 80 for six waves per SIMD (profiles/r14_hit_bits_lds.md).
+template <int TPB>
+constexpr bool hit_bits_by_lds = TPB == RTPB;
 template <int K, int HV, int ENC, int TPB>
 // (512 lanes are two wavefronts per SIMD and workgroup: three workgroups = six per SIMD — five would leave room for two)
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 ? SYLPH_READS_WAVES : 6, TPB == 256 ? SYLPH_READS_WAVES : 6))) void reads_kernel(const uint8_t* __restrict__ bases_al, uint32_t bias, uint64_t n_al,
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 
     // bookkeeping is redone once (s.redo).  cand_slack widens the superset on purpose: the tests' way of making that road common.
     const uint64_t thr_loop = HV == 2 ? (uint64_t)((uint32_t)(thr >> 32) + 1u + cand_slack) : thr;
     if (tid == 0) *s.redo = 0;                                       // (ordered before its first reader by the barriers below)
+    const HitRegs hit = hit_bits_by_lds<TPB> ? hit_regs() : HitRegs{};
     // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): give every XCD one contiguous eighth of the
     // blocks (xcd_deal_share), so that the halo a block shares with its neighbour is found in the same L2.  (Outputs are indexed by block,
     // so the order of the results does not depend on this mapping.)
@@ -98,13 +104,15 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 
             if (record_geometry<K>(s, off, in_lds, w_lo, pass + tid, R1, paired, bias, a0, avx2_compat, L, s1, s2, e2, nh, rel))
                 state->long_record = 1u;                             // the host reruns the batch through the position kernel
             uint32_t slot, rel_h, nh_h, rows;
-            const bool dealt = deal_by_length(s, nh, rel, slot, rel_h, nh_h, rows);
-            hash_record<K, HV>(s, slot, rel_h, nh_h, thr_loop);
+            const bool dealt = deal_by_length<TPB, hit_bits_by_lds<TPB>>(s, nh, rel, slot, rel_h, nh_h, rows);
+            hash_record<K, HV, TPB, hit_bits_by_lds<TPB>>(s, slot, rel_h, nh_h, thr_loop, hit);
             if (dealt) __syncthreads();                              // masks were written by other lanes
             uint32_t total = 0;
+            bool decode = hit_bits_by_lds<TPB>;                      // the pass's first round decodes what the LDS atomics left
             for (;;) {                                               // (once; HV == 2: again after a candidate failed the exact test)
                 uint32_t first;
-                const uint32_t cnt = count_hits(s, nh, first, total);
+                const uint32_t cnt = count_hits(s, nh, decode, first, total);
+                decode = false;
                 publish_markers(s, cnt, first, total, want_markers, paired, L, s1, s2, e2, rel, bias, a0);
                 const bool is_listed = list_survivors(s, nh, cnt, first, total, rows);
                 __syncthreads();

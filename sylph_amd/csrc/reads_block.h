@@ -2,7 +2,8 @@
 // runs them for every pass of a block: load_stream, stage_offsets | record_geometry, deal_by_length, hash_record, count_hits,
 // publish_markers, list_survivors, finish_survivors | close_slots (common.h: shared with the position kernel).  The LDS they share is ReadsLds; which stream words, mask bits and
 // records belong to a block is seed_plan.h's arithmetic (free of HIP, tested on the CPU).  Every value of the hash loop lives in named
-// locals of hash_record: the steps pass scalars, never per-lane state in a struct.
+// locals of hash_record: the steps pass scalars, never per-lane state in a struct (HitRegs, the 17 constant registers of the LDS hit
+// bits, is the one bundle: built once per kernel, read only).
 // What the compiler makes of the steps was held against the one-body kernel they came from (profiles/seed_steps_census.txt); three things
 // in their signatures come from that: ReadsLds travels by value and its pointers are LDS-typed, the steps' global pointers carry no
 // __restrict__ (the kernel's arguments do: a second set of alias scopes changed the schedule and spilled in two instances), and
@@ -100,9 +101,35 @@ __device__ __forceinline__ void evenodd16(uint64_t x, uint32_t& ev, uint32_t& od
 // (2.5 instructions per window at most).  Two values below
 // 2^62 take their minimum in ONE v_min_f64 (min_u62, device_common.h) where compare + two selects + the shift of the winner
 // took four.
-template <int K, int T, int HV>
+// The threshold test, LB false: v_cmp + v_addc_co_u32 shift the compare's lane mask into the lane's `mask` register, one bit per k-mer (the
+// second instruction only transposes that bit).  LB true (round 14, seed_plan.h "hit bits set by LDS atomics"): v_cmpx narrows EXEC to
+// the hits, ONE no-return ds_xor_b32 under it sets the bit in the record's mask column — `mask` is the LDS byte address of the group's
+// word there, hit.bit[T] the k-mer's constant — and s_mov_b64 puts back the EXEC of the loop (hit.exec0).  Nothing else runs under the
+// narrowed EXEC; the block clobbers vcc only and takes no "memory" clobber: the blocks are kept in program order among themselves and
+// against hit_clear_lower by passing the address THROUGH every one of them, and against ordinary loads and stores by hit_chain_begin /
+// hit_chain_end on both sides of the loop.
+struct HitRegs {
+    uint32_t bit[16];     // hit_const(T), held in registers for the whole loop (opaque to the compiler: never rebuilt per k-mer)
+    uint32_t zero;
+    uint64_t exec0;       // EXEC of the loop (hash_record reads it in front of its loop: the loop's control flow is scalar)
+};
+// (built once per kernel: 17 moves per pass are a seventh of what the spelling saves a 150 bp read)
+__device__ __forceinline__ HitRegs hit_regs() {
+    HitRegs r;
+#pragma unroll
+    for (int t = 0; t < 16; t++) asm("v_mov_b32 %0, %1" : "=v"(r.bit[t]) : "s"(hit_const(t)));
+    asm("v_mov_b32 %0, 0" : "=v"(r.zero));
+    r.exec0 = 0;
+    return r;
+}
+__device__ __forceinline__ void hit_clear_lower(uint32_t& addr, uint32_t zero) { asm("ds_write_b16 %0, %1" : "+v"(addr) : "v"(zero)); }
+__device__ __forceinline__ void hit_chain_begin(uint32_t& addr) { asm volatile("" : "+v"(addr) : : "memory"); }
+// (the compiler counts no LDS operation of the blocks: wait for them here, in front of the column's readers and the barrier)
+__device__ __forceinline__ void hit_chain_end(uint32_t& addr) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(addr) : : "memory"); }
+
+template <int K, int T, int HV, bool LB>
 __device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
-                                          uint64_t thr, uint32_t& mask) {
+                                          uint64_t thr, uint32_t& mask, const HitRegs& hit) {
     static_assert(2 * K <= 62 && 2 * K > 32, "min_u62 wants both windows below 2^62; the high word holds 2K - 32 bits");
     constexpr int HB = 2 * K - 32, T0 = T & ~1;
     uint32_t fhi, rhi;
@@ -117,23 +144,31 @@ __device__ __forceinline__ void kmer_step(uint32_t A0, uint32_t A1, uint32_t A2,
     if constexpr (HV == 2) {
         // candidate test on the HIGH word: u = hi(h) + 1 - (the low word's carry), `thr` holds hi(T) + 1 here (reads_kernel)
         const uint32_t u = mm_hash64_gfx950_hi1(canon);
-        asm("v_cmp_ge_u32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(u), "s"((uint32_t)thr) : "vcc");
+        if constexpr (LB)
+            asm("v_cmpx_ge_u32 vcc, %2, %1\n\tds_xor_b32 %0, %3\n\ts_mov_b64 exec, %4"
+                : "+v"(mask) : "v"(u), "s"((uint32_t)thr), "v"(hit.bit[T]), "s"(hit.exec0) : "vcc");
+        else
+            asm("v_cmp_ge_u32 vcc, %2, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(u), "s"((uint32_t)thr) : "vcc");
     } else {
         const uint64_t h = HV ? mm_hash64_gfx950(canon) : mm_hash64(canon);
-        asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(h), "s"(thr) : "vcc");
+        if constexpr (LB)
+            asm("v_cmpx_lt_u64 vcc, %1, %2\n\tds_xor_b32 %0, %3\n\ts_mov_b64 exec, %4"
+                : "+v"(mask) : "v"(h), "s"(thr), "v"(hit.bit[T]), "s"(hit.exec0) : "vcc");
+        else
+            asm("v_cmp_lt_u64 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(mask) : "v"(h), "s"(thr) : "vcc");
     }
 }
-template <int K, int T0, int HV>
+template <int K, int T0, int HV, bool LB>
 __device__ __forceinline__ void kmer_steps8(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2,
-                                            uint64_t thr, uint32_t& mask) {
-    kmer_step<K, T0 + 0, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 1, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 2, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 3, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 4, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 5, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 6, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
-    kmer_step<K, T0 + 7, HV>(A0, A1, A2, B0, B1, B2, thr, mask);
+                                            uint64_t thr, uint32_t& mask, const HitRegs& hit) {
+    kmer_step<K, T0 + 0, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 1, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 2, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 3, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 4, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 5, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 6, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
+    kmer_step<K, T0 + 7, HV, LB>(A0, A1, A2, B0, B1, B2, thr, mask, hit);
 }
 
 // 1. The block's stream words [0, n_words) from the aligned coordinate a0 on, as a 2-bit big-endian stream.  Only the first and the
@@ -211,8 +246,9 @@ __device__ __forceinline__ bool record_geometry(const ReadsLds<TPB> s, const uin
 // indexed by record again, so the output does not depend on the dealing.  A pass of equally long records (every
 // lane in one bin) is hashed as it lies.
 // Gives the record slot this lane hashes with that record's stream base and k-mers, and the mask rows the pass's longest record
-// reaches; returns whether the pass was dealt (uniform over the workgroup).
-template <int TPB>
+// reaches; returns whether the pass was dealt (uniform over the workgroup).  LB (hit bits by LDS atomics): the lane's own column is
+// zeroed over those rows — in a dealt pass another lane hashes into it, behind the dealing's last barrier.
+template <int TPB, bool LB>
 __device__ __forceinline__ bool deal_by_length(const ReadsLds<TPB> s, uint32_t nh, uint32_t rel, uint32_t& slot, uint32_t& rel_h, uint32_t& nh_h,
                                                uint32_t& rows) {
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -239,6 +275,11 @@ __device__ __forceinline__ bool deal_by_length(const ReadsLds<TPB> s, uint32_t n
         hg_max = bins_used ? 63u - (uint32_t)(__ffsll((unsigned long long)bins_used) - 1) : 0u;   // half-groups of 8 k-mers
     }
     rows = rows_used(hg_max);
+    if constexpr (LB) {
+        // (two rows per turn, counted in a scalar: row `rows` itself, where rows is odd, belongs to the survivors' list — not in use yet)
+        const uint32_t rows_u = (uint32_t)__builtin_amdgcn_readfirstlane((int)rows);
+        for (uint32_t w = 0; w < rows_u; w += 2) { s.mask[w][tid] = 0; s.mask[w + 1][tid] = 0; }
+    }
     if (dealt) {
         const uint32_t incl = wave_inclusive_sum(hc);
         s.perm[(uint32_t)__shfl((int)(incl - hc), (int)bin) + arrival] = (uint16_t)tid;
@@ -252,12 +293,14 @@ __device__ __forceinline__ bool deal_by_length(const ReadsLds<TPB> s, uint32_t n
 
 // 5. The hit masks of record slot `slot` (stream base rel_h, nh_h k-mers): every lane of the wavefront walks the groups of the
 // wavefront's longest record (seed_plan.h hash_hi_word: how far that reads).
-template <int K, int HV, int TPB>
-__device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot, uint32_t rel_h, uint32_t nh_h, uint64_t thr_loop) {
+template <int K, int HV, int TPB, bool LB>
+__device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot, uint32_t rel_h, uint32_t nh_h, uint64_t thr_loop,
+                                            const HitRegs& hit_consts) {
     const SY_LDS uint32_t* const sF = s.sF;
     uint32_t nh_max = nh_h;
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) nh_max = max(nh_max, (uint32_t)__shfl_xor((int)nh_max, d));
+    if constexpr (LB) nh_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)nh_max);   // the blocks restore ONE EXEC: no lane leaves the loop alone
     if (nh_max) {
         // lane-aligned stream words A(j) = bases [rel + 16 j, rel + 16 j + 16): one LDS read and one 64-bit shift each
         const uint32_t w0 = rel_h >> 4, sh = 32u - (rel_h & 15u) * 2u;      // sh in [2, 32]
@@ -276,20 +319,43 @@ __device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot
         // whatever a half that was never written holds lies beyond nh and is cleared with the tail in count_hits.
         SY_LDS uint16_t* const mask_half = (SY_LDS uint16_t*)&s.mask[0][slot];
         const uint32_t n_grp = n_half >> 1;
+        if constexpr (LB) {
+            // the same walk with the hit bits set in LDS: the column's words are zero (deal_by_length), every k-mer's block xors its
+            // constant into the group's word, the lower half is cleared behind an even group, count_hits decodes (seed_plan.h)
+            HitRegs hit = hit_consts;
+            hit.exec0 = __builtin_amdgcn_read_exec();
+            uint32_t addr = (uint32_t)(uintptr_t)&s.mask[0][slot];
+            hit_chain_begin(addr);
+            for (uint32_t g = 0; g < n_grp; g++) {
+                kmer_steps8<K, 0, HV, true>(A0, A1, A2, B0, B1, B2, thr_loop, addr, hit);
+                kmer_steps8<K, 8, HV, true>(A0, A1, A2, B0, B1, B2, thr_loop, addr, hit);
+                A0 = A1; A1 = A2; A2 = next_word(g + 3);
+                B0 = B1; B1 = B2; B2 = rcword(A2);
+                if (hit_clear_after(g)) hit_clear_lower(addr, hit.zero);
+                else addr += hit_word_offset(2, TPB);
+            }
+            if (n_half & 1u) {
+                kmer_steps8<K, 0, HV, true>(A0, A1, A2, B0, B1, B2, thr_loop, addr, hit);
+                if (hit_clear_after(n_grp)) hit_clear_lower(addr, hit.zero);
+            }
+            hit_chain_end(addr);
+            return;
+        }
+        const HitRegs hit{};
         // whole groups of 16: one straight-line block (the odd half-group of a record's tail is done after the loop —
         // with the test inside the loop the second half of every group lived in its own basic block and took two
         // extra register moves per k-mer)
         for (uint32_t g = 0; g < n_grp; g++) {
             uint32_t mask = 0;
-            kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
-            kmer_steps8<K, 8, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+            kmer_steps8<K, 0, HV, false>(A0, A1, A2, B0, B1, B2, thr_loop, mask, hit);
+            kmer_steps8<K, 8, HV, false>(A0, A1, A2, B0, B1, B2, thr_loop, mask, hit);
             A0 = A1; A1 = A2; A2 = next_word(g + 3);
             B0 = B1; B1 = B2; B2 = rcword(A2);
             mask_half[group_half(g, TPB)] = (uint16_t)mask;
         }
         if (n_half & 1u) {                                                   // a last half-group: its 8 k-mers are the top byte
             uint32_t mask = 0;
-            kmer_steps8<K, 0, HV>(A0, A1, A2, B0, B1, B2, thr_loop, mask);
+            kmer_steps8<K, 0, HV, false>(A0, A1, A2, B0, B1, B2, thr_loop, mask, hit);
             mask_half[group_half(n_grp, TPB)] = (uint16_t)(mask << 8);
         }
     }
@@ -297,14 +363,21 @@ __device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot
 
 // 6. The real hits of the lane's own record (k-mer i < nh; the bits beyond are cleared from its last word), scanned over the
 // workgroup: lanes are in record order, so `first` — the hits in front of this lane's — is file order.  Returns the lane's count.
+// `decode`: the words are as the LDS atomics left them (hit_decode, its own inverse: true in the pass's FIRST round only — the second
+// round of HV == 2 finds decoded words with the struck candidates gone).
 template <int TPB>
-__device__ __forceinline__ uint32_t count_hits(const ReadsLds<TPB> s, uint32_t nh, uint32_t& first, uint32_t& total) {
+__device__ __forceinline__ uint32_t count_hits(const ReadsLds<TPB> s, uint32_t nh, bool decode, uint32_t& first, uint32_t& total) {
     const uint32_t tid = threadIdx.x;
     uint32_t cnt = 0;
     const uint32_t nw = mask_words(nh);
-    for (uint32_t w = 0; w + 1 < nw; w++) cnt += __popc(s.mask[w][tid]);
+    for (uint32_t w = 0; w + 1 < nw; w++) {
+        uint32_t m = s.mask[w][tid];
+        if (decode) { m = hit_decode(m); s.mask[w][tid] = m; }
+        cnt += __popc(m);
+    }
     if (nw) {                                                   // the record's last word: bits beyond k-mer nh - 1 are not its own
-        const uint32_t m = s.mask[nw - 1][tid] & tail_mask(nh);
+        const uint32_t m0 = s.mask[nw - 1][tid];
+        const uint32_t m = (decode ? hit_decode(m0) : m0) & tail_mask(nh);
         s.mask[nw - 1][tid] = m;
         cnt += __popc(m);
     }

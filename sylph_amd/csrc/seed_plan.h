@@ -92,6 +92,35 @@ SY_SEED_HD constexpr bool listed(uint32_t total, uint32_t rows, uint32_t tpb) { 
 // counting-sort bin of a record with nh k-mers: longest first
 SY_SEED_HD constexpr uint32_t deal_bin(uint32_t nh) { return 63u - half_groups(nh); }
 
+// ---- hit bits set by LDS atomics (round 14) -----------------------------------------------------------------------------------------
+// The hash loop may set a k-mer's hit bit with an LDS xor issued under the threshold compare's own lane mask.  The xor's data is
+// one of 16 constants, hit_const(T) for k-mer T of its group of 16: the k-mer's bit of a 16-bit half, in BOTH halves of the word, so
+// that the two groups of a word share the constants.  The words start as zero (deal_by_length: the pass's rows_used rows of every lane); after an EVEN group
+// (a lone half-group of 8 included) a 16-bit store of zero clears the lower half (hit_clear_after, hit_cleared); the odd group then
+// goes into both halves again.  The word ends up as upper = even ^ odd, lower = odd, and hit_decode brings back the layout of
+// kmer_word / kmer_bit.  hit_decode is its own inverse — a second decode would return the encoded word — so a pass decodes its
+// words exactly once, in a step of its own in front of everything that reads or strikes a bit (reads_block.h decode_hits).
+SY_SEED_HD constexpr uint32_t hit_const(uint32_t t) { return 0x00010001u << (15u - t); }
+SY_SEED_HD constexpr bool hit_clear_after(uint32_t g) { return (g & 1u) == 0u; }
+SY_SEED_HD constexpr uint32_t hit_cleared(uint32_t m) { return m & 0xFFFF0000u; }
+SY_SEED_HD constexpr uint32_t hit_decode(uint32_t m) { return m ^ (m << 16); }
+// byte offset of group g's word behind the record's first word in a [MASKW][tpb] array (its lower half lies at that offset, the upper
+// half two bytes on: group_half counts the same halves)
+SY_SEED_HD constexpr uint32_t hit_word_offset(uint32_t g, uint32_t tpb) { return (g >> 1) * tpb * 4u; }
+// The model of one record's column, as the loop writes it: hits[i] != 0 <=> k-mer i is below the threshold, for the i < 8 * n_half
+// k-mers a wavefront with n_half half-groups walks; col[0 .. rows_used(n_half)) gets the ENCODED words.
+inline void hit_encode_model(const uint8_t* hits, uint32_t n_half, uint32_t* col) {
+    for (uint32_t w = 0; w < rows_used(n_half); w++) col[w] = 0;
+    const uint32_t n_grp = n_half >> 1;
+    for (uint32_t g = 0; g < n_grp + (n_half & 1u); g++) {
+        uint32_t& word = col[hit_word_offset(g, 1) / 4u];
+        const uint32_t n_t = g < n_grp ? 16u : 8u;
+        for (uint32_t t = 0; t < n_t; t++)
+            if (hits[g * 16u + t]) word ^= hit_const(t);
+        if (hit_clear_after(g)) word = hit_cleared(word);
+    }
+}
+
 // ---- XCD dealing ----------------------------------------------------------------------------------------------------------------
 // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): position i of the dealing of n items gives every XCD one
 // contiguous eighth.  The result may be >= n for the padding of the last XCD's range.
@@ -155,6 +184,7 @@ struct SlotMeta {
 // ---- what the comments above claim --------------------------------------------------------------------------------------------------
 static_assert(RT_MIN % 16 == 0 && RT_MAX % 16 == 0 && RT_MIN <= RT_MAX && RH % 16 == 0, "blocks and halo are whole 16-base words");
 static_assert(MASKW * 32 >= NH_MAX, "a record's k-mers have a mask bit each");
+static_assert(MASKW % 2 == 0, "the columns are zeroed two rows at a time (deal_by_length)");
 static_assert(half_groups(NH_MAX) <= 63 && deal_bin(NH_MAX) < 64 && deal_bin(0) == 63, "63 bins hold the half-groups of the longest record");
 static_assert(RTPB_RAGGED <= (1 << OWNER_LANE_BITS) && (uint64_t)MASKW * 32 <= (1ull << (32 - OWNER_LANE_BITS)), "the owner word tid | idx << 10 holds 512 lanes and MASKW * 32 indices");
 static_assert(RTPB % 64 == 0 && RTPB_RAGGED % 64 == 0 && RTPB <= RTPB_RAGGED, "whole wavefronts");

@@ -16,6 +16,9 @@
 //       (min_u62, device_common.h) where V0-V6 spend v_cmp_lt_u64 + two v_cndmask_b32 + one shift: the fallback of round 13
 //   V8  V4 with both windows BUILT right-aligned with clean tops (v_alignbit_b32 low word, v_bfe_u32 high word out of a cut that two
 //       neighbouring k-mers share) + v_min_f64: what reads_kernel runs since round 13 (profiles/r13_canon_min.md)
+//   V9  V8 with the threshold test's second instruction gone: v_cmpx_lt_u64 narrows EXEC to the hits, ONE no-return ds_xor_b32 under it
+//       sets the k-mer's bit in the lane's own LDS column (seed_plan.h hit_const / hit_cleared / hit_decode: 16 constant VGPRs, the
+//       bit in both halves of the word), s_mov_b64 puts EXEC back; per-lane column [MASKW][256] beside the stream, like the kernel's
 // Every arm prints the sum of its masks: the exact arms (all but V2) must agree.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +27,7 @@
 #include <cstdlib>
 
 #include "device_common.h"
+#include "seed_plan.h"
 
 using namespace sylph;
 
@@ -160,6 +164,75 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
     out[blockIdx.x * 256 + threadIdx.x] = acc;
 }
 
+// V9: the hit bit goes to LDS under the compare's own lane mask.  Nothing else runs under the narrowed EXEC; the block restores the EXEC
+// of the loop (exec0) and clobbers vcc only.  The blocks have no side effect the compiler knows of and take no "memory" clobber — the hash
+// chains of neighbouring k-mers stay free to interleave, the stream reads free to move — and are kept in program order among themselves
+// and against the clearing stores by passing the column's address THROUGH every one of them (hit_chain_begin / hit_chain_end close the
+// chain against ordinary loads and stores on both sides of the loop).
+__device__ __forceinline__ void hit_bit_to_lds(uint64_t h, uint64_t thr, uint32_t& addr, uint32_t bit, uint64_t exec0) {
+    asm("v_cmpx_lt_u64 vcc, %1, %2\n\tds_xor_b32 %0, %3\n\ts_mov_b64 exec, %4" : "+v"(addr) : "v"(h), "s"(thr), "v"(bit), "s"(exec0) : "vcc");
+}
+__device__ __forceinline__ void hit_clear_lower(uint32_t& addr, uint32_t zero) { asm("ds_write_b16 %0, %1" : "+v"(addr) : "v"(zero)); }
+__device__ __forceinline__ void hit_chain_begin(uint32_t& addr) { asm volatile("" : "+v"(addr) : : "memory"); }
+__device__ __forceinline__ void hit_chain_end(uint32_t& addr) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(addr) : : "memory"); }
+template <int K, int T>
+__device__ __forceinline__ void kmer_step_lds(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2, uint64_t thr, uint32_t& addr,
+                                              const uint32_t (&bit)[16], uint64_t exec0) {
+    constexpr int HB = 2 * K - 32, T0 = T & ~1;
+    const uint32_t cf = fword<2 * T0>(A0, A1, A2), cr = rword<2 * T0 + 32>(B0, B1, B2);
+    const uint32_t fhi = __builtin_amdgcn_ubfe(cf, 32 - HB - 2 * (T - T0), HB), rhi = __builtin_amdgcn_ubfe(cr, 2 * (T - T0), HB);
+    const uint32_t flo = fword<2 * T + HB>(A0, A1, A2), rlo = rword<2 * T>(B0, B1, B2);
+    hit_bit_to_lds(mm_hash64_gfx950(min_u62(((uint64_t)fhi << 32) | flo, ((uint64_t)rhi << 32) | rlo)), thr, addr, bit[T], exec0);
+}
+template <int K, int T0>
+__device__ __forceinline__ void steps8_lds(uint32_t A0, uint32_t A1, uint32_t A2, uint32_t B0, uint32_t B1, uint32_t B2, uint64_t thr, uint32_t& addr,
+                                           const uint32_t (&bit)[16], uint64_t exec0) {
+    kmer_step_lds<K, T0 + 0>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0); kmer_step_lds<K, T0 + 1>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+    kmer_step_lds<K, T0 + 2>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0); kmer_step_lds<K, T0 + 3>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+    kmer_step_lds<K, T0 + 4>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0); kmer_step_lds<K, T0 + 5>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+    kmer_step_lds<K, T0 + 6>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0); kmer_step_lds<K, T0 + 7>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void loop_kernel_lds(uint32_t n_grp, uint64_t thr, uint32_t* __restrict__ out) {
+    __shared__ uint32_t sF[256 * 10 + 64];
+    __shared__ uint32_t s_mask[seed_plan::MASKW][256];
+    for (uint32_t i = threadIdx.x; i < 256 * 10 + 64; i += 256) sF[i] = (i + blockIdx.x * 977u) * 2654435761u ^ (i * 40503u);
+    const uint32_t rows = seed_plan::rows_used(n_grp * 2);             // n_grp <= 2 * MASKW
+    for (uint32_t w = 0; w < rows; w++) s_mask[w][threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t w0 = threadIdx.x * 9, sh = 32u - (threadIdx.x & 15u) * 2u;
+    uint32_t raw = sF[w0], nxt = sF[w0 + 1], j = 0;
+    auto next_word = [&]() {
+        const uint32_t a = (uint32_t)((((uint64_t)raw << 32) | nxt) >> sh);
+        raw = nxt;
+        nxt = sF[w0 + 2 + (j++ % 8)];
+        return a;
+    };
+    uint32_t A0 = next_word(), A1 = next_word(), A2 = next_word();
+    uint32_t B0 = rcword(A0), B1 = rcword(A1), B2 = rcword(A2);
+    uint32_t bit[16], zero;
+#pragma unroll
+    for (int t = 0; t < 16; t++) asm("v_mov_b32 %0, %1" : "=v"(bit[t]) : "s"(seed_plan::hit_const(t)));   // opaque: held in registers, not rebuilt per k-mer
+    asm("v_mov_b32 %0, 0" : "=v"(zero));
+    const uint64_t exec0 = __builtin_amdgcn_read_exec();
+    uint32_t addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)&s_mask[0][threadIdx.x];
+    hit_chain_begin(addr);
+    for (uint32_t g = 0; g < n_grp; g++) {
+        steps8_lds<31, 0>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+        steps8_lds<31, 8>(A0, A1, A2, B0, B1, B2, thr, addr, bit, exec0);
+        A0 = A1; A1 = A2; A2 = next_word();
+        B0 = B1; B1 = B2; B2 = rcword(A2);
+        if (seed_plan::hit_clear_after(g)) hit_clear_lower(addr, zero);
+        else addr += seed_plan::hit_word_offset(2, 256);
+    }
+    hit_chain_end(addr);
+    uint32_t acc = 0;
+    for (uint32_t w = 0; w < rows; w++) {
+        const uint32_t m = seed_plan::hit_decode(s_mask[w][threadIdx.x]);
+        acc += (m >> 16) + (m & 0xFFFFu);
+    }
+    out[blockIdx.x * 256 + threadIdx.x] = acc;
+}
+
 template <int V>
 void run(const char* what, uint32_t* out) {
     const uint32_t n_grp = 120 / 16 + 1;                 // a 150 bp read: 120 k-mers -> 7.5 groups (8 here)
@@ -170,7 +243,8 @@ void run(const char* what, uint32_t* out) {
     float best = 1e9f;
     for (int rep = 0; rep < 5; rep++) {
         (void)hipEventRecord(a, 0);
-        hipLaunchKernelGGL(loop_kernel<V>, dim3(blocks), dim3(256), 0, 0, n_grp, thr, out);
+        if constexpr (V == 9) hipLaunchKernelGGL(loop_kernel_lds, dim3(blocks), dim3(256), 0, 0, n_grp, thr, out);
+        else hipLaunchKernelGGL(loop_kernel<V>, dim3(blocks), dim3(256), 0, 0, n_grp, thr, out);
         (void)hipEventRecord(b, 0);
         (void)hipEventSynchronize(b);
         float ms = 0;
@@ -198,8 +272,12 @@ int main() {
     run<6>("V6 V5, first and last step too", out);
     run<7>("V7 V4, canonical choice: 2 x v_lshrrev_b64 + v_min_f64", out);
     run<8>("V8 V4, clean right-aligned windows + v_min_f64 (the kernel)", out);
+    run<9>("V9 V8, hit bit by ds_xor_b32 under v_cmpx's lane mask", out);
     run<4>("V4 again (clocks settled)", out);
     run<7>("V7 again", out);
     run<8>("V8 again", out);
+    run<9>("V9 again", out);
+    run<8>("V8 a third time", out);
+    run<9>("V9 a third time", out);
     return 0;
 }
