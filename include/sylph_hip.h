@@ -360,6 +360,33 @@ int sylph_bunzip2(sylph_ctx *ctx, const void *bz, uint64_t n_bytes, int mem, syl
 int sylph_bunzip2_files(sylph_ctx *ctx, const void *const *bz, const uint64_t *n_bytes, uint32_t n_files, int mem,
                         sylph_inflated **out);
 
+/* ---- bzip2 streamed through the device decoder in bounded memory (csrc/bunzip2.hip, bunzip2_stream_plan.h) -----------------------
+ * sylph_bunzip2_files uploads every compressed byte and builds the whole text of all files in one buffer.  A stream runs the same
+ * phases over ONE SLICE of every advancing file's compressed bytes per call (slice_bytes each, plus 1 MiB of overlap, which holds the
+ * end of any block libbz2's encoder can write; 0 = the context's "bunzip2_slice_bytes", else the default; at least 64 KiB).  A bzip2
+ * block never refers to the one before it, so a file carries only where its chain stands: a bit, the open stream's level and combined
+ * CRC, counts.  Scratch and text are a function of the slice, not of the file.  The arguments and the contract are
+ * sylph_inflate_stream_*'s: bz[i] is host memory that holds file i whole and stays valid until the stream is destroyed; one step
+ * decodes file i with advance[i] != 0 (NULL = all) one slice further; the new window of file i = bytes [keep_from[i], end) of its
+ * previous window (NULL / first call: nothing) followed by the slice's blocks; *window is a sylph_inflated (sylph_inflated_file(t, i,
+ * ..) is file i's window, readable 256 bytes either side; sylph_inflated_info: members = streams begun in this step, blocks,
+ * candidates decoded); the previous window must be alive during the call; finished[i] = 1 once file i has no more bytes to give.
+ * Anything that does not add up in any slice — a broken chain, a block or stream CRC that differs, a randomised block, bytes behind
+ * the last stream, a block that runs past the overlap — makes the call return SYLPH_ERR_FORMAT (no room: SYLPH_ERR_NOMEM): the
+ * stream is dead then, the context is fine, and the caller reads the files with libbz2 from their start.  A stream never hands out a
+ * byte that libbz2 would not have produced before that point.  sylph_bunzip2_stream_info: slices decoded, text bytes handed out (kept
+ * bytes not counted), the largest scratch (bytes) any call held, the largest window.  A stream belongs to its context and must be
+ * destroyed before it.  The context option "bunzip2_whole_max_bytes" makes sylph_bunzip2_files decline that many compressed bytes or
+ * more (0, the default: no limit). */
+typedef struct sylph_bunzip2_stream sylph_bunzip2_stream;
+int sylph_bunzip2_stream_open(sylph_ctx *ctx, const void *const *bz, const uint64_t *n_bytes, uint32_t n_files, int mem,
+                              uint64_t slice_bytes, sylph_bunzip2_stream **out);
+int sylph_bunzip2_stream_next(sylph_bunzip2_stream *st, const uint8_t *advance, const uint64_t *keep_from, sylph_inflated **window,
+                              uint8_t *finished);
+int sylph_bunzip2_stream_info(const sylph_bunzip2_stream *st, uint64_t *n_slices, uint64_t *text_bytes, uint64_t *peak_scratch_bytes,
+                              uint64_t *peak_window_bytes);
+void sylph_bunzip2_stream_destroy(sylph_bunzip2_stream *st);
+
 /* Finish the sample: (k-mer, count) table in ascending k-mer order == SequencesSketch.kmer_counts
  * (types.rs:145-155) as a keyed multiset, and the number of occurrences removed as duplicates
  * (sketch.rs:886-892).  The *_device variant leaves the table in HBM (owned by the session, valid until

@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphFasta { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflateStream { _p: [u8; 0] }
+#[repr(C)] pub struct SylphBunzip2Stream { _p: [u8; 0] }
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
@@ -165,6 +166,11 @@ extern "C" {
     pub fn sylph_bunzip2(ctx: *mut SylphCtx, bz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;
     pub fn sylph_bunzip2_files(ctx: *mut SylphCtx, bz: *const *const c_void, n_bytes: *const u64, n_files: u32, mem: c_int,
                                out: *mut *mut SylphInflated) -> c_int;   // the two mates of a pair in one pass
+    // bzip2 streamed through the device decoder in bounded memory: sylph_inflate_stream_*'s calls and contract over bzip2 slices
+    pub fn sylph_bunzip2_stream_open(ctx: *mut SylphCtx, bz: *const *const c_void, n_bytes: *const u64, n_files: u32, mem: c_int, slice_bytes: u64, out: *mut *mut SylphBunzip2Stream) -> c_int;
+    pub fn sylph_bunzip2_stream_next(st: *mut SylphBunzip2Stream, advance: *const u8, keep_from: *const u64, window: *mut *mut SylphInflated, finished: *mut u8) -> c_int;
+    pub fn sylph_bunzip2_stream_info(st: *const SylphBunzip2Stream, n_slices: *mut u64, text_bytes: *mut u64, peak_scratch_bytes: *mut u64, peak_window_bytes: *mut u64) -> c_int;
+    pub fn sylph_bunzip2_stream_destroy(st: *mut SylphBunzip2Stream);
     // the resampling of bootstrap_interval (contain.rs:849-898) for n_items genomes in one launch: per resample the five counts
     // ratio_lambda / ani_from_lambda read; lambda, ANI and the percentiles stay here.  declined[i] != 0: run the crate's own loop for item i
     pub fn sylph_bootstrap_counts(ctx: *mut SylphCtx, covs: *const c_void, cov_width: u32, cov_off: *const u64, keep: *const u32,

@@ -44,7 +44,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_sketch_genomes_fasta",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
            "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
-           "sylph_bunzip2", "sylph_bunzip2_files", "sylph_bootstrap_counts"]
+           "sylph_bunzip2", "sylph_bunzip2_files",
+           "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "sylph_bunzip2_stream_info", "sylph_bunzip2_stream_destroy", "sylph_bootstrap_counts"]
 
 
 def load():
@@ -114,6 +115,11 @@ def load():
     L.sylph_inflate_stream_destroy.restype = None
     L.sylph_bunzip2.argtypes = [vp, vp, u64, i32, P(vp)]
     L.sylph_bunzip2_files.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, P(vp)]
+    L.sylph_bunzip2_stream_open.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, u64, P(vp)]
+    L.sylph_bunzip2_stream_next.argtypes = [vp, P(C.c_uint8), P(u64), P(vp), P(C.c_uint8)]
+    L.sylph_bunzip2_stream_info.argtypes = [vp, P(u64), P(u64), P(u64), P(u64)]
+    L.sylph_bunzip2_stream_destroy.argtypes = [vp]
+    L.sylph_bunzip2_stream_destroy.restype = None
     L.sylph_pack_2bit.argtypes = [vp, u64, vp]
     L.sylph_sketch_finish.argtypes = [vp, P(vp), P(vp), P(u64), P(u64)]
     L.sylph_sketch_finish_device.argtypes = [vp, P(vp), P(vp), P(u64), P(u64)]
@@ -413,6 +419,10 @@ class InflateStream:
     of compressed bytes at a time, in memory bounded by the slice (csrc/inflate.hip, inflate_stream_plan.h).  next(advance, keep_from)
     -> InflateWindow; .finished[i] says when file i has given everything.  The previous window must be open during next().  Raises
     SylphHipError with code ERR_FORMAT when a slice does not add up: the stream is dead then, inflate on the host."""
+    _calls = "sylph_inflate_stream"
+
+    def _call(self, what):
+        return getattr(load(), f"{self._calls}_{what}")
 
     def __init__(self, ctx, gz, slice_bytes=0):
         self._h = None
@@ -420,7 +430,7 @@ class InflateStream:
         ptrs = (C.c_void_p * len(self._keeps))(*[k.ctypes.data for k in self._keeps])
         lens = (C.c_uint64 * len(self._keeps))(*[len(k) for k in self._keeps])
         h = C.c_void_p()
-        _check(load().sylph_inflate_stream_open(ctx._h, ptrs, lens, len(self._keeps), MEM_HOST, int(slice_bytes), C.byref(h)))
+        _check(self._call("open")(ctx._h, ptrs, lens, len(self._keeps), MEM_HOST, int(slice_bytes), C.byref(h)))
         self._h = h
         self.n_files = len(self._keeps)
         self.finished = [False] * self.n_files
@@ -430,18 +440,18 @@ class InflateStream:
         keep = (C.c_uint64 * self.n_files)(*[int(k) for k in keep_from]) if keep_from is not None else None
         fin = (C.c_uint8 * self.n_files)()
         w = C.c_void_p()
-        _check(load().sylph_inflate_stream_next(self._h, adv, keep, C.byref(w), fin))
+        _check(self._call("next")(self._h, adv, keep, C.byref(w), fin))
         self.finished = [bool(x) for x in fin]
         return InflateWindow(w, self.n_files)
 
     def info(self):
         a, b, c, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _check(load().sylph_inflate_stream_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        _check(self._call("info")(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(n_slices=int(a.value), text_bytes=int(b.value), peak_scratch_bytes=int(c.value), peak_window_bytes=int(d.value))
 
     def close(self):
         if self._h:
-            load().sylph_inflate_stream_destroy(self._h)
+            self._call("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -456,6 +466,13 @@ class Bunzipped(Inflated):
     the same handle as Inflated's.  n_members = streams, n_blocks = bzip2 blocks, n_candidates = block magics decoded.  Raises
     SylphHipError with code ERR_FORMAT when the library declines the bytes (not bzip2, damaged, randomised, ...): decode on the host then."""
     _one, _many = "sylph_bunzip2", "sylph_bunzip2_files"
+
+
+class Bunzip2Stream(InflateStream):
+    """sylph_bunzip2_stream_*: bzip2 files decoded on the device one slice of compressed bytes at a time, in memory bounded by the slice
+    (csrc/bunzip2.hip, bunzip2_stream_plan.h).  The calls and the contract are InflateStream's; a window is an InflateWindow."""
+    _calls = "sylph_bunzip2_stream"
+
 
 class FastqText:
     """sylph_fastq_*: plain four-line FASTQ text whose records the DEVICE finds (csrc/fastq.hip).  `text`: bytes / a uint8 array

@@ -10,7 +10,7 @@
 //                     libbz2's limit/base/perm tables in LDS (6.1 KB per wave); then the one chain that stays serial: Huffman symbols,
 //                     RUNA/RUNB runs and the inverse MTF, wave-uniform (bit buffer and state in SGPRs, the 256-entry MTF list in four
 //                     VGPRs, moved by a lane shift), the BWT column written 64 bytes at a time.  Reports where the block ended.
-//   (host)            ChainWalk: which candidates are the streams' blocks; the stream CRCs
+//   (host)            chain_step (ChainWalk / SliceWalk): which candidates are the streams' blocks; the stream CRCs
 //   hist/cft/scatter  the LF mapping by a stable counting sort per block: 4 KiB chunk histograms, a scan over the chunks, then one
 //                     wave per chunk ranks its bytes 64 at a time (8 ballots give the lanes with the same byte) and writes
 //                     tt[LF(i)] = i << 8 | byte
@@ -26,10 +26,29 @@
 // The candidates are decoded in batches of SYLPH_HIP_BUNZIP2_BATCH (1024) blocks: the scratch is bounded whatever the file's size.  Any
 // doubt — a chain that breaks, a CRC that differs, a randomised block, bytes behind the last stream — returns SYLPH_ERR_FORMAT and
 // nothing else happens: the caller decodes the file with libbz2 as before.
+//
+// Two roads run these phases (Bunzip2Phases).  sylph_bunzip2_files: the files whole, the text of all of them in one buffer.
+// sylph_bunzip2_stream_*: ONE SLICE of every advancing file's compressed bytes per call, the text handed out window by window, in memory
+// bounded by the slice; what a file carries from one call to the next, the cut and the sliced chain walk are bunzip2_stream_plan.h.
 #include <algorithm>
 
 #include "bunzip2_plan.h"
+#include "bunzip2_stream_plan.h"
 #include "decode_host.h"
+
+// What a stream holds between two calls: every file's carry, and where the window it handed out last lies (the caller keeps that alive
+// for the next call: its kept tail is copied from there).  A bzip2 block needs nothing of the text in front of it.
+struct sylph_bunzip2_stream {
+    sylph_ctx* ctx = nullptr;
+    std::vector<const uint8_t*> bz;
+    std::vector<uint64_t> n_bytes;
+    uint64_t slice_bytes = 0;
+    std::vector<sylph::bunzip2_stream_plan::Carry> carry;
+    std::vector<const uint8_t*> prev_text;        // file i's text in the window handed out last
+    std::vector<uint64_t> prev_len;
+    bool dead = false;
+    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+};
 
 namespace sylph {
 namespace {
@@ -53,17 +72,29 @@ __device__ inline uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
 // =================================================================================================================================
 // scan: the block magic at every bit position
 // =================================================================================================================================
-__global__ __launch_bounds__(256) void scan_kernel(const uint32_t* __restrict__ w, uint64_t n_words, uint64_t n_bits,
+// The bits of the upload that belong to one file: its whole bytes (sylph_bunzip2_files: one entry for all files, which lie back to back
+// there) or one SLICE of them (the stream: every advancing file's slice begins at a multiple of 256 bytes, zero bytes between).  A
+// candidate starts in [begin_bit, start_end_bit) and has its 48 bits in front of end_bit; a decoder reads no word behind end_bit's.
+struct SliceBits { unsigned long long begin_bit, start_end_bit, end_bit; };
+
+__global__ __launch_bounds__(256) void scan_kernel(const uint32_t* __restrict__ w, uint64_t n_words, const SliceBits* __restrict__ lim, uint32_t n_lim,
                                                    unsigned long long* __restrict__ out, uint32_t cap, uint32_t* __restrict__ count) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_words) return;
+    // the one slice this word's bits may start a candidate of (slices do not share a word)
+    uint64_t lo = 0, hi = 0, end = 0;
+    for (uint32_t k = 0; k < n_lim; k++) {
+        const SliceBits L = lim[k];
+        if (i * 32 + 32 > L.begin_bit && i * 32 < L.start_end_bit) { lo = L.begin_bit; hi = L.start_end_bit; end = L.end_bit; }
+    }
+    if (lo == hi) return;
     const uint64_t a = ((uint64_t)bswap32(w[i]) << 32) | bswap32(w[i + 1]);     // (the buffer has PAD_BYTES of zeros behind)
     const uint64_t b = (uint64_t)bswap32(w[i + 2]) << 32;
     for (uint32_t o = 0; o < 32; o++) {
         const uint64_t win = o ? (a << o) | (b >> (64 - o)) : a;
         if ((win >> 16) == BLOCK_MAGIC) {
             const uint64_t bit = i * 32 + o;
-            if (bit + 48 <= n_bits) {
+            if (bit >= lo && bit < hi && bit + 48 <= end) {
                 const uint32_t k = atomicAdd(count, 1u);
                 if (k < cap) out[k] = bit;
             }
@@ -105,7 +136,9 @@ struct Bits {                                       // MSB-first bit reader; eve
 
 constexpr int MAX_GROUPS = 6, MAX_ALPHA = 258, MAX_CODE_LEN = 23;
 
-__global__ __launch_bounds__(64) void decode_kernel(const uint32_t* __restrict__ words, uint64_t n_words, uint64_t n_bits,
+// The wavefront reads the bytes of ITS slice only (lim, as in scan_kernel): words behind the slice's last read as zero, and a block that
+// is still going at the slice's last bit reports ST_ERR_OVERRUN there — never a bit of the other mate's slice.
+__global__ __launch_bounds__(64) void decode_kernel(const uint32_t* __restrict__ words, const SliceBits* __restrict__ lim, uint32_t n_lim,
                                                     const unsigned long long* __restrict__ cands, uint8_t* __restrict__ ll_base,
                                                     uint8_t* __restrict__ sel_base, BlockReport* __restrict__ rep) {
     __shared__ int32_t s_limit[MAX_GROUPS][24], s_base[MAX_GROUPS][24], s_min[MAX_GROUPS];
@@ -117,8 +150,15 @@ __global__ __launch_bounds__(64) void decode_kernel(const uint32_t* __restrict__
     uint8_t* ll = ll_base + (size_t)c * MAX_BLOCK;
     uint8_t* sel = sel_base + (size_t)c * MAX_SELECTORS;
     uint32_t st = ST_OK, crc = 0, rnd = 0, orig = 0, nb = 0, symbols = 0;
+    const uint64_t start = cands[c];
+    uint64_t n_bits = 0;                            // where the candidate's slice ends (wave-uniform; 0: no slice holds it)
+    for (uint32_t k = 0; k < n_lim; k++) {
+        const SliceBits L = lim[k];
+        if (start >= L.begin_bit && start < L.start_end_bit) n_bits = L.end_bit;
+    }
+    const uint64_t n_words = (n_bits + 31) / 32;
     Bits b;
-    b.init(words, n_words, cands[c]);
+    b.init(words, n_words, start);
     {
         const uint64_t m = ((uint64_t)b.get(24) << 24) | b.get(24);
         if (m != BLOCK_MAGIC) { st = ST_ERR_MAGIC; goto done; }
@@ -546,45 +586,59 @@ uint32_t batch_size() {
     return 1024;
 }
 
-// One call's state, and its phases in the order bunzip2_impl runs them.  The candidates are decoded in batches, in bit order, and the
-// chain is walked as their reports come in: each turn finishes the chain blocks of the batch in hand, then decodes the next batch.
-struct Bunzip2Call {
-    sylph_inflated* t;
+// The device phases of both roads (sylph_bunzip2_files: the files whole; sylph_bunzip2_stream_next: one slice per advancing file), in
+// the order they run.  The candidates are decoded in batches, in bit order, and the chains are walked as their reports come in: each
+// turn finishes the chain blocks of the batch in hand, then decodes the next batch.  The scratch does not depend on the file.
+struct PendingBlock { size_t cand; uint32_t n, file; };     // a chain block of the batch in hand: its candidate, BWT bytes, file
+struct Bunzip2Phases {
     sylph_ctx* ctx;
     hipStream_t s;
-    const Segments segs;
-    const uint64_t total, n_words;                      // compressed bytes, and the words that hold them
-    DevBuf d_in{ctx}, d_cand{ctx}, d_count{ctx}, d_ll{ctx}, d_sel{ctx}, d_rep{ctx}, d_tt{ctx}, d_hist{ctx}, d_succ{ctx}, d_seg{ctx}, d_offs{ctx}, d_rle{ctx}, d_jobs{ctx},
-        d_jstat{ctx}, d_raw{ctx}, d_tab{ctx}, d_x2n{ctx};
+    uint64_t total = 0, n_words = 0;                    // bytes of the upload, and the words that hold them
+    std::vector<SliceBits> lim;                         // whose bits they are
+    DevBuf d_in{ctx}, d_lim{ctx}, d_cand{ctx}, d_count{ctx}, d_ll{ctx}, d_sel{ctx}, d_rep{ctx}, d_tt{ctx}, d_hist{ctx}, d_succ{ctx}, d_seg{ctx}, d_offs{ctx}, d_rle{ctx},
+        d_jobs{ctx}, d_jstat{ctx}, d_raw{ctx}, d_tab{ctx}, d_x2n{ctx};
     std::vector<uint64_t> cand;                         // sorted candidate bits
     uint32_t B = 1;                                     // candidates per batch
     uint32_t x2n[64];
     std::vector<BlockReport> rep;                       // per candidate; those of [0, have) are known
-    ChainWalk walk;
     size_t have = 0, batch_first = 0, done_blocks = 0;
-    std::vector<uint64_t> blk_off, blk_len;             // every chain block's text
-    TextBuf text{"hipMalloc (bzip2 text)"};
-    uint64_t used = 0;
     std::vector<Job> jobs;                              // the chain blocks of the batch in hand
+    std::vector<uint32_t> stored_crc;                   // ... and the CRCs their headers store
     uint32_t max_len = 0;                               // the longest of their texts
 
-    Bunzip2Call(sylph_inflated* t_, Segments&& g)
-        : t(t_), ctx(t_->ctx), s(t_->ctx->stream), segs(std::move(g)), total(segs.total()), n_words((total + 3) / 4) {}
+    explicit Bunzip2Phases(sylph_ctx* c) : ctx(c), s(c->stream) {}
 
-    // ---- the compressed bytes, back to back, and the candidates
-    void find_candidates() {
+    uint64_t scratch_bytes() const {
+        uint64_t b = 0;
+        for (const DevBuf* d : {&d_in, &d_lim, &d_cand, &d_count, &d_ll, &d_sel, &d_rep, &d_tt, &d_hist, &d_succ, &d_seg, &d_offs, &d_rle, &d_jobs, &d_jstat, &d_raw, &d_tab, &d_x2n})
+            b += d->cap;
+        return b;
+    }
+
+    // ---- room for the compressed bytes (the caller uploads them, zero from the last one to PAD_BYTES behind the last whole word)
+    uint8_t* input(uint64_t bytes) {
+        total = bytes;
+        n_words = (bytes + 3) / 4;
         d_in.reserve(n_words * 4 + PAD_BYTES);
-        upload_segments(ctx, (uint8_t*)d_in.p, segs, PAD_BYTES);
+        return (uint8_t*)d_in.p;
+    }
+
+    // ---- the candidates: every block magic whose bits lie in one entry of `lim`
+    void find_candidates(const char* phase) {
+        d_lim.reserve(std::max<size_t>(lim.size(), 1) * sizeof(SliceBits));
+        if (!lim.empty()) ctx->h2d(d_lim.p, lim.data(), lim.size() * sizeof(SliceBits));
         const uint32_t cap = (uint32_t)std::min<uint64_t>(total / 8 + 64, 0xFFFFFFF0ull);
         d_cand.reserve((size_t)cap * 8);
         d_count.reserve(4);
         {
             ScopedKernelTimer kt(ctx, "bunzip2_scan");
-            HostPhase hp(ctx, "bunzip2: scan");
+            HostPhase hp(ctx, phase);
             SY_HIP(hipMemsetAsync(d_count.p, 0, 4, s));
-            hipLaunchKernelGGL(scan_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, d_in.as<uint32_t>(), n_words, total * 8,
-                               d_cand.as<unsigned long long>(), cap, d_count.as<uint32_t>());
-            SY_HIP(hipGetLastError());
+            if (n_words) {
+                hipLaunchKernelGGL(scan_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, s, d_in.as<uint32_t>(), n_words, d_lim.as<SliceBits>(),
+                                   (uint32_t)lim.size(), d_cand.as<unsigned long long>(), cap, d_count.as<uint32_t>());
+                SY_HIP(hipGetLastError());
+            }
             cand = fetch_candidates(ctx, d_cand.p, d_count.as<uint32_t>(), cap, "more block magics than the candidate list holds");
         }
         if (!cand.empty()) ctx->h2d(d_cand.p, cand.data(), cand.size() * 8);
@@ -603,12 +657,13 @@ struct Bunzip2Call {
     }
 
     // ---- the chain blocks of the batch in hand: inverse BWT (LF mapping, walks) and the run-length functions -> every block's length
-    void invert_batch() {
-        const uint32_t J = (uint32_t)(walk.blocks.size() - done_blocks);
+    void invert_batch(const std::vector<PendingBlock>& pend) {
+        const uint32_t J = (uint32_t)pend.size();
         jobs.resize(J);
+        stored_crc.resize(J);
         for (uint32_t j = 0; j < J; j++) {
-            const ChainBlock& cb = walk.blocks[done_blocks + j];
-            jobs[j] = Job{(uint32_t)(cb.cand - batch_first), cb.n, rep[cb.cand].orig_ptr, 0, 0};
+            jobs[j] = Job{(uint32_t)(pend[j].cand - batch_first), pend[j].n, rep[pend[j].cand].orig_ptr, 0, 0};
+            stored_crc[j] = rep[pend[j].cand].crc;
         }
         d_jobs.reserve((size_t)J * sizeof(Job));
         d_jstat.reserve((size_t)J * 4);
@@ -650,31 +705,25 @@ struct Bunzip2Call {
         std::vector<uint32_t> jstat(J);
         ctx->d2h(jstat.data(), d_jstat.p, (size_t)J * 4);
         ctx->d2h(jobs.data(), d_jobs.p, (size_t)J * sizeof(Job));
-        for (uint32_t j = 0; j < J; j++)
-            if (jstat[j]) throw FormatDecline{"block " + std::to_string(done_blocks + j) + ": inverse BWT / run lengths do not add up (" + std::to_string(jstat[j]) + ")"};
-    }
-
-    // ---- every block of the batch gets its place behind the text so far, and is written there
-    void write_batch_text() {
-        const uint32_t J = (uint32_t)jobs.size();
         max_len = 0;
         for (uint32_t j = 0; j < J; j++) {
-            jobs[j].out_off = used;
-            blk_off.push_back(used);
-            blk_len.push_back(jobs[j].out_len);
-            used += jobs[j].out_len;
+            if (jstat[j]) throw FormatDecline{"block " + std::to_string(done_blocks + j) + ": inverse BWT / run lengths do not add up (" + std::to_string(jstat[j]) + ")"};
             max_len = std::max(max_len, jobs[j].out_len);
         }
-        text.grow(used, blk_off[done_blocks], s);
+    }
+
+    // ---- every block of the batch is written at the place the caller gave it (Job::out_off, in `text`)
+    void write_batch_text(uint8_t* text) {
+        const uint32_t J = (uint32_t)jobs.size();
         ctx->h2d(d_jobs.p, jobs.data(), (size_t)J * sizeof(Job));
         ScopedKernelTimer kt(ctx, "bunzip2_rle");
         HostPhase hp(ctx, "bunzip2: text");
-        hipLaunchKernelGGL(rlewrite_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, d_jobs.as<Job>(), d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), text.text());
+        hipLaunchKernelGGL(rlewrite_kernel, dim3((NRC + 255) / 256, J), dim3(256), 0, s, d_jobs.as<Job>(), d_ll.as<uint8_t>(), d_rle.as<uint32_t>(), text);
         SY_HIP(hipGetLastError());
     }
 
     // ---- CRC-32/BZIP2 of every block of the batch, against the one its header stores
-    void check_batch_crcs() {
+    void check_batch_crcs(const uint8_t* text) {
         const uint32_t J = (uint32_t)jobs.size();
         std::vector<uint32_t> raw(J);
         {
@@ -683,19 +732,20 @@ struct Bunzip2Call {
             SY_HIP(hipMemsetAsync(d_raw.p, 0, (size_t)J * 4, s));
             const uint32_t gx = (uint32_t)(((uint64_t)max_len + (uint64_t)PIECE * 256 - 1) / ((uint64_t)PIECE * 256));
             if (gx) {
-                hipLaunchKernelGGL(crc_kernel, dim3(gx, J), dim3(256), 0, s, d_jobs.as<Job>(), text.text(), d_tab.as<uint32_t>(), d_x2n.as<uint32_t>(), d_raw.as<uint32_t>());
+                hipLaunchKernelGGL(crc_kernel, dim3(gx, J), dim3(256), 0, s, d_jobs.as<Job>(), text, d_tab.as<uint32_t>(), d_x2n.as<uint32_t>(), d_raw.as<uint32_t>());
                 SY_HIP(hipGetLastError());
             }
             ctx->d2h(raw.data(), d_raw.p, (size_t)J * 4);
         }
         for (uint32_t j = 0; j < J; j++) {
-            const uint32_t stored = rep[walk.blocks[done_blocks + j].cand].crc, got = crc_finish(x2n, raw[j], jobs[j].out_len);
+            const uint32_t stored = stored_crc[j], got = crc_finish(x2n, raw[j], jobs[j].out_len);
             if (got != stored) {
                 char msg[160];
                 snprintf(msg, sizeof(msg), "block %zu: CRC %08x, the stream says %08x", done_blocks + j, got, stored);
                 throw FormatDecline{msg};
             }
         }
+        done_blocks += J;
     }
 
     // ---- the next batch of candidates: one wavefront each, the BWT columns and the reports
@@ -709,12 +759,42 @@ struct Bunzip2Call {
         {
             ScopedKernelTimer kt(ctx, "bunzip2_decode");
             HostPhase hp(ctx, "bunzip2: decode");
-            hipLaunchKernelGGL(decode_kernel, dim3(cnt), dim3(64), 0, s, d_in.as<uint32_t>(), n_words + PAD_BYTES / 4, total * 8,
+            hipLaunchKernelGGL(decode_kernel, dim3(cnt), dim3(64), 0, s, d_in.as<uint32_t>(), d_lim.as<SliceBits>(), (uint32_t)lim.size(),
                                d_cand.as<unsigned long long>() + batch_first, d_ll.as<uint8_t>(), d_sel.as<uint8_t>(), d_rep.as<BlockReport>());
             SY_HIP(hipGetLastError());
         }
         ctx->d2h(rep.data() + batch_first, d_rep.p, (size_t)cnt * sizeof(BlockReport));
         have += cnt;
+    }
+};
+
+// sylph_bunzip2_files: the files whole, back to back; one chain through all of them; the whole text in one buffer that grows
+struct Bunzip2Call : Bunzip2Phases {
+    sylph_inflated* t;
+    const Segments segs;
+    ChainWalk walk;
+    size_t taken = 0;                                   // chain blocks handed to the phases so far
+    std::vector<uint64_t> blk_off, blk_len;             // every chain block's text
+    TextBuf text{"hipMalloc (bzip2 text)"};
+    uint64_t used = 0;
+
+    Bunzip2Call(sylph_inflated* t_, Segments&& g) : Bunzip2Phases(t_->ctx), t(t_), segs(std::move(g)) {}
+
+    void upload() {
+        upload_segments(ctx, input(segs.total()), segs, PAD_BYTES);
+        lim.assign(1, SliceBits{0, total * 8, total * 8});
+    }
+
+    // ---- every block of the batch gets its place behind the text so far
+    void place_batch() {
+        const size_t first = blk_off.size();
+        for (Job& jb : jobs) {
+            jb.out_off = used;
+            blk_off.push_back(used);
+            blk_len.push_back(jb.out_len);
+            used += jb.out_len;
+        }
+        text.grow(used, blk_off[first], s);
     }
 
     // ---- the handle: the text, the counts, every file's range (a file's blocks are consecutive in the chain)
@@ -746,25 +826,208 @@ void bunzip2_impl(sylph_inflated* t, const void* const* bzs, const uint64_t* n_b
         if (!n_bytes[i]) throw FormatDecline{"file " + std::to_string(i) + " is empty"};
         if (!stream_level(segs.ptr[i], n_bytes[i], 0)) throw FormatDecline{"file " + std::to_string(i) + " does not begin with a bzip2 stream header"};
     }
+    if (segs.total() >= ctx->bunzip2_whole_max_bytes) throw FormatDecline{"more bzip2 bytes than \"bunzip2_whole_max_bytes\" allows in one piece"};
     Bunzip2Call c(t, std::move(segs));
-    c.find_candidates();
+    c.upload();
+    c.find_candidates("bunzip2: scan");
     c.upload_crc_tables();
     c.walk.start(&c.segs, &c.cand);
     c.text.grow(std::max<uint64_t>(c.total * 5, 1u << 20), 0, c.s);
+    std::vector<PendingBlock> pend;
     for (;;) {
         const bool fin = c.walk.step(c.rep.data(), c.have);
         if (!c.walk.why.empty()) throw FormatDecline{c.walk.why};
-        if (c.walk.blocks.size() > c.done_blocks) {
-            c.invert_batch();
-            c.write_batch_text();
-            c.check_batch_crcs();
-            c.done_blocks = c.walk.blocks.size();
+        if (c.walk.blocks.size() > c.taken) {
+            pend.clear();
+            for (; c.taken < c.walk.blocks.size(); c.taken++) pend.push_back(PendingBlock{c.walk.blocks[c.taken].cand, c.walk.blocks[c.taken].n, c.walk.blocks[c.taken].file});
+            c.invert_batch(pend);
+            c.place_batch();
+            c.write_batch_text(c.text.text());
+            c.check_batch_crcs(c.text.text());
         }
         if (fin) break;
         c.decode_next_batch();
     }
     c.fill_handle();
     SY_HIP(hipStreamSynchronize(c.s));
+}
+
+// =================================================================================================================================
+// the stream: the same phases over one slice per advancing file (bookkeeping: bunzip2_stream_plan.h)
+// =================================================================================================================================
+using namespace bunzip2_stream_plan;
+constexpr uint64_t SLICE_ALIGN = 256;               // a file's slice begins at a multiple of this in the upload (zero bytes between them)
+
+struct StreamCall : Bunzip2Phases {
+    sylph_bunzip2_stream* st;
+    sylph_inflated* t;
+    const uint8_t* advance;
+    const uint64_t* keep_from;
+    struct FileSlice { uint32_t file; SliceCut sc; uint64_t off; size_t cand_lo = 0, cand_hi = 0; };   // off: where the slice's bytes lie in the upload
+    std::vector<FileSlice> slices;                  // in file order
+    std::vector<int> slice_of_file;
+    std::vector<std::vector<uint64_t>> cand_bits;   // per slice: its candidates, in bits of the FILE
+    std::vector<SliceWalk> walks;                   // per slice
+    std::vector<PendingBlock> pend;
+    TextBuf text{"hipMalloc (bzip2 window)"};
+    std::vector<uint64_t> kept, text_off;           // per file: kept bytes of the previous window; where the file's window begins
+    std::vector<uint32_t> tails;                    // files whose kept tail has a place and is not copied yet
+    uint32_t cur = 0;                               // the file whose window is being laid out (those before it are closed)
+    bool cur_open = false;
+    uint64_t used = 0;
+
+    StreamCall(sylph_bunzip2_stream* st_, sylph_inflated* t_, const uint8_t* adv, const uint64_t* keep)
+        : Bunzip2Phases(st_->ctx), st(st_), t(t_), advance(adv), keep_from(keep) {}
+
+    uint32_t n_files() const { return (uint32_t)st->bz.size(); }
+
+    void plan_slices() {
+        const uint32_t F = n_files();
+        kept.assign(F, 0);
+        text_off.assign(F + 1, 0);
+        slice_of_file.assign(F, -1);
+        uint64_t at = 0;
+        for (uint32_t f = 0; f < F; f++) {
+            if (keep_from) {
+                SY_REQUIRE(keep_from[f] <= st->prev_len[f], "sylph_bunzip2_stream_next: keep_from[%u] = %llu lies behind the previous window (%llu bytes)", f,
+                           (unsigned long long)keep_from[f], (unsigned long long)st->prev_len[f]);
+                kept[f] = st->prev_len[f] - keep_from[f];
+            }
+            if ((advance && !advance[f]) || st->carry[f].finished) continue;
+            const SliceCut sc = slice_cut(st->carry[f], st->n_bytes[f], st->slice_bytes);
+            at = (at + SLICE_ALIGN - 1) / SLICE_ALIGN * SLICE_ALIGN;
+            slice_of_file[f] = (int)slices.size();
+            slices.push_back(FileSlice{f, sc, at});
+            at += sc.end - sc.pos;
+        }
+        uint8_t* in = input(at);
+        HostPhase hp(ctx, "bunzip2 stream: upload");
+        SY_HIP(hipMemsetAsync(in, 0, n_words * 4 + PAD_BYTES, s));
+        lim.clear();
+        for (const FileSlice& fs : slices) {
+            if (fs.sc.end > fs.sc.pos) ctx->h2d(in + fs.off, st->bz[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
+            // (a block that starts at or behind the cut is the next slice's: it is neither looked for nor decoded here)
+            const uint64_t starts = fs.sc.cut < st->n_bytes[fs.file] ? fs.sc.cut : fs.sc.end;
+            lim.push_back(SliceBits{fs.off * 8, (fs.off + (starts - fs.sc.pos)) * 8, (fs.off + (fs.sc.end - fs.sc.pos)) * 8});
+        }
+    }
+
+    // every slice's candidates in bits of its file, and its walk from the file's carry
+    void start_walks() {
+        cand_bits.assign(slices.size(), {});
+        walks.assign(slices.size(), SliceWalk{});
+        for (size_t si = 0; si < slices.size(); si++) {
+            FileSlice& fs = slices[si];
+            const int64_t shift = (int64_t)(fs.sc.pos * 8) - (int64_t)(fs.off * 8);
+            fs.cand_lo = (size_t)(std::lower_bound(cand.begin(), cand.end(), lim[si].begin_bit) - cand.begin());
+            fs.cand_hi = (size_t)(std::lower_bound(cand.begin(), cand.end(), lim[si].end_bit) - cand.begin());
+            for (size_t i = fs.cand_lo; i < fs.cand_hi; i++) cand_bits[si].push_back((uint64_t)((int64_t)cand[i] + shift));
+            walks[si].start(st->bz[fs.file], st->n_bytes[fs.file], fs.file, st->carry[fs.file], fs.sc, &cand_bits[si], shift);
+        }
+    }
+
+    // follow every slice's chain as far as the reports in hand allow -> pend: the blocks that joined, in file order.  true: all walked.
+    bool walk_chains() {
+        pend.clear();
+        bool all = true;
+        for (size_t si = 0; si < slices.size(); si++) {
+            const FileSlice& fs = slices[si];
+            SliceWalk& w = walks[si];
+            const size_t before = w.blocks.size();
+            w.step(rep.data() + fs.cand_lo, std::min(std::max(have, fs.cand_lo), fs.cand_hi) - fs.cand_lo);
+            if (!w.why.empty()) throw FormatDecline{"file " + std::to_string(fs.file) + ": " + w.why};
+            for (size_t i = before; i < w.blocks.size(); i++) pend.push_back(PendingBlock{fs.cand_lo + w.blocks[i].cand, w.blocks[i].n, fs.file});
+            all = all && w.ended;
+        }
+        return all;
+    }
+
+    // ---- where everything goes in the window's text: per file, the kept tail of its previous window, then the slice's blocks.  A file's
+    // window begins where the one before it ends, so it is laid out once every earlier file's chain is walked — which it is before a
+    // report of its own can be there: the candidates are decoded in bit order, and file i's slice lies in front of file i + 1's.
+    void place_batch() {
+        const uint32_t F = n_files();
+        const uint64_t before = used;
+        size_t j = 0;
+        while (cur < F) {
+            if (!cur_open) {
+                text_off[cur] = used;
+                if (kept[cur]) tails.push_back(cur);
+                used += kept[cur];
+                cur_open = true;
+            }
+            for (; j < pend.size() && pend[j].file == cur; j++) { jobs[j].out_off = used; used += jobs[j].out_len; }
+            if (slice_of_file[cur] >= 0 && !walks[slice_of_file[cur]].ended) break;
+            text_off[++cur] = used;
+            cur_open = false;
+        }
+        SY_REQUIRE(j == pend.size(), "sylph_bunzip2_stream_next: a block of file %u came in front of its file's window", j < pend.size() ? pend[j].file : 0u);
+        text.grow(std::max<uint64_t>(used, 1), before, s);
+        for (uint32_t f : tails) SY_HIP(hipMemcpyAsync(text.text() + text_off[f], st->prev_text[f] + keep_from[f], kept[f], hipMemcpyDeviceToDevice, s));
+        tails.clear();
+    }
+
+    void fill_handle() {
+        SY_HIP(hipMemsetAsync(text.text() + used, 0, 256, s));
+        t->n = used;
+        t->n_candidates = have;
+        t->n_host_members = 0;
+        t->files.clear();
+        for (uint32_t f = 0; f < n_files(); f++) t->files.push_back({text_off[f], text_off[f + 1]});
+        for (size_t si = 0; si < slices.size(); si++) {
+            t->n_blocks += walks[si].blocks.size();
+            t->n_members += walks[si].next.pos.n_streams - st->carry[slices[si].file].pos.n_streams;
+        }
+    }
+
+    // ---- what the next call needs: every advanced file's carry
+    void commit() {
+        for (size_t si = 0; si < slices.size(); si++) {
+            st->carry[slices[si].file] = walks[si].next;
+            st->n_slices++;
+        }
+        uint64_t kept_all = 0;
+        for (uint64_t k : kept) kept_all += k;
+        st->text_bytes += used - kept_all;
+        st->peak_scratch = std::max(st->peak_scratch, scratch_bytes());
+        st->peak_window = std::max(st->peak_window, used);
+    }
+};
+
+void stream_next_impl(sylph_bunzip2_stream* st, sylph_inflated* t, const uint8_t* advance, const uint64_t* keep_from) {
+    sylph_ctx* ctx = st->ctx;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard dg(ctx->device);
+    StreamCall c(st, t, advance, keep_from);
+    // (on every way out — a decline included — the stream is idle before the scratch goes back to the pool; destroyed before `c`)
+    struct Done { hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); } } done{ctx->stream};
+    c.plan_slices();
+    if (!c.slices.empty()) {
+        c.find_candidates("bunzip2 stream: scan");
+        c.upload_crc_tables();
+        c.start_walks();
+        uint64_t guess = 0;
+        for (const auto& fs : c.slices) guess += (fs.sc.cut - fs.sc.pos) * 5;
+        for (uint64_t k : c.kept) guess += k;
+        c.text.grow(std::max<uint64_t>(guess, 1u << 20), 0, c.s);
+    }
+    for (;;) {
+        const bool all = c.walk_chains();
+        if (!c.pend.empty()) c.invert_batch(c.pend);
+        else c.jobs.clear();
+        c.place_batch();
+        if (!c.pend.empty()) {
+            c.write_batch_text(c.text.text());
+            c.check_batch_crcs(c.text.text());
+        }
+        if (all) break;
+        c.decode_next_batch();
+    }
+    c.fill_handle();
+    c.commit();
+    t->buf = c.text.release();
+    SY_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint32_t f = 0; f < c.n_files(); f++) { st->prev_text[f] = t->text() + c.text_off[f]; st->prev_len[f] = c.text_off[f + 1] - c.text_off[f]; }
 }
 
 }  // namespace
@@ -780,6 +1043,83 @@ int sylph_bunzip2_files(sylph_ctx* ctx, const void* const* bz, const uint64_t* n
 
 int sylph_bunzip2(sylph_ctx* ctx, const void* bz, uint64_t n_bytes, int mem, sylph_inflated** out) {
     return sylph_bunzip2_files(ctx, &bz, &n_bytes, 1, mem, out);
+}
+
+int sylph_bunzip2_stream_open(sylph_ctx* ctx, const void* const* bz, const uint64_t* n_bytes, uint32_t n_files, int mem, uint64_t slice_bytes,
+                              sylph_bunzip2_stream** out) {
+    if (!ctx || !out || !bz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_files; i++) if (!bz[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_bunzip2_stream_open: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
+    *out = nullptr;
+    for (uint32_t i = 0; i < n_files; i++)
+        if (!bunzip2_plan::stream_level((const uint8_t*)bz[i], n_bytes[i], 0)) { set_error("sylph_bunzip2_stream_open: declined: file %u does not begin with a bzip2 stream header", i); return SYLPH_ERR_FORMAT; }
+    sylph_bunzip2_stream* st = nullptr;
+    const int rc = guarded([&] {
+        st = new sylph_bunzip2_stream();
+        st->ctx = ctx;
+        for (uint32_t i = 0; i < n_files; i++) { st->bz.push_back((const uint8_t*)bz[i]); st->n_bytes.push_back(n_bytes[i]); }
+        if (!slice_bytes) slice_bytes = ctx->bunzip2_slice_bytes ? ctx->bunzip2_slice_bytes : bunzip2_stream_plan::DEFAULT_SLICE;
+        st->slice_bytes = std::max<uint64_t>(slice_bytes, bunzip2_stream_plan::MIN_SLICE);
+        st->carry.assign(n_files, bunzip2_stream_plan::Carry{});
+        st->prev_text.assign(n_files, nullptr);
+        st->prev_len.assign(n_files, 0);
+    });
+    if (rc != SYLPH_OK) { delete st; return rc; }
+    ctx->refs.fetch_add(1);
+    *out = st;
+    return SYLPH_OK;
+}
+
+int sylph_bunzip2_stream_next(sylph_bunzip2_stream* st, const uint8_t* advance, const uint64_t* keep_from, sylph_inflated** window, uint8_t* finished) {
+    if (!st || !window) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    *window = nullptr;
+    if (st->dead) { set_error("sylph_bunzip2_stream_next: the stream was given up by an earlier call"); return SYLPH_ERR_FORMAT; }
+    sylph_ctx* ctx = st->ctx;
+    ctx->refs.fetch_add(1);
+    sylph_inflated* t = nullptr;
+    int format = 0;
+    const int rc = guarded([&] {
+        t = new sylph_inflated();
+        t->ctx = ctx;
+        try { stream_next_impl(st, t, advance, keep_from); }
+        catch (const FormatDecline& e) { set_error("sylph_bunzip2_stream_next: declined: %s", e.msg.c_str()); format = 1; }
+    });
+    if (rc != SYLPH_OK || format) {
+        st->dead = true;
+        {
+            std::lock_guard<std::mutex> lock(ctx->mu);
+            DeviceGuard dg(ctx->device);
+            (void)hipStreamSynchronize(ctx->stream);
+            if (t && t->buf) (void)hipFree(t->buf);
+            delete t;
+        }
+        ctx_unref(ctx);
+        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
+    }
+    if (finished) for (size_t i = 0; i < st->carry.size(); i++) finished[i] = st->carry[i].finished ? 1 : 0;
+    *window = t;
+    return SYLPH_OK;
+}
+
+int sylph_bunzip2_stream_info(const sylph_bunzip2_stream* st, uint64_t* n_slices, uint64_t* text_bytes, uint64_t* peak_scratch_bytes, uint64_t* peak_window_bytes) {
+    if (!st) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (n_slices) *n_slices = st->n_slices;
+    if (text_bytes) *text_bytes = st->text_bytes;
+    if (peak_scratch_bytes) *peak_scratch_bytes = st->peak_scratch;
+    if (peak_window_bytes) *peak_window_bytes = st->peak_window;
+    return SYLPH_OK;
+}
+
+void sylph_bunzip2_stream_destroy(sylph_bunzip2_stream* st) {
+    if (!st) return;
+    sylph_ctx* ctx = st->ctx;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        delete st;
+    }
+    ctx_unref(ctx);
 }
 
 }  // extern "C"

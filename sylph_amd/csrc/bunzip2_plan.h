@@ -7,7 +7,8 @@
 //   * every bit position of the file is tested for the block magic — the CANDIDATES, a superset of the true block starts (a false
 //     one turns up with odds 2^-48 per bit position);
 //   * one wavefront decodes each candidate and reports where its end-of-block symbol ended (BlockReport);
-//   * this file walks the chain over those reports (ChainWalk): the stream header -> the candidate at bit 32 -> the one where that
+//   * this file walks the chain over those reports (chain_step, one link at a time; ChainWalk is its whole-file use,
+//     bunzip2_stream_plan.h SliceWalk the resumable one): the stream header -> the candidate at bit 32 -> the one where that
 //     block ended -> ... -> the end-of-stream magic -> the combined CRC -> the next stream's header -> ...; a candidate that is not
 //     on the chain was never a block start;
 //   * the block CRCs (CRC-32 with polynomial 0x04C11DB7, MSB first: the non-reflected form, unlike gzip's) are put together from
@@ -128,26 +129,85 @@ inline int stream_level(const uint8_t* d, uint64_t n, uint64_t p) {
 }
 
 struct ChainBlock { uint32_t cand, file, stream; uint32_t n; };
-// Walks the chain one step at a time as candidates' reports come in (the device decodes them in batches, in bit order):
-// step() follows the chain while the report it needs is there; it stops in front of a candidate index >= `have` (wants()).
+
+// Where a file's chain stands: `bit` (of the FILE) is where the next block / end-of-stream magic starts (in_stream), or 8 x the byte of
+// the next stream header.  Everything a walk needs to go on from there, so it is also what the streamed decoder carries from one slice
+// to the next (bunzip2_stream_plan.h Carry).
+struct ChainPos {
+    uint64_t bit = 0;
+    bool in_stream = false;
+    int level = 0;               // in_stream: that stream's level ...
+    uint32_t combined = 0;       // ... and its combined CRC so far
+    uint64_t n_streams = 0;      // streams begun / blocks taken so far
+    uint64_t n_blocks = 0;
+};
+// what `find` of chain_step answers for the block magic at a bit of the file: the candidate there and its report (end_bit: of the FILE),
+// or HOLD: the walk waits in front of that block (its report is not in yet; the slice ends there)
+struct BlockAt {
+    enum What { HAVE, HOLD } what = HOLD;
+    size_t cand = 0;
+    const BlockReport* r = nullptr;
+    uint64_t end_bit = 0;
+};
+enum class Link { HEADER, TRAILER, BLOCK, HOLD, DECLINED };
+// ONE link of a file's chain, the only copy of it: a stream header, an end-of-stream trailer with its combined CRC, or a block whose
+// report `find(bit, why)` hands over.  Headers and trailers are read in d[0, fn), the host's copy of the file, which is whole.
+// DECLINED: `why` says what does not add up.  BLOCK: *got is the block taken.
+template <class Find>
+Link chain_step(const uint8_t* d, uint64_t fn, uint32_t file, ChainPos& p, Find&& find, std::string& why, BlockAt* got) {
+    const uint64_t lb = p.bit;
+    if (!p.in_stream) {
+        p.level = stream_level(d, fn, lb / 8);
+        if (!p.level) { why = "no bzip2 stream header at byte " + std::to_string(lb / 8) + " of file " + std::to_string(file); return Link::DECLINED; }
+        p.in_stream = true;
+        p.combined = 0;
+        p.bit += 32;
+        p.n_streams++;
+        return Link::HEADER;
+    }
+    const uint64_t m = bits_at(d, fn, lb, 48);
+    if (m == EOS_MAGIC) {
+        if (lb + 80 > fn * 8) { why = "end-of-stream trailer beyond the end of the file"; return Link::DECLINED; }
+        const uint32_t stored = (uint32_t)bits_at(d, fn, lb + 48, 32);
+        if (stored != p.combined) { why = "stream " + std::to_string(p.n_streams - 1) + ": combined CRC differs"; return Link::DECLINED; }
+        p.in_stream = false;
+        p.bit = (lb + 80 + 7) / 8 * 8;
+        return Link::TRAILER;
+    }
+    if (m != BLOCK_MAGIC) { why = "chain breaks at bit " + std::to_string(lb) + " of file " + std::to_string(file) + " (neither a block nor the end of the stream)"; return Link::DECLINED; }
+    const BlockAt at = find(lb, why);
+    if (!why.empty()) return Link::DECLINED;
+    if (at.what == BlockAt::HOLD) return Link::HOLD;
+    const BlockReport& r = *at.r;
+    if (r.status != ST_OK) { why = "block at bit " + std::to_string(lb) + ": decoder status " + std::to_string(r.status); return Link::DECLINED; }
+    if (r.randomised) { why = "block at bit " + std::to_string(lb) + " is randomised"; return Link::DECLINED; }
+    if (r.n > (uint32_t)p.level * 100000u) { why = "block at bit " + std::to_string(lb) + " is larger than the stream's level allows"; return Link::DECLINED; }
+    if (at.end_bit + 48 > fn * 8) { why = "block at bit " + std::to_string(lb) + " runs past the end of its file"; return Link::DECLINED; }
+    if (at.end_bit <= lb) { why = "block at bit " + std::to_string(lb) + " does not move on"; return Link::DECLINED; }
+    p.combined = combine_stream(p.combined, r.crc);
+    p.bit = at.end_bit;
+    p.n_blocks++;
+    *got = at;
+    return Link::BLOCK;
+}
+
+// The whole-file use of chain_step: the files of a call back to back in one buffer, one chain through all of them (file 1's blocks
+// come behind all of file 0's).  Walks one step at a time as candidates' reports come in (the device decodes them in batches, in bit
+// order): step() follows the chain while the report it needs is there; it stops in front of a candidate index >= `have`.
 struct ChainWalk {
     const Segments* S = nullptr;
-    const std::vector<uint64_t>* cand = nullptr;   // sorted candidate bits
+    const std::vector<uint64_t>* cand = nullptr;   // sorted candidate bits (of the buffer)
     std::vector<ChainBlock> blocks;
     uint32_t n_streams = 0;
     std::string why;                               // non-empty: declined, and why
     bool done = false;
-    // position
     uint32_t file = 0;
-    uint64_t bit = 0;                              // where the next block / end-of-stream magic starts (in_stream) or the next header byte * 8
-    bool in_stream = false;
-    int level = 0;
-    uint32_t combined = 0;
+    ChainPos pos;                                  // in `file`
     size_t next_cand = 0;                          // candidates before it lie behind the chain
 
     void start(const Segments* s, const std::vector<uint64_t>* c) {
         S = s; cand = c;
-        file = 0; bit = S->base[0] * 8; in_stream = false; done = false;
+        file = 0; pos = ChainPos{}; done = false;
         skip_empty_files();
     }
     void skip_empty_files() {        // (a file without a byte is no bzip2 file)
@@ -161,44 +221,29 @@ struct ChainWalk {
     // follow the chain; reports of candidates [0, have) are known.  Returns false when it stopped for a report it has not got.
     bool step(const BlockReport* rep, size_t have) {
         while (!done && why.empty()) {
-            const uint8_t* d = S->ptr[file];
-            const uint64_t fb = S->base[file], fn = S->base[file + 1] - fb;   // the file's bytes; `bit` counts in the whole buffer
-            const uint64_t lb = bit - fb * 8;
-            if (!in_stream) {
-                level = stream_level(d, fn, lb / 8);
-                if (!level) { why = "no bzip2 stream header at byte " + std::to_string(lb / 8) + " of file " + std::to_string(file); return true; }
-                in_stream = true;
-                combined = 0;
-                bit += 32;
-                n_streams++;
-                continue;
+            const uint64_t fb = S->base[file], fn = S->base[file + 1] - fb;   // the file's bytes; the candidates count bits of the whole buffer
+            BlockAt got;
+            const Link l = chain_step(S->ptr[file], fn, file, pos, [&](uint64_t lb, std::string& w) {
+                BlockAt at;
+                const size_t i = find(fb * 8 + lb);
+                if (i == SIZE_MAX) { w = "block magic at bit " + std::to_string(lb) + " is no candidate"; return at; }
+                if (i >= have) return at;
+                at.what = BlockAt::HAVE;
+                at.cand = i;
+                at.r = &rep[i];
+                at.end_bit = rep[i].end_bit - fb * 8;
+                return at;
+            }, why, &got);
+            n_streams = (uint32_t)pos.n_streams;
+            if (l == Link::DECLINED) return true;
+            if (l == Link::HOLD) return false;
+            if (l == Link::BLOCK) blocks.push_back(ChainBlock{(uint32_t)got.cand, file, n_streams - 1, got.r->n});
+            if (l == Link::TRAILER && pos.bit == fn * 8) {
+                file++;
+                pos.bit = 0;
+                if (file + 1 == S->base.size()) { done = true; return true; }
+                skip_empty_files();
             }
-            const uint64_t m = bits_at(d, fn, lb, 48);
-            if (m == EOS_MAGIC) {
-                if (lb + 80 > fn * 8) { why = "end-of-stream trailer beyond the end of the file"; return true; }
-                const uint32_t stored = (uint32_t)bits_at(d, fn, lb + 48, 32);
-                if (stored != combined) { why = "stream " + std::to_string(n_streams - 1) + ": combined CRC differs"; return true; }
-                in_stream = false;
-                bit = fb * 8 + (lb + 80 + 7) / 8 * 8;
-                if (bit == (fb + fn) * 8) {
-                    file++;
-                    if (file + 1 == S->base.size()) { done = true; return true; }
-                    skip_empty_files();
-                }
-                continue;
-            }
-            if (m != BLOCK_MAGIC) { why = "chain breaks at bit " + std::to_string(lb) + " of file " + std::to_string(file) + " (neither a block nor the end of the stream)"; return true; }
-            const size_t i = find(bit);
-            if (i == SIZE_MAX) { why = "block magic at bit " + std::to_string(lb) + " is no candidate"; return true; }
-            if (i >= have) return false;
-            const BlockReport& r = rep[i];
-            if (r.status != ST_OK) { why = "block at bit " + std::to_string(lb) + ": decoder status " + std::to_string(r.status); return true; }
-            if (r.randomised) { why = "block at bit " + std::to_string(lb) + " is randomised"; return true; }
-            if (r.n > (uint32_t)level * 100000u) { why = "block at bit " + std::to_string(lb) + " is larger than the stream's level allows"; return true; }
-            if (r.end_bit + 48 > (fb + fn) * 8) { why = "block at bit " + std::to_string(lb) + " runs past the end of its file"; return true; }
-            blocks.push_back(ChainBlock{(uint32_t)i, file, n_streams - 1, r.n});
-            combined = combine_stream(combined, r.crc);
-            bit = r.end_bit;
         }
         return true;
     }

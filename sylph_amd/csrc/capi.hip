@@ -446,6 +446,14 @@ int sylph_ctx_set_option(sylph_ctx* ctx, const char* key, const char* value) {
             const long long v = atoll(value);
             SY_REQUIRE(v >= 1 && (unsigned long long)v <= SYLPH_INFLATE_WHOLE_MAX_BYTES, "inflate_whole_max_bytes must be in [1, %llu]", (unsigned long long)SYLPH_INFLATE_WHOLE_MAX_BYTES);
             ctx->inflate_whole_max_bytes = (uint64_t)v;
+        } else if (!strcmp(key, "bunzip2_slice_bytes")) {
+            const long long v = atoll(value);
+            SY_REQUIRE(v == 0 || v >= (64ll << 10), "bunzip2_slice_bytes must be 0 (the default) or at least 65536");
+            ctx->bunzip2_slice_bytes = (uint64_t)v;
+        } else if (!strcmp(key, "bunzip2_whole_max_bytes")) {
+            const long long v = atoll(value);
+            SY_REQUIRE(v >= 0, "bunzip2_whole_max_bytes must be 0 (no limit, the default) or a number of bytes");
+            ctx->bunzip2_whole_max_bytes = v ? (uint64_t)v : ~0ull;
         } else if (!strcmp(key, "bootstrap_bins")) {
             const long v = atol(value);
             SY_REQUIRE(v >= 2 && v <= 64, "bootstrap_bins must be 2..64");

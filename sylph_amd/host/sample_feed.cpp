@@ -176,6 +176,8 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
 // error semantics are needletail's.
 // bzip2 on the device (csrc/bunzip2.hip), the same way: the compressed bytes travel, sylph_bunzip2_files decodes them there;
 // SYLPH_HIP_BUNZIP2_DEVICE=0 keeps the host's reader (libbz2 in FastxReader).  What the library declines goes the host way.
+// A gzip or bzip2 sample too large for one piece, or one the device has no room for in one piece, is STREAMED through the same decoder in
+// bounded memory (sketch_streamed below; SYLPH_HIP_INFLATE_STREAM / SYLPH_HIP_BUNZIP2_STREAM).
 // `decode`: the container the device decodes (SampleRoute: both mates are of it, device_decode_enabled says yes); Plain: text travels.
 namespace {
 struct MappedFile {                       // the compressed bytes of one file (read-only mapping of the page cache)
@@ -208,6 +210,7 @@ struct ReadIndex {
     ReadIndex& operator=(const ReadIndex&) = delete;
     ~ReadIndex() { sylph_fastq_destroy(q); sylph_fasta_destroy(a); }
     bool made() const { return q || a; }
+    void reset() { sylph_fastq_destroy(q); sylph_fasta_destroy(a); q = nullptr; a = nullptr; }
     const char* index_name() const { return fasta ? "sylph_fasta_index" : "sylph_fastq_index"; }
     const char* index_window_name() const { return fasta ? "sylph_fasta_index_window" : "sylph_fastq_index_window"; }
     const char* push_name() const { return fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq"; }
@@ -296,10 +299,36 @@ uint8_t first_byte_of(const std::string& file) {
     return c;
 }
 
-// SYLPH_HIP_INFLATE_STREAM: "auto" (default: the stream takes what the whole-file road declines for size or for room), "1" always, "0" never
+// The streamed decoder of a container (csrc/inflate.hip sylph_inflate_stream_*, csrc/bunzip2.hip sylph_bunzip2_stream_*) behind one set of
+// calls, as ReadIndex holds the two indexes: the stream route is written once.  mode_env: "auto" (default: the stream takes what the
+// whole-file road declines for size or for room), "1" always, "0" never; whole_max_env lowers the bytes (both mates together) from which
+// the whole-file road is not tried (the tests); slice_env sets the slice.
+struct StreamDecoder {
+    const char *container, *verb, *whole_name, *open_name, *next_name, *mode_env, *whole_max_env, *slice_env;
+    uint64_t whole_max;                              // of the whole-file road itself
+    int (*whole)(sylph_ctx*, const void* const*, const uint64_t*, uint32_t, int, sylph_inflated**);
+    int (*open)(sylph_ctx*, const void* const*, const uint64_t*, uint32_t, int, uint64_t, void**);
+    int (*next)(void*, const uint8_t*, const uint64_t*, sylph_inflated**, uint8_t*);
+    int (*info)(const void*, uint64_t*, uint64_t*, uint64_t*, uint64_t*);
+    void (*destroy)(void*);
+};
+const StreamDecoder GZIP_STREAM{
+    "gzip", "inflated", "sylph_inflate_files", "sylph_inflate_stream_open", "sylph_inflate_stream_next", "SYLPH_HIP_INFLATE_STREAM", "SYLPH_HIP_INFLATE_WHOLE_MAX", "SYLPH_HIP_INFLATE_SLICE",
+    SYLPH_INFLATE_WHOLE_MAX_BYTES, sylph_inflate_files,
+    [](sylph_ctx* c, const void* const* p, const uint64_t* n, uint32_t f, int mem, uint64_t slice, void** out) { return sylph_inflate_stream_open(c, p, n, f, mem, slice, (sylph_inflate_stream**)out); },
+    [](void* h, const uint8_t* adv, const uint64_t* keep, sylph_inflated** w, uint8_t* fin) { return sylph_inflate_stream_next((sylph_inflate_stream*)h, adv, keep, w, fin); },
+    [](const void* h, uint64_t* a, uint64_t* b, uint64_t* c, uint64_t* d) { return sylph_inflate_stream_info((const sylph_inflate_stream*)h, a, b, c, d); },
+    [](void* h) { sylph_inflate_stream_destroy((sylph_inflate_stream*)h); }};
+const StreamDecoder BZIP2_STREAM{
+    "bzip2", "decoded", "sylph_bunzip2_files", "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "SYLPH_HIP_BUNZIP2_STREAM", "SYLPH_HIP_BUNZIP2_WHOLE_MAX", "SYLPH_HIP_BUNZIP2_SLICE",
+    ~0ull, sylph_bunzip2_files,
+    [](sylph_ctx* c, const void* const* p, const uint64_t* n, uint32_t f, int mem, uint64_t slice, void** out) { return sylph_bunzip2_stream_open(c, p, n, f, mem, slice, (sylph_bunzip2_stream**)out); },
+    [](void* h, const uint8_t* adv, const uint64_t* keep, sylph_inflated** w, uint8_t* fin) { return sylph_bunzip2_stream_next((sylph_bunzip2_stream*)h, adv, keep, w, fin); },
+    [](const void* h, uint64_t* a, uint64_t* b, uint64_t* c, uint64_t* d) { return sylph_bunzip2_stream_info((const sylph_bunzip2_stream*)h, a, b, c, d); },
+    [](void* h) { sylph_bunzip2_stream_destroy((sylph_bunzip2_stream*)h); }};
 enum class StreamMode { Auto, Always, Never };
-StreamMode stream_mode() {
-    const char* e = getenv("SYLPH_HIP_INFLATE_STREAM");
+StreamMode stream_mode(const StreamDecoder& d) {
+    const char* e = getenv(d.mode_env);
     if (!e || !*e || !strcmp(e, "auto")) return StreamMode::Auto;
     return atoi(e) != 0 ? StreamMode::Always : StreamMode::Never;
 }
@@ -309,10 +338,10 @@ uint64_t env_bytes(const char* name, uint64_t otherwise) {
     const unsigned long long v = strtoull(e, nullptr, 10);
     return v ? (uint64_t)v : otherwise;
 }
-// gzip bytes (both mates together) from which sylph_inflate_files declines (SYLPH_HIP_INFLATE_WHOLE_MAX lowers it: the tests)
-uint64_t inflate_whole_max() { return std::min<uint64_t>(env_bytes("SYLPH_HIP_INFLATE_WHOLE_MAX", SYLPH_INFLATE_WHOLE_MAX_BYTES), SYLPH_INFLATE_WHOLE_MAX_BYTES); }
+// compressed bytes (both mates together) from which the whole-file road declines
+uint64_t whole_max(const StreamDecoder& d) { return std::min<uint64_t>(env_bytes(d.whole_max_env, d.whole_max), d.whole_max); }
 
-// The stream route for gzip samples (csrc/inflate.hip sylph_inflate_stream_*): the compressed bytes go to the device one slice per mate
+// The stream route for gzip and bzip2 samples (StreamDecoder): the compressed bytes go to the device one slice per mate
 // at a time, the records of every window are found there and pushed, and what a window holds beyond its last pushed record is kept for
 // the next one — memory is a function of the slice, not of the sample (the reference streams records in O(batch) memory too:
 // sketch.rs:780-781, :806-815, :906).  Per step: next; index each mate's window (final = the file's finished flag; the FASTQ or the FASTA index, by the first byte of the mate's text); push
@@ -321,13 +350,13 @@ uint64_t inflate_whole_max() { return std::min<uint64_t>(env_bytes("SYLPH_HIP_IN
 // dropped at the end (lock-step readers, sketch.rs:813-815); the running mean of the mate-1 lengths is the same f64 recurrence in
 // file order, continued across windows.  false: declined at some step (the session is the caller's to drop: the host feed takes the
 // sample from its start).
-bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::vector<const void*>& ptrs, const std::vector<uint64_t>& lens,
-                          const char* name, double& mean_read_length) {
+bool sketch_streamed(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const std::vector<const void*>& ptrs,
+                     const std::vector<uint64_t>& lens, const char* name, double& mean_read_length) {
     const bool trace = FeedLaps::on();
     FeedLaps laps;
     sylph_ctx* ctx = e.context();
     const uint32_t F = (uint32_t)ptrs.size();
-    struct Stream { sylph_inflate_stream* h = nullptr; ~Stream() { sylph_inflate_stream_destroy(h); } } st;
+    struct Stream { const StreamDecoder& d; void* h = nullptr; ~Stream() { d.destroy(h); } } st{dec};
     auto declined = [&](int rc, const char* what) {
         if (rc != SYLPH_ERR_FORMAT && rc != SYLPH_ERR_NOMEM) hip_check(rc, what);
         if (trace) fprintf(stderr, "[sylph_hip feed] stream route declined %s at %s: %s\n", name, what, sylph_last_error());
@@ -337,8 +366,8 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
         if (trace) fprintf(stderr, "[sylph_hip feed] stream route declined %s: %s\n", name, why);
         return false;
     };
-    int rc = sylph_inflate_stream_open(ctx, ptrs.data(), lens.data(), F, SYLPH_MEM_HOST, env_bytes("SYLPH_HIP_INFLATE_SLICE", 0), &st.h);
-    if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_open");
+    int rc = dec.open(ctx, ptrs.data(), lens.data(), F, SYLPH_MEM_HOST, env_bytes(dec.slice_env, 0), &st.h);
+    if (rc != SYLPH_OK) return declined(rc, dec.open_name);
     sylph_sketch* const sk = open_session();
     e.batch.flush(sk);
     std::unique_ptr<InflatedText> prev;                        // the window of the step before: its kept tail is copied out of it by `next`
@@ -350,8 +379,8 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
     std::vector<int> kind(F, -1);                              // 1: the mate's text is FASTA, 0: it is not, -1: no byte of it seen yet
     for (bool first = true;; first = false) {
         std::unique_ptr<InflatedText> win(new InflatedText());
-        rc = sylph_inflate_stream_next(st.h, advance.data(), first ? nullptr : keep.data(), &win->h, finished.data());
-        if (rc != SYLPH_OK) return declined(rc, "sylph_inflate_stream_next");
+        rc = dec.next(st.h, advance.data(), first ? nullptr : keep.data(), &win->h, finished.data());
+        if (rc != SYLPH_OK) return declined(rc, dec.next_name);
         prev.reset();                                          // (its indexes went with the previous step's scope)
         std::vector<ReadIndex> fq(F);
         std::vector<uint64_t> n_rec(F, 0), bytes(F, 0), bases(F, 0);
@@ -399,11 +428,11 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
         prev = std::move(win);
     }
     uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
-    hip_check(sylph_inflate_stream_info(st.h, &n_slices, &text_bytes, &peak_scratch, &peak_window), "sylph_inflate_stream_info");
+    hip_check(dec.info(st.h, &n_slices, &text_bytes, &peak_scratch, &peak_window), "stream info");
     if (trace) {
         char what[192];
-        snprintf(what, sizeof(what), "stream route: gzip inflated on the device in %llu slices (%llu %s records, %llu text bytes, peak scratch %llu, peak window %llu)",
-                 (unsigned long long)n_slices, (unsigned long long)pairs, kind[0] > 0 ? "FASTA" : "FASTQ", (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
+        snprintf(what, sizeof(what), "stream route: %s %s on the device in %llu slices (%llu %s records, %llu text bytes, peak scratch %llu, peak window %llu)",
+                 dec.container, dec.verb, (unsigned long long)n_slices, (unsigned long long)pairs, kind[0] > 0 ? "FASTA" : "FASTQ", (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
         laps.lap(what);
     }
     mean_read_length = mean;
@@ -412,46 +441,55 @@ bool sketch_gzip_streamed(Engine& e, const std::function<sylph_sketch*()>& open_
 }  // namespace
 
 // The texts of a sample whose compressed files the device decodes, both mates in ONE call (sylph_inflate_files / sylph_bunzip2_files:
-// one scan, one decode launch, one chain — the mates share a block's latency).  gzip: the whole-file road, or — when asked, for what
-// that road declines for size or for room, and for a FASTA text too long for one index — the stream (sketch_gzip_streamed).
+// one scan, one decode launch, one chain — the mates share a block's latency): the whole-file road, or — when asked, for what that
+// road declines for size or for room, and for a FASTA text too long for one index — the stream (sketch_streamed).
 enum class Decoded { OnDevice, Streamed, Declined };      // the texts lie on the device / the sample is sketched already / the host feed's
 struct RouteTexts {
+    std::vector<std::unique_ptr<MappedFile>> maps;   // the compressed files, for as long as a stream may still want them
+    std::vector<const void*> ptrs;
+    std::vector<uint64_t> lens;
     InflatedText owner;                              // of decoded texts (destroyed behind the indexes that borrow them: declared before them)
     std::vector<TextUploader::Text> texts;
     std::vector<uint8_t> heads;                      // the first byte of every mate's TEXT: '@' FASTQ, '>' FASTA
 };
-Decoded decode_on_device(Engine& e, const std::function<sylph_sketch*()>& open_session, const std::vector<std::string>& files, bool gz, FeedLaps& laps,
+bool stream_sample(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const RouteTexts& t, const char* name, FeedLaps& laps,
+                   double& mean_read_length) {
+    if (!sketch_streamed(e, dec, open_session, t.ptrs, t.lens, name, mean_read_length)) return false;
+    laps.lap(&dec == &GZIP_STREAM ? "device route: gzip streamed through the device inflate" : "device route: bzip2 streamed through the device decoder");
+    return true;
+}
+Decoded decode_on_device(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const std::vector<std::string>& files, FeedLaps& laps,
                          RouteTexts& out, double& mean_read_length) {
     const bool trace = FeedLaps::on();
+    const bool gz = &dec == &GZIP_STREAM;
     const char* name = files[0].c_str();
-    std::vector<std::unique_ptr<MappedFile>> maps;
-    std::vector<const void*> ptrs;
-    std::vector<uint64_t> lens;
+    std::vector<const void*>& ptrs = out.ptrs;
+    std::vector<uint64_t>& lens = out.lens;
     uint64_t packed_bytes = 0;
     for (const auto& f : files) {
-        maps.emplace_back(new MappedFile(f));
-        if (!maps.back()->data) return Decoded::Declined;
-        ptrs.push_back(maps.back()->data);
-        lens.push_back(maps.back()->size);
-        packed_bytes += maps.back()->size;
+        out.maps.emplace_back(new MappedFile(f));
+        if (!out.maps.back()->data) return Decoded::Declined;
+        ptrs.push_back(out.maps.back()->data);
+        lens.push_back(out.maps.back()->size);
+        packed_bytes += out.maps.back()->size;
     }
-    const bool may_stream = gz && stream_mode() == StreamMode::Auto;
-    const bool too_large = gz && packed_bytes >= inflate_whole_max();
-    bool streamed = gz && (stream_mode() == StreamMode::Always || (may_stream && too_large));
+    const bool may_stream = stream_mode(dec) == StreamMode::Auto;
+    const bool too_large = packed_bytes >= whole_max(dec);
+    bool streamed = stream_mode(dec) == StreamMode::Always || (may_stream && too_large);
     if (!streamed && too_large) {
-        if (trace) fprintf(stderr, "[sylph_hip feed] device inflate declined %s: %llu gzip bytes, and the stream is off\n", name, (unsigned long long)packed_bytes);
+        if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %llu %s bytes, and the stream is off\n", gz ? "inflate" : "bunzip2", name,
+                           (unsigned long long)packed_bytes, dec.container);
         return Decoded::Declined;
     }
     if (!streamed) {
-        const int rc = gz ? sylph_inflate_files(e.context(), ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &out.owner.h)
-                          : sylph_bunzip2_files(e.context(), ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &out.owner.h);
+        const int rc = dec.whole(e.context(), ptrs.data(), lens.data(), (uint32_t)ptrs.size(), SYLPH_MEM_HOST, &out.owner.h);
         if (rc == SYLPH_ERR_NOMEM && may_stream) {
-            if (trace) fprintf(stderr, "[sylph_hip feed] device inflate has no room for %s in one piece (%s): the stream takes it\n", name, sylph_last_error());
+            if (trace) fprintf(stderr, "[sylph_hip feed] device %s has no room for %s in one piece (%s): the stream takes it\n", gz ? "inflate" : "bunzip2", name, sylph_last_error());
             streamed = true;
         } else if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
             if (trace) fprintf(stderr, "[sylph_hip feed] device %s declined %s: %s\n", gz ? "inflate" : "bunzip2", name, sylph_last_error());
             return Decoded::Declined;
-        } else hip_check(rc, gz ? "sylph_inflate_files" : "sylph_bunzip2_files");
+        } else hip_check(rc, dec.whole_name);
     }
     if (!streamed) {
         bool fasta_too_long = false;
@@ -465,7 +503,7 @@ Decoded decode_on_device(Engine& e, const std::function<sylph_sketch*()>& open_s
             fasta_too_long = fasta_too_long || (out.heads[i] == '>' && bytes >= FASTA_INDEX_MAX_TEXT);
         }
         laps.lap(gz ? "device route: gzip inflated on the device" : "device route: bzip2 decoded on the device");
-        // a gzip FASTA text too long for one FASTA index: the stream's windows are smaller
+        // a FASTA text too long for one FASTA index: the stream's windows are smaller
         if (may_stream && fasta_too_long && same_kind(out.heads) && fasta_reads_on_device()) {
             if (trace) fprintf(stderr, "[sylph_hip feed] device route: a FASTA text of %s is too long for one index: the stream takes it\n", name);
             out.texts.clear();
@@ -475,9 +513,7 @@ Decoded decode_on_device(Engine& e, const std::function<sylph_sketch*()>& open_s
         }
     }
     if (!streamed) return Decoded::OnDevice;
-    if (!sketch_gzip_streamed(e, open_session, ptrs, lens, name, mean_read_length)) return Decoded::Declined;
-    laps.lap("device route: gzip streamed through the device inflate");
-    return Decoded::Streamed;
+    return stream_sample(e, dec, open_session, out, name, laps, mean_read_length) ? Decoded::Streamed : Decoded::Declined;
 }
 
 // obtain the texts, decide the kind once, index, push
@@ -508,9 +544,12 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     // against 0.30 s for its first mate alone (profiles/r05_feed_device_route.txt)
     if (text && !e.text.warm() && text->a->size + (f2 ? text->b->size : 0) < (1500ull << 20)) return false;
     if (decoded) {
-        const Decoded got = decode_on_device(e, open_session, files, decode == Container::Gzip, laps, t, mean_read_length);
+        const Decoded got = decode_on_device(e, decode == Container::Gzip ? GZIP_STREAM : BZIP2_STREAM, open_session, files, laps, t, mean_read_length);
         if (got != Decoded::OnDevice) return got == Decoded::Streamed;
     }
+    // a bzip2 sample whose text is there in one piece and then has no room — or is too large — to be indexed or pushed in one piece: the
+    // stream takes it from its start (its windows are smaller), unless it is off
+    const bool stream_after_all = decoded && decode == Container::Bzip2 && stream_mode(BZIP2_STREAM) == StreamMode::Auto;
     // FASTA reads that stay on the host reader, mates of different kinds: declined — for host text and plain files, before anything travels
     auto declined = [&](const char* why) {
         if (trace) fprintf(stderr, "[sylph_hip feed] device route declined %s: %s\n", files[0].c_str(), why);
@@ -525,13 +564,27 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     }
     ReadIndex fa, fb;
     fa.fasta = fb.fasta = fasta;
+    bool to_stream = false;
+    auto streamed_instead = [&](const char* what) {
+        if (trace) fprintf(stderr, "[sylph_hip feed] device route: %s of %s in one piece (%s): the stream takes it\n", what, files[0].c_str(), sylph_last_error());
+        fa.reset();                                  // (the indexes borrow the text: they go first)
+        fb.reset();
+        t.texts.clear();
+        sylph_inflated_destroy(t.owner.h);
+        t.owner.h = nullptr;
+        return stream_sample(e, BZIP2_STREAM, open_session, t, files[0].c_str(), laps, mean_read_length);
+    };
     auto index = [&](const TextUploader::Text& x, ReadIndex& out) {
         const int rc = out.index(ctx, x.dev, x.bytes);
-        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) return fasta ? declined(sylph_last_error()) : false;   // not for this route / no room for it: the host feed
+        if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
+            // no room for the index, or more text than one index holds
+            to_stream = stream_after_all && (rc == SYLPH_ERR_NOMEM || strstr(sylph_last_error(), "per index") != nullptr);
+            return fasta && !to_stream ? declined(sylph_last_error()) : false;   // not for this route / no room for it: the host feed
+        }
         hip_check(rc, out.index_name());
         return true;
     };
-    if (!index(t.texts[0], fa) || (f2 && !index(t.texts[1], fb))) return false;
+    if (!index(t.texts[0], fa) || (f2 && !index(t.texts[1], fb))) return to_stream ? streamed_instead("no index") : false;
     uint64_t na = 0, nb = 0, bases_a = 0, bases_b = 0;
     fa.counts(na, bases_a);
     if (f2) fb.counts(nb, bases_b);
@@ -555,7 +608,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             // works through a sample in 256 Mbp batches, takes the sample from its start; the caller opens a fresh session
             if (trace) fprintf(stderr, "[sylph_hip feed] device route: no room for the batch (%s): the host feed takes the sample\n", sylph_last_error());
             tm.join();
-            return false;
+            return stream_after_all ? streamed_instead("no room for the push") : false;
         }
         hip_check(rc, fa.push_name());
     }
