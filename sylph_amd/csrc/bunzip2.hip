@@ -36,18 +36,11 @@
 #include "bunzip2_stream_plan.h"
 #include "decode_host.h"
 
-// What a stream holds between two calls: every file's carry, and where the window it handed out last lies (the caller keeps that alive
-// for the next call: its kept tail is copied from there).  A bzip2 block needs nothing of the text in front of it.
-struct sylph_bunzip2_stream {
-    sylph_ctx* ctx = nullptr;
-    std::vector<const uint8_t*> bz;
-    std::vector<uint64_t> n_bytes;
-    uint64_t slice_bytes = 0;
-    std::vector<sylph::bunzip2_stream_plan::Carry> carry;
-    std::vector<const uint8_t*> prev_text;        // file i's text in the window handed out last
-    std::vector<uint64_t> prev_len;
-    bool dead = false;
-    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+// What a stream holds between two calls beside decode_host.h's StreamBase: every file's carry.  A bzip2 block needs nothing of the text
+// in front of it.
+struct sylph_bunzip2_stream : sylph::decode_host::StreamBase {
+    using StreamBase::StreamBase;
+    std::vector<sylph::bunzip2_stream_plan::Carry> carry = std::vector<sylph::bunzip2_stream_plan::Carry>(files.size());
 };
 
 namespace sylph {
@@ -856,7 +849,6 @@ void bunzip2_impl(sylph_inflated* t, const void* const* bzs, const uint64_t* n_b
 // the stream: the same phases over one slice per advancing file (bookkeeping: bunzip2_stream_plan.h)
 // =================================================================================================================================
 using namespace bunzip2_stream_plan;
-constexpr uint64_t SLICE_ALIGN = 256;               // a file's slice begins at a multiple of this in the upload (zero bytes between them)
 
 struct StreamCall : Bunzip2Phases {
     sylph_bunzip2_stream* st;
@@ -879,23 +871,18 @@ struct StreamCall : Bunzip2Phases {
     StreamCall(sylph_bunzip2_stream* st_, sylph_inflated* t_, const uint8_t* adv, const uint64_t* keep)
         : Bunzip2Phases(st_->ctx), st(st_), t(t_), advance(adv), keep_from(keep) {}
 
-    uint32_t n_files() const { return (uint32_t)st->bz.size(); }
+    uint32_t n_files() const { return st->n_files(); }
 
     void plan_slices() {
         const uint32_t F = n_files();
-        kept.assign(F, 0);
+        kept = kept_tails(st, keep_from, "sylph_bunzip2_stream");
         text_off.assign(F + 1, 0);
         slice_of_file.assign(F, -1);
         uint64_t at = 0;
         for (uint32_t f = 0; f < F; f++) {
-            if (keep_from) {
-                SY_REQUIRE(keep_from[f] <= st->prev_len[f], "sylph_bunzip2_stream_next: keep_from[%u] = %llu lies behind the previous window (%llu bytes)", f,
-                           (unsigned long long)keep_from[f], (unsigned long long)st->prev_len[f]);
-                kept[f] = st->prev_len[f] - keep_from[f];
-            }
             if ((advance && !advance[f]) || st->carry[f].finished) continue;
             const SliceCut sc = slice_cut(st->carry[f], st->n_bytes[f], st->slice_bytes);
-            at = (at + SLICE_ALIGN - 1) / SLICE_ALIGN * SLICE_ALIGN;
+            at = slice_begin(at);
             slice_of_file[f] = (int)slices.size();
             slices.push_back(FileSlice{f, sc, at});
             at += sc.end - sc.pos;
@@ -905,7 +892,7 @@ struct StreamCall : Bunzip2Phases {
         SY_HIP(hipMemsetAsync(in, 0, n_words * 4 + PAD_BYTES, s));
         lim.clear();
         for (const FileSlice& fs : slices) {
-            if (fs.sc.end > fs.sc.pos) ctx->h2d(in + fs.off, st->bz[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
+            if (fs.sc.end > fs.sc.pos) ctx->h2d(in + fs.off, st->files[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
             // (a block that starts at or behind the cut is the next slice's: it is neither looked for nor decoded here)
             const uint64_t starts = fs.sc.cut < st->n_bytes[fs.file] ? fs.sc.cut : fs.sc.end;
             lim.push_back(SliceBits{fs.off * 8, (fs.off + (starts - fs.sc.pos)) * 8, (fs.off + (fs.sc.end - fs.sc.pos)) * 8});
@@ -922,7 +909,7 @@ struct StreamCall : Bunzip2Phases {
             fs.cand_lo = (size_t)(std::lower_bound(cand.begin(), cand.end(), lim[si].begin_bit) - cand.begin());
             fs.cand_hi = (size_t)(std::lower_bound(cand.begin(), cand.end(), lim[si].end_bit) - cand.begin());
             for (size_t i = fs.cand_lo; i < fs.cand_hi; i++) cand_bits[si].push_back((uint64_t)((int64_t)cand[i] + shift));
-            walks[si].start(st->bz[fs.file], st->n_bytes[fs.file], fs.file, st->carry[fs.file], fs.sc, &cand_bits[si], shift);
+            walks[si].start(st->files[fs.file], st->n_bytes[fs.file], fs.file, st->carry[fs.file], fs.sc, &cand_bits[si], shift);
         }
     }
 
@@ -1027,7 +1014,7 @@ void stream_next_impl(sylph_bunzip2_stream* st, sylph_inflated* t, const uint8_t
     c.commit();
     t->buf = c.text.release();
     SY_HIP(hipStreamSynchronize(ctx->stream));
-    for (uint32_t f = 0; f < c.n_files(); f++) { st->prev_text[f] = t->text() + c.text_off[f]; st->prev_len[f] = c.text_off[f + 1] - c.text_off[f]; }
+    remember_window(st, t, c.text_off);
 }
 
 }  // namespace
@@ -1047,22 +1034,13 @@ int sylph_bunzip2(sylph_ctx* ctx, const void* bz, uint64_t n_bytes, int mem, syl
 
 int sylph_bunzip2_stream_open(sylph_ctx* ctx, const void* const* bz, const uint64_t* n_bytes, uint32_t n_files, int mem, uint64_t slice_bytes,
                               sylph_bunzip2_stream** out) {
-    if (!ctx || !out || !bz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    for (uint32_t i = 0; i < n_files; i++) if (!bz[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_bunzip2_stream_open: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
-    *out = nullptr;
+    if (const int rc = stream_open_args("sylph_bunzip2_stream", ctx, bz, n_bytes, n_files, mem, out)) return rc;
     for (uint32_t i = 0; i < n_files; i++)
         if (!bunzip2_plan::stream_level((const uint8_t*)bz[i], n_bytes[i], 0)) { set_error("sylph_bunzip2_stream_open: declined: file %u does not begin with a bzip2 stream header", i); return SYLPH_ERR_FORMAT; }
     sylph_bunzip2_stream* st = nullptr;
     const int rc = guarded([&] {
-        st = new sylph_bunzip2_stream();
-        st->ctx = ctx;
-        for (uint32_t i = 0; i < n_files; i++) { st->bz.push_back((const uint8_t*)bz[i]); st->n_bytes.push_back(n_bytes[i]); }
         if (!slice_bytes) slice_bytes = ctx->bunzip2_slice_bytes ? ctx->bunzip2_slice_bytes : bunzip2_stream_plan::DEFAULT_SLICE;
-        st->slice_bytes = std::max<uint64_t>(slice_bytes, bunzip2_stream_plan::MIN_SLICE);
-        st->carry.assign(n_files, bunzip2_stream_plan::Carry{});
-        st->prev_text.assign(n_files, nullptr);
-        st->prev_len.assign(n_files, 0);
+        st = new sylph_bunzip2_stream(ctx, bz, n_bytes, n_files, std::max<uint64_t>(slice_bytes, bunzip2_stream_plan::MIN_SLICE));
     });
     if (rc != SYLPH_OK) { delete st; return rc; }
     ctx->refs.fetch_add(1);
@@ -1071,55 +1049,15 @@ int sylph_bunzip2_stream_open(sylph_ctx* ctx, const void* const* bz, const uint6
 }
 
 int sylph_bunzip2_stream_next(sylph_bunzip2_stream* st, const uint8_t* advance, const uint64_t* keep_from, sylph_inflated** window, uint8_t* finished) {
-    if (!st || !window) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    *window = nullptr;
-    if (st->dead) { set_error("sylph_bunzip2_stream_next: the stream was given up by an earlier call"); return SYLPH_ERR_FORMAT; }
-    sylph_ctx* ctx = st->ctx;
-    ctx->refs.fetch_add(1);
-    sylph_inflated* t = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        t = new sylph_inflated();
-        t->ctx = ctx;
-        try { stream_next_impl(st, t, advance, keep_from); }
-        catch (const FormatDecline& e) { set_error("sylph_bunzip2_stream_next: declined: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        st->dead = true;
-        {
-            std::lock_guard<std::mutex> lock(ctx->mu);
-            DeviceGuard dg(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-            if (t && t->buf) (void)hipFree(t->buf);
-            delete t;
-        }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    if (finished) for (size_t i = 0; i < st->carry.size(); i++) finished[i] = st->carry[i].finished ? 1 : 0;
-    *window = t;
-    return SYLPH_OK;
+    return stream_next_entry("sylph_bunzip2_stream", st, advance, keep_from, window, finished, stream_next_impl);
 }
 
 int sylph_bunzip2_stream_info(const sylph_bunzip2_stream* st, uint64_t* n_slices, uint64_t* text_bytes, uint64_t* peak_scratch_bytes, uint64_t* peak_window_bytes) {
-    if (!st) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (n_slices) *n_slices = st->n_slices;
-    if (text_bytes) *text_bytes = st->text_bytes;
-    if (peak_scratch_bytes) *peak_scratch_bytes = st->peak_scratch;
-    if (peak_window_bytes) *peak_window_bytes = st->peak_window;
-    return SYLPH_OK;
+    return stream_info(st, n_slices, text_bytes, peak_scratch_bytes, peak_window_bytes);
 }
 
 void sylph_bunzip2_stream_destroy(sylph_bunzip2_stream* st) {
-    if (!st) return;
-    sylph_ctx* ctx = st->ctx;
-    {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-        delete st;
-    }
-    ctx_unref(ctx);
+    stream_destroy(st, [](sylph_bunzip2_stream*) {});
 }
 
 }  // extern "C"

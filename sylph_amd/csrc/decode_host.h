@@ -1,5 +1,6 @@
 // decode_host.h — the host scaffold of the two device decompressors (inflate.hip, bunzip2.hip): how a call enters and fails, how the
-// compressed files reach the device, how the candidates come back, and the buffer of the text a call returns.
+// compressed files reach the device, how the candidates come back, the buffer of the text a call returns, and what the two streams'
+// handles and entries have in common.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -51,6 +52,115 @@ inline int decode_entry(const char* name, bool allow_null_empty, sylph_ctx* ctx,
     }
     *out = t;
     return SYLPH_OK;
+}
+
+// ---- the streams (sylph_inflate_stream_* / sylph_bunzip2_stream_*) -------------------------------------------------------------------
+// What a stream of either format holds between two calls, beside its files' carries: where the window it handed out last lies (the
+// caller keeps that alive for the next call: its kept tail is copied from there), and its counts.  The handles derive from it.
+struct StreamBase {
+    sylph_ctx* ctx = nullptr;
+    std::vector<const uint8_t*> files;             // the compressed files (the caller's memory)
+    std::vector<uint64_t> n_bytes;
+    uint64_t slice_bytes = 0;
+    std::vector<const uint8_t*> prev_text;         // file i's text in the window handed out last
+    std::vector<uint64_t> prev_len;
+    bool dead = false;
+    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+    StreamBase(sylph_ctx* c, const void* const* ptrs, const uint64_t* nb, uint32_t n_files, uint64_t slice)
+        : ctx(c), n_bytes(nb, nb + n_files), slice_bytes(slice), prev_text(n_files, nullptr), prev_len(n_files, 0) {
+        for (uint32_t i = 0; i < n_files; i++) files.push_back((const uint8_t*)ptrs[i]);
+    }
+    uint32_t n_files() const { return (uint32_t)files.size(); }
+};
+
+// the argument checks of <name>_open; the format check and the construction are the decoder's
+template <class Stream>
+int stream_open_args(const char* name, sylph_ctx* ctx, const void* const* ptrs, const uint64_t* n_bytes, uint32_t n_files, int mem, Stream** out) {
+    if (!ctx || !out || !ptrs || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    for (uint32_t i = 0; i < n_files; i++) if (!ptrs[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("%s_open: the compressed bytes must lie in host memory (mem kind %d)", name, mem); return SYLPH_ERR_INVALID; }
+    *out = nullptr;
+    return SYLPH_OK;
+}
+
+// The body of <name>_next.  impl fills the window's handle (and takes the context's lock itself); whatever it throws, the stream is
+// given up (every later call is declined), the device stream is idle and the half-built window and the reference on the context
+// are given back before this returns.  Stream: a StreamBase with the files' `carry`, whose entries say `finished`.
+template <class Stream>
+int stream_next_entry(const char* name, Stream* st, const uint8_t* advance, const uint64_t* keep_from, sylph_inflated** window, uint8_t* finished,
+                      void (*impl)(Stream* st, sylph_inflated* t, const uint8_t* advance, const uint64_t* keep_from)) {
+    if (!st || !window) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    *window = nullptr;
+    if (st->dead) { set_error("%s_next: the stream was given up by an earlier call", name); return SYLPH_ERR_FORMAT; }
+    sylph_ctx* ctx = st->ctx;
+    ctx->refs.fetch_add(1);
+    sylph_inflated* t = nullptr;
+    int format = 0;
+    const int rc = guarded([&] {
+        t = new sylph_inflated();
+        t->ctx = ctx;
+        try { impl(st, t, advance, keep_from); }
+        catch (const FormatDecline& e) { set_error("%s_next: declined: %s", name, e.msg.c_str()); format = 1; }
+    });
+    if (rc != SYLPH_OK || format) {
+        st->dead = true;
+        {
+            std::lock_guard<std::mutex> lock(ctx->mu);
+            DeviceGuard dg(ctx->device);
+            (void)hipStreamSynchronize(ctx->stream);
+            if (t && t->buf) (void)hipFree(t->buf);
+            delete t;
+        }
+        ctx_unref(ctx);
+        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
+    }
+    if (finished) for (size_t i = 0; i < st->carry.size(); i++) finished[i] = st->carry[i].finished ? 1 : 0;
+    *window = t;
+    return SYLPH_OK;
+}
+
+inline int stream_info(const StreamBase* st, uint64_t* n_slices, uint64_t* text_bytes, uint64_t* peak_scratch_bytes, uint64_t* peak_window_bytes) {
+    if (!st) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (n_slices) *n_slices = st->n_slices;
+    if (text_bytes) *text_bytes = st->text_bytes;
+    if (peak_scratch_bytes) *peak_scratch_bytes = st->peak_scratch;
+    if (peak_window_bytes) *peak_window_bytes = st->peak_window;
+    return SYLPH_OK;
+}
+
+// free_extra(st): the device memory that is the decoder's own, under the context's lock and with the stream idle
+template <class Stream, class FreeExtra>
+void stream_destroy(Stream* st, FreeExtra free_extra) {
+    if (!st) return;
+    sylph_ctx* ctx = st->ctx;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard dg(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+        free_extra(st);
+        delete st;
+    }
+    ctx_unref(ctx);
+}
+
+// a file's slice begins at a multiple of this in a call's upload (zero bytes between the slices)
+constexpr uint64_t SLICE_ALIGN = 256;
+inline uint64_t slice_begin(uint64_t at) { return (at + SLICE_ALIGN - 1) / SLICE_ALIGN * SLICE_ALIGN; }
+
+// per file: the bytes of its previous window that the caller keeps (from keep_from[f] to that window's end; null: none)
+inline std::vector<uint64_t> kept_tails(const StreamBase* st, const uint64_t* keep_from, const char* name) {
+    std::vector<uint64_t> kept(st->n_files(), 0);
+    for (uint32_t f = 0; keep_from && f < st->n_files(); f++) {
+        SY_REQUIRE(keep_from[f] <= st->prev_len[f], "%s_next: keep_from[%u] = %llu lies behind the previous window (%llu bytes)", name, f,
+                   (unsigned long long)keep_from[f], (unsigned long long)st->prev_len[f]);
+        kept[f] = st->prev_len[f] - keep_from[f];
+    }
+    return kept;
+}
+
+// where the window in t lies, file by file (text_off: n_files + 1 offsets into its text), for the next call's kept tails
+inline void remember_window(StreamBase* st, const sylph_inflated* t, const std::vector<uint64_t>& text_off) {
+    for (uint32_t f = 0; f < st->n_files(); f++) { st->prev_text[f] = t->text() + text_off[f]; st->prev_len[f] = text_off[f + 1] - text_off[f]; }
 }
 
 inline Segments segments_of(const void* const* ptrs, const uint64_t* n_bytes, uint32_t n_files) {

@@ -29,6 +29,11 @@
 //
 // Any doubt — a chain that breaks, an output that does not fit its region, a CRC or ISIZE that differs, no room on the device —
 // returns SYLPH_ERR_FORMAT / SYLPH_ERR_NOMEM and nothing else happens: the caller inflates with zlib as before.
+//
+// Two roads run these phases (InflatePhases).  sylph_inflate_files: the files whole, one chain, the text of all of them in one buffer.
+// sylph_inflate_stream_*: ONE SLICE of every advancing file's compressed bytes per call, one chain per slice entered with the window its
+// file's earlier slices left, the text handed out window by window, in memory bounded by the slice; what a file carries from one call
+// to the next, the cut and the sliced chain walk are inflate_stream_plan.h.
 #include <zlib.h>
 
 #include <algorithm>
@@ -37,20 +42,14 @@
 #include "inflate_plan.h"
 #include "inflate_stream_plan.h"
 
-// What a stream holds between two calls: every file's carry, its last 32 KiB of text (two buffers per file, taking turns), and where the
-// window it handed out last lies (the caller keeps that alive for the next call: its kept tail is copied from there).
-struct sylph_inflate_stream {
-    sylph_ctx* ctx = nullptr;
-    std::vector<const uint8_t*> gz;
-    std::vector<uint64_t> n_bytes;
-    uint64_t slice_bytes = 0, ratio = 0;
-    std::vector<sylph::inflate_stream_plan::Carry> carry;
+// What a stream holds between two calls beside decode_host.h's StreamBase: every file's carry and its last 32 KiB of text (two buffers
+// per file, taking turns).
+struct sylph_inflate_stream : sylph::decode_host::StreamBase {
+    using StreamBase::StreamBase;
+    uint64_t ratio = 0;                           // cells per compressed byte of a candidate's region
+    std::vector<sylph::inflate_stream_plan::Carry> carry = std::vector<sylph::inflate_stream_plan::Carry>(files.size());
     uint8_t* win = nullptr;                       // [n_files][2][WINDOW]
-    std::vector<uint8_t> win_cur;                 // which of a file's two buffers is current
-    std::vector<const uint8_t*> prev_text;        // file i's text in the window handed out last
-    std::vector<uint64_t> prev_len;
-    bool dead = false;
-    uint64_t n_slices = 0, text_bytes = 0, peak_scratch = 0, peak_window = 0;
+    std::vector<uint8_t> win_cur = std::vector<uint8_t>(files.size(), 0);   // which of a file's two buffers is current
 };
 
 namespace sylph {
@@ -1023,95 +1022,234 @@ void launch_decode_jobs(sylph_ctx* ctx, InflateScratch& S, uint64_t n_words, con
     SY_HIP(hipGetLastError());
 }
 
-// Several files in one call are ONE stream of gzip members to everything below (`cat a.gz b.gz` is a gzip file): their bytes lie back
-// to back on the device, one scan, one decode launch, one chain — the two mates of a pair share the latency of a block's wavefront
-// (~15 ms whatever the file's size) instead of paying it one after the other.
-// One call's state, and its phases in the order inflate_impl runs them.
-struct InflateCall {
-    sylph_inflated* t;
+// A device's turn at its scratch: one inflate per device at a time.  On every way out — a decline included — the stream is idle before
+// the next call may touch the scratch, and a set that outgrew SCRATCH_KEEP is freed.
+struct ScratchTurn {
+    DeviceScratch& ds;
+    hipStream_t stream;
+    std::lock_guard<std::mutex> turn;
+    explicit ScratchTurn(sylph_ctx* ctx) : ds(device_scratch(ctx->device)), stream(ctx->stream), turn(ds.mu) {}
+    ~ScratchTurn() { (void)hipStreamSynchronize(stream); if (ds.s.bytes() > SCRATCH_KEEP) ds.s.release(); }
+};
+
+// Cells a candidate's region holds per compressed byte: from the files' ISIZE where it can (bench.py's mate file: 5.3 -> 9: 7 GB of
+// cells for a 1 Gbp pair instead of 12.7 — less to allocate, and less for the process to hand back when it ends).
+// (SYLPH_HIP_INFLATE_REGION_RATIO: the tests' way to make every block outgrow its region)
+uint64_t region_ratio(const Segments& files) {
+    const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
+    return rr_env ? std::max(1, std::min(64, atoi(rr_env))) : region_ratio_from_isize(files, REGION_RATIO);
+}
+
+// The device phases of both roads (sylph_inflate_files: the files whole, one chain; sylph_inflate_stream_next: one slice per advancing
+// file, one chain per slice), in the order they run.  Whose bytes the upload holds, the blocks the chains enter at, the walk, and what
+// the CRC registers are compared with are the road's.
+struct InflatePhases {
     sylph_ctx* ctx;
     hipStream_t s;
     InflateScratch& S;
-    const Segments segs;
-    const uint64_t n, n_words;                      // compressed bytes, and the words that hold them
-    const uint64_t body0;                           // the first member's first deflate byte
-    std::vector<uint64_t> cand;                     // sorted candidate bits; cand[0] = body0 * 8
+    uint64_t n = 0, n_words = 0;                    // bytes of the upload, and the words that hold them
+    std::vector<uint64_t> cand;                     // sorted candidate bits of the upload
     uint32_t K = 0;
+    std::vector<DecodeJob> jobs;                    // per candidate: the first pass
     CellsLayout cells{};
     std::vector<BlockResult> res;                   // per candidate
-    std::vector<std::vector<uint8_t>> host_bytes;   // per Chain::host piece
-    Chain chain;
     Raw cells2;                                     // the cells of the blocks decoded again
     RedoPlan redo;
-    TextBuf text{"hipMalloc (inflated text)"};
+    std::vector<PlanBlock> plan;                    // per chain block
+    TextBuf text;
+    uint64_t scratch = 0;                           // bytes of scratch this call asked for
+    uint32_t x2n[64];
+
+    InflatePhases(sylph_ctx* c, InflateScratch& S_, const char* text_what) : ctx(c), s(c->stream), S(S_), text(text_what) { crc_x2n_table(x2n); }
+
+    void need(Raw& r, size_t bytes) { r.reserve(bytes); scratch += bytes; }
+
+    // ---- candidates among the bytes [byte_lo, n) (trailers and later headers are scanned too: no harm, and members end anywhere).  The
+    // road then adds the blocks its chains enter at, whatever their type (enter_at), and closes the list.
+    void scan(uint64_t byte_lo, const char* phase) {
+        const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
+        need(S.c1, cap1 * 8);
+        need(S.c2, cap2 * 8);
+        need(S.cnt, 64);
+        SY_HIP(hipMemsetAsync(S.cnt.p, 0, 64, s));
+        unsigned long long* cnt = S.cnt.as<unsigned long long>();
+        ScopedKernelTimer kt(ctx, "inflate_scan");
+        HostPhase hp(ctx, phase);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n - byte_lo + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
+        hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, S.gz.as<uint32_t>(), byte_lo, n, S.c1.as<uint64_t>(), cnt, cap1);
+        SY_HIP(hipGetLastError());
+        unsigned long long n1 = 0;
+        ctx->read_back(&n1, cnt, 8);
+        if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
+        if (n1) {
+            hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, S.gz.as<uint32_t>(), n * 8, S.c1.as<uint64_t>(),
+                               cnt, cap1, S.c2.as<uint64_t>(), cnt + 1, cap2);
+            SY_HIP(hipGetLastError());
+        }
+        cand = fetch_candidates(ctx, S.c2.p, cnt + 1, cap2, "more block-start candidates than the scan has room for");
+    }
+    void enter_at(uint64_t bit) { cand.insert(std::lower_bound(cand.begin(), cand.end(), bit), bit); }
+    void close_candidates() {
+        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+        if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
+        K = (uint32_t)cand.size();
+    }
+
+    // ---- decode every candidate into its region (`jobs`, filled by the road: `ratio` cells per compressed byte up to the next candidate
+    // of the span_bytes scanned, + REGION_SLACK)
+    void decode_first_pass(uint64_t span_bytes, uint64_t ratio, const char* phase) {
+        res.assign(K, BlockResult{});
+        if (!K) return;
+        cells = cells_layout(span_bytes, K, ratio, REGION_SLACK, SPILL_SLOTS, SPILL_CELLS);
+        need(S.cells, cells.total * 2);
+        need(S.res, (size_t)K * sizeof(BlockResult));
+        need(S.jobs, (size_t)K * sizeof(DecodeJob));
+        SY_HIP(hipMemsetAsync(S.cnt.as<unsigned long long>() + 2, 0, 8, s));      // the spill arena's counter
+        {
+            ScopedKernelTimer kt(ctx, "inflate_decode");
+            HostPhase hp(ctx, phase);
+            ctx->h2d(S.jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
+            launch_decode_jobs(ctx, S, n_words, S.jobs.as<DecodeJob>(), K, S.cells.as<uint16_t>(), Spill{cells.spill_base, SPILL_SLOTS}, S.res.as<BlockResult>());
+        }
+        ctx->d2h(res.data(), S.res.p, (size_t)K * sizeof(BlockResult));
+    }
+
+    // ---- blocks of the chains that outgrew their region (BlockResult::flags bit 1): once more, each into a region of exactly its size,
+    // with the window and the limit of its first pass
+    void decode_outgrown(const std::vector<ChainBlock>& blocks, const char* phase) {
+        redo = redo_plan(blocks, cand.data());
+        const size_t J = redo.jobs.size();
+        if (!J) return;
+        for (size_t q = 0; q < J; q++) {
+            const DecodeJob& first = jobs[blocks[redo.which[q]].cand];
+            redo.jobs[q].have_window = first.have_window;
+            redo.jobs[q].limit_words = first.limit_words;
+        }
+        ScopedKernelTimer kt(ctx, "inflate_decode");
+        HostPhase hp(ctx, phase);
+        Raw d_jobs2, d_res2;
+        cells2.alloc((redo.cells + 64) * 2);
+        d_jobs2.alloc(J * sizeof(DecodeJob));
+        d_res2.alloc(J * sizeof(BlockResult));
+        scratch += cells2.cap + d_jobs2.cap + d_res2.cap;
+        ctx->h2d(d_jobs2.p, redo.jobs.data(), J * sizeof(DecodeJob));
+        launch_decode_jobs(ctx, S, n_words, d_jobs2.as<DecodeJob>(), (uint32_t)J, cells2.as<uint16_t>(), Spill{0, 0}, d_res2.as<BlockResult>());
+        std::vector<BlockResult> res2(J);
+        ctx->d2h(res2.data(), d_res2.p, J * sizeof(BlockResult));
+        for (size_t q = 0; q < J; q++) {
+            const BlockResult& a = res[blocks[redo.which[q]].cand];
+            const BlockResult& b2 = res2[q];
+            if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
+                throw FormatDecline{"a block decoded a second time came out differently"};
+        }
+    }
+
+    // ---- where every chain block's cells lie and where its bytes go; room for the windows of n_groups groups (chain_groups, summed
+    // over the chains) if a block refers to one — a BGZF file's never do, and KB * 64 KB for it would be gigabytes
+    static uint32_t chain_groups(uint32_t kb) { const uint32_t G = window_group(kb); return (kb + G - 1) / G; }
+    void plan_blocks(const std::vector<ChainBlock>& blocks, uint64_t n_groups) {
+        const size_t KB = blocks.size();
+        plan.resize(KB);
+        bool any_window = false;
+        for (size_t i = 0; i < KB; i++) {
+            const ChainBlock& cb = blocks[i];
+            plan[i].cells = redo.region[i] != ~0ull ? cells2.as<uint16_t>() + redo.region[i] : S.cells.as<uint16_t>() + res[cb.cand].region;
+            plan[i].out_off = cb.out_off;
+            plan[i].n_out = cb.n_out;
+            plan[i].flags = cb.flags;
+            any_window |= (cb.flags & 1) != 0;
+        }
+        need(S.plan, KB * sizeof(PlanBlock));
+        ctx->h2d(S.plan.p, plan.data(), KB * sizeof(PlanBlock));
+        if (!any_window) return;
+        need(S.sfn, KB * WINDOW * 2);
+        need(S.ffn, (size_t)n_groups * WINDOW * 2);
+        need(S.rwin, (size_t)n_groups * WINDOW);
+    }
+
+    // ---- the text of chain blocks [b0, b0 + kb), one chain whose groups begin at group g0: the windows resolved down the chain in
+    // groups, from prev_window (null: none) in front of its first block; cells -> bytes
+    void resolve_chain(uint32_t b0, uint32_t kb, uint64_t g0, const uint8_t* prev_window, const char* windows_phase, const char* translate_phase) {
+        const uint32_t G = window_group(kb), NG = chain_groups(kb);
+        uint16_t* sfn = S.sfn.as<uint16_t>() + (uint64_t)b0 * WINDOW;
+        uint16_t* ffn = S.ffn.as<uint16_t>() + g0 * WINDOW;
+        uint8_t* rwin = S.rwin.as<uint8_t>() + g0 * WINDOW;
+        if (std::any_of(plan.begin() + b0, plan.begin() + b0 + kb, [](const PlanBlock& pb) { return (pb.flags & 1) != 0; })) {
+            ScopedKernelTimer kt(ctx, "inflate_windows");
+            HostPhase hp(ctx, windows_phase);
+            static std::once_flag once;
+            std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
+            hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>() + b0, kb, G, sfn, ffn);
+            SY_HIP(hipGetLastError());
+            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, ffn, NG, rwin, prev_window);
+            SY_HIP(hipGetLastError());
+        }
+        ScopedKernelTimer kt(ctx, "inflate_translate");
+        HostPhase hp(ctx, translate_phase);
+        hipLaunchKernelGGL(translate_kernel, dim3(kb), dim3(TR_TPB), 0, s, S.plan.as<PlanBlock>() + b0, G, sfn, rwin, text.text());
+        SY_HIP(hipGetLastError());
+    }
+
+    // ---- CRC-32 over the first `total` bytes of the text, cut at the ascending offsets m_end: the raw register of every piece
+    std::vector<uint32_t> crc_raw(const std::vector<unsigned long long>& m_end, uint64_t total, const char* phase) {
+        const uint32_t NM = (uint32_t)m_end.size();
+        need(S.mend, (size_t)NM * 8);
+        need(S.x2n, 256);
+        need(S.raw, (size_t)NM * 4);
+        std::vector<uint32_t> raw(NM);
+        {
+            ScopedKernelTimer kt(ctx, "inflate_crc");
+            HostPhase hp(ctx, phase);
+            ctx->h2d(S.mend.p, m_end.data(), (size_t)NM * 8);
+            ctx->h2d(S.x2n.p, x2n, 256);
+            SY_HIP(hipMemsetAsync(S.raw.p, 0, (size_t)NM * 4, s));
+            if (total) {
+                const uint64_t waves = (total + CRC_SPAN - 1) / CRC_SPAN;
+                hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text.text(), total,
+                                   S.mend.as<unsigned long long>(), NM, S.x2n.as<uint32_t>(), S.raw.as<uint32_t>());
+                SY_HIP(hipGetLastError());
+            }
+        }
+        ctx->d2h(raw.data(), S.raw.p, (size_t)NM * 4);
+        return raw;
+    }
+};
+
+// sylph_inflate_files.  Several files in one call are ONE stream of gzip members to everything below (`cat a.gz b.gz` is a gzip file):
+// their bytes lie back to back on the device, one scan, one decode launch, one chain — the two mates of a pair share the latency of a
+// block's wavefront (~15 ms whatever the file's size) instead of paying it one after the other.
+struct InflateCall : InflatePhases {
+    sylph_inflated* t;
+    const Segments segs;
+    const uint64_t body0;                           // the first member's first deflate byte (cand[0] = body0 * 8)
+    std::vector<std::vector<uint8_t>> host_bytes;   // per Chain::host piece
+    Chain chain;
 
     InflateCall(sylph_inflated* t_, InflateScratch& S_, Segments&& g)
-        : t(t_), ctx(t_->ctx), s(t_->ctx->stream), S(S_), segs(std::move(g)), n(segs.total()), n_words((n + 3) / 4),
-          body0(member_body(segs.ptr[0], (size_t)segs.base[1], 0)) {}
+        : InflatePhases(t_->ctx, S_, "hipMalloc (inflated text)"), t(t_), segs(std::move(g)), body0(member_body(segs.ptr[0], (size_t)segs.base[1], 0)) {
+        n = segs.total();
+        n_words = (n + 3) / 4;
+    }
 
     // ---- the compressed bytes, padded with zero words
     void upload() {
-        S.gz.reserve((n_words + GZ_PAD_WORDS) * 4);
+        need(S.gz, (n_words + GZ_PAD_WORDS) * 4);
         HostPhase hp(ctx, "inflate: upload");
         upload_segments(ctx, S.gz.as<uint8_t>(), segs, GZ_PAD_WORDS * 4);
     }
 
-    // ---- candidates (trailers and later headers are scanned too: no harm, and members end anywhere)
     void find_candidates() {
-        const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
-        S.c1.reserve(cap1 * 8);
-        S.c2.reserve(cap2 * 8);
-        S.cnt.reserve(64);
-        SY_HIP(hipMemsetAsync(S.cnt.p, 0, 64, s));
-        unsigned long long* cnt = S.cnt.as<unsigned long long>();
-        {
-            ScopedKernelTimer kt(ctx, "inflate_scan");
-            HostPhase hp(ctx, "inflate: scan");
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((n - body0 + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
-            hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, S.gz.as<uint32_t>(), body0, n, S.c1.as<uint64_t>(), cnt, cap1);
-            SY_HIP(hipGetLastError());
-            unsigned long long n1 = 0;
-            ctx->read_back(&n1, cnt, 8);
-            if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
-            if (n1) {
-                hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, S.gz.as<uint32_t>(), n * 8, S.c1.as<uint64_t>(),
-                                   cnt, cap1, S.c2.as<uint64_t>(), cnt + 1, cap2);
-                SY_HIP(hipGetLastError());
-            }
-            cand = fetch_candidates(ctx, S.c2.p, cnt + 1, cap2, "more block-start candidates than the scan has room for");
-        }
-        cand.insert(std::lower_bound(cand.begin(), cand.end(), body0 * 8), body0 * 8);      // the stream's first block, whatever its type
-        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-        if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
-        t->n_candidates = K = (uint32_t)cand.size();
+        scan(body0, "inflate: scan");
+        enter_at(body0 * 8);                        // the stream's first block
+        close_candidates();
+        t->n_candidates = K;
     }
 
-    void launch_decode(const DecodeJob* jobs, uint32_t n_jobs, uint16_t* out_cells, const Spill& sp, BlockResult* out) {
-        launch_decode_jobs(ctx, S, n_words, jobs, n_jobs, out_cells, sp, out);
-    }
-
-    // ---- decode every candidate into its region: `ratio` cells per compressed byte up to the next candidate, + REGION_SLACK.  The ratio
-    // comes from the files' ISIZE where it can (bench.py's mate file: 5.3 -> 9: 7 GB of cells for a 1 Gbp pair instead of 12.7 — less
-    // to allocate, and less for the process to hand back when it ends)
     void decode_candidates() {
-        // (SYLPH_HIP_INFLATE_REGION_RATIO: the tests' way to make every block outgrow its region)
-        const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
-        const uint64_t ratio = rr_env ? std::max(1, std::min(64, atoi(rr_env))) : region_ratio_from_isize(segs, REGION_RATIO);
-        cells = cells_layout(n - body0, K, ratio, REGION_SLACK, SPILL_SLOTS, SPILL_CELLS);
-        S.cells.reserve(cells.total * 2);
-        S.res.reserve((size_t)K * sizeof(BlockResult));
-        S.jobs.reserve((size_t)K * sizeof(DecodeJob));
-        SY_HIP(hipMemsetAsync(S.cnt.as<unsigned long long>() + 2, 0, 8, s));      // the spill arena's counter
-        res.resize(K);
-        {
-            ScopedKernelTimer kt(ctx, "inflate_decode");
-            HostPhase hp(ctx, "inflate: decode");
-            std::vector<DecodeJob> jobs(K);
-            for (uint32_t i = 0; i < K; i++) jobs[i] = decode_job(i, cand.data(), K, body0, n, ratio, REGION_SLACK);
-            ctx->h2d(S.jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
-            launch_decode(S.jobs.as<DecodeJob>(), K, S.cells.as<uint16_t>(), Spill{cells.spill_base, SPILL_SLOTS}, S.res.as<BlockResult>());
-        }
-        ctx->d2h(res.data(), S.res.p, (size_t)K * sizeof(BlockResult));
+        const uint64_t ratio = region_ratio(segs);
+        jobs.resize(K);
+        for (uint32_t i = 0; i < K; i++) jobs[i] = decode_job(i, cand.data(), K, body0, n, ratio, REGION_SLACK);
+        decode_first_pass(n - body0, ratio, "inflate: decode");
         if (getenv("SYLPH_HIP_INFLATE_STATS")) print_stats();
     }
 
@@ -1152,67 +1290,20 @@ struct InflateCall {
         for (auto& f : t->files) if (f.first == ~0ull) throw FormatDecline{"a file without a gzip member"};
     }
 
-    // ---- blocks of the chain that outgrew their region (BlockResult::flags bit 1): once more, each into a region of exactly its size
     void decode_outgrown() {
-        redo = redo_plan(chain.blocks, cand.data());
-        const size_t J = redo.jobs.size();
-        t->n_redone = J;
-        if (!J) return;
-        ScopedKernelTimer kt(ctx, "inflate_decode");
-        HostPhase hp(ctx, "inflate: decode again");
-        Raw d_jobs2, d_res2;
-        cells2.alloc((redo.cells + 64) * 2);
-        d_jobs2.alloc(J * sizeof(DecodeJob));
-        d_res2.alloc(J * sizeof(BlockResult));
-        ctx->h2d(d_jobs2.p, redo.jobs.data(), J * sizeof(DecodeJob));
-        launch_decode(d_jobs2.as<DecodeJob>(), (uint32_t)J, cells2.as<uint16_t>(), Spill{0, 0}, d_res2.as<BlockResult>());
-        std::vector<BlockResult> res2(J);
-        ctx->d2h(res2.data(), d_res2.p, J * sizeof(BlockResult));
-        for (size_t q = 0; q < J; q++) {
-            const BlockResult& a = res[chain.blocks[redo.which[q]].cand];
-            const BlockResult& b2 = res2[q];
-            if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
-                throw FormatDecline{"a block decoded a second time came out differently"};
-        }
+        InflatePhases::decode_outgrown(chain.blocks, "inflate: decode again");
+        t->n_redone = redo.jobs.size();
     }
 
-    // ---- the text: the host's pieces copied in; the windows resolved down the chain in groups; cells -> bytes
+    // ---- the text: the host's pieces copied in; the one chain's blocks, with no window in front of the first
     void write_text() {
         const uint32_t KB = (uint32_t)chain.blocks.size();
         text.grow(chain.total, 0, s);
         SY_HIP(hipMemsetAsync(text.text() + chain.total, 0, 256, s));
         for (size_t i = 0; i < chain.host.size(); i++) ctx->h2d(text.text() + chain.host[i].out_off, host_bytes[i].data(), host_bytes[i].size());
         if (!KB) return;
-        std::vector<PlanBlock> plan(KB);
-        bool any_window = false;
-        for (uint32_t i = 0; i < KB; i++) {
-            const ChainBlock& cb = chain.blocks[i];
-            plan[i].cells = redo.region[i] != ~0ull ? cells2.as<uint16_t>() + redo.region[i] : S.cells.as<uint16_t>() + res[cb.cand].region;
-            plan[i].out_off = cb.out_off;
-            plan[i].n_out = cb.n_out;
-            plan[i].flags = cb.flags;
-            any_window |= (cb.flags & 1) != 0;
-        }
-        S.plan.reserve((size_t)KB * sizeof(PlanBlock));
-        ctx->h2d(S.plan.p, plan.data(), (size_t)KB * sizeof(PlanBlock));
-        const uint32_t G = window_group(KB), NG = (KB + G - 1) / G;
-        if (any_window) {
-            ScopedKernelTimer kt(ctx, "inflate_windows");
-            HostPhase hp(ctx, "inflate: windows");
-            S.sfn.reserve((size_t)KB * WINDOW * 2);
-            S.ffn.reserve((size_t)NG * WINDOW * 2);
-            S.rwin.reserve((size_t)NG * WINDOW);
-            static std::once_flag once;
-            std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
-            hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>(), KB, G, S.sfn.as<uint16_t>(), S.ffn.as<uint16_t>());
-            SY_HIP(hipGetLastError());
-            hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, S.ffn.as<uint16_t>(), NG, S.rwin.as<uint8_t>(), (const uint8_t*)nullptr);
-            SY_HIP(hipGetLastError());
-        }
-        ScopedKernelTimer kt(ctx, "inflate_translate");
-        HostPhase hp(ctx, "inflate: translate");
-        hipLaunchKernelGGL(translate_kernel, dim3(KB), dim3(TR_TPB), 0, s, S.plan.as<PlanBlock>(), G, S.sfn.as<uint16_t>(), S.rwin.as<uint8_t>(), text.text());
-        SY_HIP(hipGetLastError());
+        plan_blocks(chain.blocks, chain_groups(KB));
+        resolve_chain(0, KB, 0, nullptr, "inflate: windows", "inflate: translate");
     }
 
     // ---- CRC-32 of every member the device decoded, against its trailer (a chain without a block is zlib's alone, and checked)
@@ -1221,26 +1312,7 @@ struct InflateCall {
         const uint32_t NM = (uint32_t)chain.members.size();
         std::vector<unsigned long long> m_end(NM);
         for (uint32_t i = 0; i < NM; i++) m_end[i] = chain.members[i].out_end;
-        uint32_t x2n[64];
-        crc_x2n_table(x2n);
-        S.mend.reserve((size_t)NM * 8);
-        S.x2n.reserve(256);
-        S.raw.reserve((size_t)NM * 4);
-        std::vector<uint32_t> raw(NM);
-        {
-            ScopedKernelTimer kt(ctx, "inflate_crc");
-            HostPhase hp(ctx, "inflate: crc");
-            ctx->h2d(S.mend.p, m_end.data(), (size_t)NM * 8);
-            ctx->h2d(S.x2n.p, x2n, 256);
-            SY_HIP(hipMemsetAsync(S.raw.p, 0, (size_t)NM * 4, s));
-            if (chain.total) {
-                const uint64_t waves = (chain.total + CRC_SPAN - 1) / CRC_SPAN;
-                hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text.text(), chain.total,
-                                   S.mend.as<unsigned long long>(), NM, S.x2n.as<uint32_t>(), S.raw.as<uint32_t>());
-                SY_HIP(hipGetLastError());
-            }
-        }
-        ctx->d2h(raw.data(), S.raw.p, (size_t)NM * 4);
+        const std::vector<uint32_t> raw = crc_raw(m_end, chain.total, "inflate: crc");
         for (uint32_t i = 0; i < NM; i++) {
             const Member& m = chain.members[i];
             if (m.on_host) continue;
@@ -1263,11 +1335,8 @@ void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_b
         if (!member_body(segs.ptr[i], (size_t)n_bytes[i], 0)) throw FormatDecline{"not a gzip file"};
     if (segs.total() >= SYLPH_INFLATE_WHOLE_MAX_BYTES) throw FormatDecline{"3 GiB of gzip bytes or more: the host reader takes them"};
     if (segs.total() >= ctx->inflate_whole_max_bytes) throw FormatDecline{"more gzip bytes than \"inflate_whole_max_bytes\" allows in one piece"};
-    DeviceScratch& DS = device_scratch(ctx->device);
-    std::lock_guard<std::mutex> turn(DS.mu);                       // one inflate per device at a time: they share the scratch
-    // (on every way out — a decline included — the stream is idle before the next call may touch the scratch; destroyed before `turn`)
-    struct Done { InflateScratch& s; hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); if (s.bytes() > SCRATCH_KEEP) s.release(); } } done{DS.s, ctx->stream};
-    InflateCall c(t, DS.s, std::move(segs));
+    ScratchTurn turn(ctx);
+    InflateCall c(t, turn.ds.s, std::move(segs));
     c.upload();
     c.find_candidates();
     c.decode_candidates();
@@ -1280,45 +1349,29 @@ void inflate_impl(sylph_inflated* t, const void* const* gzs, const uint64_t* n_b
 }
 
 // =================================================================================================================================
-// the stream: InflateCall's phases over one slice per advancing file (bookkeeping: inflate_stream_plan.h)
+// the stream: the same phases over one slice per advancing file (bookkeeping: inflate_stream_plan.h)
 // =================================================================================================================================
 using namespace inflate_stream_plan;
-constexpr uint64_t SLICE_ALIGN = 256;               // a file's slice begins at a multiple of this in the upload (zero bytes between them)
 
-struct StreamCall {
+struct StreamCall : InflatePhases {
     sylph_inflate_stream* st;
     sylph_inflated* t;
-    sylph_ctx* ctx;
-    hipStream_t s;
-    InflateScratch& S;
     const uint8_t* advance;
     const uint64_t* keep_from;
     struct FileSlice { uint32_t file; SliceCut sc; uint64_t off; };      // off: where the slice's bytes lie in the upload
     std::vector<FileSlice> slices;
     std::vector<uint64_t> entries;                  // per slice: entry_bit
-    uint64_t n = 0, n_words = 0;
-    std::vector<uint64_t> cand;                     // sorted candidate bits of the upload
-    uint32_t K = 0;
-    std::vector<DecodeJob> jobs;
-    CellsLayout cells{};
-    std::vector<BlockResult> res;
     std::vector<SliceWalk> walks;                   // per slice
     std::vector<std::vector<std::vector<uint8_t>>> host_bytes;   // per slice, per host piece
     std::vector<ChainBlock> blocks;                 // all slices' chain blocks, out_off in the window's text
     std::vector<uint32_t> first_block;              // per slice: its first block in `blocks` (+ one behind the last)
-    Raw cells2;
-    RedoPlan redo;
-    TextBuf text{"hipMalloc (inflated window)"};
     std::vector<uint64_t> kept, text_off;           // per file: kept bytes of the previous window; where the file's window begins
     uint64_t total = 0;
-    uint64_t scratch = 0;                           // bytes of scratch this call asked for
-    uint32_t x2n[64];
 
     StreamCall(sylph_inflate_stream* st_, sylph_inflated* t_, InflateScratch& S_, const uint8_t* adv, const uint64_t* keep)
-        : st(st_), t(t_), ctx(st_->ctx), s(st_->ctx->stream), S(S_), advance(adv), keep_from(keep) { crc_x2n_table(x2n); }
+        : InflatePhases(st_->ctx, S_, "hipMalloc (inflated window)"), st(st_), t(t_), advance(adv), keep_from(keep) {}
 
-    void need(Raw& r, size_t bytes) { r.reserve(bytes); scratch += bytes; }
-    uint32_t n_files() const { return (uint32_t)st->gz.size(); }
+    uint32_t n_files() const { return st->n_files(); }
 
     void plan_slices(uint64_t slice_bytes) {
         slices.clear();
@@ -1326,7 +1379,7 @@ struct StreamCall {
         for (uint32_t f = 0; f < n_files(); f++) {
             if ((advance && !advance[f]) || st->carry[f].finished) continue;
             const SliceCut sc = slice_cut(st->carry[f], st->n_bytes[f], slice_bytes);
-            at = (at + SLICE_ALIGN - 1) / SLICE_ALIGN * SLICE_ALIGN;
+            at = slice_begin(at);
             slices.push_back(FileSlice{f, sc, at});
             at += sc.end - sc.pos;
         }
@@ -1339,7 +1392,7 @@ struct StreamCall {
         HostPhase hp(ctx, "inflate stream: upload");
         SY_HIP(hipMemsetAsync(S.gz.p, 0, (n_words + GZ_PAD_WORDS) * 4, s));
         for (const FileSlice& fs : slices)
-            if (fs.sc.end > fs.sc.pos) ctx->h2d(S.gz.as<uint8_t>() + fs.off, st->gz[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
+            if (fs.sc.end > fs.sc.pos) ctx->h2d(S.gz.as<uint8_t>() + fs.off, st->files[fs.file] + fs.sc.pos, (size_t)(fs.sc.end - fs.sc.pos));
     }
 
     // the bit of the upload where the slice's chain enters a block nobody may have found: the file's very first block, whatever its
@@ -1349,7 +1402,7 @@ struct StreamCall {
         uint64_t file_bit;
         if (c.in_member) file_bit = c.bit;
         else if (c.bit == 0) {
-            const size_t body = member_body(st->gz[fs.file], (size_t)st->n_bytes[fs.file], 0);
+            const size_t body = member_body(st->files[fs.file], (size_t)st->n_bytes[fs.file], 0);
             if (!body || body >= fs.sc.end) return ~0ull;
             file_bit = (uint64_t)body * 8;
         } else return ~0ull;
@@ -1357,37 +1410,13 @@ struct StreamCall {
     }
 
     void find_candidates() {
-        const uint64_t cap1 = n / 8 + 4096, cap2 = n / 64 + 4096;
-        need(S.c1, cap1 * 8);
-        need(S.c2, cap2 * 8);
-        need(S.cnt, 64);
-        SY_HIP(hipMemsetAsync(S.cnt.p, 0, 64, s));
-        unsigned long long* cnt = S.cnt.as<unsigned long long>();
-        {
-            ScopedKernelTimer kt(ctx, "inflate_scan");
-            HostPhase hp(ctx, "inflate stream: scan");
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((n + SCAN_TPB - 1) / SCAN_TPB, 256 * 16);
-            hipLaunchKernelGGL(scan1_kernel, dim3(std::max(grid, 1u)), dim3(SCAN_TPB), 0, s, S.gz.as<uint32_t>(), (uint64_t)0, n, S.c1.as<uint64_t>(), cnt, cap1);
-            SY_HIP(hipGetLastError());
-            unsigned long long n1 = 0;
-            ctx->read_back(&n1, cnt, 8);
-            if (n1 > cap1) throw FormatDecline{"more header-like bit positions than the scan has room for"};
-            if (n1) {
-                hipLaunchKernelGGL(scan2_kernel, dim3((uint32_t)((n1 + SCAN2_TPB - 1) / SCAN2_TPB)), dim3(SCAN2_TPB), 0, s, S.gz.as<uint32_t>(), n * 8, S.c1.as<uint64_t>(),
-                                   cnt, cap1, S.c2.as<uint64_t>(), cnt + 1, cap2);
-                SY_HIP(hipGetLastError());
-            }
-            cand = fetch_candidates(ctx, S.c2.p, cnt + 1, cap2, "more block-start candidates than the scan has room for");
-        }
+        scan(0, "inflate stream: scan");
         entries.clear();
         for (const FileSlice& fs : slices) {
-            const uint64_t e = entry_bit(fs);
-            entries.push_back(e);
-            if (e != ~0ull) cand.insert(std::lower_bound(cand.begin(), cand.end(), e), e);
+            entries.push_back(entry_bit(fs));
+            if (entries.back() != ~0ull) enter_at(entries.back());
         }
-        cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-        if (cand.size() >= (1ull << 31)) throw FormatDecline{"too many candidates"};
-        K = (uint32_t)cand.size();
+        close_candidates();
         t->n_candidates += K;
     }
 
@@ -1399,29 +1428,16 @@ struct StreamCall {
     }
 
     void decode_candidates() {
-        jobs.assign(K, DecodeJob{});
-        res.assign(K, BlockResult{});
-        if (!K) return;
-        cells = cells_layout(n, K, st->ratio, REGION_SLACK, SPILL_SLOTS, SPILL_CELLS);
-        need(S.cells, cells.total * 2);
-        need(S.res, (size_t)K * sizeof(BlockResult));
-        need(S.jobs, (size_t)K * sizeof(DecodeJob));
-        SY_HIP(hipMemsetAsync(S.cnt.as<unsigned long long>() + 2, 0, 8, s));
-        {
-            ScopedKernelTimer kt(ctx, "inflate_decode");
-            HostPhase hp(ctx, "inflate stream: decode");
-            for (uint32_t i = 0; i < K; i++) {
-                DecodeJob j = decode_job(i, cand.data(), K, 0, n, st->ratio, REGION_SLACK);
-                const size_t si = slice_of(cand[i] >> 3);
-                const FileSlice& fs = slices[si];
-                j.limit_words = (fs.off + (fs.sc.end - fs.sc.pos) + 3) / 4;       // (the zero bytes behind a slice are nobody's input)
-                j.have_window = cand[i] == entries[si] ? (st->carry[fs.file].have_window ? 1u : 0u) : 1u;
-                jobs[i] = j;
-            }
-            ctx->h2d(S.jobs.p, jobs.data(), (size_t)K * sizeof(DecodeJob));
-            launch_decode_jobs(ctx, S, n_words, S.jobs.as<DecodeJob>(), K, S.cells.as<uint16_t>(), Spill{cells.spill_base, SPILL_SLOTS}, S.res.as<BlockResult>());
+        jobs.resize(K);
+        for (uint32_t i = 0; i < K; i++) {
+            DecodeJob j = decode_job(i, cand.data(), K, 0, n, st->ratio, REGION_SLACK);
+            const size_t si = slice_of(cand[i] >> 3);
+            const FileSlice& fs = slices[si];
+            j.limit_words = (fs.off + (fs.sc.end - fs.sc.pos) + 3) / 4;       // (the zero bytes behind a slice are nobody's input)
+            j.have_window = cand[i] == entries[si] ? (st->carry[fs.file].have_window ? 1u : 0u) : 1u;
+            jobs[i] = j;
         }
-        ctx->d2h(res.data(), S.res.p, (size_t)K * sizeof(BlockResult));
+        decode_first_pass(n, st->ratio, "inflate stream: decode");
     }
 
     // -> false: a slice's first block did not fit (the caller doubles the slice)
@@ -1430,7 +1446,7 @@ struct StreamCall {
         host_bytes.assign(slices.size(), {});
         for (size_t si = 0; si < slices.size(); si++) {
             const FileSlice& fs = slices[si];
-            const uint8_t* gz = st->gz[fs.file];
+            const uint8_t* gz = st->files[fs.file];
             const uint64_t fn = st->n_bytes[fs.file], lo = fs.off * 8, hi = (fs.off + (fs.sc.end - fs.sc.pos)) * 8;
             const int64_t shift = (int64_t)(fs.sc.pos * 8) - (int64_t)lo;
             std::vector<uint64_t> bits;
@@ -1455,18 +1471,11 @@ struct StreamCall {
     // ---- where everything goes in the window's text: per file, the kept tail of its previous window, then the slice's new bytes
     void lay_out_text() {
         const uint32_t F = n_files();
-        kept.assign(F, 0);
+        kept = kept_tails(st, keep_from, "sylph_inflate_stream");
         text_off.assign(F + 1, 0);
         std::vector<uint64_t> fresh(F, 0);
         for (size_t si = 0; si < slices.size(); si++) fresh[slices[si].file] = walks[si].total;
-        for (uint32_t f = 0; f < F; f++) {
-            if (keep_from) {
-                SY_REQUIRE(keep_from[f] <= st->prev_len[f], "sylph_inflate_stream_next: keep_from[%u] = %llu lies behind the previous window (%llu bytes)", f,
-                           (unsigned long long)keep_from[f], (unsigned long long)st->prev_len[f]);
-                kept[f] = st->prev_len[f] - keep_from[f];
-            }
-            text_off[f + 1] = text_off[f] + kept[f] + fresh[f];
-        }
+        for (uint32_t f = 0; f < F; f++) text_off[f + 1] = text_off[f] + kept[f] + fresh[f];
         total = text_off[F];
         blocks.clear();
         first_block.clear();
@@ -1484,34 +1493,12 @@ struct StreamCall {
     }
 
     void decode_outgrown() {
-        redo = redo_plan(blocks, cand.data());
-        const size_t J = redo.jobs.size();
-        t->n_redone = J;
-        if (!J) return;
-        for (size_t q = 0; q < J; q++) {                                            // (the first pass's window and limit, not redo_plan's guess)
-            const DecodeJob& first = jobs[blocks[redo.which[q]].cand];
-            redo.jobs[q].have_window = first.have_window;
-            redo.jobs[q].limit_words = first.limit_words;
-        }
-        ScopedKernelTimer kt(ctx, "inflate_decode");
-        HostPhase hp(ctx, "inflate stream: decode again");
-        Raw d_jobs2, d_res2;
-        cells2.alloc((redo.cells + 64) * 2);
-        d_jobs2.alloc(J * sizeof(DecodeJob));
-        d_res2.alloc(J * sizeof(BlockResult));
-        scratch += cells2.cap + d_jobs2.cap + d_res2.cap;
-        ctx->h2d(d_jobs2.p, redo.jobs.data(), J * sizeof(DecodeJob));
-        launch_decode_jobs(ctx, S, n_words, d_jobs2.as<DecodeJob>(), (uint32_t)J, cells2.as<uint16_t>(), Spill{0, 0}, d_res2.as<BlockResult>());
-        std::vector<BlockResult> res2(J);
-        ctx->d2h(res2.data(), d_res2.p, J * sizeof(BlockResult));
-        for (size_t q = 0; q < J; q++) {
-            const BlockResult& a = res[blocks[redo.which[q]].cand];
-            const BlockResult& b2 = res2[q];
-            if (b2.status != a.status || b2.n_out != a.n_out || b2.end_bit != a.end_bit || (b2.flags & 2))
-                throw FormatDecline{"a block decoded a second time came out differently"};
-        }
+        InflatePhases::decode_outgrown(blocks, "inflate stream: decode again");
+        t->n_redone = redo.jobs.size();
     }
 
+    // ---- the text: the kept tails and the host's pieces copied in; every slice's chain has its own groups, and the window its file's
+    // earlier slices left in front of its first block
     void write_text() {
         const uint32_t KB = (uint32_t)blocks.size();
         text.grow(total, 0, s);
@@ -1524,47 +1511,15 @@ struct StreamCall {
                 ctx->h2d(text.text() + base + walks[si].host[i].out_off, host_bytes[si][i].data(), host_bytes[si][i].size());
         }
         if (!KB) return;
-        std::vector<PlanBlock> plan(KB);
-        for (uint32_t i = 0; i < KB; i++) {
-            const ChainBlock& cb = blocks[i];
-            plan[i].cells = redo.region[i] != ~0ull ? cells2.as<uint16_t>() + redo.region[i] : S.cells.as<uint16_t>() + res[cb.cand].region;
-            plan[i].out_off = cb.out_off;
-            plan[i].n_out = cb.n_out;
-            plan[i].flags = cb.flags;
-        }
-        need(S.plan, (size_t)KB * sizeof(PlanBlock));
-        ctx->h2d(S.plan.p, plan.data(), (size_t)KB * sizeof(PlanBlock));
-        // every file's chain has its own groups, and the window its earlier slices left in front of its first block
         uint64_t n_groups = 0;
-        for (size_t si = 0; si < slices.size(); si++) { const uint32_t kb = first_block[si + 1] - first_block[si]; if (kb) n_groups += (kb + window_group(kb) - 1) / window_group(kb); }
-        need(S.sfn, (size_t)KB * WINDOW * 2);
-        need(S.ffn, (size_t)n_groups * WINDOW * 2);
-        need(S.rwin, (size_t)n_groups * WINDOW);
-        static std::once_flag once;
-        std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(winfn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WINDOW * 4); });
+        for (size_t si = 0; si < slices.size(); si++) if (first_block[si + 1] > first_block[si]) n_groups += chain_groups(first_block[si + 1] - first_block[si]);
+        plan_blocks(blocks, n_groups);
         uint64_t g0 = 0;
         for (size_t si = 0; si < slices.size(); si++) {
-            const uint32_t b0 = first_block[si], kb = first_block[si + 1] - b0;
+            const uint32_t b0 = first_block[si], kb = first_block[si + 1] - b0, f = slices[si].file;
             if (!kb) continue;
-            const uint32_t G = window_group(kb), NG = (kb + G - 1) / G, f = slices[si].file;
-            bool any_window = false;
-            for (uint32_t i = 0; i < kb; i++) any_window |= (blocks[b0 + i].flags & 1) != 0;
-            uint16_t* sfn = S.sfn.as<uint16_t>() + (uint64_t)b0 * WINDOW;
-            uint16_t* ffn = S.ffn.as<uint16_t>() + g0 * WINDOW;
-            uint8_t* rwin = S.rwin.as<uint8_t>() + g0 * WINDOW;
-            if (any_window) {
-                ScopedKernelTimer kt(ctx, "inflate_windows");
-                HostPhase hp(ctx, "inflate stream: windows");
-                hipLaunchKernelGGL(winfn_kernel, dim3(NG), dim3(WIN_TPB), WINDOW * 4, s, S.plan.as<PlanBlock>() + b0, kb, G, sfn, ffn);
-                SY_HIP(hipGetLastError());
-                hipLaunchKernelGGL(winchain_kernel, dim3(1), dim3(WIN_TPB), 0, s, ffn, NG, rwin, (const uint8_t*)(st->win + ((uint64_t)f * 2 + st->win_cur[f]) * WINDOW));
-                SY_HIP(hipGetLastError());
-            }
-            ScopedKernelTimer kt(ctx, "inflate_translate");
-            HostPhase hp(ctx, "inflate stream: translate");
-            hipLaunchKernelGGL(translate_kernel, dim3(kb), dim3(TR_TPB), 0, s, S.plan.as<PlanBlock>() + b0, G, sfn, rwin, text.text());
-            SY_HIP(hipGetLastError());
-            g0 += NG;
+            resolve_chain(b0, kb, g0, st->win + ((uint64_t)f * 2 + st->win_cur[f]) * WINDOW, "inflate stream: windows", "inflate stream: translate");
+            g0 += chain_groups(kb);
         }
     }
 
@@ -1586,19 +1541,7 @@ struct StreamCall {
         if (total && NM && !blocks.empty()) {
             std::vector<unsigned long long> m_end(NM);
             for (uint32_t i = 0; i < NM; i++) m_end[i] = pieces[i].end;
-            need(S.mend, (size_t)NM * 8);
-            need(S.x2n, 256);
-            need(S.raw, (size_t)NM * 4);
-            ScopedKernelTimer kt(ctx, "inflate_crc");
-            HostPhase hp(ctx, "inflate stream: crc");
-            ctx->h2d(S.mend.p, m_end.data(), (size_t)NM * 8);
-            ctx->h2d(S.x2n.p, x2n, 256);
-            SY_HIP(hipMemsetAsync(S.raw.p, 0, (size_t)NM * 4, s));
-            const uint64_t waves = (total + CRC_SPAN - 1) / CRC_SPAN;
-            hipLaunchKernelGGL(crc_kernel, dim3((uint32_t)((waves + CRC_TPB / 64 - 1) / (CRC_TPB / 64))), dim3(CRC_TPB), 0, s, text.text(), total,
-                               S.mend.as<unsigned long long>(), NM, S.x2n.as<uint32_t>(), S.raw.as<uint32_t>());
-            SY_HIP(hipGetLastError());
-            ctx->d2h(raw.data(), S.raw.p, (size_t)NM * 4);
+            raw = crc_raw(m_end, total, "inflate stream: crc");
         }
         for (uint32_t i = 0; i < NM; i++) {
             if (pieces[i].slice < 0) continue;
@@ -1643,12 +1586,10 @@ void stream_next_impl(sylph_inflate_stream* st, sylph_inflated* t, const uint8_t
     sylph_ctx* ctx = st->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
-    DeviceScratch& DS = device_scratch(ctx->device);
-    std::lock_guard<std::mutex> turn(DS.mu);                       // the device's one scratch, for this call and not between calls
-    struct Done { InflateScratch& s; hipStream_t st; ~Done() { (void)hipStreamSynchronize(st); if (s.bytes() > SCRATCH_KEEP) s.release(); } } done{DS.s, ctx->stream};
+    ScratchTurn turn(ctx);                                         // the device's one scratch, for this call and not between calls
     uint64_t slice_bytes = st->slice_bytes;
     for (uint32_t attempt = 0;; attempt++) {
-        StreamCall c(st, t, DS.s, advance, keep_from);
+        StreamCall c(st, t, turn.ds.s, advance, keep_from);
         t->n_candidates = 0;
         c.plan_slices(slice_bytes);
         if (!c.slices.empty()) {
@@ -1669,7 +1610,7 @@ void stream_next_impl(sylph_inflate_stream* st, sylph_inflated* t, const uint8_t
         c.commit();
         t->buf = c.text.release();
         SY_HIP(hipStreamSynchronize(ctx->stream));
-        for (uint32_t f = 0; f < c.n_files(); f++) { st->prev_text[f] = t->text() + c.text_off[f]; st->prev_len[f] = c.text_off[f + 1] - c.text_off[f]; }
+        remember_window(st, t, c.text_off);
         return;
     }
 }
@@ -1691,27 +1632,16 @@ int sylph_inflate(sylph_ctx* ctx, const void* gz, uint64_t n_bytes, int mem, syl
 
 int sylph_inflate_stream_open(sylph_ctx* ctx, const void* const* gz, const uint64_t* n_bytes, uint32_t n_files, int mem, uint64_t slice_bytes,
                               sylph_inflate_stream** out) {
-    if (!ctx || !out || !gz || !n_bytes || !n_files) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    for (uint32_t i = 0; i < n_files; i++) if (!gz[i]) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (mem != SYLPH_MEM_HOST && mem != SYLPH_MEM_HOST_PINNED) { set_error("sylph_inflate_stream_open: the compressed bytes must lie in host memory (mem kind %d)", mem); return SYLPH_ERR_INVALID; }
-    *out = nullptr;
+    if (const int rc = stream_open_args("sylph_inflate_stream", ctx, gz, n_bytes, n_files, mem, out)) return rc;
     for (uint32_t i = 0; i < n_files; i++)
         if (!inflate_plan::member_body((const uint8_t*)gz[i], (size_t)n_bytes[i], 0)) { set_error("sylph_inflate_stream_open: declined: not a gzip file"); return SYLPH_ERR_FORMAT; }
     sylph_inflate_stream* st = nullptr;
     const int rc = guarded([&] {
         std::lock_guard<std::mutex> lock(ctx->mu);
         DeviceGuard dg(ctx->device);
-        st = new sylph_inflate_stream();
-        st->ctx = ctx;
-        for (uint32_t i = 0; i < n_files; i++) { st->gz.push_back((const uint8_t*)gz[i]); st->n_bytes.push_back(n_bytes[i]); }
         if (!slice_bytes) slice_bytes = ctx->inflate_slice_bytes ? ctx->inflate_slice_bytes : inflate_stream_plan::DEFAULT_SLICE;
-        st->slice_bytes = std::max<uint64_t>(slice_bytes, inflate_stream_plan::MIN_SLICE);
-        const char* rr_env = getenv("SYLPH_HIP_INFLATE_REGION_RATIO");
-        st->ratio = rr_env ? std::max(1, std::min(64, atoi(rr_env))) : region_ratio_from_isize(segments_of(gz, n_bytes, n_files), REGION_RATIO);
-        st->carry.assign(n_files, inflate_stream_plan::Carry{});
-        st->win_cur.assign(n_files, 0);
-        st->prev_text.assign(n_files, nullptr);
-        st->prev_len.assign(n_files, 0);
+        st = new sylph_inflate_stream(ctx, gz, n_bytes, n_files, std::max<uint64_t>(slice_bytes, inflate_stream_plan::MIN_SLICE));
+        st->ratio = region_ratio(segments_of(gz, n_bytes, n_files));
         const hipError_t e = hipMalloc((void**)&st->win, (size_t)n_files * 2 * WINDOW);
         if (e != hipSuccess) { st->win = nullptr; (void)hipGetLastError(); throw HipError{e, "hipMalloc (inflate stream windows)", __FILE__, __LINE__}; }
         SY_HIP(hipMemsetAsync(st->win, 0, (size_t)n_files * 2 * WINDOW, ctx->stream));
@@ -1726,56 +1656,15 @@ int sylph_inflate_stream_open(sylph_ctx* ctx, const void* const* gz, const uint6
 }
 
 int sylph_inflate_stream_next(sylph_inflate_stream* st, const uint8_t* advance, const uint64_t* keep_from, sylph_inflated** window, uint8_t* finished) {
-    if (!st || !window) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    *window = nullptr;
-    if (st->dead) { set_error("sylph_inflate_stream_next: the stream was given up by an earlier call"); return SYLPH_ERR_FORMAT; }
-    sylph_ctx* ctx = st->ctx;
-    ctx->refs.fetch_add(1);
-    sylph_inflated* t = nullptr;
-    int format = 0;
-    const int rc = guarded([&] {
-        t = new sylph_inflated();
-        t->ctx = ctx;
-        try { stream_next_impl(st, t, advance, keep_from); }
-        catch (const FormatDecline& e) { set_error("sylph_inflate_stream_next: declined: %s", e.msg.c_str()); format = 1; }
-    });
-    if (rc != SYLPH_OK || format) {
-        st->dead = true;
-        {
-            std::lock_guard<std::mutex> lock(ctx->mu);
-            DeviceGuard dg(ctx->device);
-            (void)hipStreamSynchronize(ctx->stream);
-            if (t && t->buf) (void)hipFree(t->buf);
-            delete t;
-        }
-        ctx_unref(ctx);
-        return rc != SYLPH_OK ? rc : SYLPH_ERR_FORMAT;
-    }
-    if (finished) for (size_t i = 0; i < st->carry.size(); i++) finished[i] = st->carry[i].finished ? 1 : 0;
-    *window = t;
-    return SYLPH_OK;
+    return stream_next_entry("sylph_inflate_stream", st, advance, keep_from, window, finished, stream_next_impl);
 }
 
 int sylph_inflate_stream_info(const sylph_inflate_stream* st, uint64_t* n_slices, uint64_t* text_bytes, uint64_t* peak_scratch_bytes, uint64_t* peak_window_bytes) {
-    if (!st) { set_error("null argument"); return SYLPH_ERR_INVALID; }
-    if (n_slices) *n_slices = st->n_slices;
-    if (text_bytes) *text_bytes = st->text_bytes;
-    if (peak_scratch_bytes) *peak_scratch_bytes = st->peak_scratch;
-    if (peak_window_bytes) *peak_window_bytes = st->peak_window;
-    return SYLPH_OK;
+    return stream_info(st, n_slices, text_bytes, peak_scratch_bytes, peak_window_bytes);
 }
 
 void sylph_inflate_stream_destroy(sylph_inflate_stream* st) {
-    if (!st) return;
-    sylph_ctx* ctx = st->ctx;
-    {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        DeviceGuard dg(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-        if (st->win) (void)hipFree(st->win);
-        delete st;
-    }
-    ctx_unref(ctx);
+    stream_destroy(st, [](sylph_inflate_stream* g) { if (g->win) (void)hipFree(g->win); });
 }
 
 int sylph_inflated_file(const sylph_inflated* t, uint32_t i, const void** dev_text, uint64_t* n_bytes) {
