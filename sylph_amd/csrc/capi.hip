@@ -558,4 +558,29 @@ int sylph_ctx_kernel_stats(sylph_ctx* ctx, const char* family, double* total_ms,
     });
 }
 
+// BYTE_TO_SEQ (types.rs:50-59) + packing, on the host: what a feed does before a SYLPH_ENC_2BIT push.  out holds (n + 3) / 4
+// bytes; base i lands in bits 7-2(i%4) .. 6-2(i%4) of byte i/4.
+int sylph_pack_2bit(const uint8_t* ascii, uint64_t n, uint8_t* out) {
+    return guarded([&] {
+        SY_REQUIRE((ascii && out) || n == 0, "null argument");
+        static uint8_t lut[256];
+        static std::once_flag once;
+        std::call_once(once, [] {
+            memset(lut, 0, sizeof(lut));
+            lut[1] = 1; lut[2] = 2; lut[3] = 3;
+            const char* s4 = "AaCcGgTtUu";
+            const uint8_t v[10] = {0, 0, 1, 1, 2, 2, 3, 3, 3, 3};
+            for (int i = 0; i < 10; i++) lut[(uint8_t)s4[i]] = v[i];
+        });
+        uint64_t i = 0;
+        for (; i + 4 <= n; i += 4)
+            out[i >> 2] = (uint8_t)((lut[ascii[i]] << 6) | (lut[ascii[i + 1]] << 4) | (lut[ascii[i + 2]] << 2) | lut[ascii[i + 3]]);
+        if (i < n) {
+            uint8_t b = 0;
+            for (uint64_t j = i; j < n; j++) b |= (uint8_t)(lut[ascii[j]] << (6 - 2 * (j - i)));
+            out[i >> 2] = b;
+        }
+    });
+}
+
 }  // extern "C"

@@ -184,6 +184,14 @@ struct sylph_ctx {
     size_t pool_bytes = 0;
     // scratch
     sylph::DevBuf tmp_sort;                 // rocPRIM temporary storage
+    // Eight grow-only buffers that calls under `mu` take by index; nothing in one survives the call that filled it, except:
+    //   position road (position_road.hip): seeds_sorted_by_pos works in 0, 1 (slots / unsorted survivors), 4 (tile tables) and 7 (spill
+    //     regions) and leaves its result, PosSeeds, in 2 (positions) and 3 (hashes): those two are the road's until the caller has
+    //     annotated from them; the annotate step adds 5, the coarse record index.
+    //   read kernel (reads.hip): 7, the spill records of a batch's overflowing blocks.
+    //   text parsers (fasta.hip, fastq.hip, read_text.h): 0-3 while they find and gather records; they are done with them before they push.
+    //   finish_bucketed (replay_lds.hip): all eight, from the partition to the table; no push runs meanwhile (generic_replay, which
+    //     it may call half-way, takes its buffers from the pool for that reason).
     sylph::DevBuf scratch[8];
     sylph::DevBuf counters;                 // small device words (survivor counters etc.)
     void* pinned = nullptr;                 // 4 KiB pinned host page for small read-backs

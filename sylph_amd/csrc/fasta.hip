@@ -34,6 +34,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "sketch_session.h"
+#include "genomes.h"
 #include "text_lines.h"
 #include "read_text.h"
 #include "fasta_plan.h"
@@ -60,11 +61,6 @@ struct sylph_fasta {
 };
 
 namespace sylph {
-
-void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* contig_off, uint64_t n_contigs,
-                         const uint64_t* genome_contig_off, uint64_t n_genomes, uint32_t c, uint32_t k, int seed_mode,
-                         uint64_t min_spacing, int pseudotax, int mem, uint64_t** out_kmers, uint64_t* kmer_off, uint64_t** out_tracked,
-                         uint64_t* tracked_off);      // genomes.hip
 
 namespace {
 

@@ -13,12 +13,11 @@
 //     Between two anchors the recurrence is run by the anchor's thread (runs are 1-3 elements long at c = 200, spacing 30).
 //     `last_pos == 0` (:606) only holds before the first kept k-mer of a genome, which is an anchor here (end positions
 //     are >= k-1 > 0).
-#include "sketch_session.h"
+#include "genomes.h"
+#include "position_road.h"
 #include "device_common.h"
 
 namespace sylph {
-
-uint32_t seeds_sorted_by_pos(sylph_ctx* ctx, const uint8_t* d_bases, uint64_t n_bases, uint32_t c, uint32_t k, uint32_t* d_count);
 
 namespace {
 
@@ -178,10 +177,9 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
     ctx->counters.reserve(64);
     const uint32_t bias = (uint32_t)((uintptr_t)db & 15);   // a caller's device pointer need not be 16 B aligned
     SY_REQUIRE(n_bases + bias < (1ull << 32), "batch larger than 2^32-1 bases: split it");
-    const uint32_t n = seeds_sorted_by_pos(ctx, db - bias, n_bases + bias, c, k, ctx->counters.as<uint32_t>());
+    const PosSeeds seeds = seeds_sorted_by_pos(ctx, db - bias, n_bases + bias, c, k, ctx->counters.as<uint32_t>());
+    const uint32_t n = seeds.n;
     if (!n) { empty_out(); return; }
-    const uint32_t* s_pos = ctx->scratch[2].as<uint32_t>();
-    const uint64_t* s_hash = ctx->scratch[3].as<uint64_t>();
 
     DevBuf b_key(ctx), b_key_s(ctx), b_idx(ctx), b_idx_s(ctx), b_contig(ctx), b_end(ctx), b_gid(ctx), b_live(ctx), b_lpos(ctx);
     const size_t n1 = (size_t)n + 1;
@@ -192,7 +190,7 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
     {
         ScopedKernelTimer t(ctx, "annotate");
         hipLaunchKernelGGL(annotate_genomes_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_off.as<uint64_t>(), n_contigs,
-                           d_goff.as<uint64_t>(), n_genomes, s_pos, s_hash, n, bias, k, seed_mode == SYLPH_SEED_AVX2_COMPAT,
+                           d_goff.as<uint64_t>(), n_genomes, seeds.pos, seeds.hash, n, bias, k, seed_mode == SYLPH_SEED_AVX2_COMPAT,
                            b_key.as<uint64_t>(), b_contig.as<uint32_t>(), b_end.as<uint32_t>(), b_gid.as<uint32_t>(),
                            b_idx.as<uint32_t>());
         SY_HIP(hipGetLastError());
@@ -217,7 +215,7 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
     {
         ScopedKernelTimer t(ctx, "genome_filter");
         hipLaunchKernelGGL(compact_live_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, b_live.as<uint32_t>(), b_lpos.as<uint32_t>(),
-                           b_contig.as<uint32_t>(), b_end.as<uint32_t>(), b_gid.as<uint32_t>(), s_hash, n, l_contig.as<uint32_t>(),
+                           b_contig.as<uint32_t>(), b_end.as<uint32_t>(), b_gid.as<uint32_t>(), seeds.hash, n, l_contig.as<uint32_t>(),
                            l_end.as<uint32_t>(), l_gid.as<uint32_t>(), l_hash.as<uint64_t>());
         hipLaunchKernelGGL(spacing_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, l_contig.as<uint32_t>(), l_end.as<uint32_t>(),
                            d_n_live, min_spacing, b_kept.as<uint32_t>());

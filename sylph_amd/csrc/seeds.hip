@@ -16,6 +16,7 @@
 // Pure integer work, no MFMA.  Algorithmic HBM traffic: 1 B per base in, 12 B per survivor out.
 #include "common.h"
 #include "device_common.h"
+#include "seeds.h"
 #include "seed_plan.h"        // TPB, WPT, TILE_*, HALO_WORDS, STAGE_CAP, FLUSH_AT, LIST_CAP and what they promise each other
 
 namespace sylph {

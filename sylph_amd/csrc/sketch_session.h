@@ -30,7 +30,10 @@ using replay_plan::key_shift;                 // replay_plan.h: key = hash >> ke
 // the RID_A10_BIT a10_mark left in the records)
 constexpr int DEDUP_EXACT = 0, DEDUP_NONE = 1, DEDUP_FILTER = 2;
 void generic_replay(sylph_ctx* ctx, const uint64_t* d_hash, const OccRec* d_recs, uint32_t n_all, bool paired, int dedup,
-                    DevBuf& out_k, DevBuf& out_c, uint64_t& n_out, uint64_t& removed_out);   // sketch.hip
+                    DevBuf& out_k, DevBuf& out_c, uint64_t& n_out, uint64_t& removed_out);   // replay_generic.hip
+bool finish_bucketed(sylph_sketch* sk);       // replay_lds.hip: bucket partition + in-LDS replay; false = not a sample for it, the caller replays device-wide
+// reads.hip: one lane per record, seeding + markers fused; false = it declines the batch, having taken nothing
+bool push_short_reads(sylph_sketch* sk, const uint8_t* d_bases, uint32_t phase, const uint64_t* d_off, uint64_t n_records, uint64_t n_bases, int enc);
 void a10_mark(sylph_sketch* sk);              // a10.hip: marks the records (partitioned pass where one filter suffices, else the phase walk)
 void a10_settle(sylph_sketch* sk);            // a10.hip: marks if not marked, reads the partitioned pass's verdict (synchronises), redoes with the walk if it was bad
 bool a10_verdict(sylph_sketch* sk, const uint32_t words[2]);   // a10.hip: the verdict words read by the caller (finish_bucketed's tail); false = redone with the walk: start over
@@ -92,7 +95,7 @@ struct sylph_sketch {
     sylph::DevBuf fq_bases, fq_off;       // fastq.hip: the batch sylph_sketch_push_fastq gathered from FASTQ text (valid until the next such push)
     sylph::DevBuf out_k, out_c;           // final table
     uint64_t n_out = 0, dup_removed = 0;
-    sylph::DevBuf counters;               // [0] survivors (u32 @0), [1] n_valid (u64 @8), [2] removed (u64 @16)
+    sylph::DevBuf counters;               // 16 u32 words; in use: CNT_SURVIVORS, CNT_MARKED (below); each is cleared by the path that uses it
     sylph::DevBuf a10_tail;               // a10.hip: verdict words of the partitioned pass (see a10_state)
     explicit sylph_sketch(sylph_ctx* cx)
         : ctx(cx), hash(cx), recs(cx), slot_bases{sylph::DevBuf(cx), sylph::DevBuf(cx)}, slot_off{sylph::DevBuf(cx), sylph::DevBuf(cx)},
@@ -100,6 +103,10 @@ struct sylph_sketch {
 };
 
 namespace sylph {
+// Words of sylph_sketch::counters (u32 index).  CNT_SURVIVORS: the unordered position kernel's count of survivors (seeds_sorted_by_pos's
+// d_count).  CNT_MARKED: marker_lengths_kernel's flag — bit 0 set when some record of the batch has a length that carries a dedup
+// marker.  Apart: the count comes back inside seeds_sorted_by_pos while the flag, written before it, is still waiting to be read.
+constexpr uint32_t CNT_SURVIVORS = 0, CNT_MARKED = 6;
 // the block tables the short-read kernel left in the session's slot_meta buffer (seed_plan.h SlotMeta)
 inline seed_plan::SlotMeta slot_meta_of(sylph_sketch* sk, uint32_t n_blk) { return seed_plan::SlotMeta(sk->slot_meta.as<uint32_t>(), n_blk); }
 }  // namespace sylph
