@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include "seed_plan.h"
+
 namespace sylph {
 
 // seeding.rs:4-15 mm_hash64 / avx2_seeding.rs:6-30 mm_hash256.  NB first step is ~(key + (key << 21)).
@@ -194,25 +196,10 @@ __device__ __forceinline__ void pack16(uint4 v, uint32_t& F, uint32_t& R) {
     R = rcword(F);
 }
 
-// Number of k-mer start positions of a length-L sequence that the reference hashes.
-//   scalar  (seeding.rs:93,120):              L >= k ? L-k+1 : 0
-//   avx2    (avx2_seeding.rs:37-44,95):       4*((L-k+1)/4), nothing if L < min_len (k+1 reads, 2k contigs :160)
-__device__ __host__ __forceinline__ uint64_t n_hashed_kmers(uint64_t L, uint32_t k, int avx2_compat, int positions) {
-    if (L < k) return 0;
-    if (!avx2_compat) return L - k + 1;
-    const uint64_t min_len = positions ? 2ull * k : (uint64_t)k + 1;
-    if (L < min_len) return 0;
-    return ((L - k + 1) / 4) * 4;
-}
-
-// Place of the k-mer that starts at base i of a record with nh hashed k-mers in the order extract_markers emits the record's seeds
-// (sketch.rs:53-69): position order for the scalar routine (seeding.rs:86-146); the 4-lane AVX2 routine (avx2_seeding.rs:33-148) walks
-// four quarters of the record in lock step and pushes lane 0..3 of every step: (i mod len4, i div len4) with len4 = nh / 4.
-__device__ __host__ __forceinline__ uint64_t emission_rank(uint32_t i, uint32_t nh, int avx2_compat) {
-    if (!avx2_compat || nh < 4) return i;
-    const uint32_t len4 = nh >> 2, lane = i / len4;
-    return (uint64_t)(i - lane * len4) * 4 + lane;
-}
+// (n_hashed_kmers and emission_rank — how many k-mers of a record the reference hashes, and in which order it emits them — are
+//  arithmetic without HIP: seed_plan.h, tested on the CPU)
+using seed_plan::emission_rank;
+using seed_plan::n_hashed_kmers;
 
 // Adds the number of lanes with `pred` to *counter with ONE atomic per wavefront (64-bit ballot + s_bcnt1).
 __device__ __forceinline__ void wave_count_add(unsigned int* counter, bool pred) {
@@ -241,6 +228,19 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1 and 3
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
     return x;
+}
+
+// Maximum over the 64 lanes of a wavefront (all of them active), as a scalar: the same six DPP steps with v_max_u32 — lane 63 ends up
+// with the maximum of all — and one v_readlane_b32.  The __shfl_xor butterfly it replaces in the read kernel kept six lane-index registers
+// alive through the whole kernel and paid a compare, a select and a shift per step to rebuild its ds_bpermute addresses in every block.
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false));   // row_shr:1 (a lane without a source reads 0)
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false));   // row_shr:2
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false));   // row_shr:4
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false));   // row_shr:8
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1 and 3
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2 and 3
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
 // Exclusive prefix sum of one value per lane across a workgroup of TPB lanes (s_wave: TPB / 64 words of LDS, free again behind the

@@ -89,31 +89,37 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB == 256 
         if (it >= n_blk) continue;                                   // padding of the last XCD's range (uniform per workgroup)
         const uint32_t blk = blk_list ? blk_list[it] : it;
         const int64_t a0 = block_a0(blk, rt);                        // aligned coordinate of stream base 0 (multiple of 16)
-        load_stream<ENC, TPB>(s.sF, bases_al, n_al, a0, n_words);
-        const uint64_t R0 = blk_rec[blk], R1 = blk_rec[blk + 1];
+        const uint32_t rb = rel_bias(bias, a0);                      // offset -> stream base of this block, in 32 bits (seed_plan.h)
+        load_stream<ENC, TPB>(s.sF, bases_al, n_al, blk, a0, n_words);
+        const uint32_t R0 = blk_rec[blk], R1 = blk_rec[blk + 1];
         // first offset staged: a pair's mate-1 offset in front of a block that starts with a mate 2 (by value: as an out-parameter of
         // stage_offsets it cost every instance two VGPRs)
-        const uint64_t w_lo = paired ? (R0 & ~1ull) : R0;
+        const uint32_t w_lo = paired ? (R0 & ~1u) : R0;
         const bool in_lds = stage_offsets(s, off, n_rec, R0, R1, w_lo);
         __syncthreads();
         uint32_t base_prev = 0;                                      // survivors of the earlier passes of this block
         const uint64_t out0 = (uint64_t)it * slot_cap;
-        for (uint64_t pass = R0; pass < R1; pass += TPB) {          // more than TPB records in a block: only tiny reads
-            uint64_t L, s1, s2, e2;
-            uint32_t nh, rel;
-            if (record_geometry<K>(s, off, in_lds, w_lo, pass + tid, R1, paired, bias, a0, avx2_compat, L, s1, s2, e2, nh, rel))
+        // (the pass is counted by the records left, so that no 32-bit index wraps in front of the last pass; a lane's own index is meant
+        //  only where the lane has a record)
+        for (uint32_t pass = R0, left = R1 - R0; left; pass += TPB, left -= min(left, (uint32_t)TPB)) {   // more than TPB records in a block: only tiny reads
+            const uint32_t n_act = min(left, (uint32_t)TPB);
+            // What a lane carries through the hash loop for the steps behind it is two 32-bit stream bases (ba, bb: its marker windows);
+            // its k-mer count comes back from LDS, where deal_by_length put it.
+            uint32_t nh, rel, ba, bb;
+            if (record_geometry<K>(s, off, in_lds, w_lo, pass + tid, tid < n_act, paired, rb, avx2_compat, want_markers, nh, rel, ba, bb))
                 state->long_record = 1u;                             // the host reruns the batch through the position kernel
             uint32_t slot, rel_h, nh_h, rows;
             const bool dealt = deal_by_length<TPB, hit_bits_by_lds<TPB>>(s, nh, rel, slot, rel_h, nh_h, rows);
             hash_record<K, HV, TPB, hit_bits_by_lds<TPB>>(s, slot, rel_h, nh_h, thr_loop, hit);
             if (dealt) __syncthreads();                              // masks were written by other lanes
+            nh = s.nh[tid];
             uint32_t total = 0;
             bool decode = hit_bits_by_lds<TPB>;                      // the pass's first round decodes what the LDS atomics left
             for (;;) {                                               // (once; HV == 2: again after a candidate failed the exact test)
                 uint32_t first;
                 const uint32_t cnt = count_hits(s, nh, decode, first, total);
                 decode = false;
-                publish_markers(s, cnt, first, total, want_markers, paired, L, s1, s2, e2, rel, bias, a0);
+                publish_markers(s, cnt, first, total, ba, bb);
                 const bool is_listed = list_survivors(s, nh, cnt, first, total, rows);
                 __syncthreads();
                 finish_survivors<K, HV>(s, is_listed, rows, total, base_prev, slot_cap, thr, rec_base, pass, paired, avx2_compat, out0, slot_rec,

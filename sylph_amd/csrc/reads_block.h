@@ -25,8 +25,8 @@ struct KC {
 };
 
 // The workgroup's LDS.  Two arrays take over the place of two others, and nowhere else:
-//   * m0 / m1, the records' markers, lie over the staged offsets `off`: the lanes hold their offsets in registers by then (a block
-//     with several passes keeps its offsets in global memory instead);
+//   * m0 / m1, the records' markers, lie over the staged offsets `off`: the lanes have taken their stream bases from them by then
+//     (record_geometry; a block with several passes keeps its offsets in global memory instead);
 //   * hist, the dealing's histogram, lies over `first`, which is not in use before count_hits.
 // (The pointers carry the LDS address space in their type: every access through them is an LDS instruction whatever the optimiser makes
 //  of the code around it — with plain pointers the two arms of record_geometry, staged and global offsets, were merged into flat loads.)
@@ -174,27 +174,33 @@ __device__ __forceinline__ void kmer_steps8(uint32_t A0, uint32_t A1, uint32_t A
 // 1. The block's stream words [0, n_words) from the aligned coordinate a0 on, as a 2-bit big-endian stream.  Only the first and the
 // last block of a batch reach outside [0, n_al): every other block loads unconditionally.
 template <int ENC, int TPB>
-__device__ __forceinline__ void load_stream(SY_LDS uint32_t* sF, const uint8_t* bases_al, uint64_t n_al, int64_t a0, uint32_t n_words) {
+__device__ __forceinline__ void load_stream(SY_LDS uint32_t* sF, const uint8_t* bases_al, uint64_t n_al, uint32_t blk, int64_t a0, uint32_t n_words) {
     const uint32_t tid = threadIdx.x;
-    const bool interior = a0 >= 0 && (uint64_t)(a0 + (int64_t)n_words * 16) <= n_al;
+    const bool interior = block_starts_inside(blk) && (uint64_t)(a0 + (int64_t)n_words * 16) <= n_al;
+    // (the block's first word is a scalar address — a0 may be negative: it is only dereferenced at words inside [0, n_al) — and a lane
+    //  adds a 32-bit byte offset: no 64-bit coordinate per lane, in either arm)
+    const uintptr_t src0 = (uintptr_t)bases_al + (uintptr_t)(ENC == 0 ? a0 : (a0 >> 2));
+    constexpr uint32_t WB = ENC == 0 ? 16u : 4u;                   // bytes of input per stream word
     if (interior) {
         if constexpr (ENC == 0) {
-            const uint4* src = reinterpret_cast<const uint4*>(bases_al + a0);
-            for (uint32_t ci = tid; ci < n_words; ci += TPB) sF[ci] = pack16_fwd(src[ci]);
+            for (uint32_t ci = tid; ci < n_words; ci += TPB) sF[ci] = pack16_fwd(*reinterpret_cast<const uint4*>(src0 + ci * WB));
         } else {
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(bases_al + (a0 >> 2));
-            for (uint32_t ci = tid; ci < n_words; ci += TPB) sF[ci] = __builtin_amdgcn_perm(0u, src[ci], 0x00010203u);
+            for (uint32_t ci = tid; ci < n_words; ci += TPB)
+                sF[ci] = __builtin_amdgcn_perm(0u, *reinterpret_cast<const uint32_t*>(src0 + ci * WB), 0x00010203u);
         }
     } else {
+        // word ci starts at coordinate a0 + 16 ci: inside [0, n_al) for ci in [ci_lo, ci_hi) (stream_word_range, scalars)
+        uint32_t ci_lo, ci_hi;
+        stream_word_range(a0, n_al, n_words, ci_lo, ci_hi);
         for (uint32_t ci = tid; ci < n_words; ci += TPB) {
-            const int64_t a = a0 + (int64_t)ci * 16;              // aligned base coordinate of this word's first base
+            const bool inside = ci >= ci_lo && ci < ci_hi;
             if constexpr (ENC == 0) {                              // ASCII: 16 bytes -> one word
                 uint4 v = make_uint4(0, 0, 0, 0);
-                if (a >= 0 && (uint64_t)a < n_al) v = *reinterpret_cast<const uint4*>(bases_al + a);
+                if (inside) v = *reinterpret_cast<const uint4*>(src0 + ci * WB);
                 sF[ci] = pack16_fwd(v);
             } else {                                               // packed input: 4 bytes, first base in bits 7:6 of byte 0
                 uint32_t w = 0;
-                if (a >= 0 && (uint64_t)a < n_al) w = *reinterpret_cast<const uint32_t*>(bases_al + (a >> 2));
+                if (inside) w = *reinterpret_cast<const uint32_t*>(src0 + ci * WB);
                 sF[ci] = __builtin_amdgcn_perm(0u, w, 0x00010203u);
             }
         }
@@ -203,39 +209,53 @@ __device__ __forceinline__ void load_stream(SY_LDS uint32_t* sF, const uint8_t* 
 
 // 2. The offsets of the block's records [R0, R1) (+ the mate-1 offset in front of a block that starts with a mate 2, + two behind) into
 // LDS, from index w_lo on.  False — nothing staged — where they do not fit or the block takes several passes.
+// (Record indices are 32-bit — blk_rec holds them so — and what a lane adds to the scalar w_lo is a 32-bit count.)
 template <int TPB>
-__device__ __forceinline__ bool stage_offsets(const ReadsLds<TPB> s, const uint64_t* off, uint64_t n_rec, uint64_t R0, uint64_t R1,
-                                              uint64_t w_lo) {
-    const uint64_t w_hi = min(R1 + 2, n_rec);                   // last offset index needed
-    const bool in_lds = (w_hi - w_lo + 1) <= (uint64_t)(offs_staged(TPB) + 4) && (R1 - R0) <= (uint64_t)TPB;
-    if (in_lds)
-        for (uint64_t t = threadIdx.x; t <= w_hi - w_lo; t += TPB) s.off[t] = off[w_lo + t];
+__device__ __forceinline__ bool stage_offsets(const ReadsLds<TPB> s, const uint64_t* off, uint64_t n_rec, uint32_t R0, uint32_t R1,
+                                              uint32_t w_lo) {
+    const uint32_t w_hi = R1 + min((uint32_t)n_rec - R1, 2u);   // last offset index needed: min(R1 + 2, n_rec), R1 <= n_rec < 2^32
+    const uint32_t n_stage = w_hi - w_lo + 1;
+    const bool in_lds = n_stage <= (uint32_t)(offs_staged(TPB) + 4) && (R1 - R0) <= (uint32_t)TPB;
+    if (in_lds) {
+        const uint64_t* const src = off + w_lo;
+        for (uint32_t t = threadIdx.x; t < n_stage; t += TPB) s.off[t] = src[t];
+    }
     return in_lds;
 }
 
-// 3. The lane's record r (if r < R1): its length, the three offsets of its pair, the k-mers the reference hashes of it and its stream
-// base.  True: the record (or a mate of its pair) is longer than the halo — the host reruns the batch through the position kernel.
+// 3. The lane's record r (if `active`: the pass has a record for this lane): the k-mers the reference hashes of it, its stream base, and
+// the stream bases of its marker windows (seed_plan.h MarkerBases; none asked for: 0, 0).  The 64-bit offsets end HERE: a single read loads its two, a mate the three of its
+// pair (its own two are among them), the lengths are tested against the halo in 64 bits and everything that leaves is a length of at
+// most RH or a base relative to the block — one 32-bit add on an offset's low word (rb = rel_bias of the block).  The steps behind the
+// hash loop want nothing else, and four offsets carried through the loop were eight registers.
+// True: the record (or a mate of its pair) is longer than the halo — the host reruns the batch through the position kernel.
 template <int K, int TPB>
-__device__ __forceinline__ bool record_geometry(const ReadsLds<TPB> s, const uint64_t* off, bool in_lds, uint64_t w_lo, uint64_t r,
-                                                uint64_t R1, int paired, uint32_t bias, int64_t a0, int avx2_compat, uint64_t& L,
-                                                uint64_t& s1, uint64_t& s2, uint64_t& e2, uint32_t& nh, uint32_t& rel) {
-    const bool active = r < R1;
-    uint64_t start = 0;
-    L = 0; s1 = 0; s2 = 0; e2 = 0;
+__device__ __forceinline__ bool record_geometry(const ReadsLds<TPB> s, const uint64_t* off, bool in_lds, uint32_t w_lo, uint32_t r,
+                                                bool active, int paired, uint32_t rb, int avx2_compat, int want_markers, uint32_t& nh,
+                                                uint32_t& rel, uint32_t& ba, uint32_t& bb) {
+    uint64_t o0 = 0, o1 = 0, o2 = 0;                              // single: the record's start and end; paired: s1, s2, e2 of its pair
     if (active) {
+        const uint32_t r0 = paired ? (r & ~1u) : r;               // (w_lo is even where the input is paired: r0 >= w_lo)
         if (in_lds) {
-            start = s.off[r - w_lo];
-            L = s.off[r + 1 - w_lo] - start;
-            if (paired) { const uint64_t r1 = (r & ~1ull) - w_lo; s1 = s.off[r1]; s2 = s.off[r1 + 1]; e2 = s.off[r1 + 2]; }
+            const SY_LDS uint64_t* const o = s.off + (r0 - w_lo);
+            o0 = o[0]; o1 = o[1];
+            if (paired) o2 = o[2];
         } else {
-            start = off[r];
-            L = off[r + 1] - start;
-            if (paired) { const uint64_t r1 = r & ~1ull; s1 = off[r1]; s2 = off[r1 + 1]; e2 = off[r1 + 2]; }
+            const uint64_t* const o = off + r0;
+            o0 = o[0]; o1 = o[1];
+            if (paired) o2 = o[2];
         }
     }
-    const bool too_long = active && (L > (uint64_t)RH || (paired && (s2 - s1 > (uint64_t)RH || e2 - s2 > (uint64_t)RH)));
-    nh = (active && !too_long) ? (uint32_t)n_hashed_kmers(L, K, avx2_compat, 0) : 0u;
-    rel = active ? record_rel(start, bias, a0) : 0u;
+    const uint64_t d1 = o1 - o0, d2 = o2 - o1;                   // (paired: both mates' lengths; an idle lane: 0, 0)
+    const bool too_long = d1 > (uint64_t)RH || (paired && d2 > (uint64_t)RH);
+    const bool mate2 = paired && (r & 1u);
+    const uint32_t L = too_long ? 0u : (uint32_t)(mate2 ? d2 : d1);
+    const uint32_t rel1 = record_rel32(o0, rb), rel2 = record_rel32(o1, rb);
+    nh = (uint32_t)n_hashed_kmers(L, K, avx2_compat, 0);
+    rel = active ? (mate2 ? rel2 : rel1) : 0u;
+    MarkerBases mk{0u, 0u};
+    if (want_markers && active && !too_long) mk = paired ? pair_marker_bases(rel1, rel2, (uint32_t)d1, (uint32_t)d2) : single_marker_bases(rel, L);
+    ba = mk.ba; bb = mk.bb;
     return too_long;
 }
 
@@ -297,10 +317,7 @@ template <int K, int HV, int TPB, bool LB>
 __device__ __forceinline__ void hash_record(const ReadsLds<TPB> s, uint32_t slot, uint32_t rel_h, uint32_t nh_h, uint64_t thr_loop,
                                             const HitRegs& hit_consts) {
     const SY_LDS uint32_t* const sF = s.sF;
-    uint32_t nh_max = nh_h;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) nh_max = max(nh_max, (uint32_t)__shfl_xor((int)nh_max, d));
-    if constexpr (LB) nh_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)nh_max);   // the blocks restore ONE EXEC: no lane leaves the loop alone
+    const uint32_t nh_max = wave_max_u32(nh_h);     // a scalar (LB: the blocks restore ONE EXEC, no lane may leave the loop alone)
     if (nh_max) {
         // lane-aligned stream words A(j) = bases [rel + 16 j, rel + 16 j + 16): one LDS read and one 64-bit shift each
         const uint32_t w0 = rel_h >> 4, sh = 32u - (rel_h & 15u) * 2u;      // sh in [2, 32]
@@ -389,28 +406,17 @@ __device__ __forceinline__ uint32_t count_hits(const ReadsLds<TPB> s, uint32_t n
 // record's markers; then the pass's hits are dealt one per lane (finish_survivors).  (Each lane looping over its own hits made every
 // wavefront run the ~95-instruction body as often as its busiest lane had hits: 3-4 times for ~0.6 hits per lane.)
 template <int TPB>
-__device__ __forceinline__ void publish_markers(const ReadsLds<TPB> s, uint32_t cnt, uint32_t first, uint32_t total, int want_markers, int paired,
-                                                uint64_t L, uint64_t s1, uint64_t s2, uint64_t e2, uint32_t rel, uint32_t bias, int64_t a0) {
+__device__ __forceinline__ void publish_markers(const ReadsLds<TPB> s, uint32_t cnt, uint32_t first, uint32_t total, uint32_t ba, uint32_t bb) {
     const uint32_t tid = threadIdx.x;
     uint64_t m0 = 0, m1 = 0;
-    uint32_t has = 0;
-    if (cnt && want_markers) {
-        uint32_t ba = 0, bb = 0;
-        if (!paired) {
-            if (L >= 66 && L <= 400) { has = 1; ba = rel; bb = rel + (uint32_t)(L / 2); }       // sketch.rs:625-656, :923
-        } else if (s2 - s1 >= 33 && e2 - s2 >= 33) {                                             // sketch.rs:659-688
-            has = 1;
-            ba = record_rel(s1, bias, a0);
-            bb = record_rel(s2, bias, a0);
-        }
-        if (has) {
-            const uint64_t wa64 = win64(s.sF, ba), wb64 = win64(s.sF, bb);
-            uint32_t ea, oa, eb, ob;
-            evenodd16(wa64, ea, oa);
-            evenodd16(wb64, eb, ob);
-            m0 = (uint64_t)ea | ((uint64_t)eb << 32);
-            m1 = (uint64_t)oa | ((uint64_t)ob << 32);
-        }
+    const uint32_t has = (cnt && bb) ? 1u : 0u;                  // (record_geometry: which records carry markers, and where their windows start)
+    if (has) {
+        const uint64_t wa64 = win64(s.sF, ba), wb64 = win64(s.sF, bb);
+        uint32_t ea, oa, eb, ob;
+        evenodd16(wa64, ea, oa);
+        evenodd16(wb64, eb, ob);
+        m0 = (uint64_t)ea | ((uint64_t)eb << 32);
+        m1 = (uint64_t)oa | ((uint64_t)ob << 32);
     }
     s.m0[tid] = m0;
     s.m1[tid] = m1;

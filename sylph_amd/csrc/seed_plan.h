@@ -43,6 +43,33 @@ constexpr int LIST_CAP = 2048;                // survivors of a tile finished co
 
 SY_SEED_HD constexpr uint32_t half_groups(uint32_t nh) { return (nh + 7u) >> 3; }     // half-groups of 8 k-mers
 
+// ---- which k-mers of a record the reference hashes, and in which order it emits them ------------------------------------------------
+// Number of k-mer start positions of a length-L sequence that the reference hashes.
+//   scalar  (seeding.rs:93,120):              L >= k ? L-k+1 : 0
+//   avx2    (avx2_seeding.rs:37-44,95):       4*((L-k+1)/4), nothing if L < min_len (k+1 reads, 2k contigs :160)
+SY_SEED_HD constexpr uint64_t n_hashed_kmers(uint64_t L, uint32_t k, int avx2_compat, int positions) {
+    if (L < k) return 0;
+    if (!avx2_compat) return L - k + 1;
+    const uint64_t min_len = positions ? 2ull * k : (uint64_t)k + 1;
+    if (L < min_len) return 0;
+    return ((L - k + 1) / 4) * 4;
+}
+// The quarter of a record k-mer i lies in, i / len4 for i < 4 * len4 (len4 > 0): the quotient is 0..3, so three compares against len4,
+// 2 len4 and 3 len4 count it where the division was a 32-bit integer division per survivor (tests/test_pass_state_plan.py: every
+// nh <= NH_MAX, and a sample of large ones for the position kernel).
+SY_SEED_HD constexpr uint32_t emission_lane(uint32_t i, uint32_t len4) {
+    return (uint32_t)(i >= len4) + (uint32_t)(i >= 2u * len4) + (uint32_t)(i >= 3u * len4);   // (len4 <= 2^30: no product wraps)
+}
+// Place of the k-mer that starts at base i of a record with nh hashed k-mers in the order extract_markers emits the record's seeds
+// (sketch.rs:53-69): position order for the scalar routine (seeding.rs:86-146); the 4-lane AVX2 routine (avx2_seeding.rs:33-148) walks
+// four quarters of the record in lock step and pushes lane 0..3 of every step: (i mod len4, i div len4) with len4 = nh / 4 (there nh
+// is a multiple of 4, n_hashed_kmers, and i < nh).
+SY_SEED_HD constexpr uint64_t emission_rank(uint32_t i, uint32_t nh, int avx2_compat) {
+    if (!avx2_compat || nh < 4) return i;
+    const uint32_t len4 = nh >> 2, lane = emission_lane(i, len4);
+    return (uint64_t)(i - lane * len4) * 4 + lane;
+}
+
 // slots of a block / tile that expects `expect` survivors, of at most `full`: 75 % and 48 above the expectation
 SY_SEED_HD constexpr uint32_t slot_capacity(uint64_t full, uint64_t expect) {
     const uint64_t want = expect + expect * 3 / 4 + 48;
@@ -52,10 +79,20 @@ SY_SEED_HD constexpr uint32_t slot_capacity(uint64_t full, uint64_t expect) {
 // ---- a block's stream ---------------------------------------------------------------------------------------------------------
 // aligned coordinate of stream base 0 of block blk (a multiple of 16; negative for the first block)
 SY_SEED_HD constexpr int64_t block_a0(uint32_t blk, uint32_t rt) { return (int64_t)blk * rt - RH; }
+// block_a0 >= 0: every block but the first (rt >= RT_MIN > RH) — asked of the block's number, a 32-bit scalar
+SY_SEED_HD constexpr bool block_starts_inside(uint32_t blk) { return blk != 0u; }
 // stream words a block loads: its rt coordinates, RH on both sides (the end of its last record; mate 1 of a mate 2 that starts the
 // block), and the words a 64-bit window behind the last base touches
 SY_SEED_HD constexpr uint32_t stream_words(uint32_t rt) { return (rt + 2u * RH) / 16u + 3u; }
 SY_SEED_HD constexpr uint32_t lds_words(uint32_t rt) { return stream_words(rt) + RPAD; }       // what lds_bytes pays for
+// The words of a block's stream that lie inside the batch: word ci starts at coordinate a0 + 16 ci and is loaded where that is in
+// [0, n_al) — the words [lo, hi) — and zero elsewhere (only the first and the last blocks of a batch have such words)
+SY_SEED_HD void stream_word_range(int64_t a0, uint64_t n_al, uint32_t n_words, uint32_t& lo, uint32_t& hi) {
+    const int64_t left = (int64_t)n_al - a0;                      // coordinates from the block's first to the end of the batch
+    const uint64_t l = a0 < 0 ? (uint64_t)(-a0) / 16u : 0u, h = left > 0 ? ((uint64_t)left + 15u) / 16u : 0u;
+    lo = (uint32_t)(l < n_words ? l : n_words);
+    hi = (uint32_t)(h < n_words ? h : n_words);
+}
 // A record belongs to the block its aligned start coordinate (off + bias) falls into: block b begins with the first record r in
 // [0, n_rec] whose coordinate is not below block_begin(b, rt) (off is non-decreasing)
 SY_SEED_HD constexpr uint64_t block_begin(uint32_t blk, uint32_t rt) { return (uint64_t)blk * rt; }
@@ -70,6 +107,20 @@ SY_SEED_HD uint64_t first_record_of_block(const uint64_t* off, uint64_t n_rec, u
 }
 // stream base of a record (or of a mate) that starts at `start`: in [RH, RH + rt) for the records of the block itself
 SY_SEED_HD constexpr uint32_t record_rel(uint64_t start, uint32_t bias, int64_t a0) { return (uint32_t)((int64_t)(start + bias) - a0); }
+// The same base in 32 bits: the block's constant rel_bias is formed once (a scalar), a record's base is ONE 32-bit add on the low
+// word of its offset — what the truncation in record_rel leaves of the 64-bit sum and difference (tests/test_pass_state_plan.py).
+SY_SEED_HD constexpr uint32_t rel_bias(uint32_t bias, int64_t a0) { return bias - (uint32_t)(uint64_t)a0; }
+SY_SEED_HD constexpr uint32_t record_rel32(uint64_t start, uint32_t rb) { return (uint32_t)start + rb; }
+// What a lane keeps of its record for the steps behind the hash loop: the stream bases of its two marker windows (sketch.rs:625-688) — a
+// single read of 66..RH bases marks its start and its middle, a pair whose mates both have 33 bases marks the mates' starts.  bb = 0: no
+// markers (a marked record's second window starts at least 33 bases into the stream).  Lengths are at most RH here: 32 bits.
+struct MarkerBases { uint32_t ba, bb; };
+SY_SEED_HD constexpr MarkerBases single_marker_bases(uint32_t rel, uint32_t L) {
+    return (L >= 66u && L <= (uint32_t)RH) ? MarkerBases{rel, rel + L / 2u} : MarkerBases{0u, 0u};
+}
+SY_SEED_HD constexpr MarkerBases pair_marker_bases(uint32_t rel1, uint32_t rel2, uint32_t L1, uint32_t L2) {
+    return (L1 >= 33u && L2 >= 33u) ? MarkerBases{rel1, rel2} : MarkerBases{0u, 0u};
+}
 // The hash loop of a lane with stream base rel in a wavefront whose longest record has nh_max k-mers: it holds the raw words w0, w0 + 1
 // (w0 = rel >> 4), takes three lane-aligned words before the loop and one per whole group of 16, each fetching the raw word two ahead.
 SY_SEED_HD constexpr uint32_t hash_hi_word(uint32_t rel, uint32_t nh_max) { return (rel >> 4) + 4u + (half_groups(nh_max) >> 1); }
@@ -183,6 +234,7 @@ struct SlotMeta {
 
 // ---- what the comments above claim --------------------------------------------------------------------------------------------------
 static_assert(RT_MIN % 16 == 0 && RT_MAX % 16 == 0 && RT_MIN <= RT_MAX && RH % 16 == 0, "blocks and halo are whole 16-base words");
+static_assert(block_a0(0, RT_MAX) < 0 && block_a0(1, RT_MIN) >= 0 && !block_starts_inside(0) && block_starts_inside(1), "only the first block starts in front of the batch");
 static_assert(MASKW * 32 >= NH_MAX, "a record's k-mers have a mask bit each");
 static_assert(MASKW % 2 == 0, "the columns are zeroed two rows at a time (deal_by_length)");
 static_assert(half_groups(NH_MAX) <= 63 && deal_bin(NH_MAX) < 64 && deal_bin(0) == 63, "63 bins hold the half-groups of the longest record");
