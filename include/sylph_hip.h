@@ -130,7 +130,8 @@ int sylph_ctx_set_option(sylph_ctx *ctx, const char *key, const char *value);
 /* Per-kernel timing (hipEvent pairs on the ctx stream around every launch of the named kernel family) for
  * bench.py's roofline object.  enable=1 starts collecting and clears the totals.  Families (time + launches): "seeds", "compact",
  * "annotate", "sort" (the bucket partition), "replay", "a10" (the filter dedup's passes), "probe", "assemble" (hits -> result rows),
- * "exchange", "db_index", "genome_filter", "seeds_spill", "replay_overflow"; counters only (launches = how often that road was
+ * "exchange", "db_index", "genome_filter", "seeds_spill", "replay_overflow", "edge_winner", "edge_count" (the two launches of the
+ * reassignment log); counters only (launches = how often that road was
  * taken; the tests read them): "deferred", "deferred_redo", "a10_part", "a10_redo"; "replay_lane", "replay_general" (launches = buckets the
  * 256-slot replay kernel ran with one occurrence per lane / with its general body, counted on the host while "replay" is timed). */
 int sylph_ctx_profile(sylph_ctx *ctx, int enable);
@@ -466,6 +467,29 @@ int sylph_db_reassign_view(sylph_db *db, const uint64_t *sample_kmers, const uin
                            const uint32_t *passing_gids, const double *passing_ani, uint32_t n_passing,
                            const uint32_t **contain_count, const uint64_t **cov_off, const uint32_t **covs,
                            uint64_t *out_n_covs, const uint32_t **kmers_lost);
+/* The reassignment log of `profile --log-reassignments` (contain.rs:432-456): which passing genome the winner table hands how
+ * many of another passing genome's k-mers to.  Same passing-list conventions as sylph_db_reassign_view (passing_gids in the order
+ * of the reference's result vector, passing_ani their first-pass final_est_ani, n_passing entries each; a gid out of range or
+ * listed twice is SYLPH_ERR_INVALID).  genome_kmers[kmer_off[r] .. kmer_off[r+1]) are the genome_kmers of the passing genome of
+ * rank r — the caller's copy, in `mem` (host or device; 8-byte aligned): the database keeps only the inverted index.  kmer_off
+ * is a host array of n_passing + 1 non-decreasing entries.
+ * For every occurrence of a k-mer x in the list of rank i: w(x) = the passing genome with the highest passing_ani among those
+ * that hold x in genome_kmers or in the attached tracked k-mers, ties to the lowest rank (:417; the rule of the reassignment
+ * pass).  If w(x) exists and w(x) != i, the edge (winner = w(x), loser = i) counts one more (:440-449).  A k-mer no passing genome
+ * holds counts nothing (a caller's mistake, not an error); a k-mer repeated inside one list counts once per occurrence.
+ * *out_edges: every edge with count >= min_count (0 behaves as 1; the reference prints count > 10), sorted by (loser, winner)
+ * ascending — the reference's order is its hash map's —, library-allocated, released with sylph_free(); *out_n == 0 gives
+ * *out_edges == NULL.  n_passing == 0 and empty k-mer lists are SYLPH_OK with no edges.
+ * A genome's identity is its rank.  The reference compares GenomeSketch values, so two byte-identical genomes in one passing
+ * list are one genome there and two here: a divergence nobody will meet.
+ * SYLPH_ERR_INVALID on a database that is one shard of several (the edges would need a reduction over the ranks).  The call
+ * leaves the database's result block alone: views borrowed from an earlier sylph_db_contain_view* or sylph_db_reassign_view stay
+ * valid and unchanged across it.  Context option "reassign_edge_window" = "1".."8192" (default 8192, unmeasured; tests lower
+ * it): the winner ranks one counting workgroup covers. */
+typedef struct sylph_reassign_edge { uint32_t winner, loser, count; } sylph_reassign_edge;   /* ranks in the passing list */
+int sylph_db_reassign_edges(sylph_db *db, const uint64_t *genome_kmers, const uint64_t *kmer_off, int mem,
+                            const uint32_t *passing_gids, const double *passing_ani, uint32_t n_passing,
+                            uint32_t min_count, sylph_reassign_edge **out_edges, uint64_t *out_n);
 void sylph_db_destroy(sylph_db *db);
 uint64_t sylph_db_index_bytes(const sylph_db *db);   /* HBM taken by the postings index (lines + overflow runs) */
 

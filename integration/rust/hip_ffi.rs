@@ -13,6 +13,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
+#[repr(C)] pub struct SylphReassignEdge { pub winner: u32, pub loser: u32, pub count: u32 }   // sylph_reassign_edge: ranks in the passing list
 #[repr(C)] pub struct SylphCommOps {   // caller-supplied collectives on device buffers (stream = hipStream_t); 0 = success
     pub all_gather: extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: u64, stream: *mut c_void) -> c_int,
     pub all_to_all: extern "C" fn(user: *mut c_void, send: *const c_void, send_off: *const u64, recv: *mut c_void,
@@ -95,6 +96,11 @@ extern "C" {
                                   passing_gids: *const u32, passing_ani: *const f64, n_passing: u32,
                                   contain_count: *mut *const u32, cov_off: *mut *const u64, covs: *mut *const u32,
                                   out_n_covs: *mut u64, kmers_lost: *mut *const u32) -> c_int;
+    // profile --log-reassignments: the edges of winner_table's log (contain.rs:432-456), counted on the device; genome_kmers /
+    // kmer_off = the passing genomes' genome_kmers, flattened in the order of the passing list; *out_edges is freed with sylph_free
+    pub fn sylph_db_reassign_edges(db: *mut SylphDb, genome_kmers: *const u64, kmer_off: *const u64, mem: c_int,
+                                   passing_gids: *const u32, passing_ani: *const f64, n_passing: u32, min_count: u32,
+                                   out_edges: *mut *mut SylphReassignEdge, out_n: *mut u64) -> c_int;
     pub fn sylph_ctx_set_option(ctx: *mut SylphCtx, key: *const c_char, value: *const c_char) -> c_int;
     pub fn sylph_ctx_synchronize(ctx: *mut SylphCtx) -> c_int;
     // host feed: page-locked batch buffers for sylph_sketch_push(.., MEM_HOST_PINNED)

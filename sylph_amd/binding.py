@@ -29,7 +29,7 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_ctx_synchronize", "sylph_ctx_set_option", "sylph_ctx_profile", "sylph_ctx_kernel_stats", "sylph_seeds",
            "sylph_seeds_positions", "sylph_sketch_genome", "sylph_sketch_genomes", "sylph_sketch_begin", "sylph_sketch_push", "sylph_sketch_push_n",
            "sylph_sketch_finish", "sylph_sketch_finish_device", "sylph_sketch_destroy", "sylph_db_upload",
-           "sylph_db_n_genomes", "sylph_db_n_kmers", "sylph_db_contain", "sylph_db_contain_view", "sylph_db_contain_view_packed", "sylph_db_attach_tracked", "sylph_db_reassign_view", "sylph_db_destroy",
+           "sylph_db_n_genomes", "sylph_db_n_kmers", "sylph_db_contain", "sylph_db_contain_view", "sylph_db_contain_view_packed", "sylph_db_attach_tracked", "sylph_db_reassign_view", "sylph_db_reassign_edges", "sylph_db_destroy",
            "sylph_sketch_push_enc", "sylph_pack_2bit", "sylph_db_index_bytes", "sylph_db_contain_batch", "sylph_shard_bounds", "sylph_db_upload_shard", "sylph_comm_rccl_unique_id",
            "sylph_comm_create_rccl", "sylph_comm_create", "sylph_comm_destroy", "sylph_db_contain_batch_sharded",
            "sylph_pipeline_create", "sylph_pipeline_submit", "sylph_pipeline_submit_session", "sylph_pipeline_flush", "sylph_pipeline_next",
@@ -135,6 +135,7 @@ def load():
     L.sylph_db_contain_view_packed.argtypes = [vp, vp, vp, u64, i32, dbl, P(vp), P(vp), P(vp), P(u32), P(u64)]
     L.sylph_db_attach_tracked.argtypes = [vp, vp, vp, i32]
     L.sylph_db_reassign_view.argtypes = [vp, vp, vp, u64, i32, vp, vp, u32, P(vp), P(vp), P(vp), P(u64), P(vp)]
+    L.sylph_db_reassign_edges.argtypes = [vp, vp, vp, i32, vp, vp, u32, u32, P(vp), P(u64)]
     L.sylph_db_destroy.argtypes = [vp]
     L.sylph_db_destroy.restype = None
     L.sylph_db_index_bytes.argtypes = [vp]
@@ -890,6 +891,18 @@ class Database:
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(count,)).view(dtype)
         return (view(pc, G, C.c_uint32, np.uint32), view(po, G + 1, C.c_uint64, np.uint64),
                 view(pv, int(nh.value), C.c_uint32, np.uint32), view(pl, G, C.c_uint32, np.uint32))
+
+    def reassign_edges(self, genome_kmers, kmer_off, passing_gids, passing_ani, min_count=11):
+        """sylph_db_reassign_edges: genome_kmers[kmer_off[r]:kmer_off[r + 1]] = the genome_kmers of the passing genome of rank r
+        -> (winner, loser, count) uint32 arrays, ranks in the passing list, sorted by (loser, winner)."""
+        k, off = _np(genome_kmers, np.uint64), _np(kmer_off, np.uint64)
+        pg, pa = _np(passing_gids, np.uint32), _np(passing_ani, np.float64)
+        out, n = C.c_void_p(), C.c_uint64(0)
+        _check(load().sylph_db_reassign_edges(self._h, _ptr(k) if len(k) else None, _ptr(off) if len(off) else None, MEM_HOST,
+                                              _ptr(pg) if len(pg) else None, _ptr(pa) if len(pa) else None, len(pg), int(min_count),
+                                              C.byref(out), C.byref(n)))
+        e = _take(out, 3 * n.value, np.uint32).reshape(-1, 3)
+        return e[:, 0].copy(), e[:, 1].copy(), e[:, 2].copy()
 
     def close(self):
         if self._h:

@@ -458,6 +458,10 @@ int sylph_ctx_set_option(sylph_ctx* ctx, const char* key, const char* value) {
             const long v = atol(value);
             SY_REQUIRE(v >= 2 && v <= 64, "bootstrap_bins must be 2..64");
             ctx->bootstrap_bins = (uint32_t)v;
+        } else if (!strcmp(key, "reassign_edge_window")) {
+            const long v = atol(value);
+            SY_REQUIRE(v >= 1 && v <= 8192, "reassign_edge_window must be 1..8192");
+            ctx->reassign_edge_window = (uint32_t)v;
         } else if (!strcmp(key, "stream_priority")) {
             // The context's own stream is made again at another priority (hipStreamCreateWithPriority): "high" lets the small kernels of a
             // profile context through where the sketch contexts' seeding kernels keep the chip full (pipeline.hip).

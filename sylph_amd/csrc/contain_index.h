@@ -138,6 +138,74 @@ __device__ __forceinline__ LongRunStep long_run_step(const LineView& v, uint64_t
     r.match = lane < first_stop && index_plan::slot_rem(y, v.gshift) == rem;
     return r;
 }
+// every matching posting of a long overflow run, 64 entries per step, for the whole wavefront (same arguments in every lane):
+// f(genome id) is called by the lane that holds the match
+template <class F>
+__device__ __forceinline__ void long_run_for_each(const LineView& v, uint64_t start, uint64_t rem, F&& f) {
+    for (uint64_t base = start;; base += 64) {
+        const LongRunStep r = long_run_step(v, base, rem);
+        if (r.match) f(r.g);
+        if (r.ended) break;
+    }
+}
+
+// The winner table (contain.rs:410-430), asked per k-mer: the passing genome with the highest first-pass ANI among those that hold
+// the k-mer in genome_kmers (the kept index) or in pseudotax_tracked_nonused_kmers (the tracked index), ties to the lowest rank in
+// the passing list (the reference replaces only on strictly greater ANI, :417).  rank[g] = position of genome g in the passing list
+// or ~0, ani[rank].  Called by every lane of a wavefront together (live: this lane has a k-mer): the line and short overflow runs
+// are taken lane by lane; long runs (k-mers shared by hundreds of genomes) are handed to the whole wavefront, one after the other,
+// and their outcome is merged into the owning lane before the tracked pass begins.  -> the winner's rank or ~0; n_kept = the
+// k-mer's postings in the kept index, passing or not.  TRACKED_NEEDS_KEPT: the tracked index is looked at only for a k-mer some
+// genome holds in genome_kmers (the reassignment pass: nothing else can be lost or kept); otherwise for every live k-mer.
+__device__ __forceinline__ bool winner_beats(double a, uint32_t r, double ba, uint32_t br) { return a > ba || (a == ba && r < br); }
+template <bool TRACKED_NEEDS_KEPT>
+__device__ __forceinline__ uint32_t winner_of(const LineView& kept, const LineView& tracked, int have_tracked, uint64_t km, bool live,
+                                              const uint32_t* __restrict__ rank, const double* __restrict__ ani, uint32_t& n_kept) {
+    const int lane = (int)(threadIdx.x & 63);
+    auto consider = [&](uint32_t g, double& ba, uint32_t& br) {
+        const uint32_t r = rank[g];
+        if (r == 0xFFFFFFFFu) return;
+        const double a = ani[r];
+        if (winner_beats(a, r, ba, br)) { ba = a; br = r; }
+    };
+    uint32_t best_rank = 0xFFFFFFFFu;
+    double best_ani = -1.0;
+    n_kept = 0;
+    uint64_t ls = ~0ull, lr = 0;
+    if (live) for_each_posting(kept, km, [&](uint32_t g) { n_kept++; consider(g, best_ani, best_rank); }, &ls, &lr);
+    for_each_long_run(ls, lr, [&](int src, uint64_t rs, uint64_t rm) {
+        uint32_t c_l = 0, r_l = 0xFFFFFFFFu;
+        double a_l = -1.0;
+        long_run_for_each(kept, rs, rm, [&](uint32_t g) { c_l++; consider(g, a_l, r_l); });
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const uint32_t c_o = (uint32_t)__shfl_xor((int)c_l, d), r_o = (uint32_t)__shfl_xor((int)r_l, d);
+            const double a_o = __shfl_xor(a_l, d);
+            c_l += c_o;
+            if (winner_beats(a_o, r_o, a_l, r_l)) { a_l = a_o; r_l = r_o; }
+        }
+        if (lane == src) {
+            n_kept += c_l;
+            if (winner_beats(a_l, r_l, best_ani, best_rank)) { best_ani = a_l; best_rank = r_l; }
+        }
+    });
+    uint64_t lts = ~0ull, ltr = 0;
+    if ((TRACKED_NEEDS_KEPT ? n_kept != 0 : live) && have_tracked)
+        for_each_posting(tracked, km, [&](uint32_t g) { consider(g, best_ani, best_rank); }, &lts, &ltr);
+    for_each_long_run(lts, ltr, [&](int src, uint64_t rs, uint64_t rm) {
+        uint32_t r_l = 0xFFFFFFFFu;
+        double a_l = -1.0;
+        long_run_for_each(tracked, rs, rm, [&](uint32_t g) { consider(g, a_l, r_l); });
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const uint32_t r_o = (uint32_t)__shfl_xor((int)r_l, d);
+            const double a_o = __shfl_xor(a_l, d);
+            if (winner_beats(a_o, r_o, a_l, r_l)) { a_l = a_o; r_l = r_o; }
+        }
+        if (lane == src && winner_beats(a_l, r_l, best_ani, best_rank)) { best_ani = a_l; best_rank = r_l; }
+    });
+    return best_rank;
+}
 #endif
 
 // Layout of the result block, identical on the device (one buffer, ONE device->host copy) and in pinned host memory:

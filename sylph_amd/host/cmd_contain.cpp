@@ -191,6 +191,35 @@ const uint64_t* upload_offsets(sylph_ctx* ctx, const std::vector<uint64_t>& off,
     return (const uint64_t*)dev;
 }
 
+// --log-reassignments, contain.rs:432-456: the passing genomes by index, then how many k-mers of which genome the winner table
+// hands to which other one.  The device holds the winner table (resident indexes + the passing list); the host gathers its copy
+// of the passing genomes' k-mers — out of the mapping, which is unaligned: memcpy — into one buffer, in the order of `stats`, and
+// sylph_db_reassign_edges counts.  The reference prints an edge when its count is above 10, in its hash map's order; here the
+// edges come sorted by (loser, winner).  The block is ONE write.
+void log_reassignment_edges(const std::vector<GenomeSketch>& genome_sketches, const std::vector<AniResult>& stats, const std::vector<uint32_t>& pg,
+                            const std::vector<double>& pa, uint64_t threads, sylph_db* rdb) {
+    std::vector<uint64_t> off(stats.size() + 1, 0);
+    for (size_t i = 0; i < stats.size(); i++) off[i + 1] = off[i] + genome_sketches[stats[i].genome_index].n_kmers();
+    std::vector<uint64_t> kmers(off.back());
+    parallel_for(stats.size(), threads, [&](size_t i) {
+        const GenomeSketch& g = genome_sketches[stats[i].genome_index];
+        if (g.n_kmers()) memcpy(kmers.data() + off[i], g.kmers_bytes(), g.n_kmers() * 8);
+    });
+    sylph_reassign_edge* edges = nullptr;
+    uint64_t n_edges = 0;
+    hip_check(sylph_db_reassign_edges(rdb, kmers.data(), off.data(), SYLPH_MEM_HOST, pg.data(), pa.data(), (uint32_t)pg.size(), 11, &edges, &n_edges),
+              "sylph_db_reassign_edges");
+    std::vector<std::string> lines{"------------- Logging k-mer reassignments -----------------"};
+    for (size_t i = 0; i < stats.size(); i++) {
+        const GenomeSketch& g = genome_sketches[stats[i].genome_index];
+        lines.push_back("Index\t" + std::to_string(i) + "\t" + g.file_name + "\t" + g.first_contig_name);
+    }
+    for (uint64_t e = 0; e < n_edges; e++)
+        lines.push_back(std::to_string(edges[e].winner) + "->" + std::to_string(edges[e].loser) + "\t" + std::to_string(edges[e].count) + "\tkmers reassigned");
+    sylph_free(edges);
+    info_block(lines);
+}
+
 // ---- one sample's results -> statistics -> (profile: reassignment pass) -> TSV rows.  `cc / coff / covs` are the first-pass
 // views (coverage values cov_width bytes each); the sample table is given where it lies (tk / tc / tn in tmem) for the
 // reassignment probe; S carries the metadata, and the counts on the host when -u needs them.
@@ -218,6 +247,7 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
     // order of `gs` so that the output does not depend on the interleaving.  Between the two halves of a genome's statistics lies its
     // confidence interval: the genomes that want one are resampled together (bootstrap_batch: one device call, or the host's loop).
     const BootstrapRoute ci_route = args.no_ci ? BootstrapRoute::Host : bootstrap_route();
+    const bool log_reassign = args.pseudotax && args.log_reassignments;   // (`query` ignores the flag, as the reference does)
     auto run_stats = [&](const std::vector<size_t>& gs, const void* base, uint32_t width, const uint64_t* off, const uint32_t* lost) {
         std::vector<StatsHead> heads(gs.size());
         parallel_for(gs.size(), args.threads, [&](size_t i) {
@@ -226,6 +256,17 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
             heads[i] = stats_head(args, cv, genome_sketches[g].n_kmers(), S.k, lost ? std::optional<size_t>((size_t)lost[g]) : std::nullopt);
             if (heads[i].result) heads[i].result->genome_index = g;
         });
+        if (lost && log_reassign) {                                  // contain.rs:749-761: passed before the reassignment, not after it
+            const double min_ani = args.minimum_ani ? *args.minimum_ani / 100. : MIN_ANI_P_DEF;
+            for (size_t i = 0; i < gs.size(); i++) {
+                if (!heads[i].rejected) continue;
+                const GenomeSketch& g = genome_sketches[gs[i]];
+                char num[160];
+                snprintf(num, sizeof(num), " has ANI = %.2f < %.2f after reassigning %zu k-mers (%zu contained k-mers after reassign)",
+                         heads[i].rejected_ani * 100., min_ani * 100., (size_t)lost[gs[i]], heads[i].rejected_contain_count);
+                info("Genome/contig " + g.file_name + "/" + g.first_contig_name + num);
+            }
+        }
         std::vector<CiItem> ci;                                      // (gs ascends, and with it the rows of the coverage values)
         for (size_t i = 0; i < gs.size(); i++)
             if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, off[gs[i]], off[gs[i] + 1], heads[i].keep, heads[i].n_total});
@@ -254,6 +295,7 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         std::vector<uint32_t> pg(stats.size());
         std::vector<double> pa(stats.size());
         for (size_t i = 0; i < stats.size(); i++) { pg[i] = (uint32_t)stats[i].genome_index; pa[i] = stats[i].final_est_ani; }
+        if (log_reassign) log_reassignment_edges(genome_sketches, stats, pg, pa, args.threads, rdb);
         const uint32_t *cc2 = nullptr, *covs2 = nullptr, *lost2 = nullptr;
         const uint64_t* coff2 = nullptr;
         uint64_t ncov2 = 0;

@@ -21,6 +21,12 @@ inline void hip_check(int rc, const char* what) {
 }
 inline void warn(const std::string& m) { fprintf(stderr, "WARN  [sylph_hip] %s\n", m.c_str()); }
 inline void info(const std::string& m) { fprintf(stderr, "INFO  [sylph_hip] %s\n", m.c_str()); }
+// several info lines in ONE write: a block that samples reported from different threads must not interleave inside
+inline void info_block(const std::vector<std::string>& lines) {
+    std::string all;
+    for (const auto& l : lines) all += "INFO  [sylph_hip] " + l + "\n";
+    fwrite(all.data(), 1, all.size(), stderr);
+}
 
 template <class T>
 std::vector<T> take(T* p, uint64_t n) {

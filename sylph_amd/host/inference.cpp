@@ -198,7 +198,12 @@ StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_
     const auto opt_est_ani = ani_from_counts(opt_lambda, (double)k, whole.n_nonzero, n_total);   // :737
     r.final_est_ani = (!opt_lambda || !opt_est_ani || args.no_adj) ? r.naive_ani : *opt_est_ani;   // :739-744
     const double min_ani = args.minimum_ani ? *args.minimum_ani / 100. : (args.pseudotax ? MIN_ANI_P_DEF : MIN_ANI_DEF);
-    if (r.final_est_ani < min_ani) return h;                                 // :746-764
+    if (r.final_est_ani < min_ani) {                                         // :746-764
+        h.rejected = true;
+        h.rejected_ani = r.final_est_ani;
+        h.rejected_contain_count = contain_count;
+        return h;
+    }
     h.want_ci = !args.no_ci && opt_lambda;                                   // :766-773
     h.keep = keep;
     h.n_total = n_total;

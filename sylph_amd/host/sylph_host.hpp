@@ -323,7 +323,16 @@ std::optional<AniResult> stats_from_covs(const ContainArgs& args, std::vector<ui
 namespace bootstrap_plan = ::sylph::bootstrap_plan;
 constexpr uint64_t BOOTSTRAP_SEED = 7;      // fastrand::seed(7), contain.rs:854
 constexpr uint32_t BOOTSTRAP_ITERS = 100;   // contain.rs:857
-struct StatsHead { std::optional<AniResult> result; bool want_ci = false; size_t keep = 0, n_total = 0; };
+// rejected: the genome fell below the ANI cut (:749) — its final_est_ani and contain_count, for the line `--log-reassignments`
+// prints about it after the reassignment pass (:752-760) and for nothing else.
+struct StatsHead {
+    std::optional<AniResult> result;
+    bool want_ci = false;
+    size_t keep = 0, n_total = 0;
+    bool rejected = false;
+    double rejected_ani = 0.;
+    size_t rejected_contain_count = 0;
+};
 StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost);
 std::optional<double> lambda_from_summary(const bootstrap_plan::Summary& s, double min_count_correct);                 // inference.rs:207
 std::optional<double> ani_from_counts(std::optional<double> lambda, double k, size_t contain_count, size_t n_total);   // contain.rs:817
@@ -356,6 +365,7 @@ struct ContainCmdArgs : ContainArgs {   // cmdline.rs:88-160
     std::optional<std::string> file_list, out_file_name;
     uint64_t k = 31, c = 200, min_spacing_kmer = 30;
     bool individual = false;
+    bool log_reassignments = false;   // --log-reassignments (profile only, cmdline.rs:142): the k-mer reassignment log on stderr
     bool exact_dedup = false;   // --exact-dedup: raw pairs are deduplicated with the exact marker set (the reference forces its cuckoo filter, contain.rs:591)
     int gpus = 1;               // --gpus N|all (-1): raw samples are spread over N GPUs, each with a replica of the database (not in the reference: its rayon pool spans the machine by itself)
 };
