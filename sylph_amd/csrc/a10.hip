@@ -556,10 +556,9 @@ static Filter filter_geometry(const sylph_sketch* sk, int j) {
 // The partitioned pass over the session's occurrences where they lie (slots of its one batch, or the dense arrays).
 static void a10_mark_partitioned(sylph_sketch* sk) {
     sylph_ctx* ctx = sk->ctx;
-    const bool slotted = sk->pend.live;
-    const bool deferred = slotted && sk->pend.deferred;
-    const uint64_t n_slots = slotted ? (uint64_t)sk->pend.n_blk * sk->pend.slot_cap : sk->n_occ;
-    const uint64_t n_expect = deferred ? std::max<uint32_t>(1, sk->pend.n_expect) : (slotted ? sk->pend.n : sk->n_occ);
+    const Occurrences occ = sk->occurrences();
+    const bool slotted = occ.slotted();
+    const uint64_t n_slots = occ.n_slots, n_expect = occ.n_expect;
     HostPhase ph(ctx, "finish: a10 filter marks (partitioned)");
     sk->a10_tail.reserve(16);
     uint32_t* tail = sk->a10_tail.as<uint32_t>();
@@ -617,7 +616,7 @@ static void a10_mark_partitioned(sylph_sketch* sk) {
     hipLaunchKernelGGL(a10_range_kernel<256>, dim3(((B + 7) / 8) * 8 * split), dim3(256), (size_t)env_pad, ctx->stream, b_pairs.as<uint64_t>(),
                        part_cbase(b_hist.as<uint32_t>(), B, n_tiles), B, bm.mult, slot_mult, split, f0, const_cast<OccRec*>(oin.recs), tail);
     SY_HIP(hipGetLastError());
-    sk->a10_state = 1;
+    sk->a10_marks = FilterMarks::Unread;
     if (ctx->profile) ctx->stats["a10_part"].launches++;              // (tests ask sylph_ctx_kernel_stats which pass ran)
     // (the buffers go back to the pool here; stream order keeps them alive for the kernels queued above)
 }
@@ -627,41 +626,29 @@ static void a10_mark_walk(sylph_sketch* sk);
 // Which pass: the partitioned one wherever the first filter is sure (the occurrence count is known) or expected (deferred
 // batches: the verdict words tell) to take every operation; the phase walk for samples that make the filter grow.
 void a10_mark(sylph_sketch* sk) {
-    if (!sk->filter_dedup() || sk->a10_state != 0) return;
+    if (!sk->filter_dedup() || sk->a10_marks != FilterMarks::None) return;
     SY_REQUIRE(sk->dedup_capacity >= 1 && sk->dedup_capacity < (1ull << 31), "dedup_capacity out of range");
-    static const int env_force = [] { const char* e = getenv("SYLPH_HIP_A10"); return !e ? 0 : !strcmp(e, "walk") ? 1 : !strcmp(e, "part") ? 2 : 0; }();
-    const int force = sk->a10_force ? sk->a10_force : env_force;
-    const bool slotted = sk->pend.live, deferred = slotted && sk->pend.deferred;
-    const uint64_t n_slots = slotted ? (uint64_t)sk->pend.n_blk * sk->pend.slot_cap : sk->n_occ;
-    const uint64_t n_ops = 2 * (deferred ? (uint64_t)sk->pend.n_expect + sk->pend.n_expect / 8 : (slotted ? sk->pend.n : sk->n_occ));
-    const bool fits = n_slots < (1ull << 31) && n_ops <= sk->dedup_capacity && sk->n_plain == 0;
-    if (n_slots == 0) { sk->a10_state = 2; return; }
-    if (force != 1 && fits) a10_mark_partitioned(sk);
+    const Occurrences occ = sk->occurrences();
+    const bool fits = occ.n_slots < (1ull << 31) && 2 * occ.n_expect_filter <= sk->dedup_capacity && occ.n_plain == 0;
+    if (occ.n_slots == 0) { sk->a10_marks = FilterMarks::Settled; return; }
+    if (sk->a10_force != 1 && fits) a10_mark_partitioned(sk);
     else a10_mark_walk(sk);
 }
 
-// The verdict words of the partitioned pass, read by the caller together with its own tail: false = the marks were no good (a
-// bucket with more copies of one class than a workgroup takes; more operations than the first filter holds) and the phase walk
-// has marked the records again — on the dense arrays: whoever partitioned the slots starts over.
+// The verdict words of the partitioned pass, read by the caller together with its own tail or on their own: false = the marks are no
+// good (a bucket with more copies of one class than a workgroup takes; more operations than the first filter holds) and stay
+// unaccepted: the finish loop sends the sample through the walk (a10_remark_walk).  Good marks are accepted here, nothing else happens.
 bool a10_verdict(sylph_sketch* sk, const uint32_t words[2]) {
-    if (sk->a10_state != 1) return true;
-    if (words[0] == 0 && (uint64_t)words[1] <= sk->dedup_capacity) { sk->a10_state = 2; return true; }
-    if (sk->ctx->profile) sk->ctx->stats["a10_redo"].launches++;       // (tests ask sylph_ctx_kernel_stats whether this road was taken)
-    a10_mark_walk(sk);
-    return false;
+    if (sk->a10_marks != FilterMarks::Unread) return true;
+    if (words[0] != 0 || (uint64_t)words[1] > sk->dedup_capacity) return false;
+    sk->a10_marks = FilterMarks::Settled;
+    return true;
 }
 
-void a10_settle(sylph_sketch* sk) {
-    if (!sk->filter_dedup()) return;
-    for (int round = 0; round < 4 && sk->a10_state != 2; round++) {
-        if (sk->a10_state == 0) { a10_mark(sk); continue; }
-        // the verdict of a deferred batch first: a batch that is redone loses its marks (redo_deferred_batch resets a10_state)
-        if (sk->pend.live && sk->pend.deferred) { resolve_deferred_slots(sk); if (sk->a10_state != 1) continue; }
-        uint32_t words[2] = {0, 0};
-        sk->ctx->read_back(words, sk->a10_tail.p, 8);
-        a10_verdict(sk, words);
-    }
-    SY_REQUIRE(sk->a10_state == 2, "internal: the filter marks did not settle");
+// ... and the phase walk marks the records again — on the dense arrays: whoever partitioned the slots starts over.
+void a10_remark_walk(sylph_sketch* sk) {
+    if (sk->ctx->profile) sk->ctx->stats["a10_redo"].launches++;       // (tests ask sylph_ctx_kernel_stats whether this road was taken)
+    a10_mark_walk(sk);
 }
 
 // Marks (RID_A10_BIT) every occurrence of a paired session for which sketch.rs:747 / :754 would have found its (k-mer, markers)
@@ -669,7 +656,7 @@ void a10_settle(sylph_sketch* sk) {
 static void a10_mark_walk(sylph_sketch* sk) {
     sylph_ctx* ctx = sk->ctx;
     flush_pending_slots(sk);
-    sk->a10_state = 2;
+    sk->a10_marks = FilterMarks::Settled;
     const uint64_t n = sk->n_occ;
     if (!n) return;
     SY_REQUIRE(n < (1ull << 32), "more than 2^32-1 seed occurrences in one sample");

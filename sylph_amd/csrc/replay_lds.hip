@@ -301,7 +301,7 @@ struct FinishPass {
                            ra.tmp_k, ra.tmp_c, w.boff, w.d_off, w.chunk_rows, w.chunk_removed, w.n_distinct, B, ipt,
                            sk->out_k.as<uint64_t>(), sk->out_c.as<uint32_t>(), w.ovf_list, w.mid_list, w.large_list, skip_if_listed,
                            d_tail, deferred ? slot_meta_of(sk, sk->pend.n_blk).state_words : (const uint32_t*)nullptr,
-                           sk->a10_state == 1 ? sk->a10_tail.as<uint32_t>() : (const uint32_t*)nullptr, ra.p_nv);
+                           sk->a10_marks == FilterMarks::Unread ? sk->a10_tail.as<uint32_t>() : (const uint32_t*)nullptr, ra.p_nv);
         SY_HIP(hipGetLastError());
     }
     void read_tail() {
@@ -388,20 +388,20 @@ struct FinishPass {
 
 }  // namespace
 
-bool finish_bucketed(sylph_sketch* sk) {
+FinishOutcome finish_bucketed(sylph_sketch* sk) {
     sylph_ctx* ctx = sk->ctx;
-    const bool slotted = sk->pend.live;                // the sample's one batch, still in its slots (reads.hip)
+    const Occurrences occ = sk->occurrences();
+    const bool slotted = occ.slotted();                // the sample's one batch, still in its slots (reads.hip)
     // deferred verdict (sketch_session.h PendingSlots): the number of occurrences is not known on the host — geometry from the
     // expectation, capacities from the upper bound, every count the kernels need from device memory, the verdict read with the tail
-    const bool deferred = slotted && sk->pend.deferred;
-    const uint32_t n_cap = slotted ? sk->pend.n : (uint32_t)sk->n_occ;      // what the arrays must hold
-    const uint32_t n_all = deferred ? std::max<uint32_t>(1, sk->pend.n_expect) : n_cap;
+    const bool deferred = occ.deferred();
+    const uint32_t n_cap = occ.n_cap, n_all = occ.n_expect;
     sk->n_out = 0;
     sk->dup_removed = 0;
-    if (n_cap == 0) return true;
-    if (sk->c < 2) return false;   // c = 1: valid hashes reach the top bit that marks invalid occurrences
+    if (n_cap == 0) return FinishOutcome::Done;
+    if (sk->c < 2) return FinishOutcome::Declined;   // c = 1: valid hashes reach the top bit that marks invalid occurrences
     // bucket geometry: B = n / bucket_target equal hash ranges (replay_plan.h); one-word ranking keys leave room for the largest index
-    const BucketMap bm = make_bucket_map(sk->c, n_all, ctx->bucket_target, slotted ? (uint64_t)sk->pend.n_blk * sk->pend.slot_cap : (uint64_t)n_all);
+    const BucketMap bm = make_bucket_map(sk->c, n_all, ctx->bucket_target, occ.n_slots);
     const uint32_t B = bm.B;
     // partition geometry: F = 2^fine_bits buckets per coarse range (about 512 ranges), tiles of occurrences
     const PartGeom geom = part_geometry(B);
@@ -479,37 +479,31 @@ bool finish_bucketed(sylph_sketch* sk) {
     p.close_table(1);
     p.read_tail();
     const FinishTail& host = p.host;
+    // What the three answers mean for the sample is the finish loop's business (finish_plan.h); here they are only told apart, the
+    // seeding verdict first: of a batch that was not one for the short-read kernel nothing else in the block means anything.
     if (deferred) {
-        if (host.verdict[0] || host.verdict[1]) {  // not a batch for the short-read kernel after all: the checked push, then from the top
-            redo_deferred_batch(sk);
-            a10_mark(sk);                          // (filter dedup: the marks went with the slots)
-            return finish_bucketed(sk);
-        }
+        if (host.verdict[0] || host.verdict[1]) return FinishOutcome::SeedingBad;
         sk->pend.deferred = false;                 // the verdict is in: from here on an ordinary slotted sample ...
         sk->pend.n = host.n_found;                 // ... whose occurrence count is known (whoever flushes the slots to the dense arrays needs it)
     }
-    // filter dedup: were the partitioned pass's marks good (a10.hip)?  If not the phase walk has marked the records again, dense: from the top
-    if (!a10_verdict(sk, host.a10_words)) return finish_bucketed(sk);
-    if (host.overflow) return false;             // inconsistent bounds (defensive): the generic path redoes the sample
+    if (!a10_verdict(sk, host.a10_words)) return FinishOutcome::MarksBad;   // filter dedup: the partitioned pass's marks (a10.hip)
+    if (host.overflow) return FinishOutcome::Declined;   // inconsistent bounds (defensive)
     p.count_roads();
-    if (plain && host.n_ovf) {
-        // k-mers more than a thousand deep in a marker-less sample: write the occurrence records after all and take the usual
-        // kernels from the start (their overflow path works on records and on the index permutation)
-        materialise_plain_records(sk);
-        return finish_bucketed(sk);
-    }
+    // k-mers more than a thousand deep in a marker-less sample: it takes the usual kernels after all (their overflow path works on
+    // records and on the index permutation)
+    if (plain && host.n_ovf) return FinishOutcome::NeedsRecords;
     if (host.n_mid || host.n_large) {
         p.run_listed_configurations();
-        if (host.overflow) return false;
+        if (host.overflow) return FinishOutcome::Declined;
     }
     unsigned long long removed_extra = 0;
     if (host.n_ovf) {
-        if (ctx->finish_mode == 2 || host.n_ovf > 4096) return false;
+        if (ctx->finish_mode == 2 || host.n_ovf > 4096) return FinishOutcome::Declined;
         removed_extra = p.run_overflowing_buckets();
     }
     sk->n_out = host.n_seg;
     sk->dup_removed = host.removed + removed_extra;
-    return true;
+    return FinishOutcome::Done;
 }
 
 }  // namespace sylph

@@ -4,7 +4,7 @@
 //             process_batch: the short-read kernel (reads.hip) or the position road (position_road.hip: K1 seeds -> survivors by flat
 //             position -> K2 annotate) appends the batch's occurrences to the session in file order
 //   finish(): K3, the replay of dup_removal_lsh_full_exact: per bucket in LDS (replay_lds.hip), else device-wide (replay_generic.hip)
-//             -> (k-mer, count) table in ascending k-mer order
+//             -> (k-mer, count) table in ascending k-mer order; one loop over finish_plan.h decides what a late answer from the device undoes
 #include <algorithm>
 
 #include "common.h"
@@ -125,9 +125,7 @@ static void process_batch(sylph_sketch* sk, const uint8_t* d_bases, uint32_t pha
 // the session goes back to where it was before that push and the batch — its memory is still the caller's, that was the deal —
 // runs through the checked push (which falls back to the position kernel / spill regions as needed).
 void redo_deferred_batch(sylph_sketch* sk) {
-    const PendingSlots d = sk->pend;
-    sk->pend = PendingSlots{};
-    sk->a10_state = 0;                          // whatever the filter pass marked in the slots is gone with them (a10.hip)
+    const PendingSlots d = sk->drop_pending_slots();
     sk->rec_base -= d.n_records;
     if (sk->ctx->profile) sk->ctx->stats["deferred_redo"].launches++;
     NoBorrow guard(sk);
@@ -246,21 +244,41 @@ static void sketch_finish_impl(sylph_sketch* sk) {
     DeviceGuard dg(ctx->device);
     HostPhase ph_total(ctx, "finish: total incl. readback");
     SY_REQUIRE(sk->n_occ + sk->pend.n < (1ull << 32) - 1, "more than 2^32-2 seed occurrences in one sample");
-    a10_mark(sk);                                // the reference's default dedup for pairs (no-op otherwise): the filter's answers go into the records first
-    // fast path: bucket partition + in-LDS replay (replay_lds.hip); falls through to the device-wide sort path
-    // below when a bucket does not fit in LDS (some k-mer with thousands of occurrences)
-    if (ctx->finish_mode != 1) {
-        if (finish_bucketed(sk)) { sk->finished = true; return; }
-        SY_REQUIRE(ctx->finish_mode != 2, "bucket finish overflowed and finish=bucket forbids the fallback");
-    }
-    a10_settle(sk);            // (the partitioned filter pass's verdict, if finish_bucketed left before reading it)
-    flush_pending_slots(sk);   // the device-wide path works on the dense file-order arrays ...
-    if (sk->filter_dedup() && sk->a10_state != 2) a10_settle(sk);   // (... and a deferred batch that was redone just now is marked again)
-    materialise_plain_records(sk);   // ... and on occurrence records
     sk->n_out = 0;
     sk->dup_removed = 0;
-    generic_replay(ctx, sk->hash.as<uint64_t>(), sk->recs.as<OccRec>(), (uint32_t)sk->n_occ, sk->paired, sk->dedup_mode(), sk->out_k, sk->out_c, sk->n_out, sk->dup_removed);
-    sk->finished = true;
+    if (!sk->pend.live && sk->n_occ == 0) { sk->finished = true; return; }   // nothing came: the empty table, at every c and in every mode
+    // finish_plan.h says what comes next — the filter's marks (the reference's default dedup for pairs), an attempt at the fast path
+    // (bucket partition + in-LDS replay, replay_lds.hip), what a bad answer from the device undoes, and at last the device-wide path —
+    // from where the occurrences lie, what their records carry and the last answer; this loop does it and reports back.
+    using finish_plan::Action;
+    static_assert((int)finish_plan::Mode::Auto == 0 && (int)finish_plan::Mode::Generic == 1 && (int)finish_plan::Mode::Bucket == 2, "the ctx option \"finish\"");
+    FinishOutcome last = FinishOutcome::None;
+    for (;;) {
+        const finish_plan::State st{sk->occurrences().place, sk->a10_marks, sk->n_plain != 0, sk->filter_dedup(), (finish_plan::Mode)ctx->finish_mode, sk->c < 2};
+        switch (finish_plan::next(st, last)) {
+        case Action::Mark: a10_mark(sk); break;
+        case Action::Attempt:
+            last = finish_bucketed(sk);
+            if (last == FinishOutcome::Done) { sk->finished = true; return; }
+            break;
+        case Action::RedoDeferred: redo_deferred_batch(sk); break;
+        case Action::RemarkWalk: a10_remark_walk(sk); break;
+        case Action::WriteRecords: materialise_plain_records(sk); break;
+        case Action::ReadSeedingVerdict: resolve_deferred_slots(sk); break;
+        case Action::ReadFilterVerdict: {
+            uint32_t words[2] = {0, 0};
+            ctx->read_back(words, sk->a10_tail.p, 8);
+            if (!a10_verdict(sk, words)) last = FinishOutcome::MarksBad;
+            break;
+        }
+        case Action::Fail: SY_REQUIRE(false, "bucket finish overflowed and finish=bucket forbids the fallback"); break;
+        case Action::Replay:
+            flush_pending_slots(sk);   // the device-wide path works on the dense file-order arrays
+            generic_replay(ctx, sk->hash.as<uint64_t>(), sk->recs.as<OccRec>(), (uint32_t)sk->n_occ, sk->paired, sk->dedup_mode(), sk->out_k, sk->out_c, sk->n_out, sk->dup_removed);
+            sk->finished = true;
+            return;
+        }
+    }
 }
 
 }  // namespace sylph

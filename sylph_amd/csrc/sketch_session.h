@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "finish_plan.h"
 #include "replay_plan.h"
 #include "seed_plan.h"
 
@@ -31,12 +32,18 @@ using replay_plan::key_shift;                 // replay_plan.h: key = hash >> ke
 constexpr int DEDUP_EXACT = 0, DEDUP_NONE = 1, DEDUP_FILTER = 2;
 void generic_replay(sylph_ctx* ctx, const uint64_t* d_hash, const OccRec* d_recs, uint32_t n_all, bool paired, int dedup,
                     DevBuf& out_k, DevBuf& out_c, uint64_t& n_out, uint64_t& removed_out);   // replay_generic.hip
-bool finish_bucketed(sylph_sketch* sk);       // replay_lds.hip: bucket partition + in-LDS replay; false = not a sample for it, the caller replays device-wide
+// finish_plan.h: the finish is one loop (sketch.hip sketch_finish_impl) that asks the plan what to do next, does it, and feeds the answer back
+using FinishOutcome = finish_plan::Outcome;
+using FilterMarks = finish_plan::Marks;
+// replay_lds.hip: ONE attempt at bucket partition + in-LDS replay.  It reads the seeding verdict, the filter verdict and its own tail in one
+// block and says what happened; it undoes nothing and starts nothing over.  On a good seeding verdict the slots' count is recorded (pend)
+// and good filter marks are accepted before it returns, whatever it returns.
+FinishOutcome finish_bucketed(sylph_sketch* sk);
 // reads.hip: one lane per record, seeding + markers fused; false = it declines the batch, having taken nothing
 bool push_short_reads(sylph_sketch* sk, const uint8_t* d_bases, uint32_t phase, const uint64_t* d_off, uint64_t n_records, uint64_t n_bases, int enc);
 void a10_mark(sylph_sketch* sk);              // a10.hip: marks the records (partitioned pass where one filter suffices, else the phase walk)
-void a10_settle(sylph_sketch* sk);            // a10.hip: marks if not marked, reads the partitioned pass's verdict (synchronises), redoes with the walk if it was bad
-bool a10_verdict(sylph_sketch* sk, const uint32_t words[2]);   // a10.hip: the verdict words read by the caller (finish_bucketed's tail); false = redone with the walk: start over
+bool a10_verdict(sylph_sketch* sk, const uint32_t words[2]);   // a10.hip: are the partitioned pass's marks good, by its two verdict words?  Good marks are accepted (FilterMarks::Settled); nothing else happens
+void a10_remark_walk(sylph_sketch* sk);       // a10.hip: the phase walk over a sample whose verdict was bad; leaves it dense
 // A single-end session whose records carry no dedup markers so far (long reads: sketch.rs:922-927 passes no marker above 400
 // bases; --no-dedup) keeps only the hashes of its occurrences — nothing the replay looks at besides the hash exists for them
 // (no marker, no mate) — and finish() counts them without occurrence records.  The first batch that may carry markers (or a
@@ -56,7 +63,7 @@ struct PendingSlots {
     // occurrences — has NOT been read back yet.  Only for a session whose caller keeps the batch's memory valid until finish
     // ("borrow_until_finish": the pipeline's device batches, bench.py): finish_bucketed sizes everything from `n_expect` / `n`
     // (estimate / upper bound), takes every count from device memory, and reads the verdict together with its own tail block —
-    // one host round trip per sample instead of two.  A bad verdict redoes the batch the ordinary way (redo_deferred_batch).
+    // one host round trip per sample instead of two.  A bad verdict is the finish loop's to act on (finish_plan.h: redo_deferred_batch).
     bool deferred = false;
     uint32_t n_expect = 0;
     const uint8_t* bases = nullptr;            // the borrowed batch, for the redo
@@ -67,6 +74,20 @@ struct PendingSlots {
 };
 void resolve_deferred_slots(sylph_sketch* sk);   // reads.hip: reads the verdict now (block total + flags); may redo the batch
 void redo_deferred_batch(sylph_sketch* sk);      // sketch.hip: the deferred batch once more, through the ordinary (checked) push
+// Where the occurrences lie and how many there are, for everything that sizes a pass over them (a10_mark, a10_mark_partitioned,
+// finish_bucketed).  A deferred batch has no count on the host: an upper bound for what arrays must hold, and TWO expectations, kept
+// apart because results (which pass marks; the bucket geometry) depend on each: the seeding plan's for geometry, an eighth more for
+// the question whether one filter takes every operation.
+struct Occurrences {
+    finish_plan::Place place;
+    uint64_t n_slots;          // the region a pass walks: the batch's slots (blocks x slots per block), or the dense arrays
+    uint32_t n_cap;            // what arrays sized by occurrence must hold (deferred: an upper bound)
+    uint32_t n_expect;         // geometry: the count; deferred: the expected count, at least 1
+    uint64_t n_expect_filter;  // fits-one-filter test: the count; deferred: the expectation + 1/8
+    uint64_t n_plain;          // the first n_plain have no OccRec (marker-less single-end batches)
+    bool slotted() const { return place != finish_plan::Place::Dense; }
+    bool deferred() const { return place == finish_plan::Place::Deferred; }
+};
 }  // namespace sylph
 
 struct sylph_sketch {
@@ -77,9 +98,9 @@ struct sylph_sketch {
     bool borrow_until_finish = false;   // the caller keeps device batches valid until finish (sylph_sketch_set_option; see PendingSlots)
     double dedup_fpr = 0.;              // > 0 (paired sessions): the reference's default dedup over a cuckoo filter of this false-positive probability (a10.hip)
     uint64_t dedup_capacity = 10000000; // its initial capacity (sketch.rs:800)
-    // a10.hip: 0 = the records carry no marks (yet / any more: a batch was pushed or redone), 1 = marked by the partitioned pass, whose
-    // verdict words (a10_tail: buckets that overflowed, operations found) nobody has read yet, 2 = marked for good
-    int a10_state = 0;
+    // a10.hip: None = the records carry no marks (yet / any more: the slots that held them were given up), Unread = marked by the
+    // partitioned pass, whose verdict words (a10_tail: buckets that overflowed, operations found) nobody has read yet, Settled = for good
+    sylph::FilterMarks a10_marks = sylph::FilterMarks::None;
     int a10_force = 0;                  // session/test knob ("a10": 0 auto, 1 always the walk, 2 the partitioned pass wherever one filter suffices)
     bool filter_dedup() const { return paired && !no_dedup && dedup_fpr > 0.; }
     int dedup_mode() const { return no_dedup ? sylph::DEDUP_NONE : (filter_dedup() ? sylph::DEDUP_FILTER : sylph::DEDUP_EXACT); }
@@ -96,7 +117,21 @@ struct sylph_sketch {
     sylph::DevBuf out_k, out_c;           // final table
     uint64_t n_out = 0, dup_removed = 0;
     sylph::DevBuf counters;               // 16 u32 words; in use: CNT_SURVIVORS, CNT_MARKED (below); each is cleared by the path that uses it
-    sylph::DevBuf a10_tail;               // a10.hip: verdict words of the partitioned pass (see a10_state)
+    sylph::DevBuf a10_tail;               // a10.hip: verdict words of the partitioned pass (see a10_marks)
+    sylph::Occurrences occurrences() const {
+        using sylph::finish_plan::Place;
+        if (!pend.live) return {Place::Dense, n_occ, (uint32_t)n_occ, (uint32_t)n_occ, n_occ, n_plain};
+        const uint64_t region = (uint64_t)pend.n_blk * pend.slot_cap;
+        if (!pend.deferred) return {Place::Known, region, pend.n, pend.n, pend.n, n_plain};
+        return {Place::Deferred, region, pend.n, std::max<uint32_t>(1, pend.n_expect), (uint64_t)pend.n_expect + pend.n_expect / 8, n_plain};
+    }
+    // The session gives up the slots of its (deferred) batch — and with them whatever marks the filter pass left in their records.
+    sylph::PendingSlots drop_pending_slots() {
+        const sylph::PendingSlots d = pend;
+        pend = sylph::PendingSlots{};
+        a10_marks = sylph::FilterMarks::None;
+        return d;
+    }
     explicit sylph_sketch(sylph_ctx* cx)
         : ctx(cx), hash(cx), recs(cx), slot_bases{sylph::DevBuf(cx), sylph::DevBuf(cx)}, slot_off{sylph::DevBuf(cx), sylph::DevBuf(cx)},
           slot_rec(cx), slot_key(cx), slot_meta(cx), batch_ascii(cx), fq_bases(cx), fq_off(cx), out_k(cx), out_c(cx), counters(cx), a10_tail(cx) {}
