@@ -129,13 +129,14 @@ namespace {
 using shardplan::MAX_LOCAL;                  // samples a rank may contribute to one batch (shard_plan.h: the exchange's bookkeeping,
 using shardplan::MAX_WORLD;                  // host-compilable — tests/test_dist.py drives it under gloo)
 
-// split[s * (W + 1) + j] = first entry of sample s whose k-mer is >= bounds[j]   (j = 0..W; the tables are ascending)
+// split[s * (W + 1) + j] = first entry of sample s whose k-mer is >= bounds[j] (j < W; the tables are ascending); split[..W] = the
+// table's length: the last range is open-ended, as the last shard's index is (shard_plan.h split_at)
 __global__ __launch_bounds__(256) void split_kernel(const SampleRef* __restrict__ refs, uint32_t n_samples, const uint64_t* __restrict__ bounds,
                                                     uint32_t W, uint64_t* __restrict__ split) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_samples * (W + 1)) return;
     const uint32_t s = t / (W + 1), j = t % (W + 1);
-    split[t] = shardplan::lower_bound_u64(refs[s].k, refs[s].n, bounds[j]);
+    split[t] = shardplan::split_at(refs[s].k, refs[s].n, bounds, W, j);
 }
 
 // segmented copy in 4-byte words: workgroup (x = segment, y strides)

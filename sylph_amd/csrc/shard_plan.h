@@ -1,7 +1,9 @@
 // shard_plan.h — the bookkeeping of the k-mer-range exchange (shard.hip), free of HIP: which slice of which table goes where, where a
 // received slice lies, which rank owns a hit, where its group starts.  shard.hip runs these on the gathered size blocks between
 // its collectives; tests/test_dist.py compiles the same header with g++ (tests/shard_plan_capi.cpp) and drives it under gloo with
-// world sizes 2 and 3, so the arithmetic that has never met more than one physical GPU is at least exercised rank against rank.
+// world sizes 2 and 3 on the CPU (both cuts, both reductions, the keys 0 and 2^64 - 1); tests/test_gpu_shard_worlds.py runs it inside
+// shard.hip with 3, 5 and 8 ranks sharing one GPU (empty shards, 64 samples from one rank, a step nobody brings anything to, agreed
+// failures).  The arithmetic has never met more than one physical GPU; it has met eight ranks.
 #pragma once
 #include <cstdint>
 #include <algorithm>
@@ -29,6 +31,14 @@ SY_PLAN_HD uint64_t lower_bound_u64(const uint64_t* k, uint64_t n, uint64_t key)
     }
     return lo;
 }
+// split[s][j] of the ascending table k[0..n): the first entry that goes to shard j or beyond (j = 0..W).  The LAST range is open-ended, the
+// way the last shard's index is built (line_index.hip: `last ? 0 : hi`): split[s][W] is the table's length, not lower_bound(bounds[W]).
+// bounds[W] cannot say "beyond every key" (sylph_shard_bounds ends at 2^64 - 1 when that is the largest key; the genome cut always uses
+// {0, ~0, ..}), and with a lower bound there the key 2^64 - 1 belonged to no slice while the last shard held it.  Entries above the
+// database's largest key now travel to the last rank and hit nothing there: a few wasted bytes, never a wrong answer.
+SY_PLAN_HD uint64_t split_at(const uint64_t* k, uint64_t n, const uint64_t* bounds, uint32_t W, uint32_t j) {
+    return j >= W ? n : lower_bound_u64(k, n, bounds[j]);
+}
 // owner of global sample s = the rank r with prefix[r] <= s < prefix[r + 1]
 SY_PLAN_HD uint32_t owner_of_sample(uint64_t s, const uint64_t* prefix, uint32_t world) {
     uint32_t lo = 0, hi = world;
@@ -40,7 +50,7 @@ SY_PLAN_HD uint32_t owner_of_sample(uint64_t s, const uint64_t* prefix, uint32_t
 }
 
 // The all-gathered meta blocks: per rank [n_local | split[MAX_LOCAL][W + 1]] (u64), split[s][j] = first entry of the rank's sample s
-// whose k-mer is >= bounds[j].
+// whose k-mer is >= bounds[j] for j < W, and the table's length for j = W (split_at).
 inline uint64_t meta_words(uint32_t W) { return 1 + (uint64_t)MAX_LOCAL * (W + 1); }
 // whole = 1: a database sharded by GENOME (sylph_db_upload_genome_shard; north_star's wording) — every rank probes every sample in
 // full, so the "slice" of a table for any destination is the whole table [split[0], split[W]) = [0, n): the all-to-all of the slices

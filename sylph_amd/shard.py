@@ -10,7 +10,11 @@ the collectives issued through a `sylph_comm` (RCCL, or callbacks).  This module
                                    device buffer -> host -> gloo -> device), so the library's exchange code runs without RCCL;
 * `model_contain_batch_sharded`  — the same five steps written with numpy on host arrays and a pluggable probe: the executable
                                    specification of the protocol.  tests/test_dist.py runs it under gloo with world_size 2
-                                   and 3 (the CPU oracle standing in for the HIP probe) against the single-process answer.
+                                   and 3 (the CPU oracle standing in for the HIP probe) against the single-process answer,
+                                   also over a database and samples that hold the keys 0 and 2^64 - 1.
+
+The library's exchange itself runs on a GPU with one rank over RCCL and with 2 ranks (tests/test_gpu_parity.py) and 3, 5 and 8 ranks
+(tests/test_gpu_shard_worlds.py) sharing one device through `torch_callback_comm` over gloo.
 """
 import numpy as np
 import torch
@@ -122,8 +126,10 @@ def model_contain_batch_sharded(dist, bounds, n_genomes, samples, probe_fn):
         return out
 
     bounds = np.asarray(bounds, dtype=np.uint64)
-    # 1. slice boundaries of every local table, all-gathered
-    split = [np.searchsorted(k, bounds, side="left") for k, _ in samples]
+    # 1. slice boundaries of every local table, all-gathered.  The last range is open-ended, as the last shard's index is: split[W] is
+    # the table's length (shard_plan.h split_at) — bounds[W] cannot lie beyond the key 2^64 - 1, which the last shard may hold; entries
+    # above the database's largest key travel to the last rank and hit nothing there
+    split = [np.append(np.searchsorted(k, bounds[:world], side="left"), len(k)) for k, _ in samples]
     meta = all_gather_obj(split)
     prefix = np.concatenate([[0], np.cumsum([len(m) for m in meta])])
     # 2. all-to-all of the slices (modelled as an all-gather of the per-destination blocks)

@@ -13,7 +13,7 @@ extern "C" {
 uint32_t sp_max_local() { return MAX_LOCAL; }
 uint64_t sp_meta_words(uint32_t W) { return meta_words(W); }
 uint32_t sp_size_words(uint32_t W) { return size_words(W); }
-uint64_t sp_lower_bound(const uint64_t* k, uint64_t n, uint64_t key) { return lower_bound_u64(k, n, key); }
+uint64_t sp_split_at(const uint64_t* k, uint64_t n, const uint64_t* bounds, uint32_t W, uint32_t j) { return split_at(k, n, bounds, W, j); }
 uint32_t sp_owner(uint64_t s, const uint64_t* prefix, uint32_t W) { return owner_of_sample(s, prefix, W); }
 uint64_t sp_rebase(uint64_t hit, uint64_t first, uint64_t G) { return rebase_hit(hit, first, G); }
 static int g_whole = 0;                       // 1: genome shards (every slice is the whole table)

@@ -2,7 +2,8 @@
 in the HIP library (csrc/shard.hip) and needs a GPU; what runs here is its executable specification,
 sylph_amd.shard.model_contain_batch_sharded — the same five steps on host arrays — with the oracle standing in for the HIP probe.
 Every rank must recover, for its OWN samples, exactly the single-process answer over the WHOLE database.  (tests/test_gpu_parity.py
-runs the library's exchange itself over gloo with two ranks on one GPU, and over RCCL with one rank.)"""
+runs the library's exchange itself over gloo with two ranks on one GPU, and over RCCL with one rank; tests/test_gpu_shard_worlds.py with
+3, 5 and 8 ranks on one GPU.)"""
 import os
 import socket
 
@@ -24,7 +25,11 @@ def _free_port():
     return p
 
 
-def make_db(seed=5, G=37):
+EXTREME = (0, 2**64 - 1)          # the two ends of the key space: no real sketch holds them, the ABI accepts them
+
+
+def make_db(seed=5, G=37, extreme=False):
+    """extreme: genome 13 also holds the keys 0 and 2^64 - 1 (the last k-mer range must be open-ended for the second)."""
     rng = np.random.default_rng(seed)
     thr = O.threshold(200)
     pool = np.unique(rng.integers(0, thr, size=30000, dtype=np.uint64))
@@ -33,14 +38,20 @@ def make_db(seed=5, G=37):
     lens[7] = 49
     genomes = [rng.choice(pool, size=int(n), replace=False) for n in lens]
     genomes[11] = np.concatenate([genomes[11], genomes[11][:5]])       # a k-mer twice in one genome: counted twice (contain.rs:632)
+    if extreme:
+        genomes[13] = np.concatenate([genomes[13], np.array(EXTREME, dtype=np.uint64)])
     return pool, genomes
 
 
-def make_samples(pool, rank, n):
+def make_samples(pool, rank, n, edges=None):
+    """edges: keys every non-empty sample holds besides its draw from the pool (the extreme-key variant: 0, 2^64 - 1 and both sides
+    of every range boundary)."""
     rng = np.random.default_rng(100 + rank)
     out = []
     for i in range(n):
         k = np.sort(rng.choice(pool, size=3000 + 500 * rank + 100 * i, replace=False)) if (rank, i) != (1, 1) else np.zeros(0, np.uint64)
+        if edges is not None and len(k):
+            k = np.union1d(k, np.asarray(edges, dtype=np.uint64))
         out.append((k, rng.integers(0, 9, size=len(k)).astype(np.uint32)))
     return out
 
@@ -59,16 +70,22 @@ def shard_probe(genomes, lo, hi, min_number_kmers=50.0):
     return probe
 
 
-def _worker(rank, world, port, ret):
+def edge_keys(bounds):
+    """0, 2^64 - 1 and, for every boundary, the key on it and the key just below it (the two sides of lower_bound_u64's answer)."""
+    b = [int(x) for x in bounds]
+    return sorted(set(EXTREME) | set(b) | {x - 1 for x in b if x})
+
+
+def _worker(rank, world, port, ret, extreme=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        pool, genomes = make_db()
+        pool, genomes = make_db(extreme=extreme)
         G = len(genomes)
         bounds = SH.shard_bounds(int(max(g.max() for g in genomes if len(g))), world)
         hi = int(bounds[rank + 1]) if rank + 1 < world else 0
-        samples = make_samples(pool, rank, [2, 3, 0][rank])      # different batch sizes per rank, one rank may bring none
+        samples = make_samples(pool, rank, [2, 3, 0][rank], edge_keys(bounds) if extreme else None)      # different batch sizes per rank, one rank may bring none
         cc, covs = SH.model_contain_batch_sharded(dist, bounds, G, samples, shard_probe(genomes, int(bounds[rank]), hi))
         db = np.concatenate(genomes)
         goff = np.zeros(G + 1, dtype=np.uint64)
@@ -78,6 +95,7 @@ def _worker(rank, world, port, ret):
             ecc, ecov, _ = O.contain(k, c, db, goff)
             ok = ok and np.array_equal(cc[s], ecc) and all(np.array_equal(covs[s][g], np.sort(ecov[g])) for g in range(G))
             ok = ok and (len(k) == 0 or int(ecc.sum()) > 0)
+            ok = ok and (not extreme or len(k) == 0 or int(ecc[13]) >= 2)        # (the oracle counts the hits on 0 and on 2^64 - 1)
         ret[rank] = bool(ok)
     finally:
         dist.destroy_process_group()
@@ -89,6 +107,18 @@ def test_sharded_containment_gloo(world):
     mgr = mp.Manager()
     ret = mgr.dict()
     mp.spawn(_worker, args=(world, port, ret), nprocs=world, join=True)
+    assert [ret.get(r) for r in range(world)] == [True] * world
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_containment_gloo_extreme_keys(world):
+    """The same run over a database and samples that hold 0 and 2^64 - 1 (and samples that hold both sides of every range boundary):
+    sylph_shard_bounds then ends at bounds[W] = 2^64 - 1, and the key 2^64 - 1 must still travel to the last rank, whose index is
+    open-ended and holds it.  The sharded answer equals the single-process oracle's, which counts that hit."""
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_worker, args=(world, port, ret, True), nprocs=world, join=True)
     assert [ret.get(r) for r in range(world)] == [True] * world
 
 
@@ -110,19 +140,26 @@ def _plan_lib():
     import ctypes as C
     import subprocess
     import tempfile
+    import hashlib
     here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(tempfile.gettempdir(), f"sylph_shard_plan_{os.getuid()}.so")
     src = os.path.join(here, "shard_plan_capi.cpp")
     hdr = os.path.join(here, "..", "sylph_amd", "csrc", "shard_plan.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    # the cached library is named after the CONTENT of its two sources: a checkout's files may be older than a library that another
+    # commit's sources left in the same directory, so file times cannot say whether it is this tree's
+    h = hashlib.sha256()
+    for p in (src, hdr):
+        with open(p, "rb") as f:
+            h.update(f.read())
+    out = os.path.join(tempfile.gettempdir(), f"sylph_shard_plan_{os.getuid()}_{h.hexdigest()[:16]}.so")
+    if not os.path.exists(out):
         tmp = out + f".{os.getpid()}"
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src])
         os.replace(tmp, out)
     L = C.CDLL(out)
     u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
     L.sp_meta_words.restype = C.c_uint64
-    L.sp_lower_bound.restype = C.c_uint64
-    L.sp_lower_bound.argtypes = [u64p, C.c_uint64, C.c_uint64]
+    L.sp_split_at.restype = C.c_uint64
+    L.sp_split_at.argtypes = [u64p, C.c_uint64, u64p, C.c_uint32, C.c_uint32]
     L.sp_owner.argtypes = [C.c_uint64, u64p, C.c_uint32]
     L.sp_rebase.restype = C.c_uint64
     L.sp_rebase.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
@@ -162,7 +199,7 @@ def library_plan_exchange(dist, L, bounds, G, samples, probe_fn, fail=False, red
     for s, (k, _) in enumerate(samples):
         k = np.ascontiguousarray(k, dtype=np.uint64)
         for j in range(W + 1):
-            block[1 + s * (W + 1) + j] = L.sp_lower_bound(_p64(k), len(k), int(bounds[j]))
+            block[1 + s * (W + 1) + j] = L.sp_split_at(_p64(k), len(k), _p64(bounds), W, j)     # (what split_kernel calls per thread)
     import torch
     got = [torch.zeros(mw, dtype=torch.int64) for _ in range(W)]
     dist.all_gather(got, torch.from_numpy(block.view(np.int64)))
@@ -261,29 +298,31 @@ def library_plan_exchange(dist, L, bounds, G, samples, probe_fn, fail=False, red
     return cc, [[np.array(x, dtype=np.uint32) for x in per] for per in covs]
 
 
-def _plan_worker(rank, world, port, ret):
+def _plan_worker(rank, world, port, ret, extreme=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         L = _plan_lib()
-        pool, genomes = make_db()
+        pool, genomes = make_db(extreme=extreme)
         G = len(genomes)
         bounds = SH.shard_bounds(int(max(g.max() for g in genomes if len(g))), world)
         hi = int(bounds[rank + 1]) if rank + 1 < world else 0
         probe = shard_probe(genomes, int(bounds[rank]), hi)
+        edges = edge_keys(bounds) if extreme else None
         db = np.concatenate(genomes)
         goff = np.zeros(G + 1, dtype=np.uint64)
         goff[1:] = np.cumsum([len(g) for g in genomes])
         ok = True
         for step, sizes in enumerate(([2, 3, 0], [0, 1, 4], [1, 1, 1])):     # three batches of different shapes, an empty rank, an empty table
-            samples = make_samples(pool, rank + 3 * step, sizes[rank]) if step else make_samples(pool, rank, sizes[rank])
+            samples = make_samples(pool, rank + 3 * step, sizes[rank], edges) if step else make_samples(pool, rank, sizes[rank], edges)
             for reduce in ("alltoall", "allgather"):          # (round 6: the hits by all-to-all, and by ONE all-gather of padded blocks)
                 cc, covs = library_plan_exchange(dist, L, bounds, G, samples, probe, reduce=reduce)
                 ok = ok and cc.shape == (len(samples), G)
                 for s, (k, c) in enumerate(samples):
                     ecc, ecov, _ = O.contain(k, c, db, goff)
                     ok = ok and np.array_equal(cc[s], ecc) and all(np.array_equal(covs[s][g], np.sort(ecov[g])) for g in range(G))
+                    ok = ok and (not extreme or len(k) == 0 or int(ecc[13]) >= 2)
         # a rank that fails between the collectives: every rank must come out with the same (rank, class)
         res = library_plan_exchange(dist, L, bounds, G, make_samples(pool, rank, 1), probe, fail=(rank == world - 1))
         ok = ok and res == ("failed", world - 1, 1)
@@ -306,6 +345,18 @@ def test_library_exchange_bookkeeping_gloo(world):
     assert [ret.get(r) for r in range(world)] == [True] * world
 
 
+@pytest.mark.parametrize("world", [2, 3])
+def test_library_exchange_bookkeeping_gloo_extreme_keys(world):
+    """The header's arithmetic over the database and samples that hold 0 and 2^64 - 1 and both sides of every boundary: the last
+    slice of a table is open-ended (shard_plan.h split_at), as the last shard's index is."""
+    _plan_lib()
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_plan_worker, args=(world, port, ret, True), nprocs=world, join=True)
+    assert [ret.get(r) for r in range(world)] == [True] * world
+
+
 def genome_shard_probe(genomes, g0, g1, min_number_kmers=50.0):
     """CPU stand-in for a GENOME shard (sylph_db_upload_genome_shard): all k-mers of the genomes [g0, g1), global ids."""
     inner = shard_probe([g if g0 <= i < g1 else g[:0] for i, g in enumerate(genomes)], 0, 0, 0.0)
@@ -313,14 +364,15 @@ def genome_shard_probe(genomes, g0, g1, min_number_kmers=50.0):
     return lambda k, c: [(g, x) for g, x in inner(k, c) if full_len[g] >= min_number_kmers]
 
 
-def _genome_plan_worker(rank, world, port, ret):
+def _genome_plan_worker(rank, world, port, ret, extreme=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         L = _plan_lib()
         L.sp_set_whole(1)
-        pool, genomes = make_db()
+        pool, genomes = make_db(extreme=extreme)
+        edges = edge_keys(SH.shard_bounds(2**64 - 1, world)) if extreme else None
         G = len(genomes)
         db = np.concatenate(genomes)
         goff = np.zeros(G + 1, dtype=np.uint64)
@@ -334,7 +386,7 @@ def _genome_plan_worker(rank, world, port, ret):
         bounds = np.full(world + 1, np.iinfo(np.uint64).max, dtype=np.uint64)   # what the library sets for a genome shard: {0, ~0, ..}
         bounds[0] = 0
         for step, sizes in enumerate(([2, 3, 0], [0, 1, 4], [1, 1, 1])):
-            samples = make_samples(pool, rank + 3 * step, sizes[rank]) if step else make_samples(pool, rank, sizes[rank])
+            samples = make_samples(pool, rank + 3 * step, sizes[rank], edges) if step else make_samples(pool, rank, sizes[rank], edges)
             for reduce in ("alltoall", "allgather"):          # north_star's shape: whole genomes per rank AND one all-gather of the answers
                 cc, covs = library_plan_exchange(dist, L, bounds, G, samples, probe, reduce=reduce)
                 ok = ok and cc.shape == (len(samples), G)
@@ -356,6 +408,18 @@ def test_library_genome_shards_bookkeeping_gloo(world):
     mgr = mp.Manager()
     ret = mgr.dict()
     mp.spawn(_genome_plan_worker, args=(world, port, ret), nprocs=world, join=True)
+    assert [ret.get(r) for r in range(world)] == [True] * world
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_library_genome_shards_bookkeeping_gloo_extreme_keys(world):
+    """The genome cut's bounds are always {0, ~0, ..}: a whole table is [split[0], split[W]), so the key 2^64 - 1 travels only if
+    split[W] is the table's length."""
+    _plan_lib()
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_genome_plan_worker, args=(world, port, ret, True), nprocs=world, join=True)
     assert [ret.get(r) for r in range(world)] == [True] * world
 
 

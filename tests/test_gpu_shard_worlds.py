@@ -1,0 +1,73 @@
+"""The library's sharded containment exchange (csrc/shard.hip, csrc/shard_plan.h, the shard arms of db_upload_impl) with 3, 5 and 8
+ranks on ONE GPU: one torch.distributed.run launch of tests/shard_worlds_worker.py per world size, the collectives through gloo
+callbacks.  The worker's docstring lists the databases and steps; every rank checks every genome row and every coverage vector of
+its own samples against the oracle over the whole database, under both cuts and both "shard_reduce" settings.
+
+What each scenario would catch (a reader's map from a failure to the code):
+  W = 3, 5, 8                  owner_of_sample's search with more than one step; the per-bin LDS cursors of wave_take; `start[r] + base[r] +
+                               slot` in owner_scatter_kernel; plan_hits_gather's `before` sum (me > 1); d_allsizes' parity slot at odd AND even W
+  D0 step 1 / 5 (>4,096 hits)  owner_scatter_kernel's loop over several tiles: bins reset per tile, cursor[] carried across tiles and workgroups
+  D1 (holes), D2 (W > genomes) db_upload_impl's `hi == lo` arm and `ab[1] == ab[0]` arm, a range with no posting, probe_batch's return on
+                               !kept.n_postings inside the exchange (a rank that sends zero-length groups and still receives its answers)
+  D3 (0, 2^64 - 1, edges)      split_at's open-ended last range; lower_bound_u64 on both sides of every boundary
+  step 2 (nobody)              S_total == 0: no probe, empty collectives, empty results
+  step 3 (64 tiny samples)     MAX_LOCAL's meta block; wave_take's leader loop when owner and row change inside a wavefront; slice_in_block's sums
+  step 4 (one range)           zero-length blocks in both all-to-alls; all hits from one source rank
+  step 5 (counts)              plan_hits' max_mine per OWNER (the widths differ between ranks of one batch); finish_hits beyond 16 bits
+  step 7 (length filter)       glen[] of the WHOLE genome on a k-mer-range shard
+  step 8 (failure)             plan_hits' first failed rank, the same verdict on every rank; state left behind for the next batch
+"""
+import os
+import signal
+import socket
+import subprocess
+import sys
+import time
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+# Wall time of one launch measured on an MI355X host with 16 CPUs for the ranks: 5.3 s, 5.7 s and 16.0 s, beside 4.7-5.2 s for one case
+# of test_sharded_containment_two_ranks_one_gpu in the same session.  About 5 s of each is the launcher and the ranks' start-up.  One
+# exchange costs ~5 ms with 3 and 5 ranks; with 8 ranks it was 118-127 ms in three sessions and 43 ms in a fourth (8.6 s for the launch);
+# the worker's PLAN_AT_8 keeps that launch to 88 exchanges.  The limit is a few times the measurement: a launch that reaches it is a hang
+# to be explained from the worker's output, not to be retried.
+LIMIT_S = {3: 45, 5: 45, 8: 90}
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+@pytest.mark.parametrize("world", [3, 5, 8])
+def test_sharded_containment_worlds_one_gpu(world):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+           "--master-port", str(_free_port()), os.path.join(root, "tests", "shard_worlds_worker.py")]
+    t0 = time.time()
+    p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
+    try:
+        out, err = p.communicate(timeout=LIMIT_S[world])
+    except subprocess.TimeoutExpired:
+        os.killpg(p.pid, signal.SIGKILL)              # the launcher and every rank: its own session = its own process group
+        out, err = p.communicate()
+        pytest.fail(f"world {world}: no end after {LIMIT_S[world]} s (a hang)\n" + out[-3000:] + err[-4000:])
+    print(f"world {world}: launch took {time.time() - t0:.1f} s (limit {LIMIT_S[world]} s)")
+    print("\n".join(ln for ln in out.splitlines() if ln.startswith("SHARD_WORLDS_TIME")))
+    assert p.returncode == 0 and f"SHARD_WORLDS_OK world={world}" in out, out[-3000:] + err[-6000:]
+    steps = [ln.split()[1:] for ln in out.splitlines() if ln.startswith("SHARD_WORLDS_STEP ")]
+    # one line per (database, cut, reduce, step).  3 and 5 ranks: 10 steps x 2 reduces x (2 cuts for D0, D2, D3; 3 for D1, with the
+    # hand-made bounds).  8 ranks: all of D0 and the worker's PLAN_AT_8 for the others (3 steps x 2 x 2, + 2 steps x 2 for D1's hand-made bounds)
+    lines = {"D0": 40, "D1": 60, "D2": 40, "D3": 40} if world < 8 else {"D0": 40, "D1": 16, "D2": 12, "D3": 12}
+    assert len(steps) == len({tuple(s) for s in steps}) == sum(lines.values()), len(steps)
+    for name, n in lines.items():
+        assert sum(1 for s in steps if s[0] == name) == n, name
+    for name in lines:             # every (step, cut) that ran, ran under both reduces
+        ran = {(s[1], s[3]) for s in steps if s[0] == name}
+        assert all([name, cut, red, label] in steps for cut, label in ran for red in ("alltoall", "allgather")), name
+    assert {s[1] for s in steps} == {"kmer", "kmer-hand", "genome"} and {s[2] for s in steps} == {"alltoall", "allgather"}
