@@ -11,7 +11,7 @@
 namespace sylph {
 namespace {
 
-using namespace replay_plan;     // BucketMap, bucket_of_key, bucket_lo_hash / bucket_lo_key, sub_range_of: replay_plan.h
+using namespace replay_plan;     // BucketMap, bucket_of_key, bucket_lo_hash / bucket_lo_key, sub_range_of, MAX_COARSE: replay_plan.h
 
 // The place an entry takes inside its bin: how many took one there before it.  `fill` holds one 16-bit counter per bin, zeroed by the
 // caller (16-bit LDS atomics do not exist: the counter pairs share a word; add 1 or 65536 to the word and take the half).
@@ -37,7 +37,6 @@ struct PartIn {
 };
 constexpr int PART_TPB = 256;
 constexpr uint32_t BLK_PER_TILE = 16;     // slotted: blocks of the seeding kernel per partition tile (~3,000 occurrences)
-constexpr uint32_t MAX_COARSE = 4096;     // coarse ranges (LDS counters of the histogram / scatter kernels)
 constexpr uint32_t MAX_FINE = 4096;       // buckets per coarse range (LDS counters of the fine kernel)
 #ifndef SYLPH_STAGE_PAIRS
 #define SYLPH_STAGE_PAIRS 4096

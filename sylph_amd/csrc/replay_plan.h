@@ -27,6 +27,7 @@ constexpr int IDX_BITS = 10;         // arrival index inside a bucket (< CAP_LAR
 // A bucket holding a k-mer with SEG_LIMIT or more occurrences (a genome at ~100x and above) is handed to the medium / large
 // configuration, whose marker test is a hash table in LDS: linear in the bucket size.
 constexpr uint32_t SEG_LIMIT = 96;
+constexpr uint32_t MAX_COARSE = 4096;     // coarse ranges of the partition (LDS counters of its histogram / scatter kernels)
 
 SY_PLAN_HD int bits_of(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
 SY_PLAN_HD uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }

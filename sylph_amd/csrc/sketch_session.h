@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "a10_plan.h"
 #include "finish_plan.h"
 #include "replay_plan.h"
 #include "seed_plan.h"
@@ -13,12 +14,7 @@ namespace sylph {
 // its record's EMISSION order (device_common.h emission_rank — the order extract_markers pushed the record's seeds in, which is the
 // order sketch.rs:828-867 hands them to the dedup: it decides nothing for the exact set, and for the filter which of two items of
 // one pair meets the other); bits 0..41 = global record index (file order; mate = bit 0).
-constexpr uint64_t RID_MARKER_BIT = 1ull << 63;
-constexpr uint64_t RID_A10_BIT = 1ull << 62;
-constexpr int RID_RANK_SHIFT = 42;
-constexpr uint64_t RID_RANK_MAX = (1ull << 20) - 1;
-constexpr uint64_t RID_MASK = (1ull << RID_RANK_SHIFT) - 1;
-constexpr uint64_t INVALID_HASH = ~0ull;
+// (RID_MARKER_BIT, RID_A10_BIT, RID_RANK_SHIFT, RID_RANK_MAX, RID_MASK and INVALID_HASH: a10_plan.h, which compiles without HIP)
 // One surviving seed occurrence.  Array-of-structs (32 B, one sector) because finish() gathers occurrences through a sort
 // permutation: four scattered 8 B reads per occurrence cost 4x the HBM sectors of one 32 B read.
 struct alignas(32) OccRec { uint64_t hash, rid, m0, m1; };

@@ -109,6 +109,42 @@ def bucket_roads(hashes, c, target):
     return dict(B=B, composite=composite, n=n, bucket=bucket, fill=fill)
 
 
+# ---- a10: the filter dedup's hashes restated in numpy (sylph_amd/csrc/a10_plan.h; tests/test_oracle.py holds them against the model's
+# walk, tests/test_a10_plan.py the header against them) ----
+_FX_K = np.uint64(0x517cc1b727220a95)
+_GOLD = np.uint64(0x9E3779B97F4A7C15)
+
+
+def _fx_add(h, w):
+    with np.errstate(over="ignore"):
+        return (((h << np.uint64(5)) | (h >> np.uint64(59))) ^ w) * _FX_K
+
+
+def a10_item_hash(km, marker):
+    z = np.zeros_like(km)
+    with np.errstate(over="ignore"):
+        return _fx_add(_fx_add(_fx_add(z, km), marker & np.uint64(0xffffffff)), marker >> np.uint64(32)) * _GOLD
+
+
+def a10_filter_geometry(fpr_j, cap_j):
+    """-> (fingerprint bits, buckets) of a filter of that capacity and false-positive probability"""
+    fp_bits = min(31, max(1, int(np.ceil(np.log2(1.0 / fpr_j) + np.log2(8.0)))))
+    nb = 1
+    while nb * 4 < cap_j:
+        nb <<= 1
+    return fp_bits, nb
+
+
+def a10_reduced_key(h, fpr_j, cap_j):
+    """(fingerprint, smaller of the item's two buckets): what a cuckoo filter can still tell apart (a10.hip header)"""
+    fp_bits, nb = a10_filter_geometry(fpr_j, cap_j)
+    f = (h >> np.uint64(32)) & np.uint64((1 << fp_bits) - 1)
+    f = np.where(f == 0, np.uint64(1), f)
+    i1 = h & np.uint64(nb - 1)
+    i2 = (i1 ^ (_fx_add(np.zeros_like(f), f) >> np.uint64(11))) & np.uint64(nb - 1)
+    return (f << np.uint64(32)) | np.minimum(i1, i2)
+
+
 def build_path(stem, deps, suffix=""):
     """Where a test keeps what it compiles from `deps` (sources first, then the headers they include): a file in the temporary
     directory named after the CONTENTS of deps, so that a binary left there by another commit's sources is never taken for this one's.

@@ -8,7 +8,7 @@ import pytest
 
 from oracle import oracle as O
 
-from .helpers import concat, hist, random_seq, xor_sum
+from .helpers import a10_item_hash as _a10_item_hash, a10_reduced_key as _a10_reduced_key, concat, hist, random_seq, xor_sum
 
 
 @pytest.fixture(scope="module")
@@ -259,34 +259,6 @@ def test_a10_default_dedup_model_stays_close_to_the_exact_set():
 
 
 # ---- a10: the data-parallel formulation of the filter walk (sylph_amd/csrc/a10.hip), restated in numpy against the model's walk ----
-_FX_K = np.uint64(0x517cc1b727220a95)
-_GOLD = np.uint64(0x9E3779B97F4A7C15)
-
-
-def _fx_add(h, w):
-    with np.errstate(over="ignore"):
-        return (((h << np.uint64(5)) | (h >> np.uint64(59))) ^ w) * _FX_K
-
-
-def _a10_item_hash(km, marker):
-    z = np.zeros_like(km)
-    with np.errstate(over="ignore"):
-        return _fx_add(_fx_add(_fx_add(z, km), marker & np.uint64(0xffffffff)), marker >> np.uint64(32)) * _GOLD
-
-
-def _a10_reduced_key(h, fpr_j, cap_j):
-    """(fingerprint, smaller of the item's two buckets): what a cuckoo filter can still tell apart (a10.hip header)"""
-    fp_bits = min(31, max(1, int(np.ceil(np.log2(1.0 / fpr_j) + np.log2(8.0)))))
-    nb = 1
-    while nb * 4 < cap_j:
-        nb <<= 1
-    f = (h >> np.uint64(32)) & np.uint64((1 << fp_bits) - 1)
-    f = np.where(f == 0, np.uint64(1), f)
-    i1 = h & np.uint64(nb - 1)
-    i2 = (i1 ^ (_fx_add(np.zeros_like(f), f) >> np.uint64(11))) & np.uint64(nb - 1)
-    return (f << np.uint64(32)) | np.minimum(i1, i2)
-
-
 def a10_contained_by_classes(km, marker, fpr, cap0):
     """contained[i] of the walk 'test item i, insert it when absent' WITHOUT walking: an item is contained iff it is not the first
     of its reduced-key class among the items that reach the current filter, or a closed filter holds its class; the item that
