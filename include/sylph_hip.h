@@ -602,6 +602,26 @@ int sylph_db_contain_batch_sharded(sylph_db *db, sylph_comm *comm, const sylph_s
  * other ranks (the payload of the two all-to-alls; the all-gathers of sizes carry a few KB).  For scaling reports. */
 int sylph_db_exchange_stats(sylph_db *db, uint64_t *batches, uint64_t *table_bytes_sent, uint64_t *hit_bytes_sent, int reset);
 
+/* ---- a sample given as its sketch: the table of a .sylsp file, unpacked on the device ----------------------------------- */
+
+/* The table of a .sylsp file is bincode's Vec<(u64, u32)> (types.rs:132-138): n_entries packed little-endian entries of 12
+ * bytes (k-mer, count) from file offset 8.  The reference rebuilds a hash map from them (types.rs:117-129: a repeated k-mer
+ * keeps the count read last); here the entries travel as they are and the device makes the table the probe wants: k-mers
+ * strictly ascending, each once, with the count of its last entry (a count of 0 stays; the probe ignores it).  Entries that
+ * ascend strictly already — every file this project writes — are only unpacked (*was_ascending = 1); any other order is sorted
+ * (stable radix sort) and deduplicated on the device.
+ * entries: SYLPH_MEM_HOST / SYLPH_MEM_HOST_PINNED memory of any alignment is copied by the call; SYLPH_MEM_DEVICE memory must be
+ * 4-byte aligned and readable 16 bytes either side, and is read by the call only.  n_entries >= 2^31: SYLPH_ERR_INVALID; no
+ * room on the device for the table and the scratch of either road: SYLPH_ERR_NOMEM; both before anything is copied or launched
+ * (the one allocation made later is the radix sort's own temporary storage, on the sort road: SYLPH_ERR_NOMEM there leaves no
+ * table and the caller's memory as it was).  n_entries == 0 is an empty table.
+ * The view's pointers live on the context's device until sylph_table_destroy and go where a sample table goes under
+ * SYLPH_MEM_DEVICE: sylph_db_contain*, sylph_db_reassign_view.  Kernel timers: "sylsp" (unpack), "sort" + "sylsp_dedup". */
+typedef struct sylph_table sylph_table;
+int sylph_table_from_entries(sylph_ctx *ctx, const void *entries, uint64_t n_entries, int mem, sylph_table **out);
+int sylph_table_view(const sylph_table *t, const uint64_t **dev_kmers, const uint32_t **dev_counts, uint64_t *n, int *was_ascending);
+void sylph_table_destroy(sylph_table *t);
+
 /* ---- a stream of samples through both stages (sketch -> profile), overlapped inside the library -------------------------- */
 
 /* The reference runs its samples on the rayon pool (sketch.rs:313,371 sketches files on parallel workers; contain.rs:267-289 walks
@@ -665,6 +685,15 @@ int sylph_pipeline_replica_of_last(sylph_pipeline *p);
 /* SYLPH_ERR_STATE when `depth` samples are outstanding already (take one with sylph_pipeline_next first). */
 int sylph_pipeline_submit(sylph_pipeline *p, const sylph_read_batch *batches, uint32_t n_batches, int mem, int enc, uint64_t tag);
 int sylph_pipeline_submit_session(sylph_pipeline *p, sylph_sketch *sk, uint64_t tag);
+/* A sample that is sketched already (sylph_table_from_entries above: the entries of its .sylsp file): a worker unpacks them on
+ * its context instead of sketching.  `entries` is borrowed until sylph_pipeline_next has returned the sample.  The result's
+ * n_table counts the distinct k-mers, dup_removed is 0, t_sketch_begin / t_sketch_end bracket the unpack; everything else —
+ * order, depth, want_table, sharded batches and flush, the replica a sample of host or device memory goes to — is as for
+ * sylph_pipeline_submit. */
+int sylph_pipeline_submit_entries(sylph_pipeline *p, const void *entries, uint64_t n_entries, int mem, uint64_t tag);
+/* Of the sample the last successful sylph_pipeline_next returned: 1 = its entries ascended strictly (unpacked only), 0 = they were
+ * sorted on the device, -1 = it was not submitted as entries (or p is null).  sylph_table_view's was_ascending for a pipeline. */
+int sylph_pipeline_ascending_of_last(sylph_pipeline *p);
 /* Sharded pipelines only need it: everything submitted so far may be probed in a batch smaller than max_batch. */
 int sylph_pipeline_flush(sylph_pipeline *p);
 /* Blocks until the OLDEST outstanding sample is done.  Every pointer of *out stays valid until the next sylph_pipeline_next /

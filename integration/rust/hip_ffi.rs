@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflateStream { _p: [u8; 0] }
 #[repr(C)] pub struct SylphBunzip2Stream { _p: [u8; 0] }
+#[repr(C)] pub struct SylphTable { _p: [u8; 0] }
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
@@ -212,6 +213,15 @@ extern "C" {
     pub fn sylph_pipeline_submit(p: *mut SylphPipeline, batches: *const SylphReadBatch, n_batches: u32, mem: c_int, enc: c_int,
                                  tag: u64) -> c_int;
     pub fn sylph_pipeline_submit_session(p: *mut SylphPipeline, sk: *mut SylphSketch, tag: u64) -> c_int;
+    // a sample given as its sketch (get_seq_sketch's *.sylsp branch, contain.rs:551-570): the file's packed (u64, u32) entries as they
+    // lie behind the 8-byte length — a worker unpacks them into the table on the device instead of sketching; borrowed until next()
+    pub fn sylph_pipeline_submit_entries(p: *mut SylphPipeline, entries: *const c_void, n_entries: u64, mem: c_int, tag: u64) -> c_int;
+    pub fn sylph_pipeline_ascending_of_last(p: *mut SylphPipeline) -> c_int;   // of the sample next() returned last: 1 ascending, 0 sorted, -1 no entries job
+    // the same table without a pipeline: strictly ascending k-mers, each once with its last count (types.rs:117-129's map insertion);
+    // the view's device pointers go to sylph_db_contain* / sylph_db_reassign_view under MEM_DEVICE
+    pub fn sylph_table_from_entries(ctx: *mut SylphCtx, entries: *const c_void, n_entries: u64, mem: c_int, out: *mut *mut SylphTable) -> c_int;
+    pub fn sylph_table_view(t: *const SylphTable, dev_kmers: *mut *const u64, dev_counts: *mut *const u32, n: *mut u64, was_ascending: *mut c_int) -> c_int;
+    pub fn sylph_table_destroy(t: *mut SylphTable);
     pub fn sylph_pipeline_flush(p: *mut SylphPipeline) -> c_int;
     pub fn sylph_pipeline_next(p: *mut SylphPipeline, out: *mut SylphPipelineResult) -> c_int;
     pub fn sylph_pipeline_outstanding(p: *mut SylphPipeline) -> u32;

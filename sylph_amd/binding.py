@@ -45,7 +45,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
            "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
            "sylph_bunzip2", "sylph_bunzip2_files",
-           "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "sylph_bunzip2_stream_info", "sylph_bunzip2_stream_destroy", "sylph_bootstrap_counts"]
+           "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "sylph_bunzip2_stream_info", "sylph_bunzip2_stream_destroy", "sylph_bootstrap_counts",
+           "sylph_table_from_entries", "sylph_table_view", "sylph_table_destroy", "sylph_pipeline_submit_entries", "sylph_pipeline_ascending_of_last"]
 
 
 def load():
@@ -169,6 +170,12 @@ def load():
     L.sylph_genome_shard_bounds.argtypes = [vp, u64, u32, vp]
     L.sylph_db_upload_genome_shard.argtypes = [vp, vp, vp, u64, i32, vp, u32, u32, P(vp)]
     L.sylph_bootstrap_counts.argtypes = [vp, vp, u32, vp, vp, vp, u32, i32, u64, u32, vp, vp]
+    L.sylph_table_from_entries.argtypes = [vp, vp, u64, i32, P(vp)]
+    L.sylph_table_view.argtypes = [vp, P(vp), P(vp), P(u64), P(i32)]
+    L.sylph_table_destroy.argtypes = [vp]
+    L.sylph_table_destroy.restype = None
+    L.sylph_pipeline_submit_entries.argtypes = [vp, vp, u64, i32, u64]
+    L.sylph_pipeline_ascending_of_last.argtypes = [vp]
     _LIB = L
     return L
 
@@ -916,6 +923,36 @@ class Database:
             pass
 
 
+class Table:
+    """sylph_table: the (k-mer, count) table of a pre-sketched sample, made on the device from the packed 12-byte entries of its
+    .sylsp file.  entries: a bytes-like / uint8 array of n_entries * 12 bytes (host), or with mem=MEM_DEVICE an integer address."""
+
+    def __init__(self, ctx, entries, n_entries=None, mem=MEM_HOST):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        if mem == MEM_DEVICE:
+            ptr, n = C.c_void_p(int(entries)), int(n_entries)
+        else:
+            self._keep = entries if isinstance(entries, np.ndarray) else np.frombuffer(bytes(entries), dtype=np.uint8)
+            n = int(n_entries) if n_entries is not None else self._keep.nbytes // 12
+            ptr = C.c_void_p(self._keep.ctypes.data)
+        _check(load().sylph_table_from_entries(ctx._h, ptr, n, mem, C.byref(self._h)))
+        k, c, m, asc = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_int(0)
+        _check(load().sylph_table_view(self._h, C.byref(k), C.byref(c), C.byref(m), C.byref(asc)))
+        self.dev_kmers, self.dev_counts, self.n, self.was_ascending = k.value or 0, c.value or 0, int(m.value), bool(asc.value)
+
+    def close(self):
+        if self._h:
+            load().sylph_table_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ReadBatch(C.Structure):
     _fields_ = [("bases", C.c_void_p), ("rec_off", C.c_void_p), ("n_records", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -976,6 +1013,16 @@ class Pipeline:
         sketcher._h = C.c_void_p()
         return True
 
+    def submit_entries(self, entries, n_entries, tag=0, mem=MEM_HOST):
+        """A sample that is sketched already: `entries` = the address of n_entries packed 12-byte (k-mer, count) entries as a
+        .sylsp file holds them from offset 8 (borrowed until next() has returned the sample).  False when `depth` samples are
+        outstanding already."""
+        rc = load().sylph_pipeline_submit_entries(self._h, entries, n_entries, mem, tag)
+        if rc == -4:
+            return False
+        _check(rc)
+        return True
+
     def flush(self):
         _check(load().sylph_pipeline_flush(self._h))
 
@@ -1007,6 +1054,10 @@ class Pipeline:
                 out["kmers"] = view(r.kmers, int(r.n_table), C.c_uint64, np.uint64)
                 out["counts"] = view(r.counts, int(r.n_table), C.c_uint32, np.uint32)
         return out
+
+    def ascending_of_last(self):
+        """Of the sample next() returned last: 1 its entries ascended strictly, 0 they were sorted, -1 not submitted as entries."""
+        return int(load().sylph_pipeline_ascending_of_last(self._h))
 
     @property
     def outstanding(self):

@@ -26,6 +26,7 @@
 
 #include "contain_index.h"
 #include "sketch_session.h"
+#include "sylsp_table.h"
 
 using namespace sylph;
 
@@ -51,7 +52,12 @@ struct Job {
     int mem = SYLPH_MEM_DEVICE, enc = SYLPH_ENC_ASCII;
     sylph_sketch* sk = nullptr;
     bool adopted = false;        // the caller's session (sylph_pipeline_submit_session)
+    bool is_entries = false;     // a sample that is sketched already (sylph_pipeline_submit_entries): entries / n_entries in `mem`
+    const void* entries = nullptr;
+    uint64_t n_entries = 0;
+    sylph_table* table = nullptr;    // ... and the table a worker unpacked them into, on its context
     int worker = -1;             // the worker whose context owns `sk` (adopted: none)
+    sylph_ctx* table_ctx() const { return table ? table->ctx : sk->ctx; }   // the context the sample's table lives on
     JobState state = JobState::Queued;
     int status = SYLPH_OK;
     std::string error;
@@ -109,6 +115,7 @@ struct sylph_pipeline {
     std::vector<sylph_pipeline*> children;
     std::deque<uint32_t> route;                  // guarded by mu
     uint32_t last_replica = 0;                   // replica of the sample sylph_pipeline_next returned last
+    int last_ascending = -1;                     // that sample's entries ascended (1) / were sorted (0); -1: not an entries job
 
     Block* take_block() {                        // mu held
         for (auto& b : blocks)
@@ -123,6 +130,13 @@ struct sylph_pipeline {
     void sketch_job(Job* j, int w) {
         j->t_sketch0 = now_s();
         int rc = SYLPH_OK;
+        if (j->is_entries) {                     // nothing to sketch: the entries become the table on this worker's context
+            rc = sylph_table_from_entries(wctx[w], j->entries, j->n_entries, j->mem, &j->table);
+            if (rc == SYLPH_OK) rc = sylph_table_view(j->table, &j->dev_k, &j->dev_c, &j->n_table, nullptr);
+            if (rc != SYLPH_OK) fail(j, rc);
+            j->t_sketch1 = now_s();
+            return;
+        }
         if (!j->sk) {
             rc = sylph_sketch_begin(wctx[w], c, k, reads_mode, no_dedup, seed_mode, &j->sk);
             j->worker = w;
@@ -245,7 +259,7 @@ struct sylph_pipeline {
             if (rc == SYLPH_OK && want_table) {
                 rc = guarded([&] {
                     for (Job* j : good) {
-                        sylph_ctx* cx = j->sk->ctx;
+                        sylph_ctx* cx = j->table_ctx();
                         std::lock_guard<std::mutex> lock(cx->mu);
                         DeviceGuard dg(cx->device);
                         j->host_k.resize(j->n_table);
@@ -281,17 +295,25 @@ struct sylph_pipeline {
     }
     // mu held.  Returns a session the CALLER of this function must destroy after dropping the lock (an adopted session lives
     // on a context of the pipeline's user), or nullptr (sessions of the workers go back to the thread that owns their context).
-    sylph_sketch* release_returned() {
+    // The table of an entries job goes the same way out: sylph_table_destroy takes its context's lock itself.
+    struct Dead {
+        sylph_sketch* sk = nullptr;
+        sylph_table* table = nullptr;
+        explicit operator bool() const { return sk || table; }
+        void destroy() { if (sk) sylph_sketch_destroy(sk); if (table) sylph_table_destroy(table); sk = nullptr; table = nullptr; }
+    };
+    Dead release_returned() {
         Job* j = returned;
         returned = nullptr;
-        if (!j) return nullptr;
+        Dead dead;
+        if (!j) return dead;
         if (j->block && j->block->users) j->block->users--;
-        sylph_sketch* dead = j->sk;
+        dead.sk = j->sk;
+        dead.table = j->table;
         const bool adopted = j->adopted;
         const int w = j->worker;
         delete j;
-        if (!dead) return nullptr;
-        if (!adopted && w >= 0) { trash[w].push_back(dead); cv_work.notify_all(); return nullptr; }
+        if (dead.sk && !adopted && w >= 0) { trash[w].push_back(dead.sk); cv_work.notify_all(); dead.sk = nullptr; }
         return dead;
     }
 };
@@ -443,6 +465,17 @@ int sylph_pipeline_replica_of_last(sylph_pipeline* p) {
     return p->children.empty() ? 0 : (int)p->last_replica;
 }
 
+int sylph_pipeline_ascending_of_last(sylph_pipeline* p) {
+    if (!p) return -1;
+    sylph_pipeline* c = p;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (!p->children.empty()) c = p->children[p->last_replica];
+        else return p->last_ascending;
+    }
+    return sylph_pipeline_ascending_of_last(c);
+}
+
 int sylph_pipeline_submit(sylph_pipeline* p, const sylph_read_batch* batches, uint32_t n_batches, int mem, int enc, uint64_t tag) {
     if (!p || (n_batches && !batches)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
     if (!p->children.empty()) {
@@ -471,6 +504,23 @@ int sylph_pipeline_submit_session(sylph_pipeline* p, sylph_sketch* sk, uint64_t 
     return submit_job(p, std::move(j));
 }
 
+int sylph_pipeline_submit_entries(sylph_pipeline* p, const void* entries, uint64_t n_entries, int mem, uint64_t tag) {
+    if (!p || (n_entries && !entries)) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    if (!p->children.empty()) {
+        int device = -1;
+        if (mem == SYLPH_MEM_DEVICE && n_entries) {
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, entries) != hipSuccess) { (void)hipGetLastError(); set_error("sylph_pipeline_submit_entries: cannot tell the device of the entries' memory"); return SYLPH_ERR_INVALID; }
+            device = at.device;
+        }
+        return route_submit(p, device, "sylph_pipeline_submit_entries", [&](sylph_pipeline* c) { return sylph_pipeline_submit_entries(c, entries, n_entries, mem, tag); });
+    }
+    std::unique_ptr<Job> j(new Job());
+    j->is_entries = true;
+    j->entries = entries; j->n_entries = n_entries; j->mem = mem; j->tag = tag;
+    return submit_job(p, std::move(j));
+}
+
 int sylph_pipeline_flush(sylph_pipeline* p) {
     return guarded([&] {
         SY_REQUIRE(p, "null argument");
@@ -496,7 +546,7 @@ int sylph_pipeline_next(sylph_pipeline* p, sylph_pipeline_result* out) {
     return guarded([&] {
         SY_REQUIRE(p && out, "null argument");
         std::unique_lock<std::mutex> lk(p->mu);
-        if (sylph_sketch* dead = p->release_returned()) { lk.unlock(); sylph_sketch_destroy(dead); lk.lock(); }
+        if (sylph_pipeline::Dead dead = p->release_returned()) { lk.unlock(); dead.destroy(); lk.lock(); }
         SY_REQUIRE(!p->order.empty(), "sylph_pipeline_next: nothing is outstanding");
         Job* j = p->order.front();
         if (p->comm && j->state != JobState::Profiled && p->flush_upto <= j->seq) {
@@ -517,6 +567,7 @@ int sylph_pipeline_next(sylph_pipeline* p, sylph_pipeline_result* out) {
         out->error = j->status == SYLPH_OK ? nullptr : j->error.c_str();
         out->n_table = j->n_table;
         out->dup_removed = j->dup_removed;
+        p->last_ascending = j->table ? j->table->was_ascending : -1;
         out->dev_kmers = j->dev_k;
         out->dev_counts = j->dev_c;
         if (p->want_table && j->status == SYLPH_OK) { out->kmers = j->host_k.data(); out->counts = j->host_c.data(); }
@@ -625,14 +676,14 @@ void sylph_pipeline_destroy(sylph_pipeline* p) {
         delete p;
         return;
     }
-    sylph_sketch* dead = nullptr;
+    sylph_pipeline::Dead dead;
     {
         std::unique_lock<std::mutex> lk(p->mu);
         dead = p->release_returned();
         p->flush_upto = p->next_seq;             // sharded: what is outstanding goes in a last, partial batch (as after sylph_pipeline_flush;
                                                  // every rank destroys its pipeline with the same number of samples outstanding)
     }
-    if (dead) sylph_sketch_destroy(dead);
+    dead.destroy();
     p->cv_sketched.notify_all();
     // outstanding samples are finished (their inputs are the caller's memory: nothing may still read them afterwards)
     for (;;) {
@@ -644,7 +695,7 @@ void sylph_pipeline_destroy(sylph_pipeline* p) {
         p->returned = j;
         dead = p->release_returned();
         lk.unlock();
-        if (dead) sylph_sketch_destroy(dead);
+        dead.destroy();
     }
     {
         std::lock_guard<std::mutex> lk(p->mu);

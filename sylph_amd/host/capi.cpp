@@ -145,6 +145,25 @@ int sylph_host_read_sylsp(const char* path, uint64_t* kmers, uint32_t* counts, u
     } catch (const Error&) { return -1; }
 }
 
+// read_sylsp_header for the tests: the metadata, the table's entry count and its offset in the file; -1 on an Error, whose message
+// goes to err (as sylph_host_sylsp_error gives read_sylsp's: the two must fail alike)
+int sylph_host_read_sylsp_header(const char* path, uint64_t* n_entries, uint64_t* entries_offset, uint64_t* c, uint64_t* k, int* paired,
+                                 double* mean_read_length, char* file_name, char* sample_name, uint64_t name_cap, int* has_sample_name,
+                                 char* err, uint64_t err_cap) {
+    try {
+        const SylspView v = read_sylsp_header(path);
+        const SequencesSketch& s = v.meta;
+        *n_entries = v.n_entries; *entries_offset = v.entries_offset; *c = s.c; *k = s.k; *paired = s.paired; *mean_read_length = s.mean_read_length;
+        *has_sample_name = s.sample_name ? 1 : 0;
+        snprintf(file_name, name_cap, "%s", s.file_name.c_str());
+        snprintf(sample_name, name_cap, "%s", s.sample_name ? s.sample_name->c_str() : "");
+        return s.kmers.empty() && s.counts.empty() ? 0 : -2;
+    } catch (const Error& e) { snprintf(err, err_cap, "%s", e.msg.c_str()); return -1; }
+}
+int sylph_host_sylsp_error(const char* path, char* err, uint64_t err_cap) {
+    try { (void)read_sylsp(path); return 0; } catch (const Error& e) { snprintf(err, err_cap, "%s", e.msg.c_str()); return -1; }
+}
+
 // .syldb: number of genomes, then per-genome accessors
 void* sylph_host_read_syldb(const char* path) {
     try { return new std::vector<GenomeSketch>(read_syldb(path)); } catch (const Error&) { return nullptr; }

@@ -396,6 +396,63 @@ void upload_database(Engine& e, const std::vector<GenomeSketch>& genome_sketches
     }
 }
 
+// --gpus N|all: the database replicated on N GPUs (index copied device to device), samples dealt to them, one router pipeline over
+// the replicas (sylph_pipeline_create_multi): the reference's sample loop spans the machine through its rayon pool
+// (contain.rs:252-295), this is the same for the GPUs of a node.  One GPU: the database as it is, a plain pipeline.
+// (SYLPH_HIP_SHARE_GPUS=1: more replicas than devices — they wrap around; how the one-GPU test box runs `--gpus 2`)
+// Both sample roads — raw reads and sketch files — set their replicas and their pipeline up here.
+struct ReplicaSet {
+    std::vector<std::unique_ptr<Engine>> engines;                    // (declared before the replicas: destroyed after them)
+    std::vector<sylph_db*> dbs;                                      // dbs[0]: the command's own database, not owned
+    std::vector<int> device;
+    int n_gpus = 1;
+    ReplicaSet(Engine& e, const ContainCmdArgs& args, sylph_db* db, size_t n_samples) {
+        n_gpus = args.gpus < 0 ? sylph_device_count() : getenv("SYLPH_HIP_SHARE_GPUS") ? args.gpus : std::min(args.gpus, std::max(1, sylph_device_count()));
+        n_gpus = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_gpus), n_samples));
+        dbs.push_back(db);
+        device.push_back(e.device);
+        const int dev0 = e.device < 0 ? 0 : e.device;                // (Engine(-1) = the current device = 0 in a fresh process)
+        const auto t_r0 = std::chrono::steady_clock::now();
+        try {
+            for (int g = 1; g < n_gpus; g++) {
+                const int dev = (dev0 + g) % std::max(1, sylph_device_count());
+                engines.emplace_back(new Engine(dev));
+                sylph_db* r = nullptr;
+                hip_check(sylph_db_replicate(db, engines.back()->context(), &r), "sylph_db_replicate");
+                dbs.push_back(r);
+                device.push_back(dev);
+            }
+        } catch (...) { destroy_replicas(); throw; }
+        if (n_gpus > 1) {
+            char b[160];
+            snprintf(b, sizeof(b), "database replicated on %d GPUs (device to device) in %.3f s", n_gpus,
+                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_r0).count());
+            info(b);
+        }
+    }
+    ~ReplicaSet() { destroy_replicas(); }
+    ReplicaSet(const ReplicaSet&) = delete;
+    ReplicaSet& operator=(const ReplicaSet&) = delete;
+    void destroy_replicas() { for (size_t i = 1; i < dbs.size(); i++) sylph_db_destroy(dbs[i]); dbs.resize(std::min<size_t>(dbs.size(), 1)); }
+    // the command's pipeline over the set: `n_workers` library threads, `depth` samples outstanding at the most
+    sylph_pipeline* create_pipeline(const ContainCmdArgs& args, uint32_t n_workers, uint32_t depth, sylph_pipeline_config& cfg) {
+        memset(&cfg, 0, sizeof(cfg));
+        cfg.struct_size = sizeof(cfg);
+        cfg.n_workers = n_workers;
+        cfg.depth = depth;
+        cfg.max_batch = 4;
+        cfg.c = (uint32_t)args.c; cfg.k = (uint32_t)args.k;
+        cfg.reads_mode = SYLPH_READS_PAIRED; cfg.seed_mode = SYLPH_SEED_AVX2_COMPAT;
+        cfg.want_table = args.estimate_unknown ? 1 : 0;                 // -u walks the counts on the host
+        cfg.min_number_kmers = args.min_number_kmers;
+        sylph_pipeline* pipe = nullptr;
+        if (n_gpus > 1) hip_check(sylph_pipeline_create_multi(dbs.data(), (uint32_t)dbs.size(), &cfg, &pipe), "sylph_pipeline_create_multi");
+        else hip_check(sylph_pipeline_create(dbs[0], &cfg, &pipe), "sylph_pipeline_create");
+        return pipe;
+    }
+};
+struct PipeGuard { sylph_pipeline* p; ~PipeGuard() { sylph_pipeline_destroy(p); } };
+
 // ---- raw read samples (contain.rs:239-291 sketches and profiles them chunk by chunk on the rayon pool).  Here: up to `-t`
 // sample threads, each with a GPU context of its own, read + index + pack + push their files into sessions, in input order;
 // the sessions go through a sylph_pipeline (finish on the device -> probe, tables never leave HBM), and this thread takes the
@@ -409,37 +466,10 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
     std::vector<std::promise<Prepared>> promises(n_raw);
     std::vector<std::future<Prepared>> futures;
     for (auto& p : promises) futures.push_back(p.get_future());
-    // --gpus N|all: the database replicated on N GPUs (index copied device to device), sample threads dealt to them in turn,
-    // one router pipeline over the replicas (sylph_pipeline_create_multi): the reference's sample loop spans the machine through
-    // its rayon pool (contain.rs:252-295), this is the same for the GPUs of a node.  One GPU: everything as before.
-    // (SYLPH_HIP_SHARE_GPUS=1: more replicas than devices — they wrap around; how the one-GPU test box runs `--gpus 2`)
-    int n_gpus = args.gpus < 0 ? sylph_device_count() : getenv("SYLPH_HIP_SHARE_GPUS") ? args.gpus : std::min(args.gpus, std::max(1, sylph_device_count()));
-    n_gpus = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_gpus), n_raw));
-    std::vector<std::unique_ptr<Engine>> replica_engines;            // (declared before the replicas: destroyed after them)
-    struct Replicas { std::vector<sylph_db*> v; ~Replicas() { for (size_t i = 1; i < v.size(); i++) sylph_db_destroy(v[i]); } } replicas;
-    std::vector<sylph_db*>& dbs = replicas.v;
-    dbs.push_back(db);
-    std::vector<int> replica_device{e.device};
-    {
-        int dev0 = e.device;
-        if (dev0 < 0) dev0 = 0;                                      // (Engine(-1) = the current device = 0 in a fresh process)
-        replica_device[0] = e.device;
-        const auto t_r0 = std::chrono::steady_clock::now();
-        for (int g = 1; g < n_gpus; g++) {
-            const int dev = (dev0 + g) % std::max(1, sylph_device_count());
-            replica_engines.emplace_back(new Engine(dev));
-            sylph_db* r = nullptr;
-            hip_check(sylph_db_replicate(db, replica_engines.back()->context(), &r), "sylph_db_replicate");
-            dbs.push_back(r);
-            replica_device.push_back(dev);
-        }
-        if (n_gpus > 1) {
-            char b[160];
-            snprintf(b, sizeof(b), "database replicated on %d GPUs (device to device) in %.3f s", n_gpus,
-                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_r0).count());
-            info(b);
-        }
-    }
+    ReplicaSet replicas(e, args, db, n_raw);                         // sample threads are dealt to the replicas' devices in turn
+    const int n_gpus = replicas.n_gpus;
+    std::vector<sylph_db*>& dbs = replicas.dbs;
+    const std::vector<int>& replica_device = replicas.device;
     std::atomic<size_t> worker_no{0};
     const size_t n_workers = sample_workers(args.threads, (size_t)n_gpus, n_raw);
     const size_t ahead_limit = n_workers + 2;                        // sessions that may wait, sketched, for the profile stage
@@ -488,20 +518,10 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
             prepare(*eng, j);
         }
     };
-    sylph_pipeline* pipe = nullptr;
     sylph_pipeline_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.struct_size = sizeof(cfg);
-    cfg.n_workers = 2;                       // (they only finish the sessions the sample threads pushed)
-    cfg.depth = (uint32_t)ahead_limit + 1;
-    cfg.max_batch = 4;
-    cfg.c = (uint32_t)args.c; cfg.k = (uint32_t)args.k;
-    cfg.reads_mode = SYLPH_READS_PAIRED; cfg.seed_mode = SYLPH_SEED_AVX2_COMPAT;
-    cfg.want_table = args.estimate_unknown ? 1 : 0;                 // -u walks the counts on the host
-    cfg.min_number_kmers = args.min_number_kmers;
-    if (n_gpus > 1) hip_check(sylph_pipeline_create_multi(dbs.data(), (uint32_t)dbs.size(), &cfg, &pipe), "sylph_pipeline_create_multi");
-    else hip_check(sylph_pipeline_create(db, &cfg, &pipe), "sylph_pipeline_create");
-    struct PipeGuard { sylph_pipeline* p; ~PipeGuard() { sylph_pipeline_destroy(p); } } pipe_guard{pipe};
+    // 2 library workers (they only finish the sessions the sample threads pushed)
+    sylph_pipeline* pipe = replicas.create_pipeline(args, 2, (uint32_t)ahead_limit + 1, cfg);
+    PipeGuard pipe_guard{pipe};
     std::vector<std::thread> pool;
     size_t submitted = 0;
     struct Unconsumed {   // (declared before PoolJoin: runs after the sample threads are joined) sessions nobody took over
@@ -558,27 +578,162 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
     }
 }
 
-// ---- samples given as sketches (*.sylsp): the table is on the host
-void profile_sketch_files(const ContainCmdArgs& args, const std::vector<std::string>& read_sketch_files, sylph_db* db, const ReportTo& to) {
+// ---- samples given as sketches (*.sylsp; get_seq_sketch, contain.rs:544-599) ----
+// The road sketch files take when SYLPH_HIP_SYLSP_DEVICE is not set.  The project's ship rule (as for FASTA reads): the device's
+// road is the default only where whole `profile` commands over 64 sketches beat the host's road by more than both spreads, on
+// ascending and on shuffled files alike — profiles/sylsp_pipeline.txt holds the record: 2.3x and 6.3x, so it is on.
+constexpr bool SYLSP_DEVICE_DEFAULT = true;
+// contain.rs:551-570's refusal of a sketch whose c the database cannot serve (the reference says "Exiting." and goes on, so do we)
+void sketch_c_too_large(const std::string& file, uint64_t c, uint64_t genome_c) {
+    fprintf(stderr, "ERROR [sylph_hip] %s value of -c is %llu; this is greater than the smallest value of -c = %llu for a genome sketch. Exiting.\n",
+            file.c_str(), (unsigned long long)c, (unsigned long long)genome_c);
+}
+// SYLPH_HIP_FEED_TRACE: one line per sketch file — the road its table took, and whether the file's entries came strictly ascending
+void trace_sketch_route(const std::string& file, const char* route, int ascending, uint64_t n_entries, uint64_t n_table) {
+    if (!FeedLaps::on()) return;
+    fprintf(stderr, "[sylph_hip feed] sylsp %s: route %s, table %s, %llu entries -> %llu k-mers\n", file.c_str(), route,
+            ascending < 0 ? "sorted on the host" : ascending ? "ascending" : "sorted on the device", (unsigned long long)n_entries, (unsigned long long)n_table);
+}
+// The host's road: the table copied out of the file, sorted and deduplicated on one thread (read_sylsp), uploaded for the probe
+// and, in `profile`, once more for the reassignment pass.  What every sketch file took before the device unpacked tables; still
+// the road of SYLPH_HIP_SYLSP_DEVICE=0 and of a file with 2^31 entries or more.
+void profile_sketch_on_host(const ContainCmdArgs& args, const std::string& file, sylph_db* db, const ReportTo& to) {
     const uint64_t genome_c = to.genome_sketches[0].c;
-    for (const auto& sf : read_sketch_files) {
-        const std::vector<std::string> files{sf};
-        // get_seq_sketch, contain.rs:544-599
-        std::optional<SequencesSketch> seq;
-        {
-            SequencesSketch s = read_sylsp(files[0]);
-            if (s.c > genome_c) { fprintf(stderr, "ERROR [sylph_hip] %s value of -c is %llu; this is greater than the smallest value of -c = %llu for a genome sketch. Exiting.\n", files[0].c_str(), (unsigned long long)s.c, (unsigned long long)genome_c); }
-            else seq = std::move(s);
+    const SequencesSketch S = read_sylsp(file);
+    if (S.c > genome_c) { sketch_c_too_large(file, S.c, genome_c); return; }
+    trace_sketch_route(file, "host", -1, S.kmers.size(), S.kmers.size());
+    // first pass: GPU probe of every genome, then host statistics
+    const uint32_t* cc = nullptr; const uint64_t* coff = nullptr; const uint32_t* covs = nullptr; uint64_t ncov = 0;
+    hip_check(sylph_db_contain_view(db, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST,
+                                    args.min_number_kmers, &cc, &coff, &covs, &ncov), "sylph_db_contain_view");
+    report(to, S, file, cc, coff, covs, 4, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST, db);
+}
+// SYLPH_HIP_SYLSP_DEVICE: 1 = the tables of sketch files are unpacked on the device and go through the pipeline, 0 = the host's
+// road; unset = the default, which profiles/sylsp_pipeline.txt's measurement decides
+bool sylsp_device_enabled() {
+    static const bool on = [] { const char* v = getenv("SYLPH_HIP_SYLSP_DEVICE"); return v ? strcmp(v, "0") != 0 : SYLSP_DEVICE_DEFAULT; }();
+    return on;
+}
+
+// The device's road: up to `-t` threads map and validate the files ahead, in input order, and touch the tables' pages
+// (read_sylsp_header: the table stays in the mapping); this thread hands the entries to the pipeline as they lie in the file
+// (sylph_pipeline_submit_entries: a worker unpacks them on the device, ascending files are never sorted), takes the results in
+// input order and reports from the table in HBM, as for raw samples: file j + 1 is read while file j is probed and the
+// statistics of file j - 1 run; the probe is batched; --gpus N deals the samples to N replicas.  Order and messages are the
+// host road's: a file is refused, skipped or reported when its turn has come, after the rows of every file before it.
+void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vector<std::string>& read_sketch_files, sylph_db* db, const ReportTo& to) {
+    const size_t n_files = read_sketch_files.size();
+    if (n_files == 0) return;
+    if (!sylsp_device_enabled()) {
+        for (const auto& sf : read_sketch_files) { profile_sketch_on_host(args, sf, db, to); finished({sf}); }
+        return;
+    }
+    const uint64_t genome_c = to.genome_sketches[0].c;
+    struct Prepared { std::optional<SylspView> view; std::exception_ptr error; };
+    std::vector<std::promise<Prepared>> promises(n_files);
+    std::vector<std::future<Prepared>> futures;
+    for (auto& p : promises) futures.push_back(p.get_future());
+    ReplicaSet replicas(e, args, db, n_files);
+    const size_t n_workers = sample_workers(args.threads, 1, n_files);
+    const size_t ahead_limit = n_workers + 2;                        // files that may wait, mapped and touched, for their turn
+    std::atomic<size_t> next_job{0}, released{0};
+    std::atomic<bool> cancel{false};
+    std::mutex gate_mu;
+    std::condition_variable gate_cv;
+    auto prepare = [&](size_t j) {
+        Prepared pr;
+        try {
+            pr.view = read_sylsp_header(read_sketch_files[j]);
+            const SylspView& v = *pr.view;
+            if (v.meta.c <= genome_c && v.n_entries < (1ull << 31)) {   // (else nothing of the table is read on this road)
+                const volatile uint8_t* page = v.entries;            // one byte of every page: the faults are taken here, not under the staging copy
+                for (uint64_t at = 0, bytes = v.n_entries * 12; at < bytes; at += 4096) (void)page[at];
+            }
+        } catch (...) { pr.error = std::current_exception(); }
+        promises[j].set_value(std::move(pr));
+    };
+    auto worker = [&] {
+        for (;;) {
+            const size_t j = next_job++;
+            if (j >= n_files) return;
+            {
+                std::unique_lock<std::mutex> lk(gate_mu);
+                gate_cv.wait(lk, [&] { return cancel.load() || j < released.load() + ahead_limit; });
+            }
+            if (cancel) { promises[j].set_value(Prepared{}); continue; }
+            prepare(j);
         }
-        if (seq) {
-            const SequencesSketch& S = *seq;
-            // first pass: GPU probe of every genome, then host statistics
-            const uint32_t* cc = nullptr; const uint64_t* coff = nullptr; const uint32_t* covs = nullptr; uint64_t ncov = 0;
-            hip_check(sylph_db_contain_view(db, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST,
-                                            args.min_number_kmers, &cc, &coff, &covs, &ncov), "sylph_db_contain_view");
-            report(to, S, files[0], cc, coff, covs, 4, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST, db);
+    };
+    sylph_pipeline_config cfg;
+    sylph_pipeline* pipe = replicas.create_pipeline(args, 2, (uint32_t)ahead_limit + 1, cfg);
+    PipeGuard pipe_guard{pipe};                                      // (finishes what is outstanding: the mappings below outlive it)
+    std::vector<std::thread> pool;
+    struct PoolJoin {   // on every way out: the prepare threads stop taking work and are joined
+        std::vector<std::thread>& pool; std::atomic<bool>& cancel; std::mutex& mu; std::condition_variable& cv;
+        ~PoolJoin() {
+            { std::lock_guard<std::mutex> lk(mu); cancel = true; }
+            cv.notify_all();
+            for (auto& t : pool) if (t.joinable()) t.join();
         }
-        finished(files);
+    };
+    enum class Turn { Device, Host, Skip, Failed };
+    std::vector<std::optional<SylspView>> views(n_files);           // a submitted file's mapping stays until its result has been taken
+    std::vector<Turn> turn(n_files, Turn::Skip);
+    std::vector<std::exception_ptr> errors(n_files);
+    struct Drain {      // (declared behind `views`: runs first) nothing may still read a mapping when it goes
+        sylph_pipeline* p;
+        ~Drain() { sylph_pipeline_result r; while (sylph_pipeline_outstanding(p) && sylph_pipeline_next(p, &r) == SYLPH_OK) {} }
+    } drain{pipe};
+    PoolJoin pool_join{pool, cancel, gate_mu, gate_cv};
+    for (size_t w = 0; w < n_workers; w++) pool.emplace_back(worker);
+    size_t submitted = 0, done = 0, submit_end = n_files;            // submit_end: nothing is handed over behind a file that failed, or that waits for the host's road
+    auto release_one = [&] { { std::lock_guard<std::mutex> lk(gate_mu); released++; } gate_cv.notify_all(); };
+    while (done < n_files) {
+        // hand over every prepared file that is ready, in input order (wait for one only when nothing is outstanding)
+        while (submitted < submit_end && sylph_pipeline_outstanding(pipe) < cfg.depth) {
+            const bool must_wait = sylph_pipeline_outstanding(pipe) == 0 && submitted == done;
+            if (!must_wait && futures[submitted].wait_for(std::chrono::seconds(0)) != std::future_status::ready) break;
+            Prepared pr = futures[submitted].get();
+            const size_t j = submitted++;
+            if (pr.error || !pr.view) {
+                turn[j] = Turn::Failed;
+                errors[j] = pr.error ? pr.error : std::make_exception_ptr(Error{1, "The sketch `" + read_sketch_files[j] + "` was not read"});
+                submit_end = submitted;
+                break;
+            }
+            views[j] = std::move(pr.view);
+            if (views[j]->meta.c > genome_c) turn[j] = Turn::Skip;
+            else if (views[j]->n_entries >= (1ull << 31)) {
+                // the host's road probes the database from this thread: nothing is handed over behind such a file until it has had
+                // its turn, so the pipeline is idle (every earlier sample returned) while that probe runs
+                turn[j] = Turn::Host;
+                submit_end = submitted;
+                break;
+            } else {
+                hip_check(sylph_pipeline_submit_entries(pipe, views[j]->entries, views[j]->n_entries, SYLPH_MEM_HOST, j), "sylph_pipeline_submit_entries");
+                turn[j] = Turn::Device;
+            }
+        }
+        const size_t j = done;
+        if (j >= submitted) continue;        // (the wait above guarantees progress)
+        const std::string& file = read_sketch_files[j];
+        if (turn[j] == Turn::Failed) std::rethrow_exception(errors[j]);
+        if (turn[j] == Turn::Skip) sketch_c_too_large(file, views[j]->meta.c, genome_c);
+        else if (turn[j] == Turn::Host) { profile_sketch_on_host(args, file, db, to); submit_end = n_files; }
+        else {
+            sylph_pipeline_result r;
+            hip_check(sylph_pipeline_next(pipe, &r), "sylph_pipeline_next");
+            if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + file + ": " + (r.error ? r.error : "GPU stage failed")};
+            trace_sketch_route(file, "device", sylph_pipeline_ascending_of_last(pipe), views[j]->n_entries, r.n_table);
+            SequencesSketch& S = views[j]->meta;
+            if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+            report(to, S, file, r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
+                   replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))]);
+        }
+        finished({file});
+        views[j].reset();
+        done++;
+        release_one();
     }
 }
 }  // namespace
@@ -614,7 +769,7 @@ int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
     print_header(args.pseudotax, out, args.estimate_unknown);
     const ReportTo to{args, genome_sketches, out, e.context()};
     if (!read_files.empty()) profile_raw_samples(e, args, read_files, db.d, to);
-    profile_sketch_files(args, read_sketch_files, db.d, to);
+    profile_sketch_files(e, args, read_sketch_files, db.d, to);
     fflush(out);
     join_background();
     info("sylph finished.");

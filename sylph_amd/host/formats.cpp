@@ -137,12 +137,42 @@ void write_sylsp(const std::string& path, const SequencesSketch& s) {
     w.finish();
 }
 
-SequencesSketch read_sylsp(const std::string& path) {
-    Reader r(path);
-    SequencesSketch s;
+namespace {
+// the length of a .sylsp file's table, its n * 12 bytes checked against the file (the reader stands at the first entry)
+uint64_t sylsp_table_length(Reader& r) {
     const uint64_t n = r.u64();
     if (n > r.b.size() / 12) r.need(r.b.size() + 1);
     r.need(n * 12);
+    return n;
+}
+// what follows the table (trailing bytes behind it are tolerated, as bincode's deserialize_from does)
+void read_sylsp_tail(Reader& r, SequencesSketch& s) {
+    s.c = r.u64();
+    s.k = r.u64();
+    s.file_name = r.str();
+    if (r.u8()) s.sample_name = r.str();
+    s.paired = r.u8() != 0;
+    s.mean_read_length = r.f64();
+}
+}  // namespace
+
+SylspView read_sylsp_header(const std::string& path) {
+    auto rd = std::make_shared<Reader>(path);
+    Reader& r = *rd;
+    SylspView v;
+    v.n_entries = sylsp_table_length(r);
+    v.entries_offset = r.p;
+    v.entries = v.n_entries ? (const uint8_t*)&r.b[r.p] : nullptr;
+    r.p += v.n_entries * 12;
+    read_sylsp_tail(r, v.meta);
+    v.mapping = rd;
+    return v;
+}
+
+SequencesSketch read_sylsp(const std::string& path) {
+    Reader r(path);
+    SequencesSketch s;
+    const uint64_t n = sylsp_table_length(r);
     std::vector<std::pair<uint64_t, uint32_t>> kv(n);
     for (uint64_t i = 0; i < n; i++) { kv[i].first = r.u64(); kv[i].second = r.u32(); }
     // the reference inserts into a map (types.rs:117-129): a repeated key keeps its last value
@@ -152,12 +182,7 @@ SequencesSketch read_sylsp(const std::string& path) {
         s.kmers.push_back(kv[i].first);
         s.counts.push_back(kv[i].second);
     }
-    s.c = r.u64();
-    s.k = r.u64();
-    s.file_name = r.str();
-    if (r.u8()) s.sample_name = r.str();
-    s.paired = r.u8() != 0;
-    s.mean_read_length = r.f64();
+    read_sylsp_tail(r, s);
     return s;
 }
 

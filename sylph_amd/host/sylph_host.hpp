@@ -71,6 +71,17 @@ struct GenomeSketch {
 // ---- on-disk formats: bincode 1.3.3 default options (little-endian, fixed-width ints, u64 lengths) ----
 void write_sylsp(const std::string& path, const SequencesSketch& s);          // sketch.rs:360,411
 SequencesSketch read_sylsp(const std::string& path);                          // contain.rs:559
+// the same file mapped and validated (read_sylsp's checks, its error, its tolerance of trailing bytes) with the table left where it
+// lies: `meta` carries everything but kmers / counts, `entries` the n_entries packed 12-byte (k-mer, count) entries as bincode wrote
+// them (any order, k-mers may repeat) inside `mapping` — what sylph_pipeline_submit_entries takes
+struct SylspView {
+    SequencesSketch meta;
+    const uint8_t* entries = nullptr;
+    uint64_t n_entries = 0;
+    uint64_t entries_offset = 0;      // where the first entry lies in the file
+    std::shared_ptr<void> mapping;
+};
+SylspView read_sylsp_header(const std::string& path);
 void write_syldb(const std::string& path, const std::vector<GenomeSketch>& g); // sketch.rs:474
 std::vector<GenomeSketch> read_syldb(const std::string& path);                // contain.rs:495
 // the same without copying a k-mer: one pass over the record headers of the mapped file (contain.rs:492-500 is the reference's
