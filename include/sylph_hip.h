@@ -634,8 +634,12 @@ void sylph_table_destroy(sylph_table *t);
  * (sylph_pipeline_submit_session: the pipeline finishes it and owns it from then on).
  * The profile thread probes the oldest sketched sample together with every consecutive sample that is ready by then, up to
  * `max_batch` tables per launch.  With a sharded database (`comm` set; every rank runs a pipeline with the same max_batch and
- * submits the same number of samples) a batch is always exactly the next max_batch samples — or, after sylph_pipeline_flush,
- * what is left up to the flush point — so that all ranks enter the exchange of sylph_db_contain_batch_sharded together. */
+ * makes the same sequence of submit / flush calls) a batch is always exactly the next max_batch samples — or, after
+ * sylph_pipeline_flush, what is left up to the flush point — so that all ranks enter the exchange of
+ * sylph_db_contain_batch_sharded together: the batch boundaries are a function of the call sequence alone, never of the timing of
+ * the threads (every flush leaves a boundary of its own; a later flush does not move an earlier one).
+ * The rules and the defaults below are csrc/pipeline_plan.h, the threads and queues csrc/pipeline_core.h; both are tested without
+ * a GPU. */
 typedef struct sylph_pipeline sylph_pipeline;
 typedef struct sylph_read_batch {   /* the arguments of sylph_sketch_push_enc */
     const uint8_t *bases;
@@ -644,7 +648,7 @@ typedef struct sylph_read_batch {   /* the arguments of sylph_sketch_push_enc */
 } sylph_read_batch;
 typedef struct sylph_pipeline_config {
     uint32_t struct_size;     /* sizeof(sylph_pipeline_config) */
-    uint32_t n_workers;       /* sketch threads / contexts; 0 = default (3) */
+    uint32_t n_workers;       /* sketch threads / contexts; 0 = default (3): the defaults are pipeline_plan.h's */
     uint32_t depth;           /* samples that may be outstanding (submitted, not yet returned by sylph_pipeline_next); 0 = n_workers + 5 */
     uint32_t max_batch;       /* sample tables per probe launch at most (<= 64); 0 = default (8) */
     uint32_t c, k;            /* sylph_sketch_begin's arguments for the samples submitted as batches */
@@ -694,7 +698,8 @@ int sylph_pipeline_submit_entries(sylph_pipeline *p, const void *entries, uint64
 /* Of the sample the last successful sylph_pipeline_next returned: 1 = its entries ascended strictly (unpacked only), 0 = they were
  * sorted on the device, -1 = it was not submitted as entries (or p is null).  sylph_table_view's was_ascending for a pipeline. */
 int sylph_pipeline_ascending_of_last(sylph_pipeline *p);
-/* Sharded pipelines only need it: everything submitted so far may be probed in a batch smaller than max_batch. */
+/* Sharded pipelines only need it: everything submitted so far may be probed in a batch smaller than max_batch, and no batch
+ * reaches across the flush point — flushes with samples outstanding in between leave one batch boundary each. */
 int sylph_pipeline_flush(sylph_pipeline *p);
 /* Blocks until the OLDEST outstanding sample is done.  Every pointer of *out stays valid until the next sylph_pipeline_next /
  * sylph_pipeline_destroy on this pipeline (the sample's session and its share of the result block are released then). */

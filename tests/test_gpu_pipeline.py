@@ -228,6 +228,28 @@ def test_pipeline_sharded_one_rank(ctx):
     p.close(); db.close(); comm.close()
 
 
+@pytest.mark.timeout(300)
+def test_pipeline_sharded_two_flushes_leave_two_boundaries(ctx):
+    """Submit 2, flush, submit 2, flush on a sharded pipeline with max_batch 4: the probe batches are 2 and 2 whatever the timing of the
+    workers — every flush leaves a boundary of its own (pipeline_plan.h), so that all ranks enter the exchange with the same batches.
+    (While a flush point was one word that the second flush overwrote, a rank whose workers were late formed one batch of 4.)"""
+    rng, genomes, db_k, goff = small_world(7)
+    comm = S.Comm(0, 1, ctx=ctx, rccl_id=S.Comm.rccl_unique_id())
+    bounds = S.shard_bounds(int(db_k.max()), 1)
+    db = S.Database(ctx, db_k, goff, shard=(bounds, 1, 0))
+    p = S.Pipeline(db, c=50, paired=True, n_workers=2, depth=6, max_batch=4, comm=comm)
+    data = [sample_reads(rng, genomes, [i % 5], 300) for i in range(4)]
+    for i, (b, off) in enumerate(data):
+        assert p.submit_device([(b.ctypes.data, off.ctypes.data, len(off) - 1, int(off[-1]))], tag=i, mem=MEM_HOST)
+        if i % 2 == 1:
+            p.flush()
+    for i in range(4):
+        r = p.next()
+        assert r["tag"] == i and r["probe_batch"] == 2
+        check_result(r, O.sketch_reads(*data[i], c=50, paired=True), db_k, goff)
+    p.close(); db.close(); comm.close()
+
+
 @pytest.mark.parametrize("db_mode", ["default", "shard", "genome"])
 def test_bench_two_ranks_on_one_gpu_small_workload(db_mode):
     """`bench.py --gpus 2` end to end on whatever the box has (one GPU: the two ranks share it): the N > 1 code path of the bench —
