@@ -520,6 +520,53 @@ int sylph_bootstrap_counts(sylph_ctx *ctx, const void *covs, uint32_t cov_width,
                            const uint32_t *n_total, uint32_t n_items, int mem, uint64_t seed, uint32_t iters,
                            sylph_bootstrap_summary *out, uint8_t *declined);
 
+/* ---- coverage rows summarised on the device (csrc/row_stats.hip, csrc/row_stats_plan.h) -----------------------------------------
+ * Everything the statistics half of get_stats (contain.rs:657-690) reads off a genome's ascending coverage row before its first
+ * floating-point operation is integer work: the median, the prefix the Poisson cut keeps (:666-684), the wrapping u32 sum of that
+ * prefix, and the five counts ratio_lambda reads (inference.rs:207-242).  This call reduces every non-empty row to those integers
+ * and drops the rows that cannot reach the ANI cut; what comes back are the CANDIDATES, in ascending row order, each with all its
+ * coverage values.  The caller makes the exact f64 decision for every candidate (host/inference.cpp stats_head_from_summary), so
+ * the statistics stay bit for bit the caller's own.
+ * The filter is the caller's: cut[m], m = 0..29, is the largest x with poisson_cdf(m, y) < CUTOFF_PVALUE for every integer y in
+ * [m, x] — built at run time from the caller's own cdf — or SYLPH_ROW_CUT_NONE where poisson_cdf(m, m) fails the test already.  A row
+ * is dropped only when its containment index — contain_count / row_kmers, or with a lambda (and no_adj == 0)
+ * keep / (1 - exp(-lambda)) / (row_kmers - contain_count + keep) — lies below reject_below; an index that is not finite or not >= 0
+ * is never dropped.  The caller sets reject_below = min_ani^k * (1 - 2^-30): the margin is about a million times the rounding of
+ * pow, exp and two divisions, and costs only the rows inside the band.  reject_below = 0 drops nothing: every non-empty row
+ * comes back.
+ * covs: values of cov_width = 1, 2 or 4 bytes in `mem` (host or device), ascending within a row; row i is
+ * covs[cov_off[i] .. cov_off[i + 1]).  cov_off (n_rows + 1 entries; cov_off[0] need not be 0) and row_kmers (n_rows entries: the
+ * k-mers of genome i) are host arrays, borrowed for the call.  Results are library-allocated and released with sylph_free():
+ * (*rows)[j] for candidate j, (*row_cov_off)[j .. j + 1] its values in *row_covs (cov_width bytes each, (*row_cov_off)[0] = 0).
+ * *n == 0 gives *rows == NULL and *row_covs == NULL.  SYLPH_ERR_INVALID for a width other than 1, 2, 4, a cov_off that decreases,
+ * a row longer than its genome (contain_count > row_kmers) or than 2^32 - 1 values, a null filter or one of the wrong struct_size.
+ * Kernel timer: "row_stats". */
+#define SYLPH_ROW_CUT_ENTRIES 30
+#define SYLPH_ROW_CUT_NONE 0xFFFFFFFFu
+typedef struct sylph_row_filter {
+    uint32_t struct_size;        /* sizeof(sylph_row_filter) */
+    uint32_t k;
+    double reject_below;         /* min_ani^k * (1 - 2^-30); 0 = keep every non-empty row */
+    double min_count_correct;    /* ratio_lambda's (inference.rs:236) */
+    uint32_t no_adj;             /* --no-adjust: the index is always contain_count / row_kmers */
+    uint32_t reserved;           /* 0 */
+    uint32_t cut[SYLPH_ROW_CUT_ENTRIES];
+} sylph_row_filter;
+typedef struct sylph_row_summary {
+    uint32_t row;            /* index of the row (the genome) */
+    uint32_t contain_count;  /* values in the row */
+    uint32_t median;         /* row[contain_count / 2] */
+    uint32_t keep;           /* length of the prefix the Poisson cut keeps = the summary's n_nonzero */
+    uint32_t sum;            /* wrapping u32 sum of the kept prefix */
+    uint32_t n_distinct;     /* distinct values of the kept prefix, saturating at 2 */
+    uint32_t mode;           /* most frequent value of the kept prefix; ties go to the larger value */
+    uint32_t mode_count;
+    uint32_t next_count;     /* how often mode + 1 occurs inside the kept prefix */
+} sylph_row_summary;
+int sylph_row_summaries(sylph_ctx *ctx, const void *covs, uint32_t cov_width, const uint64_t *cov_off, const uint32_t *row_kmers,
+                        uint32_t n_rows, int mem, const sylph_row_filter *filter, sylph_row_summary **rows, uint32_t *n,
+                        uint64_t **row_cov_off, void **row_covs);
+
 /* ---- batched containment: S samples per call --------------------------------------------------------------------- */
 
 /* One sample table: n (k-mer, count) entries, k-mers ascending and distinct (what sylph_sketch_finish[_device] returns). */
@@ -698,6 +745,19 @@ int sylph_pipeline_submit_entries(sylph_pipeline *p, const void *entries, uint64
 /* Of the sample the last successful sylph_pipeline_next returned: 1 = its entries ascended strictly (unpacked only), 0 = they were
  * sorted on the device, -1 = it was not submitted as entries (or p is null).  sylph_table_view's was_ascending for a pipeline. */
 int sylph_pipeline_ascending_of_last(sylph_pipeline *p);
+/* The statistics head counted on the device (sylph_row_summaries above) for every probe batch of the pipeline.  Call
+ * sylph_pipeline_set_row_filter before the first submit (SYLPH_ERR_STATE after it; SYLPH_ERR_INVALID on a sharded pipeline, for a null
+ * filter or one of the wrong struct_size).  From then on the profile thread summarises the rows of every result block on the device
+ * and copies ONLY THE CANDIDATES to the host: contain_count / cov_off / covs of every sylph_pipeline_result are NULL (cov_width and
+ * n_covs, the sample's total, are still reported), and sylph_pipeline_rows_of_last hands out the candidates of the sample the last
+ * successful sylph_pipeline_next returned: rows[0 .. *n) in ascending genome order (`row` = the genome's index), the values of
+ * candidate j = row_covs[row_cov_off[j] .. row_cov_off[j + 1]) (cov_width bytes each; the samples of a probe batch share
+ * row_covs, so row_cov_off[0] is 0 only for the first of them — always index through it).  The pointers live as long as the
+ * result's other pointers.  Without a filter — or for a sample whose status is not SYLPH_OK — *n is 0 and the pointers are NULL.
+ * The router of sylph_pipeline_create_multi forwards both calls. */
+int sylph_pipeline_set_row_filter(sylph_pipeline *p, const sylph_row_filter *filter);
+int sylph_pipeline_rows_of_last(sylph_pipeline *p, const sylph_row_summary **rows, uint32_t *n, const uint64_t **row_cov_off,
+                                const void **row_covs, uint32_t *cov_width);
 /* Sharded pipelines only need it: everything submitted so far may be probed in a batch smaller than max_batch, and no batch
  * reaches across the flush point — flushes with samples outstanding in between leave one batch boundary each. */
 int sylph_pipeline_flush(sylph_pipeline *p);

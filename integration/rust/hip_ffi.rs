@@ -14,6 +14,8 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphUpload { _p: [u8; 0] }
 #[repr(C)] pub struct SylphSampleRef { pub kmers: *const u64, pub counts: *const u32, pub n: u64 }   // one sorted (k-mer, count) table
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
+#[repr(C)] pub struct SylphRowFilter { pub struct_size: u32, pub k: u32, pub reject_below: f64, pub min_count_correct: f64, pub no_adj: u32, pub reserved: u32, pub cut: [u32; 30] }   // sylph_row_filter; cut[m] = 0xFFFFFFFF: none
+#[repr(C)] pub struct SylphRowSummary { pub row: u32, pub contain_count: u32, pub median: u32, pub keep: u32, pub sum: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one candidate row
 #[repr(C)] pub struct SylphReassignEdge { pub winner: u32, pub loser: u32, pub count: u32 }   // sylph_reassign_edge: ranks in the passing list
 #[repr(C)] pub struct SylphCommOps {   // caller-supplied collectives on device buffers (stream = hipStream_t); 0 = success
     pub all_gather: extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: u64, stream: *mut c_void) -> c_int,
@@ -183,6 +185,17 @@ extern "C" {
     pub fn sylph_bootstrap_counts(ctx: *mut SylphCtx, covs: *const c_void, cov_width: u32, cov_off: *const u64, keep: *const u32,
                                   n_total: *const u32, n_items: u32, mem: c_int, seed: u64, iters: u32,
                                   out: *mut SylphBootstrapSummary, declined: *mut u8) -> c_int;
+    // the integer half of get_stats' statistics (contain.rs:657-690) for every row of a coverage view in one call: the rows that cannot
+    // reach the ANI cut are dropped on the device, the candidates come back in row order with their values (freed with sylph_free);
+    // the f64 half and the exact decision stay here
+    pub fn sylph_row_summaries(ctx: *mut SylphCtx, covs: *const c_void, cov_width: u32, cov_off: *const u64, row_kmers: *const u32,
+                               n_rows: u32, mem: c_int, filter: *const SylphRowFilter, rows: *mut *mut SylphRowSummary, n: *mut u32,
+                               row_cov_off: *mut *mut u64, row_covs: *mut *mut c_void) -> c_int;
+    // the pipeline's form of it: set before the first submit, every probe batch is then summarised on the device and only the
+    // candidates travel (the result's contain_count / cov_off / covs are null); rows_of_last = those of the sample next() returned
+    pub fn sylph_pipeline_set_row_filter(p: *mut SylphPipeline, filter: *const SylphRowFilter) -> c_int;
+    pub fn sylph_pipeline_rows_of_last(p: *mut SylphPipeline, rows: *mut *const SylphRowSummary, n: *mut u32, row_cov_off: *mut *const u64,
+                                       row_covs: *mut *const c_void, cov_width: *mut u32) -> c_int;
     // k-mer-range shards: bounds for `world` GPUs, upload of this rank's range, communicator, the collective batch call
     pub fn sylph_shard_bounds(max_kmer: u64, world: u32, bounds: *mut u64) -> c_int;
     pub fn sylph_db_upload_shard(ctx: *mut SylphCtx, kmers: *const u64, genome_off: *const u64, n_genomes: u64, mem: c_int,

@@ -46,7 +46,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
            "sylph_bunzip2", "sylph_bunzip2_files",
            "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "sylph_bunzip2_stream_info", "sylph_bunzip2_stream_destroy", "sylph_bootstrap_counts",
-           "sylph_table_from_entries", "sylph_table_view", "sylph_table_destroy", "sylph_pipeline_submit_entries", "sylph_pipeline_ascending_of_last"]
+           "sylph_table_from_entries", "sylph_table_view", "sylph_table_destroy", "sylph_pipeline_submit_entries", "sylph_pipeline_ascending_of_last",
+           "sylph_row_summaries", "sylph_pipeline_set_row_filter", "sylph_pipeline_rows_of_last"]
 
 
 def load():
@@ -176,6 +177,9 @@ def load():
     L.sylph_table_destroy.restype = None
     L.sylph_pipeline_submit_entries.argtypes = [vp, vp, u64, i32, u64]
     L.sylph_pipeline_ascending_of_last.argtypes = [vp]
+    L.sylph_pipeline_set_row_filter.argtypes = [vp, vp]
+    L.sylph_pipeline_rows_of_last.argtypes = [vp, P(vp), P(u32), P(vp), P(vp), P(u32)]
+    L.sylph_row_summaries.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp, P(vp), P(u32), P(vp), P(vp)]
     _LIB = L
     return L
 
@@ -315,6 +319,42 @@ def bootstrap_counts(ctx, covs, cov_off, keep, n_total, seed=7, iters=100, cov_w
         ptr, width, mem = C.c_void_p(int(covs)), int(cov_width), MEM_DEVICE
     _check(load().sylph_bootstrap_counts(ctx._h, ptr, width, _ptr(off), _ptr(kp), _ptr(nt), n, mem, int(seed), int(iters), _ptr(out), _ptr(declined)))
     return out, declined
+
+
+ROW_CUT_ENTRIES, ROW_CUT_NONE = 30, 0xFFFFFFFF
+ROW_SUMMARY = np.dtype([("row", np.uint32), ("contain_count", np.uint32), ("median", np.uint32), ("keep", np.uint32), ("sum", np.uint32),
+                        ("n_distinct", np.uint32), ("mode", np.uint32), ("mode_count", np.uint32), ("next_count", np.uint32)])
+
+
+class RowFilter(C.Structure):
+    """sylph_row_filter"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("reject_below", C.c_double), ("min_count_correct", C.c_double),
+                ("no_adj", C.c_uint32), ("reserved", C.c_uint32), ("cut", C.c_uint32 * ROW_CUT_ENTRIES)]
+
+
+def row_filter(cut, k=31, reject_below=0.0, min_count_correct=3.0, no_adj=False):
+    f = RowFilter(C.sizeof(RowFilter), int(k), float(reject_below), float(min_count_correct), int(bool(no_adj)), 0)
+    for m, c in enumerate(cut):
+        f.cut[m] = int(c)
+    return f
+
+
+def row_summaries(ctx, covs, cov_off, row_kmers, filt, cov_width=None):
+    """sylph_row_summaries: -> (rows[n] of ROW_SUMMARY, row_cov_off[n + 1], row_covs) — the candidates in ascending row order.  covs: a
+    uint8 / uint16 / uint32 array (MEM_HOST), or the integer address of device memory with cov_width given (MEM_DEVICE).  filt: a
+    RowFilter, or None (an error)."""
+    off, rk = _np(cov_off, np.uint64), _np(row_kmers, np.uint32)
+    if cov_width is None:
+        a = np.ascontiguousarray(covs)
+        ptr, width, mem, dtype = (_ptr(a) if len(a) else None), a.dtype.itemsize, MEM_HOST, a.dtype
+    else:
+        ptr, width, mem = C.c_void_p(int(covs)), int(cov_width), MEM_DEVICE
+        dtype = {1: np.uint8, 2: np.uint16, 4: np.uint32}.get(width, np.uint8)
+    rows, n, roff, rcovs = C.c_void_p(), C.c_uint32(0), C.c_void_p(), C.c_void_p()
+    _check(load().sylph_row_summaries(ctx._h, ptr, width, _ptr(off), _ptr(rk) if len(rk) else None, len(rk), mem,
+                                      C.byref(filt) if filt is not None else None, C.byref(rows), C.byref(n), C.byref(roff), C.byref(rcovs)))
+    out_off = _take(roff, n.value + 1, np.uint64)
+    return _take(rows, n.value, ROW_SUMMARY), out_off, _take(rcovs, int(out_off[-1]), dtype)
 
 
 def pack_2bit(ascii_bases):
@@ -1035,7 +1075,8 @@ class Pipeline:
         out = dict(tag=int(r.tag), n_table=int(r.n_table), dup_removed=int(r.dup_removed), dev_kmers=r.dev_kmers or 0,
                    replica=int(load().sylph_pipeline_replica_of_last(self._h)),
                    dev_counts=r.dev_counts or 0, n_covs=int(r.n_covs), probe_batch=int(r.probe_batch),
-                   t=(r.t_submit, r.t_sketch_begin, r.t_sketch_end, r.t_profile_begin, r.t_done))
+                   t=(r.t_submit, r.t_sketch_begin, r.t_sketch_end, r.t_profile_begin, r.t_done),
+                   cov_width=int(r.cov_width), result_pointers=(r.contain_count or 0, r.cov_off or 0, r.covs or 0))
         if views:
             G = self.db.n_genomes
 
@@ -1048,12 +1089,29 @@ class Pipeline:
             out["contain_count"] = view(r.contain_count, G, C.c_uint32, np.uint32)
             out["cov_off"] = off
             # covs is the base of the whole batch's values; cov_off indexes it
-            hi = int(off[G]) if G else 0
+            hi = int(off[G]) if G and len(off) else 0                  # (a pipeline with a row filter hands out no views)
             out["covs"] = view(r.covs, hi, ct, dt)
             if self._want_table:
                 out["kmers"] = view(r.kmers, int(r.n_table), C.c_uint64, np.uint64)
                 out["counts"] = view(r.counts, int(r.n_table), C.c_uint32, np.uint32)
         return out
+
+    def set_row_filter(self, filt):
+        """sylph_pipeline_set_row_filter (before the first submit): from then on only the candidates of every sample reach the host —
+        rows_of_last(); contain_count / cov_off / covs of next() are empty.  filt: a RowFilter (row_filter()), or None (an error)."""
+        _check(load().sylph_pipeline_set_row_filter(self._h, C.byref(filt) if filt is not None else None))
+
+    def rows_of_last(self):
+        """Of the sample next() returned last: (rows[n] of ROW_SUMMARY, row_cov_off[n + 1], row_covs up to row_cov_off[n]) — copies."""
+        rows, n, off, covs, width = C.c_void_p(), C.c_uint32(0), C.c_void_p(), C.c_void_p(), C.c_uint32(0)
+        _check(load().sylph_pipeline_rows_of_last(self._h, C.byref(rows), C.byref(n), C.byref(off), C.byref(covs), C.byref(width)))
+        dt = {1: np.uint8, 2: np.uint16, 4: np.uint32}.get(width.value, np.uint8)
+        if not n.value:
+            return np.zeros(0, dtype=ROW_SUMMARY), np.zeros(1, dtype=np.uint64), np.zeros(0, dtype=dt)
+        r = np.frombuffer(C.string_at(rows, n.value * ROW_SUMMARY.itemsize), dtype=ROW_SUMMARY).copy()
+        o = np.frombuffer(C.string_at(off, (n.value + 1) * 8), dtype=np.uint64).copy()
+        v = np.frombuffer(C.string_at(covs, int(o[-1]) * width.value), dtype=dt).copy()
+        return r, o, v
 
     def ascending_of_last(self):
         """Of the sample next() returned last: 1 its entries ascended strictly, 0 they were sorted, -1 not submitted as entries."""

@@ -21,6 +21,7 @@
 #include "contain_index.h"
 #include "shard_plan.h"
 #include "device_common.h"
+#include "row_stats.h"
 
 namespace sylph {
 namespace {
@@ -362,9 +363,36 @@ bool probe_batch_async(sylph_db* db, std::vector<SampleRef>& refs, double min_nu
 
 // copies the block assembled in db->res out — straight into pinned host memory (the db's own block or the caller's, which carries its
 // layout itself; no staging copy, nothing pageable registered with HIP), one copy, + kmers_lost — and waits for it
+// With a row filter (db->row_filter, a pipeline's probe batch): the rows of the block in db->res are summarised on the device
+// (row_stats.hip) and only the candidates travel — their summaries, offsets and values, and where every sample's values began
+// (CandidateLayout).  The sizes come from the device: row_stats_device reads its two totals back, which is one small synchronisation
+// more than the plain road's; the copy is sized by them.
+static void copy_out_candidates(sylph_db* db, uint32_t n_hits, uint32_t width, uint64_t n_rows, HostBlock* dst) {
+    sylph_ctx* ctx = db->ctx;
+    const uint64_t G = db->n_genomes, n_samples = G ? n_rows / G : 0;
+    const ResultLayout lay(n_rows, n_hits, width, 0);
+    const char* d = db->res.as<char>();
+    RowStatsResult res(ctx);
+    row_stats_device(ctx, d + lay.covs, width, (const uint64_t*)d, db->glen.as<uint32_t>(), (uint32_t)G, (uint32_t)n_rows, n_hits, *db->row_filter, res);
+    const CandidateLayout c(res.n, res.n_vals, width, n_samples);
+    dst->ensure(c.end + 64);
+    dst->lay = lay;
+    dst->cand = c;
+    char* h = (char*)dst->p;
+    if (res.n) SY_HIP(hipMemcpyAsync(h, res.rows.p, (size_t)res.n * sizeof(row_stats_plan::RowSummary), hipMemcpyDeviceToHost, ctx->stream));
+    SY_HIP(hipMemcpyAsync(h + c.off, res.cov_off.p, ((size_t)res.n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (res.n_vals) SY_HIP(hipMemcpyAsync(h + c.covs, res.covs.p, (size_t)res.n_vals * width, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_rows) SY_HIP(hipMemcpyAsync(h + c.sample_off, res.sample_off.p, ((size_t)n_samples + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    else memset(h + c.sample_off, 0, 8);
+    SY_HIP(hipStreamSynchronize(ctx->stream));
+    if (!ctx->pending.empty()) profile_collect(ctx);
+}
+
 static void copy_out_rows(sylph_db* db, uint32_t n_hits, uint32_t width, uint64_t n_rows, bool with_lost, HostBlock* dst) {
     sylph_ctx* ctx = db->ctx;
     const uint64_t G = db->n_genomes;
+    if (db->row_filter && dst && !with_lost) { copy_out_candidates(db, n_hits, width, n_rows, dst); return; }
+    if (dst) dst->cand = CandidateLayout();
     const ResultLayout lay(n_rows, n_hits, width, with_lost ? G : 0);
     if (!dst) { db->lay = lay; db->last_rows = n_rows; dst = &db->h_block; }
     dst->ensure(lay.end + 64);
@@ -554,14 +582,20 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
 }
 
 uint32_t sylph::contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples, uint32_t n_samples, int mem, double min_number_kmers,
-                                   uint32_t* cov_width, HostBlock* dst, ResultViews* views) {
+                                   uint32_t* cov_width, HostBlock* dst, ResultViews* views, const row_stats_plan::Filter* row_filter) {
     SY_REQUIRE(db && cov_width, "null argument");
+    SY_REQUIRE(!row_filter || dst, "a row filter needs a block of the caller's");
     SY_REQUIRE(n_samples == 0 || samples, "null samples");
     SY_REQUIRE(mem == SYLPH_MEM_HOST || mem == SYLPH_MEM_DEVICE, "bad mem kind %d", mem);
     SY_REQUIRE(db->world == 1, "this database is one shard of %u: use sylph_db_contain_batch_sharded", db->world);
     sylph_ctx* ctx = db->ctx;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard dg(ctx->device);
+    struct FilterScope {      // the filter holds for this call alone
+        sylph_db* db;
+        FilterScope(sylph_db* d, const row_stats_plan::Filter* f) : db(d) { db->row_filter = f; }
+        ~FilterScope() { db->row_filter = nullptr; }
+    } filter_scope(db, row_filter);
     std::vector<SampleRef> refs(n_samples);
     uint64_t total = 0;
     for (uint32_t s = 0; s < n_samples; s++) {

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "index_plan.h"
+#include "row_stats_plan.h"
 
 namespace sylph {
 
@@ -218,11 +219,26 @@ struct ResultLayout {
         : ccount((R + 1) * 8), covs(ccount + R * 4), lost((covs + n_hits * width + 7) & ~(size_t)7), end(lost + lost_entries * 4) {}
 };
 
+// Layout of the block a call with a row filter leaves instead (row_stats.hip: only the candidates travel):
+// [rows n x sylph_row_summary | pad to 8 | cov_off (n+1) u64 | covs n_vals x width | pad to 8 | sample_off (S+1) u64]
+// with sample_off[s] = the full block's cov_off[s * n_genomes]: where the values of sample s began, for its n_covs.
+struct CandidateLayout {
+    bool on = false;
+    uint32_t n = 0;
+    uint64_t n_vals = 0;
+    size_t off = 0, covs = 0, sample_off = 0, end = 0;
+    CandidateLayout() = default;
+    CandidateLayout(uint32_t n_, uint64_t n_vals_, uint32_t width, uint64_t n_samples)
+        : on(true), n(n_), n_vals(n_vals_), off(((size_t)n_ * sizeof(row_stats_plan::RowSummary) + 7) & ~(size_t)7), covs(off + ((size_t)n_ + 1) * 8),
+          sample_off((covs + n_vals_ * width + 7) & ~(size_t)7), end(sample_off + (n_samples + 1) * 8) {}
+};
+
 // A block of page-locked host memory that results are copied into (grow-only).
 struct HostBlock {
     void* p = nullptr;
     size_t cap = 0;
     ResultLayout lay;            // layout of the result block it holds
+    CandidateLayout cand;        // cand.on: it holds the candidates of the block instead
     HostBlock() = default;
     HostBlock(const HostBlock&) = delete;
     HostBlock& operator=(const HostBlock&) = delete;
@@ -266,6 +282,7 @@ struct sylph_db {
     uint32_t rc_rep = 0, rc_rows = 0;
     hipEvent_t ev_cnt = nullptr;             // "the probe's counter words have arrived in pinned host memory"
     sylph::ResultLayout lay;                 // layout of the last result
+    const sylph::row_stats_plan::Filter* row_filter = nullptr;   // for the length of one contain_batch_impl call: summarise the rows, copy out the candidates only
     uint64_t last_rows = 0;
     sylph::HostBlock h_block;                // pinned host results of the plain entry points (the pipeline brings its own blocks)
     explicit sylph_db(sylph_ctx* cx)
@@ -301,9 +318,10 @@ void finish_hits(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_r
 // `views` (optional): the three result pointers into the block the call filled, taken while the context lock is still held —
 // a pipeline's profile thread working on the same database between the lock's release and the caller's own look at
 // db->lay / db->h_block would otherwise hand the caller somebody else's layout.
+// `row_filter` (optional, with `dst`): the rows are summarised on the device and only the candidates land in `dst` (dst->cand).
 struct ResultViews { const uint64_t* cov_off = nullptr; const uint32_t* contain_count = nullptr; const void* covs = nullptr; };
 uint32_t contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples, uint32_t n_samples, int mem, double min_number_kmers,
-                            uint32_t* cov_width, HostBlock* dst, ResultViews* views = nullptr);
+                            uint32_t* cov_width, HostBlock* dst, ResultViews* views = nullptr, const row_stats_plan::Filter* row_filter = nullptr);
 uint32_t contain_batch_sharded_impl(sylph_db* db, sylph_comm* comm, const sylph_sample_ref* samples, uint32_t n_local, int mem,
                                     double min_number_kmers, uint32_t* cov_width, HostBlock* dst, ResultViews* views = nullptr);
 inline void fill_views(const HostBlock& b, ResultViews* v) {

@@ -44,6 +44,7 @@ struct Block {   // one pinned result block (+ its layout), shared by the sample
     uint32_t width = 4;
     int status = SYLPH_OK;       // of the probe that filled it
     std::string error;
+    std::vector<uint32_t> cand_first;   // with a row filter: the candidates of slot s are cand_first[s] .. cand_first[s + 1] of the block's
 };
 
 struct Job : pipeline_core::JobBase<Block> {     // (owner: the worker whose context owns `sk`; adopted sessions and tables: none)
@@ -130,6 +131,8 @@ struct sylph_pipeline {      // the opaque handle: an Engine or a Router
     virtual int kernel_stats(const char* family, double* total_ms, uint64_t* launches) = 0;
     virtual int replica_of_last() = 0;
     virtual int ascending_of_last() = 0;
+    virtual int set_row_filter(const sylph_row_filter* f) = 0;
+    virtual int rows_of_last(const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs, uint32_t* cov_width) = 0;
 };
 
 namespace {
@@ -144,6 +147,11 @@ struct Engine final : sylph_pipeline {
     const double min_number_kmers;
     std::vector<sylph_ctx*> wctx;
     bool db_ref = false;                         // the profile thread works on the database's context
+    // sylph_pipeline_set_row_filter: set before the first submit and never again, so the profile thread reads it without a lock
+    std::unique_ptr<row_stats_plan::Filter> row_filter;
+    std::atomic<bool> submitted{false};
+    struct LastRows { const sylph_row_summary* rows = nullptr; uint32_t n = 0; const uint64_t* off = nullptr; const void* covs = nullptr; uint32_t width = 0; };
+    LastRows last_rows;                          // of the sample next returned last (the caller's thread only)
     std::atomic<int> last_ascending{-1};         // of the sample next returned last: its entries ascended (1) / were sorted (0); -1: not an entries job
     // tuning (sylph_pipeline_set_option): see the option table in include/sylph_hip.h
     std::atomic<uint32_t> serial_outside{0};     // "serialize_outside" = 1: the r01-r04 placement of that wait (A/B; profiles/r05_ab_seed_turn.txt)
@@ -261,8 +269,21 @@ struct Engine final : sylph_pipeline {
         if (!good.empty() || comm) {
             rc = guarded([&] {
                 if (comm) contain_batch_sharded_impl(db, comm, refs.data(), (uint32_t)refs.size(), SYLPH_MEM_DEVICE, min_number_kmers, &blk.width, &blk.mem);
-                else contain_batch_impl(db, refs.data(), (uint32_t)refs.size(), SYLPH_MEM_DEVICE, min_number_kmers, &blk.width, &blk.mem);
+                else contain_batch_impl(db, refs.data(), (uint32_t)refs.size(), SYLPH_MEM_DEVICE, min_number_kmers, &blk.width, &blk.mem, nullptr, row_filter.get());
             });
+        }
+        if (rc == SYLPH_OK && row_filter && blk.mem.cand.on) {
+            // The candidates come in ascending block row = slot * n_genomes + genome: where every slot's begin, then `row` becomes the genome
+            auto* rows = (sylph_row_summary*)blk.mem.p;
+            const uint64_t G = db->n_genomes;
+            const uint32_t n = blk.mem.cand.n;
+            blk.cand_first.assign(refs.size() + 1, n);
+            uint32_t at = 0;
+            for (size_t s = 0; s < refs.size(); s++) {
+                while (at < n && rows[at].row < s * G) at++;
+                blk.cand_first[s] = at;
+            }
+            for (uint32_t i = 0; i < n; i++) rows[i].row = (uint32_t)(rows[i].row % G);
         }
         if (rc == SYLPH_OK && want_table) {
             rc = guarded([&] {
@@ -295,6 +316,7 @@ struct Engine final : sylph_pipeline {
         j->is_entries = s.is_entries; j->entries = s.entries; j->n_entries = s.n_entries;
         j->mem = s.mem; j->enc = s.enc; j->tag = s.tag;
         j->t_submit = now_s();
+        submitted.store(true);
         switch (core->submit(j)) {
         case pipeline_core::Refusal::None: return SYLPH_OK;
         case pipeline_core::Refusal::Full:
@@ -332,7 +354,16 @@ struct Engine final : sylph_pipeline {
         out->t_submit = j->t_submit; out->t_sketch_begin = j->t_sketch0; out->t_sketch_end = j->t_sketch1;
         out->t_profile_begin = j->t_profile0; out->t_done = j->t_done;
         out->probe_batch = j->batch_size;
-        if (j->slot >= 0) {
+        last_rows = LastRows{};
+        if (j->slot >= 0 && b.mem.cand.on) {     // a row filter: the candidates only (sylph_pipeline_rows_of_last)
+            const char* h = (const char*)b.mem.p;
+            const CandidateLayout& c = b.mem.cand;
+            const uint64_t* sample_off = (const uint64_t*)(h + c.sample_off);
+            const uint32_t lo = b.cand_first[(size_t)j->slot], hi = b.cand_first[(size_t)j->slot + 1];
+            out->cov_width = b.width;
+            out->n_covs = sample_off[j->slot + 1] - sample_off[j->slot];
+            last_rows = LastRows{(const sylph_row_summary*)h + lo, hi - lo, (const uint64_t*)(h + c.off) + lo, h + c.covs, b.width};
+        } else if (j->slot >= 0) {
             const char* h = (const char*)b.mem.p;
             const uint64_t G = db->n_genomes, row0 = (uint64_t)j->slot * G;
             out->cov_off = (const uint64_t*)h + row0;                  // G + 1 entries; values index `covs`
@@ -366,6 +397,27 @@ struct Engine final : sylph_pipeline {
     }
     int replica_of_last() override { return 0; }
     int ascending_of_last() override { return last_ascending.load(); }
+    int set_row_filter(const sylph_row_filter* f) override {
+        return guarded([&] {
+            SY_REQUIRE(f, "sylph_pipeline_set_row_filter: null filter");
+            SY_REQUIRE(f->struct_size == sizeof(sylph_row_filter), "sylph_pipeline_set_row_filter: filter of %u bytes, this library's has %zu", f->struct_size,
+                       sizeof(sylph_row_filter));
+            SY_REQUIRE(!comm, "sylph_pipeline_set_row_filter: a sharded pipeline takes no row filter");
+            SY_REQUIRE_STATE(!submitted.load(), "sylph_pipeline_set_row_filter: call it before the first submit");
+            static_assert(sizeof(row_stats_plan::Filter) == sizeof(sylph_row_filter), "the ABI's filter is the plan's");
+            std::unique_ptr<row_stats_plan::Filter> mine(new row_stats_plan::Filter());
+            memcpy(mine.get(), f, sizeof(*f));
+            row_filter = std::move(mine);
+        });
+    }
+    int rows_of_last(const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs, uint32_t* cov_width) override {
+        *rows = last_rows.n ? last_rows.rows : nullptr;
+        *n = last_rows.n;
+        *row_cov_off = last_rows.off;
+        *row_covs = last_rows.n ? last_rows.covs : nullptr;
+        if (cov_width) *cov_width = last_rows.width;
+        return SYLPH_OK;
+    }
 };
 
 // A pipeline over several replicas of one database (sylph_pipeline_create_multi: one per GPU of the node) is only a router:
@@ -415,6 +467,10 @@ struct Router final : sylph_pipeline {
     }
     int replica_of_last() override { std::lock_guard<std::mutex> lk(mu); return (int)last_replica; }
     int ascending_of_last() override { return children[(size_t)replica_of_last()]->ascending_of_last(); }
+    int set_row_filter(const sylph_row_filter* f) override { return for_each_ok(children, [&](Engine* c) { return c->set_row_filter(f); }); }
+    int rows_of_last(const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs, uint32_t* cov_width) override {
+        return children[(size_t)replica_of_last()]->rows_of_last(rows, n, row_cov_off, row_covs, cov_width);
+    }
 };
 
 void require_config(const sylph_pipeline_config* cfg) {
@@ -473,6 +529,11 @@ int sylph_pipeline_create_multi(sylph_db* const* dbs, uint32_t n_dbs, const sylp
 
 int sylph_pipeline_replica_of_last(sylph_pipeline* p) { return p ? p->replica_of_last() : -1; }
 int sylph_pipeline_ascending_of_last(sylph_pipeline* p) { return p ? p->ascending_of_last() : -1; }
+int sylph_pipeline_set_row_filter(sylph_pipeline* p, const sylph_row_filter* filter) { return p ? p->set_row_filter(filter) : null_argument(); }
+int sylph_pipeline_rows_of_last(sylph_pipeline* p, const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs,
+                                uint32_t* cov_width) {
+    return p && rows && n && row_cov_off && row_covs ? p->rows_of_last(rows, n, row_cov_off, row_covs, cov_width) : null_argument();
+}
 
 int sylph_pipeline_submit(sylph_pipeline* p, const sylph_read_batch* batches, uint32_t n_batches, int mem, int enc, uint64_t tag) {
     if (!p || (n_batches && !batches)) return null_argument();

@@ -51,6 +51,34 @@ static void fill_stats(const AniResult& r, SylphHostStats* out) {
     out->contain_count = r.contain_count; out->n_kmers = r.n_kmers;
 }
 
+// The statistics head in its two halves (csrc/row_stats_plan.h): the table behind the Poisson cut (out: 30 entries), the filter the
+// drivers hand to sylph_row_summaries, and sylph_host_stats from a row's summary — `covs` = the row's ascending values (at least
+// s->keep of them; the confidence interval resamples them), whoever counted the summary.  Fills out like sylph_host_stats.
+void sylph_host_row_cut_table(uint32_t* out) { std::copy(row_cut_table(), row_cut_table() + row_stats_plan::CUT_ENTRIES, out); }
+static ContainArgs args_of(double min_count_correct, double minimum_ani_or_neg, int pseudotax, int no_ci, int no_adj, int mean_coverage) {
+    ContainArgs a;
+    a.min_count_correct = min_count_correct;
+    if (minimum_ani_or_neg >= 0) a.minimum_ani = minimum_ani_or_neg;
+    a.pseudotax = pseudotax; a.no_ci = no_ci; a.no_adj = no_adj; a.mean_coverage = mean_coverage;
+    return a;
+}
+void sylph_host_row_filter(uint64_t k, double min_count_correct, double minimum_ani_or_neg, int pseudotax, int no_adj, sylph_row_filter* out) {
+    *out = row_filter_for(args_of(min_count_correct, minimum_ani_or_neg, pseudotax, 0, no_adj, 0), k);
+}
+int sylph_host_stats_from_summary(const sylph_row_summary* s, const uint32_t* covs, uint64_t n_genome_kmers, uint64_t k, double min_count_correct,
+                                  double minimum_ani_or_neg, int pseudotax, int no_ci, int no_adj, int mean_coverage, SylphHostStats* out) {
+    memset(out, 0, sizeof(*out));
+    const ContainArgs a = args_of(min_count_correct, minimum_ani_or_neg, pseudotax, no_ci, no_adj, mean_coverage);
+    row_stats_plan::RowSummary rs;
+    static_assert(sizeof(rs) == sizeof(*s), "the ABI's summary is the plan's");
+    memcpy(&rs, s, sizeof(rs));
+    StatsHead h = stats_head_from_summary(a, rs, n_genome_kmers, k, std::nullopt);
+    if (!h.result) return 0;
+    if (h.want_ci) bootstrap_host(covs, h.keep, h.n_total, (double)k, a, *h.result);
+    fill_stats(*h.result, out);
+    return 1;
+}
+
 // The batch form of sylph_host_stats, the way `profile` / `query` run it: genome i has the coverage values covs[cov_off[i] ..
 // cov_off[i + 1]) (any order) and n_genome_kmers[i] k-mers; the first halves on the host, the resampling of every interval in one
 // device call on ctx (route: 0 the host's loop, 1 the device with the host's loop for what it declines, 2 device only), the second

@@ -229,8 +229,41 @@ struct ReportTo {   // what every sample's report shares
     FILE* out;
     sylph_ctx* ctx;                                     // the command's own context: the genomes' confidence intervals are resampled on it
 };
+// The road of the first pass's statistics head.  Host: every row with a hit is walked on this thread (stats_head).  Device: the
+// pipeline summarises the rows on the device and hands over the candidates only (sylph_pipeline_set_row_filter; csrc/row_stats.hip),
+// the f64 half runs here on their summaries (stats_head_from_summary) — same output, bit for bit.  SYLPH_HIP_STATS_DEVICE = 0 | 1 |
+// only (only: a sample that cannot take the device's road is an Error).  The project's ship rule decides the default: on only where
+// whole `profile` and `query` commands beat the parent commit's binary by more than both spreads — profiles/row_stats.txt holds the
+// record: 2.0x and 2.4x over 64 sketches against 20,000 genomes, so unset means 1.
+enum class StatsRoute { Host, Device, DeviceOnly };
+constexpr StatsRoute STATS_ROUTE_DEFAULT = StatsRoute::Device;
+StatsRoute stats_route() {
+    const char* e = getenv("SYLPH_HIP_STATS_DEVICE");
+    if (!e || !*e) return STATS_ROUTE_DEFAULT;
+    if (!strcmp(e, "0")) return StatsRoute::Host;
+    if (!strcmp(e, "1")) return StatsRoute::Device;
+    if (!strcmp(e, "only")) return StatsRoute::DeviceOnly;
+    throw Error{1, std::string("SYLPH_HIP_STATS_DEVICE must be 0, 1 or only, not ") + e};
+}
+// the candidates of a sample (sylph_pipeline_rows_of_last)
+struct Candidates {
+    const sylph_row_summary* rows = nullptr;
+    uint32_t n = 0;
+    const uint64_t* off = nullptr;
+    const void* covs = nullptr;
+    uint32_t width = 0;
+};
+// SYLPH_HIP_FEED_TRACE: one line per sample — the road of its first statistics pass and what it walked.  The device's road brings
+// only the candidates to the host: the number of rows with hits stays on the device.
+void trace_stats_road(const std::string& sample, const char* road, size_t rows_with_hits, bool hits_known, size_t candidates) {
+    if (!FeedLaps::on()) return;
+    if (hits_known) fprintf(stderr, "[sylph_hip feed] stats %s: road %s, %zu rows with hits, %zu candidates\n", sample.c_str(), road, rows_with_hits, candidates);
+    else fprintf(stderr, "[sylph_hip feed] stats %s: road %s, %zu candidates\n", sample.c_str(), road, candidates);
+}
+
+// `cand` (optional): the first pass takes the device's road — cc / coff / covs are null then.
 void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const uint32_t* cc, const uint64_t* coff, const void* covs,
-            uint32_t cov_width, const uint64_t* tk, const uint32_t* tc, uint64_t tn, int tmem, sylph_db* rdb) {
+            uint32_t cov_width, const uint64_t* tk, const uint32_t* tc, uint64_t tn, int tmem, sylph_db* rdb, const Candidates* cand = nullptr) {
     const ContainCmdArgs& args = to.args;
     const std::vector<GenomeSketch>& genome_sketches = to.genome_sketches;
     FILE* const out = to.out;
@@ -276,13 +309,29 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         return res;
     };
     std::vector<AniResult> stats;
-    {
+    for (size_t g = 0; g < genome_sketches.size(); g++)
+        if (genome_sketches[g].c < S.c) throw Error{1, "c parameter for reads > c parameter for genome"};   // :616-623
+    if (cand) {
+        // the candidates' summaries came counted: the f64 half, then the intervals from the gathered values (candidates ascend by genome)
+        std::vector<StatsHead> heads(cand->n);
+        parallel_for(cand->n, args.threads, [&](size_t i) {
+            row_stats_plan::RowSummary rs;
+            memcpy(&rs, &cand->rows[i], sizeof(rs));
+            heads[i] = stats_head_from_summary(args, rs, genome_sketches[rs.row].n_kmers(), S.k, std::nullopt);
+            if (heads[i].result) heads[i].result->genome_index = rs.row;
+        });
+        std::vector<CiItem> ci;
+        for (size_t i = 0; i < heads.size(); i++)
+            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, cand->off[i], cand->off[i + 1], heads[i].keep, heads[i].n_total});
+        bootstrap_batch(to.ctx, ci_route, args, S.k, cand->covs, cand->width, ci, args.threads);
+        for (auto& h : heads) if (h.result) stats.push_back(*h.result);
+        trace_stats_road(first_file, "device", 0, false, cand->n);
+    } else {
         std::vector<size_t> with_hits;
-        for (size_t g = 0; g < genome_sketches.size(); g++) {
-            if (genome_sketches[g].c < S.c) throw Error{1, "c parameter for reads > c parameter for genome"};   // :616-623
+        for (size_t g = 0; g < genome_sketches.size(); g++)
             if (cc[g] != 0) with_hits.push_back(g);                  // :654
-        }
         for (auto& r : run_stats(with_hits, covs, cov_width, coff, nullptr)) if (r) stats.push_back(*r);
+        trace_stats_road(first_file, "host", with_hits.size(), true, with_hits.size());
     }
     std::optional<double> kmer_id_opt;                               // contain.rs:274-281
     if (args.seq_id) kmer_id_opt = std::pow(*args.seq_id / 100., (double)S.k);
@@ -435,7 +484,8 @@ struct ReplicaSet {
     ReplicaSet& operator=(const ReplicaSet&) = delete;
     void destroy_replicas() { for (size_t i = 1; i < dbs.size(); i++) sylph_db_destroy(dbs[i]); dbs.resize(std::min<size_t>(dbs.size(), 1)); }
     // the command's pipeline over the set: `n_workers` library threads, `depth` samples outstanding at the most
-    sylph_pipeline* create_pipeline(const ContainCmdArgs& args, uint32_t n_workers, uint32_t depth, sylph_pipeline_config& cfg) {
+    // (with SYLPH_HIP_STATS_DEVICE on, its profile thread also summarises the rows: `k` is the genomes')
+    sylph_pipeline* create_pipeline(const ContainCmdArgs& args, uint64_t k, uint32_t n_workers, uint32_t depth, sylph_pipeline_config& cfg) {
         memset(&cfg, 0, sizeof(cfg));
         cfg.struct_size = sizeof(cfg);
         cfg.n_workers = n_workers;
@@ -448,10 +498,22 @@ struct ReplicaSet {
         sylph_pipeline* pipe = nullptr;
         if (n_gpus > 1) hip_check(sylph_pipeline_create_multi(dbs.data(), (uint32_t)dbs.size(), &cfg, &pipe), "sylph_pipeline_create_multi");
         else hip_check(sylph_pipeline_create(dbs[0], &cfg, &pipe), "sylph_pipeline_create");
+        if (stats_route() != StatsRoute::Host) {
+            const sylph_row_filter f = row_filter_for(args, k);
+            const int rc = sylph_pipeline_set_row_filter(pipe, &f);
+            if (rc != SYLPH_OK) { sylph_pipeline_destroy(pipe); hip_check(rc, "sylph_pipeline_set_row_filter"); }
+        }
         return pipe;
     }
 };
 struct PipeGuard { sylph_pipeline* p; ~PipeGuard() { sylph_pipeline_destroy(p); } };
+// of the sample sylph_pipeline_next just returned, when the pipeline carries the row filter (create_pipeline); else nothing
+std::optional<Candidates> candidates_of_last(sylph_pipeline* pipe) {
+    if (stats_route() == StatsRoute::Host) return std::nullopt;
+    Candidates c;
+    hip_check(sylph_pipeline_rows_of_last(pipe, &c.rows, &c.n, &c.off, &c.covs, &c.width), "sylph_pipeline_rows_of_last");
+    return c;
+}
 
 // ---- raw read samples (contain.rs:239-291 sketches and profiles them chunk by chunk on the rayon pool).  Here: up to `-t`
 // sample threads, each with a GPU context of its own, read + index + pack + push their files into sessions, in input order;
@@ -520,7 +582,7 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
     };
     sylph_pipeline_config cfg;
     // 2 library workers (they only finish the sessions the sample threads pushed)
-    sylph_pipeline* pipe = replicas.create_pipeline(args, 2, (uint32_t)ahead_limit + 1, cfg);
+    sylph_pipeline* pipe = replicas.create_pipeline(args, genome_k, 2, (uint32_t)ahead_limit + 1, cfg);
     PipeGuard pipe_guard{pipe};
     std::vector<std::thread> pool;
     size_t submitted = 0;
@@ -568,8 +630,9 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
             if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + read_files[j][0] + ": " + (r.error ? r.error : "GPU stage failed")};
             SequencesSketch& S = *metas[j];
             if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+            const std::optional<Candidates> cand = candidates_of_last(pipe);
             report(to, S, read_files[j][0], r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
-                   dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))]);
+                   dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))], cand ? &*cand : nullptr);
         }
         finished(read_files[j]);
         metas[j].reset();
@@ -665,7 +728,7 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
         }
     };
     sylph_pipeline_config cfg;
-    sylph_pipeline* pipe = replicas.create_pipeline(args, 2, (uint32_t)ahead_limit + 1, cfg);
+    sylph_pipeline* pipe = replicas.create_pipeline(args, to.genome_sketches[0].k, 2, (uint32_t)ahead_limit + 1, cfg);
     PipeGuard pipe_guard{pipe};                                      // (finishes what is outstanding: the mappings below outlive it)
     std::vector<std::thread> pool;
     struct PoolJoin {   // on every way out: the prepare threads stop taking work and are joined
@@ -719,7 +782,11 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
         const std::string& file = read_sketch_files[j];
         if (turn[j] == Turn::Failed) std::rethrow_exception(errors[j]);
         if (turn[j] == Turn::Skip) sketch_c_too_large(file, views[j]->meta.c, genome_c);
-        else if (turn[j] == Turn::Host) { profile_sketch_on_host(args, file, db, to); submit_end = n_files; }
+        else if (turn[j] == Turn::Host) {
+            if (stats_route() == StatsRoute::DeviceOnly) throw Error{1, "SYLPH_HIP_STATS_DEVICE=only: " + file + " takes the host's road"};
+            profile_sketch_on_host(args, file, db, to);
+            submit_end = n_files;
+        }
         else {
             sylph_pipeline_result r;
             hip_check(sylph_pipeline_next(pipe, &r), "sylph_pipeline_next");
@@ -727,8 +794,9 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
             trace_sketch_route(file, "device", sylph_pipeline_ascending_of_last(pipe), views[j]->n_entries, r.n_table);
             SequencesSketch& S = views[j]->meta;
             if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+            const std::optional<Candidates> cand = candidates_of_last(pipe);
             report(to, S, file, r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
-                   replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))]);
+                   replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))], cand ? &*cand : nullptr);
         }
         finished({file});
         views[j].reset();
@@ -741,6 +809,7 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
 // contain.rs:115-351
 int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
     if (pseudotax_in) args.pseudotax = true;
+    (void)stats_route();                                             // (a bad SYLPH_HIP_STATS_DEVICE fails the command before any work)
     std::vector<std::string> genome_sketch_files, genome_files, read_sketch_files;
     std::vector<std::vector<std::string>> read_files;
     std::vector<std::string> all_files = args.files;

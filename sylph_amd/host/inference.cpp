@@ -3,6 +3,7 @@
 // and inference.rs:104-124,207-242 (mean, var, ratio_lambda).  Third-party arithmetic (statrs Poisson::cdf, fastrand) is
 // restated from its published definition and is "parity unpinned" (DESIGN.md §2).
 #include <algorithm>
+#include <array>
 #include <cmath>
 
 #include "sylph_host.hpp"
@@ -44,6 +45,7 @@ double poisson_cdf(double lambda, uint64_t x) { return gamma_q((double)x + 1.0, 
 // A histogram of coverage values -> what ratio_lambda and ani_from_lambda read off it (csrc/bootstrap_plan.h: the device counts the
 // resamples of the bootstrap into the same five numbers)
 using bootstrap_plan::Summary;
+using row_stats_plan::RowSummary;
 namespace {
 // hist[v] = how often v occurs; one bin beyond the largest value, so that hist[mode + 1] is there
 Summary summary_of(const std::vector<uint32_t>& hist) { return bootstrap_plan::summary_of_histogram(hist.data(), (uint32_t)hist.size()); }
@@ -158,34 +160,49 @@ void bootstrap_host(const uint32_t* kept, size_t keep, size_t n_total, double k,
     finish_ci(summaries.data(), summaries.size(), n_total, k, args, out);
 }
 
-// contain.rs:657-813 up to the decision about the confidence interval
-StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost) {
+// The table behind the Poisson cut (contain.rs:666-675; csrc/row_stats_plan.h), from this file's own poisson_cdf, once
+const uint32_t* row_cut_table() {
+    static const std::array<uint32_t, row_stats_plan::CUT_ENTRIES> table = [] {
+        std::array<uint32_t, row_stats_plan::CUT_ENTRIES> t{};
+        row_stats_plan::build_cut_table([](uint32_t m, uint32_t x) { return poisson_cdf((double)m, x) < CUTOFF_PVALUE; }, t.data());
+        return t;
+    }();
+    return table.data();
+}
+static_assert(row_stats_plan::SAMPLE_SIZE_CUTOFF == SAMPLE_SIZE_CUTOFF && (double)row_stats_plan::MEDIAN_LAMBDA_MAX == MEDIAN_ANI_THRESHOLD,
+              "the plan's reject follows these constants");
+
+// what the device needs to drop the rows that cannot pass the ANI cut of `args` (csrc/row_stats_plan.h surely_rejected)
+sylph_row_filter row_filter_for(const ContainArgs& args, uint64_t k) {
+    sylph_row_filter f{};
+    f.struct_size = sizeof(f);
+    f.k = (uint32_t)k;
+    const double min_ani = args.minimum_ani ? *args.minimum_ani / 100. : (args.pseudotax ? MIN_ANI_P_DEF : MIN_ANI_DEF);
+    f.reject_below = min_ani > 0. ? std::pow(min_ani, (double)k) * (1. - std::ldexp(1., -30)) : 0.;
+    f.min_count_correct = args.min_count_correct;
+    f.no_adj = args.no_adj ? 1 : 0;
+    std::copy(row_cut_table(), row_cut_table() + row_stats_plan::CUT_ENTRIES, f.cut);
+    return f;
+}
+
+// contain.rs:657-813 up to the decision about the confidence interval, from the integers a sorted row comes down to (:657-690;
+// csrc/row_stats_plan.h RowSummary, counted here by stats_head or on the device by csrc/row_stats.hip): the f64 half
+StatsHead stats_head_from_summary(const ContainArgs& args, const RowSummary& s, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost) {
     StatsHead h;
-    if (covs.empty()) return h;                                              // :654
-    const size_t contain_count = covs.size();
+    if (s.contain_count == 0) return h;                                      // :654
+    const size_t contain_count = s.contain_count;
     AniResult r;
     r.naive_ani = std::pow((double)contain_count / (double)n_genome_kmers, 1. / (double)k);   // :657-660
-    if (!std::is_sorted(covs.begin(), covs.end())) std::sort(covs.begin(), covs.end());   // :661 (already sorted when they come from the GPU)
-    const double median_cov = (double)covs[covs.size() / 2];                 // :663
-    double max_cov = 1.7976931348623157e308;                                 // f64::MAX
-    if (median_cov < 30.) {                                                  // :666-675
-        for (size_t i = covs.size() / 2; i < covs.size(); i++) {
-            if (poisson_cdf(median_cov, covs[i]) < CUTOFF_PVALUE) max_cov = (double)covs[i];
-            else break;
-        }
-    }
-    // full_covs (:679-684) = n_genome_kmers - contain_count zeros, then the values up to max_cov: a prefix of the sorted values
-    size_t keep = 0;
-    while (keep < covs.size() && (double)covs[keep] <= max_cov) keep++;
+    const double median_cov = (double)s.median;                              // :663
+    // full_covs (:679-684) = n_genome_kmers - contain_count zeros, then the values the Poisson cut (:666-675) keeps: a prefix of the sorted values
+    const size_t keep = s.keep;
     const size_t n_total = n_genome_kmers - contain_count + keep;
-    uint32_t sum = 0;
-    for (size_t i = 0; i < keep; i++) sum += covs[i];                        // iter().sum::<u32>()
-    const double geq1_mean_cov = (double)sum / (double)covs.size();          // :690
+    const double geq1_mean_cov = (double)s.sum / (double)contain_count;      // :690 (iter().sum::<u32>())
     Summary whole{0, 0, 0, 0, 0};                                            // of full_covs; read only where a lambda is estimated
     std::optional<double> test_lambda;
     if (median_cov > MEDIAN_ANI_THRESHOLD) r.lambda_status = AdjustStatus::High;   // :692-694
     else {
-        whole = summary_of_values(covs.data(), keep);
+        whole = Summary{s.keep, s.n_distinct, s.mode, s.mode_count, s.next_count};
         test_lambda = lambda_from_summary(whole, args.min_count_correct);    // :695-713 (default estimator)
         r.lambda_status = test_lambda ? AdjustStatus::Lambda : AdjustStatus::Low;
         if (test_lambda) r.lambda = *test_lambda;
@@ -214,6 +231,13 @@ StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_
     r.kmers_lost = kmers_lost;
     h.result = r;
     return h;
+}
+
+// the same from the row: summarise it here (:661-690, the integer half), then the f64 half above
+StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost) {
+    if (covs.empty()) return StatsHead{};                                    // :654
+    if (!std::is_sorted(covs.begin(), covs.end())) std::sort(covs.begin(), covs.end());   // :661 (already sorted when they come from the GPU)
+    return stats_head_from_summary(args, row_stats_plan::summarise_row(covs.data(), (uint32_t)covs.size(), row_cut_table()), n_genome_kmers, k, kmers_lost);
 }
 
 // contain.rs:657-813

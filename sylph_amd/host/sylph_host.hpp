@@ -19,6 +19,7 @@
 
 #include "../../include/sylph_hip.h"
 #include "../csrc/bootstrap_plan.h"
+#include "../csrc/row_stats_plan.h"
 
 namespace sylph_host {
 
@@ -345,6 +346,15 @@ struct StatsHead {
     size_t rejected_contain_count = 0;
 };
 StatsHead stats_head(const ContainArgs& args, std::vector<uint32_t>& covs, size_t n_genome_kmers, uint64_t k, std::optional<size_t> kmers_lost);
+// stats_head in two halves (csrc/row_stats_plan.h): the integers a sorted row comes down to — summarised by stats_head itself or, for
+// every row of a result block at once, by sylph_row_summaries on the device — and stats_head_from_summary, the f64 half: one body
+// whichever side counted.  row_cut_table: cut[0..30) behind the Poisson cut, built once from poisson_cdf.  row_filter_for: the filter
+// that lets the device drop the rows which cannot pass the ANI cut of `args`.
+namespace row_stats_plan = ::sylph::row_stats_plan;
+StatsHead stats_head_from_summary(const ContainArgs& args, const row_stats_plan::RowSummary& s, size_t n_genome_kmers, uint64_t k,
+                                  std::optional<size_t> kmers_lost);
+const uint32_t* row_cut_table();
+sylph_row_filter row_filter_for(const ContainArgs& args, uint64_t k);
 std::optional<double> lambda_from_summary(const bootstrap_plan::Summary& s, double min_count_correct);                 // inference.rs:207
 std::optional<double> ani_from_counts(std::optional<double> lambda, double k, size_t contain_count, size_t n_total);   // contain.rs:817
 void finish_ci(const bootstrap_plan::Summary* summaries, size_t iters, size_t n_total, double k, const ContainArgs& args, AniResult& out);
