@@ -1,10 +1,10 @@
 // cmd_contain.cpp — the `query` / `profile` command (contain.rs:115-351): the database made resident on the device, raw samples
 // sketched and probed through the library's pipeline, the statistics on the containment results, the reference's TSV rows.
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
 
 #include "host_internal.hpp"
+#include "ordered_ahead.hpp"
 
 namespace sylph_host {
 
@@ -220,9 +220,8 @@ void log_reassignment_edges(const std::vector<GenomeSketch>& genome_sketches, co
     info_block(lines);
 }
 
-// ---- one sample's results -> statistics -> (profile: reassignment pass) -> TSV rows.  `cc / coff / covs` are the first-pass
-// views (coverage values cov_width bytes each); the sample table is given where it lies (tk / tc / tn in tmem) for the
-// reassignment probe; S carries the metadata, and the counts on the host when -u needs them.
+// ---- one sample's results -> statistics -> (profile: reassignment pass) -> TSV rows.  The first pass's rows come as FirstPass,
+// the sample's table where it lies as SampleTable; S carries the metadata, and the counts on the host when -u needs them.
 struct ReportTo {   // what every sample's report shares
     const ContainCmdArgs& args;
     const std::vector<GenomeSketch>& genome_sketches;   // the database, in the order of its device-side index
@@ -261,76 +260,100 @@ void trace_stats_road(const std::string& sample, const char* road, size_t rows_w
     else fprintf(stderr, "[sylph_hip feed] stats %s: road %s, %zu candidates\n", sample.c_str(), road, candidates);
 }
 
-// `cand` (optional): the first pass takes the device's road — cc / coff / covs are null then.
-void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const uint32_t* cc, const uint64_t* coff, const void* covs,
-            uint32_t cov_width, const uint64_t* tk, const uint32_t* tc, uint64_t tn, int tmem, sylph_db* rdb, const Candidates* cand = nullptr) {
+// The first pass's rows: the whole view of the probe (`cc / coff / covs`, values `width` bytes each), or — `cand` set, the rest
+// null — the device's road: the candidates alone, summarised there.
+struct FirstPass {
+    const uint32_t* cc = nullptr;
+    const uint64_t* coff = nullptr;
+    const void* covs = nullptr;
+    uint32_t width = 0;
+    const Candidates* cand = nullptr;
+};
+// The sample's table where it lies (tmem: SYLPH_MEM_*), for the reassignment probe
+struct SampleTable {
+    const uint64_t* tk;
+    const uint32_t* tc;
+    uint64_t tn;
+    int tmem;
+};
+// One row of a statistics pass: its genome, its [lo, hi) in the pass's coverage values, and the integers it comes down to
+struct StatsRow {
+    size_t genome;
+    uint64_t lo, hi;
+    row_stats_plan::RowSummary summary;
+};
+
+void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const FirstPass& first, const SampleTable& table, sylph_db* rdb) {
     const ContainCmdArgs& args = to.args;
     const std::vector<GenomeSketch>& genome_sketches = to.genome_sketches;
     FILE* const out = to.out;
     if (genome_sketches[0].k != S.k) throw Error{1, "k parameter for reads != k parameter for genome"};   // contain.rs:608-615
     const std::string seq_name = S.sample_name ? *S.sample_name : S.file_name;   // :775-781
-    auto cov_vector = [&](const void* base, uint32_t width, uint64_t lo, uint64_t hi) {
-        std::vector<uint32_t> cv(hi - lo);
-        if (width == 4) memcpy(cv.data(), (const uint32_t*)base + lo, (hi - lo) * 4);
-        else if (width == 2) for (uint64_t i = lo; i < hi; i++) cv[i - lo] = ((const uint16_t*)base)[i];
-        else for (uint64_t i = lo; i < hi; i++) cv[i - lo] = ((const uint8_t*)base)[i];
-        return cv;
+    // a row of the host's: summarised here, as stats_head does (contain.rs:654, :661)
+    auto host_row = [&](size_t g, const void* base, uint32_t width, const uint64_t* off) {
+        StatsRow r{g, off[g], off[g + 1], {}};
+        std::vector<uint32_t> cv(r.hi - r.lo);
+        if (width == 4) memcpy(cv.data(), (const uint32_t*)base + r.lo, (r.hi - r.lo) * 4);
+        else if (width == 2) for (uint64_t i = r.lo; i < r.hi; i++) cv[i - r.lo] = ((const uint16_t*)base)[i];
+        else for (uint64_t i = r.lo; i < r.hi; i++) cv[i - r.lo] = ((const uint8_t*)base)[i];
+        if (cv.empty()) return r;
+        if (!std::is_sorted(cv.begin(), cv.end())) std::sort(cv.begin(), cv.end());
+        r.summary = row_stats_plan::summarise_row(cv.data(), (uint32_t)cv.size(), row_cut_table());
+        return r;
     };
     // The statistics of different genomes are independent (contain.rs:284 runs them on the rayon pool): -t threads, results in the
-    // order of `gs` so that the output does not depend on the interleaving.  Between the two halves of a genome's statistics lies its
-    // confidence interval: the genomes that want one are resampled together (bootstrap_batch: one device call, or the host's loop).
+    // order of the rows so that the output does not depend on the interleaving.  Between the two halves of a genome's statistics lies
+    // its confidence interval: the genomes that want one are resampled together (bootstrap_batch: one device call, or the host's loop).
+    // `row(i)`, i < n: the pass's rows, ascending by genome and with it in the coverage values `base`; `lost`: the second pass.
     const BootstrapRoute ci_route = args.no_ci ? BootstrapRoute::Host : bootstrap_route();
     const bool log_reassign = args.pseudotax && args.log_reassignments;   // (`query` ignores the flag, as the reference does)
-    auto run_stats = [&](const std::vector<size_t>& gs, const void* base, uint32_t width, const uint64_t* off, const uint32_t* lost) {
-        std::vector<StatsHead> heads(gs.size());
-        parallel_for(gs.size(), args.threads, [&](size_t i) {
-            const size_t g = gs[i];
-            std::vector<uint32_t> cv = cov_vector(base, width, off[g], off[g + 1]);
-            heads[i] = stats_head(args, cv, genome_sketches[g].n_kmers(), S.k, lost ? std::optional<size_t>((size_t)lost[g]) : std::nullopt);
+    auto run_stats = [&](size_t n, const void* base, uint32_t width, const uint32_t* lost, auto&& row) {
+        std::vector<StatsHead> heads(n);
+        std::vector<StatsRow> rows(n);
+        parallel_for(n, args.threads, [&](size_t i) {
+            rows[i] = row(i);
+            const size_t g = rows[i].genome;
+            heads[i] = stats_head_from_summary(args, rows[i].summary, genome_sketches[g].n_kmers(), S.k, lost ? std::optional<size_t>((size_t)lost[g]) : std::nullopt);
             if (heads[i].result) heads[i].result->genome_index = g;
         });
         if (lost && log_reassign) {                                  // contain.rs:749-761: passed before the reassignment, not after it
             const double min_ani = args.minimum_ani ? *args.minimum_ani / 100. : MIN_ANI_P_DEF;
-            for (size_t i = 0; i < gs.size(); i++) {
+            for (size_t i = 0; i < n; i++) {
                 if (!heads[i].rejected) continue;
-                const GenomeSketch& g = genome_sketches[gs[i]];
+                const GenomeSketch& g = genome_sketches[rows[i].genome];
                 char num[160];
                 snprintf(num, sizeof(num), " has ANI = %.2f < %.2f after reassigning %zu k-mers (%zu contained k-mers after reassign)",
-                         heads[i].rejected_ani * 100., min_ani * 100., (size_t)lost[gs[i]], heads[i].rejected_contain_count);
+                         heads[i].rejected_ani * 100., min_ani * 100., (size_t)lost[rows[i].genome], heads[i].rejected_contain_count);
                 info("Genome/contig " + g.file_name + "/" + g.first_contig_name + num);
             }
         }
-        std::vector<CiItem> ci;                                      // (gs ascends, and with it the rows of the coverage values)
-        for (size_t i = 0; i < gs.size(); i++)
-            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, off[gs[i]], off[gs[i] + 1], heads[i].keep, heads[i].n_total});
+        std::vector<CiItem> ci;
+        for (size_t i = 0; i < n; i++)
+            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, rows[i].lo, rows[i].hi, heads[i].keep, heads[i].n_total});
         bootstrap_batch(to.ctx, ci_route, args, S.k, base, width, ci, args.threads);
-        std::vector<std::optional<AniResult>> res(gs.size());
-        for (size_t i = 0; i < gs.size(); i++) res[i] = std::move(heads[i].result);
+        std::vector<std::optional<AniResult>> res(n);
+        for (size_t i = 0; i < n; i++) res[i] = std::move(heads[i].result);
         return res;
     };
     std::vector<AniResult> stats;
     for (size_t g = 0; g < genome_sketches.size(); g++)
         if (genome_sketches[g].c < S.c) throw Error{1, "c parameter for reads > c parameter for genome"};   // :616-623
-    if (cand) {
-        // the candidates' summaries came counted: the f64 half, then the intervals from the gathered values (candidates ascend by genome)
-        std::vector<StatsHead> heads(cand->n);
-        parallel_for(cand->n, args.threads, [&](size_t i) {
-            row_stats_plan::RowSummary rs;
-            memcpy(&rs, &cand->rows[i], sizeof(rs));
-            heads[i] = stats_head_from_summary(args, rs, genome_sketches[rs.row].n_kmers(), S.k, std::nullopt);
-            if (heads[i].result) heads[i].result->genome_index = rs.row;
-        });
-        std::vector<CiItem> ci;
-        for (size_t i = 0; i < heads.size(); i++)
-            if (heads[i].result && heads[i].want_ci) ci.push_back({&*heads[i].result, cand->off[i], cand->off[i + 1], heads[i].keep, heads[i].n_total});
-        bootstrap_batch(to.ctx, ci_route, args, S.k, cand->covs, cand->width, ci, args.threads);
-        for (auto& h : heads) if (h.result) stats.push_back(*h.result);
+    if (const Candidates* cand = first.cand) {
+        // the candidates' summaries came counted on the device
+        for (auto& r : run_stats(cand->n, cand->covs, cand->width, nullptr, [&](size_t i) {
+                 StatsRow r{0, cand->off[i], cand->off[i + 1], {}};
+                 memcpy(&r.summary, &cand->rows[i], sizeof(r.summary));
+                 r.genome = r.summary.row;
+                 return r;
+             }))
+            if (r) stats.push_back(*r);
         trace_stats_road(first_file, "device", 0, false, cand->n);
     } else {
         std::vector<size_t> with_hits;
         for (size_t g = 0; g < genome_sketches.size(); g++)
-            if (cc[g] != 0) with_hits.push_back(g);                  // :654
-        for (auto& r : run_stats(with_hits, covs, cov_width, coff, nullptr)) if (r) stats.push_back(*r);
+            if (first.cc[g] != 0) with_hits.push_back(g);            // :654
+        for (auto& r : run_stats(with_hits.size(), first.covs, first.width, nullptr, [&](size_t i) { return host_row(with_hits[i], first.covs, first.width, first.coff); }))
+            if (r) stats.push_back(*r);
         trace_stats_road(first_file, "host", with_hits.size(), true, with_hits.size());
     }
     std::optional<double> kmer_id_opt;                               // contain.rs:274-281
@@ -348,12 +371,11 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         const uint32_t *cc2 = nullptr, *covs2 = nullptr, *lost2 = nullptr;
         const uint64_t* coff2 = nullptr;
         uint64_t ncov2 = 0;
-        hip_check(sylph_db_reassign_view(rdb, tk, tc, tn, tmem, pg.data(), pa.data(), (uint32_t)pg.size(), &cc2, &coff2, &covs2, &ncov2, &lost2),
+        hip_check(sylph_db_reassign_view(rdb, table.tk, table.tc, table.tn, table.tmem, pg.data(), pa.data(), (uint32_t)pg.size(), &cc2, &coff2, &covs2, &ncov2, &lost2),
                   "sylph_db_reassign_view");
-        std::vector<AniResult> stats2;
-        std::vector<size_t> passing(stats.size());               // (in genome order still: ascending)
-        for (size_t i = 0; i < stats.size(); i++) passing[i] = stats[i].genome_index;
-        const std::vector<std::optional<AniResult>> res2 = run_stats(passing, covs2, 4, coff2, lost2);
+        std::vector<AniResult> stats2;                           // (the passing genomes are in genome order still: ascending)
+        const std::vector<std::optional<AniResult>> res2 =
+            run_stats(stats.size(), covs2, 4, lost2, [&](size_t i) { return host_row(stats[i].genome_index, covs2, 4, coff2); });
         for (size_t i = 0; i < stats.size(); i++) {
             const auto& r = res2[i];
             if (!r) continue;
@@ -483,13 +505,13 @@ struct ReplicaSet {
     ReplicaSet(const ReplicaSet&) = delete;
     ReplicaSet& operator=(const ReplicaSet&) = delete;
     void destroy_replicas() { for (size_t i = 1; i < dbs.size(); i++) sylph_db_destroy(dbs[i]); dbs.resize(std::min<size_t>(dbs.size(), 1)); }
-    // the command's pipeline over the set: `n_workers` library threads, `depth` samples outstanding at the most
-    // (with SYLPH_HIP_STATS_DEVICE on, its profile thread also summarises the rows: `k` is the genomes')
-    sylph_pipeline* create_pipeline(const ContainCmdArgs& args, uint64_t k, uint32_t n_workers, uint32_t depth, sylph_pipeline_config& cfg) {
+    // the command's pipeline over the set: `n_workers` library threads, as deep as a prepare pool that runs `ahead_limit` samples
+    // ahead needs (with SYLPH_HIP_STATS_DEVICE on, its profile thread also summarises the rows: `k` is the genomes')
+    sylph_pipeline* create_pipeline(const ContainCmdArgs& args, uint64_t k, uint32_t n_workers, size_t ahead_limit, sylph_pipeline_config& cfg) {
         memset(&cfg, 0, sizeof(cfg));
         cfg.struct_size = sizeof(cfg);
         cfg.n_workers = n_workers;
-        cfg.depth = depth;
+        cfg.depth = (uint32_t)ordered_ahead::pipeline_depth(ahead_limit);
         cfg.max_batch = 4;
         cfg.c = (uint32_t)args.c; cfg.k = (uint32_t)args.k;
         cfg.reads_mode = SYLPH_READS_PAIRED; cfg.seed_mode = SYLPH_SEED_AVX2_COMPAT;
@@ -506,7 +528,6 @@ struct ReplicaSet {
         return pipe;
     }
 };
-struct PipeGuard { sylph_pipeline* p; ~PipeGuard() { sylph_pipeline_destroy(p); } };
 // of the sample sylph_pipeline_next just returned, when the pipeline carries the row filter (create_pipeline); else nothing
 std::optional<Candidates> candidates_of_last(sylph_pipeline* pipe) {
     if (stats_route() == StatsRoute::Host) return std::nullopt;
@@ -514,6 +535,39 @@ std::optional<Candidates> candidates_of_last(sylph_pipeline* pipe) {
     hip_check(sylph_pipeline_rows_of_last(pipe, &c.rows, &c.n, &c.off, &c.covs, &c.width), "sylph_pipeline_rows_of_last");
     return c;
 }
+// The pipeline of a sample road (2 library workers: they finish the sessions, or unpack the entries, that the road hands over) and
+// what both roads do with a result.  The replica set outlives it.
+struct SamplePipe {
+    ReplicaSet& replicas;
+    sylph_pipeline_config cfg;
+    sylph_pipeline* const p;
+    SamplePipe(ReplicaSet& r, const ContainCmdArgs& args, uint64_t genome_k, size_t ahead_limit) : replicas(r), p(r.create_pipeline(args, genome_k, 2, ahead_limit, cfg)) {}
+    ~SamplePipe() { sylph_pipeline_destroy(p); }
+    SamplePipe(const SamplePipe&) = delete;
+    SamplePipe& operator=(const SamplePipe&) = delete;
+    size_t outstanding() const { return sylph_pipeline_outstanding(p); }
+    // every result still outstanding is taken: nothing reads what was submitted after that
+    void drain() { sylph_pipeline_result r; while (sylph_pipeline_outstanding(p) && sylph_pipeline_next(p, &r) == SYLPH_OK) {} }
+    // the next sample's result, in submission order
+    sylph_pipeline_result next(const std::string& file) {
+        sylph_pipeline_result r;
+        hip_check(sylph_pipeline_next(p, &r), "sylph_pipeline_next");
+        if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + file + ": " + (r.error ? r.error : "GPU stage failed")};
+        return r;
+    }
+    // ... -> the counts -u walks -> the candidates -> the sample's rows, reassigned on the replica that holds its table
+    void report_last(const ReportTo& to, const sylph_pipeline_result& r, SequencesSketch& S, const std::string& file) {
+        if (to.args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+        const std::optional<Candidates> cand = candidates_of_last(p);
+        report(to, S, file, FirstPass{r.contain_count, r.cov_off, r.covs, r.cov_width, cand ? &*cand : nullptr},
+               SampleTable{r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE}, replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(p))]);
+    }
+    // the ordered hand-over of `pool`'s jobs through this pipeline (ordered_ahead.hpp: order, failure rule, clean-up)
+    template <class P, class Submit, class Consume>
+    void run(ordered_ahead::Pool<P>& pool, Submit&& submit, Consume&& consume) {
+        ordered_ahead::run(pool, cfg.depth, [&] { return outstanding(); }, submit, consume, [&] { drain(); });
+    }
+};
 
 // ---- raw read samples (contain.rs:239-291 sketches and profiles them chunk by chunk on the rayon pool).  Here: up to `-t`
 // sample threads, each with a GPU context of its own, read + index + pack + push their files into sessions, in input order;
@@ -522,123 +576,58 @@ std::optional<Candidates> candidates_of_last(sylph_pipeline* pipe) {
 // sample j and the statistics of sample j - 1.
 void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vector<std::vector<std::string>>& read_files, sylph_db* db,
                          const ReportTo& to) {
+    using ordered_ahead::Turn;
     const size_t n_raw = read_files.size();
     const uint64_t genome_c = to.genome_sketches[0].c, genome_k = to.genome_sketches[0].k;
-    struct Prepared { std::optional<SequencesSketch> meta; sylph_sketch* session = nullptr; std::exception_ptr error; };
-    std::vector<std::promise<Prepared>> promises(n_raw);
-    std::vector<std::future<Prepared>> futures;
-    for (auto& p : promises) futures.push_back(p.get_future());
+    struct Prepared { std::optional<SequencesSketch> meta; sylph_sketch* session = nullptr; };   // no meta: refused or skipped
     ReplicaSet replicas(e, args, db, n_raw);                         // sample threads are dealt to the replicas' devices in turn
-    const int n_gpus = replicas.n_gpus;
-    std::vector<sylph_db*>& dbs = replicas.dbs;
-    const std::vector<int>& replica_device = replicas.device;
-    std::atomic<size_t> worker_no{0};
-    const size_t n_workers = sample_workers(args.threads, (size_t)n_gpus, n_raw);
-    const size_t ahead_limit = n_workers + 2;                        // sessions that may wait, sketched, for the profile stage
+    const size_t n_workers = sample_workers(args.threads, (size_t)replicas.n_gpus, n_raw);
     std::vector<SampleFiles> job_files;
     for (const auto& r : read_files) job_files.push_back({r[0], r.size() > 1 ? std::optional<std::string>(r[1]) : std::nullopt});
     FeedShared feed(std::move(job_files), n_workers);
-    std::atomic<size_t> next_job{0}, released{0};
-    std::atomic<bool> cancel{false};
-    std::mutex gate_mu;
-    std::condition_variable gate_cv;
     // contain.rs:591: raw pairs are sketched with the default filter (DEFAULT_FPR) — unless the exact set is asked for (not in the reference)
     const double raw_pair_fpr = exact_dedup_accepted(args.exact_dedup) ? 0. : DEFAULT_FPR;
     auto prepare = [&](Engine& eng, size_t j) {
         Prepared pr;
-        try {
-            const auto& files = read_files[j];
-            if (genome_c < args.c) {
-                fprintf(stderr, "ERROR [sylph_hip] %s error: value of -c for contain = %llu -- greater than the smallest value of -c for a genome sketch = %llu. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.c, (unsigned long long)genome_c);
-            } else if (genome_k != args.k) {
-                fprintf(stderr, "ERROR [sylph_hip] %s -k %llu is not equal to -k %llu found in sketches. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.k, (unsigned long long)genome_k);
-            } else {
+        const auto& files = read_files[j];
+        if (genome_c < args.c) {
+            fprintf(stderr, "ERROR [sylph_hip] %s error: value of -c for contain = %llu -- greater than the smallest value of -c for a genome sketch = %llu. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.c, (unsigned long long)genome_c);
+        } else if (genome_k != args.k) {
+            fprintf(stderr, "ERROR [sylph_hip] %s -k %llu is not equal to -k %llu found in sketches. Continuing without sketching.\n", files[0].c_str(), (unsigned long long)args.k, (unsigned long long)genome_k);
+        } else {
+            try {
                 SampleRoute route(eng, feed, j, false);
                 SampleParams p;   // contain.rs:591: no sample name, duplicates always removed
                 p.c = args.c; p.k = args.k; p.dedup_fpr = raw_pair_fpr;
                 pr.meta = sketch_sample(eng, feed.ahead.files(j), p, route, &pr.session);
-            }
-        } catch (...) { pr.error = std::current_exception(); }
-        promises[j].set_value(std::move(pr));
+            } catch (...) { sylph_sketch_destroy(pr.session); throw; }
+        }
+        return pr;
     };
-    auto worker = [&] {
-        // every sample thread brings its own context: the database's context (the caller's engine) stays free for the
-        // profile stage and the reassignment probes
-        std::unique_ptr<Engine> own;
-        Engine* eng = nullptr;
-        try { own.reset(new Engine(replica_device[worker_no++ % replica_device.size()])); eng = own.get(); }
-        catch (...) { eng = nullptr; }
-        for (;;) {
-            const size_t j = next_job++;
-            if (j >= n_raw) return;
-            {   // do not run further ahead of the consumer than ahead_limit samples (their sessions hold HBM)
-                std::unique_lock<std::mutex> lk(gate_mu);
-                gate_cv.wait(lk, [&] { return cancel.load() || j < released.load() + ahead_limit; });
-            }
-            if (cancel) { promises[j].set_value(Prepared{}); continue; }
-            if (!eng) { Prepared pr; pr.error = std::make_exception_ptr(Error{1, "could not create a GPU context for a sample thread"}); promises[j].set_value(std::move(pr)); continue; }
-            prepare(*eng, j);
-        }
+    // every sample thread brings its own context, made and destroyed on that thread: the database's context (the caller's engine)
+    // stays free for the profile stage and the reassignment probes
+    std::atomic<size_t> worker_no{0};
+    auto sample_thread = [&]() -> ordered_ahead::Pool<Prepared>::Prepare {
+        std::shared_ptr<Engine> own;
+        try { own.reset(new Engine(replicas.device[worker_no++ % replicas.device.size()])); }
+        catch (...) { throw Error{1, "could not create a GPU context for a sample thread"}; }
+        return [own, &prepare](size_t j) { return prepare(*own, j); };
     };
-    sylph_pipeline_config cfg;
-    // 2 library workers (they only finish the sessions the sample threads pushed)
-    sylph_pipeline* pipe = replicas.create_pipeline(args, genome_k, 2, (uint32_t)ahead_limit + 1, cfg);
-    PipeGuard pipe_guard{pipe};
-    std::vector<std::thread> pool;
-    size_t submitted = 0;
-    struct Unconsumed {   // (declared before PoolJoin: runs after the sample threads are joined) sessions nobody took over
-        std::vector<std::future<Prepared>>& futures; size_t& submitted;
-        ~Unconsumed() {
-            for (size_t j = submitted; j < futures.size(); j++) {
-                if (!futures[j].valid() || futures[j].wait_for(std::chrono::seconds(0)) != std::future_status::ready) continue;
-                try { Prepared pr = futures[j].get(); if (pr.session) sylph_sketch_destroy(pr.session); } catch (...) {}
-            }
-        }
-    } unconsumed{futures, submitted};
-    struct PoolJoin {   // on every way out: the sample threads stop taking work and are joined
-        std::vector<std::thread>& pool; std::atomic<bool>& cancel; std::mutex& mu; std::condition_variable& cv;
-        ~PoolJoin() {
-            { std::lock_guard<std::mutex> lk(mu); cancel = true; }
-            cv.notify_all();
-            for (auto& t : pool) if (t.joinable()) t.join();
-        }
-    } pool_join{pool, cancel, gate_mu, gate_cv};
-    for (size_t w = 0; w < n_workers; w++) pool.emplace_back(worker);
-    std::vector<std::optional<SequencesSketch>> metas(n_raw);
-    std::vector<char> submitted_ok(n_raw, 0);
-    size_t done = 0;
-    auto release_one = [&] { { std::lock_guard<std::mutex> lk(gate_mu); released++; } gate_cv.notify_all(); };
-    while (done < n_raw) {
-        // hand over every prepared sample that is ready, in input order (wait for one only when nothing is outstanding)
-        while (submitted < n_raw && sylph_pipeline_outstanding(pipe) < cfg.depth) {
-            const bool must_wait = sylph_pipeline_outstanding(pipe) == 0 && submitted == done;
-            if (!must_wait && futures[submitted].wait_for(std::chrono::seconds(0)) != std::future_status::ready) break;
-            Prepared pr = futures[submitted].get();
-            if (pr.error) { if (pr.session) sylph_sketch_destroy(pr.session); submitted++; std::rethrow_exception(pr.error); }
-            metas[submitted] = std::move(pr.meta);
-            if (metas[submitted] && pr.session) {
-                hip_check(sylph_pipeline_submit_session(pipe, pr.session, submitted), "sylph_pipeline_submit_session");
-                submitted_ok[submitted] = 1;
-            } else if (pr.session) sylph_sketch_destroy(pr.session);
-            submitted++;
-        }
-        const size_t j = done;
-        if (j >= submitted) continue;        // (the wait above guarantees progress)
-        if (submitted_ok[j]) {
-            sylph_pipeline_result r;
-            hip_check(sylph_pipeline_next(pipe, &r), "sylph_pipeline_next");
-            if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + read_files[j][0] + ": " + (r.error ? r.error : "GPU stage failed")};
-            SequencesSketch& S = *metas[j];
-            if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
-            const std::optional<Candidates> cand = candidates_of_last(pipe);
-            report(to, S, read_files[j][0], r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
-                   dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))], cand ? &*cand : nullptr);
-        }
-        finished(read_files[j]);
-        metas[j].reset();
-        done++;
-        release_one();
-    }
+    SamplePipe pipe(replicas, args, genome_k, ordered_ahead::ahead_limit(n_workers));
+    std::vector<std::optional<SequencesSketch>> metas(n_raw);      // of the samples handed over, until their rows are out
+    ordered_ahead::Pool<Prepared> pool(n_raw, n_workers, sample_thread, [](Prepared& pr) { sylph_sketch_destroy(pr.session); });
+    pipe.run(pool,
+             [&](size_t j, Prepared&& pr) {
+                 if (!pr.meta || !pr.session) { sylph_sketch_destroy(pr.session); return Turn::Skip; }
+                 hip_check(sylph_pipeline_submit_session(pipe.p, pr.session, j), "sylph_pipeline_submit_session");
+                 metas[j] = std::move(pr.meta);
+                 return Turn::Pipeline;
+             },
+             [&](size_t j, Turn turn) {
+                 if (turn == Turn::Pipeline) pipe.report_last(to, pipe.next(read_files[j][0]), *metas[j], read_files[j][0]);
+                 finished(read_files[j]);
+                 metas[j].reset();
+             });
 }
 
 // ---- samples given as sketches (*.sylsp; get_seq_sketch, contain.rs:544-599) ----
@@ -669,7 +658,7 @@ void profile_sketch_on_host(const ContainCmdArgs& args, const std::string& file,
     const uint32_t* cc = nullptr; const uint64_t* coff = nullptr; const uint32_t* covs = nullptr; uint64_t ncov = 0;
     hip_check(sylph_db_contain_view(db, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST,
                                     args.min_number_kmers, &cc, &coff, &covs, &ncov), "sylph_db_contain_view");
-    report(to, S, file, cc, coff, covs, 4, S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST, db);
+    report(to, S, file, FirstPass{cc, coff, covs, 4, nullptr}, SampleTable{S.kmers.data(), S.counts.data(), S.kmers.size(), SYLPH_MEM_HOST}, db);
 }
 // SYLPH_HIP_SYLSP_DEVICE: 1 = the tables of sketch files are unpacked on the device and go through the pipeline, 0 = the host's
 // road; unset = the default, which profiles/sylsp_pipeline.txt's measurement decides
@@ -685,6 +674,7 @@ bool sylsp_device_enabled() {
 // statistics of file j - 1 run; the probe is batched; --gpus N deals the samples to N replicas.  Order and messages are the
 // host road's: a file is refused, skipped or reported when its turn has come, after the rows of every file before it.
 void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vector<std::string>& read_sketch_files, sylph_db* db, const ReportTo& to) {
+    using ordered_ahead::Turn;
     const size_t n_files = read_sketch_files.size();
     if (n_files == 0) return;
     if (!sylsp_device_enabled()) {
@@ -692,117 +682,43 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
         return;
     }
     const uint64_t genome_c = to.genome_sketches[0].c;
-    struct Prepared { std::optional<SylspView> view; std::exception_ptr error; };
-    std::vector<std::promise<Prepared>> promises(n_files);
-    std::vector<std::future<Prepared>> futures;
-    for (auto& p : promises) futures.push_back(p.get_future());
+    using Prepared = std::optional<SylspView>;
     ReplicaSet replicas(e, args, db, n_files);
     const size_t n_workers = sample_workers(args.threads, 1, n_files);
-    const size_t ahead_limit = n_workers + 2;                        // files that may wait, mapped and touched, for their turn
-    std::atomic<size_t> next_job{0}, released{0};
-    std::atomic<bool> cancel{false};
-    std::mutex gate_mu;
-    std::condition_variable gate_cv;
-    auto prepare = [&](size_t j) {
-        Prepared pr;
-        try {
-            pr.view = read_sylsp_header(read_sketch_files[j]);
-            const SylspView& v = *pr.view;
-            if (v.meta.c <= genome_c && v.n_entries < (1ull << 31)) {   // (else nothing of the table is read on this road)
-                const volatile uint8_t* page = v.entries;            // one byte of every page: the faults are taken here, not under the staging copy
-                for (uint64_t at = 0, bytes = v.n_entries * 12; at < bytes; at += 4096) (void)page[at];
-            }
-        } catch (...) { pr.error = std::current_exception(); }
-        promises[j].set_value(std::move(pr));
+    auto prepare = [&](size_t j) -> Prepared {
+        SylspView v = read_sylsp_header(read_sketch_files[j]);
+        if (v.meta.c <= genome_c && v.n_entries < (1ull << 31)) {   // (else nothing of the table is read on this road)
+            const volatile uint8_t* page = v.entries;            // one byte of every page: the faults are taken here, not under the staging copy
+            for (uint64_t at = 0, bytes = v.n_entries * 12; at < bytes; at += 4096) (void)page[at];
+        }
+        return v;
     };
-    auto worker = [&] {
-        for (;;) {
-            const size_t j = next_job++;
-            if (j >= n_files) return;
-            {
-                std::unique_lock<std::mutex> lk(gate_mu);
-                gate_cv.wait(lk, [&] { return cancel.load() || j < released.load() + ahead_limit; });
-            }
-            if (cancel) { promises[j].set_value(Prepared{}); continue; }
-            prepare(j);
-        }
-    };
-    sylph_pipeline_config cfg;
-    sylph_pipeline* pipe = replicas.create_pipeline(args, to.genome_sketches[0].k, 2, (uint32_t)ahead_limit + 1, cfg);
-    PipeGuard pipe_guard{pipe};                                      // (finishes what is outstanding: the mappings below outlive it)
-    std::vector<std::thread> pool;
-    struct PoolJoin {   // on every way out: the prepare threads stop taking work and are joined
-        std::vector<std::thread>& pool; std::atomic<bool>& cancel; std::mutex& mu; std::condition_variable& cv;
-        ~PoolJoin() {
-            { std::lock_guard<std::mutex> lk(mu); cancel = true; }
-            cv.notify_all();
-            for (auto& t : pool) if (t.joinable()) t.join();
-        }
-    };
-    enum class Turn { Device, Host, Skip, Failed };
-    std::vector<std::optional<SylspView>> views(n_files);           // a submitted file's mapping stays until its result has been taken
-    std::vector<Turn> turn(n_files, Turn::Skip);
-    std::vector<std::exception_ptr> errors(n_files);
-    struct Drain {      // (declared behind `views`: runs first) nothing may still read a mapping when it goes
-        sylph_pipeline* p;
-        ~Drain() { sylph_pipeline_result r; while (sylph_pipeline_outstanding(p) && sylph_pipeline_next(p, &r) == SYLPH_OK) {} }
-    } drain{pipe};
-    PoolJoin pool_join{pool, cancel, gate_mu, gate_cv};
-    for (size_t w = 0; w < n_workers; w++) pool.emplace_back(worker);
-    size_t submitted = 0, done = 0, submit_end = n_files;            // submit_end: nothing is handed over behind a file that failed, or that waits for the host's road
-    auto release_one = [&] { { std::lock_guard<std::mutex> lk(gate_mu); released++; } gate_cv.notify_all(); };
-    while (done < n_files) {
-        // hand over every prepared file that is ready, in input order (wait for one only when nothing is outstanding)
-        while (submitted < submit_end && sylph_pipeline_outstanding(pipe) < cfg.depth) {
-            const bool must_wait = sylph_pipeline_outstanding(pipe) == 0 && submitted == done;
-            if (!must_wait && futures[submitted].wait_for(std::chrono::seconds(0)) != std::future_status::ready) break;
-            Prepared pr = futures[submitted].get();
-            const size_t j = submitted++;
-            if (pr.error || !pr.view) {
-                turn[j] = Turn::Failed;
-                errors[j] = pr.error ? pr.error : std::make_exception_ptr(Error{1, "The sketch `" + read_sketch_files[j] + "` was not read"});
-                submit_end = submitted;
-                break;
-            }
-            views[j] = std::move(pr.view);
-            if (views[j]->meta.c > genome_c) turn[j] = Turn::Skip;
-            else if (views[j]->n_entries >= (1ull << 31)) {
-                // the host's road probes the database from this thread: nothing is handed over behind such a file until it has had
-                // its turn, so the pipeline is idle (every earlier sample returned) while that probe runs
-                turn[j] = Turn::Host;
-                submit_end = submitted;
-                break;
-            } else {
-                hip_check(sylph_pipeline_submit_entries(pipe, views[j]->entries, views[j]->n_entries, SYLPH_MEM_HOST, j), "sylph_pipeline_submit_entries");
-                turn[j] = Turn::Device;
-            }
-        }
-        const size_t j = done;
-        if (j >= submitted) continue;        // (the wait above guarantees progress)
-        const std::string& file = read_sketch_files[j];
-        if (turn[j] == Turn::Failed) std::rethrow_exception(errors[j]);
-        if (turn[j] == Turn::Skip) sketch_c_too_large(file, views[j]->meta.c, genome_c);
-        else if (turn[j] == Turn::Host) {
-            if (stats_route() == StatsRoute::DeviceOnly) throw Error{1, "SYLPH_HIP_STATS_DEVICE=only: " + file + " takes the host's road"};
-            profile_sketch_on_host(args, file, db, to);
-            submit_end = n_files;
-        }
-        else {
-            sylph_pipeline_result r;
-            hip_check(sylph_pipeline_next(pipe, &r), "sylph_pipeline_next");
-            if (r.status != SYLPH_OK) throw Error{1, std::string("sample ") + file + ": " + (r.error ? r.error : "GPU stage failed")};
-            trace_sketch_route(file, "device", sylph_pipeline_ascending_of_last(pipe), views[j]->n_entries, r.n_table);
-            SequencesSketch& S = views[j]->meta;
-            if (args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
-            const std::optional<Candidates> cand = candidates_of_last(pipe);
-            report(to, S, file, r.contain_count, r.cov_off, r.covs, r.cov_width, r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE,
-                   replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(pipe))], cand ? &*cand : nullptr);
-        }
-        finished({file});
-        views[j].reset();
-        done++;
-        release_one();
-    }
+    SamplePipe pipe(replicas, args, to.genome_sketches[0].k, ordered_ahead::ahead_limit(n_workers));
+    std::vector<Prepared> views(n_files);                           // a file's mapping stays until its turn is over
+    ordered_ahead::Pool<Prepared> pool(n_files, n_workers, [&]() -> ordered_ahead::Pool<Prepared>::Prepare { return prepare; }, [](Prepared&) {});
+    pipe.run(pool,
+             [&](size_t j, Prepared&& view) {
+                 views[j] = std::move(view);
+                 if (views[j]->meta.c > genome_c) return Turn::Skip;
+                 // the host's road probes the database from this thread: it runs with the pipeline idle
+                 if (views[j]->n_entries >= (1ull << 31)) return Turn::Inline;
+                 hip_check(sylph_pipeline_submit_entries(pipe.p, views[j]->entries, views[j]->n_entries, SYLPH_MEM_HOST, j), "sylph_pipeline_submit_entries");
+                 return Turn::Pipeline;
+             },
+             [&](size_t j, Turn turn) {
+                 const std::string& file = read_sketch_files[j];
+                 if (turn == Turn::Skip) sketch_c_too_large(file, views[j]->meta.c, genome_c);
+                 else if (turn == Turn::Inline) {
+                     if (stats_route() == StatsRoute::DeviceOnly) throw Error{1, "SYLPH_HIP_STATS_DEVICE=only: " + file + " takes the host's road"};
+                     profile_sketch_on_host(args, file, db, to);
+                 } else {
+                     const sylph_pipeline_result r = pipe.next(file);
+                     trace_sketch_route(file, "device", sylph_pipeline_ascending_of_last(pipe.p), views[j]->n_entries, r.n_table);
+                     pipe.report_last(to, r, views[j]->meta, file);
+                 }
+                 finished({file});
+                 views[j].reset();
+             });
 }
 }  // namespace
 

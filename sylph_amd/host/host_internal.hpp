@@ -1,6 +1,7 @@
 // host_internal.hpp — what the host's own source files share (engine.cpp, sample_feed.cpp, cmd_sketch.cpp, cmd_contain.cpp): messages,
 // path helpers, the session wrapper, the background threads and the types of a sample's way to the device.  Not part of the
-// interface in sylph_host.hpp: neither installed nor exported.
+// interface in sylph_host.hpp: neither installed nor exported.  (cmd_contain.cpp's hand-over of samples to the pipeline — the
+// prepare-ahead pool and the ordered driver — is ordered_ahead.hpp, a header of its own that includes nothing of this one.)
 #pragma once
 #include <sys/stat.h>
 

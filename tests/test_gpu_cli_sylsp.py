@@ -152,3 +152,14 @@ def test_refused_and_broken_files_fail_as_on_the_host_road(data):
     assert len(names) == 3                                                                     # the three good files in front of the broken one
     assert any("value of -c is 400" in l for l in told(a)) and any("truncated.sylsp` is not a valid sketch" in l for l in told(a))
     assert sum("Finished sample" in l for l in told(a)) == 4                                   # (the refused file "finishes" too, as in the reference)
+
+
+def test_a_broken_file_fails_the_command_at_its_turn(data):
+    """The failure rule of the command's hand-over (host/ordered_ahead.hpp), end to end with the rows summarised on the device: of three
+    files with the middle one truncated, the rows of the first are out — all of them, nothing of the third — and the command fails."""
+    s = data["samples"]
+    alone = run(1, "profile", data["db"], s[0], SYLPH_HIP_STATS_DEVICE="1")
+    assert len(alone.stdout.strip().split("\n")) >= 1 + 2                                      # the header and two genomes at the least
+    p = run(1, "profile", data["db"], s[0], data["truncated"], s[1], check=False, SYLPH_HIP_STATS_DEVICE="1")
+    assert p.returncode != 0
+    assert p.stdout == alone.stdout
