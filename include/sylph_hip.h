@@ -758,6 +758,37 @@ int sylph_pipeline_ascending_of_last(sylph_pipeline *p);
 int sylph_pipeline_set_row_filter(sylph_pipeline *p, const sylph_row_filter *filter);
 int sylph_pipeline_rows_of_last(sylph_pipeline *p, const sylph_row_summary **rows, uint32_t *n, const uint64_t **row_cov_off,
                                 const void **row_covs, uint32_t *cov_width);
+/* K15 — the integers --estimate-unknown reads off a sample's table (contain.rs:901-951 get_kmer_identity, :392-408
+ * estimate_covered_bases), counted on the device.  Over the counts in table order, x_1 .. x_S the counts above 1, m_0 = 0 and
+ * m_i = m_(i-1) + 1 if x_i > m_(i-1), else m_(i-1) - 1:  steps = S, median_sum = m_1 + .. + m_S, max_state = the largest m_i;
+ * num_1s = the counts equal to 1, num_not1s = the sum of the others modulo 2^32 (the reference's u32), total_counts = the sum
+ * of all.  The reference's f64 values follow exactly: mov_avg_median = (double)median_sum / (1 + steps).  The walk runs in
+ * parallel on a short ladder of caps (csrc/table_summary_plan.h: why that is exact, and when it is not possible); `rung` is the one
+ * that answered, open_chunks what its ordered pass had to walk again.  A summary that DECLINES sets SYLPH_TABLE_SUMMARY_DECLINED
+ * and one reason in `flags`: no rung answered (_LADDER: a table whose state passes every cap, or one that never lets a chunk's
+ * bounds meet), median_sum reached 2^53 (_SUM: the f64 sums would round), 2^31 entries or more (_SIZE: nothing is counted).
+ * The sums (steps, num_1s, num_not1s, total_counts) are valid after _LADDER and _SUM; median_sum and max_state are 0, rung is the
+ * number of rungs.  Declining is not an error: the call returns SYLPH_OK and the caller walks the counts itself.
+ * Context options, for tests: "table_summary_caps" / "table_summary_chunk" = up to four comma-separated numbers (caps ascending,
+ * 2 .. 2^30; a single chunk holds for every rung; "" = the default ladder), "table_summary_max_open" (default 64).  Kernel
+ * statistics family: "table_summary". */
+#define SYLPH_TABLE_SUMMARY_DECLINED 1u
+#define SYLPH_TABLE_SUMMARY_DECLINED_LADDER 2u
+#define SYLPH_TABLE_SUMMARY_DECLINED_SUM 4u
+#define SYLPH_TABLE_SUMMARY_DECLINED_SIZE 8u
+typedef struct sylph_table_summary_t {
+    uint64_t median_sum, total_counts;
+    uint32_t steps, num_1s, num_not1s, max_state, flags, rung, open_chunks, reserved;
+} sylph_table_summary_t;
+/* counts[0 .. n): host memory (copied over) or device memory (mem: SYLPH_MEM_*). */
+int sylph_table_summary(sylph_ctx *ctx, const uint32_t *counts, uint64_t n, int mem, sylph_table_summary_t *out);
+/* On a pipeline: sylph_pipeline_set_option "table_summary" = "1" (default "0") makes the profile thread summarise every sample's
+ * table where it lies — sessions, raw batches and entries alike —, and this call hands out the summary of the sample the last
+ * successful sylph_pipeline_next returned (SYLPH_ERR_STATE without the option, before the first sample, or for a sample whose
+ * status is not SYLPH_OK).  A sample whose summary DECLINED carries a host copy of its counts in result.counts (kmers stays
+ * NULL), so the caller can walk them itself.  want_table is independent of it.  The router of sylph_pipeline_create_multi forwards the call to
+ * the replica that held the sample. */
+int sylph_pipeline_summary_of_last(sylph_pipeline *p, sylph_table_summary_t *out);
 /* Sharded pipelines only need it: everything submitted so far may be probed in a batch smaller than max_batch, and no batch
  * reaches across the flush point — flushes with samples outstanding in between leave one batch boundary each. */
 int sylph_pipeline_flush(sylph_pipeline *p);

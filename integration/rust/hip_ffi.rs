@@ -16,6 +16,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphBootstrapSummary { pub n_nonzero: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one resample
 #[repr(C)] pub struct SylphRowFilter { pub struct_size: u32, pub k: u32, pub reject_below: f64, pub min_count_correct: f64, pub no_adj: u32, pub reserved: u32, pub cut: [u32; 30] }   // sylph_row_filter; cut[m] = 0xFFFFFFFF: none
 #[repr(C)] pub struct SylphRowSummary { pub row: u32, pub contain_count: u32, pub median: u32, pub keep: u32, pub sum: u32, pub n_distinct: u32, pub mode: u32, pub mode_count: u32, pub next_count: u32 }   // one candidate row
+#[repr(C)] pub struct SylphTableSummary { pub median_sum: u64, pub total_counts: u64, pub steps: u32, pub num_1s: u32, pub num_not1s: u32, pub max_state: u32, pub flags: u32, pub rung: u32, pub open_chunks: u32, pub reserved: u32 }   // get_kmer_identity's walks as integers; flags & 1: declined
 #[repr(C)] pub struct SylphReassignEdge { pub winner: u32, pub loser: u32, pub count: u32 }   // sylph_reassign_edge: ranks in the passing list
 #[repr(C)] pub struct SylphCommOps {   // caller-supplied collectives on device buffers (stream = hipStream_t); 0 = success
     pub all_gather: extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes: u64, stream: *mut c_void) -> c_int,
@@ -196,6 +197,12 @@ extern "C" {
     pub fn sylph_pipeline_set_row_filter(p: *mut SylphPipeline, filter: *const SylphRowFilter) -> c_int;
     pub fn sylph_pipeline_rows_of_last(p: *mut SylphPipeline, rows: *mut *const SylphRowSummary, n: *mut u32, row_cov_off: *mut *const u64,
                                        row_covs: *mut *const c_void, cov_width: *mut u32) -> c_int;
+    // --estimate-unknown's walks over a sample's counts (contain.rs:901-951, :392-408) counted where the table lies: the running median's
+    // steps and state sum, the multiplicity-1 share, the total; mov_avg_median = median_sum as f64 / (1 + steps) as f64, bit for bit.
+    // flags & 1: the summary declined (walk the counts yourself; the pipeline then carries them in result.counts)
+    pub fn sylph_table_summary(ctx: *mut SylphCtx, counts: *const u32, n: u64, mem: c_int, out: *mut SylphTableSummary) -> c_int;
+    // the pipeline's form: sylph_pipeline_set_option(p, "table_summary", "1"), then the summary of the sample next() returned last
+    pub fn sylph_pipeline_summary_of_last(p: *mut SylphPipeline, out: *mut SylphTableSummary) -> c_int;
     // k-mer-range shards: bounds for `world` GPUs, upload of this rank's range, communicator, the collective batch call
     pub fn sylph_shard_bounds(max_kmer: u64, world: u32, bounds: *mut u64) -> c_int;
     pub fn sylph_db_upload_shard(ctx: *mut SylphCtx, kmers: *const u64, genome_off: *const u64, n_genomes: u64, mem: c_int,

@@ -47,7 +47,8 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_bunzip2", "sylph_bunzip2_files",
            "sylph_bunzip2_stream_open", "sylph_bunzip2_stream_next", "sylph_bunzip2_stream_info", "sylph_bunzip2_stream_destroy", "sylph_bootstrap_counts",
            "sylph_table_from_entries", "sylph_table_view", "sylph_table_destroy", "sylph_pipeline_submit_entries", "sylph_pipeline_ascending_of_last",
-           "sylph_row_summaries", "sylph_pipeline_set_row_filter", "sylph_pipeline_rows_of_last"]
+           "sylph_row_summaries", "sylph_pipeline_set_row_filter", "sylph_pipeline_rows_of_last", "sylph_table_summary",
+           "sylph_pipeline_summary_of_last"]
 
 
 def load():
@@ -180,6 +181,8 @@ def load():
     L.sylph_pipeline_set_row_filter.argtypes = [vp, vp]
     L.sylph_pipeline_rows_of_last.argtypes = [vp, P(vp), P(u32), P(vp), P(vp), P(u32)]
     L.sylph_row_summaries.argtypes = [vp, vp, u32, vp, vp, u32, i32, vp, P(vp), P(u32), P(vp), P(vp)]
+    L.sylph_table_summary.argtypes = [vp, vp, u64, i32, vp]
+    L.sylph_pipeline_summary_of_last.argtypes = [vp, vp]
     _LIB = L
     return L
 
@@ -248,6 +251,18 @@ class Context:
         _check(load().sylph_ctx_kernel_stats(self._h, family.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def table_summary(self, counts, n=None):
+        """sylph_table_summary: the integers --estimate-unknown reads off a table's counts -> a dict of TABLE_SUMMARY's fields.  counts: a
+        uint32 array (MEM_HOST), or the integer address of device memory with n given (MEM_DEVICE)."""
+        out = np.zeros(1, dtype=TABLE_SUMMARY)
+        if n is None:
+            a = _np(counts, np.uint32)
+            ptr, n, mem = (_ptr(a) if len(a) else None), len(a), MEM_HOST
+        else:
+            ptr, mem = C.c_void_p(int(counts)), MEM_DEVICE
+        _check(load().sylph_table_summary(self._h, ptr, int(n), mem, _ptr(out)))
+        return {f: int(out[0][f]) for f in TABLE_SUMMARY.names}
+
     # extract_markers, sketch.rs:53
     def extract_markers(self, seq, c=200, k=31, seed_mode=SEED_AVX2_COMPAT):
         a = _bases(seq)
@@ -301,6 +316,11 @@ class Context:
                                                  C.byref(ok), _ptr(koff), C.byref(ot), _ptr(toff)))
         return _take(ok, int(koff[-1]), np.uint64), koff, _take(ot, int(toff[-1]), np.uint64), toff
 
+
+# sylph_table_summary_t; flags: TABLE_SUMMARY_DECLINED | why
+TABLE_SUMMARY = np.dtype([("median_sum", np.uint64), ("total_counts", np.uint64), ("steps", np.uint32), ("num_1s", np.uint32), ("num_not1s", np.uint32),
+                          ("max_state", np.uint32), ("flags", np.uint32), ("rung", np.uint32), ("open_chunks", np.uint32), ("reserved", np.uint32)])
+TABLE_SUMMARY_DECLINED, TABLE_SUMMARY_DECLINED_LADDER, TABLE_SUMMARY_DECLINED_SUM, TABLE_SUMMARY_DECLINED_SIZE = 1, 2, 4, 8
 
 BOOTSTRAP_SUMMARY = np.dtype([("n_nonzero", np.uint32), ("n_distinct", np.uint32), ("mode", np.uint32), ("mode_count", np.uint32),
                               ("next_count", np.uint32)])
@@ -1112,6 +1132,13 @@ class Pipeline:
         o = np.frombuffer(C.string_at(off, (n.value + 1) * 8), dtype=np.uint64).copy()
         v = np.frombuffer(C.string_at(covs, int(o[-1]) * width.value), dtype=dt).copy()
         return r, o, v
+
+    def summary_of_last(self):
+        """Of the sample next() returned last, on a pipeline with the option "table_summary" = "1": the dict Context.table_summary gives
+        for its table's counts (sylph_pipeline_summary_of_last)."""
+        out = np.zeros(1, dtype=TABLE_SUMMARY)
+        _check(load().sylph_pipeline_summary_of_last(self._h, _ptr(out)))
+        return {f: int(out[0][f]) for f in TABLE_SUMMARY.names}
 
     def ascending_of_last(self):
         """Of the sample next() returned last: 1 its entries ascended strictly, 0 they were sorted, -1 not submitted as entries."""

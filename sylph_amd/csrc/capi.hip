@@ -4,6 +4,7 @@
 
 #include <thread>
 
+#include "table_summary.h"
 #include "common.h"
 
 namespace sylph {
@@ -462,6 +463,18 @@ int sylph_ctx_set_option(sylph_ctx* ctx, const char* key, const char* value) {
             const long v = atol(value);
             SY_REQUIRE(v >= 1 && v <= 8192, "reassign_edge_window must be 1..8192");
             ctx->reassign_edge_window = (uint32_t)v;
+        } else if (!strcmp(key, "table_summary_caps") || !strcmp(key, "table_summary_chunk")) {
+            // "c0,c1,.." — up to four rungs; "" = the default again.  The ladder as a whole is checked where it is used.
+            uint32_t vals[4] = {0, 0, 0, 0};
+            const int n_vals = parse_rung_numbers(value, vals);
+            SY_REQUIRE(n_vals >= 0, "%s must be up to four numbers in [1, 2^30], comma-separated", key);
+            const bool caps = key[14] == 'c' && key[15] == 'a';
+            (caps ? ctx->table_summary_n_caps : ctx->table_summary_n_chunks) = (uint32_t)n_vals;
+            memcpy(caps ? ctx->table_summary_caps : ctx->table_summary_chunks, vals, sizeof(vals));
+        } else if (!strcmp(key, "table_summary_max_open")) {
+            const long long v = atoll(value);
+            SY_REQUIRE(v >= 0 && v <= 0xFFFFFFFFll, "table_summary_max_open must be in [0, 2^32)");
+            ctx->table_summary_max_open = (uint32_t)v;
         } else if (!strcmp(key, "stream_priority")) {
             // The context's own stream is made again at another priority (hipStreamCreateWithPriority): "high" lets the small kernels of a
             // profile context through where the sketch contexts' seeding kernels keep the chip full (pipeline.hip).

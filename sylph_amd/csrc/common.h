@@ -151,6 +151,11 @@ struct sylph_ctx {
     uint32_t bootstrap_shape = 0;           // "bootstrap_shape": how sylph_bootstrap_counts gets a drawn index's value, 0 = gather (default), 1 = table of boundaries (bootstrap.hip)
     uint32_t bootstrap_bins = 64;           // "bootstrap_bins" (tests lower it): an item of sylph_bootstrap_counts with a kept value of this or more declines
     uint32_t reassign_edge_window = 8192;   // "reassign_edge_window" (tests lower it): winner ranks per count workgroup of sylph_db_reassign_edges (reassign_edges_plan.h WINDOW_DEFAULT, unmeasured)
+    // "table_summary_caps" / "table_summary_chunk" (comma-separated, one per rung; tests lower them) and "table_summary_max_open": the
+    // ladder of sylph_table_summary (table_summary.hip table_summary_ladder); none given = table_summary_plan.h's default
+    uint32_t table_summary_n_caps = 0, table_summary_caps[4] = {0, 0, 0, 0};
+    uint32_t table_summary_n_chunks = 0, table_summary_chunks[4] = {0, 0, 0, 0};
+    uint32_t table_summary_max_open = 64;
     uint64_t inflate_slice_bytes = 0;       // "inflate_slice_bytes" (tests lower it): compressed bytes per slice of a sylph_inflate_stream opened with slice_bytes 0; 0 = the default (inflate_stream_plan.h)
     uint64_t inflate_whole_max_bytes = SYLPH_INFLATE_WHOLE_MAX_BYTES;   // "inflate_whole_max_bytes" (tests lower it): sylph_inflate_files declines this many gzip bytes or more
     uint64_t bunzip2_slice_bytes = 0;       // "bunzip2_slice_bytes" (tests lower it): compressed bytes per slice of a sylph_bunzip2_stream opened with slice_bytes 0; 0 = the default (bunzip2_stream_plan.h)

@@ -27,6 +27,7 @@
 #include "pipeline_core.h"
 #include "sketch_session.h"
 #include "sylsp_table.h"
+#include "table_summary.h"
 
 using namespace sylph;
 namespace plan = sylph::pipeline_plan;
@@ -64,6 +65,8 @@ struct Job : pipeline_core::JobBase<Block> {     // (owner: the worker whose con
     uint64_t n_table = 0, dup_removed = 0;
     std::vector<uint64_t> host_k;    // want_table
     std::vector<uint32_t> host_c;
+    table_summary_plan::Summary summary{};   // "table_summary"
+    bool has_summary = false;
     double t_submit = 0, t_sketch0 = 0, t_sketch1 = 0, t_profile0 = 0, t_done = 0;
 };
 
@@ -133,6 +136,7 @@ struct sylph_pipeline {      // the opaque handle: an Engine or a Router
     virtual int ascending_of_last() = 0;
     virtual int set_row_filter(const sylph_row_filter* f) = 0;
     virtual int rows_of_last(const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs, uint32_t* cov_width) = 0;
+    virtual int summary_of_last(sylph_table_summary_t* out) = 0;
 };
 
 namespace {
@@ -152,6 +156,9 @@ struct Engine final : sylph_pipeline {
     std::atomic<bool> submitted{false};
     struct LastRows { const sylph_row_summary* rows = nullptr; uint32_t n = 0; const uint64_t* off = nullptr; const void* covs = nullptr; uint32_t width = 0; };
     LastRows last_rows;                          // of the sample next returned last (the caller's thread only)
+    std::atomic<uint32_t> table_summary{0};      // "table_summary" = 1: the profile thread summarises every sample's counts on the device (table_summary.hip)
+    table_summary_plan::Summary last_summary{};  // of the sample next returned last (the caller's thread only)
+    bool last_has_summary = false;
     std::atomic<int> last_ascending{-1};         // of the sample next returned last: its entries ascended (1) / were sorted (0); -1: not an entries job
     // tuning (sylph_pipeline_set_option): see the option table in include/sylph_hip.h
     std::atomic<uint32_t> serial_outside{0};     // "serialize_outside" = 1: the r01-r04 placement of that wait (A/B; profiles/r05_ab_seed_turn.txt)
@@ -300,6 +307,23 @@ struct Engine final : sylph_pipeline {
                 }
             });
         }
+        if (rc == SYLPH_OK && table_summary.load()) {
+            // every table where it lies: on the context that sketched or unpacked it (its ladder knobs are that context's)
+            rc = guarded([&] {
+                for (Job* j : good) {
+                    sylph_ctx* cx = j->table_ctx();
+                    std::lock_guard<std::mutex> lock(cx->mu);
+                    DeviceGuard dg(cx->device);
+                    table_summary_device(cx, j->dev_c, j->n_table, j->summary);
+                    j->has_summary = true;
+                    // a summary that declines brings the counts along (result.counts, as with want_table): the caller walks them
+                    if ((j->summary.flags & table_summary_plan::DECLINED) && !want_table) {
+                        j->host_c.resize(j->n_table);
+                        if (j->n_table) cx->d2h(j->host_c.data(), j->dev_c, j->n_table * 4);
+                    }
+                }
+            });
+        }
         blk.status = rc;
         if (rc != SYLPH_OK) blk.error = sylph_last_error();
         const double t1 = now_s();
@@ -351,9 +375,12 @@ struct Engine final : sylph_pipeline {
         out->dev_kmers = j->dev_k;
         out->dev_counts = j->dev_c;
         if (want_table && out->status == SYLPH_OK) { out->kmers = j->host_k.data(); out->counts = j->host_c.data(); }
+        else if (j->has_summary && (j->summary.flags & table_summary_plan::DECLINED) && out->status == SYLPH_OK) out->counts = j->host_c.data();
         out->t_submit = j->t_submit; out->t_sketch_begin = j->t_sketch0; out->t_sketch_end = j->t_sketch1;
         out->t_profile_begin = j->t_profile0; out->t_done = j->t_done;
         out->probe_batch = j->batch_size;
+        last_has_summary = j->has_summary && out->status == SYLPH_OK;
+        last_summary = j->summary;
         last_rows = LastRows{};
         if (j->slot >= 0 && b.mem.cand.on) {     // a row filter: the candidates only (sylph_pipeline_rows_of_last)
             const char* h = (const char*)b.mem.p;
@@ -378,7 +405,7 @@ struct Engine final : sylph_pipeline {
     int set_option(const char* key, const char* value) override {
         // the pipeline's own knobs; everything else goes to the workers' contexts
         std::atomic<uint32_t>* knob = !strcmp(key, "serialize_seeding") ? &serialize_seeding : !strcmp(key, "serialize_outside") ? &serial_outside
-                                    : !strcmp(key, "min_batch") ? &core->min_batch : !strcmp(key, "batch_wait_us") ? &core->batch_wait_us : nullptr;
+                                    : !strcmp(key, "table_summary") ? &table_summary : !strcmp(key, "min_batch") ? &core->min_batch : !strcmp(key, "batch_wait_us") ? &core->batch_wait_us : nullptr;
         if (knob) { knob->store((uint32_t)strtoul(value, nullptr, 10)); return SYLPH_OK; }
         if (!strcmp(key, "shard_reduce")) return sylph_ctx_set_option(db->ctx, key, value);      // (the database's context only: "alltoall" | "allgather")
         if (!strcmp(key, "dedup_fpr") || !strcmp(key, "dedup_capacity")) {      // for the sessions opened from now on (checked by the session)
@@ -417,6 +444,13 @@ struct Engine final : sylph_pipeline {
         *row_covs = last_rows.n ? last_rows.covs : nullptr;
         if (cov_width) *cov_width = last_rows.width;
         return SYLPH_OK;
+    }
+    int summary_of_last(sylph_table_summary_t* out) override {
+        return guarded([&] {
+            SY_REQUIRE_STATE(last_has_summary, "sylph_pipeline_summary_of_last: no summary of the last sample (set the option \"table_summary\" before submitting it)");
+            static_assert(sizeof(table_summary_plan::Summary) == sizeof(sylph_table_summary_t), "the ABI's summary is the plan's");
+            memcpy(out, &last_summary, sizeof(*out));
+        });
     }
 };
 
@@ -471,6 +505,7 @@ struct Router final : sylph_pipeline {
     int rows_of_last(const sylph_row_summary** rows, uint32_t* n, const uint64_t** row_cov_off, const void** row_covs, uint32_t* cov_width) override {
         return children[(size_t)replica_of_last()]->rows_of_last(rows, n, row_cov_off, row_covs, cov_width);
     }
+    int summary_of_last(sylph_table_summary_t* out) override { return children[(size_t)replica_of_last()]->summary_of_last(out); }
 };
 
 void require_config(const sylph_pipeline_config* cfg) {
@@ -534,6 +569,8 @@ int sylph_pipeline_rows_of_last(sylph_pipeline* p, const sylph_row_summary** row
                                 uint32_t* cov_width) {
     return p && rows && n && row_cov_off && row_covs ? p->rows_of_last(rows, n, row_cov_off, row_covs, cov_width) : null_argument();
 }
+
+int sylph_pipeline_summary_of_last(sylph_pipeline* p, sylph_table_summary_t* out) { return p && out ? p->summary_of_last(out) : null_argument(); }
 
 int sylph_pipeline_submit(sylph_pipeline* p, const sylph_read_batch* batches, uint32_t n_batches, int mem, int enc, uint64_t tag) {
     if (!p || (n_batches && !batches)) return null_argument();

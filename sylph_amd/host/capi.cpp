@@ -131,7 +131,7 @@ double sylph_host_covered_bases(const uint64_t* gn_size, const double* cov, uint
     std::vector<GenomeSketch> gs(n_genomes);
     std::vector<AniResult> rs(n_genomes);
     for (uint64_t i = 0; i < n_genomes; i++) { gs[i].gn_size = gn_size[i]; rs[i].final_est_cov = cov[i]; rs[i].genome_index = i; }
-    return estimate_covered_bases(rs, gs, S, mean_read_length, k);
+    return estimate_covered_bases(rs, gs, S.c, table_summary_host(S.counts).total_counts, mean_read_length, k);
 }
 
 // `inspect` scalars (tests): returns the length written (without the terminator), 0 if the buffer is too small

@@ -65,24 +65,45 @@ void print_header(bool pseudotax, FILE* out, bool estimate_unknown) {         //
 // It only decides whether a short-read sample counts as "depth < 3" and gets the fixed 99.5 % identity — a sample right at
 // that limit may take the other branch than `sylph profile -u` does; -I (contain.rs:275) bypasses the walk altogether.
 // The integer types are the reference's: `num_not1s` is a u32 that wraps in a release build.
-std::optional<double> get_kmer_identity(const SequencesSketch& S, bool estimate_unknown) {
-    if (!estimate_unknown) return std::nullopt;
+//
+// Two halves.  The walks over the counts (table_summary_host; on the device's road csrc/table_summary.hip counts the same integers
+// where the table lies: unknown_from_device) and the decision in f64 (kmer_identity_from_summary): both roads go through the one tail.
+UnknownSummary table_summary_host(const std::vector<uint32_t>& counts) {
+    UnknownSummary s;
     uint32_t median = 0;
     double mov_avg_median = 0., n = 1.;
-    for (const uint32_t count : S.counts) {
+    for (const uint32_t count : counts) {
         if (count > 1) {
             if (count > median) median += 1; else median -= 1;
             mov_avg_median += (double)median;
             n += 1.;
         }
     }
-    mov_avg_median /= n;
-    int32_t num_1s = 0;
-    uint32_t num_not1s = 0;
-    for (const uint32_t count : S.counts) {
-        if (count == 1) num_1s += 1; else num_not1s += count;
+    s.mov_avg_median = mov_avg_median / n;
+    for (const uint32_t count : counts) {
+        if (count == 1) s.num_1s += 1; else s.num_not1s += count;
     }
-    const double eps = (double)num_not1s / ((double)num_not1s + (double)num_1s + 0.1);
+    for (const uint32_t count : counts) s.total_counts += count;     // contain.rs:392-408's own walk
+    return s;
+}
+// median_sum < 2^53 (a summary at or above that declines): the f64 additions above are exact on the same integers, so the quotient
+// is the host's, bit for bit; 1 + steps <= 2^31 is exact as well
+UnknownSummary unknown_from_device(const sylph_table_summary_t& d) {
+    UnknownSummary s;
+    s.mov_avg_median = (double)d.median_sum / (1. + (double)d.steps);
+    s.num_1s = (int32_t)d.num_1s;
+    s.num_not1s = d.num_not1s;
+    s.total_counts = d.total_counts;
+    return s;
+}
+std::optional<double> get_kmer_identity(const SequencesSketch& S, bool estimate_unknown) {
+    if (!estimate_unknown) return std::nullopt;
+    return kmer_identity_from_summary(table_summary_host(S.counts), S.k, S.mean_read_length, S.file_name);
+}
+double kmer_identity_from_summary(const UnknownSummary& s, uint64_t k, double mean_read_length, const std::string& file_name) {
+    const struct { const std::string& file_name; double mean_read_length; uint64_t k; } S{file_name, mean_read_length, k};
+    const double mov_avg_median = s.mov_avg_median;
+    const double eps = (double)s.num_not1s / ((double)s.num_not1s + (double)s.num_1s + 0.1);
     {   // which branch the walk chose, and how close the call was (the walk's order is this host's, not hashbrown's: see above).
         // The reference prints neither line: the first only under SYLPH_HIP_DEBUG, the warning only inside the 10 % band.
         const bool near_limit = S.mean_read_length < 400. && std::fabs(mov_avg_median - MED_KMER_FOR_ID_EST) <= 0.1 * MED_KMER_FOR_ID_EST;
@@ -115,14 +136,12 @@ void estimate_true_cov(std::vector<AniResult>& results, std::optional<double> km
 }
 
 // contain.rs:392-408: share of the sample's bases the profiled genomes account for
-double estimate_covered_bases(const std::vector<AniResult>& results, const std::vector<GenomeSketch>& genomes, const SequencesSketch& S,
+double estimate_covered_bases(const std::vector<AniResult>& results, const std::vector<GenomeSketch>& genomes, uint64_t c, uint64_t num_total_counts,
                               double read_length, uint64_t k) {
     const double multiplier = read_length / (read_length - (double)k + 1.);
     double num_covered_bases = 0.;
     for (const auto& r : results) num_covered_bases += (double)genomes[r.genome_index].gn_size * r.final_est_cov;
-    uint64_t num_total_counts = 0;
-    for (const uint32_t count : S.counts) num_total_counts += count;
-    const double num_tentative_bases = (double)(S.c * num_total_counts) * multiplier;
+    const double num_tentative_bases = (double)(c * num_total_counts) * multiplier;
     if (num_tentative_bases == 0.) return 0.;
     return std::min(num_covered_bases / num_tentative_bases, 1.);
 }
@@ -244,6 +263,23 @@ StatsRoute stats_route() {
     if (!strcmp(e, "only")) return StatsRoute::DeviceOnly;
     throw Error{1, std::string("SYLPH_HIP_STATS_DEVICE must be 0, 1 or only, not ") + e};
 }
+// The road of --estimate-unknown's walks over a sample's counts.  Host: the pipeline copies every table to the host (want_table) and
+// this thread walks the counts (table_summary_host).  Device: the pipeline's profile thread counts the walks' integers where the table
+// lies (the option "table_summary"; csrc/table_summary.hip) and nothing of the table travels; a summary that declines brings the
+// counts along and they are walked here.  SYLPH_HIP_UNKNOWN_DEVICE = 0 | 1 | only (only: a declined summary is an Error).  Same
+// output, bit for bit.  The project's ship rule decides the default — on only where whole `profile -u` and `query -u` commands beat
+// the parent commit's binary by more than both spreads: in profiles/table_summary.txt's record the device's road was faster in every
+// pair (1.08x and 1.18x over 64 sketches), `profile -u` beyond the spreads and `query -u` not, so unset means 0.
+enum class UnknownRoute { Host, Device, DeviceOnly };
+constexpr UnknownRoute UNKNOWN_ROUTE_DEFAULT = UnknownRoute::Host;
+UnknownRoute unknown_route() {
+    const char* e = getenv("SYLPH_HIP_UNKNOWN_DEVICE");
+    if (!e || !*e) return UNKNOWN_ROUTE_DEFAULT;
+    if (!strcmp(e, "0")) return UnknownRoute::Host;
+    if (!strcmp(e, "1")) return UnknownRoute::Device;
+    if (!strcmp(e, "only")) return UnknownRoute::DeviceOnly;
+    throw Error{1, std::string("SYLPH_HIP_UNKNOWN_DEVICE must be 0, 1 or only, not ") + e};
+}
 // the candidates of a sample (sylph_pipeline_rows_of_last)
 struct Candidates {
     const sylph_row_summary* rows = nullptr;
@@ -283,7 +319,9 @@ struct StatsRow {
     row_stats_plan::RowSummary summary;
 };
 
-void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const FirstPass& first, const SampleTable& table, sylph_db* rdb) {
+// unknown: with -u, what the walks over the sample's counts came down to on the device; none: they run here, over S.counts
+void report(const ReportTo& to, const SequencesSketch& S, const std::string& first_file, const FirstPass& first, const SampleTable& table, sylph_db* rdb,
+            const std::optional<UnknownSummary>& unknown = std::nullopt) {
     const ContainCmdArgs& args = to.args;
     const std::vector<GenomeSketch>& genome_sketches = to.genome_sketches;
     FILE* const out = to.out;
@@ -358,7 +396,7 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
     }
     std::optional<double> kmer_id_opt;                               // contain.rs:274-281
     if (args.seq_id) kmer_id_opt = std::pow(*args.seq_id / 100., (double)S.k);
-    else kmer_id_opt = get_kmer_identity(S, args.estimate_unknown);
+    else if (args.estimate_unknown) kmer_id_opt = kmer_identity_from_summary(unknown ? *unknown : table_summary_host(S.counts), S.k, S.mean_read_length, S.file_name);
     estimate_true_cov(stats, kmer_id_opt, args.estimate_unknown, S.mean_read_length, S.k);   // :295
     if (args.pseudotax) {
         info(first_file + " taxonomic profiling; reassigning k-mers for " + std::to_string(stats.size()) + " genomes...");
@@ -388,7 +426,8 @@ void report(const ReportTo& to, const SequencesSketch& S, const std::string& fir
         info(first_file + " has " + std::to_string(stats.size()) + " genomes passing profiling threshold. ");
         double bases_explained = 1.;                                 // :313-317
         if (args.estimate_unknown) {
-            bases_explained = estimate_covered_bases(stats, genome_sketches, S, S.mean_read_length, S.k);
+            const uint64_t total_counts = unknown ? unknown->total_counts : table_summary_host(S.counts).total_counts;
+            bases_explained = estimate_covered_bases(stats, genome_sketches, S.c, total_counts, S.mean_read_length, S.k);
             char buf[64];
             snprintf(buf, sizeof buf, "%.2f", bases_explained * 100.);
             info(first_file + " has " + buf + "% of reads detected in database by profile");
@@ -515,11 +554,16 @@ struct ReplicaSet {
         cfg.max_batch = 4;
         cfg.c = (uint32_t)args.c; cfg.k = (uint32_t)args.k;
         cfg.reads_mode = SYLPH_READS_PAIRED; cfg.seed_mode = SYLPH_SEED_AVX2_COMPAT;
-        cfg.want_table = args.estimate_unknown ? 1 : 0;                 // -u walks the counts on the host
+        const bool unknown_on_device = args.estimate_unknown && unknown_route() != UnknownRoute::Host;
+        cfg.want_table = args.estimate_unknown && !unknown_on_device ? 1 : 0;   // -u walks the counts on the host, or (below) the device does
         cfg.min_number_kmers = args.min_number_kmers;
         sylph_pipeline* pipe = nullptr;
         if (n_gpus > 1) hip_check(sylph_pipeline_create_multi(dbs.data(), (uint32_t)dbs.size(), &cfg, &pipe), "sylph_pipeline_create_multi");
         else hip_check(sylph_pipeline_create(dbs[0], &cfg, &pipe), "sylph_pipeline_create");
+        if (unknown_on_device) {
+            const int rc = sylph_pipeline_set_option(pipe, "table_summary", "1");
+            if (rc != SYLPH_OK) { sylph_pipeline_destroy(pipe); hip_check(rc, "sylph_pipeline_set_option"); }
+        }
         if (stats_route() != StatsRoute::Host) {
             const sylph_row_filter f = row_filter_for(args, k);
             const int rc = sylph_pipeline_set_row_filter(pipe, &f);
@@ -558,9 +602,19 @@ struct SamplePipe {
     // ... -> the counts -u walks -> the candidates -> the sample's rows, reassigned on the replica that holds its table
     void report_last(const ReportTo& to, const sylph_pipeline_result& r, SequencesSketch& S, const std::string& file) {
         if (to.args.estimate_unknown && r.counts) S.counts.assign(r.counts, r.counts + r.n_table);
+        std::optional<UnknownSummary> unknown;
+        if (to.args.estimate_unknown && unknown_route() != UnknownRoute::Host) {
+            sylph_table_summary_t s;
+            hip_check(sylph_pipeline_summary_of_last(p, &s), "sylph_pipeline_summary_of_last");
+            if (!(s.flags & SYLPH_TABLE_SUMMARY_DECLINED)) unknown = unknown_from_device(s);
+            else if (unknown_route() == UnknownRoute::DeviceOnly)
+                throw Error{1, "SYLPH_HIP_UNKNOWN_DEVICE=only: the table summary of " + file + " declined (flags " + std::to_string(s.flags) + ")"};
+            if (FeedLaps::on())
+                fprintf(stderr, "[sylph_hip feed] unknown %s: road %s, rung %u, %u chunks walked again\n", file.c_str(), unknown ? "device" : "host (declined)", s.rung, s.open_chunks);
+        }
         const std::optional<Candidates> cand = candidates_of_last(p);
         report(to, S, file, FirstPass{r.contain_count, r.cov_off, r.covs, r.cov_width, cand ? &*cand : nullptr},
-               SampleTable{r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE}, replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(p))]);
+               SampleTable{r.dev_kmers, r.dev_counts, r.n_table, SYLPH_MEM_DEVICE}, replicas.dbs[(size_t)std::max(0, sylph_pipeline_replica_of_last(p))], unknown);
     }
     // the ordered hand-over of `pool`'s jobs through this pipeline (ordered_ahead.hpp: order, failure rule, clean-up)
     template <class P, class Submit, class Consume>
@@ -726,6 +780,7 @@ void profile_sketch_files(Engine& e, const ContainCmdArgs& args, const std::vect
 int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
     if (pseudotax_in) args.pseudotax = true;
     (void)stats_route();                                             // (a bad SYLPH_HIP_STATS_DEVICE fails the command before any work)
+    (void)unknown_route();                                           // (and a bad SYLPH_HIP_UNKNOWN_DEVICE)
     std::vector<std::string> genome_sketch_files, genome_files, read_sketch_files;
     std::vector<std::vector<std::string>> read_files;
     std::vector<std::string> all_files = args.files;

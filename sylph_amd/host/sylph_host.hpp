@@ -395,9 +395,20 @@ struct ContainCmdArgs : ContainArgs {   // cmdline.rs:88-160
 // SYLPH_HIP_EXACT_DEDUP=1 in the environment (neither is in the reference), or --fpr 0 where the command has it
 bool exact_dedup_accepted(bool flag);
 // --estimate-unknown (contain.rs:901-951, :377-408)
+// What the walks over a sample's counts come down to: from the counts on the host (table_summary_host: the reference's loops), or
+// from the integers counted on the device (unknown_from_device: csrc/table_summary.hip; exact, see csrc/table_summary_plan.h)
+struct UnknownSummary {
+    double mov_avg_median = 0.;    // the running "continuous median" of the counts above 1, averaged
+    int32_t num_1s = 0;
+    uint32_t num_not1s = 0;        // wraps, as the reference's u32 does in a release build
+    uint64_t total_counts = 0;
+};
+UnknownSummary table_summary_host(const std::vector<uint32_t>& counts);
+UnknownSummary unknown_from_device(const sylph_table_summary_t& s);   // of a summary that did not decline
+double kmer_identity_from_summary(const UnknownSummary& s, uint64_t k, double mean_read_length, const std::string& file_name);
 std::optional<double> get_kmer_identity(const SequencesSketch& S, bool estimate_unknown);
 void estimate_true_cov(std::vector<AniResult>& results, std::optional<double> kmer_id_opt, bool estimate_unknown, double read_length, uint64_t k);
-double estimate_covered_bases(const std::vector<AniResult>& results, const std::vector<GenomeSketch>& genomes, const SequencesSketch& S,
+double estimate_covered_bases(const std::vector<AniResult>& results, const std::vector<GenomeSketch>& genomes, uint64_t c, uint64_t total_counts,
                               double read_length, uint64_t k);
 // `inspect` (inspect.rs:117): YAML summary of *.syldb / *.sylsp files; host only
 struct InspectArgs {   // cmdline.rs:166-173
