@@ -1180,9 +1180,36 @@ def test_reassign_on_device_matches_reference_semantics(ctx):
     db.close()
 
 
+def assert_reassigned(result, genomes, tracked, smap, passing, ani, tag=None):
+    """one sylph_db_reassign_view result (contain_count, cov_off, covs, kmers_lost) against a direct restatement of winner_table + the
+    winner pass (contain.rs:410-430, :637-646): every genome's kept coverages and kmers_lost"""
+    cc, off, covs, lost = result
+    winner = {}
+    for r, g in enumerate(passing):
+        for km in list(genomes[g].tolist()) + list(tracked[g].tolist()):
+            if km not in winner or ani[r] > winner[km][0]:
+                winner[km] = (ani[r], int(g))
+    pset = set(int(x) for x in passing)
+    for g in range(len(genomes)):
+        got = covs[int(off[g]):int(off[g + 1])]
+        if g not in pset:
+            assert cc[g] == 0 and len(got) == 0 and lost[g] == 0
+            continue
+        exp, exp_lost = [], 0
+        for km in genomes[g].tolist():
+            c = smap.get(km, 0)
+            if c == 0:
+                continue
+            if winner[km][1] != g:
+                exp_lost += 1
+            else:
+                exp.append(c)
+        assert cc[g] == len(exp) and lost[g] == exp_lost, (tag, g)
+        assert np.array_equal(got, np.sort(np.array(exp, dtype=np.uint32)))
+
+
 def check_reassign(ctx, genomes, tracked, sk, sc, rng, min_passing, min_lost):
-    """sylph_db_reassign_view over three passing lists (the first with every ANI tied) against a direct restatement of winner_table +
-    the winner pass (contain.rs:410-430, :637-646): every genome's kept coverages and kmers_lost"""
+    """sylph_db_reassign_view over three passing lists (the first with every ANI tied) against assert_reassigned's restatement"""
     G = len(genomes)
     db_k, goff = flat_db(genomes)
     t_k, toff = flat_db(tracked)
@@ -1192,30 +1219,9 @@ def check_reassign(ctx, genomes, tracked, sk, sc, rng, min_passing, min_lost):
     for trial in range(3):
         passing = rng.permutation(G)[: int(rng.integers(min_passing, G + 1))]
         ani = rng.choice([0.95, 0.96, 0.97, 0.97, 0.99], size=len(passing)) if trial else np.full(len(passing), 0.97)   # trial 0: all tied
-        winner = {}
-        for r, g in enumerate(passing):
-            for km in list(genomes[g].tolist()) + list(tracked[g].tolist()):
-                if km not in winner or ani[r] > winner[km][0]:
-                    winner[km] = (ani[r], int(g))
-        cc, off, covs, lost = db.reassign_view(sk, sc, passing, ani)
-        pset = set(int(x) for x in passing)
-        for g in range(G):
-            got = covs[int(off[g]):int(off[g + 1])]
-            if g not in pset:
-                assert cc[g] == 0 and len(got) == 0 and lost[g] == 0
-                continue
-            exp, exp_lost = [], 0
-            for km in genomes[g].tolist():
-                c = smap.get(km, 0)
-                if c == 0:
-                    continue
-                if winner[km][1] != g:
-                    exp_lost += 1
-                else:
-                    exp.append(c)
-            assert cc[g] == len(exp) and lost[g] == exp_lost, (trial, g)
-            assert np.array_equal(got, np.sort(np.array(exp, dtype=np.uint32)))
-        assert int(lost.sum()) > min_lost
+        result = db.reassign_view(sk, sc, passing, ani)
+        assert_reassigned(result, genomes, tracked, smap, passing, ani, trial)
+        assert int(result[3].sum()) > min_lost
     db.close()
 
 
@@ -1487,8 +1493,9 @@ def test_hit_row_assembly_paths(ctx):
     inside a wavefront), long rows (LDS histogram over the values), a batch whose largest count does not fit the histogram (4096
     and above: the sorted path of rounds 1-3 takes it, decided from the device word), a hit list that overflows its first buffer
     (probe + assembly run twice), row spaces of different sizes one after the other on the same database (batches of 1, 3, 1
-    tables: the counters and tickets must come back clean every time), and the same calls with SYLPH_HIP_HIT_SORT-style sorting
-    giving identical blocks is covered by every other contain test having passed on the old path in round 3."""
+    tables: the counters and tickets must come back clean every time).  The sorted path on ordinary inputs (SYLPH_HIP_HIT_SORT forcing
+    it for every batch) is run by tests/contain_edges_worker.py, a child process of tests/test_gpu_contain_edges.py; the thresholds
+    themselves (4095 / 4096, rows of 63 .. 65 and 255 .. 257 hits, tile and table counts) by that file."""
     rng = np.random.default_rng(404)
     thr = O.threshold(200)
     big = [np.unique(rng.integers(0, thr, size=n, dtype=np.uint64)) for n in (30_000, 12_000, 5_000)]
