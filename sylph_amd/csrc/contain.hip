@@ -306,10 +306,9 @@ static void probe_launch(sylph_db* db, const std::vector<SampleRef>& refs, const
     const uint64_t G = db->n_genomes;
     uint32_t* d_cnt = db->counter.as<uint32_t>();   // [0] = number of hits, [1] = largest count among the hits
     const int check_len = (double)db->min_glen < min_number_kmers;
-    SY_REQUIRE(cap < (1ull << 32), "more than 2^32-1 hits for one batch: split it");
+    SY_REQUIRE(hits_plan::fits(cap), "more than 2^32-1 hits for one batch: split it");
     db->hits.reserve(cap * 8);
-    if (db->cnt_dirty) SY_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));   // (the row assembly leaves the counter zeroed: hits.hip)
-    db->cnt_dirty = true;
+    if (db->cnt_dirty) SY_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));   // (the flag: finish_driver, from the plan's record)
     ScopedKernelTimer t(ctx, "probe");
 #define SY_LAUNCH_PROBE(I)                                                                                                                   \
     hipLaunchKernelGGL(probe_kernel<I>, dim3(std::min<uint32_t>((uint32_t)chunks, probe_grid())), dim3(PROBE_TPB), 0, ctx->stream,            \
@@ -318,47 +317,6 @@ static void probe_launch(sylph_db* db, const std::vector<SampleRef>& refs, const
     if (ilp == 4) SY_LAUNCH_PROBE(4); else if (ilp == 2) SY_LAUNCH_PROBE(2); else SY_LAUNCH_PROBE(1);
 #undef SY_LAUNCH_PROBE
     SY_HIP(hipGetLastError());
-}
-
-// A kernel that counts its hits into db->counter ([0] = hits, [1] = largest count), launched by launch(cap, attempt) with a hit array
-// of `cap` entries: waits for the two words and, when the array was too small, launches once more with room for all the hits.
-// Returns the number of hits.
-template <class L>
-static uint32_t launch_until_hits_fit(sylph_db* db, uint64_t cap, uint32_t* max_count, L&& launch) {
-    uint32_t hc[2] = {0, 0};
-    for (int attempt = 0; attempt < 2; attempt++) {
-        launch(cap, attempt);
-        db->ctx->read_back(hc, db->counter.p, 8);
-        if (hc[0] <= cap) break;
-        SY_REQUIRE(attempt == 0, "hit buffer overflow persisted");
-        cap = hc[0];
-    }
-    *max_count = hc[1];
-    return hc[0];
-}
-
-uint32_t probe_batch(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint32_t* max_count) {
-    uint64_t total = 0, ilp = 2;
-    RefPack pack{};
-    const uint64_t chunks = probe_prepare(db, refs, &total, &pack, &ilp);
-    *max_count = 0;
-    if (!chunks) return 0;
-    return launch_until_hits_fit(db, std::max<uint64_t>(total * 2, 1u << 20), max_count,
-                                 [&](uint64_t cap, int) { probe_launch(db, refs, pack, chunks, ilp, min_number_kmers, cap); });
-}
-
-bool probe_batch_async(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t want_cap, uint64_t* cap) {
-    sylph_ctx* ctx = db->ctx;
-    uint64_t total = 0, ilp = 2;
-    RefPack pack{};
-    const uint64_t chunks = probe_prepare(db, refs, &total, &pack, &ilp);
-    if (!chunks) return false;
-    *cap = std::max<uint64_t>(std::max<uint64_t>(total * 2, 1u << 20), want_cap);
-    probe_launch(db, refs, pack, chunks, ilp, min_number_kmers, *cap);
-    if (!db->ev_cnt) SY_HIP(hipEventCreateWithFlags(&db->ev_cnt, hipEventDisableTiming));
-    SY_HIP(hipMemcpyAsync((char*)ctx->pinned + 256, db->counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SY_HIP(hipEventRecord(db->ev_cnt, ctx->stream));
-    return true;
 }
 
 // copies the block assembled in db->res out — straight into pinned host memory (the db's own block or the caller's, which carries its
@@ -394,7 +352,7 @@ static void copy_out_rows(sylph_db* db, uint32_t n_hits, uint32_t width, uint64_
     if (db->row_filter && dst && !with_lost) { copy_out_candidates(db, n_hits, width, n_rows, dst); return; }
     if (dst) dst->cand = CandidateLayout();
     const ResultLayout lay(n_rows, n_hits, width, with_lost ? G : 0);
-    if (!dst) { db->lay = lay; db->last_rows = n_rows; dst = &db->h_block; }
+    if (!dst) dst = &db->h_block;
     dst->ensure(lay.end + 64);
     dst->lay = lay;
     char* h = (char*)dst->p;
@@ -445,73 +403,113 @@ static void finish_hits_sorted(sylph_db* db, uint32_t n_hits, uint32_t max_count
     copy_out_rows(db, n_hits, width, n_rows, with_lost, dst);
 }
 
-// Host-known hit count (the reassignment pass, the sharded exchange): row assembly when the values fit its histogram, else the
-// sorted path.
-void finish_hits(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_rows, uint32_t* cov_width, bool with_lost, HostBlock* dst) {
+// The hit finish: from "probe this" or "these many hits lie in db->hits" to the result block in `dst`, one loop over the plan
+// (hits_plan.h).  The plan names the step — probe, assemble, read the two words, probe once more with room for all the hits, the sorted
+// finish, copy out — from the road the job asks for and the verdict on the list's sizes; this function only carries the steps out,
+// and sets the database's two clean-on-entry flags from the plan's record behind every step.  SYLPH_HIP_HIT_SORT (A/B knob: the sorted
+// path of rounds 1-3 for every call) is read here and nowhere else.
+HitSizes finish_driver(sylph_db* db, const HitFinish& job) {
+    namespace hp = hits_plan;
     sylph_ctx* ctx = db->ctx;
-    SY_REQUIRE(n_rows < (1ull << 32) - 1, "too many result rows");
-    static const bool force_sorted = getenv("SYLPH_HIP_HIT_SORT") != nullptr;   // A/B knob: the sorted path of rounds 1-3
-    const ResultLayout lay0(n_rows, 0, 4, 0);
-    bool taken = false;
-    if (!force_sorted && n_rows) {
-        db->res.reserve(lay0.covs + (size_t)std::max<uint32_t>(n_hits, 1) * 4 + 64);
-        ScopedKernelTimer t(ctx, "assemble");
-        taken = launch_row_assembly(db, nullptr, n_hits, max_count, std::max<uint32_t>(n_hits, 1), n_rows, cov_width ? 1 : 0, db->res.as<char>(), lay0.covs,
-                                    lay0.ccount);
+    static const bool force_sorted = getenv("SYLPH_HIP_HIT_SORT") != nullptr;
+    const bool to_probe = job.probe.call != nullptr;
+    uint32_t n_hits = job.n_hits, max_count = job.max_count;
+    uint64_t cap = to_probe ? hp::first_capacity(job.total) : std::max<uint32_t>(n_hits, 1);
+    const ResultLayout lay0(job.n_rows, 0, 4, 0);
+    hp::State s = hp::start(to_probe, job.sizes, force_sorted, hp::geometry(job.n_rows, 1, 0).taken, job.finish, db->rc_dirty, db->cnt_dirty,
+                            hp::verdict(n_hits, max_count, (uint32_t)cap));
+    auto record = [&] { db->rc_dirty = s.rc_dirty; db->cnt_dirty = s.cnt_dirty; };
+    try {
+        for (;;) {
+            const hp::Step step = hp::next(s);
+            hp::Verdict answer = hp::Verdict::Rows;
+            switch (step) {
+            case hp::Step::RegrowProbe:
+                cap = n_hits;
+                [[fallthrough]];
+            case hp::Step::Probe:
+                job.probe.call(job.probe.self, cap, (int)s.probes);
+                if (hp::behind_probe(s)) {                       // the two words on their way to pinned memory, in front of the assembly
+                    if (!db->ev_cnt) SY_HIP(hipEventCreateWithFlags(&db->ev_cnt, hipEventDisableTiming));
+                    SY_HIP(hipMemcpyAsync((char*)ctx->pinned + 256, db->counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+                    SY_HIP(hipEventRecord(db->ev_cnt, ctx->stream));
+                }
+                break;
+            case hp::Step::Assemble: {
+                const bool behind = !s.read;                     // sizes from the device words; else the host's, in an array of just that size
+                const uint64_t room = behind ? cap : std::max<uint32_t>(n_hits, 1);
+                const hp::Geometry g = hp::geometry(job.n_rows, room, behind ? room / 2 : n_hits);
+                db->res.reserve(lay0.covs + (size_t)room * 4 + 64);
+                ScopedKernelTimer t(ctx, "assemble");
+                launch_row_assembly(db, g, behind ? db->counter.as<uint32_t>() : nullptr, n_hits, max_count, (uint32_t)room, job.cov_width ? 1 : 0,
+                                    db->res.as<char>(), lay0.covs, lay0.ccount);
+                break;
+            }
+            case hp::Step::ReadWords: {
+                uint32_t hc[2];
+                if (hp::behind_probe(s)) {
+                    SY_HIP(hipEventSynchronize(db->ev_cnt));     // (the assembly's kernels are still running)
+                    memcpy(hc, (const char*)ctx->pinned + 256, 8);
+                } else ctx->read_back(hc, db->counter.p, 8);
+                n_hits = hc[0];
+                max_count = hc[1];
+                answer = hp::verdict(n_hits, max_count, (uint32_t)cap);
+                break;
+            }
+            case hp::Step::Sorted:
+                // (host-known sizes that the row road turns down have always counted one empty "assemble" interval)
+                if (s.sizes == hp::Sizes::Host && !force_sorted && job.n_rows) { ScopedKernelTimer t(ctx, "assemble"); }
+                finish_hits_sorted(db, n_hits, max_count, job.n_rows, job.cov_width, job.with_lost, job.dst);
+                return HitSizes{n_hits, max_count};
+            case hp::Step::CopyOut: {
+                const uint32_t width = index_plan::coverage_width(job.cov_width != nullptr, max_count);
+                if (job.cov_width) *job.cov_width = width;
+                copy_out_rows(db, n_hits, width, job.n_rows, job.with_lost, job.dst);
+                return HitSizes{n_hits, max_count};
+            }
+            case hp::Step::Done:
+                return HitSizes{n_hits, max_count};
+            case hp::Step::Fail:
+                SY_REQUIRE(false, "hit buffer overflow persisted");
+            }
+            s = hp::after(s, step, answer);
+            record();
+        }
+    } catch (...) {
+        s = hp::failed(s);
+        record();
+        throw;
     }
-    if (!taken) { finish_hits_sorted(db, n_hits, max_count, n_rows, cov_width, with_lost, dst); return; }
-    const uint32_t width = index_plan::coverage_width(cov_width != nullptr, max_count);
-    if (cov_width) *cov_width = width;
-    copy_out_rows(db, n_hits, width, n_rows, with_lost, dst);
 }
 
-uint32_t probe_and_finish(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t n_rows, uint32_t* cov_width, HostBlock* dst) {
-    sylph_ctx* ctx = db->ctx;
+// "probe these refs": the driver over probe_launch
+static HitSizes drive_refs(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, HitFinish job) {
+    uint64_t total = 0, ilp = 2;
+    RefPack pack{};
+    const uint64_t chunks = refs.empty() ? 0 : probe_prepare(db, refs, &total, &pack, &ilp);
+    auto launch = [&](uint64_t cap, int) { probe_launch(db, refs, pack, chunks, ilp, min_number_kmers, cap); };
+    if (chunks) { job.probe = ProbeStep(launch); job.total = total; }
+    return finish_driver(db, job);
+}
+
+uint32_t probe_batch(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint32_t* max_count) {
+    HitFinish job;
+    job.finish = false;
+    const HitSizes z = drive_refs(db, refs, min_number_kmers, job);
+    *max_count = z.max_count;
+    return z.n_hits;
+}
+
+// Probe + finish of a batch of device-resident tables into `dst` (nullptr: the database's block): the assembly runs behind the probe,
+// without a host round trip between them.  Returns the number of hits.
+static uint32_t contain_refs(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t n_rows, uint32_t* cov_width, HostBlock* dst) {
     SY_REQUIRE(n_rows < (1ull << 32) - 1, "too many result rows");
-    static const bool force_sorted = getenv("SYLPH_HIP_HIT_SORT") != nullptr;
-    if (force_sorted || !n_rows) {
-        uint32_t max_count = 0;
-        const uint32_t n_hits = refs.empty() ? 0 : probe_batch(db, refs, min_number_kmers, &max_count);
-        finish_hits_sorted(db, n_hits, max_count, n_rows, cov_width, false, dst);
-        return n_hits;
-    }
-    const ResultLayout lay0(n_rows, 0, 4, 0);
-    uint64_t want_cap = 0;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        uint64_t cap = 0;
-        const bool probed = !refs.empty() && probe_batch_async(db, refs, min_number_kmers, want_cap, &cap);
-        if (!probed) {   // nothing to probe: an all-zero block through the same kernels (host-known: no hits)
-            finish_hits(db, 0, 0, n_rows, cov_width, false, dst);
-            return 0;
-        }
-        db->res.reserve(lay0.covs + (size_t)cap * 4 + 64);
-        bool taken;
-        {
-            ScopedKernelTimer t(ctx, "assemble");
-            taken = launch_row_assembly(db, db->counter.as<uint32_t>(), 0, 0, (uint32_t)cap, n_rows, cov_width ? 1 : 0, db->res.as<char>(), lay0.covs, lay0.ccount);
-        }
-        SY_HIP(hipEventSynchronize(db->ev_cnt));             // the two counter words (the kernels above are still running)
-        uint32_t hc[2];
-        memcpy(hc, (const char*)ctx->pinned + 256, 8);
-        const uint32_t n_hits = hc[0], max_count = hc[1];
-        if (n_hits > cap) {                                   // the hit array was too small: once more with room for all of them
-            SY_REQUIRE(attempt == 0, "hit buffer overflow persisted");
-            db->rc_dirty = true;                              // (the assembly kernels bailed out half-way: counters are not clean)
-            want_cap = n_hits;
-            continue;
-        }
-        if (!taken || max_count >= row_assembly_max_value()) {   // values beyond the LDS histogram: the sorted path, from the same hit list
-            db->rc_dirty = true;
-            finish_hits_sorted(db, n_hits, max_count, n_rows, cov_width, false, dst);
-            return n_hits;
-        }
-        db->cnt_dirty = false;                                // rows_sort_kernel's last workgroup zeroes the counter
-        const uint32_t width = index_plan::coverage_width(cov_width != nullptr, max_count);
-        if (cov_width) *cov_width = width;
-        copy_out_rows(db, n_hits, width, n_rows, false, dst);
-        return n_hits;
-    }
-    return 0;
+    HitFinish job;
+    job.sizes = hits_plan::Sizes::Device;
+    job.n_rows = n_rows;
+    job.cov_width = cov_width;
+    job.dst = dst;
+    return drive_refs(db, refs, min_number_kmers, job).n_hits;
 }
 
 }  // namespace sylph
@@ -528,7 +526,6 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
     SY_REQUIRE(db->world == 1, "this database is one shard of %u: use sylph_db_contain_batch_sharded", db->world);
     sylph_ctx* ctx = db->ctx;
     const uint64_t G = db->n_genomes;
-    uint32_t n_hits = 0, max_count = 0;
     const uint64_t* d_k = sample_kmers;
     const uint32_t* d_c = sample_counts;
     if (n && mem == SYLPH_MEM_HOST) {
@@ -544,7 +541,7 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
         if (n) SY_REQUIRE(d_k && d_c, "null sample");
         std::vector<SampleRef> refs(1);
         refs[0].k = d_k; refs[0].c = d_c; refs[0].n = n;
-        return probe_and_finish(db, refs, min_number_kmers, G, cov_width, nullptr);
+        return contain_refs(db, refs, min_number_kmers, G, cov_width, nullptr);
     }
     // rank[g] = position of genome g in the passing list (or ~0), ani[rank], lost[g] = 0
     SY_REQUIRE(re->n_passing == 0 || (re->passing_gids && re->passing_ani), "null passing list");
@@ -560,25 +557,30 @@ static uint32_t contain_impl(sylph_db* db, const uint64_t* sample_kmers, const u
     ctx->h2d(db->rank_of.p, rank.data(), rank.size() * 4);
     if (re->n_passing) ctx->h2d(db->ani.p, re->passing_ani, (size_t)re->n_passing * 8);
     SY_HIP(hipMemsetAsync(db->lost.p, 0, rank.size() * 4, ctx->stream));
+    // the pass's launch is the driver's probe step: it counts into the probe's two words, and the host waits for them
+    uint32_t* d_cnt = db->counter.as<uint32_t>();
+    auto launch = [&](uint64_t cap, int attempt) {
+        SY_REQUIRE(hits_plan::fits(cap), "more than 2^32-1 hits for one sample");
+        db->hits.reserve(cap * 8);
+        SY_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
+        if (attempt) SY_HIP(hipMemsetAsync(db->lost.p, 0, std::max<uint64_t>(1, G) * 4, ctx->stream));
+        ScopedKernelTimer t(ctx, "probe");
+        hipLaunchKernelGGL(reassign_kernel, dim3(std::min<uint32_t>(grid_for64(n, PROBE_TPB), probe_grid())), dim3(PROBE_TPB), 0, ctx->stream,
+                           d_k, d_c, (uint32_t)n, db->kept.view(), db->tracked.view(), db->tracked.n_postings ? 1 : 0,
+                           db->rank_of.as<uint32_t>(), db->ani.as<double>(), db->lost.as<uint32_t>(), db->hits.as<uint64_t>(),
+                           (uint32_t)cap, d_cnt);
+        SY_HIP(hipGetLastError());
+    };
+    HitFinish job;
+    job.n_rows = G;
+    job.cov_width = cov_width;
+    job.with_lost = true;
     if (n && db->kept.n_postings && re->n_passing) {
         SY_REQUIRE(d_k && d_c, "null sample");
-        uint32_t* d_cnt = db->counter.as<uint32_t>();
-        n_hits = launch_until_hits_fit(db, std::max<uint64_t>(n * 2, 1u << 20), &max_count, [&](uint64_t cap, int attempt) {
-            SY_REQUIRE(cap < (1ull << 32), "more than 2^32-1 hits for one sample");
-            db->hits.reserve(cap * 8);
-            SY_HIP(hipMemsetAsync(d_cnt, 0, 8, ctx->stream));
-            db->cnt_dirty = true;                             // (this pass counts into the probe's words and nobody zeroes them after it)
-            if (attempt) SY_HIP(hipMemsetAsync(db->lost.p, 0, std::max<uint64_t>(1, G) * 4, ctx->stream));
-            ScopedKernelTimer t(ctx, "probe");
-            hipLaunchKernelGGL(reassign_kernel, dim3(std::min<uint32_t>(grid_for64(n, PROBE_TPB), probe_grid())), dim3(PROBE_TPB), 0, ctx->stream,
-                               d_k, d_c, (uint32_t)n, db->kept.view(), db->tracked.view(), db->tracked.n_postings ? 1 : 0,
-                               db->rank_of.as<uint32_t>(), db->ani.as<double>(), db->lost.as<uint32_t>(), db->hits.as<uint64_t>(),
-                               (uint32_t)cap, d_cnt);
-            SY_HIP(hipGetLastError());
-        });
+        job.probe = ProbeStep(launch);
+        job.total = n;
     }
-    finish_hits(db, n_hits, max_count, G, cov_width, true);
-    return n_hits;
+    return finish_driver(db, job).n_hits;
 }
 
 uint32_t sylph::contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples, uint32_t n_samples, int mem, double min_number_kmers,
@@ -620,7 +622,7 @@ uint32_t sylph::contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples
     } else {
         for (uint32_t s = 0; s < n_samples; s++) { refs[s].k = samples[s].kmers; refs[s].c = samples[s].counts; refs[s].n = samples[s].n; }
     }
-    const uint32_t n_hits = probe_and_finish(db, refs, min_number_kmers, (uint64_t)n_samples * db->n_genomes, cov_width, dst);
+    const uint32_t n_hits = contain_refs(db, refs, min_number_kmers, (uint64_t)n_samples * db->n_genomes, cov_width, dst);
     fill_views(dst ? *dst : db->h_block, views);
     return n_hits;
 }
@@ -688,7 +690,7 @@ int sylph_db_reassign_view(sylph_db* db, const uint64_t* sample_kmers, const uin
         ReassignArgs re{passing_gids, passing_ani, n_passing};
         const uint32_t n_hits = contain_impl(db, sample_kmers, sample_counts, n, mem, 0.0, &re);
         own_views(db, cov_off, contain_count, covs);
-        *kmers_lost = (const uint32_t*)((const char*)db->h_block.p + db->lay.lost);
+        *kmers_lost = (const uint32_t*)((const char*)db->h_block.p + db->h_block.lay.lost);
         if (out_n_covs) *out_n_covs = n_hits;
     });
 }

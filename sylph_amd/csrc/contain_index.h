@@ -3,6 +3,7 @@
 // index's arithmetic is index_plan.h.  Internal, not part of the ABI.
 #pragma once
 #include "common.h"
+#include "hits_plan.h"
 #include "index_plan.h"
 #include "row_stats_plan.h"
 
@@ -274,16 +275,13 @@ struct sylph_db {
     // per-query scratch (owned by the db so concurrent dbs on one ctx do not alias)
     sylph::DevBuf q_kmers, q_counts, q_refs, hits, hits_sorted, res, counter;   // res: device copy of the result block
     sylph::DevBuf x_send, x_recv, x_meta;    // shard exchange buffers (shard.hip)
-    // row assembly of the hits (hits.hip): replicated row counters + tile offsets / tickets / row lists.  The kernels leave the
-    // counters (and the probe's hit counter) zeroed; *_dirty = they must be cleared before the next use (first use, a fallback
-    // batch, a failure half-way)
+    // row assembly of the hits (hits.hip): row counters (rc_rows of them) + tile totals / snapshot / row lists.  *_dirty = the counters
+    // / the probe's two counter words must be cleared before their next use: the record of hits_plan.h, kept by finish_driver
     sylph::DevBuf row_counters, row_meta;
     bool rc_dirty = true, cnt_dirty = true;
-    uint32_t rc_rep = 0, rc_rows = 0;
+    uint32_t rc_rows = 0;
     hipEvent_t ev_cnt = nullptr;             // "the probe's counter words have arrived in pinned host memory"
-    sylph::ResultLayout lay;                 // layout of the last result
     const sylph::row_stats_plan::Filter* row_filter = nullptr;   // for the length of one contain_batch_impl call: summarise the rows, copy out the candidates only
-    uint64_t last_rows = 0;
     sylph::HostBlock h_block;                // pinned host results of the plain entry points (the pipeline brings its own blocks)
     explicit sylph_db(sylph_ctx* cx)
         : ctx(cx), kept(cx), tracked(cx), glen(cx), rank_of(cx), ani(cx), lost(cx), q_kmers(cx), q_counts(cx), q_refs(cx), hits(cx),
@@ -296,28 +294,36 @@ namespace sylph {
 // kept index and leaves unsorted hits ((row << 32) | count, row = sample * n_genomes + genome) in db->hits.
 // Returns the number of hits; *max_count = largest count among them.
 uint32_t probe_batch(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint32_t* max_count);
-// The same without waiting for the counts: launches the probe (hit array of *cap entries, grown to fit `want_cap`), queues the copy of
-// the two counter words [hits, largest count] into the context's pinned page (+256) and records db->ev_cnt behind it.  Returns
-// false when there is nothing to probe (no k-mers, empty index): the counts are 0 then and nothing was launched.
-bool probe_batch_async(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t want_cap, uint64_t* cap);
 // hits.hip: hit list in db->hits -> cov_off / contain_count / per-row ascending coverage values in the device result block, five
-// launches, sizes from device memory (d_cnt) or from the host (n_imm, max_imm).  false = not taken (nothing launched).
-bool launch_row_assembly(sylph_db* db, const uint32_t* d_cnt, uint32_t n_imm, uint32_t max_imm, uint32_t cap, uint64_t n_rows, int want_narrow,
-                         char* d_res, size_t covs_offset, size_t ccount_offset);
-uint32_t row_assembly_max_value();
-// Probe + assembly of a batch of device-resident tables (refs) into `dst` (nullptr: the database's block) without a host round trip
-// between the probe and the assembly.  Returns the number of hits.
-uint32_t probe_and_finish(sylph_db* db, std::vector<SampleRef>& refs, double min_number_kmers, uint64_t n_rows, uint32_t* cov_width,
-                          HostBlock* dst);
-// Sorts n_hits hits of db->hits (rows < n_rows) and assembles + copies out the result block (layout db->lay) into `dst`
-// (nullptr: the database's own block).
-void finish_hits(sylph_db* db, uint32_t n_hits, uint32_t max_count, uint64_t n_rows, uint32_t* cov_width, bool with_lost,
-                 HostBlock* dst = nullptr);
+// launches over a geometry that is taken, sizes from device memory (d_cnt) or from the host (n_imm, max_imm).
+void launch_row_assembly(sylph_db* db, const hits_plan::Geometry& g, const uint32_t* d_cnt, uint32_t n_imm, uint32_t max_imm, uint32_t cap,
+                         int want_narrow, char* d_res, size_t covs_offset, size_t ccount_offset);
+// The hit finish (contain.hip finish_driver, planned by hits_plan.h): what one call of it is to do.
+struct ProbeStep {                   // a caller's launch(cap, attempt), by reference: fills db->hits (cap entries), counts into db->counter
+    void* self = nullptr;
+    void (*call)(void*, uint64_t, int) = nullptr;
+    ProbeStep() = default;
+    template <class L>
+    explicit ProbeStep(L& launch) : self(&launch), call([](void* p, uint64_t cap, int attempt) { (*static_cast<L*>(p))(cap, attempt); }) {}
+};
+struct HitFinish {
+    ProbeStep probe;                 // empty: n_hits hits with a largest count of max_count lie in db->hits already
+    uint64_t total = 0;              // the sample k-mers the probe walks (sizes its first hit array)
+    hits_plan::Sizes sizes = hits_plan::Sizes::Host;   // Device: assemble behind the probe, sizes from its two words
+    uint32_t n_hits = 0, max_count = 0;
+    bool finish = true;              // false: the hit list only
+    uint64_t n_rows = 0;             // rows of the result block (hits of rows beyond it are dropped) into `dst` (nullptr: the database's own)
+    uint32_t* cov_width = nullptr;
+    bool with_lost = false;
+    HostBlock* dst = nullptr;
+};
+struct HitSizes { uint32_t n_hits, max_count; };
+HitSizes finish_driver(sylph_db* db, const HitFinish& job);
 // The bodies of sylph_db_contain_batch / sylph_db_contain_batch_sharded (they take the context lock themselves); the result
 // block lands in `dst` (nullptr: the database's own).  Return the number of coverage values.
 // `views` (optional): the three result pointers into the block the call filled, taken while the context lock is still held —
 // a pipeline's profile thread working on the same database between the lock's release and the caller's own look at
-// db->lay / db->h_block would otherwise hand the caller somebody else's layout.
+// db->h_block would otherwise hand the caller somebody else's layout.
 // `row_filter` (optional, with `dst`): the rows are summarised on the device and only the candidates land in `dst` (dst->cand).
 struct ResultViews { const uint64_t* cov_off = nullptr; const uint32_t* contain_count = nullptr; const void* covs = nullptr; };
 uint32_t contain_batch_impl(sylph_db* db, const sylph_sample_ref* samples, uint32_t n_samples, int mem, double min_number_kmers,

@@ -24,41 +24,36 @@
 //                        (consecutive lanes, consecutive bytes: one lane writing a bin's thousand copies byte by byte took 0.8 ms);
 //                        re-zeroes the row's cursor and, at the very end, the probe's hit counter
 //
-// Every launch takes the list's length from DEVICE memory (the word the probe counted into): the host reads that word with an
-// asynchronous copy while these kernels run and only needs it to size the final device -> host copy.  5 dispatches instead of 14,
-// no memset, no round trip in front of them, no "last workgroup" tickets (512 workgroups taking a ticket on one word cost 0.06 ms).  Values of 4096 and above (a k-mer seen thousands of times) do not fit the LDS
-// histogram: such a batch — decided from the same device word, the same way on both sides — goes through the sorted path of rounds
-// 1-3 (finish_hits_sorted, contain.hip), which stays the fallback.
+// Behind a probe every launch takes the list's length from DEVICE memory (the word the probe counted into): the host reads that word
+// with an asynchronous copy while these kernels run and only needs it to size the final device -> host copy.  5 dispatches instead of
+// 14, no memset, no round trip in front of them, no "last workgroup" tickets (512 workgroups taking a ticket on one word cost 0.06 ms).
+//
+// The plan is hits_plan.h: the constants, where a row's counter and a workgroup's stretch lie, the geometry of one assembly, and
+// verdict() — whether a hit list is one for these kernels (Rows), for the sorted finish of rounds 1-3 (values of 4096 and above do
+// not fit the LDS histogram) or must be probed again into a larger array.  rows_sum_kernel writes that verdict into snap[2] and the
+// later kernels obey it; the host's driver (contain.hip finish_driver) calls the same function on the same two numbers.
 #include "contain_index.h"
 
 namespace sylph {
 
 namespace {
 
-constexpr int ROWS_TPB = 256, ROWS_PER_THREAD = 8, ROWS_TILE = ROWS_TPB * ROWS_PER_THREAD;
-constexpr uint32_t SMALL_ROW = 64;            // rows up to one wavefront of values are ranked by shuffles
-constexpr uint32_t MAX_VALUE_LDS = 4096;      // rows_sort_kernel's histogram: values below this
+using namespace hits_plan;
 
 struct HitsSrc {                 // where the list's length / largest value come from
     const uint32_t* d_cnt;       // device words [n_hits, max_count] (the probe's counter), or nullptr:
     uint32_t n_imm, max_imm;     // host-known values
     uint32_t cap;                // entries the hit array holds (a probe that overflowed counted more than it stored)
 };
-__device__ __forceinline__ uint32_t src_n(const HitsSrc& s) { return min(s.d_cnt ? s.d_cnt[0] : s.n_imm, s.cap); }
+__device__ __forceinline__ uint32_t src_counted(const HitsSrc& s) { return s.d_cnt ? s.d_cnt[0] : s.n_imm; }
+__device__ __forceinline__ uint32_t src_n(const HitsSrc& s) { return min(src_counted(s), s.cap); }
 __device__ __forceinline__ uint32_t src_max(const HitsSrc& s) { return s.d_cnt ? s.d_cnt[1] : s.max_imm; }
-__device__ __forceinline__ bool src_overflowed(const HitsSrc& s) { return s.d_cnt && s.d_cnt[0] > s.cap; }
 
-// stretch hash: the hits of a workgroup's stretch of the list in an LDS table of HIT_SLOTS (row, count) entries (open addressing);
-// a stretch with more distinct rows than the table may hold sends the surplus hits straight to the global counters
-#ifndef SYLPH_HIT_SLOTS_LOG2
-#define SYLPH_HIT_SLOTS_LOG2 12
-#endif
-constexpr uint32_t HIT_SLOTS = 1u << SYLPH_HIT_SLOTS_LOG2, HIT_SLOTS_FULL = HIT_SLOTS * 3 / 4, SLOT_EMPTY_ROW = 0xFFFFFFFFu, NO_SLOT = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t hash_row(uint32_t row) { return (row * 2654435761u) >> (32 - SYLPH_HIT_SLOTS_LOG2); }   // top bits
-// -> the row's slot, claiming a free one.  Whether the table still takes NEW rows is decided between rounds of 256 hits, for the
-// whole workgroup at once (`frozen`): a row then either owns a slot — and EVERY hit of it in the stretch goes through the slot —
-// or never gets one, and every hit of it goes straight to the global counter; a hit-by-hit decision could turn one hit of a row
-// away and take the next (a round adds at most 256 rows, and the table freezes a quarter below its capacity)
+constexpr uint32_t SLOT_EMPTY_ROW = 0xFFFFFFFFu, NO_SLOT = 0xFFFFFFFFu;
+// -> the row's slot in the stretch table, claiming a free one.  Whether the table still takes NEW rows is decided between rounds of
+// 256 hits, for the whole workgroup at once (`frozen`): a row then either owns a slot — and EVERY hit of it in the stretch goes
+// through the slot — or never gets one, and every hit of it goes straight to the global counter; a hit-by-hit decision could turn
+// one hit of a row away and take the next (hits_plan.h asserts that a round cannot fill the table)
 __device__ __forceinline__ uint32_t table_claim(uint32_t* s_key, uint32_t* s_used, uint32_t row, bool frozen) {
     uint32_t slot = hash_row(row);
     for (uint32_t probes = 0; probes < HIT_SLOTS; probes++) {
@@ -85,14 +80,6 @@ __device__ __forceinline__ uint32_t table_find(const uint32_t* s_key, uint32_t r
     }
     return NO_SLOT;
 }
-// where the counter of a row lives: a bijection of [0, 2^m) that sends neighbouring rows to different cache lines
-__device__ __forceinline__ uint32_t rc_at(uint32_t row, uint32_t rc_mask) { return (row * 0x9E3779B1u) & rc_mask; }
-// the stretch of workgroup b: whole multiples of 256 hits
-__device__ __forceinline__ void stretch_of(uint32_t n, uint32_t& lo, uint32_t& hi) {
-    const uint32_t per = ((n + gridDim.x - 1) / gridDim.x + 255u) & ~255u;
-    lo = min(n, blockIdx.x * per);
-    hi = min(n, lo + per);
-}
 
 __global__ __launch_bounds__(256) void hits_count_kernel(const uint64_t* __restrict__ hits, HitsSrc src, uint32_t n_rows, uint32_t rc_mask,
                                                          uint32_t* __restrict__ rc, uint32_t* __restrict__ lists) {
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(256) void hits_count_kernel(const uint64_t* __restr
     if (blockIdx.x == 0 && threadIdx.x < 2) lists[threadIdx.x] = 0;      // (rows_scan_kernel appends to them: stream order)
     const uint32_t n = src_n(src);
     uint32_t lo, hi;
-    stretch_of(n, lo, hi);
+    stretch_of(n, gridDim.x, blockIdx.x, lo, hi);
     if (lo >= hi) return;
     for (uint32_t s = threadIdx.x; s < HIT_SLOTS; s += 256) { s_key[s] = SLOT_EMPTY_ROW; s_cnt[s] = 0; }
     if (threadIdx.x == 0) s_used = 0;
@@ -135,8 +122,8 @@ __device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t* s_w) {
     return s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
-// snap: [0] = entries of the hit list (clamped to the array), [1] = largest value, [2] = 1: not a batch for this path (a value
-// beyond the LDS histogram, or the probe overflowed its array) — what the later kernels read instead of the probe's live counter
+// snap: [0] = entries of the hit list (clamped to the array), [1] = largest value, [2] = 1: the verdict is not Rows — what the
+// later kernels read instead of the probe's live counter
 __global__ __launch_bounds__(ROWS_TPB) void rows_sum_kernel(const uint32_t* __restrict__ rc, uint32_t n_rows, uint32_t rc_mask,
                                                             uint32_t* __restrict__ tile_sum, HitsSrc src, uint32_t* __restrict__ snap) {
     __shared__ uint32_t s_w[4];
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(ROWS_TPB) void rows_sum_kernel(const uint32_t* __re
     if (t == 0 && threadIdx.x == 0) {
         snap[0] = src_n(src);
         snap[1] = src_max(src);
-        snap[2] = (src_max(src) >= MAX_VALUE_LDS || src_overflowed(src)) ? 1u : 0u;
+        snap[2] = verdict(src_counted(src), src_max(src), src.cap) != Verdict::Rows ? 1u : 0u;
     }
     uint32_t v = 0;
 #pragma unroll
@@ -232,7 +219,7 @@ __global__ __launch_bounds__(256) void hits_scatter_kernel(const uint64_t* __res
     if (snap[2]) return;                                              // the sorted path takes this batch (uniform over the grid)
     const uint32_t n = snap[0];
     uint32_t lo, hi;
-    stretch_of(n, lo, hi);
+    stretch_of(n, gridDim.x, blockIdx.x, lo, hi);
     if (lo >= hi) return;
     for (uint32_t s = threadIdx.x; s < HIT_SLOTS; s += 256) { s_key[s] = SLOT_EMPTY_ROW; s_cnt[s] = 0; }
     if (threadIdx.x == 0) s_used = 0;
@@ -274,7 +261,7 @@ __device__ __forceinline__ void store_cov(void* covs, uint32_t width, uint32_t a
 }
 
 // want_narrow: 1 = values stored with the narrowest of 1 / 2 / 4 bytes that holds the batch's largest one (the host applies the
-// same rule to the same word: finish_hits), 0 = always u32
+// same rule to the same word), 0 = always u32
 __global__ __launch_bounds__(256) void rows_sort_kernel(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ snap, uint32_t rc_mask,
                                                         uint32_t* __restrict__ rc, const uint64_t* __restrict__ cov_off,
                                                         const uint32_t* __restrict__ contain_count, const uint32_t* __restrict__ lists,
@@ -344,52 +331,36 @@ __global__ __launch_bounds__(256) void rows_sort_kernel(const uint32_t* __restri
 
 }  // namespace
 
-// Launches the five kernels for the hit list in db->hits.  d_cnt != nullptr: the list's length and largest value are the two
-// device words the probe counted into (the caller learns them from its asynchronous copy); else n_imm / max_imm.  Returns false —
-// having launched nothing — when the row path cannot take the batch for a reason the HOST can see (host-known largest value
-// beyond the LDS histogram).  Output: d_res filled per ResultLayout(n_rows, ., width, .) — cov_off, contain_count, and the
-// coverage values at their fixed offset — for any n_hits.
-bool launch_row_assembly(sylph_db* db, const uint32_t* d_cnt, uint32_t n_imm, uint32_t max_imm, uint32_t cap, uint64_t n_rows, int want_narrow,
+// Launches the five kernels for the hit list in db->hits over the geometry g (taken).  d_cnt != nullptr: the list's length and largest
+// value are the two device words the probe counted into (the caller learns them from its asynchronous copy); else n_imm / max_imm.
+// Output: d_res filled per ResultLayout(n_rows, ., width, .) — cov_off, contain_count, and the coverage values at their fixed offset
+// — for any n_hits.  The row counters must be all zero on entry: db->rc_dirty says whether they are (the driver keeps it from the
+// plan's record); only a reallocation is noticed here.
+void launch_row_assembly(sylph_db* db, const Geometry& g, const uint32_t* d_cnt, uint32_t n_imm, uint32_t max_imm, uint32_t cap, int want_narrow,
                          char* d_res, size_t covs_offset, size_t ccount_offset) {
     sylph_ctx* ctx = db->ctx;
-    if (!d_cnt && max_imm >= MAX_VALUE_LDS) return false;
-    if (n_rows == 0 || n_rows >= (1ull << 31)) return false;
-    const uint32_t R = (uint32_t)n_rows;
-    uint32_t R2 = 1024;                                        // counters: a power of two (rc_at is a bijection of [0, R2))
-    while (R2 < R) R2 <<= 1;
-    const uint32_t n_tiles = (R + ROWS_TILE - 1) / ROWS_TILE;
-    const uint32_t list_cap = (uint32_t)std::min<uint64_t>(R, std::max<uint32_t>(cap, 1));
-    const size_t rc_bytes = (size_t)R2 * 4, meta_bytes = ((size_t)n_tiles + 4 + 2 + list_cap) * 4 + 64;
-    // rc must be all zero on entry.  The kernels leave it that way; after a failure, a fallback batch or a reallocation it is cleared here.
-    if (db->row_counters.cap < rc_bytes || db->rc_rows != R2) { db->row_counters.reserve(rc_bytes); db->rc_dirty = true; }
-    if (db->row_meta.cap < meta_bytes) db->row_meta.reserve(meta_bytes);
+    if (db->row_counters.cap < g.rc_bytes || db->rc_rows != g.R2) { db->row_counters.reserve(g.rc_bytes); db->rc_dirty = true; }
+    if (db->row_meta.cap < g.meta_bytes) db->row_meta.reserve(g.meta_bytes);
     uint32_t* rc = db->row_counters.as<uint32_t>();
-    uint32_t* tile_sum = db->row_meta.as<uint32_t>();          // n_tiles
-    uint32_t* snap = tile_sum + n_tiles;                       // 4 words
-    uint32_t* lists = snap + 4;                                // [0], [1] lengths, then list_cap entries
-    if (db->rc_dirty) SY_HIP(hipMemsetAsync(rc, 0, rc_bytes, ctx->stream));
-    db->rc_dirty = true;                                       // until the chain below has been queued completely
-    db->rc_rows = R2;
+    uint32_t* tile_sum = db->row_meta.as<uint32_t>() + g.tile_sum_at;
+    uint32_t* snap = db->row_meta.as<uint32_t>() + g.snap_at;
+    uint32_t* lists = db->row_meta.as<uint32_t>() + g.lists_at;
+    if (db->rc_dirty) SY_HIP(hipMemsetAsync(rc, 0, g.rc_bytes, ctx->stream));
+    db->rc_rows = g.R2;
     db->hits_sorted.reserve((size_t)std::max<uint32_t>(cap, 1) * 4);   // the values, grouped by row, before they are sorted
     uint32_t* vals = db->hits_sorted.as<uint32_t>();
     const HitsSrc src{d_cnt, n_imm, max_imm, cap};
-    // a few dozen long stretches: the fewer workgroups, the fewer atomics per row counter (one per workgroup and distinct row)
-    const uint64_t n_guess = d_cnt ? (uint64_t)cap / 2 : n_imm;
-    const uint32_t hit_grid = (uint32_t)std::max<uint64_t>(16, std::min<uint64_t>(n_guess / 6144, 768));
     uint64_t* cov_off = reinterpret_cast<uint64_t*>(d_res);
     uint32_t* ccount = reinterpret_cast<uint32_t*>(d_res + ccount_offset);
     const uint64_t* hits = db->hits.as<uint64_t>();
-    hipLaunchKernelGGL(hits_count_kernel, dim3(hit_grid), dim3(256), 0, ctx->stream, hits, src, R, R2 - 1, rc, lists);
-    hipLaunchKernelGGL(rows_sum_kernel, dim3(n_tiles), dim3(ROWS_TPB), 0, ctx->stream, rc, R, R2 - 1, tile_sum, src, snap);
-    hipLaunchKernelGGL(rows_scan_kernel, dim3(n_tiles), dim3(ROWS_TPB), 0, ctx->stream, rc, R, R2 - 1, n_tiles, tile_sum, cov_off, ccount, lists, list_cap);
-    hipLaunchKernelGGL(hits_scatter_kernel, dim3(hit_grid), dim3(256), 0, ctx->stream, hits, snap, R, R2 - 1, rc, cov_off, vals);
-    hipLaunchKernelGGL(rows_sort_kernel, dim3(512), dim3(256), 0, ctx->stream, vals, snap, R2 - 1, rc, cov_off, ccount, lists, list_cap, want_narrow,
+    hipLaunchKernelGGL(hits_count_kernel, dim3(g.hit_grid), dim3(256), 0, ctx->stream, hits, src, g.R, g.rc_mask, rc, lists);
+    hipLaunchKernelGGL(rows_sum_kernel, dim3(g.n_tiles), dim3(ROWS_TPB), 0, ctx->stream, rc, g.R, g.rc_mask, tile_sum, src, snap);
+    hipLaunchKernelGGL(rows_scan_kernel, dim3(g.n_tiles), dim3(ROWS_TPB), 0, ctx->stream, rc, g.R, g.rc_mask, g.n_tiles, tile_sum, cov_off, ccount, lists,
+                       g.list_cap);
+    hipLaunchKernelGGL(hits_scatter_kernel, dim3(g.hit_grid), dim3(256), 0, ctx->stream, hits, snap, g.R, g.rc_mask, rc, cov_off, vals);
+    hipLaunchKernelGGL(rows_sort_kernel, dim3(512), dim3(256), 0, ctx->stream, vals, snap, g.rc_mask, rc, cov_off, ccount, lists, g.list_cap, want_narrow,
                        (void*)(d_res + covs_offset), const_cast<uint32_t*>(d_cnt));
     SY_HIP(hipGetLastError());
-    db->rc_dirty = false;
-    return true;
 }
-
-uint32_t row_assembly_max_value() { return MAX_VALUE_LDS; }
 
 }  // namespace sylph

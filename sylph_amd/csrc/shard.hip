@@ -470,7 +470,10 @@ uint32_t sylph::contain_batch_sharded_impl(sylph_db* db, sylph_comm* comm, const
         }
         ph.reset(); ph.reset(new HostPhase(ctx, "shard 6: sort + assemble + copy out"));
         // ---- 6. sort + assemble this rank's samples
-        finish_hits(db, n_mine, max_mine, (uint64_t)n_local * G, cov_width, false, dst);
+        HitFinish job;                                                     // host-known sizes
+        job.n_hits = n_mine; job.max_count = max_mine;
+        job.n_rows = (uint64_t)n_local * G; job.cov_width = cov_width; job.dst = dst;
+        finish_driver(db, job);
         fill_views(dst ? *dst : db->h_block, views);
         ph.reset();
         return n_mine;

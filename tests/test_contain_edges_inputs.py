@@ -26,7 +26,7 @@ def source(name):
 
 
 def test_the_constants_the_inputs_are_written_around():
-    hits, index, probe, plan = source("hits.hip"), source("contain_index.h"), source("contain.hip"), source("index_plan.h")
+    hits, index, probe, plan = source("hits_plan.h"), source("contain_index.h"), source("contain.hip"), source("index_plan.h")
     m = re.search(r"ROWS_TPB = (\d+), ROWS_PER_THREAD = (\d+), ROWS_TILE = ROWS_TPB \* ROWS_PER_THREAD;", hits)
     assert int(m.group(1)) * int(m.group(2)) == E.ROWS_TILE and int(m.group(1)) == 256        # (rows_scan_kernel's stride over the tiles)
     assert int(re.search(r"constexpr uint32_t SMALL_ROW = (\d+);", hits).group(1)) == E.SMALL_ROW

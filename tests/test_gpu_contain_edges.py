@@ -162,7 +162,7 @@ def reassign_path_checked(ctx, db, sk, sc, passing, ani, wide):
 
 @pytest.mark.parametrize("cap", [255, 256, 4095, 4096, 65536, 3_000_000_000])
 def test_reassignment_with_wide_counts(ctx, cap):
-    """finish_hits(with_lost) with a host-known largest count below and from 4096: kmers_lost sits behind a block whose layout follows
+    """finish_driver (with_lost) with a host-known largest count below and from 4096: kmers_lost sits behind a block whose layout follows
     the path and the width"""
     genomes, tracked, sk, sc = E.shared_core_db(cap)
     rng = np.random.default_rng(cap % 1000)

@@ -13,7 +13,7 @@ What each scenario would catch (a reader's map from a failure to the code):
   step 2 (nobody)              S_total == 0: no probe, empty collectives, empty results
   step 3 (64 tiny samples)     MAX_LOCAL's meta block; wave_take's leader loop when owner and row change inside a wavefront; slice_in_block's sums
   step 4 (one range)           zero-length blocks in both all-to-alls; all hits from one source rank
-  step 5 (counts)              plan_hits' max_mine per OWNER (the widths differ between ranks of one batch); finish_hits beyond 16 bits
+  step 5 (counts)              plan_hits' max_mine per OWNER (the widths differ between ranks of one batch); finish_driver beyond 16 bits
   step 7 (length filter)       glen[] of the WHOLE genome on a k-mer-range shard
   step 8 (failure)             plan_hits' first failed rank, the same verdict on every rank; state left behind for the next batch
 """
