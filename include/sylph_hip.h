@@ -176,6 +176,30 @@ int sylph_sketch_genomes(sylph_ctx *ctx, const uint8_t *bases, const uint64_t *c
                          uint64_t min_spacing, int pseudotax, int mem, uint64_t **out_kmers, uint64_t *kmer_off,
                          uint64_t **out_tracked, uint64_t *tracked_off);
 
+/* sketch_genome for ONE genome of 2^32 bases or more, which no single batch holds: the genome goes in pushes of whole contigs and
+ * the finish gives what sylph_sketch_genome gives for all contigs in one batch.  c, k, seed_mode, min_spacing and pseudotax are
+ * sylph_sketch_genome's.  The accumulator keeps its context alive; calls on it are serialised with the context's other calls. */
+typedef struct sylph_genome_acc sylph_genome_acc;
+int sylph_genome_acc_create(sylph_ctx *ctx, uint32_t c, uint32_t k, int seed_mode, uint64_t min_spacing, int pseudotax,
+                            sylph_genome_acc **out);
+/* The next n_contigs whole contigs of the genome: contig i = bases[contig_off[i], contig_off[i+1]), contig_off[0] == 0, offsets
+ * that do not decrease, fewer than 2^32 bases (for SYLPH_MEM_DEVICE: counted from `bases` rounded down to 16 bytes, and readable as
+ * for sylph_sketch_push); `mem` is SYLPH_MEM_HOST or SYLPH_MEM_DEVICE, the offsets are host memory.  The contigs are seeded and the
+ * valid seeds appended to arrays in HBM (16 bytes per seed, doubling as they fill); the bases are not kept and may be reused on
+ * return.  One accumulator holds at most 2^32-1 contigs and 2^32-2 seeds.  SYLPH_ERR_INVALID: a bad argument, a push that would
+ * cross one of these bounds, a push after the finish; SYLPH_ERR_NOMEM: no room on the device.  The accumulator is then as it was
+ * before the call.  Context option "genome_acc_first_capacity" (seeds; tests lower it) sets the arrays' first size. */
+int sylph_genome_acc_push(sylph_genome_acc *acc, const uint8_t *bases, const uint64_t *contig_off, uint64_t n_contigs, int mem);
+/* contigs, bases and valid seeds pushed so far (any of the three may be NULL) */
+int sylph_genome_acc_counts(const sylph_genome_acc *acc, uint64_t *n_contigs, uint64_t *n_bases, uint64_t *n_seeds);
+/* The genome-wide duplicate removal and the spacing filter over everything pushed (about 90 bytes of HBM per seed while it runs):
+ * genome_kmers in (contig, pos) order and, with pseudotax, the spacing's rejects in the same order, as sylph_sketch_genome returns
+ * them (out_tracked / n_tracked may be NULL); both arrays are released with sylph_free().  Once: after a finish that returned
+ * SYLPH_OK only sylph_genome_acc_destroy is valid (SYLPH_ERR_INVALID).  SYLPH_ERR_NOMEM leaves the accumulator as it was. */
+int sylph_genome_acc_finish(sylph_genome_acc *acc, uint64_t **out_kmers, uint64_t *n_kmers, uint64_t **out_tracked,
+                            uint64_t *n_tracked);
+void sylph_genome_acc_destroy(sylph_genome_acc *acc);
+
 /* ---- read sketching (one session = one sample) --------------------------------------------------------- */
 
 /* Replaces sketch_sequences_needle (sketch.rs:897-959) / sketch_pair_sequences (sketch.rs:771-895) after record

@@ -7,6 +7,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct SylphComm { _p: [u8; 0] }
 #[repr(C)] pub struct SylphFastq { _p: [u8; 0] }
 #[repr(C)] pub struct SylphFasta { _p: [u8; 0] }
+#[repr(C)] pub struct SylphGenomeAcc { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflated { _p: [u8; 0] }
 #[repr(C)] pub struct SylphInflateStream { _p: [u8; 0] }
 #[repr(C)] pub struct SylphBunzip2Stream { _p: [u8; 0] }
@@ -154,6 +155,12 @@ extern "C" {
     pub fn sylph_sketch_genomes_fasta(ctx: *mut SylphCtx, files: *const *mut SylphFasta, n_files: u32, individual: c_int, c: u32, k: u32,
                                       seed_mode: c_int, min_spacing: u64, pseudotax: c_int, out_kmers: *mut *mut u64, kmer_off: *mut u64,
                                       out_tracked: *mut *mut u64, tracked_off: *mut u64) -> c_int;
+    // one genome of 2^32 bases or more: whole contigs in pushes (each below 2^32 bases), one finish = sylph_sketch_genome of them all
+    pub fn sylph_genome_acc_create(ctx: *mut SylphCtx, c: u32, k: u32, seed_mode: c_int, min_spacing: u64, pseudotax: c_int, out: *mut *mut SylphGenomeAcc) -> c_int;
+    pub fn sylph_genome_acc_push(acc: *mut SylphGenomeAcc, bases: *const u8, contig_off: *const u64, n_contigs: u64, mem: c_int) -> c_int;
+    pub fn sylph_genome_acc_counts(acc: *const SylphGenomeAcc, n_contigs: *mut u64, n_bases: *mut u64, n_seeds: *mut u64) -> c_int;
+    pub fn sylph_genome_acc_finish(acc: *mut SylphGenomeAcc, out_kmers: *mut *mut u64, n_kmers: *mut u64, out_tracked: *mut *mut u64, n_tracked: *mut u64) -> c_int;
+    pub fn sylph_genome_acc_destroy(acc: *mut SylphGenomeAcc);
     // round 6: gzip inflated on the device (what flate2 does inside parse_fastx_file, sketch.rs:780-781 / :906): compressed bytes in,
     // text in HBM out (hand the pointer to sylph_fastq_index with MEM_DEVICE); ERR_FORMAT = -5: keep the flate2 reader for this file
     pub fn sylph_inflate(ctx: *mut SylphCtx, gz: *const c_void, n_bytes: u64, mem: c_int, out: *mut *mut SylphInflated) -> c_int;

@@ -42,6 +42,7 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
            "sylph_sketch_push_fasta", "sylph_fasta_index_window", "sylph_fasta_record_offset",
            "sylph_sketch_genomes_fasta",
+           "sylph_genome_acc_create", "sylph_genome_acc_push", "sylph_genome_acc_counts", "sylph_genome_acc_finish", "sylph_genome_acc_destroy",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
            "sylph_inflate_stream_open", "sylph_inflate_stream_next", "sylph_inflate_stream_info", "sylph_inflate_stream_destroy",
            "sylph_bunzip2", "sylph_bunzip2_files",
@@ -103,6 +104,12 @@ def load():
     L.sylph_fasta_record_offset.argtypes = [vp, u64, P(u64)]
     L.sylph_fasta_destroy.restype = None
     L.sylph_sketch_genomes_fasta.argtypes = [vp, P(vp), u32, i32, u32, u32, i32, u64, i32, P(vp), vp, P(vp), vp]
+    L.sylph_genome_acc_create.argtypes = [vp, u32, u32, i32, u64, i32, P(vp)]
+    L.sylph_genome_acc_push.argtypes = [vp, vp, vp, u64, i32]
+    L.sylph_genome_acc_counts.argtypes = [vp, P(u64), P(u64), P(u64)]
+    L.sylph_genome_acc_finish.argtypes = [vp, P(vp), P(u64), P(vp), P(u64)]
+    L.sylph_genome_acc_destroy.argtypes = [vp]
+    L.sylph_genome_acc_destroy.restype = None
     L.sylph_inflate.argtypes = [vp, vp, u64, i32, P(vp)]
     L.sylph_inflated_text.argtypes = [vp, P(vp), P(u64)]
     L.sylph_inflate_files.argtypes = [vp, P(vp), P(u64), C.c_uint32, i32, P(vp)]
@@ -315,6 +322,52 @@ class Context:
         _check(load().sylph_sketch_genomes_fasta(self._h, hs, len(files), int(bool(individual)), c, k, seed_mode, min_spacing, int(pseudotax),
                                                  C.byref(ok), _ptr(koff), C.byref(ot), _ptr(toff)))
         return _take(ok, int(koff[-1]), np.uint64), koff, _take(ot, int(toff[-1]), np.uint64), toff
+
+    # sketch_genome for one genome of 2^32 bases or more: whole contigs in pushes, one finish
+    def genome_acc(self, c=200, k=31, seed_mode=SEED_AVX2_COMPAT, min_spacing=30, pseudotax=True):
+        return GenomeAcc(self, c, k, seed_mode, min_spacing, pseudotax)
+
+
+class GenomeAcc:
+    """sylph_genome_acc: push(bases, contig_off) whole contigs of ONE genome, each push below 2^32 bases; finish() -> what
+    Context.sketch_genome gives for all of them in one batch (csrc/genome_acc.hip)."""
+
+    def __init__(self, ctx, c=200, k=31, seed_mode=SEED_AVX2_COMPAT, min_spacing=30, pseudotax=True):
+        self._h = C.c_void_p()
+        _check(load().sylph_genome_acc_create(ctx._h, c, k, seed_mode, min_spacing, int(pseudotax), C.byref(self._h)))
+
+    def push(self, bases, contig_off, device_ptr=None):
+        """`bases` is a host array, or pass device_ptr (int) with bases=None."""
+        off = _np(contig_off, np.uint64)
+        if device_ptr is None:
+            a = _bases(bases)
+            ptr, mem = (_ptr(a) if len(a) else None), MEM_HOST
+        else:
+            ptr, mem = C.c_void_p(int(device_ptr)), MEM_DEVICE
+        _check(load().sylph_genome_acc_push(self._h, ptr, _ptr(off), len(off) - 1, mem))
+
+    def counts(self):
+        """-> (contigs, bases, valid seeds) pushed so far"""
+        nc, nb, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(load().sylph_genome_acc_counts(self._h, C.byref(nc), C.byref(nb), C.byref(ns)))
+        return nc.value, nb.value, ns.value
+
+    def finish(self):
+        ok, ot, n, nt = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        gn_size = self.counts()[1]
+        _check(load().sylph_genome_acc_finish(self._h, C.byref(ok), C.byref(n), C.byref(ot), C.byref(nt)))
+        return dict(genome_kmers=_take(ok, n.value, np.uint64), tracked=_take(ot, nt.value, np.uint64), gn_size=gn_size)
+
+    def close(self):
+        if self._h:
+            load().sylph_genome_acc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # sylph_table_summary_t; flags: TABLE_SUMMARY_DECLINED | why

@@ -544,6 +544,10 @@ int sylph_ctx_set_option(sylph_ctx* ctx, const char* key, const char* value) {
             SY_HIP(hipExtStreamCreateWithCUMask(&ns, (uint32_t)mask.size(), mask.data()));
             (void)hipStreamDestroy(ctx->stream);
             ctx->stream = ns;
+        } else if (!strcmp(key, "genome_acc_first_capacity")) {
+            const long long v = strtoll(value, nullptr, 10);
+            SY_REQUIRE(v >= 0 && v <= (1ll << 32) - 2, "genome_acc_first_capacity must be 0 (the default) or a number of seeds up to 2^32-2");
+            ctx->genome_acc_first_capacity = (uint64_t)v;
         } else if (!strcmp(key, "index_pass_max")) {
             const long long v = strtoll(value, nullptr, 10);
             SY_REQUIRE(v >= 1 && v <= (1ll << 31), "index_pass_max must be in [1, 2^31]");

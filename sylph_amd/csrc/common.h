@@ -160,6 +160,7 @@ struct sylph_ctx {
     uint64_t inflate_whole_max_bytes = SYLPH_INFLATE_WHOLE_MAX_BYTES;   // "inflate_whole_max_bytes" (tests lower it): sylph_inflate_files declines this many gzip bytes or more
     uint64_t bunzip2_slice_bytes = 0;       // "bunzip2_slice_bytes" (tests lower it): compressed bytes per slice of a sylph_bunzip2_stream opened with slice_bytes 0; 0 = the default (bunzip2_stream_plan.h)
     uint64_t bunzip2_whole_max_bytes = ~0ull;   // "bunzip2_whole_max_bytes" (tests lower it): sylph_bunzip2_files declines this many bzip2 bytes or more; 0 = no limit, the default
+    uint64_t genome_acc_first_capacity = 0;  // "genome_acc_first_capacity" (tests lower it): seeds in a genome accumulator's first arrays; 0 = the default (genome_acc_plan.h FIRST_CAPACITY)
     uint32_t fail_next_peer_copy = 0;       // fault injection for the tests ("fail_next_peer_copy"): the next sylph_db_replicate INTO this context finds no device-to-device road
     uint32_t fail_next_shard_probe = 0;     // fault injection for the tests ("fail_next_shard_probe"): the next sharded probe on this context throws
     uint32_t index_lambda = 0;              // 0 = the default for the line size (contain_index.h DEFAULT_INDEX_LAMBDA: 4 per 64-byte line); postings per bucket line of a database index aimed for ("index_lambda"; r04: 3 -> 4, 38.5 -> 29.1 GB at GTDB scale for +3 % probe time alone)

@@ -131,8 +131,6 @@ __global__ __launch_bounds__(256) void genome_offsets_kernel(const uint32_t* __r
 
 }  // namespace
 
-struct GenomeBatchOut { std::vector<uint64_t> kmers, tracked, koff, toff; };
-
 void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* contig_off, uint64_t n_contigs,
                          const uint64_t* genome_contig_off, uint64_t n_genomes, uint32_t c, uint32_t k, int seed_mode,
                          uint64_t min_spacing, int pseudotax, int mem, uint64_t** out_kmers, uint64_t* kmer_off, uint64_t** out_tracked,
@@ -181,12 +179,10 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
     const uint32_t n = seeds.n;
     if (!n) { empty_out(); return; }
 
-    DevBuf b_key(ctx), b_key_s(ctx), b_idx(ctx), b_idx_s(ctx), b_contig(ctx), b_end(ctx), b_gid(ctx), b_live(ctx), b_lpos(ctx);
-    const size_t n1 = (size_t)n + 1;
-    b_key.reserve((size_t)n * 8); b_key_s.reserve((size_t)n * 8);
-    b_idx.reserve((size_t)n * 4); b_idx_s.reserve((size_t)n * 4);
+    DevBuf b_key(ctx), b_idx(ctx), b_contig(ctx), b_end(ctx), b_gid(ctx);
+    b_key.reserve((size_t)n * 8);
+    b_idx.reserve((size_t)n * 4);
     b_contig.reserve((size_t)n * 4); b_end.reserve((size_t)n * 4); b_gid.reserve((size_t)n * 4);
-    b_live.reserve(n1 * 4); b_lpos.reserve(n1 * 4);
     {
         ScopedKernelTimer t(ctx, "annotate");
         hipLaunchKernelGGL(annotate_genomes_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, d_off.as<uint64_t>(), n_contigs,
@@ -195,7 +191,22 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
                            b_idx.as<uint32_t>());
         SY_HIP(hipGetLastError());
     }
-    sort_pairs_u64_u32(ctx, b_key.as<uint64_t>(), b_key_s.as<uint64_t>(), b_idx.as<uint32_t>(), b_idx_s.as<uint32_t>(), n, 0, 64);
+    filter_annotated_genomes(ctx, AnnotatedSeeds{b_key.as<uint64_t>(), seeds.hash, b_contig.as<uint32_t>(), b_end.as<uint32_t>(),
+                                                 b_gid.as<uint32_t>(), b_idx.as<uint32_t>(), n},
+                             n_genomes, min_spacing, pseudotax, out_kmers, kmer_off, out_tracked, tracked_off);
+}
+
+// The duplicate removal, the spacing filter and the copy-out, for whoever has the annotated survivors: the batch above and the
+// accumulator's finish (genome_acc.hip).
+void filter_annotated_genomes(sylph_ctx* ctx, const AnnotatedSeeds& a, uint64_t n_genomes, uint64_t min_spacing, int pseudotax,
+                              uint64_t** out_kmers, uint64_t* kmer_off, uint64_t** out_tracked, uint64_t* tracked_off) {
+    const uint32_t n = a.n;
+    const size_t n1 = (size_t)n + 1;
+    DevBuf b_key_s(ctx), b_idx_s(ctx), b_live(ctx), b_lpos(ctx);
+    b_key_s.reserve((size_t)n * 8);
+    b_idx_s.reserve((size_t)n * 4);
+    b_live.reserve(n1 * 4); b_lpos.reserve(n1 * 4);
+    sort_pairs_u64_u32(ctx, a.key, b_key_s.as<uint64_t>(), a.idx, b_idx_s.as<uint32_t>(), n, 0, 64);
     DevBuf l_contig(ctx), l_end(ctx), l_gid(ctx), l_hash(ctx), b_kept(ctx), b_kpos(ctx), d_koff(ctx), d_toff(ctx);
     l_contig.reserve((size_t)n * 4); l_end.reserve((size_t)n * 4); l_gid.reserve((size_t)n * 4); l_hash.reserve((size_t)n * 8);
     b_kept.reserve(n1 * 4); b_kpos.reserve(n1 * 4);
@@ -208,14 +219,14 @@ void sketch_genomes_impl(sylph_ctx* ctx, const uint8_t* bases, const uint64_t* c
         SY_HIP(hipMemsetAsync(b_live.as<uint32_t>() + n, 0, 4, ctx->stream));   // scan sentinels
         SY_HIP(hipMemsetAsync(b_kept.p, 0, n1 * 4, ctx->stream));
         hipLaunchKernelGGL(genome_dup_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, b_key_s.as<uint64_t>(), b_idx_s.as<uint32_t>(),
-                           b_gid.as<uint32_t>(), n, b_live.as<uint32_t>());
+                           a.gid, n, b_live.as<uint32_t>());
     }
     exclusive_sum_u32(ctx, b_live.as<uint32_t>(), b_lpos.as<uint32_t>(), n1);
     const uint32_t* d_n_live = b_lpos.as<uint32_t>() + n;
     {
         ScopedKernelTimer t(ctx, "genome_filter");
         hipLaunchKernelGGL(compact_live_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, b_live.as<uint32_t>(), b_lpos.as<uint32_t>(),
-                           b_contig.as<uint32_t>(), b_end.as<uint32_t>(), b_gid.as<uint32_t>(), seeds.hash, n, l_contig.as<uint32_t>(),
+                           a.contig, a.end, a.gid, a.hash, n, l_contig.as<uint32_t>(),
                            l_end.as<uint32_t>(), l_gid.as<uint32_t>(), l_hash.as<uint64_t>());
         hipLaunchKernelGGL(spacing_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, l_contig.as<uint32_t>(), l_end.as<uint32_t>(),
                            d_n_live, min_spacing, b_kept.as<uint32_t>());

@@ -4,10 +4,22 @@
 #include <cstring>
 
 #include "host_internal.hpp"
+#include "../csrc/genome_acc_plan.h"
 
 namespace sylph_host {
 
-GenomeBatch::Parsed GenomeBatch::parse_file(const std::string& ref_file, bool individual) {
+namespace acc_plan = sylph::genome_acc_plan;
+
+uint64_t genome_push_limit() {
+    static const uint64_t limit = [] {
+        const char* e = getenv("SYLPH_HIP_GENOME_PUSH_BASES");
+        const long long v = e ? atoll(e) : 0;
+        return v > 0 && (uint64_t)v < acc_plan::PUSH_LIMIT ? (uint64_t)v : acc_plan::PUSH_LIMIT;
+    }();
+    return limit;
+}
+
+GenomeBatch::Parsed GenomeBatch::parse_file(const std::string& ref_file, bool /*individual: every record's id is kept either way*/) {
     Parsed p;
     p.file = ref_file;
     std::unique_ptr<FastxReader> reader;
@@ -16,7 +28,7 @@ GenomeBatch::Parsed GenomeBatch::parse_file(const std::string& ref_file, bool in
     FastxRecord rec;
     try {
         while (reader->next(rec)) {
-            if (individual || p.ids.empty()) p.ids.push_back(rec.id);
+            p.ids.push_back(rec.id);
             p.bases.insert(p.bases.end(), rec.seq.begin(), rec.seq.end());
             p.ends.push_back(p.bases.size());
         }
@@ -94,6 +106,11 @@ void GenomeBatch::add_window_device(const std::vector<std::string>& files, size_
         dv[i].file = files[lo + i];
         dv[i].text_bytes = bytes;
         hip_check(sylph_fasta_counts(f, &dv[i].n_records, &dv[i].n_bases, &dv[i].id_bytes), "sylph_fasta_counts");
+        // More than one batch: the host reader cuts it (append).  Such a file has been read, perhaps decoded, and indexed here for nothing
+        // and is read again there: the number of bases is not known before the index (the text's size bounds it only from above), and at
+        // the default limit the index declines a text that large by itself.  With SYLPH_HIP_GENOME_PUSH_BASES lowered, a node that expects
+        // mostly such files does better with the host road (SYLPH_HIP_FASTA_DEVICE unset).
+        if (dv[i].n_bases >= genome_push_limit()) { dv[i] = DeviceGenomeFile(); return; }
         ok[i] = 1;
     };
     auto decode = [&](Container c, size_t first, size_t count) {          // true: files [first, first + count) decoded and indexed
@@ -138,7 +155,7 @@ void GenomeBatch::add_window_device(const std::vector<std::string>& files, size_
     std::vector<Parsed> parsed(n);
     on_threads(host_files.size(), threads, [&](size_t j) { parsed[host_files[j]] = parse_file(files[lo + host_files[j]], individual); });
     // in file order; the batch of the other road is flushed first
-    constexpr uint64_t LIMIT = (1ull << 32) - 4096;
+    const uint64_t LIMIT = genome_push_limit();
     for (size_t i = 0; i < n; i++) {
         if (!ok[i]) { flush_device(); append(std::move(parsed[i]), individual); continue; }
         flush();
@@ -222,12 +239,12 @@ bool GenomeBatch::append(Parsed p, bool individual) {
     for (const auto& w : p.warnings) warn(w);
     if (!p.ok) return false;
     const std::string& ref_file = p.file;
-    // one sylph_sketch_genomes call holds < 2^32 bases: a file that would push the batch over the limit starts a new batch,
-    // and a single genome beyond it is skipped with a warning instead of aborting the whole run
-    constexpr uint64_t LIMIT = (1ull << 32) - 4096;
+    // one sylph_sketch_genomes call holds fewer than L bases: a file that would push the batch over the limit starts a new batch,
+    // and a file that holds L bases or more by itself is cut at its record boundaries
+    const uint64_t LIMIT = genome_push_limit();
     if (p.bases.size() >= LIMIT) {
-        warn(ref_file + " holds " + std::to_string(p.bases.size()) + " bases, more than one device batch (2^32): skipping it");
-        return false;
+        flush();
+        return individual ? append_split(p) : append_accumulated(p);
     }
     if (bases.size() + p.bases.size() >= LIMIT) flush();
     const uint64_t bases0 = bases.size();
@@ -253,23 +270,130 @@ bool GenomeBatch::append(Parsed p, bool individual) {
     return true;
 }
 
-void GenomeBatch::flush() {
-    if (pending.empty()) return;
-    const uint64_t G = pending.size();
+namespace {
+std::vector<uint64_t> record_lengths(const std::vector<uint64_t>& ends) {
+    std::vector<uint64_t> lens(ends.size());
+    for (size_t r = 0; r < ends.size(); r++) lens[r] = ends[r] - (r ? ends[r - 1] : 0);
+    return lens;
+}
+std::string over_limit(uint64_t n_bases) {
+    return " holds " + std::to_string(n_bases) + " bases, more than one device batch (" + std::to_string(genome_push_limit()) + ")";
+}
+}  // namespace
+
+// one genome per record: every run of the plan's cut is a batch of its own, in file order
+bool GenomeBatch::append_split(const Parsed& p) {
+    FeedLaps laps;
+    const uint64_t LIMIT = genome_push_limit();
+    const std::vector<uint64_t> lens = record_lengths(p.ends);
+    const uint64_t n = lens.size();
+    uint64_t batches = 0, skipped = 0;
+    auto batch = [&](const acc_plan::Run& run) {
+        const uint64_t base0 = run.first ? p.ends[run.first - 1] : 0;
+        std::vector<uint64_t> off_(run.n + 1, 0), goff_(run.n + 1, 0);
+        std::vector<GenomeSketch> names(run.n);
+        for (uint64_t i = 0; i < run.n; i++) {
+            off_[i + 1] = p.ends[run.first + i] - base0;
+            goff_[i + 1] = i + 1;
+            names[i].file_name = p.file; names[i].first_contig_name = p.ids[run.first + i]; names[i].gn_size = lens[run.first + i];
+        }
+        sketch_batch(p.bases.data() + base0, off_, goff_, names);
+        batches++;
+    };
+    for (uint64_t at = 0; at < n;) {
+        at = acc_plan::cut(lens.data(), n, at, LIMIT, batch);
+        if (at < n) {                                                     // a record no batch holds: the others are still sketched
+            warn(p.file + ": record " + p.ids[at] + over_limit(lens[at]) + ": skipping it");
+            skipped++;
+            at++;
+        }
+    }
+    if (FeedLaps::on()) {
+        const std::string what = "genomes split: " + p.file + " records=" + std::to_string(n) + " batches=" + std::to_string(batches) +
+                                 " skipped=" + std::to_string(skipped);
+        laps.lap(what.c_str());
+    }
+    return batches > 0;
+}
+
+// one genome per file: the runs of the plan's cut are pushed through an accumulator, whose finish removes the duplicates of the whole
+// file (sketch.rs:590-600) and runs the spacing filter, which restarts at every contig (:606)
+bool GenomeBatch::append_accumulated(const Parsed& p) {
+    FeedLaps laps;
+    const uint64_t LIMIT = genome_push_limit();
+    const std::vector<uint64_t> lens = record_lengths(p.ends);
+    const uint64_t n = lens.size();
+    std::vector<acc_plan::Run> runs;
+    const uint64_t misfit = acc_plan::cut(lens.data(), n, 0, LIMIT, [&](const acc_plan::Run& run) { runs.push_back(run); });
+    if (misfit < n) {   // positions inside a contig are 32-bit in the seeding kernels: the one difference from the reference left
+        warn(p.file + ": contig " + p.ids[misfit] + over_limit(lens[misfit]) + ": skipping the file");
+        return false;
+    }
+    sylph_genome_acc* h = nullptr;
+    hip_check(sylph_genome_acc_create(e.context(), (uint32_t)c, (uint32_t)k, SYLPH_SEED_AVX2_COMPAT, min_spacing, pseudotax ? 1 : 0, &h),
+              "sylph_genome_acc_create");
+    std::unique_ptr<sylph_genome_acc, void (*)(sylph_genome_acc*)> acc(h, sylph_genome_acc_destroy);
+    uint64_t pushes = 0;
+    int rc = SYLPH_OK;
+    const char* what = "sylph_genome_acc_push";
+    for (const acc_plan::Run& run : runs) {
+        if (rc != SYLPH_OK) break;
+        const uint64_t base0 = run.first ? p.ends[run.first - 1] : 0;
+        std::vector<uint64_t> off_(run.n + 1, 0);
+        for (uint64_t i = 0; i < run.n; i++) off_[i + 1] = p.ends[run.first + i] - base0;
+        rc = sylph_genome_acc_push(acc.get(), p.bases.data() + base0, off_.data(), run.n, SYLPH_MEM_HOST);
+        pushes++;
+    }
+    uint64_t *gk = nullptr, *tr = nullptr, nk = 0, nt = 0, n_seeds = 0;
+    if (rc == SYLPH_OK) {
+        hip_check(sylph_genome_acc_counts(acc.get(), nullptr, nullptr, &n_seeds), "sylph_genome_acc_counts");
+        what = "sylph_genome_acc_finish";
+        rc = sylph_genome_acc_finish(acc.get(), &gk, &nk, &tr, &nt);
+    }
+    if (rc == SYLPH_ERR_NOMEM) {
+        warn(p.file + ": no room on the device for the seeds of " + std::to_string(p.bases.size()) + " bases (" + what + "): skipping the file");
+        return false;
+    }
+    hip_check(rc, what);
+    struct Free { uint64_t* p; ~Free() { sylph_free(p); } } f1{gk}, f2{tr};
+    GenomeSketch s;
+    s.file_name = p.file;
+    if (!p.ids.empty()) s.first_contig_name = p.ids.front();
+    s.gn_size = p.bases.size();
+    s.genome_kmers.assign(gk, gk + nk);
+    if (pseudotax) s.pseudotax_tracked_nonused_kmers = std::vector<uint64_t>(tr, tr + nt);
+    s.c = c; s.k = k; s.min_spacing = min_spacing;
+    out.push_back(std::move(s));
+    if (FeedLaps::on()) {
+        const std::string line = "genomes accumulate: " + p.file + " contigs=" + std::to_string(n) + " bases=" + std::to_string(p.bases.size()) +
+                                 " pushes=" + std::to_string(pushes) + " seeds=" + std::to_string(n_seeds);
+        laps.lap(line.c_str());
+    }
+    return true;
+}
+
+void GenomeBatch::sketch_batch(const uint8_t* bases_, const std::vector<uint64_t>& off_, const std::vector<uint64_t>& goff_,
+                               std::vector<GenomeSketch>& names) {
+    const uint64_t G = names.size();
     std::vector<uint64_t> koff(G + 1), toff(G + 1);
     uint64_t *gk = nullptr, *tr = nullptr;
-    hip_check(sylph_sketch_genomes(e.context(), bases.data(), off.data(), off.size() - 1, goff.data(), G, (uint32_t)c, (uint32_t)k,
+    hip_check(sylph_sketch_genomes(e.context(), bases_, off_.data(), off_.size() - 1, goff_.data(), G, (uint32_t)c, (uint32_t)k,
                                    SYLPH_SEED_AVX2_COMPAT, min_spacing, pseudotax ? 1 : 0, SYLPH_MEM_HOST, &gk, koff.data(), &tr,
                                    toff.data()),
               "sylph_sketch_genomes");
     struct Free { uint64_t* p; ~Free() { sylph_free(p); } } f1{gk}, f2{tr};
     for (uint64_t g = 0; g < G; g++) {
-        GenomeSketch& s = pending[g];
+        GenomeSketch& s = names[g];
         s.genome_kmers.assign(gk + koff[g], gk + koff[g + 1]);
         if (pseudotax) s.pseudotax_tracked_nonused_kmers = std::vector<uint64_t>(tr + toff[g], tr + toff[g + 1]);
         s.c = c; s.k = k; s.min_spacing = min_spacing;
         out.push_back(std::move(s));
     }
+}
+
+void GenomeBatch::flush() {
+    if (pending.empty()) return;
+    sketch_batch(bases.data(), off, goff, pending);
     pending.clear(); bases.clear(); off.assign(1, 0); goff.assign(1, 0);
 }
 

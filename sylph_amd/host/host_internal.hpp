@@ -215,6 +215,9 @@ struct DeviceGenomeFile {
     std::unique_ptr<sylph_fasta, void (*)(sylph_fasta*)> fa{nullptr, sylph_fasta_destroy};
     uint64_t text_bytes = 0, n_records = 0, n_bases = 0, id_bytes = 0;
 };
+// The per-batch limit of bases, L: 2^32 - 4096 (csrc/genome_acc_plan.h PUSH_LIMIT), or a positive SYLPH_HIP_GENOME_PUSH_BASES below it (tests,
+// small-memory nodes).  A batch holds fewer bases than L; a file with L bases or more is cut at record boundaries (GenomeBatch::append).
+uint64_t genome_push_limit();
 // A batch of genomes sketched by ONE sylph_sketch_genomes call (seeding, genome-wide duplicate removal and the spacing
 // filter all run on the device; sketch.rs:550-622 / :481-548 per genome).  On the host road files are parsed on the host and appended
 // until the batch holds BATCH_BASES; on the device road (add_files) indexed files are collected and sketched by ONE
@@ -238,7 +241,7 @@ struct GenomeBatch {
         std::string file;
         std::vector<uint8_t> bases;
         std::vector<uint64_t> ends;                 // end of every record in `bases`
-        std::vector<std::string> ids;               // first record only unless `individual`
+        std::vector<std::string> ids;               // one per record (a warning about a record names it)
         std::vector<std::string> warnings;
         bool ok = false;
     };
@@ -247,8 +250,16 @@ struct GenomeBatch {
     bool add_file(const std::string& ref_file, bool individual) { return append(parse_file(ref_file, individual), individual); }
     // files [0, n) parsed on up to `threads` threads, a window of them at a time, appended (and flushed) in file order
     void add_files(const std::vector<std::string>& files, bool individual, uint64_t threads);
+    // A file below the batch limit joins the batch.  One of L bases or more (host_internal.hpp genome_push_limit) is cut into runs of
+    // whole records below L by the plan's greedy rule: one genome per record, each run is a batch of its own (append_split: a record
+    // of L bases or more is skipped, the others are sketched); one genome per file, the runs go through a device accumulator that
+    // removes duplicates over the whole file (append_accumulated: a contig of L bases or more refuses the file).
     bool append(Parsed p, bool individual);
+    bool append_split(const Parsed& p);
+    bool append_accumulated(const Parsed& p);
     void flush();
+    // one sylph_sketch_genomes call: genome g = contigs [goff_[g], goff_[g + 1]) of off_ over bases_; names[g] is filled and moved to `out`
+    void sketch_batch(const uint8_t* bases_, const std::vector<uint64_t>& off_, const std::vector<uint64_t>& goff_, std::vector<GenomeSketch>& names);
     // the device road: files [lo, lo + n) read by the threads, decoded and indexed by this thread; what the device declines is parsed on
     // the host as before.  A group of indexed files is bounded by BATCH_BASES bytes of text and by the batch limit of bases.
     std::vector<DeviceGenomeFile> dev_group;
