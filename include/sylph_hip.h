@@ -316,6 +316,28 @@ int sylph_fasta_index_window(sylph_ctx *ctx, const void *text, uint64_t n_bytes,
                              uint64_t *consumed);
 int sylph_fasta_record_offset(sylph_fasta *f, uint64_t record, uint64_t *offset);
 
+/* ---- INTERLEAVED paired reads: one text, mate 1, mate 2, mate 1, ... (csrc/interleave_plan.h) ------------------------------------
+ * An extension (the reference reads a pair from two files only).  Pair p of an index is its records 2 p and 2 p + 1; an index of n
+ * records holds n / 2 pairs, a last record without a mate belongs to none.  sylph_sketch_push_fast[aq]_interleaved sketch pairs
+ * [first_pair, first_pair + n_pairs) of ONE index into a PAIRED session: the session ends up exactly as after
+ * sylph_sketch_push_fast[aq](sk, a, b, first_pair, n_pairs) with a = the even records and b = the odd ones.  (Passing the same index as
+ * a and b to sylph_sketch_push_fast[aq] keeps meaning what it means: record i twice.)  Limits, SYLPH_ERR_NOMEM — returned before
+ * anything of the session is touched — and "borrow_until_finish" are sylph_sketch_push_fastq's; SYLPH_ERR_INVALID, with the session
+ * left as it was: a single-end session, 2 (first_pair + n_pairs) beyond the index's records, 2 n_pairs >= 2^31.
+ * sylph_fast[aq]_mates is the check that makes the format safe to accept — a file that lost one read to a filter is out of phase from
+ * there to its end.  The id of a record is its header line without the leading '@' / '>' up to, not including, the first space or tab
+ * (a '\r' or the line end ends it too).  The records of a pair are mates if their ids are equal, or if the first id ends in "/1", the
+ * second in "/2" and everything in front is equal; nothing else pairs ("SRR1.1" / "SRR1.2" are two spots).  *first_bad = the
+ * smallest i in [0, n_pairs) such that pair first_pair + i is not one of mates; n_pairs: all are.  The headers are read on the device,
+ * once, up to the step in which the ids end.
+ * A text that arrives in windows needs no further call: sylph_fast[aq]_index_window gives the complete records, n of them; the caller
+ * checks and pushes n / 2 pairs and keeps the text from sylph_fast[aq]_record_offset(2 (n / 2)), so a kept tail always begins at an even
+ * record.  The running mean of the read lengths is that of the mate-1 records, the even ones (sketch.rs:824-826). */
+int sylph_sketch_push_fastq_interleaved(sylph_sketch *sk, sylph_fastq *f, uint64_t first_pair, uint64_t n_pairs);
+int sylph_sketch_push_fasta_interleaved(sylph_sketch *sk, sylph_fasta *f, uint64_t first_pair, uint64_t n_pairs);
+int sylph_fastq_mates(sylph_fastq *f, uint64_t first_pair, uint64_t n_pairs, uint64_t *first_bad);
+int sylph_fasta_mates(sylph_fasta *f, uint64_t first_pair, uint64_t n_pairs, uint64_t *first_bad);
+
 /* ---- gzip inflated on the device (csrc/inflate.hip, round 6) ------------------------------------------------------------------
  * The reference's normal input is gzip (README.md:51): parse_fastx_file (sketch.rs:780-781, :906; :491, :562 for genomes) hands the
  * file to flate2 and inflates it on the calling thread.  sylph_inflate replaces that step: the COMPRESSED bytes of one file (host

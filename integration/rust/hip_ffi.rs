@@ -152,6 +152,12 @@ extern "C" {
     pub fn sylph_sketch_push_fasta(sk: *mut SylphSketch, a: *mut SylphFasta, b: *mut SylphFasta, first: u64, n_items: u64) -> c_int;   // FASTA-format reads: the twin of sylph_sketch_push_fastq
     pub fn sylph_fasta_index_window(ctx: *mut SylphCtx, text: *const c_void, n_bytes: u64, mem: c_int, is_final: c_int, out: *mut *mut SylphFasta, consumed: *mut u64) -> c_int;
     pub fn sylph_fasta_record_offset(f: *mut SylphFasta, record: u64, offset: *mut u64) -> c_int;   // where a record's '>' lies
+    // interleaved paired reads: pair p of ONE index = its records 2p and 2p+1, pushed to a PAIRED session; *_mates: the first pair of
+    // the range (counted from first_pair) whose ids are not those of mates (equal, or ".../1" and ".../2"), n_pairs if all are
+    pub fn sylph_sketch_push_fastq_interleaved(sk: *mut SylphSketch, f: *mut SylphFastq, first_pair: u64, n_pairs: u64) -> c_int;
+    pub fn sylph_sketch_push_fasta_interleaved(sk: *mut SylphSketch, f: *mut SylphFasta, first_pair: u64, n_pairs: u64) -> c_int;
+    pub fn sylph_fastq_mates(f: *mut SylphFastq, first_pair: u64, n_pairs: u64, first_bad: *mut u64) -> c_int;
+    pub fn sylph_fasta_mates(f: *mut SylphFasta, first_pair: u64, n_pairs: u64, first_bad: *mut u64) -> c_int;
     pub fn sylph_sketch_genomes_fasta(ctx: *mut SylphCtx, files: *const *mut SylphFasta, n_files: u32, individual: c_int, c: u32, k: u32,
                                       seed_mode: c_int, min_spacing: u64, pseudotax: c_int, out_kmers: *mut *mut u64, kmer_off: *mut u64,
                                       out_tracked: *mut *mut u64, tracked_off: *mut u64) -> c_int;

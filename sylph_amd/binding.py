@@ -41,6 +41,7 @@ EXPORTS = ["sylph_version", "sylph_last_error", "sylph_free", "sylph_pinned_allo
            "sylph_fastq_index", "sylph_fastq_index_window", "sylph_fastq_record_offset", "sylph_fastq_counts", "sylph_fastq_lengths", "sylph_sketch_push_fastq", "sylph_fastq_destroy",
            "sylph_fasta_index", "sylph_fasta_counts", "sylph_fasta_lengths", "sylph_fasta_ids", "sylph_fasta_bases", "sylph_fasta_destroy",
            "sylph_sketch_push_fasta", "sylph_fasta_index_window", "sylph_fasta_record_offset",
+           "sylph_sketch_push_fastq_interleaved", "sylph_sketch_push_fasta_interleaved", "sylph_fastq_mates", "sylph_fasta_mates",
            "sylph_sketch_genomes_fasta",
            "sylph_genome_acc_create", "sylph_genome_acc_push", "sylph_genome_acc_counts", "sylph_genome_acc_finish", "sylph_genome_acc_destroy",
            "sylph_inflate", "sylph_inflate_files", "sylph_inflated_file", "sylph_inflated_text", "sylph_inflated_info", "sylph_inflated_read", "sylph_inflated_destroy",
@@ -102,6 +103,10 @@ def load():
     L.sylph_sketch_push_fasta.argtypes = [vp, vp, vp, u64, u64]
     L.sylph_fasta_index_window.argtypes = [vp, vp, u64, i32, i32, P(vp), P(u64)]
     L.sylph_fasta_record_offset.argtypes = [vp, u64, P(u64)]
+    L.sylph_sketch_push_fastq_interleaved.argtypes = [vp, vp, u64, u64]
+    L.sylph_sketch_push_fasta_interleaved.argtypes = [vp, vp, u64, u64]
+    L.sylph_fastq_mates.argtypes = [vp, u64, u64, P(u64)]
+    L.sylph_fasta_mates.argtypes = [vp, u64, u64, P(u64)]
     L.sylph_fasta_destroy.restype = None
     L.sylph_sketch_genomes_fasta.argtypes = [vp, P(vp), u32, i32, u32, u32, i32, u64, i32, P(vp), vp, P(vp), vp]
     L.sylph_genome_acc_create.argtypes = [vp, u32, u32, i32, u64, i32, P(vp)]
@@ -635,6 +640,14 @@ class FastqText:
         _check(load().sylph_fastq_record_offset(self._h, int(record), C.byref(v)))
         return int(v.value)
 
+    def mates(self, first_pair=0, n_pairs=None):
+        """sylph_fastq_mates over pairs [first_pair, first_pair + n_pairs) of an interleaved text (pair p = records 2 p, 2 p + 1): the
+        first of them, counted from first_pair, whose records are not mates by their ids; n_pairs: all are"""
+        n_pairs = self.n_records // 2 - first_pair if n_pairs is None else n_pairs
+        v = C.c_uint64(0)
+        _check(load().sylph_fastq_mates(self._h, int(first_pair), int(n_pairs), C.byref(v)))
+        return int(v.value)
+
     def close(self):
         if self._h:
             load().sylph_fastq_destroy(self._h)
@@ -701,6 +714,13 @@ class FastaText:
         """sylph_fasta_record_offset: where the record's '>' lies in the text; record == n_records: where the text behind the records begins"""
         v = C.c_uint64(0)
         _check(load().sylph_fasta_record_offset(self._h, int(record), C.byref(v)))
+        return int(v.value)
+
+    def mates(self, first_pair=0, n_pairs=None):
+        """sylph_fasta_mates: as FastqText.mates"""
+        n_pairs = self.n_records // 2 - first_pair if n_pairs is None else n_pairs
+        v = C.c_uint64(0)
+        _check(load().sylph_fasta_mates(self._h, int(first_pair), int(n_pairs), C.byref(v)))
         return int(v.value)
 
     def close(self):
@@ -775,6 +795,15 @@ class ReadSketcher:
         if n_items is None:
             n_items = (min(a.n_records, b.n_records) if b is not None else a.n_records) - first
         _check(load().sylph_sketch_push_fasta(self._h, a._h, b._h if b is not None else None, int(first), int(n_items)))
+
+    def push_interleaved(self, f, first_pair=0, n_pairs=None):
+        """sylph_sketch_push_fast[aq]_interleaved: pairs [first_pair, first_pair + n_pairs) of ONE interleaved FastqText / FastaText
+        (pair p = its records 2 p and 2 p + 1) into this paired session."""
+        if n_pairs is None:
+            n_pairs = f.n_records // 2 - first_pair
+        L = load()
+        fn = L.sylph_sketch_push_fasta_interleaved if isinstance(f, FastaText) else L.sylph_sketch_push_fastq_interleaved
+        _check(fn(self._h, f._h, int(first_pair), int(n_pairs)))
 
     def finish(self):
         ok, oc, n, d = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)

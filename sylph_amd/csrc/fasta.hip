@@ -214,6 +214,14 @@ struct FaLen {
     __device__ uint32_t operator()(uint64_t first, uint64_t j) const { return rp::batch_len(ra, rb, first, j); }
 };
 
+// the header of record r for the mate check (read_text.h mates_kernel): the '>' line behind its '>', without its line end
+struct FaHdr {
+    const uint8_t* t;
+    const uint64_t* id_pos;
+    const uint32_t* id_len;
+    __device__ const uint8_t* operator()(uint64_t r, uint64_t& n) const { n = id_len[r]; return t + id_pos[r]; }
+};
+
 // One workgroup per 4 KiB tile of the batch, one lane per 16 output bytes (fasta_reads_plan.h lane_walk).  ja / jb: the joined bases of
 // the two files (16-byte aligned, readable 32 bytes past their last base; jb = nullptr: single-end), ra / rb: their record offsets;
 // off: the batch's offsets, n_rec of them + 1, off[n_rec] = total; bases: 16-byte aligned, room for total rounded up to 16.
@@ -416,6 +424,47 @@ int sylph_sketch_push_fasta(sylph_sketch* sk, sylph_fasta* a, sylph_fasta* b, ui
                                a->joined.as<uint8_t>(), ra, b ? b->joined.as<uint8_t>() : nullptr, rb, first, n_rec_batch, off, n_bases,
                                sk->fq_bases.as<uint8_t>());
         });
+}
+
+// The pairs of ONE interleaved text (interleave_plan.h: pair p = records 2 p and 2 p + 1) to a paired session: the batch is the
+// records as they lie, which is the order a paired batch has — the single-end launch, fed record 2 first_pair + j
+int sylph_sketch_push_fasta_interleaved(sylph_sketch* sk, sylph_fasta* f, uint64_t first_pair, uint64_t n_pairs) {
+    if (!sk || !f) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    const char* entry = "sylph_sketch_push_fasta_interleaved";
+    if (n_pairs >= (1ull << 30)) { set_error("%s: at most 2^31 - 1 records per push (%llu pairs)", entry, (unsigned long long)n_pairs); return SYLPH_ERR_INVALID; }
+    const uint64_t pairs = interleave_plan::pairs_of(f->n_rec);
+    if (first_pair > pairs || n_pairs > pairs - first_pair) {
+        set_error("%s: pairs [%llu, +%llu) are not all there (%llu records)", entry, (unsigned long long)first_pair, (unsigned long long)n_pairs, (unsigned long long)f->n_rec);
+        return SYLPH_ERR_INVALID;
+    }
+    sylph_ctx* ctx = sk->ctx;
+    const uint64_t first = interleave_plan::record_of(first_pair, 0);
+    const uint64_t* ra = f->rec_off.as<uint64_t>();
+    return push_read_text(
+        entry, sk, f, (sylph_fasta*)nullptr, first, 2 * n_pairs, FaLen{ra, nullptr},
+        [&] { return f->joined_ready ? uint64_t(0) : f->n_bases + 64; },
+        [&] {                                                            // the join, once per index (as sylph_sketch_push_fasta's)
+            if (f->joined_ready) return;
+            ctx->counters.reserve(64);
+            f->joined.reserve(f->n_bases + 64);
+            SY_HIP(hipMemsetAsync(ctx->counters.p, 0, 4, ctx->stream));
+            if (f->n_bases) fasta_join(f, f->joined.as<uint8_t>(), ctx->counters.as<uint32_t>());
+            check_join(ctx, ctx->counters.as<uint32_t>());
+            f->joined_ready = true;
+        },
+        [&](const uint32_t* off, uint64_t n_rec_batch, uint64_t n_bases) {
+            if (!n_bases) return;
+            ScopedKernelTimer t(ctx, "fasta_batch");
+            hipLaunchKernelGGL(fa_batch_kernel, dim3((uint32_t)((n_bases + rp::TILE_BYTES - 1) / rp::TILE_BYTES)), dim3(FQ_TPB), 0, ctx->stream,
+                               f->joined.as<uint8_t>(), ra, (const uint8_t*)nullptr, (const uint64_t*)nullptr, first, n_rec_batch, off, n_bases,
+                               sk->fq_bases.as<uint8_t>());
+        },
+        true);
+}
+
+int sylph_fasta_mates(sylph_fasta* f, uint64_t first_pair, uint64_t n_pairs, uint64_t* first_bad) {
+    return index_mates("sylph_fasta_mates", f, first_pair, n_pairs, first_bad,
+                       [&] { return FaHdr{f->text, f->id_pos.as<uint64_t>(), f->id_len.as<uint32_t>()}; });
 }
 
 int sylph_fasta_counts(const sylph_fasta* f, uint64_t* n_records, uint64_t* n_bases, uint64_t* id_bytes) {

@@ -30,10 +30,11 @@ struct sylph_fastq {
     const uint8_t* text = nullptr;        // device pointer to byte 0
     uint64_t n = 0;                       // bytes without the trailing blank space
     sylph::DevBuf seq_start, seq_len;     // u64 / u32 per record
+    sylph::DevBuf hdr_start;              // u64 per record: where its '@' line starts (all three kinds of index: the mate check reads the header)
     sylph::DevBuf rec_start;              // sylph_fastq_index_window only: u64 per record + one, where its '@' line starts (the last: behind the records)
     bool has_starts = false;
     uint64_t n_rec = 0, n_bases = 0;
-    explicit sylph_fastq(sylph_ctx* c) : ctx(c), text_own(c), seq_start(c), seq_len(c), rec_start(c) {}
+    explicit sylph_fastq(sylph_ctx* c) : ctx(c), text_own(c), seq_start(c), seq_len(c), hdr_start(c), rec_start(c) {}
 };
 
 namespace sylph {
@@ -68,7 +69,8 @@ __global__ __launch_bounds__(FQ_TPB) void fq_count_kernel(const uint8_t* __restr
 }
 
 __global__ __launch_bounds__(256) void fq_records_kernel(const uint8_t* __restrict__ t, const uint64_t* __restrict__ line_start, uint64_t n_rec,
-                                                         uint64_t* __restrict__ seq_start, uint32_t* __restrict__ seq_len, FqWords* __restrict__ w) {
+                                                         uint64_t* __restrict__ seq_start, uint32_t* __restrict__ seq_len,
+                                                         uint64_t* __restrict__ hdr_start, FqWords* __restrict__ w) {
     __shared__ unsigned long long s_sum[4];
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long len = 0;
@@ -81,6 +83,7 @@ __global__ __launch_bounds__(256) void fq_records_kernel(const uint8_t* __restri
         const bool ok = t[s0] == '@' && t[s2] == '+' && sl == ql && sl <= 0xFFFFFFFEull;
         if (!ok) atomicMin(&w->bad_rec, (unsigned long long)r);
         seq_start[r] = s1;
+        hdr_start[r] = s0;
         seq_len[r] = ok ? (uint32_t)sl : 0u;
         len = ok ? sl : 0ull;
     }
@@ -113,6 +116,17 @@ __global__ void fq_record_starts_kernel(const uint64_t* __restrict__ line_start,
 struct FqLen {
     const uint32_t *la, *lb;
     __device__ uint32_t operator()(uint64_t first, uint64_t j) const { return lb ? ((j & 1) ? lb[first + (j >> 1)] : la[first + (j >> 1)]) : la[first + j]; }
+};
+
+// the header of record r for the mate check (read_text.h mates_kernel): the '@' line behind its '@', up to the sequence line
+struct FqHdr {
+    const uint8_t* t;
+    const uint64_t *hdr_start, *seq_start;
+    __device__ const uint8_t* operator()(uint64_t r, uint64_t& n) const {
+        const uint64_t s0 = hdr_start[r];
+        n = seq_start[r] - s0 - 1;
+        return t + s0 + 1;
+    }
 };
 
 // What there is to index.  Whole: a whole text (sylph_fastq_index).  WholeWithStarts: the same, and where every record starts
@@ -163,10 +177,11 @@ void fastq_index_impl(sylph_fastq* f, const void* text, uint64_t n_bytes, int me
     b_lines.reserve((n_lines + 1) * 8);
     f->seq_start.reserve(f->n_rec * 8);
     f->seq_len.reserve(f->n_rec * 4 + 4);
+    f->hdr_start.reserve(f->n_rec * 8);
     hipLaunchKernelGGL(fq_lines_kernel, dim3((uint32_t)n_tiles), dim3(FQ_TPB), 0, ctx->stream, t.al, t.bias, d_w, b_base.as<uint32_t>(), n_lines,
                        b_lines.as<uint64_t>());
     hipLaunchKernelGGL(fq_records_kernel, dim3(grid1(f->n_rec, 256, 1u << 30)), dim3(256), 0, ctx->stream, f->text, b_lines.as<uint64_t>(), f->n_rec,
-                       f->seq_start.as<uint64_t>(), f->seq_len.as<uint32_t>(), d_w);
+                       f->seq_start.as<uint64_t>(), f->seq_len.as<uint32_t>(), f->hdr_start.as<uint64_t>(), d_w);
     SY_HIP(hipGetLastError());
     ctx->read_back(&hw, d_w, sizeof(hw));
     if (hw.bad_rec != ~0ull) throw FormatError{"record " + std::to_string(hw.bad_rec) + " is not a four-line record ('@' line, sequence, '+' line, quality of the sequence's length)"};
@@ -267,6 +282,32 @@ int sylph_sketch_push_fastq(sylph_sketch* sk, sylph_fastq* a, sylph_fastq* b, ui
             hipLaunchKernelGGL(fq_gather_kernel, dim3(grid1(n_rec_batch, 4, 1u << 16)), dim3(256), 0, sk->ctx->stream, a->text, a->seq_start.as<uint64_t>(),
                                b ? b->text : nullptr, b ? b->seq_start.as<uint64_t>() : nullptr, first, n_rec_batch, off, sk->fq_bases.as<uint8_t>());
         });
+}
+
+// The pairs of ONE interleaved text (interleave_plan.h: pair p = records 2 p and 2 p + 1) to a paired session: the batch is the
+// records as they lie, which is the order a paired batch has — the single-end gather, fed record 2 first_pair + j
+int sylph_sketch_push_fastq_interleaved(sylph_sketch* sk, sylph_fastq* f, uint64_t first_pair, uint64_t n_pairs) {
+    if (!sk || !f) { set_error("null argument"); return SYLPH_ERR_INVALID; }
+    const char* entry = "sylph_sketch_push_fastq_interleaved";
+    if (n_pairs >= (1ull << 30)) { set_error("%s: at most 2^31 - 1 records per push (%llu pairs)", entry, (unsigned long long)n_pairs); return SYLPH_ERR_INVALID; }
+    const uint64_t pairs = interleave_plan::pairs_of(f->n_rec);
+    if (first_pair > pairs || n_pairs > pairs - first_pair) {
+        set_error("%s: pairs [%llu, +%llu) are not all there (%llu records)", entry, (unsigned long long)first_pair, (unsigned long long)n_pairs, (unsigned long long)f->n_rec);
+        return SYLPH_ERR_INVALID;
+    }
+    const uint64_t first = interleave_plan::record_of(first_pair, 0);
+    return push_read_text(
+        entry, sk, f, (sylph_fastq*)nullptr, first, 2 * n_pairs, FqLen{f->seq_len.as<uint32_t>(), nullptr}, [] { return uint64_t(0); }, [] {},
+        [&](const uint32_t* off, uint64_t n_rec_batch, uint64_t) {
+            hipLaunchKernelGGL(fq_gather_kernel, dim3(grid1(n_rec_batch, 4, 1u << 16)), dim3(256), 0, sk->ctx->stream, f->text, f->seq_start.as<uint64_t>(),
+                               (const uint8_t*)nullptr, (const uint64_t*)nullptr, first, n_rec_batch, off, sk->fq_bases.as<uint8_t>());
+        },
+        true);
+}
+
+int sylph_fastq_mates(sylph_fastq* f, uint64_t first_pair, uint64_t n_pairs, uint64_t* first_bad) {
+    return index_mates("sylph_fastq_mates", f, first_pair, n_pairs, first_bad,
+                       [&] { return FqHdr{f->text, f->hdr_start.as<uint64_t>(), f->seq_start.as<uint64_t>()}; });
 }
 
 }  // extern "C"

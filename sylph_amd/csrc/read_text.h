@@ -9,6 +9,7 @@
 #include "device_common.h"
 #include "sketch_session.h"
 #include "text_lines.h"
+#include "interleave_plan.h"
 
 namespace sylph {
 namespace {
@@ -82,6 +83,84 @@ __global__ void widen_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (uint64_t)gridDim.x * blockDim.x) out[j] = in[j];
 }
 
+// The mate check of an interleaved file (interleave_plan.h): pairs [first_pair, first_pair + n_pairs) of ONE index, pair p = records
+// 2 p and 2 p + 1; *first_bad (preset to n_pairs) = the smallest pair of the range, counted from first_pair, whose records are not
+// mates.  A wavefront takes 64 / GROUP_LANES pairs at a time, a group of lanes each; a group walks its two headers GROUP_LANES bytes
+// per step, lane l reading byte base + l of each — one coalesced read per header and step — and votes the plan's four masks.  The
+// step loop is wavefront-uniform: every lane of the wavefront runs every step and every vote until all its groups are done (a group
+// that is done, or has no pair, reads nothing more: its headers count as 0 bytes long from then on).
+//   hdr(record, &n)   device functor: the record's header behind its '@' / '>', n = its bytes (a line end among them is fine)
+template <class Hdr>
+__global__ __launch_bounds__(256) void mates_kernel(Hdr hdr, uint64_t first_pair, uint64_t n_pairs, unsigned long long* __restrict__ first_bad) {
+    namespace ip = interleave_plan;
+    static_assert(ip::GROUP_LANES == 32, "a group's votes are one half of a 64-lane ballot");
+    constexpr uint32_t WAVE_PAIRS = 64 / ip::GROUP_LANES;
+    const uint32_t lane = threadIdx.x & 63, group = lane / ip::GROUP_LANES, gl = lane % ip::GROUP_LANES;
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+    for (uint64_t p0 = wave * WAVE_PAIRS; p0 < n_pairs; p0 += waves * WAVE_PAIRS) {        // (p0 is the same in all lanes of a wavefront)
+        const uint64_t p = p0 + group;
+        const bool has_pair = p < n_pairs;
+        const uint8_t *ha = nullptr, *hb = nullptr;
+        uint32_t na = 0, nb = 0;
+        if (has_pair) {
+            uint64_t n = 0;
+            ha = hdr(ip::record_of(first_pair + p, 0), n);
+            na = ip::header_bytes(n);
+            hb = hdr(ip::record_of(first_pair + p, 1), n);
+            nb = ip::header_bytes(n);
+        }
+        ip::MateScan s;
+        uint32_t carry = 0;                                              // header a's byte in front of this step's first
+        for (uint32_t base = 0;; base += ip::GROUP_LANES) {
+            const bool live = !s.done();
+            const uint32_t x = base + gl;
+            const uint32_t ca = live ? ip::byte_at(ha, na, x) : (uint32_t)' ', cb = live ? ip::byte_at(hb, nb, x) : (uint32_t)' ';
+            const uint32_t up = (uint32_t)__shfl_up((int)ca, 1, ip::GROUP_LANES);
+            const uint32_t front = gl ? up : carry;
+            const uint32_t shift = group * ip::GROUP_LANES;
+            const uint32_t end_a = (uint32_t)(__ballot(ip::is_id_end((uint8_t)ca)) >> shift);
+            const uint32_t end_b = (uint32_t)(__ballot(ip::is_id_end((uint8_t)cb)) >> shift);
+            const uint32_t differ = (uint32_t)(__ballot(ca != cb) >> shift);
+            const uint32_t slash12 = (uint32_t)(__ballot(ip::lane_slash12((uint8_t)ca, (uint8_t)cb, (uint8_t)front, x)) >> shift);
+            carry = (uint32_t)__shfl((int)ca, ip::GROUP_LANES - 1, ip::GROUP_LANES);
+            if (live) s.step(base, end_a, end_b, differ, slash12);
+            if (!__any(!s.done())) break;
+        }
+        if (has_pair && gl == 0 && !s.verdict()) atomicMin(first_bad, (unsigned long long)p);
+    }
+}
+// the launch and its answer; the caller holds the context's lock.  -> the first pair of the range (from 0) that fails, n_pairs: none
+template <class Hdr>
+uint64_t first_bad_pair(sylph_ctx* ctx, Hdr hdr, uint64_t first_pair, uint64_t n_pairs) {
+    if (!n_pairs) return 0;
+    ctx->counters.reserve(64);
+    unsigned long long v = n_pairs;
+    ctx->h2d(ctx->counters.p, &v, 8);
+    {
+        ScopedKernelTimer t(ctx, "mate_check");
+        hipLaunchKernelGGL(mates_kernel<Hdr>, dim3(grid1(n_pairs, 256 / interleave_plan::GROUP_LANES, 1u << 16)), dim3(256), 0, ctx->stream, hdr,
+                           first_pair, n_pairs, ctx->counters.as<unsigned long long>());
+        SY_HIP(hipGetLastError());
+    }
+    ctx->read_back(&v, ctx->counters.p, 8);
+    return v;
+}
+// the scaffold of sylph_fastq_mates / sylph_fasta_mates: the range is checked against the index's records, then first_bad_pair
+template <class Index, class Hdr>
+int index_mates(const char* entry, Index* f, uint64_t first_pair, uint64_t n_pairs, uint64_t* first_bad, Hdr&& make_hdr) {
+    return guarded([&] {
+        SY_REQUIRE(f && first_bad, "null argument");
+        const uint64_t pairs = interleave_plan::pairs_of(f->n_rec);
+        SY_REQUIRE(first_pair <= pairs && n_pairs <= pairs - first_pair, "%s: pairs [%llu, +%llu) of %llu (records 2 p and 2 p + 1 of %llu)", entry,
+                   (unsigned long long)first_pair, (unsigned long long)n_pairs, (unsigned long long)pairs, (unsigned long long)f->n_rec);
+        *first_bad = n_pairs;
+        if (!n_pairs) return;
+        std::lock_guard<std::mutex> lock(f->ctx->mu);
+        DeviceGuard dg(f->ctx->device);
+        *first_bad = first_bad_pair(f->ctx, make_hdr(), first_pair, n_pairs);
+    });
+}
+
 // Records [first, first + n_items) of index a (pairs: of a and b, interleaved) as one batch of the session: their 32-bit offsets are
 // cut, the total and the room are checked, the session's batch buffers are reserved, the offsets widened, the caller gathers the
 // bases, and the batch goes to sylph_sketch_push_enc (SYLPH_MEM_DEVICE, SYLPH_ENC_ASCII).
@@ -90,15 +169,18 @@ __global__ void widen_kernel(const uint32_t* __restrict__ in, uint64_t n, uint64
 //   to_prepare()  bytes that must be free besides the batch's own, for what prepare() reserves
 //   prepare()     runs behind the room check and before the session's buffers are touched
 //   gather(off, n_rec_batch, n_bases)   launches the kernel that writes the bases to sk->fq_bases; off: the batch's 32-bit offsets
+//   interleaved   the records are those of ONE interleaved file (b == nullptr) and go to a PAIRED session as they lie: first and
+//                 n_items count RECORDS, both even (the *_interleaved entries hand over 2 first_pair and 2 n_pairs)
 template <class Index, class Len, class ToPrepare, class Prepare, class Gather>
 int push_read_text(const char* entry, sylph_sketch* sk, Index* a, Index* b, uint64_t first, uint64_t n_items, Len len, ToPrepare&& to_prepare,
-                   Prepare&& prepare, Gather&& gather) {
+                   Prepare&& prepare, Gather&& gather, bool interleaved = false) {
     uint64_t n_rec_batch = 0, n_bases = 0;
     const std::string no_room = std::string(entry) + ": no room for the batch";
     const int rc = guarded([&] {
         sylph_ctx* ctx = sk->ctx;
         SY_REQUIRE(a->ctx == ctx && (!b || b->ctx == ctx), "%s: the index lives on another context than the session", entry);
-        SY_REQUIRE((b != nullptr) == (sk->paired != 0), "%s: a paired session takes two texts, a single-end session one", entry);
+        if (interleaved) SY_REQUIRE(sk->paired != 0 && !b, "%s: the pairs of an interleaved text go to a paired session", entry);
+        else SY_REQUIRE((b != nullptr) == (sk->paired != 0), "%s: a paired session takes two texts, a single-end session one", entry);
         SY_REQUIRE(first <= a->n_rec && n_items <= a->n_rec - first && (!b || (first <= b->n_rec && n_items <= b->n_rec - first)),
                    "%s: records [%llu, +%llu) are not all there", entry, (unsigned long long)first, (unsigned long long)n_items);
         if (!n_items) return;

@@ -628,8 +628,9 @@ struct SamplePipe {
 // the sessions go through a sylph_pipeline (finish on the device -> probe, tables never leave HBM), and this thread takes the
 // results in input order and does the statistics and the printing: the feed of sample j + 1 .. overlaps with the profile of
 // sample j and the statistics of sample j - 1.
-void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vector<std::vector<std::string>>& read_files, sylph_db* db,
-                         const ReportTo& to) {
+// interleaved[j]: read_files[j] is ONE file that holds the pairs itself (--interleaved)
+void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vector<std::vector<std::string>>& read_files, const std::vector<uint8_t>& interleaved,
+                         sylph_db* db, const ReportTo& to) {
     using ordered_ahead::Turn;
     const size_t n_raw = read_files.size();
     const uint64_t genome_c = to.genome_sketches[0].c, genome_k = to.genome_sketches[0].k;
@@ -637,7 +638,10 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
     ReplicaSet replicas(e, args, db, n_raw);                         // sample threads are dealt to the replicas' devices in turn
     const size_t n_workers = sample_workers(args.threads, (size_t)replicas.n_gpus, n_raw);
     std::vector<SampleFiles> job_files;
-    for (const auto& r : read_files) job_files.push_back({r[0], r.size() > 1 ? std::optional<std::string>(r[1]) : std::nullopt});
+    for (size_t j = 0; j < n_raw; j++) {
+        const auto& r = read_files[j];
+        job_files.push_back({r[0], r.size() > 1 ? std::optional<std::string>(r[1]) : std::nullopt, interleaved[j] != 0, !args.no_mate_check});
+    }
     FeedShared feed(std::move(job_files), n_workers);
     // contain.rs:591: raw pairs are sketched with the default filter (DEFAULT_FPR) — unless the exact set is asked for (not in the reference)
     const double raw_pair_fpr = exact_dedup_accepted(args.exact_dedup) ? 0. : DEFAULT_FPR;
@@ -679,7 +683,8 @@ void profile_raw_samples(Engine& e, const ContainCmdArgs& args, const std::vecto
              },
              [&](size_t j, Turn turn) {
                  if (turn == Turn::Pipeline) pipe.report_last(to, pipe.next(read_files[j][0]), *metas[j], read_files[j][0]);
-                 finished(read_files[j]);
+                 if (interleaved[j]) info("Finished paired sample " + read_files[j][0] + " (interleaved).");
+                 else finished(read_files[j]);
                  metas[j].reset();
              });
 }
@@ -796,7 +801,10 @@ int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
     if (args.first_pair.size() != args.second_pair.size())
         throw Error{1, "Different number of paired sequences (-1, -2) for sketching. Exiting."};
     for (size_t i = 0; i < args.first_pair.size(); i++) read_files.push_back({args.first_pair[i], args.second_pair[i]});
+    std::vector<uint8_t> interleaved(read_files.size(), 0);                  // two-file pairs, then interleaved files, then single-end reads
+    for (const auto& f : args.interleaved) { read_files.push_back({f}); interleaved.push_back(1); }
     for (const auto& r : args.reads) read_files.push_back({r});
+    interleaved.resize(read_files.size(), 0);
     if (genome_sketch_files.empty() && genome_files.empty())
         throw Error{1, "No genome files found; see sylph query/profile -h for help. Exiting"};
     if (read_sketch_files.empty() && read_files.empty())
@@ -808,7 +816,7 @@ int contain(Engine& e, ContainCmdArgs args, bool pseudotax_in, FILE* out) {
 
     print_header(args.pseudotax, out, args.estimate_unknown);
     const ReportTo to{args, genome_sketches, out, e.context()};
-    if (!read_files.empty()) profile_raw_samples(e, args, read_files, db.d, to);
+    if (!read_files.empty()) profile_raw_samples(e, args, read_files, interleaved, db.d, to);
     profile_sketch_files(e, args, read_sketch_files, db.d, to);
     fflush(out);
     join_background();

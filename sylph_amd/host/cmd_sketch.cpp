@@ -422,7 +422,7 @@ int sketch(Engine& e, const SketchArgs& args) {
     std::vector<std::string> read_inputs, genome_inputs, first_pairs, second_pairs;
     const bool nothing = args.files.empty() && !args.list_sequence && args.first_pair.empty() && args.second_pair.empty() &&
                          args.genomes.empty() && args.reads.empty() && !args.list_genomes && !args.list_reads &&
-                         !args.list_first_pair && !args.list_second_pair;
+                         !args.list_first_pair && !args.list_second_pair && args.interleaved.empty() && !args.list_interleaved;
     if (nothing) throw Error{1, "No input sequences found; see sylph sketch -h for help. Exiting."};   // :144-157
     if (args.fpr < 0. || args.fpr >= 1.) throw Error{1, "Invalid FPR for sketching. Must be in [0,1)."};   // :158-161
     std::vector<std::string> all_files;
@@ -443,10 +443,13 @@ int sketch(Engine& e, const SketchArgs& args) {
     if (args.list_first_pair) parse_line_file(*args.list_first_pair, first_pairs);
     if (args.list_second_pair) parse_line_file(*args.list_second_pair, second_pairs);
     if (first_pairs.size() != second_pairs.size()) throw Error{1, "Different number of paired sequences. Exiting."};
+    std::vector<std::string> interleaved = args.interleaved;                 // (not in the reference) pairs in ONE file each
+    if (args.list_interleaved) parse_line_file(*args.list_interleaved, interleaved);
     std::optional<std::vector<std::string>> sample_names;                    // :260-274
     if (args.list_sample_names) { sample_names.emplace(); parse_line_file(*args.list_sample_names, *sample_names); }
     else if (args.sample_names) sample_names = args.sample_names;
-    if (sample_names && sample_names->size() != first_pairs.size() + read_inputs.size())
+    // jobs, and the names that go with them, in this order: two-file pairs, interleaved files, single-end reads
+    if (sample_names && sample_names->size() != first_pairs.size() + interleaved.size() + read_inputs.size())
         throw Error{1, "Sample name length is not equal to the number of reads. Exiting"};   // :288-292
     // a10: pairs are deduplicated as the reference does — --fpr != 0 (default 1e-4, cmdline.rs:77): the set behind a cuckoo filter
     // (sketch.rs:733-769; the session option "dedup_fpr"); --fpr 0: the exact set (:690-731).  --exact-dedup / SYLPH_HIP_EXACT_DEDUP=1
@@ -457,7 +460,7 @@ int sketch(Engine& e, const SketchArgs& args) {
     // its own GPU context (calls on one context are serialised) and its own page-locked batch, takes them in input order.
     // The parsing / inflating of different samples overlaps; the GPU work of one sample is ~2 ms per Gbp.
     create_dir_all(args.sample_output_dir);
-    const size_t n_jobs = first_pairs.size() + read_inputs.size();
+    const size_t n_jobs = first_pairs.size() + interleaved.size() + read_inputs.size();
     // (a command's first sample is gathered into pageable memory while the GPU runtime comes up and the device route's uploader serves the
     //  samples BEHIND it: with one sample nobody ever wants the page-locked feed buffers — ~80 ms of hipHostMalloc beside the sample's own
     //  push, and as much again when the process is torn down)
@@ -478,6 +481,7 @@ int sketch(Engine& e, const SketchArgs& args) {
     // the next sample of every worker is indexed while the current one is gathered and pushed
     std::vector<SampleFiles> job_files;
     for (size_t j = 0; j < first_pairs.size(); j++) job_files.push_back({first_pairs[j], second_pairs[j]});
+    for (const auto& f : interleaved) job_files.push_back({f, std::nullopt, true, !args.no_mate_check});
     for (const auto& r : read_inputs) job_files.push_back({r, std::nullopt});
     FeedShared feed(std::move(job_files), n_workers);
     // a finished sketch is written by the writers' thread while its worker takes the next sample; the first error is rethrown by the command
@@ -512,7 +516,7 @@ int sketch(Engine& e, const SketchArgs& args) {
                      sk.kmers.size(), (unsigned long long)occ);
             info(b);
         };
-        const bool paired = files.second.has_value();                        // pairs :311-367, single files :369-420
+        const bool paired = files.paired();                                  // pairs :311-367 (an interleaved file is one), single files :369-420
         SampleParams p;
         p.c = args.c; p.k = args.k; p.no_dedup = args.no_dedup; p.dedup_fpr = pair_fpr;
         if (sample_names) p.sample_name = (*sample_names)[j];

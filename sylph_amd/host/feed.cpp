@@ -33,8 +33,10 @@ struct ChunkStream::Impl {
     std::deque<RecordChunk> q;
     bool done = false, stop = false;
     RecordChunk cur;
-    size_t rec_i = 0, base_i = 0;
-    bool have_cur = false;
+    size_t rec_i = 0, base_i = 0, head_i = 0;
+    bool have_cur = false, keep_headers = false;
+    const uint8_t* last_head = nullptr;
+    uint32_t last_head_len = 0;
     static constexpr size_t CHUNK_BASES = 8u << 20, QUEUE_DEPTH = 4;
 
     void run() {
@@ -51,6 +53,11 @@ struct ChunkStream::Impl {
         for (;;) {
             bool ok = false, err = false;
             try { ok = reader->next(rec); } catch (const Error&) { err = true; }
+            if (keep_headers && (err || ok)) {
+                const size_t n = err ? 0 : std::min<size_t>(rec.id.size(), 0xFFFFFFFEu);
+                c.heads.insert(c.heads.end(), rec.id.begin(), rec.id.begin() + n);
+                c.head_len.push_back((uint32_t)n);
+            }
             if (err) {
                 c.len.push_back(RecordChunk::ERR);
             } else if (!ok) {
@@ -77,7 +84,8 @@ struct ChunkStream::Impl {
     }
 };
 
-ChunkStream::ChunkStream(const std::string& path) : p_(new Impl) {
+ChunkStream::ChunkStream(const std::string& path, bool keep_headers) : p_(new Impl) {
+    p_->keep_headers = keep_headers;
     p_->reader.reset(new FastxReader(path));   // throws Error exactly where FastxReader does
     p_->th = std::thread([this] { p_->run(); });
 }
@@ -103,6 +111,12 @@ ChunkStream::Kind ChunkStream::next(const uint8_t*& seq, uint32_t& len) {
         s.have_cur = true;
         s.rec_i = 0;
         s.base_i = 0;
+        s.head_i = 0;
+    }
+    if (s.keep_headers) {
+        s.last_head = s.cur.heads.data() + s.head_i;
+        s.last_head_len = s.cur.head_len[s.rec_i];
+        s.head_i += s.last_head_len;
     }
     const uint32_t l = s.cur.len[s.rec_i++];
     if (l == RecordChunk::ERR) return ERR;
@@ -110,6 +124,11 @@ ChunkStream::Kind ChunkStream::next(const uint8_t*& seq, uint32_t& len) {
     len = l;
     s.base_i += l;
     return REC;
+}
+
+void ChunkStream::last_header(const uint8_t*& header, uint32_t& len) const {
+    header = p_->last_head;
+    len = p_->last_head_len;
 }
 
 // ---- page-locked batch ---------------------------------------------------------------------------------------------

@@ -126,7 +126,15 @@ void write_behind(std::function<void()> f);
 void drain_writers();
 
 // ---- sample_feed.cpp: the way of one sample's reads to the device ----
-struct SampleFiles { std::string first; std::optional<std::string> second; };   // second: the mate file of a pair
+// second: the mate file of a pair.  interleaved (--interleaved; no second file): `first` holds the pairs itself, mate 1, mate 2,
+// mate 1, ... — the sample means what `-1 A -2 B` means with A = its even records and B = its odd ones (csrc/interleave_plan.h);
+// mate_check: every pair's two ids are checked before it is pushed (--no-mate-check turns that off)
+struct SampleFiles {
+    std::string first;
+    std::optional<std::string> second;
+    bool interleaved = false, mate_check = true;
+    bool paired() const { return second.has_value() || interleaved; }
+};
 struct SampleParams {
     uint64_t c = 0, k = 0;
     bool no_dedup = false;

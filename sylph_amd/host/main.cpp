@@ -61,6 +61,9 @@ int run_sketch(Argv a) {
         else if (t == "--gpus") { const std::string v = a.one(); s.gpus = v == "all" ? -1 : std::max(1, atoi(v.c_str())); }
         else if (t == "-1" || t == "--first-pairs") append(s.first_pair, a.multi());
         else if (t == "-2" || t == "--second-pairs") append(s.second_pair, a.multi());
+        else if (t == "--interleaved") append(s.interleaved, a.multi());
+        else if (t == "--lI") s.list_interleaved = a.one();
+        else if (t == "--no-mate-check") { s.no_mate_check = true; a.i++; }
         else if (t == "--debug" || t == "--trace") a.i++;
         else if (t[0] == '-' && t.size() > 1) throw Error{2, "unknown option " + t};
         else { s.files.push_back(t); a.i++; }
@@ -89,6 +92,8 @@ int run_contain(Argv a, bool profile) {
         else if (t == "-r" || t == "--reads") append(c.reads, a.multi());
         else if (t == "-1" || t == "--first-pairs") append(c.first_pair, a.multi());
         else if (t == "-2" || t == "--second-pairs") append(c.second_pair, a.multi());
+        else if (t == "--interleaved") append(c.interleaved, a.multi());
+        else if (t == "--no-mate-check") { c.no_mate_check = true; a.i++; }
         else if (t == "-c") c.c = strtoull(a.one().c_str(), nullptr, 10);
         else if (t == "-k") c.k = strtoull(a.one().c_str(), nullptr, 10);
         else if (t == "-i" || t == "--individual-records") { c.individual = true; a.i++; }
@@ -173,7 +178,13 @@ static int run_in_child(int argc, char** argv) {
 int main(int argc, char** argv) {
     (void)run_in_child(argc, argv);          // (the parent never returns from here)
     trace_mark("main()");
-    if (argc < 2) { fprintf(stderr, "usage: sylph-hip <sketch|profile|query|inspect> ...\n"); return 2; }
+    if (argc < 2) {
+        fprintf(stderr, "usage: sylph-hip <sketch|profile|query|inspect> ...\n"
+                        "  reads: -r FILE... (single-end), -1 FILE... -2 FILE... (pairs in two files), --interleaved FILE... (pairs in one file:\n"
+                        "  mate 1, mate 2, mate 1, ...; sketch also takes --lI LIST); --no-mate-check: do not compare the ids of an interleaved\n"
+                        "  file's pairs (by default a pair whose ids are neither equal nor <id>/1 and <id>/2 skips the sample)\n");
+        return 2;
+    }
     int rc = 2;
     try {
         const std::string cmd = argv[1];

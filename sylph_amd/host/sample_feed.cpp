@@ -8,8 +8,11 @@
 #include <cstring>
 
 #include "host_internal.hpp"
+#include "../csrc/interleave_plan.h"
 
 namespace sylph_host {
+
+namespace ip = sylph::interleave_plan;
 
 bool exact_dedup_accepted(bool flag) {
     const char* e = getenv("SYLPH_HIP_EXACT_DEDUP");
@@ -38,6 +41,14 @@ bool device_decode_enabled(Container c) {
 }
 
 namespace {
+// An interleaved sample found out of phase by one of the roads (the warning is out): sketch_sample drops the session and gives no
+// sketch, as behind any invalid file.
+struct SampleSkipped {};
+std::string id_of_header(const uint8_t* h, size_t n) { return std::string((const char*)h, (size_t)ip::id_len(h, n)); }
+void warn_out_of_phase(const std::string& file, uint64_t pair, const std::string& id1, const std::string& id2) {
+    warn("Interleaved file " + file + ": records " + std::to_string(ip::record_of(pair, 0)) + " and " + std::to_string(ip::record_of(pair, 1)) +
+         " are not mates ('" + id1 + "' and '" + id2 + "'): the file is out of phase from there on; skipping the sample (--no-mate-check takes the records as they come).");
+}
 // Uncompressed 4-line FASTQ (the common case): the files are indexed by parse_threads() workers, whole batches are gathered
 // into page-locked memory in parallel and pushed; the record loop of the reference shrinks to its one sequential piece, the
 // running mean of the read lengths (f64, file order: sketch.rs:941-943, :825-826), which runs on its own thread meanwhile.
@@ -76,13 +87,16 @@ bool finish_index(IndexedInput& in) {
     return in.a->ok && (!in.b || in.b->ok);
 }
 // Batches of whole records (pairs) of at most BATCH_BASES bases / BATCH_RECS records
-std::vector<std::pair<size_t, size_t>> cut_batches(size_t n, bool paired, const std::vector<uint64_t>& ca, const std::vector<uint64_t>& cb) {
+// (interleaved: pairs of ONE file, item i = its records 2 i and 2 i + 1)
+std::vector<std::pair<size_t, size_t>> cut_batches(size_t n, bool paired, const std::vector<uint64_t>& ca, const std::vector<uint64_t>& cb, bool interleaved = false) {
     std::vector<std::pair<size_t, size_t>> out;
     size_t i0 = 0;
     while (i0 < n) {
         // largest i1 with at most BATCH_BASES bases and BATCH_RECS records in [i0, i1)
-        size_t lo = i0 + 1, hi = std::min(n, i0 + PinnedBatch::BATCH_RECS / (paired ? 2 : 1));
-        auto bases_upto = [&](size_t i) { return ca[i] - ca[i0] + (paired ? cb[i] - cb[i0] : 0); };
+        size_t lo = i0 + 1, hi = std::min(n, i0 + PinnedBatch::BATCH_RECS / (paired || interleaved ? 2 : 1));
+        auto bases_upto = [&](size_t i) {
+            return interleaved ? ca[ip::record_of(i, 0)] - ca[ip::record_of(i0, 0)] : ca[i] - ca[i0] + (paired ? cb[i] - cb[i0] : 0);
+        };
         while (lo < hi) {
             const size_t mid = lo + (hi - lo + 1) / 2;
             if (bases_upto(mid) <= PinnedBatch::BATCH_BASES) lo = mid; else hi = mid - 1;
@@ -95,25 +109,60 @@ std::vector<std::pair<size_t, size_t>> cut_batches(size_t n, bool paired, const 
 // open_session: creates the sample's session — it waits for the engine's context, so it is called as late as possible: whatever
 // batches can be gathered and packed before the context is up (the first sample of a process: ~0.15 s of idle parse threads otherwise)
 // are gathered into pageable memory first (round 5)
-void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_session, const IndexedInput& in, double& mean_read_length) {
+// the mate check of the indexed host feed: the header of a record is the line in front of its sequence line
+void check_mates_indexed(const std::string& file, const FastqIndex& a, size_t n_pairs, unsigned threads) {
+    auto header = [&](size_t r, size_t& len) {
+        const size_t end = (size_t)a.seq_off[r] - 1;                         // the header line's '\n'
+        const void* nl = end ? memrchr(a.data, '\n', end) : nullptr;
+        const size_t at = nl ? (size_t)((const uint8_t*)nl - a.data) + 1 : 0;   // its '@'
+        len = end - at - 1;
+        return a.data + at + 1;
+    };
+    std::atomic<uint64_t> bad{n_pairs};
+    const size_t CHUNK = 4096;
+    parallel_for((n_pairs + CHUNK - 1) / CHUNK, threads, [&](size_t c) {
+        const size_t p1 = std::min(n_pairs, (c + 1) * CHUNK);
+        for (size_t p = c * CHUNK; p < p1 && p < bad.load(std::memory_order_relaxed); p++) {
+            size_t l1 = 0, l2 = 0;
+            const uint8_t *h1 = header(ip::record_of(p, 0), l1), *h2 = header(ip::record_of(p, 1), l2);
+            if (ip::mates(h1, ip::id_len(h1, l1), h2, ip::id_len(h2, l2))) continue;
+            uint64_t seen = bad.load();
+            while (p < seen && !bad.compare_exchange_weak(seen, p)) {}
+            break;
+        }
+    });
+    const uint64_t p = bad.load();
+    if (p >= n_pairs) return;
+    size_t l1 = 0, l2 = 0;
+    const uint8_t *h1 = header(ip::record_of(p, 0), l1), *h2 = header(ip::record_of(p, 1), l2);
+    warn_out_of_phase(file, p, id_of_header(h1, l1), id_of_header(h2, l2));
+    throw SampleSkipped{};
+}
+void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_session, const IndexedInput& in, double& mean_read_length, const SampleFiles& files) {
     const unsigned T = parse_threads();
     FeedLaps laps;
     const FastqIndex& a = *in.a;
     const FastqIndex* b = in.b.get();
-    const size_t n = b ? std::min(a.n_records(), b->n_records()) : a.n_records();   // lock-step readers: sketch.rs:813-815
+    const bool il = files.interleaved;                                       // pairs from consecutive records of ONE index (interleave_plan.h)
+    const size_t n = il ? (size_t)ip::pairs_of(a.n_records()) : b ? std::min(a.n_records(), b->n_records()) : a.n_records();   // lock-step readers: sketch.rs:813-815
+    const size_t step = il ? 2 : 1;                                          // records of `a` per item
+    if (il && files.mate_check) {
+        check_mates_indexed(files.first, a, n, T);
+        laps.lap("host feed: interleaved mates checked");
+    }
     static const std::vector<uint64_t> no_cum;
     const std::vector<uint64_t>& ca = a.cum;                             // prefix sums of the read lengths, from the index workers
     const std::vector<uint64_t>& cb = b ? b->cum : no_cum;
     // the one sequential piece of the reference's record loop (f64, file order: sketch.rs:941-943, :825-826), on its own thread
     // while the batches travel
     double mean = 0.;
-    std::thread tm([&] { double counter = 0.; for (size_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a.seq_len[i] - mean) / counter; } });
+    std::thread tm([&] { double counter = 0.; for (size_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a.seq_len[step * i] - mean) / counter; } });
     ThreadJoiner jm{tm};
-    const auto batches = cut_batches(n, b != nullptr, ca, cb);
+    const auto batches = cut_batches(n, b != nullptr, ca, cb, il);
     size_t early = 0;
     constexpr size_t MAX_EARLY = 16;                                     // 4 Gbp = 1 GB of packed bases in pageable memory at most
     while (!e.ready() && early < batches.size() && early < MAX_EARLY) {
-        e.batch.gather_packed_early(a, b, ca, b ? &cb : nullptr, batches[early].first, batches[early].second, T);
+        e.batch.gather_packed_early(a, b, ca, b ? &cb : nullptr, step * batches[early].first, step * batches[early].second, T);
         early++;
     }
     if (early) laps.lap("early batches: gather + pack (context still coming up)");
@@ -122,7 +171,7 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
     if (early) {
         e.batch.push_early(sk);
         if (early < batches.size()) {
-            a.release_behind(a.seq_off[batches[early].first]);
+            a.release_behind(a.seq_off[step * batches[early].first]);
             if (b) b->release_behind(b->seq_off[batches[early].first]);
         }
         laps.lap("early batches: pushed");
@@ -131,8 +180,8 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
     // slot is on its way to the device: the push of batch i (PCIe + kernels) hides behind the gather of batch i + 1.
     if (early < batches.size()) {
         e.wait_pinned();
-        e.batch.gather_packed((int)(early & 1), a, b, ca, b ? &cb : nullptr, batches[early].first, batches[early].second, T);
-        laps.lap("batch: gather + pack");
+        e.batch.gather_packed((int)(early & 1), a, b, ca, b ? &cb : nullptr, step * batches[early].first, step * batches[early].second, T);
+        laps.lap(il ? "batch: gather + pack (interleaved)" : "batch: gather + pack");
     }
     for (size_t bi = early; bi < batches.size(); bi++) {
         std::exception_ptr err;
@@ -140,7 +189,7 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
         ThreadJoiner jg{tg};
         if (bi + 1 < batches.size())
             tg = std::thread([&, bi] {
-                try { e.batch.gather_packed((int)((bi + 1) & 1), a, b, ca, b ? &cb : nullptr, batches[bi + 1].first, batches[bi + 1].second, T); }
+                try { e.batch.gather_packed((int)((bi + 1) & 1), a, b, ca, b ? &cb : nullptr, step * batches[bi + 1].first, step * batches[bi + 1].second, T); }
                 catch (...) { err = std::current_exception(); }
             });
         e.batch.push_packed(sk, (int)(bi & 1));
@@ -148,10 +197,10 @@ void sketch_indexed(Engine& e, const std::function<sylph_sketch*()>& open_sessio
         if (err) std::rethrow_exception(err);
         // everything before the next batch's first record has been gathered: an inflated copy gives those pages back
         if (bi + 1 < batches.size()) {
-            a.release_behind(a.seq_off[batches[bi + 1].first]);
+            a.release_behind(a.seq_off[step * batches[bi + 1].first]);
             if (b) b->release_behind(b->seq_off[batches[bi + 1].first]);
         }
-        laps.lap("batch: push || gather next");
+        laps.lap(il ? "batch: push || gather next (interleaved)" : "batch: push || gather next");
     }
     tm.join();
     mean_read_length = mean;
@@ -214,6 +263,16 @@ struct ReadIndex {
     const char* index_name() const { return fasta ? "sylph_fasta_index" : "sylph_fastq_index"; }
     const char* index_window_name() const { return fasta ? "sylph_fasta_index_window" : "sylph_fastq_index_window"; }
     const char* push_name() const { return fasta ? "sylph_sketch_push_fasta" : "sylph_sketch_push_fastq"; }
+    const char* push_interleaved_name() const { return fasta ? "sylph_sketch_push_fasta_interleaved" : "sylph_sketch_push_fastq_interleaved"; }
+    // an interleaved text: pairs [first_pair, +n_pairs) of this one index; the first of them that is not one of mates (n_pairs: none)
+    static int push_interleaved(sylph_sketch* sk, const ReadIndex& f, uint64_t first_pair, uint64_t n_pairs) {
+        return f.fasta ? sylph_sketch_push_fasta_interleaved(sk, f.a, first_pair, n_pairs) : sylph_sketch_push_fastq_interleaved(sk, f.q, first_pair, n_pairs);
+    }
+    uint64_t first_bad_pair(uint64_t first_pair, uint64_t n_pairs) const {
+        uint64_t bad = n_pairs;
+        hip_check(fasta ? sylph_fasta_mates(a, first_pair, n_pairs, &bad) : sylph_fastq_mates(q, first_pair, n_pairs, &bad), "sylph_fastx_mates");
+        return bad;
+    }
     int index(sylph_ctx* ctx, const void* dev, uint64_t bytes) {
         return fasta ? sylph_fasta_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &a) : sylph_fastq_index(ctx, dev, bytes, SYLPH_MEM_DEVICE, &q);
     }
@@ -246,11 +305,46 @@ struct ReadLengths {
         else { q.resize(n); hip_check(sylph_fastq_lengths(x.q, 0, n, q.data()), "sylph_fastq_lengths"); }
     }
     uint64_t at(uint64_t i) const { return fasta ? a[i] : q[i]; }
-    void continue_mean(uint64_t n, double& mean, double& counter) const {
-        if (fasta) for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a[i] - mean) / counter; }
-        else for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)q[i] - mean) / counter; }
+    // stride 2: over the mate-1 records of an interleaved text, the even ones (interleave_plan.h MEAN_STRIDE); n counts the steps
+    void continue_mean(uint64_t n, double& mean, double& counter, uint64_t stride = 1) const {
+        if (fasta) for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)a[stride * i] - mean) / counter; }
+        else for (uint64_t i = 0; i < n; i++) { counter += 1.; mean = mean + ((double)q[stride * i] - mean) / counter; }
     }
 };
+// what a road knows about the one file of an interleaved sample
+struct Interleave { bool on = false, check = true; };
+// The ids of pair `bad` of an index that knows where its records start, read from the text through read(offset, n, dst) — the text
+// lies on the device or in a file —, in the warning that ends the sample.  pair: the pair's number in the file.
+template <class Read>
+[[noreturn]] void skip_out_of_phase(const std::string& file, const ReadIndex& x, uint64_t bad, uint64_t pair, uint64_t text_bytes, Read&& read) {
+    std::string id[2];
+    for (uint32_t m = 0; m < 2; m++) {
+        const uint64_t at = std::min(x.record_offset(ip::record_of(bad, m)), text_bytes);
+        uint8_t buf[1024];
+        const uint64_t n = std::min<uint64_t>(sizeof(buf), text_bytes - at);
+        if (n < 2 || !read(at, n, buf)) continue;
+        const uint8_t* end = (const uint8_t*)memchr(buf + 1, '\n', n - 1);
+        id[m] = id_of_header(buf + 1, end ? (size_t)(end - (buf + 1)) : (size_t)n - 1);
+    }
+    warn_out_of_phase(file, pair, id[0], id[1]);
+    throw SampleSkipped{};
+}
+// pushes of whole pairs of an interleaved text below 2^31 bases and 2^30 pairs (l: the lengths of its records 0 .. 2 n_pairs)
+std::vector<std::pair<uint64_t, uint64_t>> cut_pushes_interleaved(const ReadLengths& l, uint64_t n_pairs, uint64_t bases) {
+    std::vector<std::pair<uint64_t, uint64_t>> pushes;
+    if (bases < (1ull << 31) && n_pairs < (1ull << 29)) {
+        if (n_pairs) pushes.emplace_back(0, n_pairs);
+        return pushes;
+    }
+    uint64_t i0 = 0, sum = 0;
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        const uint64_t len = l.at(ip::record_of(i, 0)) + l.at(ip::record_of(i, 1));
+        if (i > i0 && (sum + len >= (1ull << 31) || i - i0 >= (1ull << 29))) { pushes.emplace_back(i0, i - i0); i0 = i; sum = 0; }
+        sum += len;
+    }
+    if (n_pairs > i0) pushes.emplace_back(i0, n_pairs - i0);
+    return pushes;
+}
 // pushes of whole records (pairs) below 2^31 bases and 2^30 items: one for anything up to ~2 Gbp
 std::vector<std::pair<uint64_t, uint64_t>> cut_pushes(const ReadIndex* m2, const ReadLengths& l1, uint64_t n, uint64_t bases) {
     std::vector<std::pair<uint64_t, uint64_t>> pushes;
@@ -350,8 +444,11 @@ uint64_t whole_max(const StreamDecoder& d) { return std::min<uint64_t>(env_bytes
 // dropped at the end (lock-step readers, sketch.rs:813-815); the running mean of the mate-1 lengths is the same f64 recurrence in
 // file order, continued across windows.  false: declined at some step (the session is the caller's to drop: the host feed takes the
 // sample from its start).
+// An interleaved sample (il.on; one file, a paired session): every window's complete records are n, pairs_of(n) pairs are checked
+// (il.check) and pushed, and the text is kept from record kept_record(n) on, so a kept tail always begins at an even record; the
+// mean continues across the windows over the even records only.  A pair that fails the check ends the sample (SampleSkipped).
 bool sketch_streamed(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const std::vector<const void*>& ptrs,
-                     const std::vector<uint64_t>& lens, const char* name, double& mean_read_length) {
+                     const std::vector<uint64_t>& lens, const char* name, double& mean_read_length, Interleave il = {}) {
     const bool trace = FeedLaps::on();
     FeedLaps laps;
     sylph_ctx* ctx = e.context();
@@ -400,8 +497,27 @@ bool sketch_streamed(Engine& e, const StreamDecoder& dec, const std::function<sy
             if (rc != SYLPH_OK) return declined(rc, fq[i].index_window_name());
             fq[i].counts(n_rec[i], bases[i]);
         }
-        const uint64_t n = F == 2 ? std::min(n_rec[0], n_rec[1]) : n_rec[0];
-        if (n) {
+        const uint64_t n = il.on ? ip::pairs_of(n_rec[0]) : F == 2 ? std::min(n_rec[0], n_rec[1]) : n_rec[0];
+        if (n && il.on) {
+            if (il.check) {
+                const uint64_t bad = fq[0].first_bad_pair(0, n);
+                if (bad < n) {
+                    const void* base = nullptr;
+                    hip_check(sylph_inflated_text(win->h, &base, nullptr), "sylph_inflated_text");
+                    const uint64_t file_at = (uint64_t)((const uint8_t*)dev[0] - (const uint8_t*)base);
+                    skip_out_of_phase(name, fq[0], bad, pairs + bad, bytes[0],
+                                      [&](uint64_t at, uint64_t len, uint8_t* dst) { return sylph_inflated_read(win->h, file_at + at, len, dst) == SYLPH_OK; });
+                }
+            }
+            la.fetch(fq[0], ip::kept_record(n_rec[0]));
+            la.continue_mean(n, mean, counter, ip::MEAN_STRIDE);   // sketch.rs:824-826: the mate-1 records
+            for (const auto& p : cut_pushes_interleaved(la, n, bases[0])) {
+                rc = ReadIndex::push_interleaved(sk, fq[0], p.first, p.second);
+                if (rc == SYLPH_ERR_NOMEM) return declined(rc, fq[0].push_interleaved_name());
+                hip_check(rc, fq[0].push_interleaved_name());
+            }
+            pairs += n;
+        } else if (n) {
             la.fetch(fq[0], n);
             la.continue_mean(n, mean, counter);                // sketch.rs:941-943, :825-826
             for (const auto& p : cut_pushes(F == 2 ? &fq[1] : nullptr, la, n, bases[0] + (F == 2 ? bases[1] : 0))) {
@@ -414,12 +530,12 @@ bool sketch_streamed(Engine& e, const StreamDecoder& dec, const std::function<sy
         bool all_done = true;
         for (uint32_t i = 0; i < F; i++) {
             keep[i] = bytes[i];
-            if (fq[i].made()) keep[i] = std::min(fq[i].record_offset(n), bytes[i]);
+            if (fq[i].made()) keep[i] = std::min(fq[i].record_offset(il.on ? ip::kept_record(n_rec[i]) : n), bytes[i]);
             all_done = all_done && finished[i];
         }
         // a finished mate with nothing waiting ends the lock-step reading: the other mate's surplus is dropped (sketch.rs:813-815)
         bool starved = false;
-        for (uint32_t i = 0; i < F; i++) starved = starved || (finished[i] && n_rec[i] == n);
+        for (uint32_t i = 0; i < F && !il.on; i++) starved = starved || (finished[i] && n_rec[i] == n);
         if (all_done || starved) break;
         const uint64_t waiting0 = n_rec[0] - n, waiting1 = F == 2 ? n_rec[1] - n : 0;
         advance[0] = !finished[0] && (F == 1 || waiting0 <= waiting1 || finished[1]);
@@ -431,8 +547,8 @@ bool sketch_streamed(Engine& e, const StreamDecoder& dec, const std::function<sy
     hip_check(dec.info(st.h, &n_slices, &text_bytes, &peak_scratch, &peak_window), "stream info");
     if (trace) {
         char what[192];
-        snprintf(what, sizeof(what), "stream route: %s %s on the device in %llu slices (%llu %s records, %llu text bytes, peak scratch %llu, peak window %llu)",
-                 dec.container, dec.verb, (unsigned long long)n_slices, (unsigned long long)pairs, kind[0] > 0 ? "FASTA" : "FASTQ", (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
+        snprintf(what, sizeof(what), "stream route: %s %s on the device in %llu slices (%llu %s%s records, %llu text bytes, peak scratch %llu, peak window %llu)",
+                 dec.container, dec.verb, (unsigned long long)n_slices, (unsigned long long)pairs, il.on ? "interleaved pairs of " : "", kind[0] > 0 ? "FASTA" : "FASTQ", (unsigned long long)text_bytes, (unsigned long long)peak_scratch, (unsigned long long)peak_window);
         laps.lap(what);
     }
     mean_read_length = mean;
@@ -453,13 +569,14 @@ struct RouteTexts {
     std::vector<uint8_t> heads;                      // the first byte of every mate's TEXT: '@' FASTQ, '>' FASTA
 };
 bool stream_sample(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const RouteTexts& t, const char* name, FeedLaps& laps,
-                   double& mean_read_length) {
-    if (!sketch_streamed(e, dec, open_session, t.ptrs, t.lens, name, mean_read_length)) return false;
-    laps.lap(&dec == &GZIP_STREAM ? "device route: gzip streamed through the device inflate" : "device route: bzip2 streamed through the device decoder");
+                   double& mean_read_length, Interleave il) {
+    if (!sketch_streamed(e, dec, open_session, t.ptrs, t.lens, name, mean_read_length, il)) return false;
+    if (il.on) laps.lap(&dec == &GZIP_STREAM ? "device route: interleaved gzip streamed through the device inflate" : "device route: interleaved bzip2 streamed through the device decoder");
+    else laps.lap(&dec == &GZIP_STREAM ? "device route: gzip streamed through the device inflate" : "device route: bzip2 streamed through the device decoder");
     return true;
 }
 Decoded decode_on_device(Engine& e, const StreamDecoder& dec, const std::function<sylph_sketch*()>& open_session, const std::vector<std::string>& files, FeedLaps& laps,
-                         RouteTexts& out, double& mean_read_length) {
+                         RouteTexts& out, double& mean_read_length, Interleave il) {
     const bool trace = FeedLaps::on();
     const bool gz = &dec == &GZIP_STREAM;
     const char* name = files[0].c_str();
@@ -513,7 +630,7 @@ Decoded decode_on_device(Engine& e, const StreamDecoder& dec, const std::functio
         }
     }
     if (!streamed) return Decoded::OnDevice;
-    return stream_sample(e, dec, open_session, out, name, laps, mean_read_length) ? Decoded::Streamed : Decoded::Declined;
+    return stream_sample(e, dec, open_session, out, name, laps, mean_read_length, il) ? Decoded::Streamed : Decoded::Declined;
 }
 
 // obtain the texts, decide the kind once, index, push
@@ -522,6 +639,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     if (!device_feed_enabled()) return false;
     const std::string* f2 = sample.second ? &*sample.second : nullptr;
     const bool decoded = !text && (decode == Container::Gzip || decode == Container::Bzip2);
+    const Interleave il{sample.interleaved, sample.mate_check};
     std::vector<std::string> files{sample.first};
     if (f2) files.push_back(*f2);
     RouteTexts t;
@@ -544,7 +662,7 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     // against 0.30 s for its first mate alone (profiles/r05_feed_device_route.txt)
     if (text && !e.text.warm() && text->a->size + (f2 ? text->b->size : 0) < (1500ull << 20)) return false;
     if (decoded) {
-        const Decoded got = decode_on_device(e, decode == Container::Gzip ? GZIP_STREAM : BZIP2_STREAM, open_session, files, laps, t, mean_read_length);
+        const Decoded got = decode_on_device(e, decode == Container::Gzip ? GZIP_STREAM : BZIP2_STREAM, open_session, files, laps, t, mean_read_length, il);
         if (got != Decoded::OnDevice) return got == Decoded::Streamed;
     }
     // a bzip2 sample whose text is there in one piece and then has no room — or is too large — to be indexed or pushed in one piece: the
@@ -572,10 +690,12 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
         t.texts.clear();
         sylph_inflated_destroy(t.owner.h);
         t.owner.h = nullptr;
-        return stream_sample(e, BZIP2_STREAM, open_session, t, files[0].c_str(), laps, mean_read_length);
+        return stream_sample(e, BZIP2_STREAM, open_session, t, files[0].c_str(), laps, mean_read_length, il);
     };
     auto index = [&](const TextUploader::Text& x, ReadIndex& out) {
-        const int rc = out.index(ctx, x.dev, x.bytes);
+        // (an interleaved text: the index that also knows where its records start — a warning names two of them by their ids)
+        uint64_t consumed = 0;
+        const int rc = il.on ? out.index_window(ctx, x.dev, x.bytes, 1, &consumed) : out.index(ctx, x.dev, x.bytes);
         if (rc == SYLPH_ERR_FORMAT || rc == SYLPH_ERR_NOMEM) {
             // no room for the index, or more text than one index holds
             to_stream = stream_after_all && (rc == SYLPH_ERR_NOMEM || strstr(sylph_last_error(), "per index") != nullptr);
@@ -588,21 +708,37 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
     uint64_t na = 0, nb = 0, bases_a = 0, bases_b = 0;
     fa.counts(na, bases_a);
     if (f2) fb.counts(nb, bases_b);
-    const uint64_t n = f2 ? std::min(na, nb) : na;                         // lock-step readers: sketch.rs:813-815
+    // lock-step readers: sketch.rs:813-815; an interleaved text: its pairs, a last record without a mate is dropped the same way
+    const uint64_t n = il.on ? ip::pairs_of(na) : f2 ? std::min(na, nb) : na;
     laps.lap(fasta ? "device route: FASTA records found" : "device route: records found");
+    if (il.on && il.check) {
+        const uint64_t bad = fa.first_bad_pair(0, n);
+        laps.lap("device route: interleaved mates checked");
+        if (bad < n) {
+            const void* base = nullptr;
+            if (decoded) hip_check(sylph_inflated_text(t.owner.h, &base, nullptr), "sylph_inflated_text");
+            struct Fd { int fd = -1; ~Fd() { if (fd >= 0) close(fd); } } file;
+            if (!decoded && !text) file.fd = open(sample.first.c_str(), O_RDONLY);
+            skip_out_of_phase(sample.first, fa, bad, bad, t.texts[0].bytes, [&](uint64_t at, uint64_t len, uint8_t* dst) {
+                if (text) { memcpy(dst, text->a->data + at, len); return true; }
+                if (decoded) return sylph_inflated_read(t.owner.h, (uint64_t)(t.texts[0].dev - (const uint8_t*)base) + at, len, dst) == SYLPH_OK;
+                return file.fd >= 0 && pread(file.fd, dst, len, (off_t)at) == (ssize_t)len;
+            });
+        }
+    }
     ReadLengths la;
-    la.fetch(fa, n);
+    la.fetch(fa, il.on ? ip::kept_record(na) : n);
     // the one sequential piece of the reference's record loop (f64, file order: sketch.rs:941-943, :825-826), on its own thread
     double mean = 0.;
-    std::thread tm([&] { double counter = 0.; la.continue_mean(n, mean, counter); });
+    std::thread tm([&] { double counter = 0.; la.continue_mean(n, mean, counter, il.on ? ip::MEAN_STRIDE : 1); });
     ThreadJoiner jm{tm};
-    const auto pushes = cut_pushes(f2 ? &fb : nullptr, la, n, bases_a + bases_b);
+    const auto pushes = il.on ? cut_pushes_interleaved(la, n, bases_a) : cut_pushes(f2 ? &fb : nullptr, la, n, bases_a + bases_b);
     sylph_sketch* const sk = open_session();
     e.batch.flush(sk);
     // one push: the batch is the session's own buffer, valid until finish — the seeding verdict may wait for it (one host round trip less)
     if (pushes.size() == 1) hip_check(sylph_sketch_set_option(sk, "borrow_until_finish", "1"), "sylph_sketch_set_option");
     for (const auto& p : pushes) {
-        const int rc = ReadIndex::push(sk, fa, f2 ? &fb : nullptr, p.first, p.second);
+        const int rc = il.on ? ReadIndex::push_interleaved(sk, fa, p.first, p.second) : ReadIndex::push(sk, fa, f2 ? &fb : nullptr, p.first, p.second);
         if (rc == SYLPH_ERR_NOMEM) {
             // no room on the device for this route's batch (the whole sample in one piece, up to 2 Gbp): not an error — the host feed, which
             // works through a sample in 256 Mbp batches, takes the sample from its start; the caller opens a fresh session
@@ -610,9 +746,9 @@ bool sketch_fastq_on_device(Engine& e, const std::function<sylph_sketch*()>& ope
             tm.join();
             return stream_after_all ? streamed_instead("no room for the push") : false;
         }
-        hip_check(rc, fa.push_name());
+        hip_check(rc, il.on ? fa.push_interleaved_name() : fa.push_name());
     }
-    laps.lap("device route: pushed");
+    laps.lap(il.on ? "device route: interleaved pairs pushed" : "device route: pushed");
     tm.join();
     mean_read_length = mean;
     return true;
@@ -683,6 +819,48 @@ std::optional<double> read_pair_sequentially(Engine& e, const std::function<sylp
     e.batch.flush(sk);
     return mean_read_length;
 }
+// An interleaved file through the one reader: records 2 i and 2 i + 1 are a pair, their headers reach the mate check, a last record
+// without a mate is dropped.  There is no second reader to go on with, so the two-file rules of sketch.rs:878-883 do not carry over:
+// a malformed record anywhere, or a pair that fails the check, gives no sketch.
+std::optional<double> read_interleaved_sequentially(Engine& e, const std::function<sylph_sketch*()>& open_session, const SampleFiles& files) {
+    const std::string& read_file = files.first;
+    std::unique_ptr<ChunkStream> reader;
+    try { reader.reset(new ChunkStream(read_file, true)); }
+    catch (const Error&) { warn(read_file + " is not a valid fasta/fastq file; skipping."); return std::nullopt; }
+    if (FeedLaps::on()) fprintf(stderr, "[sylph_hip feed] sequential reader: interleaved %s\n", read_file.c_str());
+    sylph_sketch* const sk = open_session();
+    double mean_read_length = 0., counter = 0.;
+    std::vector<uint8_t> m1, h1;
+    const uint8_t *s = nullptr, *h = nullptr;
+    uint32_t len = 0, hl = 0;
+    for (uint64_t pair = 0;; pair++) {
+        ChunkStream::Kind kind = reader->next(s, len);
+        if (kind == ChunkStream::END) break;
+        if (kind == ChunkStream::REC) {
+            m1.assign(s, s + len);                                           // (valid until the next call only)
+            reader->last_header(h, hl);
+            h1.assign(h, h + hl);
+            kind = reader->next(s, len);
+            if (kind == ChunkStream::END) break;                             // a last record without a mate is dropped
+        }
+        if (kind == ChunkStream::ERR) {
+            warn("File " + read_file + " is not a valid fasta/fastq file; an interleaved file with a malformed record gives no sketch; skipping.");
+            e.batch.flush(sk);
+            return std::nullopt;
+        }
+        reader->last_header(h, hl);
+        if (files.mate_check && !ip::mates(h1.data(), ip::id_len(h1.data(), h1.size()), h, ip::id_len(h, hl))) {
+            warn_out_of_phase(read_file, pair, id_of_header(h1.data(), h1.size()), id_of_header(h, hl));
+            e.batch.flush(sk);
+            return std::nullopt;
+        }
+        e.batch.add(sk, m1.data(), (uint32_t)m1.size(), s, len, true);
+        counter += 1.;                                                       // :824-826 (mate-1 length only)
+        mean_read_length = mean_read_length + ((double)m1.size() - mean_read_length) / counter;
+    }
+    e.batch.flush(sk);
+    return mean_read_length;
+}
 }  // namespace
 
 void IndexAhead::start(size_t j) {
@@ -732,8 +910,9 @@ SampleRoute::~SampleRoute() {
     if (pre) background([x = std::make_shared<std::optional<IndexedInput>>(std::move(pre))]() mutable { x.reset(); });
 }
 
-std::optional<SequencesSketch> sketch_sample(Engine& e, const SampleFiles& files, const SampleParams& p, SampleRoute& route, sylph_sketch** keep) {
-    const bool paired = files.second.has_value();
+namespace {
+std::optional<SequencesSketch> sketch_by_route(Engine& e, const SampleFiles& files, const SampleParams& p, SampleRoute& route, sylph_sketch** keep) {
+    const bool paired = files.paired();
     std::optional<Session> so;
     const std::function<sylph_sketch*()> open_session = [&] { so.emplace(e, p.c, p.k, paired, p.no_dedup, p.dedup_fpr); return so->sk; };
     auto sketched = [&](double mean_read_length) {
@@ -758,13 +937,20 @@ std::optional<SequencesSketch> sketch_sample(Engine& e, const SampleFiles& files
     std::optional<IndexedInput> own;
     if (!index) { own = index_inputs(files); index = &own; }
     if (*index) {   // uncompressed 4-line FASTQ: block-parallel feed
-        sketch_indexed(e, open_session, **index, mean);
+        sketch_indexed(e, open_session, **index, mean, files);
         return sketched(mean);
     }
-    const std::optional<double> seq_mean = paired ? read_pair_sequentially(e, open_session, files.first, *files.second)
-                                                  : read_single_sequentially(e, open_session, files.first);
+    const std::optional<double> seq_mean = files.interleaved ? read_interleaved_sequentially(e, open_session, files)
+                                           : paired          ? read_pair_sequentially(e, open_session, files.first, *files.second)
+                                                             : read_single_sequentially(e, open_session, files.first);
     if (!seq_mean) return std::nullopt;
     return sketched(*seq_mean);
+}
+}  // namespace
+
+std::optional<SequencesSketch> sketch_sample(Engine& e, const SampleFiles& files, const SampleParams& p, SampleRoute& route, sylph_sketch** keep) {
+    try { return sketch_by_route(e, files, p, route, keep); }
+    catch (const SampleSkipped&) { return std::nullopt; }   // an interleaved sample out of phase: warned about, its session dropped on the way here
 }
 
 }  // namespace sylph_host

@@ -116,13 +116,19 @@ struct RecordChunk {
     std::vector<uint8_t> bases;                    // sequences of the chunk's records, concatenated
     std::vector<uint32_t> len;
     std::string first_id;
+    std::vector<uint8_t> heads;                    // ChunkStream(keep_headers): the records' header lines, concatenated
+    std::vector<uint32_t> head_len;                // ... one per entry of `len`
 };
 class ChunkStream {
    public:
-    explicit ChunkStream(const std::string& path);   // throws Error like FastxReader; starts the reader thread
+    // throws Error like FastxReader; starts the reader thread.  keep_headers: the records' header lines travel with them (the mate
+    // check of an interleaved file reads them)
+    explicit ChunkStream(const std::string& path, bool keep_headers = false);
     ~ChunkStream();
     enum Kind { REC, ERR, END };
     Kind next(const uint8_t*& seq, uint32_t& len);    // records in file order; seq stays valid until the next call
+    // the header line (without '@' / '>') of the record the last next() returned; keep_headers only, valid until the next call
+    void last_header(const uint8_t*& header, uint32_t& len) const;
    private:
     struct Impl;
     std::unique_ptr<Impl> p_;
@@ -380,6 +386,12 @@ struct SketchArgs {   // cmdline.rs:28-86
     double fpr = DEFAULT_FPR;
     int gpus = 1;               // --gpus N|all (-1): the samples' workers are dealt to N GPUs (not in the reference: its rayon pool spans the machine, sketch.rs:313, :371)
     std::optional<std::string> list_sequence, list_reads, list_genomes, list_first_pair, list_second_pair, list_sample_names;
+    // --interleaved FILE... / --lI LIST (not in the reference): paired samples of ONE file each, mate 1, mate 2, mate 1, ...; such a
+    // sample means what `-1 A -2 B` means with A = the file's even records and B = its odd ones.  --no-mate-check: the two ids of a
+    // pair are not compared (by default the first pair that is not one of mates skips the sample)
+    std::vector<std::string> interleaved;
+    std::optional<std::string> list_interleaved;
+    bool no_mate_check = false;
 };
 struct ContainCmdArgs : ContainArgs {   // cmdline.rs:88-160
     std::vector<std::string> files, reads, first_pair, second_pair;
@@ -389,6 +401,8 @@ struct ContainCmdArgs : ContainArgs {   // cmdline.rs:88-160
     bool log_reassignments = false;   // --log-reassignments (profile only, cmdline.rs:142): the k-mer reassignment log on stderr
     bool exact_dedup = false;   // --exact-dedup: raw pairs are deduplicated with the exact marker set (the reference forces its cuckoo filter, contain.rs:591)
     int gpus = 1;               // --gpus N|all (-1): raw samples are spread over N GPUs, each with a replica of the database (not in the reference: its rayon pool spans the machine by itself)
+    std::vector<std::string> interleaved;   // --interleaved FILE... (not in the reference): raw paired samples of one interleaved file each (SketchArgs)
+    bool no_mate_check = false;             // --no-mate-check
 };
 // a10: paired input is deduplicated as the reference does — behind its cuckoo filter for --fpr != 0
 // (the default; raw pairs in profile / query always: contain.rs:591) — unless the caller asks for the exact set: --exact-dedup,
